@@ -15,6 +15,13 @@ before the timed region.  Prints ONE JSON line on rank 0.
 --scaling weak (default): every rank runs the workload's tasks-per-GPU (32), global meta-batch 32*N -- BASELINE config 4's
 reading (256 tasks sharded 32/GPU over 8 GPUs).  --scaling strong: the global meta-batch stays at the workload's size (32),
 rank r runs its contiguous share of 32/N tasks.
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` / `ms_per_step` and the line's identity, nothing else.
+--full adds every other leg after the timed region, each as before: the CPU oracle baseline and its per-task comparison, the dominant
+kernel's roofline (HIP events around its launches in the timed steps), the measured HBM copy rate, the train + validation and sampled
+legs, the fp32-pipe and fp16-plane forms, the strong-scaling leg, the collective record, the shader clock and the other workloads.
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs) as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -131,6 +138,20 @@ def make_batch(wl, task_ids):
     return np.stack(ds), np.stack(ls)
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each of `arrays` (name -> tensor, number or None) as out_dir/<name>.npy, fp32 kept as fp32, everything else as
+    fp64 (None as NaN).  Called right after the timed region, before any other leg reuses the engine's output buffers.  What a step returns
+    (flat parameters, meta-gradient, per-task figures) is well under 1 MB for every workload, so nothing is sampled."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a is None:
+            a = np.array(np.nan)
+        elif torch.is_tensor(a):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, f'{name}.npy'), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 def cpu_baseline_vision(wl, spec, theta_flat, budget_s=20.0, max_tasks=16):      # max_tasks = n_cmp of run_vision
     """The oracle (CPU restatement of the reference loop, fp32) on a bounded sample of the same workload: the first tasks of
@@ -244,6 +265,7 @@ def run_vision(args, wl, rank, world, local, dist):
         d, l = pool[out['n'] % len(pool)]
         out['n'] += 1
         loss, acc, grad, _ = run_batch(th, d, l, wl['shots'], wl['steps'], wl['lr'], first_order=wl['first_order'])
+        out['last'] = (loss, acc, grad)         # (per-task figures and the meta-gradient, reduced in place by trainer.step)
         return loss, acc, grad
 
     def adam_fn(th, grad, scale):               # maml_vision.py:139-141
@@ -260,32 +282,38 @@ def run_vision(args, wl, rank, world, local, dist):
             dist.barrier()
         torch.cuda.synchronize()
 
-    # post-adaptation loss / accuracy at the INITIAL parameters on the tasks the CPU oracle will also run (task ids 0..15; untimed)
-    n_cmp = 16
-    cdata, clabels = make_batch(wl, list(range(n_cmp)))
-    l0, a0, _, _ = run_batch(theta, torch.from_numpy(cdata).cuda(), torch.from_numpy(clabels).cuda(), wl['shots'], wl['steps'], wl['lr'],
-                             first_order=wl['first_order'], with_grad=False)
-    eng_loss0, eng_acc0 = l0.cpu().numpy().astype(np.float64), a0.cpu().numpy().astype(np.float64)
-    del cdata, clabels
-    lall, aall, _, _ = run_batch(theta, data, labels, wl['shots'], wl['steps'], wl['lr'], first_order=wl['first_order'], with_grad=False)
-    init_loss_mean, init_acc_mean = float(lall.mean()), float(aall.mean())
+    if args.full:
+        # post-adaptation loss / accuracy at the INITIAL parameters on the tasks the CPU oracle will also run (task ids 0..15; untimed)
+        n_cmp = 16
+        cdata, clabels = make_batch(wl, list(range(n_cmp)))
+        l0, a0, _, _ = run_batch(theta, torch.from_numpy(cdata).cuda(), torch.from_numpy(clabels).cuda(), wl['shots'], wl['steps'], wl['lr'],
+                                 first_order=wl['first_order'], with_grad=False)
+        eng_loss0, eng_acc0 = l0.cpu().numpy().astype(np.float64), a0.cpu().numpy().astype(np.float64)
+        del cdata, clabels
+        lall, aall, _, _ = run_batch(theta, data, labels, wl['shots'], wl['steps'], wl['lr'], first_order=wl['first_order'], with_grad=False)
+        init_loss_mean, init_acc_mean = float(lall.mean()), float(aall.mean())
 
     for _ in range(args.warmup):
         step()
 
-    # Dominant kernel: found on one untimed, fully profiled step with everything on one stream (additive per-kernel times); the
-    # timed region then records HIP events around exactly that kernel's launches, on the stream they are launched on.
+    # Dominant kernel (--full): found on one untimed, fully profiled step with everything on one stream (additive per-kernel times);
+    # the timed region then records HIP events around exactly that kernel's launches, on the stream they are launched on.  A plain
+    # run takes the same untimed step without events, so that its timed steps see the same parameters and task batches.
     n_img = T * wl['ways'] * wl['shots'] * (2 if wl.get('anil') else 1)
-    eng.set_overlap(False)
-    eng.profile(True)
-    step()
-    torch.cuda.synchronize()
-    first = eng.profile_collect()
-    eng.profile(False)
-    eng.set_overlap(not args.no_overlap)
-    dom = pick_dominant(spec, first, n_img)
-    if dom:
-        eng.profile(True, *dom)
+    dom, first = None, {}
+    if args.full:
+        eng.set_overlap(False)
+        eng.profile(True)
+        step()
+        torch.cuda.synchronize()
+        first = eng.profile_collect()
+        eng.profile(False)
+        eng.set_overlap(not args.no_overlap)
+        dom = pick_dominant(spec, first, n_img)
+        if dom:
+            eng.profile(True, *dom)
+    else:
+        step()
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -299,9 +327,12 @@ def run_vision(args, wl, rank, world, local, dist):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
     acc_after_timed, loss_after_timed = float(out['acc']), float(out['loss'])
+    if args.dump_outputs and rank == 0:
+        loss_l, acc_l, grad_l = out['last']
+        dump_outputs(args.dump_outputs, {'loss': loss_l, 'acc': acc_l, 'meta_grad': grad_l, 'theta': theta})
 
     secondary = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # Secondary figure: the reference runs one validation fast_adapt per train task without backward
         # (maml_vision.py:117-124).  MAML: ONE fused call over [train tasks | validation tasks] (mi_meta_batch_maml_tv) -- the validation
         # tasks' K support steps and query forward ride in the train tasks' launches, only the backward half is train-only.  ANIL: a second
@@ -362,7 +393,7 @@ def run_vision(args, wl, rank, world, local, dist):
     # RemapLabels / ConsecutiveLabels, utils/data_pre.py:70-112; the reference calls tasks.sample() per task on the host, maml_vision.py:103) --
     # from a dataset resident in HBM: the host draws image indices, one mi_sample_tasks launch gathers the pixels, then the same step.
     sampled = None
-    if not args.no_sampled and not wl.get('anil') and wl['dataset'] == 'min':
+    if args.full and not args.no_sampled and not wl.get('anil') and wl['dataset'] == 'min':
         from exploring_meta_amd.utils.task_sampler import ResidentDataset, TaskSampler
         k2 = 2 * wl['shots']
         imgs = torch.cat([d.reshape(-1, *d.shape[2:]) for d, _ in pool[:2]])          # [batches * T * 2SW, C, H, W]: class c = (batch, task, way)
@@ -409,9 +440,9 @@ def run_vision(args, wl, rank, world, local, dist):
                 adam[k] = v
         del imgs, sampler, trainer_smp
 
-    hbm_copy_gbps = measure_stream_copy(eng)
+    hbm_copy_gbps = measure_stream_copy(eng) if args.full else None
     collective = collective_record(dist, world, theta, eng.param_count + 2 * T,
-                                   'one in-place all-reduce per meta-iteration of [meta-gradient | per-task losses | accuracies]')
+                                   'one in-place all-reduce per meta-iteration of [meta-gradient | per-task losses | accuracies]') if args.full else None
 
     # Everything below keeps stepping (other operand form, clock sampling): parameters and optimiser state are put back afterwards, so
     # no theta-dependent figure of this line depends on how long those legs ran.
@@ -435,7 +466,7 @@ def run_vision(args, wl, rank, world, local, dist):
     fp32_pipe = None
     mask = C.c_uint(0)
     # (pooling nets only: the stride-1 hidden blocks are where the two operand forms differ; a bisecting run's variant mask is left alone)
-    if wl['dataset'] == 'min' and not args.no_fp32_pipe and eng.lib.mi_conv_get_split_bf16(C.byref(mask)) and mask.value == 0x3ffff:
+    if args.full and wl['dataset'] == 'min' and not args.no_fp32_pipe and eng.lib.mi_conv_get_split_bf16(C.byref(mask)) and mask.value == 0x3ffff:
         form_was = eng.lib.mi_conv_set_split_bf16(0)
         n32 = max(3, min(5, args.steps))
         timed(2)
@@ -447,7 +478,7 @@ def run_vision(args, wl, rank, world, local, dist):
     # The two-plane fp16 operand form (mi_conv_set_split_bf16(2)): 22-bit operands, i.e. narrower than the reference's fp32 however small its
     # measured errors -- a separately labelled, non-default line, never `value`.
     fp16_planes = None
-    if wl['dataset'] == 'min' and not args.no_fp32_pipe and eng.lib.mi_conv_get_split_bf16(C.byref(mask)) == 1 and mask.value == 0x3ffff:
+    if args.full and wl['dataset'] == 'min' and not args.no_fp32_pipe and eng.lib.mi_conv_get_split_bf16(C.byref(mask)) == 1 and mask.value == 0x3ffff:
         theta.copy_(snap_theta)
         form_was = eng.lib.mi_conv_set_split_bf16(2)
         n16 = max(3, min(5, args.steps))
@@ -463,7 +494,7 @@ def run_vision(args, wl, rank, world, local, dist):
     # The other reading of north_star's ">= 6x at 8 GPUs" in the same run: with N > 1 ranks under the default weak scaling, a short leg that keeps
     # the GLOBAL meta-batch at the workload's size and gives every rank its contiguous share of it (what --scaling strong times as `value`).
     strong = None
-    if world > 1 and args.scaling == 'weak' and Tw >= world and not args.no_secondary:
+    if args.full and world > 1 and args.scaling == 'weak' and Tw >= world and not args.no_secondary:
         lo_s, hi_s = shard_range(Tw, rank, world)
         Ts = hi_s - lo_s
         theta.copy_(snap_theta)
@@ -493,7 +524,7 @@ def run_vision(args, wl, rank, world, local, dist):
                           'measured after the timed region (value / ms_per_step of this line are the weak-scaling figures)'}
         if secondary is not None:
             secondary['strong_scaling'] = strong
-    clock = clock_record(step, world, ms_per_step=dt / args.steps * 1e3) if rank == 0 and not args.no_clock else None
+    clock = clock_record(step, world, ms_per_step=dt / args.steps * 1e3) if args.full and rank == 0 and not args.no_clock else None
     theta.copy_(snap_theta)
     for k, v in snap_adam.items():
         if torch.is_tensor(v):
@@ -566,11 +597,12 @@ def run_vision(args, wl, rank, world, local, dist):
                 for (op, layer), (ms, cnt) in sorted(full.items(), key=lambda kv: -kv[1][0]):
                     f.write(f'{op},{layer},{cnt},{ms:.4f},{ms / cnt:.4f},{ms / tot:.4f}\n')
 
-    cpu, post = None, {'query_loss_mean_all_tasks_at_init': round(init_loss_mean, 5), 'query_acc_mean_all_tasks_at_init': round(init_acc_mean, 5),
-                       'query_loss_mean_last_step': round(loss_after_timed, 5), 'query_acc_mean_last_step': round(acc_after_timed, 5),
+    cpu, post = None, {'query_loss_mean_last_step': round(loss_after_timed, 5), 'query_acc_mean_last_step': round(acc_after_timed, 5),
                        'task_pool': f'{len(pool)} resident batches of {T} tasks per GPU, rotated every step (each batch is met again only after '
                                     f'{len(pool) - 1} others: the last timed step does not score a batch the parameters were just fitted to)'}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        post = {'query_loss_mean_all_tasks_at_init': round(init_loss_mean, 5), 'query_acc_mean_all_tasks_at_init': round(init_acc_mean, 5), **post}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, ol, oa = cpu_baseline_vision(wl, spec, theta0)
         n = len(ol)
         ol, oa = np.asarray(ol), np.asarray(oa)
@@ -593,7 +625,8 @@ def run_vision(args, wl, rank, world, local, dist):
                    'shots': wl['shots'], 'adapt_steps': wl['steps'], 'inner_lr': wl['lr'],
                    'second_order': not wl['first_order'], 'parallelism': f'task-sharded dp{world}, 1 all-reduce/iter',
                    'task_hardness': HARDNESS[wl['dataset']]},
-        'post_adapt': post, 'secondary': secondary, 'sampled': sampled, 'hbm_stream_copy_GBps': round(hbm_copy_gbps, 1), 'roofline': roofline,
+        'post_adapt': post, 'secondary': secondary, 'sampled': sampled,
+        'hbm_stream_copy_GBps': round(hbm_copy_gbps, 1) if hbm_copy_gbps is not None else None, 'roofline': roofline,
         'cpu_baseline': cpu, 'collective': collective, 'arithmetic': arithmetic_note(eng, T), 'fp32_pipe': fp32_pipe, 'fp16_planes': fp16_planes, 'strong_scaling': strong, 'clock': clock,
     }
 
@@ -793,8 +826,41 @@ def run_trpo(args, wl, rank, world, local, dist):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
 
-    # Dominant device call: the Fisher-vector product (11 per step).  Timed with events on the stream it is launched on.
-    ctx = out['r']['context']
+    r = out['r']
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict({k: r[k] for k in ('grad', 'step', 'old_loss', 'old_kl', 'new_loss', 'kl')},
+                                             line_search_step=-1 if r['accepted'] is None else r['accepted'], theta=policy.flat()))
+    ctx = r['context']
+    B = int(ctx.qry['states'].shape[1])
+    roofline = fvp_roofline(ctx, theta0, B, hi - lo) if args.full else None
+
+    collective = collective_record(dist, world, policy.flat(), theta0.numel() + 2,
+                                   'task-count-weighted means of (loss, KL, gradient) and of every Fisher-vector product: one all-reduce each') if args.full else None
+    cpu = None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cpu = cpu_baseline_trpo(p, policy, theta0, replays, olds, out['r'])
+    if rank != 0:
+        return None
+    value = global_T * args.steps / dt
+    return {
+        'metric': 'tasks/sec', 'value': round(value, 2), 'unit': 'tasks/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
+        'dtype': 'f32', 'data': 'synthetic',
+        'config': {'workload': wl['name'], 'tasks_per_gpu': hi - lo, 'global_meta_batch': global_T, 'rows_per_replay': B,
+                   'parallelism': f'task-sharded dp{world}, 1 + 11 + <=15 small all-reduces per step',
+                   **{k: p[k] for k in ('inner_lr', 'max_kl', 'adapt_steps')}},
+        'post_adapt': {'surrogate_loss_before': float(r['old_loss']), 'surrogate_loss_after': None if r['new_loss'] is None else float(r['new_loss']),
+                       'kl_after': None if r['kl'] is None else float(r['kl']), 'line_search_step': r['accepted'],
+                       **(cpu.pop('_post') if cpu else {})},
+        'secondary': {'metric': 'meta_optimize_trpo iterations/sec', 'value': round(args.steps / dt, 3)},
+        'roofline': roofline, 'cpu_baseline': cpu, 'collective': collective,
+        'clock': clock_record(step, world, ms_per_step=dt / args.steps * 1e3) if args.full and not args.no_clock else None,
+    }
+
+
+def fvp_roofline(ctx, theta0, B, n_tasks):
+    """Dominant device call of cfg5 (--full): the Fisher-vector product (11 per step) on the last timed step's context, after the timed
+    region.  Timed with events on the stream it is launched on."""
     v = torch.randn_like(theta0)
     ctx.evaluate(theta0, want_grad=True)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -806,9 +872,8 @@ def run_trpo(args, wl, rank, world, local, dist):
     e1.record()
     torch.cuda.synchronize()
     fvp_ms = e0.elapsed_time(e1) / nf
-    B = int(ctx.qry['states'].shape[1])
     fwd = 2.0 * B * (2 * 100 + 100 * 100 + 100 * 2)                   # one dense forward over a task's padded batch
-    flops = 16.0 * fwd * (hi - lo)                                       # (I - aH) F (I - aH) v: two 6-pass Hessian products + JVP/VJP through the query forward
+    flops = 16.0 * fwd * n_tasks                                       # (I - aH) F (I - aH) v: two 6-pass Hessian products + JVP/VJP through the query forward
     achieved = flops / (fvp_ms * 1e-3) / 1e12
     traffic = None
     tpath = os.path.join(REPO, 'profiles', 'pmc_traffic.json')
@@ -823,30 +888,7 @@ def run_trpo(args, wl, rank, world, local, dist):
                     '(two 6-pass Hessian-vector sweeps + tangent forward / backward through the query pass); a sweep takes 32-row slabs through the whole '
                     'chain inside one workgroup with both 100x100 weight matrices resident in LDS (csrc/policy_sweep.h); round 2 ran one product as ~34 '
                     'per-layer launches in 0.86 ms')
-
-    collective = collective_record(dist, world, policy.flat(), theta0.numel() + 2,
-                                   'task-count-weighted means of (loss, KL, gradient) and of every Fisher-vector product: one all-reduce each')
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline_trpo(p, policy, theta0, replays, olds, out['r'])
-    if rank != 0:
-        return None
-    value = global_T * args.steps / dt
-    r = out['r']
-    return {
-        'metric': 'tasks/sec', 'value': round(value, 2), 'unit': 'tasks/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
-        'dtype': 'f32', 'data': 'synthetic',
-        'config': {'workload': wl['name'], 'tasks_per_gpu': hi - lo, 'global_meta_batch': global_T, 'rows_per_replay': B,
-                   'parallelism': f'task-sharded dp{world}, 1 + 11 + <=15 small all-reduces per step',
-                   **{k: p[k] for k in ('inner_lr', 'max_kl', 'adapt_steps')}},
-        'post_adapt': {'surrogate_loss_before': float(r['old_loss']), 'surrogate_loss_after': None if r['new_loss'] is None else float(r['new_loss']),
-                       'kl_after': None if r['kl'] is None else float(r['kl']), 'line_search_step': r['accepted'],
-                       **(cpu.pop('_post') if cpu else {})},
-        'secondary': {'metric': 'meta_optimize_trpo iterations/sec', 'value': round(args.steps / dt, 3)},
-        'roofline': roofline, 'cpu_baseline': cpu, 'collective': collective,
-        'clock': clock_record(step, world, ms_per_step=dt / args.steps * 1e3) if not args.no_clock else None,
-    }
+    return roofline
 
 
 def cpu_baseline_trpo(p, policy, theta0, replays, olds, gpu_out):
@@ -888,7 +930,7 @@ def other_workloads(current, steps=5, warmup=2):
         if name == current:
             continue
         cmd = [sys.executable, os.path.abspath(__file__), '--workload', name, '--steps', str(steps), '--warmup', str(warmup), '--pool', '2',
-               '--no-cpu-baseline', '--no-fp32-pipe', '--no-secondary', '--no-clock', '--no-dist', '--no-other', '--no-sampled']
+               '--full', '--no-cpu-baseline', '--no-fp32-pipe', '--no-secondary', '--no-clock', '--no-dist', '--no-other', '--no-sampled']
         env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
         t0 = time.perf_counter()
         try:
@@ -927,7 +969,13 @@ def main():
     ap.add_argument('--no-other', action='store_true', help='skip the short runs of the other BASELINE configurations (N = 1 only; child processes)')
     ap.add_argument('--launch-check', action='store_true', help='ranks only join the process group, all-reduce one number and rank 0 prints '
                     '{"launch_check": true, "world_size": N}: exercises the self-launch path without a GPU (MI_DIST_BACKEND=gloo)')
+    ap.add_argument('--full', action='store_true', help='after the timed region, also run every other leg of the line (CPU baseline, roofline, '
+                    'HBM copy, train + validation, sampled, fp32-pipe / fp16-plane forms, strong scaling, collective, clock, other '
+                    'workloads); the --no-* switches above leave out single legs of a --full run')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write what the last timed step returned as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     wl = dict(WORKLOADS[args.workload])
     if args.tasks:
         wl['tasks'] = args.tasks
@@ -968,7 +1016,7 @@ def main():
             dist, dist_note = None, f'single-rank process group failed: {type(e).__name__}: {e}'
     runner = run_trpo if wl.get('kind') == 'trpo' else run_vision
     line = runner(args, wl, rank, world, local, dist)
-    if rank == 0 and world == 1 and line is not None and not args.no_other and not profiled and not args.tasks:
+    if args.full and rank == 0 and world == 1 and line is not None and not args.no_other and not profiled and not args.tasks:
         line['other_workloads'] = other_workloads(args.workload)
     if rank == 0:
         if dist_note and line is not None:

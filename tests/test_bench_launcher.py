@@ -45,3 +45,10 @@ def test_self_launch_only_from_a_bare_shell(monkeypatch):
     monkeypatch.setenv('WORLD_SIZE', '2')
     monkeypatch.setenv('RANK', '0')
     assert bench.self_launch(['--gpus', '2']) is None                           # already one of torchrun's ranks
+
+
+def test_steps_must_be_positive():
+    """--steps sets the number of timed steps: ms_per_step divides by it, so zero is refused before anything touches a GPU."""
+    r = subprocess.run([sys.executable, BENCH, '--steps', '0'], capture_output=True, text=True, timeout=300, cwd=REPO, env=_bare_env())
+    assert r.returncode != 0 and '--steps' in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith('{')]

@@ -4,7 +4,7 @@ files under profiles/ alone (the --stats summary aggregates every launch of a te
 name and differ only in their grid).
 
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 bench.py --no-dist --no-clock --no-other --no-sampled --no-cpu-baseline --no-overlap ...
-    python3 tools/dominant_kernel_trace.py DIR --kernel 'conv3x3_s1_mfma_kernel<32, 2, 2, 0, true, false>' [--bench bench.json] > profiles/rN/rocprofv3_dominant_kernel_*.txt
+    python3 tools/dominant_kernel_trace.py DIR --kernel 'conv3x3_s1_mfma_kernel<32, 2, 2, 0, true, false>' [--bench bench.json (a bench.py --full line)] > profiles/rN/rocprofv3_dominant_kernel_*.txt
 
 Launches are grouped by grid shape (x = threads, y = tasks, z) and, with --cycle N, by their position in the repeating launch order
 (the two-term tangent convolution runs once per hidden block and Hessian-vector pass: blocks 2, 3, 4, 2, 3, 4, ... so --cycle 3; blocks
@@ -33,7 +33,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('trace', help='kernel_trace.csv or the rocprofv3 output directory')
     ap.add_argument('--kernel', required=True, help='substring of the kernel name (as rocprofv3 prints the template instantiation)')
-    ap.add_argument('--bench', default='', help="bench.py's JSON line of the un-profiled run (roofline record) for the FLOP / byte counts")
+    ap.add_argument('--bench', default='', help="bench.py's JSON line of an un-profiled --full run (roofline record) for the FLOP / byte counts")
     ap.add_argument('--cycle', type=int, default=1, help='launches of this kernel repeat in a cycle of this length (one per block): group by position too')
     ap.add_argument('--list', type=int, default=12, help='individual launches to list for the dominant group')
     a = ap.parse_args()

@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:?run on the GPU box}
 cd $ROOT
 O=$ROOT/${1:-gpurun_out/b1_xsplit}; mkdir -p $O
 run() {  # tag, form
-  env MI_B1_BF16X3=$2 timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-fp32-pipe --no-secondary --no-clock --no-other --no-sampled --no-dist > $O/bench_$1.json 2> $O/bench_$1.err
+  env MI_B1_BF16X3=$2 timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-fp32-pipe --no-secondary --no-clock --no-other --no-sampled --no-dist > $O/bench_$1.json 2> $O/bench_$1.err
   python - $O/bench_$1.json $1 <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ cd $ROOT
 O=$ROOT/${1:-gpurun_out/sparse_ab}; mkdir -p $O
 timeout -k 10 600 python -m pytest tests/test_gpu_tangent_kernels.py -q -m gpu -p no:cacheprovider -k "block1_kernels" -x > $O/tests_block1.log 2>&1; echo "block1 kernel tests rc=$?"; tail -n 3 $O/tests_block1.log
 run() {  # tag, value, workload args
-  env MI_SPARSE_WGRAD_BF16=$2 timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-pipe --no-secondary --no-clock --no-other --no-sampled --no-dist "${@:3}" > $O/bench_$1.json 2> $O/bench_$1.err
+  env MI_SPARSE_WGRAD_BF16=$2 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-pipe --no-secondary --no-clock --no-other --no-sampled --no-dist "${@:3}" > $O/bench_$1.json 2> $O/bench_$1.err
   python - $O/bench_$1.json $1 <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -11,9 +11,9 @@ if [ "$2" != "notests" ]; then
   timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log
 fi
 for W in cfg2 cfg1 cfg3 cfg4; do
-  timeout -k 10 300 python bench.py --workload $W --steps 20 --warmup 3 --breakdown $O/event_breakdown_$W.csv > $O/bench_$W.json 2> $O/bench_$W.err
+  timeout -k 10 300 python bench.py --full --workload $W --steps 20 --warmup 3 --breakdown $O/event_breakdown_$W.csv > $O/bench_$W.json 2> $O/bench_$W.err
 done
-timeout -k 10 300 python bench.py --workload cfg5 --steps 10 --warmup 2 > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+timeout -k 10 300 python bench.py --full --workload cfg5 --steps 10 --warmup 2 > $O/bench_cfg5.json 2> $O/bench_cfg5.err
 python tools/roofline_table.py $O/event_breakdown_cfg2.csv > $O/roofline_table_cfg2.md 2>/dev/null
 timeout -k 10 300 python tools/t_sweep.py --workload cfg2 --tasks 1,2,4,8,16,32 --out $O/t_sweep_cfg2.md > $O/t_sweep_cfg2.log 2>&1
 timeout -k 10 300 python tools/t_sweep.py --workload cfg4 --tasks 8,16,32,64,256 --out $O/t_sweep_cfg4.md > $O/t_sweep_cfg4.log 2>&1
