@@ -1796,6 +1796,19 @@ extern "C" int mi_gram_bn_stats(void* stream, const double* g, int tasks, int ci
   return MI_OK;
 }
 
+static bool cka_shape_ok(int pairs, int n, int p) { return pairs >= 1 && n >= 2 && n <= (1 << 18) && p >= 1 && p <= 128; }
+extern "C" size_t mi_cka_scratch_bytes(int pairs, int n, int p) {
+  return cka_shape_ok(pairs, n, p) ? cka_scratch_bytes(pairs, n, p) : 0;
+}
+extern "C" int mi_cka(void* stream, const float* x, const float* y, int pairs, int n, int p, double sigma, void* scratch,
+                      size_t scratch_bytes, double* out) {
+  if (!x || !y || !scratch || !out || !cka_shape_ok(pairs, n, p))
+    return fail(nullptr, MI_ERR_ARG, "mi_cka: bad arguments (1 <= p <= 128, 2 <= n <= 2^18, pairs >= 1, non-null pointers)");
+  if (scratch_bytes < cka_scratch_bytes(pairs, n, p)) return fail(nullptr, MI_ERR_WORKSPACE, "mi_cka: scratch too small");
+  HIPCHK0(launch_cka(reinterpret_cast<hipStream_t>(stream), x, y, pairs, n, p, sigma, scratch, out));
+  return MI_OK;
+}
+
 extern "C" int mi_stream_copy(void* stream, const void* src, void* dst, size_t bytes) {
   if (!src || !dst || bytes % 16) return fail(nullptr, MI_ERR_ARG, "mi_stream_copy: null pointer or size not a multiple of 16");
   HIPCHK0(launch_stream_copy(reinterpret_cast<hipStream_t>(stream), src, dst, bytes));

@@ -268,3 +268,7 @@ struct BnExportArgs {
 hipError_t launch_bn_export(hipStream_t st, const BnExportArgs& a, int tasks);
 hipError_t launch_adam(hipStream_t st, float* theta, const float* grad, float* m, float* v, size_t n, int step, float lr,
                        float b1, float b2, float eps, float gscale);
+
+// Linear and RBF-kernel CKA of [n, p] representation pairs (cka.hip)
+size_t cka_scratch_bytes(int pairs, int n, int p);
+hipError_t launch_cka(hipStream_t st, const float* x, const float* y, int pairs, int n, int p, double sigma, void* scratch, double* out);

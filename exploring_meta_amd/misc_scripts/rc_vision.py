@@ -3,8 +3,10 @@
 task and collect, per layer, the representation of the adaptation data before and after adaptation.  The similarity measures
 (CCA / CKA, ``utils/cca.py``, ``utils/cka.py``) run on the returned arrays."""
 import numpy as np
+import torch
 
 from ..core_functions import accuracy, prepare_batch
+from ..utils.cka import cka
 
 default_params = {"adapt_steps": 1, "inner_lr": 0.1, "n_tasks": 5, "layers": [0, 1, 2, 3, 4]}
 
@@ -36,3 +38,40 @@ def run_rep_exp(model, loss, tasks, device, ways, shots, rep_params=default_para
         for layer in reps:
             reps[layer].append((get_rep_from_batch(adapt_model, adapt_d, layer), get_rep_from_batch(init_model, adapt_d, layer)))
     return acc, reps
+
+
+def _device_rep(model, batch, layer):
+    """get_rep_from_batch's [c*h*w, b] matrix (a reshape of the contiguous [b, c, h, w] rep, not a transpose), kept on the device."""
+    if layer == -1:
+        return model(batch).detach()
+    rep = model.get_rep_i(batch, layer).detach()
+    b, c, h, w = rep.shape
+    return rep.reshape((c * h * w, b))
+
+
+def run_rep_cka(model, loss, tasks, device, ways, shots, rep_params=default_params, sigma=None):
+    """run_rep_exp's loop with the CKA the reference leaves commented out (rc_vision.py:89-91): per layer, linear and RBF-kernel
+    CKA (utils/cka.py) between the adapted and the initial representation of each task's adaptation data, as ONE batched GPU
+    call per layer over all tasks.  Returns (acc [n_tasks, 2], {'linear': {layer: [n_tasks floats]}, 'kernel': {...}})."""
+    init_model = model.clone()
+    adapt_model = model.clone()
+    acc = np.zeros((rep_params['n_tasks'], 2))
+    layers = [int(layer) for layer in rep_params['layers']]
+    reps = {layer: ([], []) for layer in layers}
+    for t in range(rep_params['n_tasks']):
+        adapt_d, adapt_l, eval_d, eval_l = prepare_batch(tasks.sample(), shots, ways, device)
+        for _ in range(rep_params['adapt_steps']):
+            train_error = loss(adapt_model(adapt_d), adapt_l)
+            train_error = train_error / len(adapt_d)
+            adapt_model.adapt(train_error)
+            acc[t, 0] = accuracy(adapt_model(eval_d), eval_l).item()
+            acc[t, 1] = accuracy(init_model(eval_d), eval_l).item()
+        for layer in layers:
+            reps[layer][0].append(_device_rep(adapt_model, adapt_d, layer))
+            reps[layer][1].append(_device_rep(init_model, adapt_d, layer))
+    results = {'linear': {}, 'kernel': {}}
+    for layer in layers:
+        r = cka(torch.stack(reps[layer][0]), torch.stack(reps[layer][1]), sigma)
+        results['linear'][layer] = r.linear.cpu().tolist()
+        results['kernel'][layer] = r.kernel.cpu().tolist()
+    return acc, results

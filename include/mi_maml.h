@@ -266,6 +266,17 @@ int mi_input_gram(void* stream, const float* x, int tasks, int n, int h, int w, 
 int mi_gram_bn_stats(void* stream, const double* g, int tasks, int ci, int co, const float* w9, size_t pstride, const float* w9d,
                      size_t vstride, int pixels, float* out0, float* out1, const float* mu, const float* rstd);
 
+/* Centred kernel alignment of layer representations (reference utils/cka.py:9-60; the CKA calls the reference leaves commented
+ * out in misc_scripts/rc_vision.py:89-91, on the [c*h*w, b] reshape of rc_vision.py:150-165), computed without any n x n matrix
+ * (cka.hip).  x, y: fp32 [pairs][n][p] row-major, rows = points; 1 <= p <= 128, 2 <= n <= 2^18, pairs >= 1 (MI_ERR_ARG otherwise,
+ * before any HIP call; the scratch size is 0 then).  sigma > 0: fixed bandwidth for every matrix; sigma <= 0: the median heuristic
+ * per matrix (sigma^2 = median of the nonzero squared distances, numpy's rule).  out: fp64 [pairs][4] = {linear_cka, kernel_cka,
+ * sigma_x, sigma_y}, device memory; degenerate inputs give NaN as numpy does.  Scratch is O(pairs (n + p^2)); results are
+ * bitwise reproducible and do not depend on how many pairs share the call. */
+size_t mi_cka_scratch_bytes(int pairs, int n, int p);
+int mi_cka(void* stream, const float* x, const float* y, int pairs, int n, int p, double sigma,
+           void* scratch, size_t scratch_bytes, double* out);
+
 /* Device-to-device streaming copy (bytes % 16 == 0): the kernel bench.py uses to measure the achievable HBM bandwidth in the
  * same run as the engine kernels ("measured HBM roofline"). */
 int mi_stream_copy(void* stream, const void* src, void* dst, size_t bytes);
