@@ -110,6 +110,9 @@ _SIGS = {
     'mi_cka_scratch_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'mi_cka': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t,
                          C.c_void_p]),
+    'mi_cca_scratch_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'mi_cca': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                         C.c_size_t, C.c_void_p, C.c_void_p]),
     'mi_stream_copy': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     'mi_sample_tasks': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_void_p]),

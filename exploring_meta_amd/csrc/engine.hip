@@ -1809,6 +1809,21 @@ extern "C" int mi_cka(void* stream, const float* x, const float* y, int pairs, i
   return MI_OK;
 }
 
+static bool cca_shape_ok(int pairs, int n, int p) { return pairs >= 1 && pairs <= (1 << 20) && n >= 2 && n <= (1 << 18) && p >= 1 && p <= 64; }
+extern "C" size_t mi_cca_scratch_bytes(int pairs, int n, int p) {
+  return cca_shape_ok(pairs, n, p) ? cca_scratch_bytes(pairs, n, p) : 0;
+}
+extern "C" int mi_cca(void* stream, const float* x, const float* y, int pairs, int n, int p, double epsilon, double threshold,
+                      void* scratch, size_t scratch_bytes, double* coefs, double* stats) {
+  if (!x || !y || !scratch || !coefs || !stats || !cca_shape_ok(pairs, n, p))
+    return fail(nullptr, MI_ERR_ARG, "mi_cca: bad arguments (1 <= p <= 64, 2 <= n <= 2^18, 1 <= pairs <= 2^20, non-null pointers)");
+  if (!(epsilon >= 0.0) || !(threshold >= 0.0 && threshold <= 1.0))
+    return fail(nullptr, MI_ERR_ARG, "mi_cca: epsilon must be >= 0 and threshold in [0, 1]");
+  if (scratch_bytes < cca_scratch_bytes(pairs, n, p)) return fail(nullptr, MI_ERR_WORKSPACE, "mi_cca: scratch too small");
+  HIPCHK0(launch_cca(reinterpret_cast<hipStream_t>(stream), x, y, pairs, n, p, epsilon, threshold, scratch, coefs, stats));
+  return MI_OK;
+}
+
 extern "C" int mi_stream_copy(void* stream, const void* src, void* dst, size_t bytes) {
   if (!src || !dst || bytes % 16) return fail(nullptr, MI_ERR_ARG, "mi_stream_copy: null pointer or size not a multiple of 16");
   HIPCHK0(launch_stream_copy(reinterpret_cast<hipStream_t>(stream), src, dst, bytes));

@@ -272,3 +272,8 @@ hipError_t launch_adam(hipStream_t st, float* theta, const float* grad, float* m
 // Linear and RBF-kernel CKA of [n, p] representation pairs (cka.hip)
 size_t cka_scratch_bytes(int pairs, int n, int p);
 hipError_t launch_cka(hipStream_t st, const float* x, const float* y, int pairs, int n, int p, double sigma, void* scratch, double* out);
+
+// Canonical correlations of [n, p] representation pairs (cca.hip)
+size_t cca_scratch_bytes(int pairs, int n, int p);
+hipError_t launch_cca(hipStream_t st, const float* x, const float* y, int pairs, int n, int p, double epsilon, double threshold,
+                      void* scratch, double* coefs, double* stats);

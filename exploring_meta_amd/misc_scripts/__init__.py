@@ -1,2 +1,3 @@
 """Counterparts of the reference's misc_scripts that drive the learner step by step (continual-learning accuracy matrix,
-representation change); the analysis / plotting around them (CCA, CKA, plots, result files) stays with the caller."""
+representation change); plots and result files stay with the caller.  CCA and CKA of the representations run on the GPU
+(``rc_vision.run_rep_cca`` / ``rc_vision.run_rep_cka``)."""

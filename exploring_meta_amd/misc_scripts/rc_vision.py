@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Representation-change experiment (reference misc_scripts/rc_vision.py:34-99,150-165): adapt a clone of the model to each
 task and collect, per layer, the representation of the adaptation data before and after adaptation.  The similarity measures
-(CCA / CKA, ``utils/cca.py``, ``utils/cka.py``) run on the returned arrays."""
+(CCA / CKA, ``utils/cca.py``, ``utils/cka.py``) run on the returned arrays, or on the device in ``run_rep_cca`` / ``run_rep_cka``."""
 import numpy as np
 import torch
 
 from ..core_functions import accuracy, prepare_batch
+from ..utils.cca import cca
 from ..utils.cka import cka
 
 default_params = {"adapt_steps": 1, "inner_lr": 0.1, "n_tasks": 5, "layers": [0, 1, 2, 3, 4]}
@@ -75,3 +76,28 @@ def run_rep_cka(model, loss, tasks, device, ways, shots, rep_params=default_para
         results['linear'][layer] = r.linear.cpu().tolist()
         results['kernel'][layer] = r.kernel.cpu().tolist()
     return acc, results
+
+
+def run_rep_cca(model, loss, tasks, device, ways, shots, rep_params=default_params, epsilon=1e-10):
+    """run_rep_exp's loop with the measure the reference runs (rc_vision.py:84-88): per layer, the mean canonical correlation
+    ``get_cca_similarity(adapted_rep.T, init_rep.T, epsilon=1e-10)[1]`` (utils/cca.py) between the adapted and the initial
+    representation of each task's adaptation data, as ONE batched GPU call per layer over all tasks.  Returns
+    (acc [n_tasks, 2], {layer: [n_tasks floats]}); the dict is what the reference dumps as cca_results.json (:56,88,124)."""
+    init_model = model.clone()
+    adapt_model = model.clone()
+    acc = np.zeros((rep_params['n_tasks'], 2))
+    layers = [int(layer) for layer in rep_params['layers']]
+    reps = {layer: ([], []) for layer in layers}
+    for t in range(rep_params['n_tasks']):
+        adapt_d, adapt_l, eval_d, eval_l = prepare_batch(tasks.sample(), shots, ways, device)
+        for _ in range(rep_params['adapt_steps']):
+            train_error = loss(adapt_model(adapt_d), adapt_l)
+            train_error = train_error / len(adapt_d)
+            adapt_model.adapt(train_error)
+            acc[t, 0] = accuracy(adapt_model(eval_d), eval_l).item()
+            acc[t, 1] = accuracy(init_model(eval_d), eval_l).item()
+        for layer in layers:
+            reps[layer][0].append(_device_rep(adapt_model, adapt_d, layer))
+            reps[layer][1].append(_device_rep(init_model, adapt_d, layer))
+    # the [c*h*w, b] matrix is already the transpose the reference passes: rows = datapoints, columns = the b images
+    return acc, {layer: cca(torch.stack(reps[layer][0]), torch.stack(reps[layer][1]), epsilon).mean.cpu().tolist() for layer in layers}

@@ -277,6 +277,29 @@ size_t mi_cka_scratch_bytes(int pairs, int n, int p);
 int mi_cka(void* stream, const float* x, const float* y, int pairs, int n, int p, double sigma,
            void* scratch, size_t scratch_bytes, double* out);
 
+/* Canonical correlation analysis of layer representations: the SVCCA measure the reference's representation-change study runs and
+ * writes to cca_results.json (reference utils/cca.py:226-362, compute_ccas :104-174, remove_small :69-101, sum_threshold :177-195;
+ * called as get_cca_similarity(adapted_rep.T, init_rep.T, epsilon=1e-10)[1] in misc_scripts/rc_vision.py:84-88 and rc_rl.py:276).
+ * x, y: fp32 [pairs][n][p] row-major, rows = datapoints, columns = neurons, the same p on both sides; 1 <= p <= 64,
+ * 2 <= n <= 2^18, 1 <= pairs <= 2^20, epsilon >= 0, 0 <= threshold <= 1 (MI_ERR_ARG otherwise, before any HIP call; the scratch
+ * size is 0 for an unsupported shape).  Per pair, in fp64 (cca.hip): covariance blocks, each scaled by its largest magnitude;
+ * neuron i of a side is kept iff its scaled variance is >= epsilon; epsilon is added to both diagonals; inverse square roots by
+ * Jacobi eigen-decomposition with the pseudo-inverse rule (|w_i| <= 1e-15 max|w| contributes 0, every other eigenvalue
+ * |w_i|^(-1/2)); the singular values of Sxx^(-1/2) Sxy Syy^(-1/2) by one-sided Jacobi.
+ * coefs: fp64 [pairs][p], the canonical correlations in descending order in the first `count` slots, NaN after them.
+ * stats: fp64 [pairs][8] = {mean, thresholded_mean, sum, count, kept_x, kept_y, cond_x, cond_y}: count = min(kept_x, kept_y);
+ * thresholded_mean = mean of the first idx coefficients, idx the first i in [0, count) with sum(s[:i]) / sum(s) >= threshold (all
+ * of them if there is none); cond_* = max|w| / min|w| of the block as it enters the inverse, inf if the smallest eigenvalue is cut.
+ * Either side keeps no neuron (a constant matrix, for every epsilon): mean = thresholded_mean = sum = count = 0, every
+ * coefficient NaN, cond_* NaN.  A singular block with epsilon = 0 gives the finite value of the pseudo-inverse rule (the reference
+ * does not return there).  On return the scratch begins with the kept masks, uint64 [pairs][2] (X, Y; bit i = neuron i kept),
+ * followed at the next multiple of 256 bytes by int32 [pairs][4] = {sweeps of the X and the Y eigen-problem, sweeps of the
+ * singular-value iteration, 1 if a sweep cap was reached}.  Results are bitwise reproducible and do not depend on how many pairs
+ * share the call; the number of launches does not depend on pairs either. */
+size_t mi_cca_scratch_bytes(int pairs, int n, int p);
+int mi_cca(void* stream, const float* x, const float* y, int pairs, int n, int p, double epsilon, double threshold,
+           void* scratch, size_t scratch_bytes, double* coefs, double* stats);
+
 /* Device-to-device streaming copy (bytes % 16 == 0): the kernel bench.py uses to measure the achievable HBM bandwidth in the
  * same run as the engine kernels ("measured HBM roofline"). */
 int mi_stream_copy(void* stream, const void* src, void* dst, size_t bytes);
