@@ -1839,6 +1839,23 @@ extern "C" int mi_sample_tasks(void* stream, const void* dataset, int dataset_is
   return MI_OK;
 }
 
+extern "C" int mi_draw_tasks(void* stream, const int32_t* class_offsets, const int32_t* class_index, int n_classes, int ways, int k,
+                             const uint8_t* rot_table, int n_rot, int remap_shuffle, uint64_t seed, uint64_t first_slot,
+                             uint64_t num_tasks, int tasks, int64_t* index_out, int64_t* labels_out, uint8_t* rot_out,
+                             uint64_t* task_id_out) {
+  if (!class_offsets || !class_index || !index_out || !labels_out || tasks < 1)
+    return fail(nullptr, MI_ERR_ARG, "mi_draw_tasks: null pointer or tasks < 1");
+  if (ways < 1 || ways > kDrawMaxWays || ways > n_classes)
+    return fail(nullptr, MI_ERR_ARG, "mi_draw_tasks: ways must be 1.." + std::to_string(kDrawMaxWays) + " and at most n_classes");
+  if (k < 1 || k > kDrawMaxK) return fail(nullptr, MI_ERR_ARG, "mi_draw_tasks: k must be 1.." + std::to_string(kDrawMaxK));
+  if (n_rot < 0 || n_rot > 256 || (n_rot > 0) != (rot_table != nullptr) || (n_rot > 0) != (rot_out != nullptr))
+    return fail(nullptr, MI_ERR_ARG, "mi_draw_tasks: rot_table and rot_out go with 1 <= n_rot <= 256, NULL with n_rot == 0");
+  if (num_tasks >> 32) return fail(nullptr, MI_ERR_ARG, "mi_draw_tasks: num_tasks must be below 2^32");
+  HIPCHK0(launch_draw_tasks(reinterpret_cast<hipStream_t>(stream), class_offsets, class_index, n_classes, ways, k, rot_table, n_rot,
+                            remap_shuffle, seed, first_slot, num_tasks, tasks, index_out, labels_out, rot_out, task_id_out));
+  return MI_OK;
+}
+
 extern "C" int mi_conv3x3_bn_stats(void* stream, const float* x, const float* w9, size_t pstride, int tasks, int n, int h,
                                    int wd, int ci, int co, int stride, float* z, float* mu, float* rstd, void* scratch,
                                    size_t scratch_bytes) {

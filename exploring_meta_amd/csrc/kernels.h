@@ -277,3 +277,10 @@ hipError_t launch_cka(hipStream_t st, const float* x, const float* y, int pairs,
 size_t cca_scratch_bytes(int pairs, int n, int p);
 hipError_t launch_cca(hipStream_t st, const float* x, const float* y, int pairs, int n, int p, double epsilon, double threshold,
                       void* scratch, double* coefs, double* stats);
+
+// Counter-based draw of a meta-batch's image indices / task labels / class rotations (sampler.hip); one wave per task
+constexpr int kDrawMaxWays = 32, kDrawMaxK = 64;
+hipError_t launch_draw_tasks(hipStream_t st, const int32_t* class_offsets, const int32_t* class_index, int n_classes, int ways, int k,
+                             const uint8_t* rot_table, int n_rot, int remap_shuffle, uint64_t seed, uint64_t first_slot,
+                             uint64_t num_tasks, int tasks, int64_t* index_out, int64_t* labels_out, uint8_t* rot_out,
+                             uint64_t* task_id_out);

@@ -314,6 +314,24 @@ int mi_stream_copy(void* stream, const void* src, void* dst, size_t bytes);
 int mi_sample_tasks(void* stream, const void* dataset, int dataset_is_u8, size_t num_images, int c, int h, int w,
                     const int64_t* index, const uint8_t* rot, int tasks, int n2, float* data_out);
 
+/* The draw that precedes mi_sample_tasks, on the device: the task transforms of utils/data_pre.py:16-112 (FilterLabels, NWays,
+ * KShots(2*shots), RemapLabels, ConsecutiveLabels, RandomClassRotation, num_tasks) for `tasks` tasks in one launch, with no host
+ * arrays, copies or synchronisation.  A task is a pure function of (seed, task id): Philox4x32-10, key = seed, counter =
+ * (id_lo, id_hi, stream, block), Lemire's bounded integers and an ordered Fisher-Yates selection, all in integer arithmetic
+ * (exploring_meta_amd.utils.task_sampler.TaskSampler.describe_task is the numpy restatement, equal bit for
+ * bit).  Slot first_slot + t becomes task id bounded(num_tasks) on stream 0 of the slot, or the slot itself when num_tasks == 0;
+ * the result does not depend on `tasks` or on which other slots share the launch.
+ *   class_offsets [n_classes + 1] int32   the eligible classes in ascending original label: class c owns
+ *   class_index   [class_offsets[n_classes]] int32   class_index[class_offsets[c] .. class_offsets[c + 1]), ascending image ids
+ *   rot_table     [n_rot] uint8           quarter turns to choose from per class and task; n_rot == 0: no rotations
+ *   index_out, labels_out [tasks, ways * k] int64, rot_out [tasks, ways * k] uint8 (NULL iff n_rot == 0): the layout
+ *                                         mi_sample_tasks and the engine take;  task_id_out [tasks] uint64 or NULL
+ * 1 <= ways <= min(32, n_classes), 1 <= k <= 64, 0 <= n_rot <= 256, num_tasks < 2^32, tasks >= 1 (MI_ERR_ARG otherwise, before any
+ * HIP call).  The tables are trusted: every class must hold at least k images (the caller checks, the kernel does not). */
+int mi_draw_tasks(void* stream, const int32_t* class_offsets, const int32_t* class_index, int n_classes, int ways, int k,
+                  const uint8_t* rot_table, int n_rot, int remap_shuffle, uint64_t seed, uint64_t first_slot, uint64_t num_tasks,
+                  int tasks, int64_t* index_out, int64_t* labels_out, uint8_t* rot_out, uint64_t* task_id_out);
+
 /* conv3x3 pad 1 (ConvBlock.conv, vision_models.py:177-185, bias dropped: batch-stat BN cancels it) + per-channel
  * sum / sum-of-squares partials; then finalize -> mu, rstd (BatchNorm2d train mode, eps 1e-5, biased variance). */
 int mi_conv3x3_bn_stats(void* stream, const float* x, const float* w9, size_t pstride, int tasks, int n, int h, int wd,
