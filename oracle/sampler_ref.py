@@ -40,3 +40,21 @@ def check_task_structure(index, labels, rot, dataset_labels, ways, shots, classe
         assert (rr == rr[:, :1]).all(), 'RandomClassRotation: one angle per class'
     # what prepare_batch (data_pre.py:122-127) then produces: `shots` rows of every class in each half, same label order
     assert (labels[0::2] == labels[1::2]).all()
+
+
+# The task-id draw with a bound above 2^31, where Lemire's rejection loop runs often: a word is rejected with probability
+# (2^32 mod b) / 2^32 = (2^31 - 1) / 2^32 for b = 2^31 + 1 and 1/4 for b = 3 * 2^30 (no bound below 2^16 rejects one draw in 65536).
+# (num_tasks, seed, slots); tests/test_device_sampler_host.py checks that at least 8 of the slots reject at least once.
+REJECTION_DRAWS = ((2 ** 31 + 1, 11, 64), (3 * 2 ** 30, 12, 64))
+
+
+def id_draw_words(seed, slot, num_tasks):
+    """(task id, words consumed) of the id draw of one slot: stream 0 of the slot through the mirror's bounded()."""
+    from exploring_meta_amd.utils import task_sampler as TS
+    used = [0]
+
+    def counted():
+        for w in TS.philox_words(seed, slot, TS.STREAM_TASK_ID):
+            used[0] += 1
+            yield w
+    return TS.bounded(counted(), num_tasks), used[0]

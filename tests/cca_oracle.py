@@ -111,3 +111,35 @@ THRESHOLD = 0.98
 def bar(cond_x, cond_y):
     """max(1e-9, 1024 cond 2^-53), cond from the golden file"""
     return max(1e-9, 1024.0 * max(cond_x, cond_y) * 2.0 ** -53)
+
+
+# ---- cases at the limits of the domain mi_maml.h states (not in the golden file: CASES indexes it, this table does not)
+LIMIT_CASES = [  # (kind, seed, n, p, epsilon, zeroed columns of X, zeroed columns of Y)
+    ('relu', 60, 300, 63, 1e-10, (), ()),                   # odd p at the LDS maximum: the round-robin's padding player
+    ('gauss', 61, 300, 64, 1e-10, (3,), (7, 8, 9)),         # p = 64 with odd kept counts 63 and 61
+    ('gauss', 62, 200, 3, 1e-10, (1,), ()),                 # kept 2 x 3: the whitened block is wider than tall
+    ('relu', 63, 200, 3, 1e-10, (), (1,)),                  # kept 3 x 2
+    ('gauss', 64, 50, 1, 1e-10, (), ()),
+    ('relu', 65, 50, 2, 0.0, (), ()),
+    ('gauss', 66, 5, 25, 1e-6, (), ()),                     # n < p: both covariance blocks have rank 4, epsilon carries the rest
+    ('relu', 67, 1025, 3, 1e-10, (), ()),                   # the first n with two row chunks
+    ('gauss', 68, 70001, 3, 1e-10, (), ()),                 # past the cap of 64 row chunks
+    ('relu', 69, 1 << 18, 2, 1e-10, (), ()),                # the largest n
+]
+
+
+def make_limit_case(kind, seed, n, p, zero_x=(), zero_y=()):
+    x, y = (a.copy() for a in _base(kind, seed, n, p))
+    x[:, list(zero_x)] = 0.0
+    y[:, list(zero_y)] = 0.0
+    return x, y
+
+
+def thresholded(s, threshold):
+    """(idx, mean of s[:idx]) by the reference's sum_threshold + np.mean (utils/cca.py:177-195,347-355): NaN for an empty prefix,
+    which is what np.mean of an empty slice returns there."""
+    idx = threshold_index(s, threshold)
+    return idx, (float(s[:idx].mean()) if idx else float('nan'))
+
+
+PAIR_CASES = [('gauss', 70 + k) if k % 2 == 0 else ('relu', 70 + k) for k in range(7)]       # the seven 3 x 2 pairs of the 70000-pair call

@@ -115,3 +115,50 @@ CASES = [  # (kind, seed, n, p, sigma or 0 = median)
     ('rep', 12, 800, 25, 0.0),
     ('gauss', 13, 200, 5, 2.5), ('relu', 14, 800, 25, 1.5),
 ]
+
+
+# ---- cases at the limits of the domain mi_maml.h states (not in the golden file: CASES indexes it, this table does not)
+LIMIT_SHAPES = [  # (n, p): p at and beside the maximum, the histogram's 64 KiB LDS crossing (512 p + 16384 bytes: p = 96 -> 97), the
+    # smallest n, the 64-row tile edge, the first column split of the symmetric passes (n = 1025: S = 2) and its next tile count
+    (130, 128), (130, 127), (70, 97), (70, 96), (2, 3), (3, 1), (63, 4), (64, 4), (65, 4), (1025, 3), (2049, 2),
+]
+_RELU_SEED = {(3, 1): 59}      # relu rows [0, a, a] / [b, 0, b] with a, b > 0 (most seeds clip a or b to 0: every output NaN)
+LIMIT_CASES = [(kind, _RELU_SEED.get((n, p), 50 + i) if kind == 'relu' else 50 + i, n, p, 0.0)
+               for i, (n, p) in enumerate(LIMIT_SHAPES) for kind in ('gauss', 'relu')]
+LIMIT_CASES += [('gauss', 50, 130, 128, 2.0), ('relu', 50, 130, 128, 2.0)]            # (kind, seed, n, p, sigma or 0 = median)
+
+
+def nonzero_sqdists(X):
+    """The nonzero squared distances of the rows i < j, sorted: sum_k (x_ik - x_jk)^2 in fp64 without the square root that _sqdist
+    takes and squares again (cdist gives 5.000000000000001 for the lattice distance 5), so integer inputs give exact integers.
+    Holds an [n, n, p] array: small inputs only."""
+    X = np.asarray(X, dtype=np.float64)
+    d = ((X[:, None, :] - X[None, :, :]) ** 2).sum(-1)[np.triu_indices(X.shape[0], 1)]
+    return np.sort(d[d != 0])
+
+
+def middle_ranks(X):
+    """(count, value at rank (count - 1) // 2, value at rank count // 2) of the nonzero squared distances: the median is their mean."""
+    v = nonzero_sqdists(X)
+    return v.size, float(v[(v.size - 1) // 2]), float(v[v.size // 2])
+
+
+def lattice_rows(seed, n, dup=None):
+    """fp32 [n, 2] rows on the integer lattice {0..3}^2 (every squared distance an exact small integer, heavily tied); dup = (i, j):
+    row i := row j."""
+    x = np.floor(synthetic.hash_uniform(seed, (n, 2)) * 4.0).astype(np.float32)
+    if dup is not None:
+        x[dup[0]] = x[dup[1]]
+    return x
+
+
+TIE_CASES = [  # (seed of X, seed of Y, n, dup): n = 40, and n = 41 with row 40 a copy of row 7.  The X of the last two has an even
+    # count of nonzero distances whose two middle ranks are 4 and 5 (tests/test_cka_host.py checks it): sigma^2 = 4.5
+    (1, 2, 40, None), (3, 4, 41, (40, 7)), (359, 6, 40, None), (332, 8, 41, (40, 7)),
+]
+
+
+def exact_median_sigma2(X):
+    """numpy's median of the nonzero squared distances from nonzero_sqdists: exact on lattice inputs"""
+    count, lo, hi = middle_ranks(X)
+    return 0.5 * (lo + hi)

@@ -145,3 +145,51 @@ def test_cca_has_no_cpu_fallback():
         get_cca_similarity(x, x)                              # neurons >= datapoints
     with pytest.raises(AssertionError):
         get_cca_similarity(x.T, x.T[:, :9])
+
+
+# ---- the inputs of the limit tests (tests/test_gpu_cca.py), checked without a GPU
+
+def test_limit_cases_cover_the_stated_edges_and_stay_out_of_the_golden_table():
+    shapes = [(n, p, eps, len(zx), len(zy)) for _, _, n, p, eps, zx, zy in O.LIMIT_CASES]
+    assert shapes == [(300, 63, 1e-10, 0, 0), (300, 64, 1e-10, 1, 3), (200, 3, 1e-10, 1, 0), (200, 3, 1e-10, 0, 1), (50, 1, 1e-10, 0, 0),
+                      (50, 2, 0.0, 0, 0), (5, 25, 1e-6, 0, 0), (1025, 3, 1e-10, 0, 0), (70001, 3, 1e-10, 0, 0), (1 << 18, 2, 1e-10, 0, 0)]
+    assert O.LIMIT_CASES[1][5:] == ((3,), (7, 8, 9))
+    assert not {c[:5] for c in O.LIMIT_CASES} & set(O.CASES)
+    assert sum(n >= 4000 for n, *_ in shapes) == 2                       # the two linear-cost oracle calls
+    assert (70001 + 1023) // 1024 > 64 >= (65536 + 1023) // 1024        # the row-chunk cap binds from n = 65537 on
+
+
+@pytest.mark.parametrize('idx', range(8))                                 # (the two large cases run once, beside the GPU)
+def test_limit_cases_keep_what_they_are_meant_to_keep(idx):
+    kind, seed, n, p, eps, zx, zy = O.LIMIT_CASES[idx]
+    x, y = O.make_limit_case(kind, seed, n, p, zx, zy)
+    r = O.cca(x, y, eps, O.THRESHOLD)
+    assert (r['kept_x'], r['kept_y'], r['count']) == (p - len(zx), p - len(zy), p - max(len(zx), len(zy)))
+    assert not r['x_idxs'][list(zx)].any() and not r['y_idxs'][list(zy)].any()
+    assert np.all(np.isfinite(r['coefs'])) and np.isfinite(r['cond_x']) and np.isfinite(r['cond_y'])
+    if n < p:
+        assert 1e6 < max(r['cond_x'], r['cond_y']) < 1e7 and O.bar(r['cond_x'], r['cond_y']) < 1e-6
+    else:
+        assert O.bar(r['cond_x'], r['cond_y']) == 1e-9
+
+
+def test_threshold_ends_of_the_restated_sum_threshold():
+    x, y = O.make_case('relu', 9, 800, 25)
+    s = O.cca(x, y, 1e-10)['coefs']
+    idx0, mean0 = O.thresholded(s, 0.0)
+    idx1, mean1 = O.thresholded(s, 1.0)
+    assert idx0 == 0 and np.isnan(mean0) and idx1 == 25 and mean1 == float(s.mean()) and s.min() > 1e-4
+
+
+def test_the_seven_pairs_of_the_many_pairs_call_differ_and_include_degenerate_ones():
+    kept = []
+    for kind, seed in O.PAIR_CASES:
+        x, y = O.make_case(kind, seed, 3, 2)
+        r = O.cca(x, y, 1e-6)
+        kept.append((r['kept_x'], r['kept_y']))
+    assert len(O.PAIR_CASES) == 7 and (1, 0) in kept and (2, 1) in kept and kept.count((2, 2)) == 5
+
+
+def test_scratch_of_many_pairs(lib):
+    assert lib.mi_cca_scratch_bytes(70000, 3, 2) >= 70000 * (16 + 16 + 2 * 2 * 8 + 3 * 4 * 8)
+    assert lib.mi_cca_scratch_bytes(1 << 20, 3, 2) > 0 == lib.mi_cca_scratch_bytes((1 << 20) + 1, 3, 2)

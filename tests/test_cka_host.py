@@ -90,3 +90,51 @@ def test_cka_has_no_cpu_fallback():
         for fn in (get_linear_CKA, get_kernel_CKA):
             with pytest.raises(RuntimeError):
                 fn(x, x)
+
+
+# ---- the inputs of the limit tests (tests/test_gpu_cka.py): what the GPU side relies on, checked without a GPU
+
+def test_limit_cases_cover_the_stated_edges_and_stay_out_of_the_golden_table():
+    shapes = {(c[2], c[3]) for c in O.LIMIT_CASES}
+    assert shapes == set(O.LIMIT_SHAPES) and {c[0] for c in O.LIMIT_CASES} == {'gauss', 'relu'}
+    assert {(130, 128), (130, 127), (70, 97), (70, 96), (2, 3), (3, 1), (63, 4), (64, 4), (65, 4), (1025, 3), (2049, 2)} == shapes
+    assert 512 * 96 + 16384 == 64 * 1024 < 512 * 97 + 16384              # the histogram kernel's dynamic LDS crosses 64 KiB between them
+    assert [((n + 63) // 64, (n + 63) // 64 // 8) for n in (65, 1025, 2049)] == [(2, 0), (17, 2), (33, 4)]    # tiles, column splits (0 -> 1)
+    assert [c for c in O.LIMIT_CASES if c[4] > 0] == [('gauss', 50, 130, 128, 2.0), ('relu', 50, 130, 128, 2.0)]
+    assert all(c[2] < 4000 for c in O.LIMIT_CASES) and not set(O.LIMIT_CASES) & set(O.CASES)
+
+
+def test_limit_cases_are_nan_only_where_two_rows_coincide():
+    """relu at n = 2 makes both rows of Y equal (no nonzero distance, no variance): NaN there and only there."""
+    for kind, seed, n, p, sigma in O.LIMIT_CASES:
+        if n > 65:
+            continue                                                     # (the large ones are plainly non-degenerate and cost seconds)
+        x, y = O.make_case(kind, seed, n, p)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            r = O.cka(x, y, sigma if sigma > 0 else None)
+        nans = [k for k in ('linear', 'kernel', 'sigma_x', 'sigma_y') if np.isnan(r[k])]
+        assert nans == (['linear', 'kernel', 'sigma_y'] if (kind, n) == ('relu', 2) else []), (kind, seed, n, p, r)
+
+
+def test_lattice_inputs_have_tied_medians_and_one_splits_its_middle_ranks():
+    split = 0
+    for sx, sy, n, dup in O.TIE_CASES:
+        for seed in (sx, sy):
+            x = O.lattice_rows(seed, n, dup)
+            assert x.shape == (n, 2) and x.dtype == np.float32 and set(x.ravel().tolist()) <= {0.0, 1.0, 2.0, 3.0}
+            if dup is not None:
+                assert np.array_equal(x[dup[0]], x[dup[1]])
+            v = O.nonzero_sqdists(x)
+            assert np.array_equal(v, np.round(v)) and len(set(v.tolist())) <= 9 and v.size < n * (n - 1) // 2       # ties and duplicates
+            count, lo, hi = O.middle_ranks(x)
+            assert np.count_nonzero(v == lo) > 20 and np.count_nonzero(v == hi) > 20
+            exact = O.exact_median_sigma2(x)
+            assert abs(O.median_sigma2(x) - exact) <= 4 * np.finfo(np.float64).eps * exact       # the blocked oracle squares a square root
+            if lo != hi:
+                assert count % 2 == 0 and (lo, hi, exact) == (4.0, 5.0, 4.5)
+                split += 1
+    assert split >= 1
+
+
+def test_scratch_of_a_split_call_is_that_of_its_largest_chunk(lib):
+    assert lib.mi_cka_scratch_bytes(8195, 4, 2) == lib.mi_cka_scratch_bytes(8192, 4, 2) > lib.mi_cka_scratch_bytes(5, 4, 2) > 0

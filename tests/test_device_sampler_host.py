@@ -209,3 +209,40 @@ def test_abi_rejects_unsupported_shapes_before_any_launch():
         assert b'mi_draw_tasks' in lib.mi_last_error(None)
     with pytest.raises(_lib.MiError):
         _lib.check(call(40, 33, 2))
+
+
+# ---- the inputs of the limit tests (tests/test_gpu_device_sampler.py), checked on the mirror
+
+@pytest.mark.parametrize('num_tasks,seed,slots', S.REJECTION_DRAWS)
+def test_large_bounds_reject_often_enough_to_test_the_loop(num_tasks, seed, slots):
+    """At least 8 of the 64 slots consume more than one word for the id draw (expected: 32 and 16), the recount agrees with
+    task_ids, and the first word of a rejecting slot is indeed below the threshold 2^32 mod b."""
+    assert num_tasks in (2 ** 31 + 1, 3 * 2 ** 30) and slots == 64
+    labels, ds = _dataset(10, 6)
+    sm = TaskSampler(ds, 5, 1, num_tasks=num_tasks, seed=seed)
+    draws = [S.id_draw_words(seed, slot, num_tasks) for slot in range(slots)]
+    assert sm.task_ids(0, slots).tolist() == [d[0] for d in draws] and all(0 <= d[0] < num_tasks for d in draws)
+    rejecting = [slot for slot, d in enumerate(draws) if d[1] > 1]
+    print(f'num_tasks {num_tasks}: {len(rejecting)} of {slots} slots reject, at most {max(d[1] for d in draws)} words')
+    assert len(rejecting) >= 8
+    t = (2 ** 32 - num_tasks) % num_tasks
+    for slot in range(slots):
+        first = next(TS.philox_words(seed, slot, TS.STREAM_TASK_ID))
+        assert ((first * num_tasks) & 0xffffffff < t) == (slot in rejecting)
+
+
+def test_python_surface_admits_256_rotations_and_full_tables():
+    labels, ds = _dataset(30, 12)
+    rotations = [90.0 * (i & 3) for i in range(256)]
+    sm = TaskSampler(ds, 20, 1, rotations=rotations, seed=13)
+    assert sm.rotations.dtype == np.uint8 and sm.rotations.tolist() == [i & 3 for i in range(256)]
+    index, lab, rot = sm.describe_task(5)
+    words = TS.philox_words(13, 5, TS.STREAM_ROTATIONS)
+    assert rot[::2].tolist() == [TS.bounded(words, 256) & 3 for _ in range(20)]
+    # ways = 32, k = 64 on 34 classes of 64..70 images
+    sizes = [64 + (3 * c) % 7 for c in range(34)]
+    lab34 = np.repeat(np.arange(34) * 3 + 7, sizes)
+    ds34 = ResidentDataset(torch.zeros(len(lab34), 1, 2, 2), lab34, device='cpu')
+    big = TaskSampler(ds34, 32, 32, rotations=[0.0, 90.0, 180.0, 270.0], seed=6)
+    index, lab, rot = big.describe_task(1)
+    S.check_task_structure(index, lab, rot, lab34, 32, 32, big.classes.tolist())

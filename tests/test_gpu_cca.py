@@ -192,3 +192,93 @@ def test_run_rep_cca_matches_per_pair_calls():
             assert d['idx1'] == d['idx2'] == O.threshold_index(s, 0.98)
             assert abs(d['mean'][0] - s[:d['idx1']].mean()) <= 1e-12 and d['mean'][0] == d['mean'][1]
     report('run_rep_cca', worst_vs_per_pair=worst)
+
+
+# ------------------------------------------------------------------------------------------ the limits of the stated domain
+# mi_maml.h: 1 <= p <= 64, 2 <= n <= 2^18, 1 <= pairs <= 2^20, epsilon >= 0, 0 <= threshold <= 1.  Inputs: cca_oracle.LIMIT_CASES /
+# PAIR_CASES (their host side is tests/test_cca_host.py).
+
+def _check_all(r, det, k, o, p):
+    """Pair k of a detailed result against the oracle's dict: coefficients, the eight statistics, the kept masks, no sweep cap.
+    The bar on the coefficients and the three means / sums is cca_oracle.bar with the ORACLE's condition numbers.  The condition
+    numbers themselves: the smallest eigenvalue carries an absolute error of a few roundings of the largest, i.e. a relative error of
+    that many roundings times cond -- the same quantity, so the same bar, taken relatively; inf and NaN must match as such."""
+    bar = O.bar(o['cond_x'], o['cond_y']) if o['count'] else 1e-9
+    stats = [float(v[k]) for v in (r.mean, r.thresholded_mean, r.sum, r.count, r.kept_x, r.kept_y, r.cond_x, r.cond_y)]
+    assert stats[3:6] == [float(o['count']), float(o['kept_x']), float(o['kept_y'])], (stats, o)
+    assert np.array_equal(_mask(det.x_mask[k], p), o['x_idxs']) and np.array_equal(_mask(det.y_mask[k], p), o['y_idxs'])
+    assert int(det.sweeps[k, 3]) == 0, det.sweeps[k].tolist()
+    got = r.coefs[k].cpu().numpy()
+    count = o['count']
+    assert np.all(np.isnan(got[count:])) and np.all(np.isfinite(got[:count]))
+    err = 0.0
+    if count:
+        err = float(np.abs(got[:count] - o['coefs']).max())
+    for g, w in zip(stats[:3], (o['mean'], o['thresholded_mean'], o['sum'])):
+        assert np.isnan(g) == np.isnan(w), (stats, o)
+        if not np.isnan(w):
+            err = max(err, abs(g - w))
+    assert err <= bar, (err, bar, stats)
+    cerr = 0.0
+    for g, w in zip(stats[6:], (o['cond_x'], o['cond_y'])):
+        assert np.isnan(g) == np.isnan(w) and np.isinf(g) == np.isinf(w), (stats, o)
+        if np.isfinite(w):
+            cerr = max(cerr, abs(g - w) / w)
+    assert cerr <= bar, (cerr, bar, stats)
+    return err, cerr, bar
+
+
+@pytest.mark.parametrize('idx', range(len(O.LIMIT_CASES)), ids=['{}-n{}-p{}-eps{}'.format(c[0], c[2], c[3], c[4]) for c in O.LIMIT_CASES])
+def test_cca_at_the_limits_of_the_domain(idx):
+    """Odd p at the LDS maximum (63; 64 with 63 x 61 kept), rectangular whitened blocks at p = 3 in both directions, p = 1, epsilon = 0,
+    n < p, two row chunks, the chunk cap (n = 70001) and n = 2^18."""
+    kind, seed, n, p, eps, zx, zy = O.LIMIT_CASES[idx]
+    x, y = O.make_limit_case(kind, seed, n, p, zx, zy)
+    r, det = _cca(x, y, eps, detail=True)
+    o = O.cca(x, y, eps, O.THRESHOLD)
+    assert (o['kept_x'], o['kept_y']) == (p - len(zx), p - len(zy))
+    err, cerr, bar = _check_all(r, det, 0, o, p)
+    report(f'cca_limit[{kind},n{n},p{p},eps{eps}]', err=err, cond_rel_err=cerr, bar=bar, sweeps=det.sweeps[0].tolist())
+
+
+@pytest.mark.parametrize('threshold', [0.0, 1.0])
+def test_cca_threshold_at_its_ends(threshold):
+    """threshold = 0: the reference's sum_threshold returns index 0 (0 / sum >= 0) and np.mean of the empty prefix is NaN;
+    threshold = 1: no proper prefix reaches the whole sum, every coefficient counts."""
+    from exploring_meta_amd.utils.cca import cca, get_cca_similarity
+    x, y = O.make_case('relu', 9, 800, 25)
+    o = O.cca(x, y, 1e-10, threshold)
+    idx, tmean = O.thresholded(o['coefs'], threshold)
+    assert (idx, np.isnan(tmean)) == ((0, True) if threshold == 0.0 else (25, False)) and o['idx'] == idx
+    r, det = cca(torch.as_tensor(x).cuda(), torch.as_tensor(y).cuda(), 1e-10, threshold, detail=True)
+    err, cerr, bar = _check_all(r, det, 0, o, 25)
+    got = float(r.thresholded_mean[0])
+    assert np.isnan(got) if np.isnan(tmean) else abs(got - tmean) <= bar
+    d, mean = get_cca_similarity(x.T, y.T, epsilon=1e-10, threshold=threshold)
+    assert d['idx1'] == d['idx2'] == idx
+    assert np.isnan(d['mean'][0]) if np.isnan(tmean) else abs(d['mean'][0] - tmean) <= bar
+    assert abs(mean - o['mean']) <= bar
+    report(f'cca_threshold[{threshold}]', err=err, idx=idx, thresholded_mean=got)
+
+
+def test_cca_more_pairs_than_a_16_bit_grid_dimension():
+    """pairs = 70000 > 65535: seven distinct 3 x 2 pairs (one keeps no neuron, one keeps 2 x 1) repeated cyclically; every row of the big
+    call -- coefficients, statistics, kept masks, sweep counts -- must be the row of the 7-pair call bit for bit."""
+    pairs, n, p, eps = 70000, 3, 2, 1e-6
+    mats = [O.make_case(kind, seed, n, p) for kind, seed in O.PAIR_CASES]
+    x7 = torch.from_numpy(np.stack([m[0] for m in mats])).cuda()
+    y7 = torch.from_numpy(np.stack([m[1] for m in mats])).cuda()
+    small, sdet = _cca(x7, y7, eps, detail=True)
+    worst = 0.0
+    for k, (xm, ym) in enumerate(mats):
+        err, cerr, bar = _check_all(small, sdet, k, O.cca(xm, ym, eps, O.THRESHOLD), p)
+        worst = max(worst, err / bar, cerr / bar)
+    idx = torch.arange(pairs, device='cuda') % 7
+    big, bdet = _cca(x7[idx].contiguous(), y7[idx].contiguous(), eps, detail=True)
+    bits = lambda t: t.contiguous().view(torch.int64) if t.dtype == torch.float64 else t           # noqa: E731  (NaN rows compare as bits)
+    differing = 0
+    for name, b, s in list(zip(small._fields, big, small)) + list(zip(sdet._fields, bdet, sdet)):
+        same = bits(b) == bits(s[idx])
+        differing += int((~same).sum())
+        assert bool(same.all()), (name, (~same.reshape(pairs, -1).all(dim=1)).nonzero().flatten()[:8].tolist())
+    report('cca_70000_pairs', worst_share_of_bar=worst, entries_differing=differing)

@@ -171,3 +171,106 @@ def test_run_rep_cka_matches_per_pair_calls():
                 assert vals == [1.0, 1.0]
             for t, (ra, ri) in enumerate(reps[layer]):
                 assert abs(vals[t] - fn(ra, ri)) <= 1e-9, (kind, layer, t)
+
+
+# ------------------------------------------------------------------------------------------ the limits of the stated domain
+# mi_maml.h: 1 <= p <= 128, 2 <= n <= 2^18, pairs >= 1.  Inputs and expectations: cka_oracle.LIMIT_CASES / TIE_CASES (the host side
+# of these checks is tests/test_cka_host.py).
+
+_ORACLE = {}
+
+
+def _oracle_row(kind, seed, n, p, sigma):
+    """(linear, kernel, sigma_x, sigma_y) of the fp64 restatement, computed once per case"""
+    key = (kind, seed, n, p, sigma)
+    if key not in _ORACLE:
+        x, y = O.make_case(kind, seed, n, p)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            o = O.cka(x, y, sigma if sigma > 0 else None)
+        _ORACLE[key] = np.array([o['linear'], o['kernel'], o['sigma_x'], o['sigma_y']], dtype=np.float64)
+    return _ORACLE[key]
+
+
+def _check_nan_aware(got, want, tol=TOL):
+    """_check where the oracle is finite; NaN exactly where the oracle (numpy's rule) gives NaN.  -> (err_cka, err_sigma2)"""
+    assert list(np.isnan(got)) == list(np.isnan(want)), (got, want)
+    err_cka = max([abs(got[k] - want[k]) for k in (0, 1) if not np.isnan(want[k])], default=0.0)
+    err_sig = max([abs(got[k] ** 2 - want[k] ** 2) / want[k] ** 2 for k in (2, 3) if not np.isnan(want[k])], default=0.0)
+    assert err_cka <= tol and err_sig <= tol, (got, want, err_cka, err_sig)
+    return err_cka, err_sig
+
+
+@pytest.mark.parametrize('idx', range(len(O.LIMIT_CASES)), ids=['{}-n{}-p{}-s{}'.format(c[0], c[2], c[3], c[4]) for c in O.LIMIT_CASES])
+def test_cka_at_the_limits_of_the_domain(idx):
+    """p = 128 / 127, the histogram's 64 KiB LDS crossing (p = 96 -> 97), n = 2 and 3, the tile edge n = 63 / 64 / 65, the first column
+    split n = 1025 and n = 2049, each with the median bandwidth; (130, 128) also with sigma = 2."""
+    kind, seed, n, p, sigma = O.LIMIT_CASES[idx]
+    x, y = O.make_case(kind, seed, n, p)
+    got = _row(_cka(x, y, sigma if sigma > 0 else None))
+    e = _check_nan_aware(got, _oracle_row(kind, seed, n, p, sigma))
+    report(f'cka_limit[{kind},n{n},p{p},sigma{sigma}]', cka_err=e[0], sigma2_err=e[1])
+
+
+def test_cka_median_of_heavily_tied_distances():
+    """Rows on the lattice {0..3}^2: nine distinct squared distances, hundreds of ties, both middle ranks inside one radix bin or
+    (the last two cases' X) on the two values 4 and 5.  Every distance is an exact small integer in fp32 and in fp64, so sigma^2 must
+    be numpy's median exactly."""
+    worst = 0.0
+    for sx, sy, n, dup in O.TIE_CASES:
+        x, y = O.lattice_rows(sx, n, dup), O.lattice_rows(sy, n, dup)
+        got = _row(_cka(x, y))
+        want2 = (O.exact_median_sigma2(x), O.exact_median_sigma2(y))
+        print(f'[cka] lattice {sx} {sy} n={n}: sigma^2 {got[2] ** 2!r} {got[3] ** 2!r} want {want2}', flush=True)
+        assert got[2] == np.sqrt(want2[0]) and got[3] == np.sqrt(want2[1]), (got, want2)          # the kernel's sqrt of the exact median
+        o = O.cka(x, y)
+        worst = max(worst, *_check(got, (o['linear'], o['kernel'], o['sigma_x'], o['sigma_y'])))
+    report('cka_lattice_ties', worst=worst, sigma2_rel_err=0.0)
+
+
+@pytest.mark.parametrize('kind,seed', [('gauss', 81), ('relu', 82)])
+def test_cka_under_power_of_two_scaling(kind, seed):
+    """(2^20 X, 2^-20 Y) against (X, Y): scaling by a power of two is exact in fp32, the distances scale by 2^40 / 2^-40 exactly, so
+    the bandwidths scale by exactly 2^20 / 2^-20 and both CKAs stay within TOL of the oracle's value for (X, Y)."""
+    x, y = O.make_case(kind, seed, 200, 5)
+    base = _row(_cka(x, y))
+    got = _row(_cka(x * np.float32(2.0 ** 20), y * np.float32(2.0 ** -20)))
+    o = O.cka(x, y)
+    e = _check(base, (o['linear'], o['kernel'], o['sigma_x'], o['sigma_y']))
+    err = max(abs(got[0] - o['linear']), abs(got[1] - o['kernel']))
+    assert err <= TOL, (got, o)
+    assert got[2] / base[2] == 2.0 ** 20 and got[3] / base[3] == 2.0 ** -20, (got, base)
+    report(f'cka_pow2_scaling[{kind}]', cka_err=err, unscaled_cka_err=e[0], cka_bit_identical=bool(got[0] == base[0] and got[1] == base[1]),
+           linear_delta=abs(got[0] - base[0]), kernel_delta=abs(got[1] - base[1]))
+
+
+def test_cka_more_pairs_than_one_launch_sequence():
+    """pairs = 8195 > the 8192 pairs of one launch sequence: the second chunk's input and output offsets and the scratch it reuses.
+    Five distinct 4 x 2 pairs repeated cyclically; row k must be row k mod 5 of the 5-pair call bit for bit.  The C ABI directly, the
+    scratch exactly mi_cka_scratch_bytes(8195, 4, 2) with a guard behind it."""
+    from exploring_meta_amd import _lib
+    lib = _lib.load()
+    pairs, n, p = 8195, 4, 2
+    cases = [('gauss', 90), ('relu', 91), ('gauss', 92), ('relu', 93), ('gauss', 94)]
+    mats = [O.make_case(kind, seed, n, p) for kind, seed in cases]
+    x5 = torch.from_numpy(np.stack([m[0] for m in mats])).cuda()
+    y5 = torch.from_numpy(np.stack([m[1] for m in mats])).cuda()
+    small = torch.stack(list(_cka(x5, y5)), dim=1)                                   # [5, 4]
+    worst = [0.0, 0.0]
+    for k, (kind, seed) in enumerate(cases):
+        e = _check_nan_aware(small[k].cpu().numpy(), _oracle_row(kind, seed, n, p, 0.0))
+        worst = [max(a, b) for a, b in zip(worst, e)]
+    idx = torch.arange(pairs, device='cuda') % 5
+    xs, ys = x5[idx].contiguous(), y5[idx].contiguous()
+    need = lib.mi_cka_scratch_bytes(pairs, n, p)
+    assert 0 < need == lib.mi_cka_scratch_bytes(8192, n, p)
+    guard = 4096
+    scratch = torch.full((need + guard,), 0xA5, dtype=torch.uint8, device='cuda')
+    out = torch.full((pairs + 1, 4), -7.0, dtype=torch.float64, device='cuda')
+    _lib.check(lib.mi_cka(torch.cuda.current_stream().cuda_stream, xs.data_ptr(), ys.data_ptr(), pairs, n, p, 0.0, scratch.data_ptr(), need,
+                          out.data_ptr()))
+    torch.cuda.synchronize()
+    assert bool((scratch[need:] == 0xA5).all()) and bool((out[pairs] == -7.0).all())
+    same = out[:pairs].view(torch.int64) == small[idx].contiguous().view(torch.int64)
+    bad = (~same.all(dim=1)).nonzero().flatten().tolist()
+    assert not bad, ('first rows that differ from the 5-pair call', bad[:8])
+    report('cka_8195_pairs', oracle_cka=worst[0], oracle_sigma2=worst[1], rows_differing=len(bad))

@@ -8,6 +8,7 @@ import torch
 from exploring_meta_amd.utils import synthetic
 from exploring_meta_amd.utils.task_sampler import ResidentDataset, TaskSampler
 from oracle import sampler_ref as S
+from gpu_utils import report
 
 pytestmark = pytest.mark.gpu
 
@@ -169,3 +170,51 @@ def test_argument_errors():
     with pytest.raises(ValueError):
         TaskSampler(ds, 2, 1).sample_batch(2, rank=1, world=2)             # rank slices need the counter-based draw
     assert sm.base == 0
+
+
+# ------------------------------------------------------------------------------------------ the limits of the stated domain
+# mi_maml.h: ways <= 32, k <= 64, n_rot <= 256, num_tasks < 2^32
+
+@pytest.mark.parametrize('num_tasks,seed,slots', S.REJECTION_DRAWS)
+def test_id_draw_with_a_bound_above_2_31_runs_the_rejection_loop(num_tasks, seed, slots):
+    """Philox::bounded's `while (l < t)`: with num_tasks = 2^31 + 1 / 3 * 2^30 a word is rejected with probability 1/2 / 1/4 (the host
+    test counts the slots that do), so the device loop runs; ids, indices, labels and rotations equal the mirror."""
+    labels, sm = _sampler('20w1s_rot_subset', seed=seed, num_tasks=num_tasks)
+    rejecting = sum(S.id_draw_words(seed, slot, num_tasks)[1] > 1 for slot in range(slots))
+    assert rejecting >= 8
+    windex, wlabels, wrot, wids = _assert_draw_equals_mirror(sm, slots)
+    assert wids.tolist() == [S.id_draw_words(seed, slot, num_tasks)[0] for slot in range(slots)]
+    assert len(set(wids.tolist())) == slots and int(wids.max()) >= 2 ** 30 and wrot is not None
+    report(f'draw_rejection[{num_tasks}]', slots_rejecting=rejecting, mismatches=0)
+
+
+def test_every_table_full_32_ways_of_64_rows():
+    """ways = 32 with k = 64: every LDS table of the kernel full (2048 rows per task, 64 override entries per lane), rotations on."""
+    sizes = [64 + (3 * c) % 7 for c in range(34)]
+    assert min(sizes) == 64 and max(sizes) == 70
+    imgs, labels, ds = _dataset(sizes)
+    sm = TaskSampler(ds, 32, 32, rotations=[0.0, 90.0, 180.0, 270.0], seed=6, draw='device')
+    windex, wlabels, wrot, _ = _assert_draw_equals_mirror(sm, 3)
+    assert windex.shape == (3, 2048)
+    for t in range(3):
+        S.check_task_structure(windex[t], wlabels[t], wrot[t], labels, 32, 32, sm.classes.tolist())
+    assert len(set(wrot.ravel().tolist())) == 4
+    report('draw_32_ways_64_rows', mismatches=0)
+
+
+def test_rotation_table_at_its_cap():
+    """n_rot = 256: the rotation stream is stream 3 with bounded(256); the table entry i is i & 3, so a row's turns are the low bits of
+    the entry the draw picked."""
+    imgs, labels, ds = _dataset([12] * 30)
+    rotations = [90.0 * (i & 3) for i in range(256)]
+    sm = TaskSampler(ds, 20, 1, rotations=rotations, seed=13, draw='device')
+    assert sm.rotations.tolist() == [i & 3 for i in range(256)]
+    windex, wlabels, wrot, wids = _assert_draw_equals_mirror(sm, 40)
+    from exploring_meta_amd.utils import task_sampler as TS
+    for t in (0, 17, 39):
+        words = TS.philox_words(13, int(wids[t]), TS.STREAM_ROTATIONS)
+        assert wrot[t, ::2].tolist() == [TS.bounded(words, 256) & 3 for _ in range(20)]
+    assert len(set(wrot.ravel().tolist())) == 4
+    with pytest.raises(ValueError):
+        TaskSampler(ds, 20, 1, rotations=rotations + [0.0], draw='device')
+    report('draw_256_rotations', mismatches=0)

@@ -680,6 +680,148 @@ def test_gae_kernel_matches_oracle(S, lens, ep_len, truncated, normalize):
     assert worst < 5e-7                               # fp32 output rounding
 
 
+# ---- mi_gae_advantages at the limits mi_maml.h states (state_dim 1..8, rows <= mi_gae_max_rows, count / weight_in / weight_out optional)
+GAE_BAR, PRED_BAR = 5e-7, 1e-6                      # the bars of test_gae_kernel_matches_oracle
+GAMMA, TAU, REG = 0.99, 0.95, 2.0
+
+
+def _gae_oracle(ep, S, normalize, base=None):
+    """(advantages [n], the baseline used) of the oracle: fitted on `ep` unless a fitted `base` is given (update_vf=False)"""
+    fit = base is None
+    base = RL.LinearValue(S, REG) if fit else base
+    ref = RL.compute_advantages(base, TAU, GAMMA, ep, fit)
+    if normalize:
+        ref = RL.normalize(ref)
+    return ref.reshape(-1).numpy(), base
+
+
+def _adv_err(got, ref):
+    return float(np.abs(got.double().cpu().numpy() - ref).max()) / max(1.0, float(np.abs(ref).max()))
+
+
+def _pred_err(base, ep, wts):
+    f = base._features(ep['states'])
+    pred_ref, pred = (f @ base.weight).reshape(-1).numpy(), (f @ wts.cpu().reshape(-1, 1)).reshape(-1).numpy()
+    return float(np.abs(pred - pred_ref).max()) / max(1.0, float(np.abs(pred_ref).max()))
+
+
+def _gae_device(eps, S, normalize, **kw):
+    from exploring_meta_amd.engine import gae_advantages
+    from exploring_meta_amd.core_functions.rl import _device_batch
+    batch = _device_batch(eps, S, 2, torch.device('cuda'))
+    count = kw.pop('count', batch['count'])
+    out = gae_advantages(batch['states'], batch['next_states'], batch['rewards'], batch['dones'], count, GAMMA, TAU, REG, normalize=normalize, **kw)
+    torch.cuda.synchronize()
+    return out
+
+
+def _check_replays(name, eps, S, normalize, adv, wts):
+    worst = worst_pred = 0.0
+    for i, ep in enumerate(eps):
+        n = ep['states'].shape[0]
+        ref, base = _gae_oracle(ep, S, normalize)
+        worst = max(worst, _adv_err(adv[i, :n], ref))
+        assert float(adv[i, n:].abs().sum()) == 0.0
+        worst_pred = max(worst_pred, _pred_err(base, ep, wts[i]))
+    report(name, max_rel=worst, pred_rel=worst_pred)
+    assert worst < GAE_BAR and worst_pred <= PRED_BAR, (worst, worst_pred)
+
+
+def test_gae_one_state_dimension():
+    eps = [_random_replay(60 + i, n, 1, 10) for i, n in enumerate([40, 7])]
+    adv, wts = _gae_device(eps, 1, True, want_weights=True)
+    assert wts.shape == (2, 6)
+    _check_replays('gae_limit[S1,[40,7]]', eps, 1, True, adv, wts)
+
+
+def _abi_status(rows, S):
+    """the status of mi_gae_advantages for one replay of `rows` rows (real buffers of that size)"""
+    from exploring_meta_amd import _lib
+    z = torch.zeros(rows * S, dtype=torch.float32, device='cuda')
+    r, adv = torch.zeros(rows, dtype=torch.float32, device='cuda'), torch.zeros(rows, dtype=torch.float32, device='cuda')
+    rc = _lib.load().mi_gae_advantages(torch.cuda.current_stream().cuda_stream, z.data_ptr(), z.data_ptr(), r.data_ptr(), r.data_ptr(), None, None,
+                                       1, rows, S, GAMMA, TAU, REG, 1, adv.data_ptr(), None)
+    torch.cuda.synchronize()
+    return rc
+
+
+def test_gae_longest_replay_that_fits_in_lds():
+    """rows = mi_gae_max_rows(8): the 160 KiB LDS limit with the widest state; one row more is MI_ERR_ARG (also for S = 2)."""
+    from exploring_meta_amd.engine import gae_max_rows
+    rows = gae_max_rows(8)
+    assert rows * (8 + 8 + 4 + 4 * 8) <= 160 * 1024 - 11776 < (rows + 1) * (8 + 8 + 4 + 4 * 8) and rows == 2924
+    eps = [_random_replay(62, rows, 8, 100)]
+    adv, wts = _gae_device(eps, 8, True, want_weights=True)
+    _check_replays(f'gae_limit[S8,[{rows}]]', eps, 8, True, adv, wts)
+    assert _abi_status(rows + 1, 8) == -1 and _abi_status(gae_max_rows(2) + 1, 2) == -1          # MI_ERR_ARG
+    assert _abi_status(gae_max_rows(2), 2) == 0
+
+
+def test_gae_without_a_count_array():
+    """count = NULL: every replay uses all its rows"""
+    eps = [_random_replay(63 + i, 96, 3, 24, truncated=bool(i)) for i in range(3)]
+    adv, wts = _gae_device(eps, 3, True, want_weights=True, count=None)
+    with_count = _gae_device(eps, 3, True)
+    assert torch.equal(adv, with_count)
+    _check_replays('gae_limit[count=NULL]', eps, 3, True, adv, wts)
+
+
+def test_gae_replay_without_rows_between_two_others():
+    """count = 0 for the middle replay: its advantages are zeros, its neighbours' are those of a call without it, bit for bit"""
+    eps = [_random_replay(66 + i, n, 2, 20) for i, n in enumerate([80, 80, 57])]
+    count = torch.tensor([80, 0, 57], dtype=torch.int32, device='cuda')
+    adv, wts = _gae_device(eps, 2, True, want_weights=True, count=count)
+    assert float(adv[1].abs().sum()) == 0.0 and bool(torch.isfinite(adv).all())
+    alone, wts2 = _gae_device([eps[0], eps[2]], 2, True, want_weights=True)
+    assert torch.equal(adv[0], alone[0]) and torch.equal(adv[2], alone[1])
+    assert torch.equal(wts[0], wts2[0]) and torch.equal(wts[2], wts2[1])
+    _check_replays('gae_limit[count=0 between]', [eps[0], eps[2]], 2, True, alone, wts2)
+
+
+def _hand_made_dones(n=2100):
+    """a done at row 0, then episodes of 1, 2, 3, 4, 5, 1, 1, 8 rows repeating (every exit of the scan's four-row groups), a pair of
+    episode ends 1024 rows apart (both walked by one thread) and a last episode cut by the end of the replay"""
+    d = np.zeros(n)
+    d[0] = 1.0
+    pos, k, lens = 1, 0, (1, 2, 3, 4, 5, 1, 1, 8)
+    while pos + lens[k % 8] - 1 < n:
+        pos += lens[k % 8]
+        d[pos - 1] = 1.0
+        k += 1
+    i = int(np.nonzero(d[:1000])[0][40])
+    d[i + 1024] = 1.0
+    d[n - 3:] = 0.0
+    ends = np.nonzero(d)[0]
+    assert d[0] == 1.0 and d[i] == d[i + 1024] == 1.0 and d[n - 1] == 0.0
+    assert {1, 2, 3, 4, 5, 8} <= set(np.diff(ends).tolist())
+    return d
+
+
+@pytest.mark.parametrize('normalize', [True, False])
+def test_gae_hand_made_episode_pattern(normalize):
+    ep = _random_replay(70, 2100, 2, 100, truncated=True)
+    ep['dones'] = torch.from_numpy(_hand_made_dones()).reshape(-1, 1)
+    adv, wts = _gae_device([ep], 2, normalize, want_weights=True)
+    _check_replays(f'gae_limit[hand-made dones,normalize={normalize}]', [ep], 2, normalize, adv, wts)
+
+
+def test_gae_with_given_baseline_weights():
+    """weight_in (compute_advantages' update_vf=False, rl.py:401): the baseline fitted on replay A, the advantages of replay B; weight_out
+    echoes weight_in"""
+    a, b = _random_replay(71, 150, 3, 30), _random_replay(72, 150, 3, 25, truncated=True)
+    _, w_a = _gae_device([a], 3, True, want_weights=True)
+    adv, w_out = _gae_device([b], 3, True, want_weights=True, weights=w_a)
+    assert torch.equal(w_out, w_a)
+    no_echo = _gae_device([b], 3, True, weights=w_a)
+    assert torch.equal(no_echo, adv)
+    _, base = _gae_oracle(a, 3, True)
+    ref, _ = _gae_oracle(b, 3, True, base=base)
+    fitted_on_b, _ = _gae_oracle(b, 3, True)
+    err = _adv_err(adv[0], ref)
+    report('gae_limit[weight_in]', max_rel=err, pred_rel=_pred_err(base, a, w_a[0]), distance_to_own_fit=float(np.abs(ref - fitted_on_b).max()))
+    assert err < GAE_BAR and float(np.abs(ref - fitted_on_b).max()) > 1e-3          # (the two baselines give different advantages)
+
+
 @pytest.mark.parametrize('lens', [[85, 60, 17, 1], [64, 64, 64], [2000] * 27 + [1731] * 110])
 def test_packed_device_batch_matches_the_general_path(lens, monkeypatch):
     """_device_batch of replays whose fields already lie on the device as fp32 tensors (what the runners produce): mi_copy_segments packs
