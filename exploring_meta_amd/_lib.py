@@ -40,6 +40,18 @@ class MiBlock1Args(C.Structure):
                 ('tasks', C.c_int32), ('n', C.c_int32), ('h', C.c_int32), ('w_', C.c_int32), ('ci', C.c_int32), ('co', C.c_int32)]
 
 
+class MiTailArgs(C.Structure):
+    _fields_ = [('z', C.c_void_p), ('zd', C.c_void_p), ('mu', C.c_void_p), ('rstd', C.c_void_p), ('m1', C.c_void_p), ('m2', C.c_void_p),
+                ('gamma', C.c_void_p), ('beta', C.c_void_p), ('wl', C.c_void_p), ('bl', C.c_void_p), ('pstride', C.c_size_t),
+                ('gammad', C.c_void_p), ('betad', C.c_void_p), ('wld', C.c_void_p), ('bld', C.c_void_p), ('vstride', C.c_size_t),
+                ('y', C.c_void_p), ('f', C.c_void_p), ('dp', C.c_void_p), ('prob', C.c_void_p), ('dl', C.c_void_p),
+                ('pooled', C.c_void_p), ('loss', C.c_void_p), ('acc', C.c_void_p), ('logits', C.c_void_p),
+                ('dwl', C.c_void_p), ('dbl', C.c_void_p), ('sum0', C.c_void_p), ('sum1', C.c_void_p), ('gstride', C.c_size_t),
+                ('df', C.c_void_p),
+                ('tasks', C.c_int32), ('n', C.c_int32), ('ho', C.c_int32), ('wo', C.c_int32), ('c', C.c_int32), ('pool', C.c_int32),
+                ('ways', C.c_int32), ('with_grad', C.c_int32), ('bwd_tasks', C.c_int32)]
+
+
 class MiError(RuntimeError):
     pass
 
@@ -131,6 +143,16 @@ _SIGS = {
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     'mi_kernel_scratch_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'mi_head_grads': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p] + [C.c_int] * 4 +
+                      [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mi_head_tangent': (C.c_int, [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int] * 5 +
+                        [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mi_spatial_mean': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    'mi_spatial_mean_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    'mi_tail_supported': (C.c_int, [C.c_int] * 7),
+    'mi_tail_lds_bytes': (C.c_size_t, [C.c_int] * 4),
+    'mi_tail_scratch_bytes': (C.c_size_t, [C.c_int] * 7),
+    'mi_tail_run': (C.c_int, [C.c_void_p, C.POINTER(MiTailArgs), C.c_int, C.c_void_p, C.c_size_t]),
     'mi_conv3x3_tangent': (C.c_int, [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p] * 4 + [C.c_size_t]),
     'mi_conv3x3_bwd2': (C.c_int, [C.c_void_p] * 7 + [C.c_size_t] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     'mi_bn_tangent_fwd': (C.c_int, [C.c_void_p, C.POINTER(MiBnTangentArgs), C.c_void_p]),

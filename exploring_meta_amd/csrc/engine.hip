@@ -136,6 +136,19 @@ static int fail(mi_engine* e, int code, const std::string& msg) {
       return fail(e, MI_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s) + " @" + std::to_string(__LINE__)); \
   } while (0)
 
+// The head's gradient launch keeps a whole task's dlogits in LDS (head.hip): sizes that do not fit are an argument error, reported before the launch.
+static int head_lds_check(mi_engine* e, const char* who, int n, int ways, int tangent) {
+  if (head_lds_fits(n, ways, tangent)) return MI_OK;
+  return fail(e, MI_ERR_ARG, std::string(who) + ": the classifier head's " + (tangent ? "tangent" : "gradient") + " launch with n = " + std::to_string(n) +
+                                 " rows per task and ways = " + std::to_string(ways) + " needs " + std::to_string(head_grads_lds_bytes(n, ways, tangent)) +
+                                 " bytes of LDS, the device has " + std::to_string(head_lds_limit_bytes()) + " (n * ways <= " + (tangent ? "19712" : "39424") + ")");
+}
+#define HEAD_LDS(e, who, n, ways, tangent)                                         \
+  do {                                                                             \
+    const int _hrc = head_lds_check(e, who, n, ways, tangent);                     \
+    if (_hrc) return _hrc;                                                         \
+  } while (0)
+
 static FinArgs fin_of(const mi_engine* e, int T, double inv_m, int mode, float* o0, size_t s0, float* o1, size_t s1) {
   const bool on = e->fuse_fin && e->counters && T <= mi_engine::kMaxCounterTasks;
   return FinArgs{on ? e->counters : nullptr, o0, o1, s0, s1, inv_m, mode};
@@ -890,6 +903,7 @@ static int head_pass(mi_engine* e, hipStream_t st, float* hscr, const float* f, 
   ha.df = with_grad ? df : nullptr;
   ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
   head_scratch(e, ha, hscr, T, n);
+  if (with_grad) HEAD_LDS(e, "head", n, ha.ways, 0);
   LAUNCH(e, st, OP_HEAD, 0, launch_head_fwd_bwd(st, ha, T, with_grad ? 1 : 0));
   return MI_OK;
 }
@@ -1076,6 +1090,7 @@ static int pass_hvp(mi_engine* e, hipStream_t st, Plan& pl, ActSet& A, const flo
     tail_common(e, pl, ta);
     LAUNCH(e, st, OP_HEAD_TAN, 0, launch_tail(st, ta, T, L.pool, 1));
   } else {
+    HEAD_LDS(e, "head tangent", n, ha.ways, 1);
     LAUNCH(e, st, OP_HEAD_TAN, 0, launch_head_tangent(st, ha, T));
   }
   if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean_bwd(st, X.rdf, X.dpd[cur], T * n, e->head_hw, e->head_c));
@@ -1477,6 +1492,7 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const float* theta, 
       ha.df = ap.rdf;
       ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
       head_scratch(e, ha, ap.hscr, T, n);
+      HEAD_LDS(e, "head tangent", n, ha.ways, 1);
       LAUNCH(e, st, OP_HEAD_TAN, 0, launch_head_tangent(st, ha, T));
       LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, ap.dfs, ap.rdf, inner_lr, fsz, ap.dfs));   // dfs -= lr * R{df}
       LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, ap.lam, ap.hv, inner_lr, TP, ap.lam));     // lam -= lr * H lam
@@ -1670,6 +1686,7 @@ extern "C" int mi_learner_backward(mi_engine* e, void* stream, const float* thet
   ha.dwl = pl.lam + e->off_wl; ha.dbl = pl.lam + e->off_bl; ha.gstride = e->PS;
   ha.df = A.df;
   ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
+  HEAD_LDS(e, "head backward", n, ha.ways, 0);
   LAUNCH(e, st, OP_HEAD, 0, launch_head_grads(st, ha, tasks));
   if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean_bwd(st, A.df, A.dp[nl - 1], tasks * n, e->head_hw, e->head_c));
   rc = trunk_backward(e, st, pl, A, pl.xq, n, tasks, pl.theta, pl.lam);
@@ -1728,6 +1745,7 @@ extern "C" int mi_learner_hvp(mi_engine* e, void* stream, const float* theta, in
   ha.dwl = pl.g + e->off_wl; ha.dbl = pl.g + e->off_bl; ha.gstride = e->PS;
   ha.df = A.df;
   ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
+  HEAD_LDS(e, "head backward", n, ha.ways, 0);
   LAUNCH(e, st, OP_HEAD, 0, launch_head_grads(st, ha, tasks));
   if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean_bwd(st, A.df, A.dp[nl - 1], tasks * n, e->head_hw, e->head_c));
   rc = trunk_backward(e, st, pl, A, pl.xs, n, tasks, pl.theta, pl.g);
@@ -1942,6 +1960,8 @@ extern "C" int mi_head_fwd_bwd(void* stream, const float* f, const float* wl, co
   ha.prob = prob; ha.dl = dl; ha.dwl = dwl; ha.dbl = dbl; ha.gstride = gstride; ha.df = df;
   ha.n = n; ha.feat = feat; ha.ways = ways;
   if (!df || (size_t)feat < 2) return fail(nullptr, MI_ERR_ARG, "mi_head_fwd_bwd needs df (its first 2*tasks*n floats double as row scratch)");
+  if (tasks < 1 || n < 1 || ways < 1 || ways > 64) return fail(nullptr, MI_ERR_ARG, "mi_head_fwd_bwd: tasks, n >= 1 and ways in 1..64");
+  if (dwl) HEAD_LDS(nullptr, "mi_head_fwd_bwd", n, ways, 0);      // (before the rows launch: a refused call launches nothing)
   ha.rowloss = df; ha.rowhit = df + (size_t)tasks * n;   // consumed by the reduce launch before the gradient launch overwrites df
   // (the engine's own passes give the rows kernel separate scratch and let the gradient launch fold loss / acc; here the row
   // scratch aliases df, so the three launches stay separate)
@@ -1950,6 +1970,130 @@ extern "C" int mi_head_fwd_bwd(void* stream, const float* f, const float* wl, co
     ha.loss = nullptr; ha.acc = nullptr;
     HIPCHK0(launch_head_grads(reinterpret_cast<hipStream_t>(stream), ha, tasks));
   }
+  return MI_OK;
+}
+
+// launch_head_grads alone: dWl, dbl, df (may be NULL) from given dlogits
+extern "C" int mi_head_grads(void* stream, const float* f, const float* wl, size_t pstride, const float* dl, int tasks, int n, int feat,
+                             int ways, float* dwl, float* dbl, size_t gstride, float* df) {
+  if (!f || !wl || !dl || !dwl || !dbl || tasks < 1 || n < 1 || feat < 1 || ways < 1 || ways > 64)
+    return fail(nullptr, MI_ERR_ARG, "mi_head_grads: null pointer, or tasks / n / feat < 1, or ways outside 1..64");
+  HEAD_LDS(nullptr, "mi_head_grads", n, ways, 0);
+  HeadArgs ha{};
+  ha.f = f; ha.wl = wl; ha.pstride = pstride; ha.dl = const_cast<float*>(dl);
+  ha.dwl = dwl; ha.dbl = dbl; ha.gstride = gstride; ha.df = df;
+  ha.n = n; ha.feat = feat; ha.ways = ways;
+  HIPCHK0(launch_head_grads(reinterpret_cast<hipStream_t>(stream), ha, tasks));
+  return MI_OK;
+}
+
+// launch_head_tangent: the rows launch (logit tangents, R{dlogits}) and the gradient launch (R{dWl}, R{dbl}, R{df})
+extern "C" int mi_head_tangent(void* stream, const float* f, const float* fd, const float* wl, const float* bl, size_t pstride,
+                               const float* wld, const float* bld, size_t vstride, const float* prob, const float* dl, float* rdl,
+                               float* ld_out, int fixed_dl, int tasks, int n, int feat, int ways, float* dwl, float* dbl,
+                               size_t gstride, float* df) {
+  if (!f || !wl || !bl || !wld || !bld || !dl || !rdl || !dwl || !dbl || (!fixed_dl && !prob) || tasks < 1 || n < 1 || feat < 1 || ways < 1 || ways > 64)
+    return fail(nullptr, MI_ERR_ARG, "mi_head_tangent: null pointer, or tasks / n / feat < 1, or ways outside 1..64");
+  HEAD_LDS(nullptr, "mi_head_tangent", n, ways, 1);
+  HeadArgs ha{};
+  ha.f = f; ha.fd = fd; ha.wl = wl; ha.bl = bl; ha.pstride = pstride; ha.wld = wld; ha.bld = bld; ha.vstride = vstride;
+  ha.prob = const_cast<float*>(prob); ha.dl = const_cast<float*>(dl); ha.rdl = rdl; ha.ld_out = ld_out; ha.fixed_dl = fixed_dl ? 1 : 0;
+  ha.dwl = dwl; ha.dbl = dbl; ha.gstride = gstride; ha.df = df;
+  ha.n = n; ha.feat = feat; ha.ways = ways;
+  HIPCHK0(launch_head_tangent(reinterpret_cast<hipStream_t>(stream), ha, tasks));
+  return MI_OK;
+}
+
+extern "C" int mi_spatial_mean(void* stream, const float* p, float* f, int rows, int hw, int c) {
+  if (!p || !f || rows < 1 || hw < 1 || c < 1) return fail(nullptr, MI_ERR_ARG, "mi_spatial_mean: null pointer or empty shape");
+  HIPCHK0(launch_spatial_mean(reinterpret_cast<hipStream_t>(stream), p, f, rows, hw, c));
+  return MI_OK;
+}
+extern "C" int mi_spatial_mean_bwd(void* stream, const float* df, float* dp, int rows, int hw, int c) {
+  if (!df || !dp || rows < 1 || hw < 1 || c < 1) return fail(nullptr, MI_ERR_ARG, "mi_spatial_mean_bwd: null pointer or empty shape");
+  HIPCHK0(launch_spatial_mean_bwd(reinterpret_cast<hipStream_t>(stream), df, dp, rows, hw, c));
+  return MI_OK;
+}
+
+// The one-launch tail (tail.hip) on flat pointers.  Scratch layout: [arrival counters: tasks x u32 | BatchNorm partials (fp64) | dWl partials |
+// per-row scalars | R{dlogits} | row loss | row hit], every part on a 256-byte boundary.  The counters come first and are the CALLER's to zero
+// once (the kernels leave them at zero).
+namespace {
+struct TailCarve { size_t counter, bpart, wpart, scr, rdl, rowloss, rowhit, bytes; };
+TailCarve tail_carve_host(int tasks, int n, int c, int feat, int ways) {
+  TailCarve k{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) { off = align_up(off, 256); const size_t at = off; off += bytes; return at; };
+  k.counter = take((size_t)tasks * sizeof(unsigned));
+  k.bpart = take(tail_bpart_doubles(tasks, c) * sizeof(double));
+  k.wpart = take(tail_wpart_floats(tasks, feat, ways) * sizeof(float));
+  k.scr = take(tail_scr_floats(tasks, n, ways) * sizeof(float));
+  k.rdl = take((size_t)tasks * n * ways * sizeof(float));
+  k.rowloss = take((size_t)tasks * n * sizeof(float));
+  k.rowhit = take((size_t)tasks * n * sizeof(float));
+  k.bytes = align_up(off, 256);
+  return k;
+}
+int tail_feat(int ho, int wo, int c, int pool) { return (pool ? (ho / 2) * (wo / 2) : ho * wo) * c; }
+}  // namespace
+
+extern "C" int mi_tail_supported(int n, int ho, int wo, int c, int pool, int feat, int ways) {
+  return tail_supported(n, ho, wo, c, pool, feat, ways) ? 1 : 0;
+}
+extern "C" size_t mi_tail_lds_bytes(int n, int feat, int ways, int tangent) {
+  return (n < 1 || feat < 1 || ways < 1) ? 0 : tail_lds_bytes_host(n, feat, ways, tangent ? 1 : 0);
+}
+extern "C" size_t mi_tail_scratch_bytes(int tasks, int n, int ho, int wo, int c, int pool, int ways) {
+  if (tasks < 1 || n < 1 || ho < 1 || wo < 1 || c < 1 || ways < 1) return 0;
+  return tail_carve_host(tasks, n, c, tail_feat(ho, wo, c, pool), ways).bytes;
+}
+extern "C" int mi_tail_run(void* stream, const mi_tail_args* a, int tangent, void* scratch, size_t scratch_bytes) {
+  if (!a || !scratch) return fail(nullptr, MI_ERR_ARG, "mi_tail_run: null argument");
+  const int T = a->tasks, n = a->n, c = a->c, ways = a->ways;
+  if (T < 1 || T > 65535 || n < 1 || a->ho < 1 || a->wo < 1 || c < 1 || ways < 1) return fail(nullptr, MI_ERR_ARG, "mi_tail_run: empty shape, or more than 65535 tasks");
+  const int feat = tail_feat(a->ho, a->wo, c, a->pool);
+  if (!tail_supported(n, a->ho, a->wo, c, a->pool, feat, ways))
+    return fail(nullptr, MI_ERR_ARG, "mi_tail_run: the one-launch tail does not take n = " + std::to_string(n) + ", map " + std::to_string(a->ho) + " x " +
+                                         std::to_string(a->wo) + " x " + std::to_string(c) + (a->pool ? " (pooled)" : "") + ", ways = " + std::to_string(ways) +
+                                         " (tail_supported, csrc/tail.hip)");
+  if (a->pstride % 4 || a->vstride % 4 || a->gstride % 4)
+    return fail(nullptr, MI_ERR_ARG, "mi_tail_run: the per-task strides must be multiples of 4 floats (16-byte loads of the BatchNorm vectors, 16-byte stores of dWl)");
+  const bool primal = !tangent;
+  if (!a->z || !a->mu || !a->rstd || !a->gamma || !a->beta || !a->wl || !a->bl || !a->pooled || !a->prob || !a->dl ||
+      (primal && (!a->y || !a->loss || !a->acc)) ||
+      ((tangent || a->with_grad) && (!a->dwl || !a->dbl || !a->df || !a->sum0 || !a->sum1)) ||
+      (tangent && (!a->zd || !a->m1 || !a->m2 || !a->gammad || !a->betad || !a->wld || !a->bld || !a->f || !a->dp)))
+    return fail(nullptr, MI_ERR_ARG, "mi_tail_run: null pointer argument");
+  const TailCarve k = tail_carve_host(T, n, c, feat, ways);
+  if (scratch_bytes < k.bytes) return fail(nullptr, MI_ERR_WORKSPACE, "mi_tail_run: scratch too small: need " + std::to_string(k.bytes) + " bytes");
+  char* sb = reinterpret_cast<char*>(scratch);
+  TailArgs ta{};
+  BnArgs& ba = ta.bn;
+  ba.z = a->z; ba.zd = a->zd; ba.mu = a->mu; ba.rstd = a->rstd; ba.m1 = a->m1; ba.m2 = a->m2;
+  ba.gamma = a->gamma; ba.beta = a->beta; ba.pstride = a->pstride;
+  ba.gammad = a->gammad; ba.betad = a->betad; ba.vstride = a->vstride;
+  ba.dp = a->dp;
+  ba.n = n; ba.ho = a->ho; ba.wo = a->wo; ba.c = c;
+  ba.inv_m = 1.f / (float)(n * a->ho * a->wo);
+  HeadArgs& ha = ta.hd;
+  ha.f = a->f;
+  ha.wl = a->wl; ha.bl = a->bl; ha.pstride = a->pstride;
+  ha.wld = a->wld; ha.bld = a->bld; ha.vstride = a->vstride;
+  ha.y = a->y; ha.loss = a->loss; ha.acc = a->acc; ha.logits = a->logits; ha.prob = a->prob; ha.dl = a->dl;
+  ha.dwl = a->dwl; ha.dbl = a->dbl; ha.gstride = a->gstride; ha.df = a->df;
+  ha.rdl = reinterpret_cast<float*>(sb + k.rdl);
+  ha.rowloss = reinterpret_cast<float*>(sb + k.rowloss);
+  ha.rowhit = reinterpret_cast<float*>(sb + k.rowhit);
+  ha.n = n; ha.feat = feat; ha.ways = ways;
+  ta.pooled = a->pooled;
+  ta.sum0 = a->sum0; ta.sum1 = a->sum1; ta.sum_stride = a->gstride;
+  ta.with_grad = tangent ? 1 : (a->with_grad ? 1 : 0);
+  ta.bwd_tasks = tangent ? T : a->bwd_tasks;
+  ta.counter = reinterpret_cast<unsigned*>(sb + k.counter);
+  ta.bpart = reinterpret_cast<double*>(sb + k.bpart);
+  ta.wpart = reinterpret_cast<float*>(sb + k.wpart);
+  ta.scr = reinterpret_cast<float*>(sb + k.scr);
+  HIPCHK0(launch_tail(reinterpret_cast<hipStream_t>(stream), ta, T, a->pool ? 1 : 0, tangent ? 1 : 0));
   return MI_OK;
 }
 

@@ -36,9 +36,12 @@ __global__ void head_reduce_kernel(const float* __restrict__ rowloss, const floa
                                    float* __restrict__ loss, float* __restrict__ acc) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= tasks) return;
-  float ls = 0.f, cs = 0.f;
-  for (int k = 0; k < n; ++k) { ls += rowloss[(size_t)t * n + k]; cs += rowhit[(size_t)t * n + k]; }
-  loss[t] = ls / (float)n;
+  // (the row losses in fp64: a sequential fp32 sum of n terms is off by ~sqrt(n) ulp of the SUM -- 2.8e-6 of the mean at n = 2464; the hits are
+  // small integers, exact in fp32)
+  double ls = 0.0;
+  float cs = 0.f;
+  for (int k = 0; k < n; ++k) { ls += (double)rowloss[(size_t)t * n + k]; cs += rowhit[(size_t)t * n + k]; }
+  loss[t] = (float)(ls / (double)n);
   acc[t] = cs / (float)n;
 }
 
@@ -59,30 +62,51 @@ __global__ void spatial_mean_bwd_kernel(const float* __restrict__ df, float* __r
   dp[e] = df[row * c + ch] / (float)hw;
 }
 
+// Dynamic LDS of head_grads_kernel: a whole task's dl [n][ways] (tangent: R{dl} and dl) and the [3][8][64] fold buffer of the row groups.
+// The kernel has no static LDS, so a request may take all of a CU's 160 KiB (gfx950; one workgroup may hold the whole of it):
+//   primal  n * ways <= 39424,   tangent  n * ways <= 19712.
+size_t head_grads_lds_bytes(int n, int ways, int tangent) { return ((size_t)(tangent ? 2 : 1) * (size_t)n * (size_t)ways + 3 * 8 * 64) * sizeof(float); }
+size_t head_lds_limit_bytes() { return (size_t)160 * 1024; }
+bool head_lds_fits(int n, int ways, int tangent) { return n >= 1 && ways >= 1 && head_grads_lds_bytes(n, ways, tangent) <= head_lds_limit_bytes(); }
+
+// A request above 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize, once per (kernel, device): raised to the device's whole LDS, so that
+// a later, larger request of the same process is covered too.  A request above the device's LDS is refused before anything is launched.
+template <bool TANGENT>
+static hipError_t head_grads_launch(hipStream_t st, const HeadArgs& a, int tasks) {
+  const size_t sm = head_grads_lds_bytes(a.n, a.ways, TANGENT ? 1 : 0);
+  if (sm > head_lds_limit_bytes()) return hipErrorInvalidValue;
+  if (sm > 64 * 1024) {
+    static unsigned attr_done = 0;             // one bit per device: the attribute belongs to the device's copy of the kernel
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    if (!(attr_done & (1u << (dev & 31)))) {
+      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(head_grads_kernel<TANGENT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)head_lds_limit_bytes()); e != hipSuccess) return e;
+      attr_done |= 1u << (dev & 31);
+    }
+  }
+  hipLaunchKernelGGL(head_grads_kernel<TANGENT>, dim3(tasks, ceil_div(a.feat, 64)), dim3(256), sm, st, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_head_fwd_bwd(hipStream_t st, const HeadArgs& a, int tasks, int with_grad) {
   if (a.ways > 64) return hipErrorInvalidValue;
+  if (with_grad && !head_lds_fits(a.n, a.ways, 0)) return hipErrorInvalidValue;      // (before the rows launch: nothing runs)
   hipLaunchKernelGGL(head_rows_kernel<false>, dim3(tasks, ceil_div(a.n, 4)), dim3(256), 0, st, a);
-  if (with_grad) {     // the gradient launch also folds the row losses / hits into loss[t], acc[t]
-    const size_t sm = (size_t)(a.n * a.ways + 3 * 8 * 64) * sizeof(float);
-    hipLaunchKernelGGL(head_grads_kernel<false>, dim3(tasks, ceil_div(a.feat, 64)), dim3(256), sm, st, a);
-  } else {
-    hipLaunchKernelGGL(head_reduce_kernel, dim3(ceil_div(tasks, 64)), dim3(64), 0, st, a.rowloss, a.rowhit, tasks, a.n, a.loss, a.acc);
-  }
+  if (with_grad) return head_grads_launch<false>(st, a, tasks);     // the gradient launch also folds the row losses / hits into loss[t], acc[t]
+  hipLaunchKernelGGL(head_reduce_kernel, dim3(ceil_div(tasks, 64)), dim3(64), 0, st, a.rowloss, a.rowhit, tasks, a.n, a.loss, a.acc);
   return hipGetLastError();
 }
 hipError_t launch_head_tangent(hipStream_t st, const HeadArgs& a, int tasks) {
-  if (a.ways > 64) return hipErrorInvalidValue;
+  if (a.ways > 64 || !head_lds_fits(a.n, a.ways, 1)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(head_rows_kernel<true>, dim3(tasks, ceil_div(a.n, 4)), dim3(256), 0, st, a);
-  const size_t sm = (size_t)(2 * a.n * a.ways + 3 * 8 * 64) * sizeof(float);
-  hipLaunchKernelGGL(head_grads_kernel<true>, dim3(tasks, ceil_div(a.feat, 64)), dim3(256), sm, st, a);
-  return hipGetLastError();
+  return head_grads_launch<true>(st, a, tasks);
 }
 // Backward of the linear head from caller-supplied dlogits (a.dl): dWl, dbl, df.  Used by the step-wise learner whose loss
 // is computed outside the engine (rc_vision.py:68-70 scales it, cl_vision.py:58-59 does not).
 hipError_t launch_head_grads(hipStream_t st, const HeadArgs& a, int tasks) {
-  const size_t sm = (size_t)(a.n * a.ways + 3 * 8 * 64) * sizeof(float);
-  hipLaunchKernelGGL(head_grads_kernel<false>, dim3(tasks, ceil_div(a.feat, 64)), dim3(256), sm, st, a);
-  return hipGetLastError();
+  if (a.ways > 64 || !head_lds_fits(a.n, a.ways, 0)) return hipErrorInvalidValue;
+  return head_grads_launch<false>(st, a, tasks);
 }
 hipError_t launch_spatial_mean(hipStream_t st, const float* p, float* f, int rows, int hw, int c) {
   const size_t n = (size_t)rows * c;

@@ -269,9 +269,10 @@ __device__ __forceinline__ void head_task_sums(const HeadArgs& a, int task, int 
   // loss[t] = mean_n rowloss, acc[t] = mean_n rowhit (fixed order) -- the job of head_reduce_kernel, folded in here when a
   // gradient launch follows the rows launch anyway
   if (!TANGENT && a.loss && tid == 64) {
-    float ls = 0.f, cs = 0.f;
-    for (int k = 0; k < N; ++k) { ls += a.rowloss[(size_t)task * N + k]; cs += a.rowhit[(size_t)task * N + k]; }
-    a.loss[task] = ls / (float)N;
+    double ls = 0.0;                                  // (fp64, as head_reduce_kernel: the same bits whichever launch folds them)
+    float cs = 0.f;
+    for (int k = 0; k < N; ++k) { ls += (double)a.rowloss[(size_t)task * N + k]; cs += a.rowhit[(size_t)task * N + k]; }
+    a.loss[task] = (float)(ls / (double)N);
     a.acc[task] = cs / (float)N;
   }
 }

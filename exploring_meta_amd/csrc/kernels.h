@@ -214,6 +214,11 @@ struct HeadArgs {
   float* df;            // [T][n][F] output (df or R{df}); may be null
   int n, feat, ways;
 };
+// Dynamic LDS of the gradient launch (a whole task's dlogits, twice in the tangent pass) against the CU's LDS; the launchers refuse what does not fit
+// with hipErrorInvalidValue before launching anything -- callers check head_lds_fits first and report MI_ERR_ARG.
+size_t head_grads_lds_bytes(int n, int ways, int tangent);
+size_t head_lds_limit_bytes();
+bool head_lds_fits(int n, int ways, int tangent);
 hipError_t launch_head_fwd_bwd(hipStream_t st, const HeadArgs& a, int tasks, int with_grad);
 hipError_t launch_head_tangent(hipStream_t st, const HeadArgs& a, int tasks);
 hipError_t launch_head_grads(hipStream_t st, const HeadArgs& a, int tasks);   // backward only, a.dl supplied by the caller
@@ -236,6 +241,7 @@ struct TailArgs {
   unsigned long long* stamps;   // debug (mi_debug_tail_stamps): [T][4][16] wall_clock64() at the stage boundaries, thread 0 of every workgroup; or nullptr
 };
 bool tail_supported(int n, int ho, int wo, int c, int pool, int feat, int ways);
+size_t tail_lds_bytes_host(int n, int feat, int ways, int tangent);   // dynamic LDS of a tail launch (tail_supported holds the tangent kernel's to 150 KiB)
 size_t tail_wpart_floats(int tasks, int feat, int ways);
 size_t tail_bpart_doubles(int tasks, int c);
 size_t tail_scr_floats(int tasks, int n, int ways);

@@ -30,6 +30,7 @@
 #define TAIL_THREADS 512
 #define TAIL_GROUPS 4          // row groups = workgroups per task (head_grads_kernel's grouping: rows rg, rg + 4, ...)
 #define TAIL_KMAX 4            // (row, pooling window, channel quad) items per thread
+#define TAIL_LDS_CAP (150 * 1024)   // dynamic LDS a launch may ask for (tail_supported)
 
 __device__ __forceinline__ float tail_ld(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double tail_ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -214,9 +215,10 @@ __device__ __forceinline__ void tail_fold(const TailArgs& t, int task, int RL, b
   }
   __syncthreads();
   if (!TANGENT && tid == 64 && h.loss) {
-    float ls = 0.f, cs = 0.f;
-    for (int n = 0; n < N; ++n) { ls += rowv[n * WS + WY]; cs += rowv[n * WS + WY + 1]; }
-    h.loss[task] = ls / (float)N;
+    double ls = 0.0;                                  // (fp64, as head_reduce_kernel / head_task_sums)
+    float cs = 0.f;
+    for (int n = 0; n < N; ++n) { ls += (double)rowv[n * WS + WY]; cs += rowv[n * WS + WY + 1]; }
+    h.loss[task] = (float)(ls / (double)N);
     h.acc[task] = cs / (float)N;
   }
   if (!bwd) return;
@@ -623,8 +625,9 @@ bool tail_supported(int n, int ho, int wo, int c, int pool, int feat, int ways) 
   const long items = (long)((n + TAIL_GROUPS - 1) / TAIL_GROUPS) * wins * (c / 4);
   if (items > (long)TAIL_KMAX * TAIL_THREADS) return false;
   if ((long)n * (ways + 2) > 2L * TAIL_THREADS) return false;                 // the folding workgroup takes the row scalars two per thread
-  return tail_lds_bytes(n, feat, ways, 1) <= 150 * 1024;
+  return tail_lds_bytes(n, feat, ways, 1) <= TAIL_LDS_CAP;
 }
+size_t tail_lds_bytes_host(int n, int feat, int ways, int tangent) { return tail_lds_bytes(n, feat, ways, tangent); }
 size_t tail_wpart_floats(int tasks, int feat, int ways) { return (size_t)tasks * TAIL_GROUPS * ways * feat; }
 size_t tail_bpart_doubles(int tasks, int c) { return (size_t)tasks * TAIL_GROUPS * 2 * c; }
 size_t tail_scr_floats(int tasks, int n, int ways) { return (size_t)tasks * TAIL_GROUPS * ((n + TAIL_GROUPS - 1) / TAIL_GROUPS) * (ways + 2); }
@@ -635,7 +638,8 @@ static hipError_t tail_launch(K kern, hipStream_t st, const TailArgs& t, int tas
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
     if (!(*attr_done & (1u << (dev & 31)))) {
-      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
+      // (raised to the cap, not to this launch's request: the attribute is set once, and a later launch of the same kernel may ask for more)
+      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_CAP); e != hipSuccess) return e;
       *attr_done |= 1u << (dev & 31);
     }
   }

@@ -40,7 +40,11 @@ typedef struct {
   int32_t in_channels, in_h, in_w;
   int32_t hidden;         /* filters per block (32 or 64) */
   int32_t max_pool;       /* 1: stride-1 conv + MaxPool2d(2,2,floor); 0: stride-2 conv, no pooling (vision_models.py:157-165) */
-  int32_t ways;           /* classifier outputs */
+  int32_t ways;           /* classifier outputs, 1..64.  The head's gradient launch keeps a task's dlogits [n, ways] in LDS (n = rows per task,
+                           * ways * shots in the meta-batch calls): first-order passes take n * ways <= 39424 (160 KiB of LDS: 5 ways n <= 7884,
+                           * 8 ways 4928, 20 ways 1971, 64 ways 616), Hessian-vector (tangent) passes n * ways <= 19712 (5 ways n <= 3942, 8 ways
+                           * 2464, 20 ways 985, 64 ways 308); a call beyond that returns MI_ERR_ARG naming n, ways and the bytes, and launches
+                           * no head kernel */
   int32_t head_mean_pool; /* 1: x.mean(dim=[2,3]) then Linear(hidden,ways) (:53-54); 0: view(-1, hw*hidden) then Linear (:109) */
 } mi_model_desc;
 
@@ -351,6 +355,44 @@ int mi_head_fwd_bwd(void* stream, const float* f, const float* wl, const float* 
                     int tasks, int n, int feat, int ways, float* loss, float* acc, float* logits, float* prob, float* dl,
                     float* dwl, float* dbl, size_t gstride, float* df);
 size_t mi_kernel_scratch_bytes(int tasks, int n, int h, int w, int c);
+/* The head's backward alone, from given dlogits dl [tasks, n, ways]: dwl, dbl, df (may be NULL). */
+int mi_head_grads(void* stream, const float* f, const float* wl, size_t pstride, const float* dl, int tasks, int n, int feat,
+                  int ways, float* dwl, float* dbl, size_t gstride, float* df);
+/* Tangent (R-operator) of the head along the direction (wld, bld) [+ the feature tangent fd, may be NULL]:
+ *   ld = fd wl^T + f wld^T + bld (-> ld_out, may be NULL);  R{dl} = prob * (ld - sum(prob * ld)) / n  (-> rdl; fixed_dl != 0: dl is a given
+ *   cotangent, R{dl} = 0 and prob is not read);  dwl = R{dl}^T f + dl^T fd,  dbl = sum_n R{dl},  df (may be NULL) = R{dl} wl + dl wld. */
+int mi_head_tangent(void* stream, const float* f, const float* fd, const float* wl, const float* bl, size_t pstride,
+                    const float* wld, const float* bld, size_t vstride, const float* prob, const float* dl, float* rdl,
+                    float* ld_out, int fixed_dl, int tasks, int n, int feat, int ways, float* dwl, float* dbl, size_t gstride,
+                    float* df);
+/* OmniglotCNN's x.mean(dim=[2,3]): p [rows, hw, c] -> f [rows, c], and its backward df -> dp = df / hw at every position. */
+int mi_spatial_mean(void* stream, const float* p, float* f, int rows, int hw, int c);
+int mi_spatial_mean_bwd(void* stream, const float* df, float* dp, int rows, int hw, int c);
+
+/* The one-launch tail of a pass (csrc/tail.hip): the last block's BatchNorm + ReLU + MaxPool, the head with loss and accuracy, the head's
+ * backward and that block's BatchNorm-backward sums -- tangent != 0: their tangents.  mi_tail_supported: the shapes the kernel takes
+ * (feat = hp * wp * c); mi_tail_lds_bytes: the dynamic LDS of a launch (the tangent kernel's is held to 150 KiB).
+ * All per-task vectors of theta / the direction / the gradients advance by pstride / vstride / gstride floats, multiples of 4.
+ * Scratch (mi_tail_scratch_bytes) starts with `tasks` 32-bit arrival counters that the CALLER zeroes once; every launch leaves them at zero. */
+typedef struct {
+  const float *z, *zd;                  /* conv output [tasks, n, ho, wo, c] and (tangent) its tangent */
+  const float *mu, *rstd, *m1, *m2;     /* [tasks, c]; m1, m2 tangent only */
+  const float *gamma, *beta, *wl, *bl; size_t pstride;          /* BatchNorm and head parameters */
+  const float *gammad, *betad, *wld, *bld; size_t vstride;      /* the direction's (tangent) */
+  const int32_t* y;                     /* [tasks, n] labels (primal) */
+  const float *f, *dp;                  /* tangent: the primal pass's pooled output and its cotangent (= the primal df) */
+  float *prob, *dl;                     /* [tasks, n, ways]: written by the primal pass, read by the tangent pass */
+  float *pooled;                        /* [tasks, n, hp, wp, c]: p (tangent: its tangent) */
+  float *loss, *acc, *logits;           /* primal: [tasks], [tasks], [tasks, n, ways] (logits may be NULL) */
+  float *dwl, *dbl, *sum0, *sum1; size_t gstride;               /* head gradients, dgamma, dbeta (tangent: their tangents) */
+  float *df;                            /* [tasks, n, feat] */
+  int32_t tasks, n, ho, wo, c, pool, ways;
+  int32_t with_grad, bwd_tasks;         /* primal: 0 = loss and accuracy only; tasks >= bwd_tasks stop after the loss */
+} mi_tail_args;
+int mi_tail_supported(int n, int ho, int wo, int c, int pool, int feat, int ways);
+size_t mi_tail_lds_bytes(int n, int feat, int ways, int tangent);
+size_t mi_tail_scratch_bytes(int tasks, int n, int ho, int wo, int c, int pool, int ways);
+int mi_tail_run(void* stream, const mi_tail_args* a, int tangent, void* scratch, size_t scratch_bytes);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Tangent (R-operator) and fused block-1 kernels: unit-test entry points (tests/test_gpu_tangent_kernels.py).  They are the

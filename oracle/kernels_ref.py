@@ -181,11 +181,11 @@ def bn_bwd(z, mu, r, gamma, beta, dp, pool):
     return dgamma, dbeta, dz
 
 
-def bn_tangent_fwd(z, zd, mu, r, gamma, beta, gammad, betad, pool):
-    """-> pd, (m1, m2)."""
+def bn_tangent_fwd(z, zd, mu, r, gamma, beta, gammad, betad, pool, m=None):
+    """-> pd, (m1, m2).  m = (m1, m2): take the tangent statistics as given (the kernels read them as fp32 inputs)."""
     _, zh, sel = _route(z, mu, r, gamma, beta, pool)
-    m1 = zd.mean(dim=(0, 1, 2))
-    m2 = (zh * zd).mean(dim=(0, 1, 2))
+    m1 = zd.mean(dim=(0, 1, 2)) if m is None else m[0]
+    m2 = (zh * zd).mean(dim=(0, 1, 2)) if m is None else m[1]
     zhd = r * (zd - m1 - zh * m2)
     ud = gammad * zh + gamma * zhd + betad
     ad = ud * sel
@@ -244,6 +244,57 @@ def head_tangent(f, fd, wl, bl, wld, bld, prob, dl):
     probd = prob * (ld - (prob * ld).sum(dim=1, keepdim=True))
     rdl = probd / n
     return rdl.t() @ f + dl.t() @ fd, rdl.sum(dim=0), rdl @ wl + dl @ wld
+
+
+def head_logit_tangent(f, fd, wl, wld, bld):
+    """ld = fd wl^T + f wld^T + bld (fd None: no feature tangent)."""
+    ld = f @ wld.t() + bld
+    return ld if fd is None else ld + fd @ wl.t()
+
+
+def head_rdl(prob, ld):
+    """R{dl} of the mean cross-entropy: prob * (ld - sum(prob * ld)) / n."""
+    return prob * (ld - (prob * ld).sum(dim=1, keepdim=True)) / prob.shape[0]
+
+
+def head_tangent_fixed_dl(f, fd, wl, wld, bld, dl):
+    """Tangent of the head's backward for a GIVEN cotangent dl (R{dl} = 0).  -> ld, R{dwl}, R{dbl}, R{df}."""
+    ld = head_logit_tangent(f, fd, wl, wld, bld)
+    rdwl = torch.zeros_like(wl) if fd is None else dl.t() @ fd
+    return ld, rdwl, torch.zeros_like(bld), dl @ wld
+
+
+def spatial_mean(p):
+    """p [rows, hw, c] -> [rows, c]."""
+    return p.mean(dim=1)
+
+
+def spatial_mean_bwd(df, hw):
+    """df [rows, c] -> dp [rows, hw, c]."""
+    return (df / hw)[:, None, :].expand(df.shape[0], hw, df.shape[1]).contiguous()
+
+
+# ------------------------------------------------------------------------------------------ the tail of a pass (tail.hip)
+def tail_ref(z, mu, r, gamma, beta, wl, bl, y, pool):
+    """Last block's BN + ReLU + pool, flattened head with loss / accuracy, the head's backward and that block's BatchNorm-backward sums."""
+    p = bn_relu_pool_fwd(z, mu, r, gamma, beta, pool)
+    f = p.reshape(p.shape[0], -1)
+    loss, acc, logits, prob, dl, dwl, dbl, df = head_fwd_bwd(f, wl, bl, y)
+    dgamma, dbeta, _ = bn_bwd(z, mu, r, gamma, beta, df.reshape(p.shape), pool)
+    return dict(p=p, loss=loss, acc=acc, logits=logits, prob=prob, dl=dl, dwl=dwl, dbl=dbl, df=df, dgamma=dgamma, dbeta=dbeta)
+
+
+def tail_tangent_ref(z, zd, mu, r, m1, m2, gamma, beta, gammad, betad, wl, bl, wld, bld, f, prob, dl, dp, pool):
+    """Tangent of ``tail_ref`` along (gammad, betad, wld, bld) and the conv-output tangent zd; f, prob, dl, dp: what the primal pass stored
+    (pooled features, softmax, dlogits, cotangent of p); m1, m2: the tangent statistics as the kernels receive them."""
+    pd, _ = bn_tangent_fwd(z, zd, mu, r, gamma, beta, gammad, betad, pool, m=(m1, m2))
+    fd = pd.reshape(pd.shape[0], -1)
+    ld = head_logit_tangent(f, fd, wl, wld, bld)
+    rdwl, rdbl, rdf = head_tangent(f, fd, wl, bl, wld, bld, prob, dl)
+    zero = torch.zeros_like(gamma)          # (R{dgamma}, R{dbeta} do not depend on the primal sums; only R{dz} does)
+    rdgamma, rdbeta, _ = bn_tangent_bwd(z, zd, mu, r, m1, m2, gamma, beta, gammad, betad, dp.reshape(pd.shape), rdf.reshape(pd.shape),
+                                        zero, zero, pool)
+    return dict(pd=pd, ld=ld, rdl=head_rdl(prob, ld), rdwl=rdwl, rdbl=rdbl, rdf=rdf, rdgamma=rdgamma, rdbeta=rdbeta)
 
 
 # ------------------------------------------------------------------------------------------ whole-net passes
