@@ -173,6 +173,9 @@ _SIGS = {
     'mi_trpo_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     'mi_policy_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_size_t]),
+    'mi_particles_rollout_scratch_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    'mi_particles_rollout': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
+                                       C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_size_t]),
     'mi_policy_adapt': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     'mi_trpo_surrogate': (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,

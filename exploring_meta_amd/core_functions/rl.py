@@ -388,9 +388,13 @@ def _replay_on_device(ep, baseline, gamma, tau, S, A, dev, normalize=True, updat
     return dict(states=b['states'], actions=b['actions'], adv=adv, count=b['count'], done=b['dones'])
 
 
-def _gae_on_device(dev, S, rows):
+def _gae_max_rows(S):
     from ..engine import gae_max_rows
-    return torch.device(dev).type == 'cuda' and 0 < rows <= gae_max_rows(S)
+    return gae_max_rows(S)
+
+
+def _gae_on_device(dev, S, rows):
+    return torch.device(dev).type == 'cuda' and 0 < rows <= _gae_max_rows(S)
 
 
 def _pad(eps_list, advs, S, A, dev):
@@ -470,6 +474,97 @@ def fast_adapt_trpo(task, learner, baseline, params, anil=False, first_order=Fal
     query_rew = _as_replay(query_episodes)['rewards'].sum().item() / params['adapt_batch_size']                    # rl.py:403
     query_success_rate = get_ep_successes(query_episodes, params.get('max_path_length')) / params['adapt_batch_size']  # rl.py:404
     return learner, valid_loss, task_replay, query_rew, query_success_rate
+
+
+def _replay_rows(out, i, n):
+    """Task i of a padded device batch (PolicyEngine.rollout) as a ``Replay`` of its leading n rows: contiguous fp32 views, so
+    ``_device_batch_packed`` takes them as they lie."""
+    return Replay(states=out['states'][i, :n], actions=out['actions'][i, :n], rewards=out['rewards'][i, :n].unsqueeze(1),
+                  dones=out['dones'][i, :n].unsqueeze(1), next_states=out['next_states'][i, :n])
+
+
+def _rollout_theta(policies_or_theta, dev):
+    """(engine, theta [P] or [T, P]) from one policy (shared parameters), a sequence of policies (one per task), or a pair
+    (policy or PolicyEngine, theta tensor)."""
+    pt = policies_or_theta
+    if isinstance(pt, tuple) and len(pt) == 2 and torch.is_tensor(pt[1]):
+        eng = pt[0].engine() if hasattr(pt[0], 'engine') else pt[0]
+        return eng, pt[1].detach().to(dev, torch.float32)
+    if isinstance(pt, (list, tuple)):
+        pols = [_unwrap(q) for q in pt]
+        theta = _stacked_flat_parameters(pols, dev)
+        if theta is None:
+            theta = torch.stack([q.flat() for q in pols]).to(dev)
+        return pols[0].engine(), theta
+    pol = _unwrap(pt)
+    return pol.engine(), pol.flat()
+
+
+def rollout_tasks(policies_or_theta, goals, ids, seed, episodes, max_path_length, dev=None):
+    """``episodes`` Particles2D episodes for every task of a meta-batch through ONE mi_particles_rollout call and one read-back of the
+    tasks' row counts; returns the list of the tasks' ``Replay``s.  ``policies_or_theta``: one policy (every task acts with it), a
+    sequence of policies (one per task), or ``(policy or PolicyEngine, theta [P] | [tasks, P])``.  Task i's rollout is a pure
+    function of its parameters, ``goals[i]`` and ``(seed, ids[i])``."""
+    eng, theta = _rollout_theta(policies_or_theta, dev or device)
+    out = eng.rollout(theta, goals, ids, seed, episodes, max_path_length)
+    return [_replay_rows(out, i, n) for i, n in enumerate(out['count'].tolist())]
+
+
+def fast_adapt_trpo_tasks(goals, policy, baseline, params, seed, first_id, anil=False, first_order=False):
+    """``fast_adapt_trpo`` (reference rl.py:377-406) for ALL tasks of a meta-batch at once on device rollouts: per adapt step one
+    rollout call, one mi_gae_advantages launch and one mi_policy_adapt call over all tasks, then one query rollout with per-task
+    parameters.  Returns the list of the tasks' ``(learner, valid_loss, task_replay, query_rew, query_success_rate)``.  Task i's
+    run k (the support steps, then the query) uses rollout id ``first_id + i * (adapt_steps + 1) + k`` -- what task i gets from
+    ``fast_adapt_trpo`` with ``Particles2DRunner(goal, L, rollout='device', seed=seed, first_id=first_id + i * (adapt_steps + 1))``.
+    ``baseline`` is left as after that task-by-task walk: fitted to the last task's last support replay."""
+    from ..engine import gae_advantages
+    pol = _unwrap(policy)
+    eng, dev = pol.engine(), pol.sigma.device
+    goals = np.asarray(goals, dtype=np.float32).reshape(-1, 2)
+    T, K, E, L = goals.shape[0], params['adapt_steps'], params['adapt_batch_size'], params['max_path_length']
+    S, A = pol.input_size, pol.output_size
+    if not _gae_on_device(dev, S, E * L):
+        raise ValueError(f'fast_adapt_trpo_tasks keeps replays of {E} x {L} rows on the device; mi_gae_advantages takes at most '
+                         f'{_gae_max_rows(S)} rows')
+    gamma, tau = params['gamma'], params['tau']
+    if anil:                                                   # rl.py:381-382: the inner loop moves the head only
+        pol.turn_off_body_grads()
+    head_only = bool(getattr(pol, 'features_no_grad', False))
+    if anil:                                                   # rl.py:395-396
+        pol.turn_on_body_grads()
+    theta, wts = pol.flat(), None
+    replays = [[] for _ in range(T)]
+    for k in range(K + 1):
+        out = eng.rollout(theta, goals, [first_id + i * (K + 1) + k for i in range(T)], seed, E, L)
+        counts = out['count'].tolist()                         # (the one synchronisation of the step)
+        for i, n in enumerate(counts):
+            replays[i].append(_replay_rows(out, i, n))
+        if k == K:
+            break
+        adv, wts = gae_advantages(out['states'], out['next_states'], out['rewards'], out['dones'], out['count'], gamma, tau, baseline.reg,
+                                  normalize=True, want_weights=True)
+        theta, _ = eng.adapt(theta, out['states'], out['actions'], adv, out['count'], params['inner_lr'], head_only=head_only)
+    # the query replay's loss with each task's own baseline, as fitted to its last support replay (update_vf=False, rl.py:401)
+    if wts is None:
+        wts = torch.from_numpy(np.ascontiguousarray(baseline.weight)).reshape(1, -1).repeat(T, 1)
+    else:
+        baseline._weight_dev = wts[-1]
+    adv = gae_advantages(out['states'], out['next_states'], out['rewards'], out['dones'], out['count'], gamma, tau, baseline.reg,
+                         normalize=True, weights=wts)
+    thetas = theta if theta.dim() == 2 else theta.unsqueeze(0).expand(T, -1)
+    loc = eng.forward(theta, out['states'])
+    scale = torch.exp(torch.clamp(thetas[:, :A], min=float(np.log(1e-6))))
+    query_rew = (out['rewards'].sum(dim=1) / E).tolist()
+    results = []
+    for i, n in enumerate(counts):
+        learner = deepcopy(pol)
+        learner.load_flat(thetas[i].contiguous())
+        # trpo_a2c_loss's own expressions on the task's rows (rl.py:346-358)
+        lp = torch.distributions.Normal(loc=loc[i, :n], scale=scale[i]).log_prob(out['actions'][i, :n]).mean(dim=1, keepdim=True)
+        valid_loss = -(lp * adv[i, :n].reshape(-1, 1)).mean()
+        suc = get_ep_successes(replays[i][-1], params.get('max_path_length')) / E
+        results.append((learner, valid_loss, replays[i], query_rew[i], suc))
+    return results
 
 
 class _SurrogateContext:
@@ -878,17 +973,31 @@ def evaluate_trpo(env, policy, baseline, eval_params, anil=False, render=False, 
     return evaluate('trpo', env, policy, baseline, eval_params, anil, render, generator, goals)
 
 
-# ---------------------------------------------------------------------------------------------- Particles2D rollouts (host loop, device math)
+# ---------------------------------------------------------------------------------------------- Particles2D rollouts
 class Particles2DRunner:
-    """Minimal stand-in for core_functions/runner.py + learn2learn's Particles2D (both out of scope):
-    all ``episodes`` of a task advance in lock-step on the device; ``run`` returns a replay dict with episodes concatenated."""
+    """Minimal stand-in for core_functions/runner.py + learn2learn's Particles2D (both out of scope); ``run``
+    returns a replay dict with episodes concatenated.  ``rollout='host'`` (default; host loop, device math): all ``episodes`` of a
+    task advance in lock-step on the device, one step per pass of a Python loop, the noise from ``generator``.  ``rollout='device'``:
+    the whole run is one mi_particles_rollout call and one read-back of the row count; the n-th ``run`` of
+    this runner draws its noise from ``(seed, first_id + n)``, the generator is not used."""
 
-    def __init__(self, goal, max_path_length, generator=None, dev=None):
+    def __init__(self, goal, max_path_length, generator=None, dev=None, rollout='host', seed=0, first_id=0):
         self.dev = dev or device
         self.goal = torch.as_tensor(goal, dtype=torch.float32, device=self.dev)
         self.max_path_length, self.generator = max_path_length, generator
+        if rollout not in ('host', 'device'):
+            raise ValueError("rollout must be 'host' or 'device'")
+        self.rollout, self.seed, self.first_id, self.runs = rollout, int(seed), int(first_id), 0
+
+    def _run_device(self, policy, episodes):
+        pol = _unwrap(policy)
+        out = pol.engine().rollout(pol.flat(), self.goal.reshape(1, 2), [self.first_id + self.runs], self.seed, episodes, self.max_path_length)
+        self.runs += 1
+        return _replay_rows(out, 0, int(out['count'].item()))
 
     def run(self, policy, episodes):
+        if self.rollout == 'device':
+            return self._run_device(policy, episodes)
         E, L = episodes, self.max_path_length
         state = torch.zeros(E, 2, device=self.dev)
         active = torch.ones(E, dtype=torch.bool, device=self.dev)
@@ -940,8 +1049,8 @@ class Particles2DEnv:
         diff = self.state - self.goal
         return self.state.copy(), -float(np.sqrt((diff * diff).sum())), bool((np.abs(diff) < 0.01).all()), {}
 
-    def runner(self, max_path_length, generator=None, dev=None):
-        return Particles2DRunner(self.goal, max_path_length, generator, dev)
+    def runner(self, max_path_length, generator=None, dev=None, rollout='host', seed=0, first_id=0):
+        return Particles2DRunner(self.goal, max_path_length, generator, dev, rollout, seed, first_id)
 
 
 class EnvRunner:

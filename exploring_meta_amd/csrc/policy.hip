@@ -37,7 +37,7 @@ struct DenseArgs {
   int B, I, O, nterms;
   int act;               // forward: activation applied to the output (ACT_*); mask users: which phi' to form from h
 };
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
+#include "policy_handle.h"   // ACT_*, struct mi_policy
 // phi'(z) from the stored activation h = phi(z): ReLU -> [h > 0], tanh -> 1 - h^2
 __device__ __forceinline__ float act_gate(float s, float h, int act) {
   return act == ACT_TANH ? s * (1.f - h * h) : (h > 0.f ? s : 0.f);
@@ -364,23 +364,13 @@ __global__ void mean_tasks_kernel(const float* __restrict__ x, int tasks, int p,
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-struct mi_policy {
-  mi_policy_desc d;
-  int device;
-  int S, A, H1, H2;
-  int act;   // ACT_RELU / ACT_TANH between the dense layers (policies.py:32-37,76)
-  size_t o_sigma, o_w1, o_b1, o_w2, o_b2, o_w3, o_b3, P;
-  std::string err;
-  unsigned* fold_counters = nullptr;   // device, one per 256-parameter block: arrival counters of the fold that also takes the mean over tasks
-  bool fold_dirty = false;             // a counted fold was issued and not seen to launch cleanly: re-zero the counters before the next one
-                                       // (policy_sweep.h FoldArgs::counter; zero between launches).  Allocated at the first fused product.
-};
 static thread_local std::string g_perr;
-static int pfail(mi_policy* p, int code, const std::string& m) {
+int mi_policy_fail(mi_policy* p, int code, const std::string& m) {
   if (p) p->err = m;
   g_perr = m;
   return code;
 }
+static int pfail(mi_policy* p, int code, const std::string& m) { return mi_policy_fail(p, code, m); }
 #define PCHK(p, call)                                                                                 \
   do {                                                                                                \
     hipError_t _s = (call);                                                                           \

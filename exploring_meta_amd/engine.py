@@ -453,6 +453,11 @@ def upload_int32(values, dev):
     return out
 
 
+def _as_i32(u):
+    """An unsigned 32-bit value as the int32 with the same bits."""
+    return u - (1 << 32) if u >= (1 << 31) else u
+
+
 def flatten_parameters(module):
     """Flat fp32 vector in module.parameters() order (what the C ABI calls theta)."""
     return torch.cat([p.detach().reshape(-1) for p in module.parameters()]).float().contiguous()
@@ -510,6 +515,54 @@ class PolicyEngine:
         self._check(self.lib.mi_policy_forward(self._h, _stream(self.device), _ptr(theta.contiguous()), stride, _ptr(states.contiguous()), T, B,
                                                _ptr(loc), _ptr(ws), ws.numel()))
         return loc
+
+    @_on_device
+    def rollout(self, theta, goals, rollout_ids, seed, episodes, max_path_length, want_noise=False):
+        """mi_particles_rollout: ``episodes`` Particles2D episodes of up to ``max_path_length`` steps for every task, two launches in
+        all and no synchronisation.  theta [P] (shared) or [T, P]; goals [T, 2] (tensor or array); rollout_ids: T integers in
+        [0, 2^64) or an int64 device tensor holding their bit patterns; the noise is a pure function of (seed, id, episode, step).
+        Returns the padded batch {states, actions, next_states [T, B, 2], rewards, dones [T, B], count [T] int32, ep_len [T, E]
+        int32} with B = episodes * max_path_length, rows past count zero (+ noise [T, B, 2] with ``want_noise``)."""
+        dev, f32 = self.device, torch.float32
+        if torch.is_tensor(goals):
+            goals = goals.detach().to(dev, f32).reshape(-1, 2).contiguous()
+        else:
+            import numpy as np
+            g = np.ascontiguousarray(goals, dtype=np.float32).reshape(-1, 2)
+            goals = upload_int32(g.view(np.int32).reshape(-1).tolist(), dev).view(f32).view(-1, 2)
+        T, E, L = goals.shape[0], int(episodes), int(max_path_length)
+        if torch.is_tensor(rollout_ids):
+            ids = rollout_ids.to(dev, torch.int64).reshape(-1).contiguous()
+        else:                                                  # the 64-bit ids as pairs of 32-bit halves, carried in kernel arguments
+            halves = []
+            for r in rollout_ids:
+                r = int(r) & (2 ** 64 - 1)
+                halves += [_as_i32(r & 0xffffffff), _as_i32(r >> 32)]
+            ids = upload_int32(halves, dev).view(torch.int64)
+        if ids.numel() != T:
+            raise ValueError(f'{ids.numel()} rollout ids for {T} goals')
+        theta = theta.detach()
+        if theta.dtype != f32 or not theta.is_cuda or theta.dim() not in (1, 2) or theta.shape[-1] != self.param_count or \
+                (theta.dim() == 2 and theta.shape[0] != T):
+            raise ValueError(f'theta must be fp32 on the GPU, [P] or [{T}, P] with P={self.param_count}, got {tuple(theta.shape)}')
+        theta = theta.contiguous()
+        stride = 0 if theta.dim() == 1 else self.param_count
+        nb = int(self.lib.mi_particles_rollout_scratch_bytes(self._h, T, E, L))
+        ws = getattr(self, '_rollout_ws', None)
+        if nb and (ws is None or ws.numel() < nb):
+            ws = self._rollout_ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        B = max(E * L, 0)
+        out = dict(states=torch.empty(T, B, 2, dtype=f32, device=dev), actions=torch.empty(T, B, 2, dtype=f32, device=dev),
+                   next_states=torch.empty(T, B, 2, dtype=f32, device=dev), rewards=torch.empty(T, B, dtype=f32, device=dev),
+                   dones=torch.empty(T, B, dtype=f32, device=dev), count=torch.empty(T, dtype=torch.int32, device=dev),
+                   ep_len=torch.empty(T, max(E, 0), dtype=torch.int32, device=dev))
+        if want_noise:
+            out['noise'] = torch.empty(T, B, 2, dtype=f32, device=dev)
+        self._check(self.lib.mi_particles_rollout(
+            self._h, _stream(dev), _ptr(theta), stride, _ptr(goals), _ptr(ids), int(seed) & (2 ** 64 - 1), T, E, L, _ptr(out['states']),
+            _ptr(out['actions']), _ptr(out['next_states']), _ptr(out['rewards']), _ptr(out['dones']), _ptr(out['count']),
+            _ptr(out['ep_len']), _ptr(out.get('noise')), _ptr(ws), ws.numel() if ws is not None else 0))
+        return out
 
     @_on_device
     def adapt(self, theta, states, actions, adv, count, lr, head_only=False):

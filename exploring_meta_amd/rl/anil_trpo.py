@@ -3,7 +3,7 @@
 ``fast_adapt_trpo(..., anil=True, first_order=True)`` with the body under no_grad during the inner updates, and
 ``meta_optimize_trpo(..., anil=True)`` -- whose KL Hessian-vector product is exact for new != old (mi_trpo_fvp_general).
 
-    python -m exploring_meta_amd.rl.anil_trpo --meta_batch_size 20 --num_iterations 5
+    python -m exploring_meta_amd.rl.anil_trpo --meta_batch_size 20 --num_iterations 5 [--rollout device]
 """
 import argparse
 
@@ -13,15 +13,16 @@ from .maml_trpo import params as _maml_params, run as _run
 params = dict(_maml_params, inner_lr=0.01, outer_lr=0.1, fc_neurons=100)
 
 
-def run(p, log=print):
-    return _run(p, log=log, anil=True)
+def run(p, log=print, rollout=None):
+    return _run(p, log=log, anil=True, rollout=rollout)
 
 
 if __name__ == '__main__':
     parser = argparse.ArgumentParser(description='ANIL-TRPO on Particles2D (MI355X engine)')
     for k, v in params.items():
         parser.add_argument(f'--{k}', type=type(v), default=v)
+    parser.add_argument('--rollout', choices=('host', 'device'), default='host', help='see maml_trpo')
     args = parser.parse_args()
     for k in params:
         params[k] = getattr(args, k)
-    run(params)
+    run(params, rollout=args.rollout)

@@ -8,7 +8,7 @@ parameters; per iteration and task ``learner = policy.clone()`` -> ``fast_adapt_
 second-order gradient through the ``ppo_epochs`` clipped-surrogate updates comes out of one fused call per task
 (mi_policy_meta_batch).  Under torchrun the task list is sharded over ranks and the gradients are all-reduced (RCCL).
 
-    python -m exploring_meta_amd.rl.maml_ppo --meta_batch_size 20 --num_iterations 5 [--anil]
+    python -m exploring_meta_amd.rl.maml_ppo --meta_batch_size 20 --num_iterations 5 [--anil] [--rollout device]
 """
 import argparse
 import os
@@ -26,7 +26,10 @@ params = {
 }
 
 
-def run(p, anil=False, log=print):
+def run(p, anil=False, log=print, rollout=None):
+    rollout = rollout or p.get('rollout', 'host')
+    if rollout not in ('host', 'device'):
+        raise ValueError("rollout must be 'host' or 'device'")
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (('WORLD_SIZE', '1'), ('RANK', '0'), ('LOCAL_RANK', '0')))
     torch.cuda.set_device(local)
     if world > 1:
@@ -46,9 +49,11 @@ def run(p, anil=False, log=print):
         meta_optimizer.zero_grad()
         goals = rng.uniform(-0.5, 0.5, size=(T, 2))                           # env.sample_tasks: identical on every rank
         iter_reward, iter_loss = 0.0, 0.0
-        for goal in goals[lo:hi]:
+        runs = p['adapt_steps'] + 1
+        for g, goal in enumerate(goals[lo:hi], start=lo):
             learner = policy.clone()
-            task = Particles2DRunner(goal, p['max_path_length'], gen, dev)
+            # rollout='device': task g of iteration `it` owns the ids (it * T + g) * runs .. + runs - 1 at any world size
+            task = Particles2DRunner(goal, p['max_path_length'], gen, dev, rollout=rollout, seed=p['seed'], first_id=(it * T + g) * runs)
             eval_loss, task_rew, _ = fast_adapt_ppo(task, learner, baseline, p, anil=anil)
             iter_reward += task_rew
             iter_loss = iter_loss + eval_loss
@@ -75,7 +80,9 @@ if __name__ == '__main__':
     for k, v in params.items():
         parser.add_argument(f'--{k}', type=type(v), default=v)
     parser.add_argument('--anil', action='store_true')
+    parser.add_argument('--rollout', choices=('host', 'device'), default='host',
+                        help='host: Python loop over the steps, torch-generator noise; device: one mi_particles_rollout call per run of a task')
     args = parser.parse_args()
     for k in params:
         params[k] = getattr(args, k)
-    run(params, anil=args.anil)
+    run(params, anil=args.anil, rollout=args.rollout)

@@ -7,7 +7,13 @@ Same structure (rl/maml_trpo.py:82-134): per iteration sample ``meta_batch_size`
 the cherry Runner are replaced by ``Particles2DRunner``.  With torchrun the task list is sharded over ranks and the meta
 optimisation's means are completed by small all-reduces (core_functions/rl.py::_SurrogateContext._allmean).
 
-    python -m exploring_meta_amd.rl.maml_trpo --meta_batch_size 20 --num_iterations 5
+    python -m exploring_meta_amd.rl.maml_trpo --meta_batch_size 20 --num_iterations 5 [--rollout device]
+
+``--rollout device`` rolls the episodes out on the device (mi_particles_rollout) for all tasks of the rank at
+once through ``fast_adapt_trpo_tasks``.  Iteration ``it``, task ``g`` of the meta-batch, run ``k`` (support steps, then the query) draws
+its noise from ``(seed, (it * meta_batch_size + g) * (adapt_steps + 1) + k)``: every rank takes its slice of one global id range, so a
+run is reproducible from (seed, iteration, task) at any world size.  The default, ``host``, is the host-loop runner with the torch
+generator.
 """
 import argparse
 import os
@@ -18,7 +24,7 @@ import numpy as np
 import torch
 
 from ..core_functions import (DiagNormalPolicy, DiagNormalPolicyANIL, LinearValue, Particles2DRunner, fast_adapt_trpo, meta_optimize_trpo,
-                              set_device)
+                              fast_adapt_trpo_tasks, set_device)
 from ..sharding import init_process_group, shard_range
 
 params = {
@@ -28,7 +34,10 @@ params = {
 }
 
 
-def run(p, log=print, anil=False):
+def run(p, log=print, anil=False, rollout=None):
+    rollout = rollout or p.get('rollout', 'host')
+    if rollout not in ('host', 'device'):
+        raise ValueError("rollout must be 'host' or 'device'")
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (('WORLD_SIZE', '1'), ('RANK', '0'), ('LOCAL_RANK', '0')))
     torch.cuda.set_device(local)
     if world > 1:
@@ -45,7 +54,14 @@ def run(p, log=print, anil=False):
     for it in range(p['num_iterations']):
         goals = rng.uniform(-0.5, 0.5, size=(p['meta_batch_size'], 2))        # env.sample_tasks: identical on every rank
         iter_replays, iter_policies, iter_reward, iter_loss = [], [], 0.0, 0.0
-        for goal in goals[lo:hi]:
+        if rollout == 'device':
+            runs = p['adapt_steps'] + 1
+            results = fast_adapt_trpo_tasks(goals[lo:hi], policy, baseline, p, p['seed'], (it * p['meta_batch_size'] + lo) * runs,
+                                            anil=anil, first_order=True)
+            iter_policies, iter_replays = [r[0] for r in results], [r[2] for r in results]
+            iter_reward = sum(r[3] for r in results)
+            iter_loss = sum(torch.stack([r[1].reshape(()) for r in results]).tolist())        # (one read-back for all tasks)
+        for goal in (goals[lo:hi] if rollout == 'host' else ()):
             learner = deepcopy(policy)
             task = Particles2DRunner(goal, p['max_path_length'], gen, dev)
             learner, eval_loss, task_replay, task_rew, _ = fast_adapt_trpo(task, learner, baseline, p, anil=anil, first_order=True)
@@ -67,7 +83,9 @@ if __name__ == '__main__':
     for k, v in params.items():
         parser.add_argument(f'--{k}', type=type(v), default=v)
     parser.add_argument('--anil', action='store_true', help='ANIL-TRPO (reference rl/anil_trpo.py): DiagNormalPolicyANIL, head-only inner loop')
+    parser.add_argument('--rollout', choices=('host', 'device'), default='host',
+                        help='host: Python loop over the steps, torch-generator noise; device: one mi_particles_rollout call per adapt step')
     args = parser.parse_args()
     for k in params:
         params[k] = getattr(args, k)
-    run(params, anil=args.anil)
+    run(params, anil=args.anil, rollout=args.rollout)

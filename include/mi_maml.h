@@ -498,6 +498,30 @@ int mi_trpo_workspace_bytes(const mi_policy* p, int tasks, int batch, size_t* by
 /* density(state).loc (policies.py:49-52) for acting; theta shared (tstride 0) or one vector per task (tstride = P). */
 int mi_policy_forward(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states, int tasks, int batch,
                       float* loc_out, void* workspace, size_t workspace_bytes);
+
+/* Particles2D episodes on the device (rollout.hip): what Particles2DRunner.run does with a host loop of
+ * max_path_length steps (reference core_functions/runner.py + learn2learn's Particles2D), for `episodes` episodes of each of `tasks`
+ * tasks in two launches -- whatever `tasks` is -- and with no host synchronisation.  Per episode, in fp32: s_0 = 0,
+ * scale = exp(max(sigma, log 1e-6)); for t = 0 .. L-1: loc = MLP(s_t), a = loc + scale * eps_t (stored UNclipped),
+ * s_{t+1} = s_t + clamp(a, -0.1, 0.1), reward = -|s_{t+1} - goal|_2, done = both |s_{t+1} - goal| < 0.01, stored dones = done or
+ * t == L-1; the episode's rows are steps 0 .. t_done.  The noise is a pure function of (seed, rollout id, episode, step):
+ * Philox4x32-10, key = seed, counter = (id_lo, id_hi, episode, step); u1 = ((w0 >> 8) + 1) 2^-24, u2 = (w1 >> 8) 2^-24,
+ * r = sqrt(-2 log u1), eps = (r cos 2 pi u2, r sin 2 pi u2) (exploring_meta_amd.utils.rollout_ref restates it in numpy).  A task's
+ * result depends on its own theta, goal and id alone: not on `tasks`, on the other tasks of the call, or on tstride.
+ *   theta        shared (tstride 0) or one vector per task (tstride = P), the parameter order above
+ *   goals        [tasks, 2];  rollout_ids [tasks] uint64, DEVICE memory
+ *   states, actions, next_states [tasks, B, 2], rewards, dones [tasks, B], B = episodes * max_path_length (8-byte aligned): the
+ *                episodes of a task concatenated in episode order, every row past count[t] zero in all fields -- the padded batch
+ *                mi_gae_advantages and mi_policy_adapt take
+ *   count [tasks] rows in use;  ep_len [tasks, episodes] or NULL;  noise_out [tasks, B, 2] or NULL: eps of each packed row
+ * state_size == action_size == 2, 1 <= hidden1, hidden2 <= 128, ReLU or tanh, tasks >= 1 (tasks * episodes < 2^31),
+ * 1 <= episodes <= 256, 1 <= max_path_length <= 1000 (MI_ERR_ARG naming the value otherwise, before any HIP call; the scratch size
+ * is 0 then).  Results are bitwise reproducible. */
+size_t mi_particles_rollout_scratch_bytes(const mi_policy* p, int tasks, int episodes, int max_path_length);
+int mi_particles_rollout(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* goals,
+                         const uint64_t* rollout_ids, uint64_t seed, int tasks, int episodes, int max_path_length,
+                         float* states, float* actions, float* next_states, float* rewards, float* dones,
+                         int32_t* count, int32_t* ep_len, float* noise_out, void* scratch, size_t scratch_bytes);
 /* trpo_update (rl.py:361-374): theta_out[t] = theta[t] - lr * grad_t( a2c.policy_loss = -mean(log_prob * advantages) ).
  * head_only != 0: the hidden layers run under no_grad (DiagNormalPolicyANIL.turn_off_body_grads, policies.py:100-106,
  * rl.py:381-382), so only sigma and the last Linear are updated (learn2learn maml_update skips None gradients). */

@@ -1,0 +1,256 @@
+"""mi_particles_rollout on the GPU: the noise against its numpy restatement, the exact structure of the packed
+replay re-derived from the device's own outputs, every step teacher-forced against the fp64 oracle (tests/rollout_oracle.py),
+termination and packing on hand-made policies, bitwise independence of the tasks of a call, and the layers above it -- the device
+mode of Particles2DRunner, fast_adapt_trpo_tasks against the task-by-task walk, and the maml_trpo driver.
+Replaces (reference): core_functions/runner.py + learn2learn's Particles2D, whose rollouts the reference steps on the host."""
+from copy import deepcopy
+
+import numpy as np
+import pytest
+import torch
+
+import rollout_oracle as O
+from exploring_meta_amd import core_functions as cf
+from exploring_meta_amd.core_functions import rl as RLM
+from exploring_meta_amd.engine import PolicyEngine
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ('states', 'actions', 'next_states', 'rewards', 'dones')
+_engines = {}
+
+
+def _engine(hiddens, activation='relu'):
+    key = (tuple(hiddens), activation)
+    if key not in _engines:
+        _engines[key] = PolicyEngine(2, 2, tuple(hiddens), 'cuda', activation=activation)
+    return _engines[key]
+
+
+def _rollout(eng, theta, goals, ids, seed, E, L):
+    """numpy arrays of one engine call (theta [P] shared or [T, P])."""
+    th = torch.from_numpy(np.ascontiguousarray(theta, dtype=np.float32)).cuda()
+    out = eng.rollout(th, np.asarray(goals, dtype=np.float32), ids, seed, E, L, want_noise=True)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def _check_structure(out, goals, E, L):
+    """Everything that can be re-derived exactly, in numpy fp32, from the device's own outputs."""
+    goals = np.asarray(goals, dtype=np.float32).reshape(-1, 2)
+    f32 = np.float32
+    for t in range(goals.shape[0]):
+        n, lens = int(out['count'][t]), out['ep_len'][t].astype(np.int64)
+        assert n == lens.sum() and (lens >= 1).all() and (lens <= L).all()
+        st, ac, ns, dn = out['states'][t], out['actions'][t], out['next_states'][t], out['dones'][t]
+        for k in FIELDS + ('noise',):                                      # every row past count is zero in all fields
+            assert not out[k][t, n:].any(), k
+        first = np.concatenate([[0], np.cumsum(lens)[:-1]])
+        last = np.cumsum(lens) - 1
+        assert not st[first].any()                                         # s_0 = 0
+        inner = np.setdiff1d(np.arange(n), last)
+        assert np.array_equal(st[inner + 1].view(np.uint32), ns[inner].view(np.uint32))       # s_{t+1} is the next row's state, bitwise
+        step = (st[:n] + np.clip(ac[:n], f32(-0.1), f32(0.1))).astype(f32)
+        assert np.array_equal(step.view(np.uint32), ns[:n].view(np.uint32))
+        want_done = np.zeros(n, dtype=f32)
+        want_done[last] = 1.0
+        assert np.array_equal(dn[:n], want_done)
+        at_goal = (np.abs(ns[:n] - goals[t]) < f32(0.01)).all(axis=1)       # fp32 compare on the device's values
+        for a, b in zip(first, last):
+            hits = np.flatnonzero(at_goal[a:b + 1])
+            assert (hits.size and hits[0] == b - a) or (not hits.size and b - a == L - 1), (t, a, b, hits)
+
+
+# ---------------------------------------------------------------------------------------------------- 1. noise
+def test_noise_matches_the_numpy_restatement():
+    """|delta| <= 1e-5: |eps| <= 5.77, the fp32 argument 2 pi u2 <= 6.28 carries <= 4e-7 of rounding, few-ulp logf / sqrtf / cosf
+    on top: <= ~3e-6.  More means the wrong word, stream or mapping.  The constant policy walks away from the goal, so all L steps run."""
+    T, E, L, seed, ids = 2, 3, 5, 0x1234567890abcdef, [7, 2 ** 63 + 2 ** 32 + 1]
+    out = _rollout(_engine((3, 5)), O.constant_theta(), [[-0.4, -0.4], [-0.3, -0.4]], ids, seed, E, L)
+    assert out['ep_len'].tolist() == [[L] * E] * T
+    want = np.asarray([[O.noise(seed, rid, e, t) for e in range(E) for t in range(L)] for rid in ids])
+    err = np.abs(out['noise'].astype(np.float64) - want).max()
+    print(f'noise: max |delta| {err:.2e}')
+    assert err <= 1e-5
+
+
+# ---------------------------------------------------------------------------------------------------- 2 + 3. structure, teacher forcing
+CASES = {'relu100': ((100, 100), 'relu'), 'tanh100': ((100, 100), 'tanh'), 'tiny3x5': ((3, 5), 'relu'), 'limit128': ((128, 128), 'tanh')}
+
+
+@pytest.mark.parametrize('name', list(CASES))
+def test_every_row_matches_the_fp64_oracle_from_the_device_state(name):
+    """From the device's states[r] and noise[r]: |actions - (loc64 + scale64 eps)| <= 3e-6 max(1, |ref|) (the forward's bar against the
+    fp64 golden is 2e-6, plus one fp32 multiply-add rounding for the noise term); rewards to 1e-6 relative (two products, an add,
+    a square root).  No tolerance covers accumulation over the steps: every row starts from the device's own state."""
+    hiddens, act = CASES[name]
+    T, E, L, seed, ids = 3, 3, 14, 99, [5, 6, 2 ** 33]
+    goals = np.asarray([[0.03, -0.02], [0.3, -0.45], [-0.2, 0.25]], dtype=np.float32)
+    theta = np.stack([O.default_theta(hiddens, act, 10 + t) for t in range(T)])        # per-task parameters
+    out = _rollout(_engine(hiddens, act), theta, goals, ids, seed, E, L)
+    _check_structure(out, goals, E, L)
+    worst_a = worst_r = 0.0
+    for t in range(T):
+        n = int(out['count'][t])
+        loc, scale = O.loc_scale(theta[t], hiddens, act, out['states'][t, :n])
+        ref = loc + scale * out['noise'][t, :n].astype(np.float64)
+        worst_a = max(worst_a, float((np.abs(out['actions'][t, :n] - ref) / np.maximum(1.0, np.abs(ref))).max()))
+        d = out['next_states'][t, :n].astype(np.float64) - goals[t].astype(np.float64)
+        rref = -np.sqrt((d * d).sum(axis=1))
+        worst_r = max(worst_r, float((np.abs(out['rewards'][t, :n] - rref) / np.abs(rref)).max()))
+    print(f'{name}: rows {out["count"].tolist()}, actions {worst_a:.2e} (bar 3e-6), rewards {worst_r:.2e} (bar 1e-6)')
+    assert worst_a <= 3e-6 and worst_r <= 1e-6
+
+
+# ---------------------------------------------------------------------------------------------------- 4. termination and packing
+def test_homing_policy_gives_ragged_episodes_and_different_counts():
+    case = O.HOMING
+    theta = np.stack([O.homing_theta(g) for g in case['goals']])
+    out = _rollout(_engine(O.HOMING_HIDDENS), theta, case['goals'], case['ids'], case['seed'], case['episodes'], case['L'])
+    _check_structure(out, case['goals'], case['episodes'], case['L'])
+    print('device episode lengths', out['ep_len'].tolist())
+    assert len(set(out['ep_len'][0].tolist())) >= 3 and len(set(out['count'].tolist())) == 3
+    assert (out['ep_len'] == case['L']).any() and (out['ep_len'] < case['L']).any()
+    # the oracle's endings keep 9e-5 from the edge of the goal box (test_rollout_host.py): fp32 rounding cannot move them
+    assert out['ep_len'].tolist() == [r['ep_len'].tolist() for r in O.homing_rollouts()]
+
+
+def test_constant_policy_ends_after_exactly_four_rows_and_one_row():
+    case = O.CONSTANT
+    out = _rollout(_engine((3, 5)), O.constant_theta(), case['goals'], case['ids'], case['seed'], case['episodes'], case['L'])
+    _check_structure(out, case['goals'], case['episodes'], case['L'])
+    assert out['ep_len'].tolist() == [[r] * case['episodes'] for r in case['rows']]
+    assert out['count'].tolist() == [r * case['episodes'] for r in case['rows']]
+
+
+def test_one_episode_of_one_step_and_episodes_cut_by_the_cap():
+    case = O.CONSTANT
+    eng = _engine((3, 5))
+    out = _rollout(eng, O.constant_theta(), case['goals'], case['ids'], case['seed'], 1, 1)
+    _check_structure(out, case['goals'], 1, 1)
+    assert out['count'].tolist() == [1, 1] and out['dones'].tolist() == [[1.0], [1.0]]
+    out = _rollout(eng, O.constant_theta(), case['goals'][:1], case['ids'][:1], case['seed'], 4, 3)      # 4 steps needed, 3 allowed
+    _check_structure(out, case['goals'][:1], 4, 3)
+    assert out['ep_len'].tolist() == [[3] * 4] and out['dones'][0].tolist() == [0.0, 0.0, 1.0] * 4
+
+
+# ---------------------------------------------------------------------------------------------------- 5. independence
+def _same(a, b, rows=slice(None)):
+    return all(np.array_equal(a[k][rows].view(np.uint32), b[k][rows].view(np.uint32)) for k in FIELDS + ('noise', 'count', 'ep_len'))
+
+
+def test_a_task_depends_on_nothing_else_in_the_launch():
+    hiddens, E, L, seed, ids = (100, 100), 3, 10, 21, [40, 41, 2 ** 50]
+    eng = _engine(hiddens)
+    goals = np.asarray([[0.02, 0.03], [0.3, 0.1], [-0.25, 0.4]], dtype=np.float32)
+    theta = O.default_theta(hiddens, 'relu', 3)
+    both = _rollout(eng, theta, goals, ids, seed, E, L)
+    for t in range(3):                                                     # a T = 3 call equals three T = 1 calls
+        one = _rollout(eng, theta, goals[t:t + 1], ids[t:t + 1], seed, E, L)
+        assert _same({k: v[t:t + 1] for k, v in both.items()}, one), t
+    assert _same(both, _rollout(eng, np.stack([theta] * 3), goals, ids, seed, E, L))     # shared theta = the same theta per task
+    perm = [2, 0, 1]
+    shuffled = _rollout(eng, theta, goals[perm], [ids[i] for i in perm], seed, E, L)
+    assert _same({k: v[perm] for k, v in both.items()}, shuffled)         # permuting the tasks permutes the outputs
+    assert _same(both, _rollout(eng, theta, goals, ids, seed, E, L))      # the same (seed, id) twice: identical bytes
+    other = _rollout(eng, theta, goals, [ids[0] + 1] + ids[1:], seed, E, L)
+    assert not np.array_equal(other['noise'][0], both['noise'][0]) and _same(both, other, slice(1, 3))
+    assert not np.array_equal(_rollout(eng, theta, goals, ids, seed + 1, E, L)['noise'], both['noise'])
+
+
+# ---------------------------------------------------------------------------------------------------- 6. runner
+PARAMS = dict(inner_lr=0.1, max_path_length=12, adapt_steps=1, adapt_batch_size=4, gamma=0.99, tau=1.0)
+
+
+def _policy(seed=0, sigma=0.1):
+    torch.manual_seed(seed)
+    pol = cf.DiagNormalPolicy(2, 2).cuda()
+    with torch.no_grad():
+        pol.sigma.fill_(float(np.log(sigma)))
+    return pol
+
+
+def test_device_runner():
+    pol, goal, E, L = _policy(), [0.02, -0.03], 4, 12
+    runner = cf.Particles2DRunner(goal, L, rollout='device', seed=5, first_id=100)
+    replays = [runner.run(pol, E) for _ in range(3)]
+    for n_run, rep in enumerate(replays):                                  # the n-th run uses id first_id + n
+        direct = pol.engine().rollout(pol.flat(), np.asarray([goal], dtype=np.float32), [100 + n_run], 5, E, L)
+        n = int(direct['count'].item())
+        assert rep['states'].shape == (n, 2) and rep['rewards'].shape == (n, 1) and rep['dones'].shape == (n, 1)
+        for k in FIELDS:
+            assert torch.equal(rep[k].reshape(-1), direct[k][0, :n].reshape(-1)), k
+        assert rep['dones'].sum().item() == E
+    assert not torch.equal(replays[0]['actions'][:4], replays[1]['actions'][:4])
+    rep = replays[0]
+    n = rep['states'].shape[0]
+    assert RLM._device_batch_packed([rep], [n], n, 2, 2, rep['states'].device) is not None       # views of the padded buffers: the fast path
+    baseline = cf.LinearValue(2, 2)
+    new = cf.trpo_update(rep, pol, baseline, 0.1, 0.99, 1.0)
+    loss = cf.trpo_a2c_loss(replays[1], new, baseline, 0.99, 1.0, update_vf=False)
+    assert torch.isfinite(loss) and torch.isfinite(new.flat()).all() and not torch.equal(new.flat(), pol.flat())
+
+
+def test_default_runner_is_the_host_loop_with_the_callers_generator():
+    pol = _policy()
+    runs = []
+    for s in (3, 3, 4):
+        runner = cf.Particles2DRunner([0.2, -0.3], 6, torch.Generator(device='cuda').manual_seed(s))
+        assert runner.rollout == 'host'
+        runs.append(runner.run(pol, 3))
+    assert all(torch.equal(runs[0][k], runs[1][k]) for k in FIELDS) and not torch.equal(runs[0]['actions'], runs[2]['actions'])
+    with pytest.raises(ValueError):
+        cf.Particles2DRunner([0.0, 0.0], 6, rollout='gpu')
+
+
+def test_rollout_tasks_equals_the_per_task_runners():
+    pol, goals, E, L = _policy(), [[0.02, -0.03], [0.3, 0.2]], 3, 8
+    reps = cf.rollout_tasks(pol, goals, [9, 10], 77, E, L)
+    for goal, rid, rep in zip(goals, [9, 10], reps):
+        one = cf.Particles2DRunner(goal, L, rollout='device', seed=77, first_id=rid).run(pol, E)
+        assert all(torch.equal(rep[k], one[k]) for k in FIELDS)
+    per_task = cf.rollout_tasks([pol, pol], goals, [9, 10], 77, E, L)
+    assert all(torch.equal(a[k], b[k]) for a, b in zip(reps, per_task) for k in FIELDS)
+
+
+# ---------------------------------------------------------------------------------------------------- 7. fast_adapt_trpo_tasks
+@pytest.mark.parametrize('steps', [1, 2])
+def test_fast_adapt_trpo_tasks_equals_the_task_by_task_walk(steps):
+    """Replays bit-identical; adapted parameters and valid_loss to rtol 1e-5 (the same kernels, only the task batching differs);
+    query_rew to fp32 rounding; the baseline ends with the same weights."""
+    params = dict(PARAMS, adapt_steps=steps)
+    pol, seed, first_id = _policy(1), 31, 1000
+    goals = [[0.02, -0.03], [0.3, -0.2], [-0.4, 0.1]]
+    base_a, base_b = cf.LinearValue(2, 2), cf.LinearValue(2, 2)
+    batched = cf.fast_adapt_trpo_tasks(goals, pol, base_a, params, seed, first_id, first_order=True)
+    assert len(batched) == 3
+    for i, (goal, got) in enumerate(zip(goals, batched)):
+        runner = cf.Particles2DRunner(goal, params['max_path_length'], rollout='device', seed=seed, first_id=first_id + i * (steps + 1))
+        learner, loss, replay, rew, suc = cf.fast_adapt_trpo(runner, deepcopy(pol), base_b, params, first_order=True)
+        assert len(got[2]) == len(replay) == steps + 1
+        for k_run, (a, b) in enumerate(zip(got[2], replay)):
+            for k in FIELDS:
+                assert a[k].shape == b[k].shape and torch.equal(a[k], b[k]), (i, k_run, k)
+        ta, tb = got[0].flat().cpu().numpy(), learner.flat().cpu().numpy()
+        print(f'steps {steps} task {i}: max |dtheta| {np.abs(ta - tb).max():.2e}, loss {float(got[1]):.7f} / {float(loss):.7f}, '
+              f'reward {got[3]:.6f} / {rew:.6f}')
+        np.testing.assert_allclose(ta, tb, rtol=1e-5, atol=0)
+        np.testing.assert_allclose(float(got[1]), float(loss), rtol=1e-5, atol=0)
+        assert abs(got[3] - rew) <= 1e-6 * abs(rew) and got[4] == suc
+        assert not np.array_equal(ta, pol.flat().cpu().numpy())
+    np.testing.assert_array_equal(base_a.weight, base_b.weight)
+
+
+# ---------------------------------------------------------------------------------------------------- 8. driver
+def test_maml_trpo_driver_with_device_rollouts_is_reproducible():
+    from exploring_meta_amd.rl import maml_trpo
+    p = dict(maml_trpo.params, num_iterations=2, meta_batch_size=3, adapt_batch_size=4, max_path_length=12, seed=13)
+    logs = []
+    for _ in range(2):
+        lines = []
+        policy = maml_trpo.run(p, log=lines.append, rollout='device')
+        assert len(lines) == 2 and torch.isfinite(policy.flat()).all()
+        assert all('nan' not in ln and 'inf' not in ln for ln in lines), lines
+        logs.append(lines)
+    print(logs[0])
+    assert logs[0] == logs[1]
