@@ -7,4 +7,4 @@ from .policies import DiagNormalPolicy, DiagNormalPolicyANIL
 from .rl import (fast_adapt_trpo, meta_optimize_trpo, meta_surrogate_loss, trpo_update, trpo_a2c_loss, fast_adapt_vpg, fast_adapt_ppo,
                  evaluate_vpg, evaluate_ppo, evaluate_trpo,
                  compute_advantages, set_device, LinearValue, Particles2DRunner, Particles2DEnv, EnvRunner, get_ep_successes,
-                 rollout_tasks, fast_adapt_trpo_tasks)
+                 rollout_tasks, fast_adapt_trpo_tasks, fast_adapt_vpg_tasks, fast_adapt_ppo_tasks, single_ppo_update, AdaptedTasks)

@@ -904,6 +904,124 @@ def fast_adapt_ppo(task, learner, baseline, params, anil=False, render=False):
     return _adapt_and_validate(task, learner, baseline, params, 'ppo', anil, False)
 
 
+def single_ppo_update(episodes, learner, baseline, params, anil=False):
+    """reference rl.py:319-336: ONE clipped-surrogate update of the learner on ``episodes`` (normalised advantages, the baseline
+    re-fitted, old log-probabilities at the learner's current parameters) through mi_policy_update with tasks = 1.  The learner's
+    parameters are updated in place -- step size ``learner.lr`` (the MAML wrapper's, as ``learner.adapt`` uses it) or
+    ``params['inner_lr']`` -- and the loss before the update is returned.  As in ``trpo_update``, ``anil`` only allows unused
+    parameters (rl.py:335); whether the body moves is the policy's own switch (``turn_off_body_grads``)."""
+    episodes = _as_replay(episodes)
+    pol = _unwrap(learner)
+    S, A, dev = pol.input_size, pol.output_size, pol.sigma.device
+    gamma, tau = params['gamma'], params['tau']
+    if _gae_on_device(dev, S, int(episodes['states'].shape[0])):
+        b = _replay_on_device(episodes, baseline, gamma, tau, S, A, dev)
+    else:
+        b = _pad([episodes], [_advantages(episodes, baseline, gamma, tau)], S, A, dev)
+    lr = learner.lr if isinstance(getattr(learner, 'lr', None), (int, float)) else params['inner_lr']
+    theta, loss = pol.engine().update(pol.flat(), b['states'], b['actions'], b['adv'], b['count'], lr, loss='ppo', epochs=1,
+                                      clip=params.get('ppo_clip_ratio', 0.1), head_only=bool(getattr(pol, 'features_no_grad', False)))
+    pol.load_flat(theta[0].contiguous())
+    return loss[0, 0]
+
+
+class AdaptedTasks:
+    """What ``fast_adapt_vpg_tasks`` / ``fast_adapt_ppo_tasks`` return for the T tasks of a call: ``total_loss`` (0-dim, the sum of
+    the validation losses; ``.backward()`` accumulates the summed meta-gradient), ``valid_loss [T]``, ``reward [T]``, ``success [T]``,
+    ``theta [T, P]`` (the adapted parameters the query was rolled out with) and ``replays`` (per task the adapt_steps + 1 ``Replay``
+    views, or None)."""
+    __slots__ = ('total_loss', 'valid_loss', 'reward', 'success', 'theta', 'replays')
+
+    def __init__(self, total_loss, valid_loss, reward, success, theta, replays):
+        self.total_loss, self.valid_loss, self.reward, self.success = total_loss, valid_loss, reward, success
+        self.theta, self.replays = theta, replays
+
+
+def _task_rollout_ids(first_id, tasks, adapt_steps, stride=None):
+    """ids[k][i]: the rollout id of run k (support steps, then the query) of task i: ``first_id + i * stride + k``,
+    stride = adapt_steps + 1 unless the caller reserves further runs per task."""
+    stride = adapt_steps + 1 if stride is None else stride
+    return [[first_id + i * stride + k for i in range(tasks)] for k in range(adapt_steps + 1)]
+
+
+def _adapt_tasks(goals, policy, baseline, params, seed, first_id, algo, anil, first_order, dice, want_replays, stride=None):
+    from ..engine import gae_advantages, upload_int32, _as_i32
+    pol = _unwrap(policy)
+    eng, dev = pol.engine(), pol.sigma.device
+    goals = np.ascontiguousarray(np.asarray(goals, dtype=np.float32).reshape(-1, 2))
+    T, K, E, L = goals.shape[0], params['adapt_steps'], params['adapt_batch_size'], params['max_path_length']
+    S, A = pol.input_size, pol.output_size
+    name = 'fast_adapt_ppo_tasks' if algo == 'ppo' else 'fast_adapt_vpg_tasks'
+    if T < 1:
+        raise ValueError(f'{name}: no goals')
+    if not _gae_on_device(dev, S, E * L):
+        raise ValueError(f'{name} keeps replays of {E} x {L} rows on the device; mi_gae_advantages takes at most '
+                         f'{_gae_max_rows(S)} rows')
+    gamma, tau, lr = params['gamma'], params['tau'], params['inner_lr']
+    epochs = params['ppo_epochs'] if algo == 'ppo' else 1
+    clip = params.get('ppo_clip_ratio', 0.1)
+    kind = 'ppo' if algo == 'ppo' else ('dice' if dice else 'a2c')
+    # goals and the ids of all (K + 1) x T runs travel once, in kernel arguments (no pageable copy, no synchronisation)
+    goals_dev = upload_int32(goals.view(np.int32).reshape(-1).tolist(), dev).view(torch.float32).view(T, 2)
+    halves = []
+    for row in _task_rollout_ids(int(first_id), T, K, stride):
+        for r in row:
+            r &= 2 ** 64 - 1
+            halves += [_as_i32(r & 0xffffffff), _as_i32(r >> 32)]
+    ids = upload_int32(halves, dev).view(torch.int64).view(K + 1, T)
+    theta0 = pol.flat()
+    theta, sups = theta0, []
+    replays = [[] for _ in range(T)] if want_replays else None
+    for k in range(K + 1):
+        out = eng.rollout(theta, goals_dev, ids[k], seed, E, L)
+        if want_replays:                                       # (the one synchronisation of the run)
+            for i, n in enumerate(out['count'].tolist()):
+                replays[i].append(_replay_rows(out, i, n))
+        # always fitted, the query included (_adapt_and_validate); vpg_a2c_loss does not normalise (rl.py:217)
+        adv, wts = gae_advantages(out['states'], out['next_states'], out['rewards'], out['dones'], out['count'], gamma, tau, baseline.reg,
+                                  normalize=(algo == 'ppo'), want_weights=True)
+        batch = dict(states=out['states'], actions=out['actions'], adv=adv, count=out['count'], done=out['dones'])
+        if k == K:
+            break
+        sups.append(batch)
+        theta, _ = eng.update(theta, out['states'], out['actions'], adv, out['count'], lr, loss=kind, epochs=epochs, clip=clip,
+                              done=out['dones'] if kind == 'dice' else None, head_only=bool(anil))
+    baseline._weight_dev = wts[-1]                             # as after the task-by-task walk: the last task's query replay
+    sup = {key: torch.stack([b[key] for b in sups]) for key in ('states', 'actions', 'adv', 'count', 'done')} if K else None
+    step_batch = [b for b in range(K) for _ in range(epochs)]
+    need = torch.is_grad_enabled() and any(q.requires_grad for q in pol.parameters())
+    lt, _, grad = eng.meta_batch(theta0, sup, batch, step_batch, lr, loss=kind, clip=clip, head_only=bool(anil), first_order=first_order,
+                                 with_grad=need)
+    total = lt.sum()
+    if need:
+        eparams = pol._engine_params()
+        total = _PolicyMetaLoss.apply(total, grad, [q.shape for q in eparams], *eparams)
+    thetas = theta if theta.dim() == 2 else theta.unsqueeze(0).expand(T, -1)
+    reward = out['rewards'].sum(dim=1) / E
+    # the device rollout records no success signal: what get_ep_successes counts for such replays (rl.py:69-71)
+    success = torch.zeros(T, device=dev)
+    return AdaptedTasks(total, lt, reward, success, thetas, replays)
+
+
+def fast_adapt_vpg_tasks(goals, policy, baseline, params, seed, first_id, anil=False, first_order=False, dice=False, want_replays=True):
+    """``fast_adapt_vpg`` (reference rl.py:231-255) for ALL tasks of a meta-batch at once on device rollouts.  Per adapt step: one
+    rollout call with the tasks' current parameters, one mi_gae_advantages launch (not normalised) and one mi_policy_update call
+    over all tasks; then the query rollout, its advantages, and ONE mi_policy_meta_batch call from the shared parameters over all
+    support batches and the query, which returns the validation losses and the meta-gradient summed over tasks.  Task i's run k
+    uses rollout id ``first_id + i * (adapt_steps + 1) + k`` -- what it gets from ``fast_adapt_vpg`` with
+    ``Particles2DRunner(goal, L, rollout='device', seed=seed, first_id=first_id + i * (adapt_steps + 1))``.  Returns an
+    ``AdaptedTasks`` record.  With ``want_replays=False`` nothing is read back from the device during the call; otherwise the row
+    counts are read once per rollout.  ``baseline`` is left as after the task-by-task walk: fitted to the last task's query replay."""
+    return _adapt_tasks(goals, policy, baseline, params, seed, first_id, 'vpg', anil, first_order, dice, want_replays)
+
+
+def fast_adapt_ppo_tasks(goals, policy, baseline, params, seed, first_id, anil=False, want_replays=True):
+    """``fast_adapt_ppo`` (reference rl.py:267-318) for ALL tasks of a meta-batch at once: as ``fast_adapt_vpg_tasks`` with normalised
+    advantages and ``ppo_epochs`` clipped-surrogate updates per adapt step in one mi_policy_update call (old log-probabilities
+    taken once per step, at the parameters the step starts from); second order, as ``learner.adapt`` defaults."""
+    return _adapt_tasks(goals, policy, baseline, params, seed, first_id, 'ppo', anil, False, False, want_replays)
+
+
 def _eval_tasks(env, params, goals):
     """The evaluation tasks and a runner factory for them.  ``env`` as the reference passes it (rl.py:142-196: an environment NAME handed to
     make_env, whose result offers ``sample_tasks / set_task / reset``): 'Particles2D-v1' (or any name containing 'Particles2D') builds this
@@ -925,11 +1043,38 @@ def _eval_tasks(env, params, goals):
     return env, tasks
 
 
-def evaluate(algo, env, policy, baseline, params, anil=False, render=False, generator=None, goals=None):
+def _evaluate_device(algo, env, tasks, policy, baseline, params, anil, seed, first_id):
+    """evaluate() with every run on the device and all tasks per call: task i owns the rollout ids ``first_id + i * (adapt_steps + 2)
+    + k``, k = 0 .. adapt_steps for the adaptation (support steps, query) and adapt_steps + 1 for the final episodes -- the ids of
+    ``Particles2DRunner(goal, L, rollout='device', seed=seed, first_id=first_id + i * (adapt_steps + 2))`` walked as below."""
+    if not isinstance(env, Particles2DEnv):
+        raise NotImplementedError("evaluate(rollout='device') rolls out Particles2D; other environments take the host loop")
+    if algo not in ('vpg', 'ppo'):
+        raise NotImplementedError("evaluate(rollout='device') adapts with 'vpg' or 'ppo' (fast_adapt_vpg_tasks / fast_adapt_ppo_tasks)")
+    goals = np.asarray([t['goal'] for t in tasks], dtype=np.float32).reshape(-1, 2)
+    K, E, L = params['adapt_steps'], params['adapt_batch_size'], params['max_path_length']
+    with torch.no_grad():                                      # (fast_adapt_ppo is called without anil in evaluate, as below)
+        res = _adapt_tasks(goals, policy, baseline, params, seed, first_id, algo, anil and algo == 'vpg', False, False, False, stride=K + 2)
+    eng = _unwrap(policy).engine()
+    out = eng.rollout(res.theta.contiguous(), goals, [first_id + i * (K + 2) + K + 1 for i in range(len(tasks))], seed, E, L)
+    return (out['rewards'].sum(dim=1) / E).tolist(), [0.0] * len(tasks)
+
+
+def evaluate(algo, env, policy, baseline, params, anil=False, render=False, generator=None, goals=None, rollout='host', first_id=0):
     """reference rl.py:142-196: adapt a copy of the policy to every evaluation task with `algo` in {'vpg', 'ppo', 'trpo'}, then roll out
     `adapt_batch_size` query episodes with the adapted policy.  ``env``: see ``_eval_tasks`` (name, env-like, or the task goals).
+    ``rollout='device'`` ('vpg' / 'ppo' on Particles2D): all tasks are adapted and rolled out together through the batched
+    functions, noise from ``(params['seed'], first_id + ...)`` (``_evaluate_device``); the default is the task-by-task host walk.
     Returns (tasks_rewards, mean reward, mean success rate)."""
+    if rollout not in ('host', 'device'):
+        raise ValueError("rollout must be 'host' or 'device'")
     env, tasks = _eval_tasks(env, params, goals)
+    if rollout == 'device':
+        tasks_rewards, tasks_success = _evaluate_device(algo, env, tasks, policy, baseline, params, anil, params.get('seed', 42), first_id)
+        n = params.get('n_tasks', len(tasks_rewards))
+        if isinstance(n, str):
+            n = len(tasks_rewards)
+        return tasks_rewards, sum(tasks_rewards) / n, sum(tasks_success) / n
     dev = _unwrap(policy).sigma.device
     tasks_rewards, tasks_success = [], []
     for task_desc in tasks:

@@ -1147,6 +1147,35 @@ extern "C" int mi_policy_meta_workspace_bytes(const mi_policy* p, int tasks, int
   return MI_OK;
 }
 
+// One primal pass of the VPG / PPO / DiCE losses for all tasks at per-task parameters th [T][P]: forward, loss + cotangents
+// (gauss2_kernel), backward into g [T][P].  Shared by mi_policy_meta_batch and mi_policy_update: same launches, same order.
+static int meta_primal(mi_policy* p, hipStream_t st, int T, int B, float clip, StepSet& s, const float* th, const float* states,
+                       const float* actions, const float* adv, const int32_t* count, int kind, const float* oldlp, int value_ratio_one,
+                       float* g, float* loss, const float* done) {
+  const size_t P = p->P, TP = (size_t)T * P;
+  int rc = mlp_forward(p, st, T, B, states, th, P, s.a);
+  if (rc) return rc;
+  PCHK(p, hipMemsetAsync(g, 0, TP * sizeof(float), st));
+  Gauss2Args ga{};
+  ga.mu = s.a.mu; ga.rho = th + p->o_sigma; ga.rstride = P; ga.act = actions; ga.adv = adv; ga.count = count; ga.oldlp = oldlp;
+  ga.coef = s.coef; ga.coef2 = s.coef2; ga.dmu = s.dmu; ga.drho = g + p->o_sigma; ga.gstride = P; ga.loss = loss; ga.clip = clip;
+  ga.B = B; ga.A = p->A; ga.kind = kind; ga.mode = P_PRIMAL; ga.value_ratio_one = value_ratio_one; ga.done = done;
+  hipLaunchKernelGGL(gauss2_kernel, dim3(T), dim3(256), 0, st, ga);
+  PCHK(p, hipGetLastError());
+  return mlp_backward(p, st, T, B, states, th, P, s.a, s.dmu, s.d2, s.d1, g, s.pre2, s.pre1, false);
+}
+// old_log_probs = learner.log_prob(...) under no_grad (rl.py:282-283) at th [T][P] -> olp [T][B]
+static int meta_old_logp(mi_policy* p, hipStream_t st, int T, int B, StepSet& s, const float* th, const float* states,
+                         const float* actions, const int32_t* count, float* olp) {
+  int rc = mlp_forward(p, st, T, B, states, th, p->P, s.a);
+  if (rc) return rc;
+  Gauss2Args gl{};
+  gl.mu = s.a.mu; gl.rho = th + p->o_sigma; gl.rstride = p->P; gl.act = actions; gl.count = count; gl.lp_out = olp; gl.B = B; gl.A = p->A; gl.mode = P_LOGP;
+  hipLaunchKernelGGL(gauss2_kernel, dim3(T), dim3(256), 0, st, gl);
+  PCHK(p, hipGetLastError());
+  return MI_OK;
+}
+
 static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta, int steps, const int32_t* step_batch,
                                   const int32_t* step_new_old, int n_batches, const float* s_states, const float* s_actions,
                                   const float* s_adv, const int32_t* s_count, const float* s_done, const float* q_states,
@@ -1179,16 +1208,7 @@ static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta
   PCHK(p, hipGetLastError());
   auto primal = [&](StepSet& s, const float* th, const float* states, const float* actions, const float* adv, const int32_t* count,
                     int kind, const float* oldlp, int value_ratio_one, float* g, float* loss, const float* done) -> int {
-    int rc = mlp_forward(p, st, T, B, states, th, P, s.a);
-    if (rc) return rc;
-    PCHK(p, hipMemsetAsync(g, 0, TP * sizeof(float), st));
-    Gauss2Args ga{};
-    ga.mu = s.a.mu; ga.rho = th + p->o_sigma; ga.rstride = P; ga.act = actions; ga.adv = adv; ga.count = count; ga.oldlp = oldlp;
-    ga.coef = s.coef; ga.coef2 = s.coef2; ga.dmu = s.dmu; ga.drho = g + p->o_sigma; ga.gstride = P; ga.loss = loss; ga.clip = clip;
-    ga.B = B; ga.A = p->A; ga.kind = kind; ga.mode = P_PRIMAL; ga.value_ratio_one = value_ratio_one; ga.done = done;
-    hipLaunchKernelGGL(gauss2_kernel, dim3(T), dim3(256), 0, st, ga);
-    PCHK(p, hipGetLastError());
-    return mlp_backward(p, st, T, B, states, th, P, s.a, s.dmu, s.d2, s.d1, g, s.pre2, s.pre1, false);
+    return meta_primal(p, st, T, B, clip, s, th, states, actions, adv, count, kind, oldlp, value_ratio_one, g, loss, done);
   };
   // ---- inner updates
   for (int k = 0; k < K; ++k) {
@@ -1201,12 +1221,8 @@ static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta
     const int32_t* cn = s_count ? s_count + (size_t)bi * T : nullptr;
     float* olp = pl.oldlp + (size_t)bi * TB;
     if (loss_kind == MI_PLOSS_PPO && step_new_old[k]) {       // old_log_probs = learner.log_prob(...) under no_grad (rl.py:282-283)
-      int rc = mlp_forward(p, st, T, B, xs, th, P, s.a);
+      int rc = meta_old_logp(p, st, T, B, s, th, xs, as, cn, olp);
       if (rc) return rc;
-      Gauss2Args gl{};
-      gl.mu = s.a.mu; gl.rho = th + p->o_sigma; gl.rstride = P; gl.act = as; gl.count = cn; gl.lp_out = olp; gl.B = B; gl.A = p->A; gl.mode = P_LOGP;
-      hipLaunchKernelGGL(gauss2_kernel, dim3(T), dim3(256), 0, st, gl);
-      PCHK(p, hipGetLastError());
     }
     int rc = primal(s, th, xs, as, ad, cn, loss_kind, olp, 0, pl.g, pl.hv /* scratch for the step loss */,
                     s_done ? s_done + (size_t)bi * TB : nullptr);
@@ -1282,6 +1298,90 @@ extern "C" int mi_policy_meta_batch_dones(mi_policy* p, void* stream, const floa
   return policy_meta_batch_impl(p, stream, theta, steps, step_batch, step_new_old, n_batches, s_states, s_actions, s_adv, s_count, s_done,
                                 q_states, q_actions, q_adv, q_count, q_done, tasks, batch, loss_kind, clip, inner_lr, head_only,
                                 second_order, with_grad, loss_out, theta_out, grad_out, workspace, workspace_bytes);
+}
+
+// =====================================================================================================================
+// mi_policy_update: `epochs` plain (first-order) updates of per-task parameters on ONE replay per task -- the inner update of
+// fast_adapt_vpg / fast_adapt_ppo (rl.py:231-255,267-318) and single_ppo_update (rl.py:319-336) without the replay of the
+// earlier adapt steps mi_policy_meta_batch starts with.  Runs the passes of a first-order mi_policy_meta_batch step in the
+// same order (meta_old_logp, meta_primal, head mask, axpy), so from shared parameters theta_out is bit-identical to
+// mi_policy_meta_batch(steps = epochs, with_grad = 0).  theta_out itself is the working copy: u_e is updated in place.
+struct UpdatePlan { StepSet s; float *g, *loss_e, *oldlp; size_t bytes; };
+static void update_plan(const mi_policy* p, void* ws, int T, int B, int E, UpdatePlan& pl) {
+  PBump b{reinterpret_cast<char*>(ws), 0};
+  const size_t TB = (size_t)T * B, TP = (size_t)T * p->P;
+  StepSet& s = pl.s;
+  s.a.h1 = b.f(TB * p->H1); s.a.h2 = b.f(TB * p->H2); s.a.mu = b.f(TB * p->A);
+  s.dmu = b.f(TB * p->A); s.d2 = b.f(TB * p->H2); s.d1 = b.f(TB * p->H1); s.pre2 = b.f(TB * p->H2); s.pre1 = b.f(TB * p->H1);
+  s.coef = b.f(TB); s.coef2 = b.f(TB);
+  pl.g = b.f(TP); pl.loss_e = b.f((size_t)E * T); pl.oldlp = b.f(TB);
+  pl.bytes = align_up(b.off, 256);
+}
+// loss_e [E][T] (one row per gauss2 launch) -> loss_out [T][E]
+__global__ void update_loss_transpose_kernel(const float* __restrict__ in, int E, int T, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= E * T) return;
+  const int e = i / T, t = i % T;
+  out[(size_t)t * E + e] = in[i];
+}
+#define MI_UPDATE_MAX_EPOCHS 64
+static int update_args(mi_policy* p, int tasks, int batch, int epochs) {
+  if (!p) return pfail(nullptr, MI_ERR_ARG, "mi_policy_update: null policy handle");
+  if (tasks < 1) return pfail(p, MI_ERR_ARG, "mi_policy_update: tasks " + std::to_string(tasks) + " (must be >= 1)");
+  if (batch < 1) return pfail(p, MI_ERR_ARG, "mi_policy_update: batch " + std::to_string(batch) + " (must be >= 1)");
+  if (epochs < 1 || epochs > MI_UPDATE_MAX_EPOCHS)
+    return pfail(p, MI_ERR_ARG, "mi_policy_update: epochs " + std::to_string(epochs) + " (must be 1.." + std::to_string(MI_UPDATE_MAX_EPOCHS) + ")");
+  return MI_OK;
+}
+extern "C" int mi_policy_update_workspace_bytes(const mi_policy* p, int tasks, int batch, size_t* bytes) {
+  if (!p || !bytes || tasks < 1 || batch < 1) return MI_ERR_ARG;
+  UpdatePlan pl;
+  update_plan(p, nullptr, tasks, batch, MI_UPDATE_MAX_EPOCHS, pl);
+  *bytes = pl.bytes;
+  return MI_OK;
+}
+extern "C" int mi_policy_update(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
+                                const float* actions, const float* adv, const int32_t* count, const float* done, int tasks,
+                                int batch, int loss_kind, int epochs, float clip, float lr, int head_only, float* theta_out,
+                                float* loss_out, void* workspace, size_t workspace_bytes) {
+  int rc = update_args(p, tasks, batch, epochs);
+  if (rc) return rc;
+  if (!theta || !states || !actions || !adv || !theta_out || !workspace) return pfail(p, MI_ERR_ARG, "mi_policy_update: null argument");
+  if (loss_kind != MI_PLOSS_A2C && loss_kind != MI_PLOSS_PPO && loss_kind != MI_PLOSS_DICE)
+    return pfail(p, MI_ERR_ARG, "mi_policy_update: loss_kind " + std::to_string(loss_kind) + " (must be MI_PLOSS_A2C, MI_PLOSS_PPO or MI_PLOSS_DICE)");
+  if (loss_kind == MI_PLOSS_DICE && !done)
+    return pfail(p, MI_ERR_ARG, "mi_policy_update: loss_kind MI_PLOSS_DICE needs the episode-end flags (done is NULL)");
+  if (tstride != 0 && tstride != p->P)
+    return pfail(p, MI_ERR_ARG, "mi_policy_update: tstride " + std::to_string(tstride) + " (must be 0 or P = " + std::to_string(p->P) + ")");
+  if (tstride == 0 && tasks > 1 && theta == theta_out)
+    return pfail(p, MI_ERR_ARG, "mi_policy_update: theta_out may alias theta only with tstride = P");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int T = tasks, B = batch;
+  const size_t P = p->P;
+  UpdatePlan pl;
+  update_plan(p, workspace, T, B, epochs, pl);
+  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "mi_policy_update: workspace too small: need " + std::to_string(pl.bytes));
+  const dim3 pgrid(ceil_div((int)P, 256), T);
+  hipLaunchKernelGGL(axpy_bcast_kernel, pgrid, dim3(256), 0, st, theta, tstride, pl.g, 0.f, (int)P, theta_out);      // u_0
+  PCHK(p, hipGetLastError());
+  if (loss_kind == MI_PLOSS_PPO) {                            // old log-probs once, at u_0 (rl.py:280-290)
+    rc = meta_old_logp(p, st, T, B, pl.s, theta_out, states, actions, count, pl.oldlp);
+    if (rc) return rc;
+  }
+  for (int e = 0; e < epochs; ++e) {
+    rc = meta_primal(p, st, T, B, clip, pl.s, theta_out, states, actions, adv, count, loss_kind, pl.oldlp, 0, pl.g,
+                     pl.loss_e + (size_t)e * T, done);
+    if (rc) return rc;
+    if (head_only)
+      hipLaunchKernelGGL(head_mask_kernel, pgrid, dim3(256), 0, st, pl.g, (int)P, (int)p->o_w1, (int)p->o_w3);
+    hipLaunchKernelGGL(axpy_bcast_kernel, pgrid, dim3(256), 0, st, theta_out, P, pl.g, lr, (int)P, theta_out);   // in place, elementwise
+    PCHK(p, hipGetLastError());
+  }
+  if (loss_out) {
+    hipLaunchKernelGGL(update_loss_transpose_kernel, dim3(ceil_div(epochs * T, 256)), dim3(256), 0, st, pl.loss_e, epochs, T, loss_out);
+    PCHK(p, hipGetLastError());
+  }
+  return MI_OK;
 }
 
 // =====================================================================================================================

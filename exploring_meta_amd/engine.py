@@ -664,6 +664,34 @@ class PolicyEngine:
         return loss_t, theta_out, grad
 
     @_on_device
+    def update(self, theta, states, actions, adv, count, lr, loss='a2c', epochs=1, clip=0.1, done=None, head_only=False):
+        """mi_policy_update: ``epochs`` plain updates of every task's parameters on its own replay (the inner update of
+        fast_adapt_vpg / fast_adapt_ppo, reference rl.py:231-255,267-318; single_ppo_update, rl.py:319-336).  theta [P] (shared) or
+        [T, P]; states [T,B,S], actions [T,B,A], adv [T,B], count [T] int32 or None, done [T,B] (loss='dice').  PPO takes the old
+        log-probabilities once, at the parameters the call starts from.  Returns (theta_out [T, P], loss [T, epochs]: the loss
+        before each update).  No host synchronisation; the number of launches does not depend on T."""
+        T, B = states.shape[0], states.shape[1]
+        kind = {'a2c': 0, 'ppo': 1, 'dice': 2}[loss]
+        if loss == 'dice' and done is None:
+            raise ValueError("loss='dice' needs the episode-end flags of the replay (done [T, B], float32)")
+        b = C.c_size_t()
+        self._check(self.lib.mi_policy_update_workspace_bytes(self._h, T, B, C.byref(b)))
+        if self._ws is None or self._ws.numel() < b.value:
+            self._ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
+        theta = theta.detach()
+        if theta.dim() == 2 and theta.shape[0] != T:
+            raise ValueError(f'theta has {theta.shape[0]} rows for {T} tasks')
+        out = torch.empty(T, self.param_count, device=self.device)
+        losses = torch.empty(T, max(int(epochs), 1), device=self.device)
+        stride = 0 if theta.dim() == 1 else self.param_count
+        c = lambda t: None if t is None else t.contiguous()
+        theta, states, actions, adv, count, done = c(theta), c(states), c(actions), c(adv), c(count), c(done)
+        self._check(self.lib.mi_policy_update(self._h, _stream(self.device), _ptr(theta), stride, _ptr(states), _ptr(actions), _ptr(adv),
+                                              _ptr(count), _ptr(done), T, B, kind, int(epochs), float(clip), float(lr), int(head_only),
+                                              _ptr(out), _ptr(losses), _ptr(self._ws), self._ws.numel()))
+        return out, losses
+
+    @_on_device
     def kl_prepare(self, theta, sup, qry, old_loc, old_scale, inner_lr, want_grad=False):
         """After ``surrogate`` at the same theta: the context of the exact KL Hessian-vector product for new != old (ANIL-TRPO).
         Returns d mean KL / d theta [P] if ``want_grad``."""

@@ -8,7 +8,11 @@ parameters; per iteration and task ``learner = policy.clone()`` -> ``fast_adapt_
 second-order gradient through the ``ppo_epochs`` clipped-surrogate updates comes out of one fused call per task
 (mi_policy_meta_batch).  Under torchrun the task list is sharded over ranks and the gradients are all-reduced (RCCL).
 
-    python -m exploring_meta_amd.rl.maml_ppo --meta_batch_size 20 --num_iterations 5 [--anil] [--rollout device]
+With ``--rollout device --batch_tasks`` a rank adapts its whole slice of the tasks in one batched call
+(``fast_adapt_ppo_tasks``: per adapt step one rollout, one advantage launch and one mi_policy_update call over all tasks, then one
+mi_policy_meta_batch call for the losses and the summed gradient), with the rollout ids the task loop uses.
+
+    python -m exploring_meta_amd.rl.maml_ppo --meta_batch_size 20 --num_iterations 5 [--anil] [--rollout device [--batch_tasks]]
 """
 import argparse
 import os
@@ -17,7 +21,8 @@ import random
 import numpy as np
 import torch
 
-from ..core_functions import (MAML, DiagNormalPolicy, DiagNormalPolicyANIL, LinearValue, Particles2DRunner, fast_adapt_ppo, set_device)
+from ..core_functions import (MAML, DiagNormalPolicy, DiagNormalPolicyANIL, LinearValue, Particles2DRunner, fast_adapt_ppo,
+                              fast_adapt_ppo_tasks, set_device)
 from ..sharding import init_process_group, shard_range
 
 params = {
@@ -26,10 +31,12 @@ params = {
 }
 
 
-def run(p, anil=False, log=print, rollout=None):
+def run(p, anil=False, log=print, rollout=None, batch_tasks=False):
     rollout = rollout or p.get('rollout', 'host')
     if rollout not in ('host', 'device'):
         raise ValueError("rollout must be 'host' or 'device'")
+    if batch_tasks and rollout != 'device':
+        raise ValueError("batch_tasks adapts all tasks on device rollouts: it needs rollout='device'")
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (('WORLD_SIZE', '1'), ('RANK', '0'), ('LOCAL_RANK', '0')))
     torch.cuda.set_device(local)
     if world > 1:
@@ -50,7 +57,13 @@ def run(p, anil=False, log=print, rollout=None):
         goals = rng.uniform(-0.5, 0.5, size=(T, 2))                           # env.sample_tasks: identical on every rank
         iter_reward, iter_loss = 0.0, 0.0
         runs = p['adapt_steps'] + 1
-        for g, goal in enumerate(goals[lo:hi], start=lo):
+        if batch_tasks:
+            # the slice lo:hi in one call; task g keeps the ids (it * T + g) * runs .. + runs - 1 of the loop below
+            res = fast_adapt_ppo_tasks(goals[lo:hi], policy, baseline, p, p['seed'], (it * T + lo) * runs, anil=anil, want_replays=False)
+            iter_loss = res.total_loss
+            iter_reward = sum(res.reward.tolist())                             # (the iteration's one read-back)
+        walk = () if batch_tasks else goals[lo:hi]                             # without the flag: task by task, as before
+        for g, goal in enumerate(walk, start=lo):
             learner = policy.clone()
             # rollout='device': task g of iteration `it` owns the ids (it * T + g) * runs .. + runs - 1 at any world size
             task = Particles2DRunner(goal, p['max_path_length'], gen, dev, rollout=rollout, seed=p['seed'], first_id=(it * T + g) * runs)
@@ -82,7 +95,11 @@ if __name__ == '__main__':
     parser.add_argument('--anil', action='store_true')
     parser.add_argument('--rollout', choices=('host', 'device'), default='host',
                         help='host: Python loop over the steps, torch-generator noise; device: one mi_particles_rollout call per run of a task')
+    parser.add_argument('--batch_tasks', action='store_true',
+                        help='adapt all tasks of a rank in one batched call per adapt step (needs --rollout device)')
     args = parser.parse_args()
+    if args.batch_tasks and args.rollout != 'device':
+        parser.error('--batch_tasks needs --rollout device')
     for k in params:
         params[k] = getattr(args, k)
-    run(params, anil=args.anil, rollout=args.rollout)
+    run(params, anil=args.anil, rollout=args.rollout, batch_tasks=args.batch_tasks)

@@ -653,6 +653,22 @@ int mi_policy_meta_batch_dones(mi_policy* p, void* stream, const float* theta, i
                                int with_grad, float* loss_out, float* theta_out, float* grad_out, void* workspace,
                                size_t workspace_bytes);
 
+/* The inner update of fast_adapt_vpg / fast_adapt_ppo (rl.py:231-255,267-318) and single_ppo_update (rl.py:319-336) on its own,
+ * for all tasks per call and from PER-TASK parameters: per task u_0 = theta[t] (tstride 0: shared, P: one row per task),
+ *   u_{e+1} = u_e - lr * grad L(u_e), e < epochs;   theta_out[t] = u_epochs;   loss_out[t][e] = L(u_e)   (loss_out may be NULL)
+ * with L the loss mi_policy_meta_batch uses for loss_kind on the task's replay (states [tasks,batch,S], actions [tasks,batch,A],
+ * adv [tasks,batch], count [tasks] or NULL, padded like the TRPO replays).  MI_PLOSS_PPO takes the old log-probabilities once, at
+ * u_0 (rl.py:280-290); MI_PLOSS_DICE needs done [tasks,batch] (NULL otherwise).  head_only as in mi_policy_adapt.  The updates are
+ * plain (nothing is kept for a meta-gradient): the passes of a first-order mi_policy_meta_batch step in the same order, so from
+ * shared parameters theta_out is bit-identical to mi_policy_meta_batch(steps = epochs, with_grad = 0) on the same replay.  The number
+ * of launches does not depend on `tasks`.  theta_out may be theta itself when tstride = P.
+ * tasks, batch >= 1, 1 <= epochs <= 64, tstride 0 or P, loss_kind one of MI_PLOSS_*: MI_ERR_ARG with a text naming mi_policy_update
+ * and the value otherwise, before any HIP call.  The workspace size covers every epochs in range. */
+int mi_policy_update_workspace_bytes(const mi_policy* p, int tasks, int batch, size_t* bytes);
+int mi_policy_update(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states, const float* actions,
+                     const float* adv, const int32_t* count, const float* done, int tasks, int batch, int loss_kind, int epochs,
+                     float clip, float lr, int head_only, float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes);
+
 /* MAML-TRPO with `steps` >= 1 inner updates (params['adapt_steps'], one support replay per update, rl.py:447-453): the
  * generalisation of mi_trpo_surrogate / mi_trpo_fvp.  Support arrays carry a leading [steps] axis:
  * s_states [steps,tasks,batch,S], s_actions [steps,tasks,batch,A], s_adv [steps,tasks,batch], s_count [steps,tasks].
