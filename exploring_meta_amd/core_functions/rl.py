@@ -650,19 +650,23 @@ class _SurrogateContext:
             loss, kl, grad = self._allmean(loss, kl, grad)
         return loss, kl, grad
 
-    def prepare_general_kl(self, theta):
+    def prepare_general_kl(self, theta, want_grad=False):
         """ANIL-TRPO: the re-adapted policies differ from the stored old ones, the Fisher form does not apply; set up the exact
-        KL Hessian-vector product (mi_trpo_kl_prepare) at the theta of the preceding ``evaluate``."""
-        if self.steps != 1:
-            raise NotImplementedError('the exact KL Hessian-vector product (anil=True) is implemented for adapt_steps == 1, the '
-                                      'reference default (rl/anil_trpo.py)')
-        self.engine.kl_prepare(theta, self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr)
+        KL Hessian-vector product (mi_trpo_kl_prepare, mi_trpo_kl_prepare_steps for adapt_steps > 1) at the theta of the
+        preceding ``evaluate``.  Returns d mean KL / d theta if ``want_grad``."""
+        if self.steps == 1:
+            grad = self.engine.kl_prepare(theta, self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad)
+        else:
+            grad = self.engine.kl_prepare_steps(self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad)
         self.general = True
+        return None if grad is None else self._allmean(grad)[0]
 
     def fvp(self, theta, v, damping=1e-5):
         # the damping term is linear in v, so averaging the per-rank results keeps it exact
         if getattr(self, 'general', False):
-            return self._allmean(self.engine.fvp_general(theta, self.sup, self.qry, self.old_scale, self.inner_lr, damping, v))[0]
+            if self.steps == 1:
+                return self._allmean(self.engine.fvp_general(theta, self.sup, self.qry, self.old_scale, self.inner_lr, damping, v))[0]
+            return self._allmean(self.engine.fvp_general_steps(self.sup, self.qry, self.old_scale, self.inner_lr, damping, v))[0]
         if self.steps == 1:
             return self._allmean(self.engine.fvp(theta, self.sup, self.qry, self.inner_lr, damping, v))[0]
         return self._allmean(self.engine.fvp_steps(self.sup, self.qry, self.inner_lr, damping, v))[0]

@@ -12,6 +12,9 @@
 // replay.   grad_theta mean_t S_t = mean_t (I - lr H_t) grad S_t(theta'_t)          (H_t v: tangent sweep over the support pass)
 // At theta_old the adapted policy equals the stored old policy, KL's gradient is exactly zero, so
 //   Fvp(v) = mean_t (I - lr H_t) F_t (I - lr H_t) v + damping v,   F_t = J^T diag(1/(B D sigma^2), 2/D) J  (Gaussian Fisher).
+// The curvature product, by case:                      adapt_steps == 1                         adapt_steps > 1
+//   MAML-TRPO (new == old, Fisher form exact)          mi_trpo_surrogate / mi_trpo_fvp          mi_trpo_surrogate_steps / mi_trpo_fvp_steps
+//   ANIL-TRPO (new != old, exact Hessian of mean KL)   mi_trpo_kl_prepare / mi_trpo_fvp_general mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps
 #include <string>
 #include <vector>
 #include <cmath>
@@ -1410,7 +1413,7 @@ extern "C" int mi_trpo_steps_workspace_bytes(const mi_policy* p, int tasks, int 
   if (!p || !bytes || tasks < 1 || batch < 1 || steps < 1) return MI_ERR_ARG;
   MetaPlan pl;
   meta_plan(p, nullptr, tasks, batch, steps, 1, true, pl);
-  *bytes = pl.bytes + align_up((size_t)2 * tasks * sizeof(float), 256);
+  *bytes = pl.bytes + align_up((size_t)2 * tasks * sizeof(float), 256);      // per-task loss and KL behind the plan
   return MI_OK;
 }
 
@@ -1682,11 +1685,20 @@ __global__ __launch_bounds__(256) void gauss_kl_kernel(GaussKlArgs a) {
 }
 
 struct TanSweep { float *z1, *h1, *z2, *h2, *mu, *rdmu, *dh2, *dz2, *dh1, *dz1; };
+struct MixSweep { float *hcv1, *zcv2, *hcv2, *mucv, *rdmu_cv, *dh2cv, *dz2cv, *dh1cv, *dz1cv; };      // scratch of the mixed sweep
+static void tan_plan(const mi_policy* p, PBump& b, size_t TB, TanSweep& s) {
+  s.z1 = b.f(TB * p->H1); s.h1 = b.f(TB * p->H1); s.z2 = b.f(TB * p->H2); s.h2 = b.f(TB * p->H2); s.mu = b.f(TB * p->A);
+  s.rdmu = b.f(TB * p->A); s.dh2 = b.f(TB * p->H2); s.dz2 = b.f(TB * p->H2); s.dh1 = b.f(TB * p->H1); s.dz1 = b.f(TB * p->H1);
+}
+static void mix_plan(const mi_policy* p, PBump& b, size_t TB, MixSweep& m) {
+  m.hcv1 = b.f(TB * p->H1); m.zcv2 = b.f(TB * p->H2); m.hcv2 = b.f(TB * p->H2); m.mucv = b.f(TB * p->A); m.rdmu_cv = b.f(TB * p->A);
+  m.dh2cv = b.f(TB * p->H2); m.dz2cv = b.f(TB * p->H2); m.dh1cv = b.f(TB * p->H1); m.dz1cv = b.f(TB * p->H1);
+}
 struct GenPlan {
   float *k_dmu, *k_d2, *k_d1, *k_pre2, *k_pre1;      // KL primal cotangents on the query pass at theta'
   float* c;                                           // [T][P] grad KL_t(theta'_t)
   TanSweep sc, sv;                                    // c-tangent (context) and v-tangent (per product) sweeps over the support pass
-  float *hcv1, *zcv2, *hcv2, *mucv, *rdmu_cv, *dh2cv, *dz2cv, *dh1cv, *dz1cv;
+  MixSweep mx;                                        // mixed (cv) sweep scratch
   float *s3, *scr;                                    // [T][P]: third-order term, scratch
   size_t bytes;
 };
@@ -1696,13 +1708,8 @@ static void gen_plan(const mi_policy* p, void* ws, int T, int B, TrpoPlan& pl, G
   const size_t TB = (size_t)T * B, TP = (size_t)T * p->P;
   gp.k_dmu = b.f(TB * p->A); gp.k_d2 = b.f(TB * p->H2); gp.k_d1 = b.f(TB * p->H1); gp.k_pre2 = b.f(TB * p->H2); gp.k_pre1 = b.f(TB * p->H1);
   gp.c = b.f(TP);
-  auto sweep = [&](TanSweep& s) {
-    s.z1 = b.f(TB * p->H1); s.h1 = b.f(TB * p->H1); s.z2 = b.f(TB * p->H2); s.h2 = b.f(TB * p->H2); s.mu = b.f(TB * p->A);
-    s.rdmu = b.f(TB * p->A); s.dh2 = b.f(TB * p->H2); s.dz2 = b.f(TB * p->H2); s.dh1 = b.f(TB * p->H1); s.dz1 = b.f(TB * p->H1);
-  };
-  sweep(gp.sc); sweep(gp.sv);
-  gp.hcv1 = b.f(TB * p->H1); gp.zcv2 = b.f(TB * p->H2); gp.hcv2 = b.f(TB * p->H2); gp.mucv = b.f(TB * p->A); gp.rdmu_cv = b.f(TB * p->A);
-  gp.dh2cv = b.f(TB * p->H2); gp.dz2cv = b.f(TB * p->H2); gp.dh1cv = b.f(TB * p->H1); gp.dz1cv = b.f(TB * p->H1);
+  tan_plan(p, b, TB, gp.sc); tan_plan(p, b, TB, gp.sv);
+  mix_plan(p, b, TB, gp.mx);
   gp.s3 = b.f(TP); gp.scr = b.f(TP);
   gp.bytes = align_up(b.off, 256);
 }
@@ -1714,30 +1721,70 @@ extern "C" int mi_trpo_general_workspace_bytes(const mi_policy* p, int tasks, in
   return MI_OK;
 }
 
-// First-order tangent sweep over the cached support pass at theta (shared) along direction d (stride ds floats per task, 0 = one
-// direction for all tasks), keeping the pre-activation tangents the mixed sweep needs.
-static int tan_sweep(mi_policy* p, hipStream_t st, TrpoPlan& pl, int T, int B, const float* theta, const float* xs, const float* as,
-                     const int32_t* cn, const float* d, size_t ds, TanSweep& s, float* drho_scratch) {
+// The cached primal pass a tangent sweep runs over: activations, cotangents (dmu, dz2; pre2 / pre1 before the phi' factor) and
+// dL/dlogp per sample -- TrpoPlan::sa of the one-step path or the StepSet of inner update k.
+struct PassRef { const float *h1, *h2, *mu, *dmu, *d2, *pre2, *pre1, *coef; };
+static PassRef pass_of(const TrpoPlan& pl) { return {pl.sa.h1, pl.sa.h2, pl.sa.mu, pl.s_dmu, pl.s_d2, pl.s_pre2, pl.s_pre1, pl.s_coef}; }
+static PassRef pass_of(const StepSet& s) { return {s.a.h1, s.a.h2, s.a.mu, s.dmu, s.d2, s.pre2, s.pre1, s.coef}; }
+
+// First-order tangent sweep over a cached support pass at theta (stride ts floats per task, 0 = shared) along direction d (stride
+// ds, 0 = one direction for all tasks), keeping the pre-activation tangents the mixed sweep needs.  R{d L / d sigma} lands in
+// drho_out + o_sigma (rows of P floats).
+static int tan_sweep(mi_policy* p, hipStream_t st, const PassRef& ps, int T, int B, const float* theta, size_t ts, const float* xs,
+                     const float* as, const int32_t* cn, const float* d, size_t ds, TanSweep& s, float* drho_out) {
   const size_t TB = (size_t)T * B;
   { FTerm tm[1] = {{xs, d + p->o_w1, ds}};
     PCHK(p, dense_fwd_n(st, T, B, p->S, p->H1, tm, 1, d + p->o_b1, ds, s.z1)); }
-  PCHK(p, ew(st, p->act, EW_ACT_T, TB * p->H1, pl.sa.h1, s.h1, s.z1));
-  { FTerm tm[2] = {{pl.sa.h1, d + p->o_w2, ds}, {s.h1, theta + p->o_w2, 0}};
+  PCHK(p, ew(st, p->act, EW_ACT_T, TB * p->H1, ps.h1, s.h1, s.z1));
+  { FTerm tm[2] = {{ps.h1, d + p->o_w2, ds}, {s.h1, theta + p->o_w2, ts}};
     PCHK(p, dense_fwd_n(st, T, B, p->H1, p->H2, tm, 2, d + p->o_b2, ds, s.z2)); }
-  PCHK(p, ew(st, p->act, EW_ACT_T, TB * p->H2, pl.sa.h2, s.h2, s.z2));
-  { FTerm tm[2] = {{pl.sa.h2, d + p->o_w3, ds}, {s.h2, theta + p->o_w3, 0}};
+  PCHK(p, ew(st, p->act, EW_ACT_T, TB * p->H2, ps.h2, s.h2, s.z2));
+  { FTerm tm[2] = {{ps.h2, d + p->o_w3, ds}, {s.h2, theta + p->o_w3, ts}};
     PCHK(p, dense_fwd_n(st, T, B, p->H2, p->A, tm, 2, d + p->o_b3, ds, s.mu)); }
   GaussArgs ga{};
-  ga.mu = pl.sa.mu; ga.mud = s.mu; ga.rho = theta + p->o_sigma; ga.rstride = 0; ga.rhod = d + p->o_sigma; ga.vstride = ds;
-  ga.act = as; ga.count = cn; ga.coef = pl.s_coef; ga.dmu = s.rdmu; ga.drho = drho_scratch + p->o_sigma; ga.gstride = p->P;
+  ga.mu = ps.mu; ga.mud = s.mu; ga.rho = theta + p->o_sigma; ga.rstride = ts; ga.rhod = d + p->o_sigma; ga.vstride = ds;
+  ga.act = as; ga.count = cn; ga.coef = const_cast<float*>(ps.coef); ga.dmu = s.rdmu; ga.drho = drho_out + p->o_sigma; ga.gstride = p->P;
   ga.B = B; ga.A = p->A; ga.mode = G_TANGENT;
   PCHK(p, gauss(st, T, ga));
-  { FTerm tm[2] = {{s.rdmu, theta + p->o_w3, 0}, {pl.s_dmu, d + p->o_w3, ds}};
+  { FTerm tm[2] = {{s.rdmu, theta + p->o_w3, ts}, {ps.dmu, d + p->o_w3, ds}};
     PCHK(p, dense_bwd_x_n(st, T, B, p->H2, p->A, tm, 2, s.dh2)); }
-  PCHK(p, ew(st, p->act, EW_GATE_T, TB * p->H2, pl.sa.h2, s.dz2, s.dh2, s.z2, pl.s_pre2));
-  { FTerm tm[2] = {{s.dz2, theta + p->o_w2, 0}, {pl.s_d2, d + p->o_w2, ds}};
+  PCHK(p, ew(st, p->act, EW_GATE_T, TB * p->H2, ps.h2, s.dz2, s.dh2, s.z2, ps.pre2));
+  { FTerm tm[2] = {{s.dz2, theta + p->o_w2, ts}, {ps.d2, d + p->o_w2, ds}};
     PCHK(p, dense_bwd_x_n(st, T, B, p->H1, p->H2, tm, 2, s.dh1)); }
-  PCHK(p, ew(st, p->act, EW_GATE_T, TB * p->H1, pl.sa.h1, s.dz1, s.dh1, s.z1, pl.s_pre1));
+  PCHK(p, ew(st, p->act, EW_GATE_T, TB * p->H1, ps.h1, s.dz1, s.dh1, s.z1, ps.pre1));
+  return MI_OK;
+}
+
+// s3_t = T_t[v, c] = R_v{R_c{grad L_t}} over a cached support pass at theta (stride ts): the mixed (cv) second-order tangent sweep
+// from the first-order sweeps C (along c, stride cs) and V (along v, stride vs).  s3 [T][P] must be zero on entry.
+static int mixed_sweep(mi_policy* p, hipStream_t st, const PassRef& ps, int T, int B, const float* theta, size_t ts, const float* xs,
+                       const float* as, const int32_t* cn, const float* c, size_t cs, const float* v, size_t vs, const TanSweep& C,
+                       const TanSweep& V, const MixSweep& m, float* s3) {
+  const size_t P = p->P, TB = (size_t)T * B;
+  PCHK(p, ew(st, p->act, EW_ACT_CV, TB * p->H1, ps.h1, m.hcv1, nullptr, C.z1, V.z1));
+  { FTerm tm[3] = {{V.h1, c + p->o_w2, cs}, {C.h1, v + p->o_w2, vs}, {m.hcv1, theta + p->o_w2, ts}};
+    PCHK(p, dense_fwd_n(st, T, B, p->H1, p->H2, tm, 3, nullptr, 0, m.zcv2)); }
+  PCHK(p, ew(st, p->act, EW_ACT_CV, TB * p->H2, ps.h2, m.hcv2, m.zcv2, C.z2, V.z2));
+  { FTerm tm[3] = {{V.h2, c + p->o_w3, cs}, {C.h2, v + p->o_w3, vs}, {m.hcv2, theta + p->o_w3, ts}};
+    PCHK(p, dense_fwd_n(st, T, B, p->H2, p->A, tm, 3, nullptr, 0, m.mucv)); }
+  GaussKlArgs g2{};
+  g2.mu = ps.mu; g2.rho = theta + p->o_sigma; g2.rstride = ts; g2.mud = m.mucv; g2.muc = C.mu; g2.muv = V.mu;
+  g2.rhoc = c + p->o_sigma; g2.cstride = cs; g2.rhov = v + p->o_sigma; g2.vvstride = vs; g2.act = as; g2.coef = ps.coef;
+  g2.count = cn; g2.dmu = m.rdmu_cv; g2.drho = s3 + p->o_sigma; g2.gstride = P; g2.B = B; g2.A = p->A; g2.mode = G_TAN2;
+  hipLaunchKernelGGL(gauss_kl_kernel, dim3(T), dim3(256), 0, st, g2);
+  PCHK(p, hipGetLastError());
+  { WTerm tm[4] = {{m.rdmu_cv, ps.h2}, {C.rdmu, V.h2}, {V.rdmu, C.h2}, {ps.dmu, m.hcv2}};
+    PCHK(p, dense_bwd_w_n(st, T, B, p->H2, p->A, tm, 4, s3 + p->o_w3, s3 + p->o_b3, P)); }
+  { FTerm tm[3] = {{m.rdmu_cv, theta + p->o_w3, ts}, {C.rdmu, v + p->o_w3, vs}, {V.rdmu, c + p->o_w3, cs}};
+    PCHK(p, dense_bwd_x_n(st, T, B, p->H2, p->A, tm, 3, m.dh2cv)); }
+  PCHK(p, ew(st, p->act, EW_GATE_CV, TB * p->H2, ps.h2, m.dz2cv, m.dh2cv, V.z2, C.dh2, C.z2, V.dh2, m.zcv2, ps.pre2));
+  { WTerm tm[4] = {{m.dz2cv, ps.h1}, {C.dz2, V.h1}, {V.dz2, C.h1}, {ps.d2, m.hcv1}};
+    PCHK(p, dense_bwd_w_n(st, T, B, p->H1, p->H2, tm, 4, s3 + p->o_w2, s3 + p->o_b2, P)); }
+  { FTerm tm[3] = {{m.dz2cv, theta + p->o_w2, ts}, {C.dz2, v + p->o_w2, vs}, {V.dz2, c + p->o_w2, cs}};
+    PCHK(p, dense_bwd_x_n(st, T, B, p->H1, p->H2, tm, 3, m.dh1cv)); }
+  PCHK(p, ew(st, p->act, EW_GATE_CV, TB * p->H1, ps.h1, m.dz1cv, m.dh1cv, V.z1, C.dh1, C.z1, V.dh1, nullptr, ps.pre1));
+  { WTerm tm[1] = {{m.dz1cv, xs}};
+    PCHK(p, dense_bwd_w_n(st, T, B, p->S, p->H1, tm, 1, s3 + p->o_w1, s3 + p->o_b1, P)); }
   return MI_OK;
 }
 
@@ -1762,7 +1809,7 @@ extern "C" int mi_trpo_kl_prepare(mi_policy* p, void* stream, const float* theta
   PCHK(p, hipGetLastError());
   int rc = mlp_backward(p, st, T, B, q_states, pl.thetap, P, pl.qa, gp.k_dmu, gp.k_d2, gp.k_d1, gp.c, gp.k_pre2, gp.k_pre1);
   if (rc) return rc;
-  rc = tan_sweep(p, st, pl, T, B, theta, s_states, s_actions, s_count, gp.c, P, gp.sc, gp.scr);
+  rc = tan_sweep(p, st, pass_of(pl), T, B, theta, 0, s_states, s_actions, s_count, gp.c, P, gp.sc, gp.scr);
   if (rc || !kl_grad_out) return rc;
   rc = support_hvp(p, st, pl, T, B, theta, s_states, s_actions, s_count, gp.c, pl.hv);
   if (rc) return rc;
@@ -1782,7 +1829,7 @@ extern "C" int mi_trpo_fvp_general(mi_policy* p, void* stream, const float* thet
   if (!p || !theta || !s_states || !s_actions || !q_states || !old_scale || !v || !out || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch;
-  const size_t P = p->P, TB = (size_t)T * B;
+  const size_t P = p->P;
   TrpoPlan pl; GenPlan gp;
   gen_plan(p, workspace, T, B, pl, gp);
   if (gp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small");
@@ -1812,38 +1859,193 @@ extern "C" int mi_trpo_fvp_general(mi_policy* p, void* stream, const float* thet
   hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.w, P, pl.hv, inner_lr, (int)P, pl.w);
   PCHK(p, hipGetLastError());
   // ---- s3_t = T_t[v, c_t]: v-tangent sweep, then the mixed sweep
-  rc = tan_sweep(p, st, pl, T, B, theta, s_states, s_actions, s_count, v, 0, gp.sv, gp.scr);
+  rc = tan_sweep(p, st, pass_of(pl), T, B, theta, 0, s_states, s_actions, s_count, v, 0, gp.sv, gp.scr);
   if (rc) return rc;
-  const TanSweep &C = gp.sc, &V = gp.sv;
-  const float* c = gp.c;
   PCHK(p, hipMemsetAsync(gp.s3, 0, (size_t)T * P * sizeof(float), st));
-  PCHK(p, ew(st, p->act, EW_ACT_CV, TB * p->H1, pl.sa.h1, gp.hcv1, nullptr, C.z1, V.z1));
-  { FTerm tm[3] = {{V.h1, c + p->o_w2, P}, {C.h1, v + p->o_w2, 0}, {gp.hcv1, theta + p->o_w2, 0}};
-    PCHK(p, dense_fwd_n(st, T, B, p->H1, p->H2, tm, 3, nullptr, 0, gp.zcv2)); }
-  PCHK(p, ew(st, p->act, EW_ACT_CV, TB * p->H2, pl.sa.h2, gp.hcv2, gp.zcv2, C.z2, V.z2));
-  { FTerm tm[3] = {{V.h2, c + p->o_w3, P}, {C.h2, v + p->o_w3, 0}, {gp.hcv2, theta + p->o_w3, 0}};
-    PCHK(p, dense_fwd_n(st, T, B, p->H2, p->A, tm, 3, nullptr, 0, gp.mucv)); }
-  GaussKlArgs g2{};
-  g2.mu = pl.sa.mu; g2.rho = theta + p->o_sigma; g2.rstride = 0; g2.mud = gp.mucv; g2.muc = C.mu; g2.muv = V.mu;
-  g2.rhoc = c + p->o_sigma; g2.cstride = P; g2.rhov = v + p->o_sigma; g2.vvstride = 0; g2.act = s_actions; g2.coef = pl.s_coef;
-  g2.count = s_count; g2.dmu = gp.rdmu_cv; g2.drho = gp.s3 + p->o_sigma; g2.gstride = P; g2.B = B; g2.A = p->A; g2.mode = G_TAN2;
-  hipLaunchKernelGGL(gauss_kl_kernel, dim3(T), dim3(256), 0, st, g2);
-  PCHK(p, hipGetLastError());
-  { WTerm tm[4] = {{gp.rdmu_cv, pl.sa.h2}, {C.rdmu, V.h2}, {V.rdmu, C.h2}, {pl.s_dmu, gp.hcv2}};
-    PCHK(p, dense_bwd_w_n(st, T, B, p->H2, p->A, tm, 4, gp.s3 + p->o_w3, gp.s3 + p->o_b3, P)); }
-  { FTerm tm[3] = {{gp.rdmu_cv, theta + p->o_w3, 0}, {C.rdmu, v + p->o_w3, 0}, {V.rdmu, c + p->o_w3, P}};
-    PCHK(p, dense_bwd_x_n(st, T, B, p->H2, p->A, tm, 3, gp.dh2cv)); }
-  PCHK(p, ew(st, p->act, EW_GATE_CV, TB * p->H2, pl.sa.h2, gp.dz2cv, gp.dh2cv, V.z2, C.dh2, C.z2, V.dh2, gp.zcv2, pl.s_pre2));
-  { WTerm tm[4] = {{gp.dz2cv, pl.sa.h1}, {C.dz2, V.h1}, {V.dz2, C.h1}, {pl.s_d2, gp.hcv1}};
-    PCHK(p, dense_bwd_w_n(st, T, B, p->H1, p->H2, tm, 4, gp.s3 + p->o_w2, gp.s3 + p->o_b2, P)); }
-  { FTerm tm[3] = {{gp.dz2cv, theta + p->o_w2, 0}, {C.dz2, v + p->o_w2, 0}, {V.dz2, c + p->o_w2, P}};
-    PCHK(p, dense_bwd_x_n(st, T, B, p->H1, p->H2, tm, 3, gp.dh1cv)); }
-  PCHK(p, ew(st, p->act, EW_GATE_CV, TB * p->H1, pl.sa.h1, gp.dz1cv, gp.dh1cv, V.z1, C.dh1, C.z1, V.dh1, nullptr, pl.s_pre1));
-  { WTerm tm[1] = {{gp.dz1cv, s_states}};
-    PCHK(p, dense_bwd_w_n(st, T, B, p->S, p->H1, tm, 1, gp.s3 + p->o_w1, gp.s3 + p->o_b1, P)); }
+  rc = mixed_sweep(p, st, pass_of(pl), T, B, theta, 0, s_states, s_actions, s_count, gp.c, P, v, 0, gp.sc, gp.sv, gp.mx, gp.s3);
+  if (rc) return rc;
   // ---- out = mean_t (r_t - lr s3_t) + damping v
   hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.w, P, gp.s3, inner_lr, (int)P, pl.tmpP);
   hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.tmpP, T, (int)P, 1.f / (float)T, v, damping, out);
+  PCHK(p, hipGetLastError());
+  return MI_OK;
+}
+
+// =====================================================================================================================
+// The same exact Hessian-vector product of the mean KL with any number K of inner updates (rl/anil_trpo.py --adapt_steps K).
+// theta_0 = theta, theta_{k+1} = theta_k - lr grad L_k(theta_k), H_k = Hess L_k(theta_k), T_k[a, b] = d/d eps H_k(theta_k + eps a) b,
+// c = grad KL_t(theta_K) on the query replay.  Differentiating the adjoint recursion of the KL gradient once more along v:
+//   context (mi_trpo_kl_prepare_steps):  lam_K = c,   lam_k = lam_{k+1} - lr H_k lam_{k+1},      grad mean KL = mean_t lam_0
+//   product (mi_trpo_fvp_general_steps): u_0 = v,     u_{k+1} = u_k - lr H_k u_k,
+//                                        rho_K = Hess KL_t(theta_K) u_K,
+//                                        rho_k = rho_{k+1} - lr H_k rho_{k+1} - lr T_k[u_k, lam_{k+1}],    out = mean_t rho_0 + damping v
+// which at K = 1 is the formula above.  A first-order tangent sweep over the cached pass of update k along a direction d leaves
+// every tangent the mixed sweep reads AND, through three weight-gradient products, H_k d itself: the context keeps one sweep per
+// update along lam_{k+1} (it yields lam_k on the way), a product keeps one per update along u_k (it yields u_{k+1}), and only
+// H_k rho_{k+1} needs a sweep of its own.  For k >= 1 theta_k, u_k and lam_{k+1} are per task (stride P).
+// Workspace: the MetaPlan prefix of mi_trpo_surrogate_steps (theta_k, the StepSet of every update, the query pass), then the
+// KL cotangents of the query pass, lam [K+1][T][P], u [K+1][T][P], 2 K tangent sweeps and the mixed-sweep scratch.
+struct GenStepsPlan {
+  float *k_dmu, *k_d2, *k_d1, *k_pre2, *k_pre1;      // KL primal cotangents on the query pass at theta_K
+  float *lam, *u;                                     // [K+1][T][P]
+  float *rho, *s3;                                    // [T][P]
+  std::vector<TanSweep> sc, sv;                       // per update: sweeps along lam_{k+1} (context) and u_k (per product)
+  MixSweep mx;
+  size_t bytes;
+};
+static size_t trpo_steps_prefix_bytes(const MetaPlan& pl, int T) { return pl.bytes + align_up((size_t)2 * T * sizeof(float), 256); }
+static void gen_steps_plan(const mi_policy* p, void* ws, int T, int B, int K, MetaPlan& pl, GenStepsPlan& gp) {
+  meta_plan(p, ws, T, B, K, 1, true, pl);
+  PBump b{reinterpret_cast<char*>(ws), trpo_steps_prefix_bytes(pl, T)};       // past the per-task loss / KL of mi_trpo_surrogate_steps
+  const size_t TB = (size_t)T * B, TP = (size_t)T * p->P;
+  gp.k_dmu = b.f(TB * p->A); gp.k_d2 = b.f(TB * p->H2); gp.k_d1 = b.f(TB * p->H1); gp.k_pre2 = b.f(TB * p->H2); gp.k_pre1 = b.f(TB * p->H1);
+  gp.lam = b.f(TP * (K + 1)); gp.u = b.f(TP * (K + 1)); gp.rho = b.f(TP); gp.s3 = b.f(TP);
+  gp.sc.resize(K); gp.sv.resize(K);
+  for (auto& s : gp.sc) tan_plan(p, b, TB, s);
+  for (auto& s : gp.sv) tan_plan(p, b, TB, s);
+  mix_plan(p, b, TB, gp.mx);
+  gp.bytes = align_up(b.off, 256);
+}
+extern "C" int mi_trpo_general_steps_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, size_t* bytes) {
+  if (!p || !bytes || tasks < 1 || batch < 1 || steps < 1) return MI_ERR_ARG;
+  MetaPlan pl; GenStepsPlan gp;
+  gen_steps_plan(p, nullptr, tasks, batch, steps, pl, gp);
+  *bytes = gp.bytes;
+  return MI_OK;
+}
+
+// tangent sweep along d kept in s, and hv = H d from it: R{d L / d sigma} by the sweep, the weights by three products
+static int sweep_hvp(mi_policy* p, hipStream_t st, const PassRef& ps, int T, int B, const float* theta, size_t ts, const float* xs,
+                     const float* as, const int32_t* cn, const float* d, size_t ds, TanSweep& s, float* hv) {
+  const size_t P = p->P;
+  PCHK(p, hipMemsetAsync(hv, 0, (size_t)T * P * sizeof(float), st));
+  int rc = tan_sweep(p, st, ps, T, B, theta, ts, xs, as, cn, d, ds, s, hv);
+  if (rc) return rc;
+  { WTerm tm[2] = {{s.rdmu, ps.h2}, {ps.dmu, s.h2}};
+    PCHK(p, dense_bwd_w_n(st, T, B, p->H2, p->A, tm, 2, hv + p->o_w3, hv + p->o_b3, P)); }
+  { WTerm tm[2] = {{s.dz2, ps.h1}, {ps.d2, s.h1}};
+    PCHK(p, dense_bwd_w_n(st, T, B, p->H1, p->H2, tm, 2, hv + p->o_w2, hv + p->o_b2, P)); }
+  { WTerm tm[1] = {{s.dz1, xs}};
+    PCHK(p, dense_bwd_w_n(st, T, B, p->S, p->H1, tm, 1, hv + p->o_w1, hv + p->o_b1, P)); }
+  return MI_OK;
+}
+// out = a - alpha (h + s3): one step of the rho recursion in one launch (out may be a)
+__global__ void step_back_kernel(const float* a, const float* __restrict__ h, const float* __restrict__ s3, float alpha, size_t n,
+                                 float* out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = a[i] - alpha * (h[i] + s3[i]);
+}
+
+static int steps_args(mi_policy* p, const char* fn, int steps, int tasks, int batch) {
+  if (steps < 1 || tasks < 1 || batch < 1)
+    return pfail(p, MI_ERR_ARG, std::string(fn) + ": steps, tasks and batch must be >= 1");
+  return MI_OK;
+}
+
+// After mi_trpo_surrogate_steps(theta, steps, ...) on the same workspace and replays: the KL cotangent pass on the query replay at
+// theta_K (into buffers of its own: the surrogate's query cotangents stay), lam_k for every k, and the tangent sweep of every
+// update along lam_{k+1}.  kl_grad_out (optional, [P]) = d mean_t KL_t / d theta = mean_t lam_0.
+extern "C" int mi_trpo_kl_prepare_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                        const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
+                                        const float* old_scale, int tasks, int batch, float inner_lr, float* kl_grad_out,
+                                        void* workspace, size_t workspace_bytes) {
+  if (!p || !s_states || !s_actions || !q_states || !old_loc || !old_scale || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
+  int rc = steps_args(p, "mi_trpo_kl_prepare_steps", steps, tasks, batch);
+  if (rc) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int T = tasks, B = batch, K = steps;
+  const size_t P = p->P, TB = (size_t)T * B, TP = (size_t)T * P;
+  MetaPlan pl; GenStepsPlan gp;
+  gen_steps_plan(p, workspace, T, B, K, pl, gp);
+  if (gp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(gp.bytes));
+  const float* thK = pl.theta + (size_t)K * TP;
+  float* lamK = gp.lam + (size_t)K * TP;
+  PCHK(p, hipMemsetAsync(lamK, 0, TP * sizeof(float), st));
+  GaussKlArgs gk{};
+  gk.mu = pl.q.a.mu; gk.rho = thK + p->o_sigma; gk.rstride = P; gk.old_loc = old_loc; gk.old_scale = old_scale; gk.count = q_count;
+  gk.dmu = gp.k_dmu; gk.drho = lamK + p->o_sigma; gk.gstride = P; gk.B = B; gk.A = p->A; gk.mode = KL_GRAD;
+  hipLaunchKernelGGL(gauss_kl_kernel, dim3(T), dim3(256), 0, st, gk);
+  PCHK(p, hipGetLastError());
+  rc = mlp_backward(p, st, T, B, q_states, thK, P, pl.q.a, gp.k_dmu, gp.k_d2, gp.k_d1, lamK, gp.k_pre2, gp.k_pre1);
+  if (rc) return rc;
+  for (int k = K - 1; k >= 0; --k) {
+    const float* lam1 = gp.lam + (size_t)(k + 1) * TP;
+    rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, P, s_states + (size_t)k * TB * p->S,
+                   s_actions + (size_t)k * TB * p->A, s_count ? s_count + (size_t)k * T : nullptr, lam1, P, gp.sc[k], pl.hv);
+    if (rc) return rc;
+    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, lam1, P, pl.hv, inner_lr, (int)P,
+                       gp.lam + (size_t)k * TP);
+    PCHK(p, hipGetLastError());
+  }
+  if (!kl_grad_out) return MI_OK;
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gp.lam, T, (int)P, 1.f / (float)T,
+                     (const float*)nullptr, 0.f, kl_grad_out);
+  PCHK(p, hipGetLastError());
+  return MI_OK;
+}
+
+// trpo.hessian_vector_product(mean KL, params, damping)(v) (rl.py:417) at the parameters of the preceding
+// mi_trpo_surrogate_steps + mi_trpo_kl_prepare_steps on this workspace; any number of calls.  11 + 36 K kernels and 1 + 3 K
+// memsets, whatever the number of tasks.
+extern "C" int mi_trpo_fvp_general_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                         const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
+                                         int tasks, int batch, float inner_lr, float damping, const float* v, float* out,
+                                         void* workspace, size_t workspace_bytes) {
+  if (!p || !s_states || !s_actions || !q_states || !old_scale || !v || !out || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
+  int rc = steps_args(p, "mi_trpo_fvp_general_steps", steps, tasks, batch);
+  if (rc) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int T = tasks, B = batch, K = steps;
+  const size_t P = p->P, TB = (size_t)T * B, TP = (size_t)T * P;
+  MetaPlan pl; GenStepsPlan gp;
+  gen_steps_plan(p, workspace, T, B, K, pl, gp);
+  if (gp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(gp.bytes));
+  auto sup = [&](int k, const float*& xs, const float*& as, const int32_t*& cn) {
+    xs = s_states + (size_t)k * TB * p->S; as = s_actions + (size_t)k * TB * p->A; cn = s_count ? s_count + (size_t)k * T : nullptr;
+  };
+  // ---- u_0 = v for every task, u_{k+1} = u_k - lr H_k u_k; the sweep along u_k stays for the way back
+  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (size_t)0, pl.g, 0.f, (int)P, gp.u);
+  PCHK(p, hipGetLastError());
+  for (int k = 0; k < K; ++k) {
+    const float *xs, *as; const int32_t* cn;
+    sup(k, xs, as, cn);
+    const float* uk = gp.u + (size_t)k * TP;
+    rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, P, xs, as, cn, uk, P, gp.sv[k], pl.hv);
+    if (rc) return rc;
+    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, uk, P, pl.hv, inner_lr, (int)P,
+                       gp.u + (size_t)(k + 1) * TP);
+    PCHK(p, hipGetLastError());
+  }
+  // ---- rho_K = Hess KL_t(theta_K) u_K: tangent forward on the query pass, exact output Hessian, tangent backward
+  const float* thK = pl.theta + (size_t)K * TP;
+  const float* uK = gp.u + (size_t)K * TP;
+  rc = mlp_tangent_forward(p, st, T, B, q_states, thK, P, pl.q.a, uK, pl.ta);
+  if (rc) return rc;
+  PCHK(p, hipMemsetAsync(gp.rho, 0, TP * sizeof(float), st));
+  GaussKlArgs gh{};
+  gh.mu = pl.q.a.mu; gh.rho = thK + p->o_sigma; gh.rstride = P; gh.old_scale = old_scale; gh.mud = pl.ta.mu;
+  gh.rhod = uK + p->o_sigma; gh.vstride = P; gh.count = q_count; gh.dmu = pl.rdmu; gh.drho = gp.rho + p->o_sigma; gh.gstride = P;
+  gh.B = B; gh.A = p->A; gh.mode = KL_HESS;
+  hipLaunchKernelGGL(gauss_kl_kernel, dim3(T), dim3(256), 0, st, gh);
+  PCHK(p, hipGetLastError());
+  rc = mlp_tangent_backward(p, st, T, B, q_states, thK, P, pl.q.a, pl.ta, uK, gp.k_dmu, gp.k_d2, gp.k_d1, gp.k_pre2, gp.k_pre1, pl.rdmu,
+                            pl.r2, pl.r1, gp.rho);
+  if (rc) return rc;
+  // ---- rho_k = rho_{k+1} - lr (H_k rho_{k+1} + T_k[u_k, lam_{k+1}])
+  for (int k = K - 1; k >= 0; --k) {
+    const float *xs, *as; const int32_t* cn;
+    sup(k, xs, as, cn);
+    const float* th = pl.theta + (size_t)k * TP;
+    rc = hvp_step(p, st, pl, pl.st[k], T, B, th, xs, as, cn, gp.rho, pl.hv);
+    if (rc) return rc;
+    PCHK(p, hipMemsetAsync(gp.s3, 0, TP * sizeof(float), st));
+    rc = mixed_sweep(p, st, pass_of(pl.st[k]), T, B, th, P, xs, as, cn, gp.lam + (size_t)(k + 1) * TP, P, gp.u + (size_t)k * TP, P,
+                     gp.sc[k], gp.sv[k], gp.mx, gp.s3);
+    if (rc) return rc;
+    hipLaunchKernelGGL(step_back_kernel, dim3((unsigned)((TP + 255) / 256)), dim3(256), 0, st, gp.rho, pl.hv, gp.s3, inner_lr, TP, gp.rho);
+    PCHK(p, hipGetLastError());
+  }
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gp.rho, T, (int)P, 1.f / (float)T, v, damping, out);
   PCHK(p, hipGetLastError());
   return MI_OK;
 }

@@ -591,8 +591,10 @@ class PolicyEngine:
         return loss, kl, grad
 
     def _steps_ws(self, T, B, K):
+        # the ANIL-TRPO plan of K updates starts with the MAML-TRPO one: one buffer serves both, and a kl_prepare_steps after
+        # surrogate_steps finds the surrogate's per-update passes where it left them
         b = C.c_size_t()
-        self._check(self.lib.mi_trpo_steps_workspace_bytes(self._h, T, B, K, C.byref(b)))
+        self._check(self.lib.mi_trpo_general_steps_workspace_bytes(self._h, T, B, K, C.byref(b)))
         if self._ws is None or self._ws.numel() < b.value:
             self._ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
         return self._ws
@@ -619,6 +621,30 @@ class PolicyEngine:
         self._check(self.lib.mi_trpo_fvp_steps(self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']),
                                                _ptr(qry['states']), _ptr(qry['count']), T, B, float(inner_lr), float(damping),
                                                _ptr(v.contiguous()), _ptr(out), _ptr(ws), ws.numel()))
+        return out
+
+    @_on_device
+    def kl_prepare_steps(self, sup, qry, old_loc, old_scale, inner_lr, want_grad=False):
+        """After ``surrogate_steps`` at the same theta and replays: the context of the exact KL Hessian-vector product for
+        new != old with K = sup['states'].shape[0] inner updates (ANIL-TRPO).  Returns d mean KL / d theta [P] if ``want_grad``."""
+        K, T, B = sup['states'].shape[0], sup['states'].shape[1], sup['states'].shape[2]
+        ws = self._steps_ws(T, B, K)
+        grad = torch.empty(self.param_count, device=self.device) if want_grad else None
+        self._check(self.lib.mi_trpo_kl_prepare_steps(
+            self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
+            _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B, float(inner_lr), _ptr(grad), _ptr(ws), ws.numel()))
+        return grad
+
+    @_on_device
+    def fvp_general_steps(self, sup, qry, old_scale, inner_lr, damping, v):
+        """Exact Hessian-vector product of the mean KL at the theta of the preceding ``surrogate_steps`` + ``kl_prepare_steps``."""
+        K, T, B = sup['states'].shape[0], sup['states'].shape[1], sup['states'].shape[2]
+        ws = self._steps_ws(T, B, K)
+        out = torch.empty(self.param_count, device=self.device)
+        self._check(self.lib.mi_trpo_fvp_general_steps(
+            self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
+            _ptr(qry['count']), _ptr(old_scale), T, B, float(inner_lr), float(damping), _ptr(v.contiguous()), _ptr(out), _ptr(ws),
+            ws.numel()))
         return out
 
     @_on_device

@@ -683,6 +683,28 @@ int mi_trpo_fvp_steps(mi_policy* p, void* stream, int steps, const float* s_stat
                       const float* q_states, const int32_t* q_count, int tasks, int batch, float inner_lr, float damping,
                       const float* v, float* out, void* workspace, size_t workspace_bytes);
 
+/* ANIL-TRPO with `steps` >= 1 inner updates (rl/anil_trpo.py --adapt_steps K): the exact Hessian of the mean KL for new != old,
+ * the generalisation of mi_trpo_kl_prepare / mi_trpo_fvp_general.  With theta_{k+1} = theta_k - lr grad L_k(theta_k),
+ * H_k = Hess L_k(theta_k), T_k the third derivative of L_k at theta_k and c = grad KL_t(theta_K):
+ *   lam_K = c, lam_k = lam_{k+1} - lr H_k lam_{k+1};   u_0 = v, u_{k+1} = u_k - lr H_k u_k;   rho_K = Hess KL_t(theta_K) u_K,
+ *   rho_k = rho_{k+1} - lr H_k rho_{k+1} - lr T_k[u_k, lam_{k+1}];   product = mean_t rho_0 + damping v.
+ * Support arrays carry the leading [steps] axis of mi_trpo_surrogate_steps.
+ *   mi_trpo_general_steps_workspace_bytes: workspace for the two calls below AND for mi_trpo_surrogate_steps / mi_trpo_fvp_steps
+ *     (it starts with the plan mi_trpo_steps_workspace_bytes reports); it keeps two tangent sweeps per inner update.
+ *   mi_trpo_kl_prepare_steps: after mi_trpo_surrogate_steps(theta, steps, ...) on the same workspace and replays; the surrogate's
+ *     own query cotangents are left alone.  kl_grad_out (or NULL) [P] = d mean KL / d theta = mean_t lam_0.
+ *   mi_trpo_fvp_general_steps: the product, any number of times after the two calls above.
+ * steps, tasks, batch >= 1 (MI_ERR_ARG otherwise, before any HIP call).  The number of launches depends on `steps` only. */
+int mi_trpo_general_steps_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, size_t* bytes);
+int mi_trpo_kl_prepare_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                             const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
+                             const float* old_scale, int tasks, int batch, float inner_lr, float* kl_grad_out, void* workspace,
+                             size_t workspace_bytes);
+int mi_trpo_fvp_general_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                              const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
+                              int tasks, int batch, float inner_lr, float damping, const float* v, float* out, void* workspace,
+                              size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,194 @@
+"""ANIL-TRPO with more than one adaptation step: the exact Hessian-vector product of the mean KL through K inner updates
+(mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps) against double-backward autograd of the fp64 oracle's meta_surrogate_loss,
+on the small case of test_gpu_rl.py (4 tasks, 6 episodes x 25 steps, the 2-100-100-2 policy).
+
+    lam_K = grad KL(theta_K),  lam_k = lam_{k+1} - lr H_k lam_{k+1};       u_0 = v,  u_{k+1} = u_k - lr H_k u_k;
+    rho_K = Hess KL(theta_K) u_K,  rho_k = rho_{k+1} - lr H_k rho_{k+1} - lr T_k[u_k, lam_{k+1}];    product = mean_t rho_0 + damping v
+"""
+import functools
+from collections import OrderedDict
+
+import numpy as np
+import pytest
+import torch
+
+from exploring_meta_amd import core_functions as cf
+from exploring_meta_amd.core_functions.rl import _SurrogateContext
+from oracle import rl_ref as RL
+from gpu_utils import rel_err, report
+from test_gpu_rl import PARAMS, _theta64, _policy, _policy_tanh, _anil_policy, _replays_tanh
+
+pytestmark = pytest.mark.gpu
+
+
+def _cut_last_episode(ep):
+    """The replay without its last episode."""
+    ends = torch.nonzero(ep['dones'].reshape(-1)).reshape(-1)
+    n = int(ends[-2]) + 1
+    assert 0 < n < ep['states'].shape[0]
+    return {k: v[:n].clone() for k, v in ep.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def _case(act, K, lr, ragged=False):
+    """Replays and head-only old policies from the oracle (read-only: shared between tests)."""
+    P = dict(PARAMS, adapt_steps=K, inner_lr=lr)
+    activation = torch.tanh if act == 'tanh' else torch.relu
+    env, gen, theta, baseline = RL.Particles2D(seed=1), torch.Generator().manual_seed(2), _theta64(), RL.LinearValue(2, 2)
+    replays, olds = [], []
+    for task in env.sample_tasks(P['meta_batch_size']):
+        env.set_task(task)
+        learner = OrderedDict((k, v.clone().requires_grad_(True)) for k, v in theta.items())
+        adapted, _, rep, _ = RL.fast_adapt_trpo(env, learner, baseline, P, gen, first_order=True, activation=activation, anil=True)
+        assert len(rep) == K + 1
+        replays.append(rep)
+        olds.append(OrderedDict((k, v.detach()) for k, v in adapted.items()))
+    if ragged:               # task 1's second support replay and task 2's query replay lose their last episode
+        full = replays[1][1]['states'].shape[0]
+        replays[1][1] = _cut_last_episode(replays[1][1])
+        replays[2][K] = _cut_last_episode(replays[2][K])
+        assert replays[1][1]['states'].shape[0] < full and replays[2][K]['states'].shape[0] < full
+    return P, activation, theta, replays, olds
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(act, K, lr, ragged=False):
+    """fp64: mean KL, its gradient, and the exact Hessian-vector products along the seed-5 random direction and along g_KL / |g_KL|."""
+    P, activation, theta, replays, olds = _case(act, K, lr, ragged)
+    p64 = OrderedDict((k, v.clone().requires_grad_(True)) for k, v in theta.items())
+    _, kl = RL.meta_surrogate_loss(replays, olds, p64, RL.LinearValue(2, 2), P, activation=activation)
+    plist = list(p64.values())
+    gkl = torch.cat([g.reshape(-1) for g in torch.autograd.grad(kl, plist, retain_graph=True)]).detach()
+    Hvp = RL.hessian_vector_product(kl, plist)
+    vs = [torch.randn(gkl.shape, generator=torch.Generator().manual_seed(5), dtype=torch.float64), gkl / gkl.norm()]
+    refs = [Hvp(v).detach() for v in vs]
+    return float(kl.detach()), gkl, vs, refs
+
+
+def _context(act, K, lr, ragged=False, tasks=None):
+    P, _, theta, replays, olds = _case(act, K, lr, ragged)
+    mk = _policy_tanh if act == 'tanh' else _policy
+    pol = mk(theta)
+    sel = range(len(replays)) if tasks is None else tasks
+    ctx = _SurrogateContext([replays[t] for t in sel], [mk(olds[t]) for t in sel], pol, cf.LinearValue(2, 2), P)
+    assert ctx.steps == K
+    return ctx, pol.flat()
+
+
+def _check_against_autograd(name, act, K, ragged):
+    kl, gkl, vs, refs = _reference(act, K, 0.1, ragged)
+    assert kl > 1e-6                                                       # new != old: this is not the Fisher case
+    ctx, th = _context(act, K, 0.1, ragged)
+    if ragged:
+        counts = torch.cat([ctx.sup['count'].reshape(-1), ctx.qry['count'].reshape(-1)]).tolist()
+        assert min(counts) < max(counts) == ctx.qry['states'].shape[1]
+    _, k32, _ = ctx.evaluate(th, want_grad=True)
+    g32 = ctx.prepare_general_kl(th, want_grad=True)
+    errs = [rel_err(ctx.fvp(th, v.float().cuda()).cpu().numpy(), r.numpy()) for v, r in zip(vs, refs)]
+    ctx.general = False                                                    # the Fisher form J^T F J v: valid only at new == old
+    fisher_err = rel_err(ctx.fvp(th, vs[0].float().cuda()).cpu().numpy(), refs[0].numpy())
+    torch.cuda.synchronize()
+    eg = rel_err(g32.cpu().numpy(), gkl.numpy())
+    report(name, kl=float(k32), kl_ref=kl, kl_grad_rel=eg, hvp_rel=errs, fisher_form_rel=fisher_err)
+    assert abs(float(k32) - kl) < 1e-5 * max(kl, 1e-3)
+    assert eg < 1e-4
+    assert max(errs) < 1e-3
+    assert fisher_err > 10 * max(errs)
+
+
+@pytest.mark.parametrize('K', [2, 3])
+@pytest.mark.parametrize('act', ['tanh', 'relu'])
+def test_general_kl_hvp_steps_matches_autograd(act, K):
+    """KL value, KL gradient (mean_t lam_0) and two Hessian-vector products against the oracle at inner_lr = 0.1; the Fisher
+    form must miss the reference (the oracle alone puts it at 0.08 .. 0.35 here)."""
+    _check_against_autograd(f'general_kl_hvp_steps[{act}-K{K}]', act, K, False)
+
+
+def test_general_kl_hvp_steps_ragged_replays():
+    """The same at tanh, K = 2 with one support replay of update 1 and one query replay a whole episode short: `count` in every launch."""
+    _check_against_autograd('general_kl_hvp_steps[ragged]', 'tanh', 2, True)
+
+
+def test_general_kl_hvp_steps_batched_equals_task_by_task():
+    """The 4-task product is the mean of four 1-task products (damping 0): every task reads its own theta_k, u_k, lam_{k+1} and
+    sweeps.  The per-task arithmetic is the same in both runs; only the mean over tasks is rounded differently (1e-5)."""
+    v = _reference('tanh', 2, 0.1)[2][0].float().cuda()
+    ctx, th = _context('tanh', 2, 0.1)
+    ctx.evaluate(th, want_grad=True)
+    g_all = ctx.prepare_general_kl(th, want_grad=True)
+    h_all = ctx.fvp(th, v, damping=0.0).cpu().numpy()
+    g_one, h_one = [], []
+    for t in range(PARAMS['meta_batch_size']):
+        c1, _ = _context('tanh', 2, 0.1, tasks=[t])
+        c1.evaluate(th, want_grad=True)
+        g_one.append(c1.prepare_general_kl(th, want_grad=True).cpu().numpy())
+        h_one.append(c1.fvp(th, v, damping=0.0).cpu().numpy())
+    eg, eh = rel_err(g_all.cpu().numpy(), np.mean(g_one, axis=0)), rel_err(h_all, np.mean(h_one, axis=0))
+    spread = max(rel_err(h, h_all) for h in h_one)
+    report('general_kl_hvp_steps_batched_vs_single', kl_grad_rel=eg, hvp_rel=eh, task_spread=spread)
+    assert spread > 1e-2                 # the tasks' products differ: a stride taken as shared would show
+    assert eg < 1e-5 and eh < 1e-5
+
+
+def test_general_kl_steps_entry_points_at_one_step_equal_the_one_step_path():
+    """steps = 1 through mi_trpo_surrogate_steps / mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps equals mi_trpo_surrogate /
+    mi_trpo_kl_prepare / mi_trpo_fvp_general on the same inputs.  tanh: every third-derivative term is live, and both routes run
+    the same per-layer kernels (a ReLU policy's one-step surrogate goes through the fused sweeps, another summation order)."""
+    theta, replays, olds = _replays_tanh(anil=True)
+    pol = _policy_tanh(theta)
+    ctx = _SurrogateContext(replays, [_policy_tanh(o) for o in olds], pol, cf.LinearValue(2, 2), PARAMS)
+    assert ctx.steps == 1
+    th, eng = pol.flat(), ctx.engine
+    v = torch.randn(th.shape, generator=torch.Generator().manual_seed(5), dtype=torch.float64).float().cuda()
+    eng.surrogate(th, ctx.sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, True)
+    g1 = eng.kl_prepare(th, ctx.sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, want_grad=True).cpu().numpy()
+    h1 = eng.fvp_general(th, ctx.sup, ctx.qry, ctx.old_scale, ctx.inner_lr, 1e-5, v).cpu().numpy()
+    sup = {k: ctx.sup[k].unsqueeze(0).contiguous() for k in ('states', 'actions', 'adv', 'count')}
+    eng.surrogate_steps(th, sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, True)
+    gs = eng.kl_prepare_steps(sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, want_grad=True).cpu().numpy()
+    hs = eng.fvp_general_steps(sup, ctx.qry, ctx.old_scale, ctx.inner_lr, 1e-5, v).cpu().numpy()
+    eg, eh = rel_err(gs, g1), rel_err(hs, h1)
+    report('general_kl_steps_at_one_step', kl_grad_rel=eg, hvp_rel=eh)
+    assert eg < 1e-6 and eh < 1e-6
+
+
+def test_meta_optimize_anil_trpo_two_steps_matches_oracle():
+    """One whole ANIL-TRPO meta-optimisation with adapt_steps = 2 (tanh, inner_lr 0.01 as in rl/anil_trpo.py) against the oracle:
+    same accepted line-search index, gradient within 1e-5, step within the oracle's own sensitivity to fp32-rounded products."""
+    P, _, theta, replays, olds = _case('tanh', 2, 0.01)
+    p64 = OrderedDict((k, v.clone().requires_grad_(True)) for k, v in theta.items())
+    ref = RL.meta_optimize_trpo(P, p64, RL.LinearValue(2, 2), replays, olds, activation=torch.tanh)
+    assert ref['accepted'] == 0
+    pol = _anil_policy(theta)
+    out = cf.meta_optimize_trpo(P, pol, cf.LinearValue(2, 2), replays, [_anil_policy(o) for o in olds], anil=True)
+    es = rel_err(out['step'].cpu().numpy(), ref['step'].numpy())
+    eg = rel_err(out['grad'].cpu().numpy(), ref['grad'].numpy())
+    r32 = lambda x: x.float().double()            # the oracle's own sensitivity: its fp64 products and right-hand side rounded to fp32
+    s32 = RL.conjugate_gradient(lambda v: r32(ref['fvp'](r32(v))), r32(ref['grad']))
+    s32 = s32 / torch.sqrt(0.5 * torch.dot(s32, ref['fvp'](s32)) / P['max_kl'])
+    e32 = rel_err(s32.numpy(), ref['step'].numpy())
+    report('meta_optimize_anil_trpo_two_steps', step_rel=es, grad_rel=eg, step_rel_oracle_with_fp32_rounded_products=e32,
+           accepted=out['accepted'], accepted_ref=ref['accepted'])
+    assert out['accepted'] == ref['accepted']
+    assert eg < 1e-5
+    assert es <= max(2e-2, 4 * e32 + 2 * (e32 / 6e-8) * eg)
+
+
+@pytest.mark.parametrize('rollout', ['host', 'device'])
+def test_anil_trpo_driver_runs_with_two_adapt_steps(rollout, monkeypatch):
+    """rl/anil_trpo.py --adapt_steps 2 end to end: two meta-iterations complete and move the parameters."""
+    from exploring_meta_amd.rl import anil_trpo, maml_trpo
+    p = dict(anil_trpo.params, adapt_steps=2, meta_batch_size=4, adapt_batch_size=6, max_path_length=25, num_iterations=2)
+    first, real = [], maml_trpo.meta_optimize_trpo
+
+    def spy(params, policy, *a, **k):              # the parameters the first meta-optimisation starts from
+        if not first:
+            first.append(policy.flat().detach().cpu().clone())
+        return real(params, policy, *a, **k)
+    monkeypatch.setattr(maml_trpo, 'meta_optimize_trpo', spy)
+    lines = []
+    policy = maml_trpo.run(p, log=lines.append, anil=True, rollout=rollout)
+    flat = policy.flat().detach().cpu()
+    assert len(lines) == 2
+    assert bool(torch.isfinite(flat).all())
+    assert not torch.equal(flat, first[0])
