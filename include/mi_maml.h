@@ -489,6 +489,15 @@ typedef struct {
                          DiagNormalPolicyANIL body, policies.py:76) */
 } mi_policy_desc;
 
+/* Accepted domain: state_size >= 1, hidden1 >= 1, hidden2 >= 1 (the two widths need not be equal), action_size 1 .. 6, activation 0 or 1;
+ * anything else is MI_ERR_ARG with a text in mi_policy_last_error(NULL), and *out is left alone.  Every mi_policy_* / mi_trpo_* entry
+ * below takes every policy of this domain (mi_particles_rollout alone is narrower: see there).
+ * Which kernels run: a policy with hidden1 == hidden2 == 100, ReLU, state_size <= 4 (any action_size) takes the fused sweeps of
+ * csrc/policy_sweep.h in mi_trpo_surrogate and mi_trpo_fvp (mi_policy_set_fused_fvp(0) switches them off).  Every other shape, and every
+ * other entry point at any shape, runs the per-layer kernels of csrc/policy.hip: one dense product per layer and pass for all tasks
+ * (operand loads of 16 bytes where the reduction width is a multiple of 4 and at least 16, of 8 bytes where it and its half are even and
+ * the operands 8-byte aligned, scalar otherwise) and one weight-gradient launch per layer with the bias as column I of an (I + 1)-wide
+ * tile grid.  tests/test_gpu_policy_shapes.py holds the per-layer path to fp64 autograd at widths from 1 to 160. */
 int mi_policy_create(const mi_policy_desc* desc, int device, mi_policy** out);
 void mi_policy_destroy(mi_policy* p);
 const char* mi_policy_last_error(const mi_policy* p);

@@ -1,0 +1,291 @@
+"""The policy path (csrc/policy.hip through PolicyEngine) at hidden, state and action widths other than 2-100-100-2, against fp64
+autograd (tests/policy_shapes_oracle.py; its cases say which operand path of dense_mfma_kernel and which tile condition of
+dense_wgrad_mfma_kernel each one reaches).  None of these shapes takes the fused sweeps (H1 == H2 == 100, ReLU): every launch is a
+per-layer kernel, and H1 != H2 in all but one case, so a swapped width in a workspace plan or a launch sequence shows.
+
+Every vector over the parameters is compared block by block (sigma, W1, b1, W2, b2, W3, b3): a wrong bias column or a swapped width
+moves a small block that a whole-vector norm would hide.  Bars (the project's own, test_gpu_rl.py / test_gpu_anil_trpo_steps.py):
+loss and KL 1e-5 max(1, |ref|), KL in the Fisher case 1e-6 absolute, loc 2e-6 max(1, max|ref|), gradients and parameter steps 1e-4,
+Hessian- and Fisher-vector products 1e-3 relative.  The fp64 oracle run in fp32 on the CPU stays below every block bar on these inputs
+(largest: 5.0e-5 on the W1 block of a parameter step, bias_tile_128x20, where the step is 1e-3 of the parameters it is subtracted
+from), so no block takes an adjusted bar.
+
+Inputs: tests/test_policy_shapes_host.py checks the seeds, the ReLU margins and the nonzero reference blocks on the CPU."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import policy_shapes_oracle as PO
+from gpu_utils import rel_err, report
+
+pytestmark = pytest.mark.gpu
+
+NAMES = list(PO.CASES)
+LR, DAMPING, CLIP = PO.INNER_LR, PO.DAMPING, PO.CLIP
+BODY = ('W1', 'b1', 'W2', 'b2')
+
+
+def _f(x):
+    return torch.as_tensor(x).to(torch.float32).cuda().contiguous()
+
+
+def _batch(b):
+    return dict(states=_f(b['states']), actions=_f(b['actions']), adv=_f(b['adv']), done=_f(b['done']),
+                count=b['count'].to(torch.int32).cuda().contiguous())
+
+
+@functools.lru_cache(maxsize=None)
+def _setup(name):
+    """(inputs, references, engine, device batches) of a case; the references are computed once and only read."""
+    from exploring_meta_amd.engine import PolicyEngine
+    inp, ref, _ = PO.reference(name)
+    eng = PolicyEngine(inp['S'], inp['A'], inp['H'], activation=inp['activation'])
+    assert eng.param_count == inp['theta'].numel()
+    dev = dict(theta=_f(inp['theta']), cand=_f(inp['cand']), sup=_batch(inp['sup']), qry=_batch(inp['qry']),
+               sup0=_batch(PO.sup_k(inp, 0)))
+    return inp, ref, eng, dev
+
+
+def _slices(inp):
+    return PO.block_slices(inp['S'], inp['A'], *inp['H'])
+
+
+def _blocks(inp, got, ref, unchanged=()):
+    """Relative error of every parameter block; the reference block must not vanish.  ``unchanged``: blocks that must be exactly zero."""
+    got, ref = torch.as_tensor(got).detach().double().cpu(), torch.as_tensor(ref).double()
+    errs = {}
+    for k, s in _slices(inp).items():
+        if k in unchanged:
+            assert float(ref[s].abs().max()) == 0.0 and float(got[s].abs().max()) == 0.0, k
+            continue
+        assert float(ref[s].norm()) > 0.0, k
+        errs[k] = rel_err(got[s].numpy(), ref[s].numpy())
+    return errs
+
+
+def _worst(errs_list):
+    out = {}
+    for e in errs_list:
+        for k, v in e.items():
+            out[k] = max(out.get(k, 0.0), v)
+    return out
+
+
+def _scalar_ok(got, ref, bar=1e-5):
+    return abs(float(got) - float(ref)) <= bar * max(1.0, abs(float(ref)))
+
+
+def _loc_ok(got, ref, count):
+    worst, top = 0.0, 0.0
+    for t in range(ref.shape[0]):
+        n = int(count[t])
+        worst = max(worst, float((got[t, :n].double().cpu() - ref[t, :n]).abs().max()))
+        top = max(top, float(ref[t, :n].abs().max()))
+    return worst, worst <= 2e-6 * max(1.0, top)
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_forward(name):
+    """loc with shared parameters and with one parameter vector per task (the adapted ones), on the valid rows."""
+    inp, ref, eng, dev = _setup(name)
+    e1, ok1 = _loc_ok(eng.forward(dev['theta'], dev['qry']['states']), ref['loc'], inp['qry']['count'])
+    e2, ok2 = _loc_ok(eng.forward(_f(ref['theta_tasks']), dev['qry']['states']), ref['loc_tasks'], inp['qry']['count'])
+    report(f'policy_shapes_forward[{name}]', loc_abs_shared=e1, loc_abs_per_task=e2)
+    assert ok1 and ok2, (e1, e2)
+
+
+@pytest.mark.parametrize('head_only', [False, True])
+@pytest.mark.parametrize('name', NAMES)
+def test_adapt(name, head_only):
+    """theta_out - theta per task and block, and the loss; head_only leaves the hidden layers' blocks bit-identical."""
+    inp, ref, eng, dev = _setup(name)
+    b = dev['sup0']
+    out, loss = eng.adapt(dev['theta'], b['states'], b['actions'], b['adv'], b['count'], LR, head_only=head_only)
+    th_ref, loss_ref = ref['adapt', head_only]
+    step = (out - dev['theta']).cpu()
+    errs = _worst([_blocks(inp, step[t], th_ref[t] - inp['theta'], BODY if head_only else ()) for t in range(inp['T'])])
+    el = max(abs(float(loss[t]) - float(loss_ref[t])) / max(1.0, abs(float(loss_ref[t]))) for t in range(inp['T']))
+    report(f'policy_shapes_adapt[{name},head_only={head_only}]', loss_rel=el, step_rel=errs)
+    assert bool(torch.isfinite(out).all()) and el <= 1e-5
+    assert max(errs.values()) < 1e-4, errs
+
+
+def _trpo(name, K, case):
+    """surrogate (loss, KL, gradient), a line-search evaluation at a displaced theta, and the product of the mean KL's Hessian with two
+    directions: `fisher` (old = the adapted policy: mi_trpo_fvp*) or `general` (old = the head-only adapted policy: mi_trpo_kl_prepare* +
+    mi_trpo_fvp_general*), through the one-step entry points (K = 1) or the *_steps ones (K = 2)."""
+    inp, ref, eng, dev = _setup(name)
+    r = ref['trpo', K, case]
+    th, qry = dev['theta'], dev['qry']
+    old_loc, old_scale = _f(r['old_loc']), _f(r['old_scale'])
+    if K == 1:
+        sup = dev['sup0']
+        surrogate = lambda x, g: eng.surrogate(x, sup, qry, old_loc, old_scale, LR, g)
+        fvp = lambda v: eng.fvp(th, sup, qry, LR, DAMPING, v)
+        prepare = lambda: eng.kl_prepare(th, sup, qry, old_loc, old_scale, LR, want_grad=True)
+        fvp_general = lambda v: eng.fvp_general(th, sup, qry, old_scale, LR, DAMPING, v)
+    else:
+        sup = {k: dev['sup'][k] for k in ('states', 'actions', 'adv', 'count')}
+        assert sup['states'].shape[0] == K
+        surrogate = lambda x, g: eng.surrogate_steps(x, sup, qry, old_loc, old_scale, LR, g)
+        fvp = lambda v: eng.fvp_steps(sup, qry, LR, DAMPING, v)
+        prepare = lambda: eng.kl_prepare_steps(sup, qry, old_loc, old_scale, LR, want_grad=True)
+        fvp_general = lambda v: eng.fvp_general_steps(sup, qry, old_scale, LR, DAMPING, v)
+    lc, kc, _ = surrogate(dev['cand'], False)                       # the line search's call: values only
+    lc, kc = float(lc), float(kc)
+    loss, kl, grad = surrogate(th, True)                            # back at theta: the products below read its passes
+    rep = dict(loss=float(loss), loss_ref=float(r['loss']), kl=float(kl), kl_ref=float(r['kl']), cand_loss=lc, cand_loss_ref=float(r['cand_loss']),
+               cand_kl=kc, cand_kl_ref=float(r['cand_kl']), grad_rel=_blocks(inp, grad, r['grad']))
+    if case == 'general':
+        assert float(r['kl']) > 1e-6                                # new != old: this is not the Fisher case
+        rep['kl_grad_rel'] = _blocks(inp, prepare(), r['kl_grad'])
+        hv = [fvp_general(_f(v)).clone() for v in r['v']]
+    else:
+        hv = [fvp(_f(v)).clone() for v in r['v']]
+    torch.cuda.synchronize()
+    rep['hvp_rel'] = [_blocks(inp, h, h_ref) for h, h_ref in zip(hv, r['hv'])]
+    report(f'policy_shapes_trpo[{name},K={K},{case}]', **rep)
+    assert _scalar_ok(loss, r['loss']) and _scalar_ok(lc, r['cand_loss']) and _scalar_ok(kc, r['cand_kl'])
+    assert abs(float(kl) - float(r['kl'])) <= 1e-6 if case == 'fisher' else _scalar_ok(kl, r['kl'])
+    assert max(rep['grad_rel'].values()) < 1e-4, rep['grad_rel']
+    if case == 'general':
+        assert max(rep['kl_grad_rel'].values()) < 1e-4, rep['kl_grad_rel']
+    assert all(bool(torch.isfinite(h).all()) for h in hv)
+    assert max(max(e.values()) for e in rep['hvp_rel']) < 1e-3, rep['hvp_rel']
+
+
+@pytest.mark.parametrize('case', ['fisher', 'general'])
+@pytest.mark.parametrize('name', NAMES)
+def test_trpo_one_step(name, case):
+    _trpo(name, 1, case)
+
+
+@pytest.mark.parametrize('case', ['fisher', 'general'])
+@pytest.mark.parametrize('name', NAMES)
+def test_trpo_two_steps(name, case):
+    _trpo(name, 2, case)
+
+
+@pytest.mark.parametrize('kind,head_only', [('a2c', False), ('a2c', True), ('ppo', False), ('dice', False)])
+@pytest.mark.parametrize('name', NAMES)
+def test_meta_batch(name, kind, head_only):
+    """Two second-order updates on two support batches, validation loss and the meta-gradient summed over tasks."""
+    inp, ref, eng, dev = _setup(name)
+    loss, th_out, grad = eng.meta_batch(dev['theta'], dev['sup'], dev['qry'], [0, 1], LR, loss=kind, clip=CLIP, head_only=head_only,
+                                        first_order=False, with_grad=True)
+    loss_ref, th_ref, grad_ref = ref['meta', kind, head_only]
+    step = (th_out - dev['theta']).cpu()
+    es = _worst([_blocks(inp, step[t], th_ref[t] - inp['theta'], BODY if head_only else ()) for t in range(inp['T'])])
+    eg = _blocks(inp, grad, grad_ref)
+    el = max(abs(float(loss[t]) - float(loss_ref[t])) / max(1.0, abs(float(loss_ref[t]))) for t in range(inp['T']))
+    report(f'policy_shapes_meta[{name},{kind},head_only={head_only}]', loss_rel=el, step_rel=es, grad_rel=eg)
+    assert el <= 1e-5
+    assert max(es.values()) < 1e-4, es
+    assert max(eg.values()) < 1e-4, eg
+
+
+@pytest.mark.parametrize('kind', ['a2c', 'ppo'])
+@pytest.mark.parametrize('name', NAMES)
+def test_update_two_epochs(name, kind):
+    """mi_policy_update with epochs = 2 (PPO: the old log-probabilities stay those of the first epoch): parameters and both losses."""
+    inp, ref, eng, dev = _setup(name)
+    b = dev['sup0']
+    out, losses = eng.update(dev['theta'], b['states'], b['actions'], b['adv'], b['count'], LR, loss=kind, epochs=2, clip=CLIP)
+    th_ref, loss_ref = ref['update', kind]
+    step = (out - dev['theta']).cpu()
+    es = _worst([_blocks(inp, step[t], th_ref[t] - inp['theta']) for t in range(inp['T'])])
+    el = float(((losses.double().cpu() - loss_ref).abs() / loss_ref.abs().clamp(min=1.0)).max())
+    report(f'policy_shapes_update[{name},{kind}]', loss_rel=el, step_rel=es)
+    assert el <= 1e-5
+    assert max(es.values()) < 1e-4, es
+
+
+def test_python_surface_at_8_12_50_2(monkeypatch):
+    """DiagNormalPolicy(8, 2, [12, 50]) on the GPU: density and log_prob on a task's rows, and cf.trpo_update on a synthetic replay of the
+    same states and actions (rewards, dones and next states drawn here; the advantages take the host path, fp64, on both sides)."""
+    from exploring_meta_amd import core_functions as cf
+    from exploring_meta_amd.core_functions import rl as rlm
+    from oracle import rl_ref as RL
+    inp, ref, _, _ = _setup('k8_12x50')
+    o = PO.Oracle(8, 2, (12, 50), 'relu')
+    pol = cf.DiagNormalPolicy(8, 2, [12, 50]).cuda()
+    pol.load_flat(_f(inp['theta']))
+    assert torch.equal(pol.flat().cpu(), inp['theta'].float())
+    s0 = PO.sup_k(inp, 0)
+    n = int(s0['count'][1])
+    st, ac = s0['states'][1, :n], s0['actions'][1, :n]
+    p = o.unflat(inp['theta'])
+    loc_ref, scale_ref = o.loc_scale(p, st)
+    lp_ref = o.log_prob(p, st, ac)
+    d = pol.density(_f(st))
+    lp = pol.log_prob(_f(st), _f(ac))
+    e_loc = float((d.loc.double().cpu() - loc_ref).abs().max())
+    e_lp = float(((lp.double().cpu() - lp_ref).abs() / lp_ref.abs().clamp(min=1.0)).max())
+    assert e_loc <= 2e-6 * max(1.0, float(loc_ref.abs().max()))
+    assert np.allclose(d.scale.cpu().numpy(), scale_ref.numpy(), rtol=1e-6)
+    assert lp.shape == (n, 1) and e_lp <= 1e-5
+    # trpo_update: the reference's call, one replay
+    g = torch.Generator().manual_seed(77)
+    dones = (torch.rand(n, 1, generator=g, dtype=torch.float64) < 0.1).double()
+    dones[n - 1] = 1.0
+    ep = dict(states=st, actions=ac, rewards=PO._f32(-torch.rand(n, 1, generator=g, dtype=torch.float64)), dones=dones,
+              next_states=PO._f32(torch.randn(n, 8, generator=g, dtype=torch.float64)))
+    adv = RL.normalize(RL.compute_advantages(RL.LinearValue(8, 2), 1.0, 0.99, ep)).detach()
+    batch = dict(states=st[None], actions=ac[None], adv=adv.reshape(1, n), count=torch.tensor([n], dtype=torch.int32))
+    th_ref, _ = o.adapt(inp['theta'], batch, lr=LR)
+    assert o.margin >= PO.MARGIN
+    monkeypatch.setattr(rlm, '_gae_on_device', lambda *a, **k: False)
+    new = cf.trpo_update({k: v.float() for k, v in ep.items()}, pol, cf.LinearValue(8, 2), LR, 0.99, 1.0)
+    es = _blocks(inp, new.flat().cpu() - pol.flat().cpu(), th_ref[0] - inp['theta'])
+    report('policy_shapes_surface[8-12-50-2]', loc_abs=e_loc, log_prob_rel=e_lp, step_rel=es)
+    assert max(es.values()) < 1e-4, es
+
+
+def test_sigma_below_the_clamp():
+    """sigma[1] = -15 < log(1e-6) at 4-33-7-6, tanh: scale = exp(max(sigma, log 1e-6)) does not depend on that entry, so its gradient and
+    its curvature are exactly zero (the `rp > LOG_EPS` branches of gauss_kernel and of the folds): adapt returns the entry bit-identical
+    and the Fisher-vector product returns damping * v for it.  Everything is finite and every other block meets the bars.
+    Step sizes: the clamped dimension's 1 / scale^2 = 1e12 multiplies every gradient; adapt runs at the other tests' lr = 0.1 (a step far
+    larger than the parameters: no cancellation in theta_out - theta), the surrogate's inner step at 0.1 * 1e-12, which keeps theta_1 where
+    the other cases have it.  The old policy comes from the engine's own adapt + forward, as the drivers take it (at scale 1e-6 one ulp of
+    loc moves the log-ratio by ~1e4: only the engine's own loc gives ratio 1); the surrogate's loss and KL must be finite."""
+    inp, _, eng, dev = _setup('a6_33x7')
+    sl = _slices(inp)
+    theta = inp['theta'].clone()
+    theta[1] = -15.0
+    th, s0, qry = _f(theta), PO.sup_k(inp, 0), dev['qry']
+    o = PO.Oracle(inp['S'], inp['A'], inp['H'], 'tanh')
+    b = dev['sup0']
+    # adapt
+    out, loss = eng.adapt(th, b['states'], b['actions'], b['adv'], b['count'], LR)
+    th_ref, loss_ref = o.adapt(theta, s0, lr=LR)
+    assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(loss).all())
+    assert torch.equal(out[:, 1], th[1].expand(inp['T']))
+    step = (out - th).cpu()
+    es = _worst([_blocks(inp, step[t], th_ref[t] - theta) for t in range(inp['T'])])
+    el = max(abs(float(loss[t]) - float(loss_ref[t])) / max(1.0, abs(float(loss_ref[t]))) for t in range(inp['T']))
+    # Fisher-vector product after a surrogate call with a unit-sized inner step
+    lr = LR * 1e-12
+    old_theta, _ = eng.adapt(th, b['states'], b['actions'], b['adv'], b['count'], lr)
+    old_loc = eng.forward(old_theta, qry['states'])
+    old_scale = torch.exp(torch.clamp(old_theta[:, :inp['A']], min=float(np.log(1e-6)))).contiguous()
+    sloss, skl, _ = eng.surrogate(th, b, qry, old_loc, old_scale, lr, True)
+    assert bool(torch.isfinite(sloss).all()) and bool(torch.isfinite(skl).all())
+    ol64, os64 = o.adapted_density(theta, [s0], inp['qry'], lr=lr)
+    r = o.surrogate(theta, [s0], inp['qry'], ol64, os64, lr=lr)
+    vs = PO.directions(inp, r['grad'])
+    hv = [eng.fvp(th, b, qry, lr, DAMPING, _f(v)).clone() for v in vs]
+    torch.cuda.synchronize()
+    eh = []
+    for h, v in zip(hv, vs):
+        assert bool(torch.isfinite(h).all())
+        assert abs(float(h[1]) - DAMPING * float(v[1])) <= 1e-6 * abs(DAMPING * float(v[1]))
+        e = _blocks(inp, h, r['hvp'](v))
+        del e['sigma']
+        eh.append(e)
+    report('policy_shapes_sigma_clamp', adapt_loss_rel=el, adapt_step_rel=es, hvp_rel=eh, surrogate_loss=float(sloss), surrogate_kl=float(skl))
+    del es['sigma']
+    assert el <= 1e-5 and max(es.values()) < 1e-4, (el, es)
+    assert max(max(e.values()) for e in eh) < 1e-3, eh
