@@ -184,6 +184,13 @@ _SIGS = {
                                                    C.c_size_t]),
     'mi_policy_set_fused_fvp': (C.c_int, [C.c_int]),
     'mi_debug_policy_sweep_stamps': (C.c_int, [C.c_void_p]),
+    'mi_policy_learner_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    'mi_policy_vjp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                C.c_void_p, C.c_void_p, C.c_size_t]),
+    'mi_policy_hvp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    'mi_policy_set_fused_learner': (C.c_int, [C.c_int]),
+    'mi_policy_learner_fused_supported': (C.c_int, [C.c_void_p]),
     'mi_debug_conv_stamps': (C.c_int, [C.c_void_p]),
     'mi_conv_set_split_bf16': (C.c_int, [C.c_int]),
     'mi_conv_get_split_bf16': (C.c_int, [C.POINTER(C.c_uint)]),

@@ -9,7 +9,16 @@ starts every task from the base parameters (the semantics of learn2learn's ``clo
 The step-wise surface (``learner(x)``, ``learner.adapt(loss)``, ``get_rep``, ``get_rep_i`` -- what the reference's
 misc_scripts/cl_vision.py and rc_vision.py drive) holds the fast weights as one flat tensor and runs every forward /
 gradient through ``mi_learner_forward`` / ``mi_learner_backward``.
+
+Around a policy (``DiagNormalPolicy`` / ``DiagNormalPolicyANIL``) the wrapper is a step-wise learner too (the reference's
+misc_scripts/cl_rl.py:71-75: ``learner.adapt(vpg_a2c_loss(episodes, learner, ...))``): ``learner.log_prob`` / ``learner.density``
+run on the fast weights through ``mi_policy_forward`` / ``mi_policy_vjp`` / ``mi_policy_hvp`` whenever a graph is wanted (grad mode
+on and parameters that require grad) or the learner has been adapted.  ``learner(state)`` samples and never builds a graph; a
+learner that was never adapted acts through the bare policy exactly as before.
 """
+import copy
+
+
 import torch
 
 
@@ -35,11 +44,57 @@ class MAML(torch.nn.Module):
             self.__dict__['_fast'] = self.module.flat_parameters()
         return self.__dict__['_fast']
 
+    def _is_policy(self):
+        return hasattr(self.module, 'density') and hasattr(self.module, 'flat_parameters')
+
+    def _policy_theta(self):
+        """Fast weights for a policy call, or None for the bare (detached) policy: the fast weights once the learner has them (after
+        ``adapt`` / ``fast_weights``), or the parameters themselves when the caller can differentiate the result."""
+        fast = self.__dict__['_fast']
+        if fast is not None:
+            return fast
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.module.parameters()):
+            return self.module.flat_parameters()          # not kept: a learner that was never adapted holds no state
+        return None
+
     def forward(self, x):
-        """`learner(x)`: the module evaluated with this learner's current fast weights (mi_learner_forward)."""
+        """`learner(x)`: the module evaluated with this learner's current fast weights (mi_learner_forward); for a policy, an action
+        sampled from the density at the fast weights (no graph; the bare policy until the learner has fast weights)."""
+        if self._is_policy():
+            fast = self.__dict__['_fast']
+            return self.module(x) if fast is None else self.module(x, theta=fast)
         if not hasattr(self.module, 'flat_parameters'):
             return self.module(x)
         return self.module(x, theta=self.fast_weights())
+
+    def density(self, state):
+        """policies.py:49-52 at this learner's fast weights (see ``_policy_theta``)."""
+        theta = self._policy_theta()
+        return self.module.density(state) if theta is None else self.module.density(state, theta=theta)
+
+    def log_prob(self, state, action):
+        """policies.py:54-56 at this learner's fast weights; differentiable to second order (mi_policy_vjp / mi_policy_hvp)."""
+        theta = self._policy_theta()
+        return self.module.log_prob(state, action) if theta is None else self.module.log_prob(state, action, theta=theta)
+
+    def adapted_policy(self):
+        """A detached copy of the policy holding this learner's current fast weights (for rollouts: runners act with a bare policy)."""
+        pol = copy.deepcopy(self.module)
+        fast = self.__dict__['_fast']
+        if fast is not None:
+            pol.load_flat(fast.detach().float().contiguous())
+        return pol
+
+    def __deepcopy__(self, memo):
+        """nn.Module's default copy, with the fast weights (a graph node, which torch refuses to deep-copy) taken as detached values."""
+        fast = self.__dict__['_fast']
+        if fast is not None and not fast.is_leaf:
+            memo[id(fast)] = fast.detach().clone()
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = copy.deepcopy(v, memo)
+        return new
 
     def clone(self, first_order=None, allow_unused=None, allow_nograd=None):
         """reference core_functions/maml.py:23-49 (learn2learn clone_module: the clone starts from the CURRENT weights of
@@ -67,11 +122,20 @@ class MAML(torch.nn.Module):
         if first_order is None:
             first_order = self.first_order
         second_order = not first_order
+        if allow_unused is None:
+            allow_unused = self.allow_unused
+        if self.__dict__['_fast'] is None and self._is_policy():
+            # first step of a policy learner: the loss came from the parameters themselves (``_policy_theta``)
+            params = self.module._engine_params()
+            gs = torch.autograd.grad(loss, params, retain_graph=second_order, create_graph=second_order, allow_unused=bool(allow_unused))
+            g = torch.cat([(torch.zeros_like(p) if gi is None else gi).reshape(-1) for p, gi in zip(params, gs)])
+            self.__dict__['_fast'] = self.module.flat_parameters() - self.lr * g
+            return
         theta = self.fast_weights()
         if not theta.requires_grad:
             raise RuntimeError('learner.adapt needs parameters that require grad')
-        (g,) = torch.autograd.grad(loss, theta, retain_graph=second_order, create_graph=second_order)
-        self.__dict__['_fast'] = theta - self.lr * g
+        (g,) = torch.autograd.grad(loss, theta, retain_graph=second_order, create_graph=second_order, allow_unused=bool(allow_unused))
+        self.__dict__['_fast'] = theta if g is None else theta - self.lr * g
 
     def get_rep(self, input_d):
         """reference core_functions/maml.py:15-16"""

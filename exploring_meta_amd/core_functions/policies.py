@@ -1,5 +1,9 @@
 """``DiagNormalPolicy`` / ``DiagNormalPolicyANIL`` with the reference's constructors, parameter names/order and initialisers
-(core_functions/policies.py:30-67,70-126); the MLP runs on the GPU through ``mi_policy_forward``."""
+(core_functions/policies.py:30-67,70-126); the MLP runs on the GPU through ``mi_policy_forward``.
+
+Two call paths.  The bare policy (``policy.density(state)``, ``policy.log_prob(state, action)``, ``policy(state)``) is detached, as the
+fused training calls use it.  With ``theta=`` (what a ``MAML`` wrapper passes: its fast weights, a flat vector in engine order) the mean
+is a node of the autograd graph, differentiable to second order: first backward ``mi_policy_vjp``, second ``mi_policy_hvp``."""
 import math
 
 import torch
@@ -11,6 +15,54 @@ from ..engine import PolicyEngine
 EPSILON = 1e-6
 
 _engines = {}
+
+
+class _ThirdOrderGuard(torch.autograd.Function):
+    """The results of mi_policy_hvp as functions of (theta, dloc, v) in the graph, with a backward that says what is missing."""
+
+    @staticmethod
+    def forward(ctx, theta, dloc, v, hv, loc_dot):
+        return hv.view_as(hv), loc_dot.view_as(loc_dot)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        raise RuntimeError('the HIP policy differentiates to second order (mi_policy_vjp, mi_policy_hvp); a third derivative of '
+                           'density / log_prob with respect to the parameters is not implemented')
+
+
+class _PolicyLocVJP(torch.autograd.Function):
+    """g = J(theta)^T dloc (mi_policy_vjp); its backward for a cotangent v on g is ONE mi_policy_hvp call:
+    d(g.v)/dtheta = (d^2 s / dtheta^2) v and d(g.v)/ddloc = J v."""
+
+    @staticmethod
+    def forward(ctx, theta, dloc, states, engine, head_only):
+        ctx.engine, ctx.head_only = engine, head_only
+        ctx.save_for_backward(theta, dloc, states)
+        return engine.vjp(theta.detach(), states, dloc.detach(), head_only=head_only)[0].to(theta.dtype)
+
+    @staticmethod
+    def backward(ctx, v):
+        theta, dloc, states = ctx.saved_tensors
+        hv, loc_dot = ctx.engine.hvp(theta.detach(), states, dloc.detach(), v.detach().reshape(1, -1), head_only=ctx.head_only)
+        hv, loc_dot = hv[0].to(theta.dtype), loc_dot.to(dloc.dtype)
+        if torch.is_grad_enabled():
+            hv, loc_dot = _ThirdOrderGuard.apply(theta, dloc, v, hv, loc_dot)
+        return hv, loc_dot, None, None, None
+
+
+class _PolicyLoc(torch.autograd.Function):
+    """loc [1, B, A] = MLP(theta; states [1, B, S]) (mi_policy_forward: the bits of the bare path).  States get no gradient."""
+
+    @staticmethod
+    def forward(ctx, theta, states, engine, head_only):
+        ctx.engine, ctx.head_only = engine, head_only
+        ctx.save_for_backward(theta, states)
+        return engine.forward(theta.detach(), states)
+
+    @staticmethod
+    def backward(ctx, dloc):
+        theta, states = ctx.saved_tensors
+        return _PolicyLocVJP.apply(theta, dloc.contiguous(), states, ctx.engine, ctx.head_only), None, None, None
 
 
 def linear_init(module):
@@ -81,20 +133,36 @@ class DiagNormalPolicy(nn.Module):
                 p.copy_(theta[off:off + p.numel()].view_as(p))
                 off += p.numel()
 
-    def density(self, state):
-        """reference policies.py:49-52"""
+    def flat_parameters(self):
+        """The flat vector in the engine's order, CONNECTED to the parameters (what a ``MAML`` wrapper starts its fast weights from)."""
+        return torch.cat([p.reshape(-1) for p in self._engine_params()])
+
+    def density(self, state, theta=None):
+        """reference policies.py:49-52.  ``theta`` None: the module's own parameters, detached.  ``theta`` [P] (engine order): loc
+        through the differentiable HIP unit (``features_no_grad`` -> head_only: the body is a constant), scale = exp(clamp(sigma)) as
+        plain torch ops on theta's sigma slots."""
         st = state.reshape(1, -1, self.input_size).float().contiguous()
-        loc = self.engine().forward(self.flat(), st)[0].reshape(*state.shape[:-1], self.output_size)
-        scale = torch.exp(torch.clamp(self.sigma.detach(), min=math.log(EPSILON)))
+        if theta is None:
+            loc = self.engine().forward(self.flat(), st)[0].reshape(*state.shape[:-1], self.output_size)
+            scale = torch.exp(torch.clamp(self.sigma.detach(), min=math.log(EPSILON)))
+            return Normal(loc=loc, scale=scale)
+        if theta.dim() != 1:
+            raise ValueError(f'theta must be a flat parameter vector, got shape {tuple(theta.shape)}')
+        loc = _PolicyLoc.apply(theta, st, self.engine(), bool(getattr(self, 'features_no_grad', False)))
+        loc = loc[0].reshape(*state.shape[:-1], self.output_size)
+        scale = torch.exp(torch.clamp(theta[:self.output_size], min=math.log(EPSILON)))
         return Normal(loc=loc, scale=scale)
 
-    def log_prob(self, state, action):
+    def log_prob(self, state, action, theta=None):
         """reference policies.py:54-56"""
-        return self.density(state).log_prob(action).mean(dim=1, keepdim=True)
+        return self.density(state, theta).log_prob(action).mean(dim=1, keepdim=True)
 
-    def forward(self, state):
-        """reference policies.py:58-61"""
-        return self.density(state).sample()
+    def forward(self, state, theta=None):
+        """reference policies.py:58-61 (sampling never needs a graph)"""
+        if theta is None:
+            return self.density(state).sample()
+        with torch.no_grad():
+            return self.density(state, theta).sample()
 
 
 class DiagNormalPolicyANIL(DiagNormalPolicy):

@@ -422,7 +422,8 @@ def _pad(eps_list, advs, S, A, dev):
 
 # ---------------------------------------------------------------------------------------------- reference functions
 def trpo_a2c_loss(episodes, learner, baseline, gamma, tau, update_vf=True):
-    """reference rl.py:346-358: -mean(log_prob * normalised advantages) (value only; the gradient path is trpo_update)."""
+    """reference rl.py:346-358: -mean(log_prob * normalised advantages).  A value with the bare policy (the gradient path is trpo_update);
+    ``learner.log_prob`` of a ``MAML`` wrapper carries a graph while grad mode is on (core_functions/maml.py), and so does this loss."""
     episodes = _as_replay(episodes)
     dev = learner.sigma.device
     if _gae_on_device(dev, learner.input_size, int(episodes['states'].shape[0])):
@@ -892,14 +893,18 @@ def fast_adapt_vpg(task, learner, baseline, params, anil=False, first_order=Fals
 
 
 def vpg_a2c_loss(episodes, learner, baseline, gamma, tau, dice=False):
-    """reference rl.py:208-228, value only (the gradient path is the fused fast_adapt_vpg): -mean(log_prob * advantages), or with
-    ``dice`` -mean(magic_box(weighted_cumsum(log_probs, weights)) * advantages) = -mean(advantages) (magic_box evaluates to 1)."""
+    """reference rl.py:208-228: -mean(log_prob * advantages).  With a ``MAML`` wrapper as ``learner`` and grad mode on, the loss is
+    differentiable in the learner's fast weights, to second order (``learner.adapt(vpg_a2c_loss(...))``, misc_scripts/cl_rl.py:71-75:
+    mi_policy_vjp / mi_policy_hvp); with the bare policy it is a value (the fused gradient path is fast_adapt_vpg).
+    ``dice``: -mean(magic_box(weighted_cumsum(log_probs, weights)) * advantages) = -mean(advantages) (magic_box evaluates to 1); this
+    branch stays VALUE ONLY on every learner -- the DiCE gradient exists in the fused calls alone (fast_adapt_vpg(dice=True))."""
     episodes = _as_replay(episodes)
     adv = compute_advantages(baseline, tau, gamma, episodes['rewards'], episodes['dones'], episodes['states'], episodes['next_states'])
     adv_t = torch.from_numpy(adv).to(device=device, dtype=torch.float32)
     if dice:
         return -adv_t.mean()
-    lp = _unwrap(learner).log_prob(episodes['states'].to(device), episodes['actions'].to(device))
+    stepwise = hasattr(learner, 'fast_weights') and hasattr(_unwrap(learner), 'flat_parameters')
+    lp = (learner if stepwise else _unwrap(learner)).log_prob(episodes['states'].to(device), episodes['actions'].to(device))
     return -(lp * adv_t).mean()
 
 

@@ -41,6 +41,7 @@ struct DenseArgs {
   int act;               // forward: activation applied to the output (ACT_*); mask users: which phi' to form from h
 };
 #include "policy_handle.h"   // ACT_*, struct mi_policy
+#include "policy_layers.h"   // Acts, PBump and the per-layer passes other files compose
 // phi'(z) from the stored activation h = phi(z): ReLU -> [h > 0], tanh -> 1 - h^2
 __device__ __forceinline__ float act_gate(float s, float h, int act) {
   return act == ACT_TANH ? s * (1.f - h * h) : (h > 0.f ? s : 0.f);
@@ -413,15 +414,9 @@ extern "C" int mi_policy_param_count(const mi_policy* p, size_t* n) {
   return MI_OK;
 }
 
-struct Acts { float *h1, *h2, *mu; };        // post-ReLU hidden activations (mask = h > 0) and the mean
-struct PBump {
-  char* base; size_t off;
-  float* f(size_t n) { off = align_up(off, 256); float* r = base ? reinterpret_cast<float*>(base + off) : nullptr; off += n * 4; return r; }
-};
-
-static hipError_t dense_fwd(hipStream_t st, int T, int B, int I, int O, const float* x0, const float* w0, size_t ws0,
-                            const float* x1, const float* w1, size_t ws1, const float* bias, size_t bs, const float* mask,
-                            int act, float* y) {
+hipError_t dense_fwd(hipStream_t st, int T, int B, int I, int O, const float* x0, const float* w0, size_t ws0,
+                     const float* x1, const float* w1, size_t ws1, const float* bias, size_t bs, const float* mask,
+                     int act, float* y) {
   DenseArgs a{};
   a.x[0] = x0; a.w[0] = w0; a.wstride[0] = ws0; a.x[1] = x1; a.w[1] = w1; a.wstride[1] = ws1;
   a.bias = bias; a.bstride = bs; a.mask = mask; a.y = y; a.B = B; a.I = I; a.O = O; a.nterms = x1 ? 2 : 1; a.act = act;
@@ -448,7 +443,7 @@ static hipError_t dense_bwd_w(hipStream_t st, int T, int B, int I, int O, const 
 }
 
 // MLP forward on [T][B][S]; theta with per-task stride ts (0 = shared)
-static int mlp_forward(mi_policy* p, hipStream_t st, int T, int B, const float* x, const float* th, size_t ts, Acts& a) {
+int mlp_forward(mi_policy* p, hipStream_t st, int T, int B, const float* x, const float* th, size_t ts, Acts& a) {
   PCHK(p, dense_fwd(st, T, B, p->S, p->H1, x, th + p->o_w1, ts, nullptr, nullptr, 0, th + p->o_b1, ts, nullptr, p->act, a.h1));
   PCHK(p, dense_fwd(st, T, B, p->H1, p->H2, a.h1, th + p->o_w2, ts, nullptr, nullptr, 0, th + p->o_b2, ts, nullptr, p->act, a.h2));
   PCHK(p, dense_fwd(st, T, B, p->H2, p->A, a.h2, th + p->o_w3, ts, nullptr, nullptr, 0, th + p->o_b3, ts, nullptr, ACT_NONE, a.mu));
@@ -457,9 +452,9 @@ static int mlp_forward(mi_policy* p, hipStream_t st, int T, int B, const float* 
 // MLP backward from dmu: grads into g [T][P] (sigma slot untouched); scratch d2 [T][B][H2], d1 [T][B][H1] keep dz2 / dz1;
 // pre2 / pre1 (optional) keep the cotangents w.r.t. h2 / h1 before the phi' factor (a tanh HVP needs them).
 // head_only: only W3 / b3 get gradients (ANIL inner loop with the body under no_grad, rl.py:381-382, policies.py:100-106).
-static int mlp_backward(mi_policy* p, hipStream_t st, int T, int B, const float* x, const float* th, size_t ts, const Acts& a,
-                        const float* dmu, float* d2, float* d1, float* g, float* pre2 = nullptr, float* pre1 = nullptr,
-                        bool head_only = false) {
+int mlp_backward(mi_policy* p, hipStream_t st, int T, int B, const float* x, const float* th, size_t ts, const Acts& a,
+                 const float* dmu, float* d2, float* d1, float* g, float* pre2 = nullptr, float* pre1 = nullptr,
+                 bool head_only = false) {
   const size_t P = p->P;
   PCHK(p, dense_bwd_w(st, T, B, p->H2, p->A, dmu, a.h2, nullptr, nullptr, g + p->o_w3, g + p->o_b3, P));
   if (head_only) return MI_OK;
@@ -470,8 +465,8 @@ static int mlp_backward(mi_policy* p, hipStream_t st, int T, int B, const float*
   return MI_OK;
 }
 // tangent forward: direction v [T][P] (per task), primal acts a -> tangent acts ad (h1d, h2d, mud)
-static int mlp_tangent_forward(mi_policy* p, hipStream_t st, int T, int B, const float* x, const float* th, size_t ts,
-                               const Acts& a, const float* v, Acts& ad) {
+int mlp_tangent_forward(mi_policy* p, hipStream_t st, int T, int B, const float* x, const float* th, size_t ts,
+                        const Acts& a, const float* v, Acts& ad) {
   const size_t P = p->P;
   PCHK(p, dense_fwd(st, T, B, p->S, p->H1, x, v + p->o_w1, P, nullptr, nullptr, 0, v + p->o_b1, P, a.h1, p->act, ad.h1));
   PCHK(p, dense_fwd(st, T, B, p->H1, p->H2, a.h1, v + p->o_w2, P, ad.h1, th + p->o_w2, ts, v + p->o_b2, P, a.h2, p->act, ad.h2));
@@ -479,10 +474,10 @@ static int mlp_tangent_forward(mi_policy* p, hipStream_t st, int T, int B, const
   return MI_OK;
 }
 // tangent backward: R{grads} into hv [T][P]; needs primal cotangents dmu, da2 (d2), da1 (d1), tangent acts ad, R{dmu} = rdmu.
-static int mlp_tangent_backward(mi_policy* p, hipStream_t st, int T, int B, const float* x, const float* th, size_t ts,
-                                const Acts& a, const Acts& ad, const float* v, const float* dmu, const float* d2,
-                                const float* d1, const float* pre2, const float* pre1, const float* rdmu, float* r2, float* r1,
-                                float* hv) {
+int mlp_tangent_backward(mi_policy* p, hipStream_t st, int T, int B, const float* x, const float* th, size_t ts,
+                         const Acts& a, const Acts& ad, const float* v, const float* dmu, const float* d2,
+                         const float* d1, const float* pre2, const float* pre1, const float* rdmu, float* r2, float* r1,
+                         float* hv) {
   const size_t P = p->P;
   const bool th2 = p->act == ACT_TANH;      // the curvature of tanh adds  -2 h hdot dh  to R{dz}
   PCHK(p, dense_bwd_w(st, T, B, p->H2, p->A, rdmu, a.h2, dmu, ad.h2, hv + p->o_w3, hv + p->o_b3, P));

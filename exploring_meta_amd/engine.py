@@ -750,3 +750,62 @@ class PolicyEngine:
                                          _ptr(sup['count']), _ptr(qry['states']), _ptr(qry['count']), T, B, float(inner_lr),
                                          float(damping), _ptr(v.contiguous()), _ptr(out), _ptr(ws), ws.numel()))
         return out
+
+    # ------------------------------------------------------------------------------------------------- step-wise learner
+    def _learner_workspace(self, T, B):
+        """A buffer of its own: the TRPO context of ``surrogate`` / ``fvp`` lives in the other one between calls."""
+        b = C.c_size_t()
+        self._check(self.lib.mi_policy_learner_workspace_bytes(self._h, T, B, C.byref(b)))
+        ws = getattr(self, '_learner_ws', None)
+        if ws is None or ws.numel() < b.value:
+            ws = self._learner_ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def _learner_args(self, theta, states, dloc, count):
+        f32 = torch.float32
+        T, B = states.shape[0], states.shape[1]
+        if theta.dim() not in (1, 2) or theta.shape[-1] != self.param_count or (theta.dim() == 2 and theta.shape[0] != T):
+            raise ValueError(f'theta must be [P] or [{T}, P] with P={self.param_count}, got {tuple(theta.shape)}')
+        if tuple(states.shape) != (T, B, self.S) or tuple(dloc.shape) != (T, B, self.A):
+            raise ValueError(f'states [T, B, {self.S}] and dloc [T, B, {self.A}] expected, got {tuple(states.shape)} and {tuple(dloc.shape)}')
+        conv = lambda x: x.detach().to(self.device, f32).contiguous()
+        if count is not None:
+            count = count.detach().to(self.device, torch.int32).contiguous()
+            if count.numel() != T:
+                raise ValueError(f'count holds {count.numel()} values for {T} tasks')
+        return T, B, conv(theta), conv(states), conv(dloc), count, (0 if theta.dim() == 1 else self.param_count)
+
+    @_on_device
+    def vjp(self, theta, states, dloc, count=None, head_only=False):
+        """mi_policy_vjp: grad [T, P] of s_t = sum_{row < count[t]} loc . dloc w.r.t. theta_t (sigma slots zero).  theta [P] (shared) or
+        [T, P]; states [T, B, S]; dloc [T, B, A]; count [T] int32 or None.  head_only: only W3 / b3 receive a gradient."""
+        T, B, theta, states, dloc, count, stride = self._learner_args(theta, states, dloc, count)
+        ws = self._learner_workspace(T, B)
+        grad = torch.empty(T, self.param_count, device=self.device)
+        self._check(self.lib.mi_policy_vjp(self._h, _stream(self.device), _ptr(theta), stride, _ptr(states), _ptr(dloc), _ptr(count), T, B,
+                                           int(bool(head_only)), _ptr(grad), _ptr(ws), ws.numel()))
+        return grad
+
+    @_on_device
+    def hvp(self, theta, states, dloc, v, count=None, head_only=False):
+        """mi_policy_hvp, the double backward of ``vjp`` for a direction v [T, P]: (hv [T, P] = (d^2 s_t / d theta^2) v_t with dloc held
+        fixed, loc_dot [T, B, A] = J_t v_t, zero on rows past count)."""
+        T, B, theta, states, dloc, count, stride = self._learner_args(theta, states, dloc, count)
+        if tuple(v.shape) != (T, self.param_count):
+            raise ValueError(f'v must be [{T}, {self.param_count}], got {tuple(v.shape)}')
+        v = v.detach().to(self.device, torch.float32).contiguous()
+        ws = self._learner_workspace(T, B)
+        hv = torch.empty(T, self.param_count, device=self.device)
+        loc_dot = torch.empty(T, B, self.A, device=self.device)
+        self._check(self.lib.mi_policy_hvp(self._h, _stream(self.device), _ptr(theta), stride, _ptr(states), _ptr(dloc), _ptr(v), _ptr(count),
+                                           T, B, int(bool(head_only)), _ptr(hv), _ptr(loc_dot), _ptr(ws), ws.numel()))
+        return hv, loc_dot
+
+    def learner_fused(self):
+        """True if ``vjp`` / ``hvp`` of this shape take the fused sweep (while ``set_fused_learner`` is on)."""
+        return bool(self.lib.mi_policy_learner_fused_supported(self._h))
+
+    @staticmethod
+    def set_fused_learner(on):
+        """Process-wide ablation / test switch (default on): off runs ``vjp`` / ``hvp`` on the per-layer kernels at every shape."""
+        _lib.load().mi_policy_set_fused_learner(int(bool(on)))

@@ -556,6 +556,32 @@ int mi_trpo_fvp(mi_policy* p, void* stream, const float* theta, const float* s_s
  * policies.py:30-37) runs as three fused sweeps over the stored passes + three folds (csrc/policy_sweep.h) instead of ~34 per-layer
  * launches; 0: the per-layer path.  Process-wide ablation / test switch; results agree to fp32 rounding. */
 int mi_policy_set_fused_fvp(int on);
+/* Step-wise policy learner (csrc/policy_learner.hip): the mean loc = MLP(theta; states) as a twice-differentiable unit, the policy-side
+ * mirror of mi_learner_backward / mi_learner_hvp (learn2learn `learner.adapt(loss)` on a policy: reference misc_scripts/cl_rl.py:71-75).
+ * sigma -> scale, the Normal and the loss stay with the caller.  With cotangents dloc [tasks, batch, A] and
+ *   s_t(theta_t) = sum_{row < count[t]} sum_a loc * dloc          (count NULL: every row)
+ *   mi_policy_vjp: grad_out [tasks, P] = d s_t / d theta_t in the parameter order above; the sigma slots are exact zeros; rows past
+ *     count[t] contribute nothing, whatever they hold.
+ *   mi_policy_hvp: for a direction v [tasks, P] (its sigma entries are ignored), grad_theta_out [tasks, P] = (d^2 s_t / d theta^2) v_t
+ *     with dloc held fixed, and loc_dot_out [tasks, batch, A] = J_t v_t, zero on rows past count[t]: the double backward of the VJP.
+ *   head_only != 0 (DiagNormalPolicyANIL.turn_off_body_grads(): the hidden layers are constants): only W3 / b3 receive a gradient,
+ *     loc_dot = V3 h2 + vb3 and grad_theta_out is exactly zero.
+ * theta shared (tstride 0) or one vector per task (tstride = P).  Results are bitwise reproducible, and a task's outputs do not depend
+ * on the other tasks of the call.  tasks, batch >= 1, tstride 0 or P, non-null arrays: MI_ERR_ARG naming the entry and the value
+ * otherwise, before any HIP call.
+ * Which kernels run: 1 <= hidden1, hidden2 <= 128, state_size <= 16 (any action_size, ReLU or tanh) takes one fused sweep + one fold
+ * per call (W2 and the direction's V2 resident in LDS); every other shape, and every shape after mi_policy_set_fused_learner(0) (a
+ * process-wide ablation / test switch, default 1), composes the per-layer kernels of csrc/policy.hip.  The two agree to fp32 rounding.
+ * Measured at 2-100-100-2, 2000 rows per task: the fused sweep is faster for one task (what the Python learner
+ * calls), the per-layer path for 20 tasks per call; the path is never chosen from the task count (a task's bits would depend on it). */
+int mi_policy_learner_workspace_bytes(const mi_policy* p, int tasks, int batch, size_t* bytes);
+int mi_policy_vjp(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states, const float* dloc,
+                  const int32_t* count, int tasks, int batch, int head_only, float* grad_out, void* workspace, size_t workspace_bytes);
+int mi_policy_hvp(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states, const float* dloc, const float* v,
+                  const int32_t* count, int tasks, int batch, int head_only, float* grad_theta_out, float* loc_dot_out, void* workspace,
+                  size_t workspace_bytes);
+int mi_policy_set_fused_learner(int on);
+int mi_policy_learner_fused_supported(const mi_policy* p);   /* 1: the shape takes the fused sweep while the switch is on */
 /* Debug aid: shader-clock stamps (stage id << 56 | s_memtime) of workgroup 0 of every fused sweep into buf (>= 256 u64; the three sweeps of a
  * product overwrite each other: read after the call, last sweep wins); NULL switches it off. */
 int mi_debug_policy_sweep_stamps(void* buf);
