@@ -165,6 +165,8 @@ _SIGS = {
     'mi_block1_wgrad_gram': (C.c_int, [C.c_void_p, C.POINTER(MiBlock1Args), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_size_t]),
     'mi_debug_conv_tiles_per_wave': (C.c_int, [C.c_int] * 5),
+    'mi_debug_wgrad_plan': (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
+    'mi_debug_conv_plan': (C.c_int, [C.c_int] * 10 + [C.POINTER(C.c_int)]),
     'mi_debug_set_trace': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     'mi_policy_create': (C.c_int, [C.POINTER(MiPolicyDesc), C.c_int, C.POINTER(C.c_void_p)]),
     'mi_policy_destroy': (None, [C.c_void_p]),

@@ -85,8 +85,16 @@ __device__ __forceinline__ void stats_block_reduce_pairs(double s0, double q0, d
 #else
 #define B16_ST(...)
 #endif
-template <int CI, int NTERMS, int EPI, int MODE>
+// S64 (EPI_STATS only): every output value enters the BatchNorm sums in fp64, as in the 32x32x16 kernel.  Without it a lane adds the
+// up to eight values it holds of a tile (and their squares) in fp32 first: one rounding of ~2^-24 of sum z^2 per partial, which
+// var = E[z^2] - mean^2 amplifies by (mean^2 + var) / var.  Over the P partials of a channel that error averages down as 1 / sqrt(P);
+// a task whose whole map fits in ONE tile (at most 30 pixels) has P <= 4 and nothing to average: four values per channel with
+// |mean| = 30 std had rstd off by 3.3e-6 (tests/test_gpu_conv_shapes.py r4n_1x1; 2.5e-7 with S64).  The launcher takes S64 for
+// exactly those launches (one tile per task), which only mi_conv_set_b16(2) sends to this kernel; every other launch keeps the fp32
+// partials, bit for bit.
+template <int CI, int NTERMS, int EPI, int MODE, bool S64 = false>
 __global__ __launch_bounds__((ConvWaves<CI, NTERMS, true, false>::value * 64), 2) void conv3x3_s1_b16_kernel(ConvArgs a) {
+  static_assert(!S64 || EPI == EPI_STATS, "S64 is the BatchNorm-statistics epilogue's variant");
   constexpr int NW = ConvWaves<CI, NTERMS, true, false>::value, NT = NW * 64, CO = CI;
   constexpr int NCC = CI / 32, NS = NTERMS * 3 * NCC;             // row-steps per tile
   constexpr int NU = NTERMS * 9 * NCC;                            // weight units (term, tap, chunk)
@@ -519,8 +527,14 @@ __global__ __launch_bounds__((ConvWaves<CI, NTERMS, true, false>::value * 64), 2
             continue;
 #endif
             if (EPI == EPI_STATS) {
-              ts[nb] += v;
-              tq[nb] = __builtin_fmaf(v, v, tq[nb]);
+              if constexpr (S64) {
+                const double dv = (double)v;
+                s[nb] += dv;
+                q[nb] = fma(dv, dv, q[nb]);
+              } else {
+                ts[nb] += v;
+                tq[nb] = __builtin_fmaf(v, v, tq[nb]);
+              }
             } else if (EPI == EPI_TSTATS) {
               const float zh = bn_zh(zpre[mb][r][nb], mu_c[nb], r_c[nb]);
               ts[nb] += v;

@@ -1283,10 +1283,22 @@ static hipError_t launch_conv_s1_bf(hipStream_t st, ConvArgs& a, dim3 grid) {
   hipLaunchKernelGGL(k, grid, dim3(ConvWaves<CI, NTERMS, true, F16>::value * 64), lds, st, a);
   return hipGetLastError();
 }
+// the 16x16x32 kernel's BatchNorm statistics in fp64 per value where a task's whole map is one tile (conv_b16.h, S64).  The edge is
+// EMPIRICAL: the fp32 partials' cancellation does not stop at two tiles (8 partials per channel), it only averages down with their number
+static bool conv_b16_stats64(const ConvArgs& a) { return a.ntiles == 1; }
 // the split-bf16 form on 16x16x32 MFMAs with one accumulator per horizontal tap (conv_b16.h): same LDS, workgroup shape and grid
 template <int CI, int NTERMS, int EPI, int MODE>
 static hipError_t launch_conv_s1_b16(hipStream_t st, ConvArgs& a, dim3 grid) {
   const size_t lds = (size_t)NTERMS * 9 * CI * 32 * 6;
+  if constexpr (EPI == EPI_STATS) {
+    if (conv_b16_stats64(a)) {               // (a task of a single tile: conv_b16.h, S64)
+      auto k = conv3x3_s1_b16_kernel<CI, NTERMS, EPI, MODE, true>;
+      static unsigned attr_done64 = 0;
+      if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds, &attr_done64); e != hipSuccess) return e;
+      hipLaunchKernelGGL(k, grid, dim3(ConvWaves<CI, NTERMS, true, false>::value * 64), lds, st, a);
+      return hipGetLastError();
+    }
+  }
   auto k = conv3x3_s1_b16_kernel<CI, NTERMS, EPI, MODE>;
   static unsigned attr_done = 0;             // one bit per device: the attribute belongs to the device's copy of the kernel
   if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds, &attr_done); e != hipSuccess) return e;
@@ -1320,12 +1332,20 @@ extern "C" int mi_conv_set_b16(int on) { const int was = conv_b16(); if (on >= 0
 // (tools/r5_ab_env.sh, six alternating pairs on two boxes) it is -0.3 ... -1.0 % on cfg2 (16.33 against 16.41 ms) and -0.7 % on cfg3: on.
 static int conv_stagger() { static const int v = getenv("MI_CONV_STAGGER") ? atoi(getenv("MI_CONV_STAGGER")) : 2; return v; }
 static bool conv_b16_for(const ConvArgs& a) { const int m = conv_b16(); return m == 2 || (m == 1 && a.tiles_per_wave >= g_conv_b16_min_tpw); }
+// which kernel of the stride-1 family a launch takes (a.split_bf16 and a.tiles_per_wave as conv_fill left them); conv_plan reports it
+static int conv_s1_kind(const ConvArgs& a) {
+  if (a.split_bf16 == 2) return CONV_K_S1_F16;
+  if (a.split_bf16 && conv_b16_for(a)) return CONV_K_S1_BF16_16X16;
+  if (a.split_bf16) return CONV_K_S1_BF16_32X32;
+  return CONV_K_S1_F32;
+}
 template <int CI, int NTERMS, int EPI, int MODE>
 static hipError_t launch_conv_s1(hipStream_t st, ConvArgs& a, dim3 grid) {
   if constexpr (CI == 32 || (CI == 64 && NTERMS == 1)) {
-    if (a.split_bf16 == 2) return launch_conv_s1_bf<CI, NTERMS, EPI, MODE, true>(st, a, grid);
-    if (a.split_bf16 && conv_b16_for(a)) return launch_conv_s1_b16<CI, NTERMS, EPI, MODE>(st, a, grid);
-    if (a.split_bf16) return launch_conv_s1_bf<CI, NTERMS, EPI, MODE, false>(st, a, grid);
+    const int kind = conv_s1_kind(a);
+    if (kind == CONV_K_S1_F16) return launch_conv_s1_bf<CI, NTERMS, EPI, MODE, true>(st, a, grid);
+    if (kind == CONV_K_S1_BF16_16X16) return launch_conv_s1_b16<CI, NTERMS, EPI, MODE>(st, a, grid);
+    if (kind == CONV_K_S1_BF16_32X32) return launch_conv_s1_bf<CI, NTERMS, EPI, MODE, false>(st, a, grid);
   }
   const size_t lds = (size_t)NTERMS * 9 * CI * 32 * sizeof(float);
   auto k = conv3x3_s1_mfma_kernel<CI, NTERMS, EPI, MODE>;
@@ -1363,26 +1383,64 @@ static hipError_t launch_conv_ms(hipStream_t st, ConvArgs& a, dim3 grid, int mod
 }
 
 // Generic conv launcher.  mode 0 = forward, 1 = dgrad.  epi as EPI_*.  Returns blocks per task (partials written).
-hipError_t launch_conv3x3(hipStream_t st, ConvArgs a, int tasks, int nterms, int epi, int mode, int* blocks_per_task) {
+// The decisions of a launch: operand form, waves per workgroup, tile size and the tile split, left in a (split_bf16, ntiles,
+// tiles_per_wave, stagger) and grid.  have_scales: the fp16 form's largest-magnitude cells are there.  Returns waves per workgroup.
+constexpr int CONV_FIRST_WAVES = 4;          // workgroup of the first-layer kernel
+static int conv_fill(ConvArgs& a, int tasks, int nterms, int epi, int mode, bool have_scales, dim3& grid) {
   const int cot = a.g.co / 32;
   int ntiles, tpw;
-  dim3 grid;
   // the split-bf16 form of the stride-1 kernel (32 filters; 64 filters with one term): tiles of 30 output pixels, 2048 resident waves
   a.split_bf16 = ((a.g.ci == 32 || (a.g.ci == 64 && nterms == 1)) && conv_s1_ok(a) && conv_split_bf16() &&
                   (epi == EPI_BRED ? mode == 1 : (mode == 0 || epi == EPI_NONE)) &&
                   ((g_conv_split_mask >> (((nterms - 1) * 2 + mode) * 4 + epi)) & 1u)) ? conv_operand_form() : 0;
-  if (a.split_bf16 == 2 && (!a.amax[0] || (nterms == 2 && !a.amax[1]))) a.split_bf16 = 1;      // no scales: the bf16 form
+  if (a.split_bf16 == 2 && !have_scales) a.split_bf16 = 1;      // no scales: the bf16 form
   const int nw = ((a.split_bf16 == 2 && MI_F16_WIDE) || (nterms == 2 && a.g.ci == 32) || (a.split_bf16 && a.g.ci == 64)) ? 8 : 4;     // ConvWaves<CI, NTERMS, BF, F16>
   conv_grid(a.mpix, tasks, cot, nw, a.g.ci, nterms, ntiles, tpw, grid, a.split_bf16 ? 30 : 32, a.split_bf16 == 2 && MI_F16_WIDE && epi != EPI_TSTATS);
   a.ntiles = ntiles;
   a.tiles_per_wave = tpw;
   a.stagger = conv_stagger();
+  return nw;
+}
+// Which kernel a launch takes (CONV_K_*), from a as conv_fill left it; -1: no kernel takes this combination of geometry, terms, epilogue
+// and mode.  launch_conv3x3 refuses what this refuses and conv_plan reports it: the template dispatch below only spells the instance.
+static int conv_kernel_of(const ConvArgs& a, int nterms, int epi, int mode) {
+  if (a.g.co % 32 != 0 || nterms < 1 || nterms > 2 || (nterms == 2 && epi == EPI_STATS)) return -1;
+  if (a.g.ci == 1 || a.g.ci == 3)
+    return (mode == 0 && nterms == 1 && epi != EPI_BRED && (a.g.stride == 1 || a.g.stride == 2)) ? CONV_K_FIRST : -1;
+  if (a.g.ci != 32 && a.g.ci != 64) return -1;
+  if (epi == EPI_BRED) return (conv_s1_ok(a) && mode == 1) ? conv_s1_kind(a) : -1;   // only the stride-1 hidden -> hidden dgrad carries it
+  if (mode != 0 && !(mode == 1 && epi == EPI_NONE)) return -1;
+  if (conv_s1_ok(a)) return conv_s1_kind(a);
+  return (a.g.stride == 1 || a.g.stride == 2) ? CONV_K_GENERIC : -1;
+}
+// g as the launch sees it (dgrad: the geometry of the transposed convolution, input = dz); mpix = n * ho * wo
+ConvPlan conv_plan(const ConvGeom& g, int tasks, int nterms, int epi, int mode, bool have_scales) {
+  ConvArgs a{};
+  a.g = g;
+  a.mpix = g.n * g.ho * g.wo;
+  dim3 grid;
+  const int nw = conv_fill(a, tasks, nterms, epi, mode, have_scales, grid);
+  ConvPlan p{};
+  p.kernel = conv_kernel_of(a, nterms, epi, mode);
+  p.tiles_per_wave = a.tiles_per_wave;
+  p.ntiles = a.ntiles;
+  p.blocks = (int)grid.x;
+  p.tile_pix = a.split_bf16 ? 30 : 32;
+  p.waves = p.kernel == CONV_K_FIRST ? CONV_FIRST_WAVES : nw;
+  p.form = a.split_bf16;
+  p.stats64 = p.kernel == CONV_K_S1_BF16_16X16 && epi == EPI_STATS && conv_b16_stats64(a);
+  return p;
+}
+
+hipError_t launch_conv3x3(hipStream_t st, ConvArgs a, int tasks, int nterms, int epi, int mode, int* blocks_per_task) {
+  dim3 grid;
+  conv_fill(a, tasks, nterms, epi, mode, a.amax[0] && (nterms == 1 || a.amax[1]), grid);
   if (blocks_per_task) *blocks_per_task = grid.x;
-  if (a.g.co % 32 != 0) return hipErrorInvalidValue;
+  const int kind = conv_kernel_of(a, nterms, epi, mode);
+  if (kind < 0) return hipErrorInvalidValue;
   const int s = a.g.stride;
-  if (a.g.ci == 1 || a.g.ci == 3) {
-    if (mode != 0 || nterms != 1) return hipErrorInvalidValue;
-#define FIRST(CI0, E, S) hipLaunchKernelGGL((conv3x3_first_mfma_kernel<CI0, E, S>), grid, dim3(256), 0, st, a)
+  if (kind == CONV_K_FIRST) {
+#define FIRST(CI0, E, S) hipLaunchKernelGGL((conv3x3_first_mfma_kernel<CI0, E, S>), grid, dim3(CONV_FIRST_WAVES * 64), 0, st, a)
     if (a.g.ci == 3 && s == 1) { if (epi == EPI_STATS) FIRST(3, EPI_STATS, 1); else if (epi == EPI_TSTATS) FIRST(3, EPI_TSTATS, 1); else FIRST(3, EPI_NONE, 1); }
     else if (a.g.ci == 3 && s == 2) { if (epi == EPI_STATS) FIRST(3, EPI_STATS, 2); else if (epi == EPI_TSTATS) FIRST(3, EPI_TSTATS, 2); else FIRST(3, EPI_NONE, 2); }
     else if (a.g.ci == 1 && s == 1) { if (epi == EPI_STATS) FIRST(1, EPI_STATS, 1); else if (epi == EPI_TSTATS) FIRST(1, EPI_TSTATS, 1); else FIRST(1, EPI_NONE, 1); }
@@ -1523,9 +1581,7 @@ size_t wgrad_partial_floats(const ConvGeom& g, int tasks) {
   return (size_t)tasks * ceil_div(mpix, chunk) * 9 * g.ci * g.co;
 }
 
-static void launch_rows(hipStream_t st, const WgradArgs& a, dim3 grid, int rh) {
-  // EXACT: segments tile the row exactly and both channel counts are 32 (the 4-conv-32 classifier): immediates instead of per-load adds
-  const bool exact = a.g.w % rh == 0 && a.g.ci == 32 && a.g.co == 32;
+static void launch_rows(hipStream_t st, const WgradArgs& a, dim3 grid, int rh, bool exact) {
 #define ROWS(R)                                                                                                   \
   do {                                                                                                            \
     if (exact) hipLaunchKernelGGL((wgrad3x3_rows_mfma_kernel<R, true>), grid, dim3(256), 0, st, a);               \
@@ -1538,56 +1594,82 @@ static void launch_rows(hipStream_t st, const WgradArgs& a, dim3 grid, int rh) {
 #undef ROWS
 }
 
+// Every decision of launch_wgrad3x3 (kernel family, template instance, work split), host arithmetic only: the launcher launches from
+// it and mi_debug_wgrad_plan reports it.  have_scales: the fp16 form's largest-magnitude cells are there for every operand.
+WgradPlan wgrad_plan(const ConvGeom& g, int tasks, int nterms, bool have_scales) {
+  WgradPlan p{};
+  p.form = conv_operand_form();
+  if (p.form == 2 && !have_scales) p.form = 1;               // no scales: the bf16 form
+  const bool split = use_rows_kernel(g) && conv_split_bf16() && (g_conv_split_mask & (1u << (16 + (nterms - 1))));
+  if (split && wgrad_bf16_strips(g) && (size_t)g.n * g.h * g.w * g.ci * 4 < (size_t)MI_OOB &&
+      !((g_conv_split_mask >> 21) & 1u)) {                     // bit 21 (debug): the unit form on wide maps too
+    int rows, ipb, blocks;
+    strips_split_bf16(g, tasks, nterms, rows, ipb, blocks);
+    p.family = WG_FAM_STRIPS_BF16;
+    p.strip_cand = rows;
+    p.size = wgrad_bf16_strip_rows(g, rows);
+    p.per_block = ipb * nterms;                              // the item stream is nterms x items long, same workgroup count
+    p.blocks = p.nchunks = blocks;
+    p.per_term = wgrad_bf16_strip_items(g, rows);
+    return p;
+  }
+  if (split && wgrad_bf16_ok(g)) {
+    int nunits, upb, blocks;
+    rows_split_bf16(g, tasks, nunits, upb, blocks);
+    p.family = WG_FAM_ROWS_BF16;
+    p.size = 8;
+    p.per_block = upb * nterms;                              // the unit stream is nterms x nunits long, same workgroup count
+    p.blocks = p.nchunks = blocks;
+    p.per_term = nunits;
+    return p;
+  }
+  if (use_rows_kernel(g)) {
+    int rh, nunits, upb, blocks;
+    rows_split(g, tasks, rh, nunits, upb, blocks);
+    p.family = WG_FAM_ROWS_F32;
+    p.size = rh;
+    // EXACT: segments tile the row exactly and both channel counts are 32 (the 4-conv-32 classifier): immediates instead of per-load adds
+    p.exact = g.w % rh == 0 && g.ci == 32 && g.co == 32;
+    p.per_block = upb * nterms;                              // the unit stream is nterms x nunits long, same workgroup count
+    p.blocks = p.nchunks = blocks;
+    p.per_term = nunits;
+    return p;
+  }
+  const int mpix = g.n * g.ho * g.wo;
+  p.size = wgrad_chunks(mpix, tasks);
+  p.nchunks = ceil_div(mpix, p.size);
+  p.per_block = 4;                                           // one chunk per wave
+  p.blocks = ceil_div(p.nchunks, 4);
+  p.per_term = mpix;
+  if (g.ci == 1 || g.ci == 3) p.family = nterms == 1 ? WG_FAM_FIRST : -1;
+  else p.family = (g.ci % 32 || g.co % 32) ? -1 : WG_FAM_CHUNKED;
+  return p;
+}
+
 hipError_t launch_wgrad3x3(hipStream_t st, WgradArgs a, int tasks, int nterms, int* nchunks_out) {
   const int s = a.g.stride;
-  a.form = conv_operand_form();
-  if (a.form == 2 && !(a.amax_x[0] && a.amax_dz[0] && (nterms == 1 || (a.amax_x[1] && a.amax_dz[1])))) a.form = 1;   // no scales: the bf16 form
-  if (use_rows_kernel(a.g) && conv_split_bf16() && (g_conv_split_mask & (1u << (16 + (nterms - 1)))) && wgrad_bf16_strips(a.g) &&
-      (size_t)a.g.n * a.g.h * a.g.w * a.g.ci * 4 < (size_t)MI_OOB && !((g_conv_split_mask >> 21) & 1u)) {   // bit 21 (debug): the unit form on wide maps too
-    int rows, ipb, blocks;
-    strips_split_bf16(a.g, tasks, nterms, rows, ipb, blocks);
-    a.nterms = nterms;
-    a.chunk_pix = ipb * nterms;                            // the item stream is nterms x items long, same workgroup count
-    a.nchunks = blocks;
-    *nchunks_out = blocks;
-    return launch_wgrad_strips_bf16(st, a, dim3(blocks, tasks, (a.g.ci / 32) * (a.g.co / 32)), rows);
-  }
-  if (use_rows_kernel(a.g) && conv_split_bf16() && wgrad_bf16_ok(a.g) && (g_conv_split_mask & (1u << (16 + (nterms - 1))))) {
-    int nunits, upb, blocks;
-    rows_split_bf16(a.g, tasks, nunits, upb, blocks);
-    a.nterms = nterms;
-    a.chunk_pix = upb * nterms;                            // the unit stream is nterms x nunits long, same workgroup count
-    a.nchunks = blocks;
-    *nchunks_out = blocks;
-    return launch_wgrad_rows_bf16(st, a, dim3(blocks, tasks, (a.g.ci / 32) * (a.g.co / 32)));
-  }
-  if (use_rows_kernel(a.g)) {
-    int rh, nunits, upb, blocks;
-    rows_split(a.g, tasks, rh, nunits, upb, blocks);
-    a.nterms = nterms;
-    a.chunk_pix = upb * nterms;                            // the unit stream is nterms x nunits long, same workgroup count
-    a.nchunks = blocks;
-    *nchunks_out = blocks;
-    dim3 grid(blocks, tasks, (a.g.ci / 32) * (a.g.co / 32));
-    launch_rows(st, a, grid, rh);
-    return hipGetLastError();
-  }
-  a.chunk_pix = wgrad_chunks(a.mpix, tasks);
-  a.nchunks = ceil_div(a.mpix, a.chunk_pix);
-  *nchunks_out = a.nchunks;
-  if (a.g.ci == 1 || a.g.ci == 3) {
-    if (nterms != 1) return hipErrorInvalidValue;
-    dim3 grid(ceil_div(a.nchunks, 4), tasks, a.g.co / 32);
-    if (a.g.ci == 3 && s == 1) hipLaunchKernelGGL((wgrad3x3_first_mfma_kernel<3, 1>), grid, dim3(256), 0, st, a);
+  const WgradPlan p = wgrad_plan(a.g, tasks, nterms, a.amax_x[0] && a.amax_dz[0] && (nterms == 1 || (a.amax_x[1] && a.amax_dz[1])));
+  a.form = p.form;
+  a.nchunks = p.nchunks;
+  *nchunks_out = p.nchunks;
+  if (p.family < 0) return hipErrorInvalidValue;
+  const dim3 grid(p.blocks, tasks, p.family == WG_FAM_FIRST ? a.g.co / 32 : (a.g.ci / 32) * (a.g.co / 32));
+  if (p.family == WG_FAM_FIRST || p.family == WG_FAM_CHUNKED) {
+    a.chunk_pix = p.size;
+    if (p.family == WG_FAM_CHUNKED) {
+      if (nterms == 1) hipLaunchKernelGGL((wgrad3x3_mfma_kernel<1, 2>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((wgrad3x3_mfma_kernel<2, 2>), grid, dim3(256), 0, st, a);
+    } else if (a.g.ci == 3 && s == 1) hipLaunchKernelGGL((wgrad3x3_first_mfma_kernel<3, 1>), grid, dim3(256), 0, st, a);
     else if (a.g.ci == 3 && s == 2) hipLaunchKernelGGL((wgrad3x3_first_mfma_kernel<3, 2>), grid, dim3(256), 0, st, a);
     else if (a.g.ci == 1 && s == 1) hipLaunchKernelGGL((wgrad3x3_first_mfma_kernel<1, 1>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((wgrad3x3_first_mfma_kernel<1, 2>), grid, dim3(256), 0, st, a);
-  } else {
-    if (a.g.ci % 32 || a.g.co % 32) return hipErrorInvalidValue;
-    dim3 grid(ceil_div(a.nchunks, 4), tasks, (a.g.ci / 32) * (a.g.co / 32));
-    if (nterms == 1) hipLaunchKernelGGL((wgrad3x3_mfma_kernel<1, 2>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((wgrad3x3_mfma_kernel<2, 2>), grid, dim3(256), 0, st, a);
+    return hipGetLastError();
   }
+  a.nterms = nterms;
+  a.chunk_pix = p.per_block;
+  if (p.family == WG_FAM_STRIPS_BF16) return launch_wgrad_strips_bf16(st, a, grid, p.strip_cand);
+  if (p.family == WG_FAM_ROWS_BF16) return launch_wgrad_rows_bf16(st, a, grid);
+  launch_rows(st, a, grid, p.size, p.exact != 0);
   return hipGetLastError();
 }
 

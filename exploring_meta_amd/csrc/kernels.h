@@ -88,6 +88,25 @@ hipError_t launch_wgrad_reduce(hipStream_t st, const float* partial, int nchunks
 size_t wgrad_partial_floats(const ConvGeom& g, int tasks);
 int conv_max_blocks_per_task(const ConvGeom& g);
 int conv_tiles_per_wave(int mpix, int tasks, int cot);
+// What launch_wgrad3x3 launches for a problem: the launcher fills this and launches from it, mi_debug_wgrad_plan reports it (host code
+// only, no HIP call).  `stream` kernels walk one stream of units [term][unit] cut into equal runs per workgroup.
+enum { WG_FAM_FIRST = 0, WG_FAM_CHUNKED = 1, WG_FAM_ROWS_F32 = 2, WG_FAM_ROWS_BF16 = 3, WG_FAM_STRIPS_BF16 = 4 };
+struct WgradPlan {
+  int family;           // WG_FAM_*; -1: no kernel takes this geometry
+  int size;             // ROWS_F32: RH (columns per segment); ROWS_BF16: 8; STRIPS: rows per piece (evened out); FIRST / CHUNKED: pixels per chunk
+  int exact;            // ROWS_F32: the EXACT instance
+  int per_block;        // stream kernels: units / items of the stream per workgroup (WgradArgs::chunk_pix); FIRST / CHUNKED: chunks per workgroup (4)
+  int blocks;           // workgroups per task (grid.x)
+  int per_term;         // stream kernels: units / items per term; FIRST / CHUNKED: pixels
+  int form;             // operand form of the launch (WgradArgs::form)
+  int nchunks;          // partials per task (what launch_wgrad_reduce folds)
+  int strip_cand;       // STRIPS: the piece-length candidate `size` was evened out from
+};
+WgradPlan wgrad_plan(const ConvGeom& g, int tasks, int nterms, bool have_scales);
+// What launch_conv3x3 launches: kernel (CONV_K_*), tile size, waves per workgroup and the tile split.
+enum { CONV_K_FIRST = 0, CONV_K_GENERIC = 1, CONV_K_S1_F32 = 2, CONV_K_S1_BF16_32X32 = 3, CONV_K_S1_BF16_16X16 = 4, CONV_K_S1_F16 = 5 };
+struct ConvPlan { int kernel, tiles_per_wave, ntiles, blocks, tile_pix, waves, form, stats64; };   // stats64: conv_b16.h, S64
+ConvPlan conv_plan(const ConvGeom& g, int tasks, int nterms, int epi, int mode, bool have_scales);
 
 // bn_pool.hip
 int bn_blocks_per_task(int n, int ho, int wo, int c, int pool, int tasks);

@@ -236,3 +236,24 @@ extern "C" int mi_block1_wgrad_gram(void* stream, const mi_block1_args* a, const
 extern "C" int mi_debug_conv_tiles_per_wave(int tasks, int n, int ho, int wo, int co) {
   return conv_tiles_per_wave(n * ho * wo, tasks, co / 32);
 }
+
+// The launch plan of the weight gradient / of a forward or dgrad convolution for a problem given as the kernel entry points take it
+// (forward geometry n, h, w, ci, co, stride): what launch_wgrad3x3 / launch_conv3x3 would launch under the operand form in force.  Host
+// arithmetic only, no HIP call.  The fp16 form's scales are taken as present (the entry points above and the engine provide them).
+extern "C" int mi_debug_wgrad_plan(int tasks, int n, int h, int w, int ci, int co, int stride, int nterms, int* out) {
+  if (!out || tasks < 1 || n < 1 || h < 1 || w < 1 || stride < 1 || nterms < 1 || nterms > 2) return MI_ERR_ARG;
+  const ConvGeom g{n, h, w, (h - 1) / stride + 1, (w - 1) / stride + 1, ci, co, stride};
+  const WgradPlan p = wgrad_plan(g, tasks, nterms, true);
+  out[0] = p.family; out[1] = p.size; out[2] = p.exact; out[3] = p.per_block; out[4] = p.blocks; out[5] = p.per_term; out[6] = p.form;
+  out[7] = p.nchunks;
+  return p.family < 0 ? MI_ERR_ARG : MI_OK;
+}
+extern "C" int mi_debug_conv_plan(int tasks, int n, int h, int w, int ci, int co, int stride, int nterms, int epi, int mode, int* out) {
+  if (!out || tasks < 1 || n < 1 || h < 1 || w < 1 || stride < 1 || nterms < 1 || nterms > 2 || mode < 0 || mode > 1) return MI_ERR_ARG;
+  const int ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
+  const ConvGeom g = mode == 0 ? ConvGeom{n, h, w, ho, wo, ci, co, stride} : ConvGeom{n, ho, wo, h, w, co, ci, stride};
+  const ConvPlan p = conv_plan(g, tasks, nterms, epi, mode, true);
+  out[0] = p.kernel; out[1] = p.tiles_per_wave; out[2] = p.ntiles; out[3] = p.blocks; out[4] = p.tile_pix; out[5] = p.waves; out[6] = p.form;
+  out[7] = p.stats64;
+  return p.kernel < 0 ? MI_ERR_ARG : MI_OK;
+}

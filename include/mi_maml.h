@@ -466,6 +466,26 @@ int mi_block1_wgrad_gram(void* stream, const mi_block1_args* a, const double* g,
  *   Hessian-vector product) [K][tasks][P] | H_support(theta_k) lam_{k+1} [K][tasks][P]
  * (the last two only for second-order calls): the per-step state the teacher-forced parity tests check against the oracle. */
 int mi_debug_conv_tiles_per_wave(int tasks, int n, int ho, int wo, int co);
+/* Launch plans (test aids; host arithmetic only, no HIP call: they answer without a GPU).  The problem is given as the kernel entry points
+ * take it (forward geometry n, h, w, ci, co, stride); the answer is what the launchers themselves launch from, under the operand form in
+ * force (mi_conv_set_split_bf16, mi_conv_set_b16), with the fp16 form's scales taken as present.  out receives 8 ints.
+ * mi_debug_wgrad_plan (launch_wgrad3x3; nterms 1 or 2):
+ *   out[0] kernel family: 0 first layer (wgrad3x3_first_mfma_kernel), 1 generic chunked (wgrad3x3_mfma_kernel), 2 fp32 rows
+ *          (wgrad3x3_rows_mfma_kernel), 3 split-bf16 rows (wgrad3x3_rows_bf16_kernel), 4 split-bf16 strips (wgrad3x3_strip_bf16_kernel)
+ *   out[1] fp32 rows: RH (columns per segment: 7, 8, 5 or 4); bf16 rows: 8; strips: rows per piece; families 0 / 1: pixels per chunk
+ *   out[2] fp32 rows: 1 = the EXACT instance
+ *   out[3] rows / strips: units / items of the [term][unit] stream per workgroup; families 0 / 1: chunks per workgroup
+ *   out[4] workgroups per task     out[5] rows / strips: units / items per term; families 0 / 1: output pixels per task
+ *   out[6] operand form of the launch (0 fp32, 1 split bf16, 2 fp16 planes)     out[7] partials per task
+ * mi_debug_conv_plan (launch_conv3x3; mode 0 forward, 1 dgrad; epi 0 none, 1 BatchNorm statistics, 2 tangent statistics):
+ *   out[0] kernel: 0 first layer, 1 generic (conv3x3_mfma_kernel), 2 stride-1 fp32 (conv3x3_s1_mfma_kernel), 3 split bf16 on 32x32x16
+ *          MFMAs, 4 split bf16 on 16x16x32 MFMAs (conv3x3_s1_b16_kernel), 5 fp16 planes
+ *   out[1] tiles per wave   out[2] tiles per task   out[3] workgroups per task and filter tile   out[4] pixels per tile (32 / 30)
+ *   out[5] waves per workgroup   out[6] operand form of the launch
+ *   out[7] 1 = the 16x16x32 kernel's instance that adds every value to the BatchNorm statistics in fp64 (a task of one tile)
+ * Both return MI_ERR_ARG (out still filled) where no kernel takes the geometry. */
+int mi_debug_wgrad_plan(int tasks, int n, int h, int w, int ci, int co, int stride, int nterms, int* out);
+int mi_debug_conv_plan(int tasks, int n, int h, int w, int ci, int co, int stride, int nterms, int epi, int mode, int* out);
 int mi_debug_set_trace(mi_engine* e, float* buf, size_t floats);
 
 /* ------------------------------------------------------------------------------------------------------------------

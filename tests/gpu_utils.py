@@ -39,3 +39,13 @@ def rel_err(a, b):
 
 def max_err(a, b):
     return float(np.max(np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64))))
+
+
+def rand32(seed, shape, lo=-1.0, hi=1.0):
+    """Seeded fp32 uniforms in [lo, hi): a pure function of (seed, flat index) (exploring_meta_amd.utils.synthetic.hash_uniform)."""
+    from exploring_meta_amd.utils import synthetic
+    return (synthetic.hash_uniform(seed, shape) * (hi - lo) + lo).astype(np.float32)
+
+
+def t64(a):
+    return torch.from_numpy(np.asarray(a)).double()

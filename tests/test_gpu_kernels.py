@@ -103,7 +103,11 @@ def test_conv_bn_stats(lib, name, T, n, h, w, ci, co, stride):
 
 
 BN_CASES = [('pool_even', 2, 3, 42, 42, 32, 1), ('pool_odd', 2, 4, 21, 21, 32, 1), ('pool_c64', 1, 2, 10, 10, 64, 1),
-            ('nopool', 2, 5, 14, 14, 64, 0), ('nopool_small', 3, 5, 2, 2, 64, 0)]
+            ('nopool', 2, 5, 14, 14, 64, 0), ('nopool_small', 3, 5, 2, 2, 64, 0),
+            # the maps of a 4-conv model on 64x64 / 32x32 inputs, pooled outputs of one pixel (from an even and from an odd map), a
+            # rectangle with both dimensions odd, and a one-pixel map
+            ('pool_32', 2, 3, 32, 32, 32, 1), ('pool_16', 2, 3, 16, 16, 32, 1), ('pool_8', 2, 3, 8, 8, 32, 1), ('pool_4to2', 2, 3, 4, 4, 32, 1),
+            ('pool_2to1', 2, 4, 2, 2, 32, 1), ('pool_3to1', 2, 4, 3, 3, 64, 1), ('pool_odd_5x9', 2, 3, 5, 9, 32, 1), ('nopool_1x1', 2, 4, 1, 1, 64, 0)]
 
 
 @pytest.mark.parametrize('name,T,n,ho,wo,c,pool', BN_CASES)

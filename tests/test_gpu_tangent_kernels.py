@@ -15,7 +15,7 @@ from exploring_meta_amd import _lib
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 from exploring_meta_amd.utils import synthetic
 from oracle import kernels_ref as KR
-from gpu_utils import dev, ptr, stream, rel_err, max_err, report
+from gpu_utils import dev, ptr, stream, rel_err, max_err, report, rand32 as _rand, t64 as _t64
 
 pytestmark = pytest.mark.gpu
 
@@ -31,14 +31,6 @@ def lib(request):
     yield lb
     restore()
     lb.mi_block1_set_split_bf16(-1)             # back to "follow the hidden convolutions' form" (the library's default)
-
-
-def _rand(seed, shape, lo=-1.0, hi=1.0):
-    return (synthetic.hash_uniform(seed, shape) * (hi - lo) + lo).astype(np.float32)
-
-
-def _t64(a):
-    return torch.from_numpy(np.asarray(a)).double()
 
 
 def _scratch(lib, T, n, h, w, c):
@@ -277,7 +269,11 @@ def test_conv_fwd_bwd_at_bench_sizes(lib, name, T, n, h, w, ci, co, check):
 
 # ---------------------------------------------------------------------------------------------------- BatchNorm tangent kernels
 BN_TAN_CASES = [('pool_even', 2, 3, 42, 42, 32, 1), ('pool_odd', 2, 4, 21, 21, 32, 1), ('pool_c64', 1, 2, 10, 10, 64, 1),
-                ('nopool', 2, 5, 14, 14, 64, 0), ('nopool_small', 3, 5, 2, 2, 64, 0), ('bench_l2_T32', 32, 25, 42, 42, 32, 1)]
+                ('nopool', 2, 5, 14, 14, 64, 0), ('nopool_small', 3, 5, 2, 2, 64, 0), ('bench_l2_T32', 32, 25, 42, 42, 32, 1),
+                # as BN_CASES of test_gpu_kernels.py: 64x64 / 32x32 inputs' maps, one-pixel pooled outputs, an odd rectangle, a one-pixel map
+                ('pool_32', 2, 3, 32, 32, 32, 1), ('pool_16', 2, 3, 16, 16, 32, 1), ('pool_8', 2, 3, 8, 8, 32, 1), ('pool_4to2', 2, 3, 4, 4, 32, 1),
+                ('pool_2to1', 2, 4, 2, 2, 32, 1), ('pool_3to1', 2, 4, 3, 3, 64, 1), ('pool_odd_5x9', 2, 3, 5, 9, 32, 1),
+                ('nopool_1x1', 2, 4, 1, 1, 64, 0)]
 
 
 @pytest.mark.parametrize('name,T,n,ho,wo,c,pool', BN_TAN_CASES)
@@ -366,7 +362,12 @@ def test_block1_gram_wgrad_is_the_same_bits_at_every_task_count():
 
 # ---------------------------------------------------------------------------------------------------- fused block 1
 B1_CASES = [('min_small', 2, 3, 84, 84, 3, 32, None), ('one_image', 1, 1, 84, 84, 3, 32, None), ('tall', 3, 2, 20, 84, 3, 32, None), ('rect', 2, 2, 36, 42, 3, 32, None), ('ci1', 3, 4, 28, 28, 1, 32, None),
-            ('anil64', 1, 2, 84, 84, 3, 64, None), ('bench_T32', 32, 25, 84, 84, 3, 32, [0, 31])]
+            ('anil64', 1, 2, 84, 84, 3, 64, None), ('bench_T32', 32, 25, 84, 84, 3, 32, [0, 31]),
+            # 32x32 inputs; 16 wide: the edge w / 2 >= 8 of block1_supported (a tile's eight windows = one pooled row), three channels and one;
+            # an odd pooled width other than 21; one channel at the limit w * ci == 256 of sparse_wgrad_supported (a row fills the 4 x 64
+            # lanes of the sparse kernel's row store: pitch 268 floats, last column read 257)
+            ('in32', 2, 3, 32, 32, 3, 32, None), ('in16_c3', 2, 3, 16, 16, 3, 32, None), ('in16_c1', 2, 3, 16, 16, 1, 32, None),
+            ('w22', 2, 2, 12, 22, 3, 32, None), ('ci1_w256', 2, 2, 4, 256, 1, 32, None)]
 
 
 @pytest.mark.parametrize('name,T,n,h,w,ci,co,check', B1_CASES)
