@@ -26,12 +26,6 @@ struct Layer {
   size_t off_gamma, off_beta, off_w, off_b;
 };
 
-// Round 6: the query pass's block 1 through a Gram matrix of the QUERY images too (statistics as quadratic forms, weight gradient as sparse
-// part + assembly) instead of the two conv-recompute kernels (0.14 + 0.44 ms per cfg2 iteration): the fp64 Gram launch (0.23 ms) runs on the side
-// stream beside the inner loop.  cfg2 15.84 -> 15.60 ms in alternating pairs (on the caller's stream: 15.71); rounds 2 - 5 had measured no gain
-// from it -- the sparse weight gradient was slower then and the Gram launch sat on the critical path (profiles/r6/ab_gram_query.txt).
-static int gram_query_env() { static const int v = getenv("MI_GRAM_QUERY") ? atoi(getenv("MI_GRAM_QUERY")) : 2; return v; }      // 0: off; 1: on the caller's stream; 2 (default): on the side stream, beside the inner loop
-static bool fork_once_env() { static const bool v = getenv("MI_FORK_ONCE") && atoi(getenv("MI_FORK_ONCE")) != 0; return v; }
 struct mi_engine {
   mi_model_desc d;
   int device;
@@ -41,13 +35,15 @@ struct mi_engine {
   size_t PS;  // per-task stride of parameter-shaped buffers (P padded so every task's vectors stay 16-B aligned)
   int32_t* perm_dev;
   bool fuse1 = false;   // block 1 runs through the conv-recompute kernels of block1.hip
-  bool gramq = true;    // ... of the QUERY images too (round 6; the backward half's query pass: statistics + weight gradient of block 1)
   bool gram1 = true;    // ... with the statistics of repeated passes from the input Gram matrix (gram.hip) and the BN-backward
                         // reductions from zhat stored at the pooling argmax, instead of further conv-recompute passes
+  // ... and a Gram matrix of the QUERY images too (the query pass's statistics as quadratic forms, its weight gradient as sparse part +
+  // assembly, instead of the two conv-recompute kernels): its fp64 launch runs on the side stream beside the inner loop, or once on the
+  // caller's stream without one (profiles/r6/ab_gram_query.txt)
+  bool gramq = true;
   // Weight gradients of blocks >= 2 run on a side stream: they depend only on dz_l and the block input, nothing downstream of
   // them until the parameter update, and they are matrix-bound while the BatchNorm kernels of the next block are HBM-bound.
   bool overlap = true;
-  bool fork_once = fork_once_env();   // false (default): one fork / join of the side stream per hidden block; true: ONE per backward pass (mi_engine_set_overlap(e, 3), MI_FORK_ONCE=1; measured slower)
   // BatchNorm statistic / reduction partials are folded by the last workgroup of the producing kernel (finalize.h) instead of a
   // bn_finalize launch; counters: one zero-initialised arrival counter per task, owned by the engine.
   bool fuse_fin = true;
@@ -57,7 +53,6 @@ struct mi_engine {
   // the tail of every pass of mi_meta_batch_maml as ONE launch (gram.hip, advance_kernel): weight-gradient partial folds, block 1's
   // Gram-matrix assembly, the fast-weight / adjoint update and the next pass's Gram statistics -- instead of 3 reduce_partials +
   // gram_wgrad + axpy + gram_stats launches and a memset per pass.  Same arithmetic in the same order: bit-identical results.
-  bool bred_arg = true;     // block 2's dgrad epilogue reads block 1's argmax byte instead of p (MI_BRED_ARG=0: p, for A/B runs; same results)
   bool fuse_tail = true;
   // the last ConvBlock's BatchNorm + pooling, the head, its backward and that block's BatchNorm-backward sums as ONE launch, four workgroups per
   // task (tail.hip), instead of four launches per pass (MI_FUSE_LAST=0 / mi_engine_set_fused_last_block(e, 0): the separate launches)
@@ -209,7 +204,6 @@ extern "C" int mi_engine_create(const mi_model_desc* d, int device, mi_engine** 
     ci = l.co; h = l.hp; w = l.wp;
   }
   e->fuse1 = block1_supported(e->L[0].ci, e->L[0].stride, e->L[0].pool, e->L[0].ho, e->L[0].wo, e->L[0].co);
-  if (const char* ba = getenv("MI_BRED_ARG")) e->bred_arg = atoi(ba) != 0;
   e->head_c = ci;
   e->head_hw = h * w;
   e->feat = d->head_mean_pool ? ci : ci * h * w;
@@ -315,11 +309,11 @@ extern "C" int mi_engine_set_fused_last_block(mi_engine* e, int on) {
 }
 
 // 0 = every kernel on the caller's stream; 1 (default) = weight gradients of blocks >= 2 on an engine-owned side stream,
-// forked after dz_l is written and joined before the call returns control of the gradients to the caller's stream.
+// forked after dz_l is written and joined before the call returns control of the gradients to the caller's stream.  One fork per hidden
+// block: one per pass, with the weight gradients held back until block 2's dz exists, was measured slower (profiles/r5/overlap_fork_ab.txt).
 extern "C" int mi_engine_set_overlap(mi_engine* e, int on) {
   if (!e) return MI_ERR_ARG;
   e->overlap = on != 0;
-  e->fork_once = on == 3 || fork_once_env();
   return MI_OK;
 }
 
@@ -433,7 +427,7 @@ struct Plan {
   float* wgpart_side;   // partials of the weight gradients that run on the side stream
   float* wgpart_l[8];   // fused tail: one partial buffer per block (the folds wait for the pass's advance launch)
   double *gram_part, *gram_s;   // input Gram matrix of the support images (block 1 statistics), or nullptr
-  double *gram_q, *gram_part_q;   // ... of the query images (experiment: MI_GRAM_QUERY), or nullptr
+  double *gram_q, *gram_part_q;   // ... of the query images (mi_engine::gramq), or nullptr
   int half = 0;                 // stream context (engine SideCtx) this plan's side work uses
   float *tmp_loss, *tmp_acc;
   float* hscr;   // head scratch: R{dl} [T][n][ways], row loss [T][n], row hit [T][n]
@@ -547,7 +541,7 @@ static void make_plan(const mi_engine* e, void* ws, int T, int ns, int nq, int K
   if (e->fuse1 && e->gram1 && gram_supported(e->L[0].w, e->L[0].ci) && (K >= 2 || (K >= 1 && second_order))) {   // the support set is swept at least twice
     pl.gram_part = b.take<double>(gram_partial_doubles(T, ns, e->L[0].h, e->L[0].ci));
     pl.gram_s = b.take<double>(gram_doubles(T, e->L[0].ci));
-    if (e->gramq && gram_query_env() && nq == ns) {
+    if (e->gramq && nq == ns) {
       pl.gram_q = b.take<double>(gram_doubles(T, e->L[0].ci));
       pl.gram_part_q = b.take<double>(gram_partial_doubles(T, nq, e->L[0].h, e->L[0].ci));
     }
@@ -644,18 +638,15 @@ extern "C" int mi_workspace_bytes(const mi_engine* e, int tasks, int ways, int s
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-static B1Args b1_args(const mi_engine* e, Plan& pl, ActSet& A, const float* x0, int n, const float* theta) {
-  const Layer& L = e->L[0];
-  B1Args a{};
-  a.x = x0;
-  a.w = theta + L.off_w; a.wstride = e->PS;
-  a.mu = A.mu[0]; a.rstd = A.rstd[0];
-  a.gamma = theta + L.off_gamma; a.beta = theta + L.off_beta; a.pstride = e->PS;
-  a.partial = pl.bnpart; a.wpartial = pl.wgpart;
-  a.n = n; a.hh = L.ho; a.ww = L.wo; a.co = L.co;
-  a.inv_m = 1.f / (float)(n * L.ho * L.wo);
-  return a;
-}
+// "This sweep is the tangent one": trunk_forward / trunk_backward given a Tangent walk the blocks exactly as the primal sweep does, over the
+// SAVED primal pass A, and produce its directional derivative along v -- forward tangents into X, R{gradient} into hv (forward-over-reverse).
+struct Tangent {
+  const float* v;    // direction [T][PS]
+  const float* g;    // gradient of the saved primal pass (its BatchNorm-backward sums)
+  float* hv;         // R{g} = H v
+  TanSet& X;
+  int cur = 0;       // X.dpd[cur]: tangent of the cotangent of the block the backward sweep is at (ping-pong, flipped by every dgrad)
+};
 
 // (fp16 operand form) the largest-magnitude cell of a tensor a convolution is about to read, on the caller's stream `st`
 #define CELL(ptr, per_task, out)                                                   \
@@ -663,6 +654,73 @@ static B1Args b1_args(const mi_engine* e, Plan& pl, ActSet& A, const float* x0, 
     const int _crc = cell_of(e, st, pl, ptr, per_task, T, &(out));                 \
     if (_crc) return _crc;                                                         \
   } while (0)
+
+// ---- argument builders: what every launch of a block / the head has in common; the launch sites add what they write.  Tangent fields are
+// filled in the tangent sweep only.
+static B1Args b1_args(const mi_engine* e, Plan& pl, const ActSet& A, const Tangent* tan, const float* x0, int n, const float* theta) {
+  const Layer& L = e->L[0];
+  const size_t P = e->PS;
+  B1Args a{};
+  a.x = x0;
+  a.w = theta + L.off_w; a.wstride = P;
+  a.mu = A.mu[0]; a.rstd = A.rstd[0];
+  a.gamma = theta + L.off_gamma; a.beta = theta + L.off_beta; a.pstride = P;
+  a.partial = pl.bnpart; a.wpartial = pl.wgpart;
+  a.n = n; a.hh = L.ho; a.ww = L.wo; a.co = L.co;
+  a.inv_m = 1.f / (float)(n * L.ho * L.wo);
+  if (tan) {
+    a.wd = tan->v + L.off_w; a.vstride = P;
+    a.m1 = tan->X.m1[0]; a.m2 = tan->X.m2[0];
+    a.gammad = tan->v + L.off_gamma; a.betad = tan->v + L.off_beta;
+    a.dgamma = tan->g + L.off_gamma; a.dbeta = tan->g + L.off_beta; a.gstride = P;
+  }
+  return a;
+}
+
+// BatchNorm of generic block l over the saved pass A: inputs only (out, zh_out, amax_out, partial, fin and the sums a backward sweep has
+// just formed belong to the launch site)
+static BnArgs bn_args(const mi_engine* e, const ActSet& A, const Tangent* tan, int l, int n, const float* theta) {
+  const Layer& L = e->L[l];
+  const size_t P = e->PS;
+  BnArgs ba{};
+  ba.z = A.z[l]; ba.mu = A.mu[l]; ba.rstd = A.rstd[l];
+  ba.gamma = theta + L.off_gamma; ba.beta = theta + L.off_beta; ba.pstride = P;
+  ba.dp = A.dp[l];
+  ba.n = n; ba.ho = L.ho; ba.wo = L.wo; ba.c = L.co;
+  ba.inv_m = 1.f / (float)(n * L.ho * L.wo);
+  if (tan) {
+    ba.zd = tan->X.zd[l]; ba.m1 = tan->X.m1[l]; ba.m2 = tan->X.m2[l];
+    ba.gammad = tan->v + L.off_gamma; ba.betad = tan->v + L.off_beta; ba.vstride = P;
+    ba.dgamma = tan->g + L.off_gamma; ba.dbeta = tan->g + L.off_beta; ba.gstride = P;
+    ba.dpd = tan->X.dpd[tan->cur];
+  }
+  return ba;
+}
+
+// The head on features f with weights theta (tangent: direction v): gradients (or their tangents) into g -- nullptr: none -- and df.
+// hscr: head scratch R{dl} [T][n][ways], row loss [T][n], row hit [T][n] (nullptr: a launch that needs none).
+static HeadArgs head_args(const mi_engine* e, float* hscr, const float* f, const float* theta, const float* v, float* g, float* df, int n, int T) {
+  HeadArgs ha{};
+  ha.f = f;
+  ha.wl = theta + e->off_wl; ha.bl = theta + e->off_bl; ha.pstride = e->PS;
+  if (v) { ha.wld = v + e->off_wl; ha.bld = v + e->off_bl; ha.vstride = e->PS; }
+  ha.dwl = g ? g + e->off_wl : nullptr; ha.dbl = g ? g + e->off_bl : nullptr; ha.gstride = e->PS;
+  ha.df = df;
+  ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
+  if (hscr) {
+    ha.rdl = hscr;
+    ha.rowloss = hscr + (size_t)T * n * e->d.ways;
+    ha.rowhit = ha.rowloss + (size_t)T * n;
+  }
+  return ha;
+}
+// ... of a primal pass: labels in, loss / accuracy / logits out, prob & dl saved for the tangent pass
+static HeadArgs head_args_primal(const mi_engine* e, float* hscr, const float* f, const int32_t* y, int n, int T, const float* theta, float* g,
+                                 float* loss, float* acc, float* logits, float* prob, float* dl, float* df, bool with_grad) {
+  HeadArgs ha = head_args(e, hscr, f, theta, nullptr, with_grad ? g : nullptr, with_grad ? df : nullptr, n, T);
+  ha.y = y; ha.loss = loss; ha.acc = acc; ha.logits = logits; ha.prob = prob; ha.dl = dl;
+  return ha;
+}
 
 // The one-launch tail (tail.hip) serves a generic last block (not the conv-recompute block 1) feeding a flattened head, outside the fp16
 // operand form (its producers would have to fold largest-magnitude cells).
@@ -674,8 +732,21 @@ static bool fused_last_ok(const mi_engine* e, const Plan& pl, int n, int T) {
   const Layer& L = e->L[nl - 1];
   return tail_supported(n, L.ho, L.wo, L.co, L.pool, e->feat, e->d.ways);
 }
-static void tail_common(const mi_engine* e, const Plan& pl, TailArgs& ta) {
+// The last block's BatchNorm + pooling, the head `ha`, its backward and that block's BatchNorm-backward sums into g (tangent sweep: the
+// tangents of all of these) as one launch.  Tb: tasks that take the backward half.
+static TailArgs tail_args(const mi_engine* e, const Plan& pl, const ActSet& A, const Tangent* tan, const HeadArgs& ha, int n, const float* theta,
+                          float* g, bool with_grad, int Tb) {
+  const int l = (int)e->L.size() - 1;
+  const Layer& L = e->L[l];
+  TailArgs ta{};
+  ta.bn = bn_args(e, A, tan, l, n, theta);
+  ta.bn.out = tan ? tan->X.rdz[l] : A.dz[l];
+  ta.hd = ha;
+  ta.pooled = tan ? tan->X.pd[l] : A.p[l];
+  ta.sum0 = with_grad ? g + L.off_gamma : nullptr; ta.sum1 = with_grad ? g + L.off_beta : nullptr; ta.sum_stride = e->PS;
+  ta.with_grad = with_grad ? 1 : 0; ta.bwd_tasks = Tb;
   ta.wpart = pl.tail_wpart; ta.bpart = pl.tail_bpart; ta.scr = pl.tail_scr; ta.counter = e->counters; ta.stamps = e->tail_stamps;
+  return ta;
 }
 // Debug aid: while set, every launch of the one-launch tail (tail.hip) writes the 100 MHz wall clock at its stage boundaries, thread 0 of each of
 // its workgroups: buf [tasks][4][16] 64-bit words (device memory; the LAST tail launch of a call is what remains).  NULL switches it off.
@@ -685,60 +756,92 @@ extern "C" int mi_debug_tail_stamps(mi_engine* e, unsigned long long* buf) {
   return MI_OK;
 }
 
+// Block 1's backward reads the argmax its forward stored (sparse weight gradient on the matrix pipe, dense parts from the Gram matrix)
+// instead of recomputing conv1 and re-deriving the pooling / ReLU decisions.
+static bool block1_reads_stored_argmax(const mi_engine* e, const ActSet& A, const double* gram) {
+  const Layer& L = e->L[0];
+  return gram && A.arg0 && sparse_wgrad_supported(L.wo, L.ci, L.co);
+}
+
 // Trunk forward: ConvBlocks on n images per task (conv + BN-stat epilogue, finalize, BN+ReLU+pool).
 // skip_last_bn: the last block's BatchNorm + pooling belongs to the caller's tail launch.
+// tan: the tangent of that sweep over the saved pass A (two-term convs with the tangent statistics m1 / m2 in the epilogue, tangent BN).
 static int trunk_forward(mi_engine* e, hipStream_t st, Plan& pl, ActSet& A, const float* x0, int n, int T, const float* theta,
-                         const double* gram = nullptr, bool stats_ready = false, bool skip_last_bn = false) {
+                         const double* gram = nullptr, bool stats_ready = false, bool skip_last_bn = false, const Tangent* tan = nullptr) {
   const int nl = (int)e->L.size();
   const size_t P = e->PS;  // task stride
+  const int fin_mode = tan ? FIN_TSTATS : FIN_STATS, op_conv = tan ? OP_TAN_CONV : OP_CONV_FWD, op_bn = tan ? OP_BN_TAN_FWD : OP_BN_FWD;
   for (int l = 0; l < nl; ++l) {
     const Layer& L = e->L[l];
+    const int mpix = n * L.ho * L.wo;
+    const double inv_m = 1.0 / ((double)n * L.ho * L.wo);
+    float* s0 = tan ? tan->X.m1[l] : A.mu[l];      // this sweep's statistics: mean / rstd of z, or mean(zd) / mean(zhat zd)
+    float* s1 = tan ? tan->X.m2[l] : A.rstd[l];
     if (l == 0 && e->fuse1) {
-      B1Args ba = b1_args(e, pl, A, x0, n, theta);
+      B1Args ba = b1_args(e, pl, A, tan, x0, n, theta);
       int blk = 0;
       if (gram && stats_ready) {   // ... already formed by the advance launch that ended the previous pass
       } else if (gram) {   // mean / variance of conv1's output as quadratic forms of this step's weights (gram.hip)
-        LAUNCH(e, st, OP_GRAM_STATS, 0, launch_gram_stats(st, gram, T, L.ci, L.co, theta + L.off_w, P, nullptr, 0, 1.0 / ((double)n * L.ho * L.wo), 0, A.mu[0], A.rstd[0], nullptr, nullptr));
+        LAUNCH(e, st, OP_GRAM_STATS, 0, launch_gram_stats(st, gram, T, L.ci, L.co, theta + L.off_w, P, ba.wd, ba.vstride, inv_m, tan ? 1 : 0, s0, s1,
+                                                          tan ? A.mu[0] : nullptr, tan ? A.rstd[0] : nullptr));
       } else {
-        ba.fin = fin_of(e, T, 1.0 / ((double)n * L.ho * L.wo), FIN_STATS, A.mu[0], L.co, A.rstd[0], L.co);
-        LAUNCH(e, st, OP_CONV_FWD, 0, launch_block1(st, ba, T, L.ci, B1_STATS, &blk));
+        ba.fin = fin_of(e, T, inv_m, fin_mode, s0, L.co, s1, L.co);
+        LAUNCH(e, st, op_conv, 0, launch_block1(st, ba, T, L.ci, tan ? B1_TSTATS : B1_STATS, &blk));
         if (!ba.fin.counter)
-          LAUNCH(e, st, OP_BN_FINALIZE, 0, launch_bn_finalize(st, pl.bnpart, blk, T, L.co, 1.0 / ((double)n * L.ho * L.wo), FIN_STATS, A.mu[0], L.co, A.rstd[0], L.co));
+          LAUNCH(e, st, OP_BN_FINALIZE, 0, launch_bn_finalize(st, pl.bnpart, blk, T, L.co, inv_m, fin_mode, s0, L.co, s1, L.co));
         ba.fin = FinArgs{};
       }
-      ba.out = A.p[0];
-      ba.zh_out = A.zhm;
-      ba.arg_out = A.arg0;
+      int mode = B1_FWD;
+      if (tan) {
+        ba.out = tan->X.pd[0];
+        ba.zh_out = A.zhm ? tan->X.zhdm : nullptr;
+        mode = B1_TFWD;
+        if (A.zhm && A.arg0) {   // the forward pass kept zhat and the argmax: one conv with the direction's weights suffices
+          ba.arg_in = A.arg0; ba.zh_in = A.zhm;
+          mode = B1_TFWD_ARG;
+        }
+      } else {
+        ba.out = A.p[0];
+        ba.zh_out = A.zhm;
+        ba.arg_out = A.arg0;
+        // Without the Gram path this pass's backward (or tangent) kernels recompute conv1 on the fp32 pipe and re-derive the pooling / ReLU decisions
+        // from it: the forward must then round the same way.  With it every later kernel reads the decisions this launch stores.
+        // (This is NOT block1_reads_stored_argmax: the two differ where the sparse weight gradient does not take the geometry -- ADVICE.md's
+        // medium finding.  Making them agree changes results there and is left to its own change.)
+        ba.fwd_fp32 = (gram && A.arg0) ? 0 : 1;
+      }
       ba.amax_out = cell_bind(e, pl, ba.out);
-      // Without the Gram path this pass's backward (or tangent) kernels recompute conv1 on the fp32 pipe and re-derive the pooling / ReLU decisions
-      // from it: the forward must then round the same way.  With it every later kernel reads the decisions this launch stores.
-      ba.fwd_fp32 = (gram && A.arg0) ? 0 : 1;
-      LAUNCH(e, st, OP_BN_FWD, 0, launch_block1(st, ba, T, L.ci, B1_FWD, nullptr));
+      LAUNCH(e, st, op_bn, 0, launch_block1(st, ba, T, L.ci, mode, nullptr));
       continue;
     }
     ConvArgs ca{};
+    int nterms = 1;
     ca.in[0] = l == 0 ? x0 : A.p[l - 1];
-    ca.wt[0] = theta + L.off_w;
+    ca.wt[0] = (tan ? tan->v : theta) + L.off_w;
+    if (tan) {
+      if (l > 0) { ca.in[1] = tan->X.pd[l - 1]; ca.wt[1] = theta + L.off_w; nterms = 2; }
+      ca.z = A.z[l]; ca.mu = A.mu[l]; ca.rstd = A.rstd[l];
+    }
     ca.wstride = P;
-    ca.out = A.z[l];
+    ca.out = tan ? tan->X.zd[l] : A.z[l];
     ca.partial = pl.bnpart;
     ca.g = geom(L, n);
-    ca.mpix = n * L.ho * L.wo;
+    ca.mpix = mpix;
     int blk = 0;
-    ca.fin = fin_of(e, T, 1.0 / (double)ca.mpix, FIN_STATS, A.mu[l], L.co, A.rstd[l], L.co);
-    if (l >= 1) CELL(ca.in[0], (size_t)n * L.h * L.w * L.ci, ca.amax[0]);
-    LAUNCH(e, st, OP_CONV_FWD, l, launch_conv3x3(st, ca, T, 1, EPI_STATS, 0, &blk));
+    ca.fin = fin_of(e, T, 1.0 / (double)mpix, fin_mode, s0, L.co, s1, L.co);
+    if (l >= 1) {
+      CELL(ca.in[0], (size_t)n * L.h * L.w * L.ci, ca.amax[0]);
+      if (tan) CELL(ca.in[1], (size_t)n * L.h * L.w * L.ci, ca.amax[1]);
+    }
+    LAUNCH(e, st, op_conv, l, launch_conv3x3(st, ca, T, nterms, tan ? EPI_TSTATS : EPI_STATS, 0, &blk));
     if (!ca.fin.counter)
-      LAUNCH(e, st, OP_BN_FINALIZE, l, launch_bn_finalize(st, pl.bnpart, blk, T, L.co, 1.0 / (double)ca.mpix, FIN_STATS, A.mu[l], L.co, A.rstd[l], L.co));
+      LAUNCH(e, st, OP_BN_FINALIZE, l, launch_bn_finalize(st, pl.bnpart, blk, T, L.co, 1.0 / (double)mpix, fin_mode, s0, L.co, s1, L.co));
     if (skip_last_bn && l == nl - 1) break;
-    BnArgs ba{};
-    ba.z = A.z[l]; ba.mu = A.mu[l]; ba.rstd = A.rstd[l];
-    ba.gamma = theta + L.off_gamma; ba.beta = theta + L.off_beta; ba.pstride = P;
-    ba.out = A.p[l];
-    ba.zh_out = A.zhl[l];
-    ba.n = n; ba.ho = L.ho; ba.wo = L.wo; ba.c = L.co;
+    BnArgs ba = bn_args(e, A, tan, l, n, theta);
+    ba.out = tan ? tan->X.pd[l] : A.p[l];
+    ba.zh_out = tan ? (A.zhl[l] ? tan->X.zhdl[l] : nullptr) : A.zhl[l];
     ba.amax_out = cell_bind(e, pl, ba.out);
-    LAUNCH(e, st, OP_BN_FWD, l, launch_bn_fwd(st, ba, T, L.pool));
+    LAUNCH(e, st, op_bn, l, tan ? launch_bn_tan_fwd(st, ba, T, L.pool) : launch_bn_fwd(st, ba, T, L.pool));
   }
   return MI_OK;
 }
@@ -748,161 +851,149 @@ static const float* zh_at_argmax(const mi_engine* e, const ActSet& A, int lower)
   return (lower == 0 && e->fuse1) ? A.zhm : A.zhl[lower];
 }
 
-// Trunk backward from A.dp[last] (gradient w.r.t. the last block's output): writes gamma/beta/conv-weight gradients into g.
-// adv != nullptr (fused tail): weight-gradient folds and block 1's Gram assembly are recorded in *adv for the caller's advance launch
-// instead of being launched here; every block then writes its own partial buffer (pl.wgpart_l).
 static void adv_add_seg(AdvanceArgs* adv, size_t off, int nelem, const float* partial, int nchunks) {
   AdvanceSeg& sg = adv->seg[adv->nseg++];
   sg.off = (unsigned)off; sg.nelem = (unsigned)nelem; sg.partial = partial; sg.nchunks = nchunks;
 }
+// Trunk backward from A.dp[last] (gradient w.r.t. the last block's output): writes gamma/beta/conv-weight gradients into g.
+// adv != nullptr (fused tail): weight-gradient folds and block 1's Gram assembly are recorded in *adv for the caller's advance launch
+// instead of being launched here; every block then writes its own partial buffer (pl.wgpart_l).
 // last_bn_done: the caller's tail launch already formed the last block's dgamma / dbeta (the apply is launched here).
+// tan: the tangent of that sweep, from tan->X.dpd[tan->cur]: g is then tan->hv, and every launch has the primal term and its tangent.
 static int trunk_backward(mi_engine* e, hipStream_t st, Plan& pl, ActSet& A, const float* x0, int n, int T, const float* theta,
-                          float* g, const double* gram = nullptr, AdvanceArgs* adv = nullptr, bool last_bn_done = false) {
+                          float* g, const double* gram = nullptr, AdvanceArgs* adv = nullptr, bool last_bn_done = false, Tangent* tan = nullptr) {
   const int nl = (int)e->L.size();
   const size_t P = e->PS;
-  bool forked = false, red_done[9] = {false, false, false, false, false, false, false, false, false};
-  WgradArgs held[9]; int held_l[9], nheld = 0;                  // weight gradients held back for the pass's one fork of the side stream   // [l]: block l's sums rode in block l+1's dgrad
+  const int op_red = tan ? OP_BN_TAN_BWD_REDUCE : OP_BN_BWD_REDUCE, op_apply = tan ? OP_BN_TAN_BWD_APPLY : OP_BN_BWD_APPLY,
+            op_wgrad = tan ? OP_TAN_WGRAD : OP_WGRAD, op_dgrad = tan ? OP_TAN_DGRAD : OP_DGRAD;
+  bool forked = false, red_done[9] = {false, false, false, false, false, false, false, false, false};   // [l]: block l's sums rode in block l+1's dgrad
+  auto issue_wgrad = [&](hipStream_t ws, WgradArgs& w, int wl) -> int {
+    const Layer& Lw = e->L[wl];
+    w.partial = adv ? pl.wgpart_l[wl] : (ws != st ? pl.wgpart_side : pl.wgpart);
+    int nch = 0;
+    LAUNCH(e, ws, op_wgrad, wl, launch_wgrad3x3(ws, w, T, (tan && wl > 0) ? 2 : 1, &nch));
+    if (adv) adv_add_seg(adv, Lw.off_w, 9 * Lw.ci * Lw.co, w.partial, nch);
+    else LAUNCH(e, ws, OP_WGRAD_REDUCE, wl, launch_wgrad_reduce(ws, w.partial, nch, 9 * Lw.ci * Lw.co, T, g + Lw.off_w, P));
+    return MI_OK;
+  };
   for (int l = nl - 1; l >= 0; --l) {
     const Layer& L = e->L[l];
     const int mpix = n * L.ho * L.wo;
-    const bool b1red_done = red_done[0];
+    const float* dpd = tan ? tan->X.dpd[tan->cur] : nullptr;
     if (l == 0 && e->fuse1) {
-      B1Args b1 = b1_args(e, pl, A, x0, n, theta);
-      b1.dp = A.dp[0];
+      B1Args b1 = b1_args(e, pl, A, tan, x0, n, theta);
+      b1.dp = A.dp[0]; b1.dpd = dpd;
       int blk = 0;
       const FinArgs fin = fin_of(e, T, 1.0, FIN_SUMS, g + L.off_gamma, P, g + L.off_beta, P);
-      if (b1red_done) {   // already summed in the epilogue of block 2's dgrad
+      if (red_done[0]) {   // already summed in the epilogue of block 2's dgrad
       } else if (A.zhm) {   // dgamma / dbeta from pooled-resolution tensors (no conv recompute)
-        PoolRedArgs pr{A.p[0], A.zhm, nullptr, A.dp[0], nullptr, pl.bnpart, n * L.hp * L.wp, L.co, fin};
-        LAUNCH(e, st, OP_BN_BWD_REDUCE, 0, launch_pooled_reduce(st, pr, T, 0, &blk));
+        PoolRedArgs pr{A.p[0], A.zhm, tan ? tan->X.zhdm : nullptr, A.dp[0], dpd, pl.bnpart, n * L.hp * L.wp, L.co, fin};
+        LAUNCH(e, st, op_red, 0, launch_pooled_reduce(st, pr, T, tan ? 1 : 0, &blk));
       } else {
         b1.fin = fin;
-        LAUNCH(e, st, OP_BN_BWD_REDUCE, 0, launch_block1(st, b1, T, L.ci, B1_BWD_REDUCE, &blk));
+        LAUNCH(e, st, op_red, 0, launch_block1(st, b1, T, L.ci, tan ? B1_TBWD_REDUCE : B1_BWD_REDUCE, &blk));
         b1.fin = FinArgs{};
       }
-      if (!fin.counter && !b1red_done)
+      if (!fin.counter && !red_done[0])
         LAUNCH(e, st, OP_BN_FINALIZE, 0, launch_bn_finalize(st, pl.bnpart, blk, T, L.co, 1.0, FIN_SUMS, g + L.off_gamma, P, g + L.off_beta, P));
-      b1.dgamma = g + L.off_gamma; b1.dbeta = g + L.off_beta; b1.gstride = P;
-      if (gram && A.arg0 && sparse_wgrad_supported(L.wo, L.ci, L.co)) {   // sparse part on the matrix pipe, dense parts from the Gram matrix: no conv recompute
+      if (tan) { b1.rdgamma = g + L.off_gamma; b1.rdbeta = g + L.off_beta; b1.hstride = P; }
+      else { b1.dgamma = g + L.off_gamma; b1.dbeta = g + L.off_beta; b1.gstride = P; }
+      if (block1_reads_stored_argmax(e, A, gram)) {
         SparseWgArgs sw{};
         sw.x = x0; sw.arg = A.arg0; sw.dp = A.dp[0]; sw.wpartial = pl.wgpart; sw.n = n; sw.hh = L.ho; sw.ww = L.wo; sw.co = L.co;
-        LAUNCH(e, st, OP_WGRAD, 0, launch_sparse_wgrad(st, sw, T, L.ci, 0, &blk));
-        GramWgArgs gw{};
-        gw.g = gram; gw.spartial = pl.wgpart; gw.nblk = blk; gw.w = theta + L.off_w; gw.wstride = P;
-        gw.mu = A.mu[0]; gw.rstd = A.rstd[0]; gw.gamma = theta + L.off_gamma; gw.pstride = P;
-        gw.dgamma = g + L.off_gamma; gw.dbeta = g + L.off_beta; gw.gstride = P;
+        if (tan) {
+          sw.dpd = dpd; sw.rstd = A.rstd[0]; sw.m2 = b1.m2;
+          sw.gamma = b1.gamma; sw.pstride = P; sw.gammad = b1.gammad; sw.vstride = P;
+        }
+        LAUNCH(e, st, op_wgrad, 0, launch_sparse_wgrad(st, sw, T, L.ci, tan ? 1 : 0, &blk));
+        GramWgArgs gw{};   // (b1's tangent fields are null / 0 in the primal sweep)
+        gw.g = gram; gw.spartial = pl.wgpart; gw.nblk = blk; gw.w = b1.w; gw.wstride = P; gw.wd = b1.wd; gw.vstride = b1.vstride;
+        gw.mu = A.mu[0]; gw.rstd = A.rstd[0]; gw.m1 = b1.m1; gw.m2 = b1.m2;
+        gw.gamma = b1.gamma; gw.pstride = P; gw.gammad = b1.gammad;
+        gw.dgamma = b1.dgamma; gw.dbeta = b1.dbeta; gw.gstride = P;
+        gw.rdgamma = b1.rdgamma; gw.rdbeta = b1.rdbeta; gw.hstride = b1.hstride;
         gw.out = g + L.off_w; gw.ostride = P; gw.ci = L.ci; gw.co = L.co; gw.inv_m = 1.0 / (double)mpix;
-        if (adv) { adv->b1_wgrad = 1; adv->gw_tangent = 0; adv->gw = gw; }
-        else LAUNCH(e, st, OP_WGRAD_REDUCE, 0, launch_gram_wgrad(st, gw, T, 0));
+        if (adv) { adv->b1_wgrad = 1; adv->gw_tangent = tan ? 1 : 0; adv->gw = gw; }
+        else LAUNCH(e, st, OP_WGRAD_REDUCE, 0, launch_gram_wgrad(st, gw, T, tan ? 1 : 0));
         continue;
       }
-      LAUNCH(e, st, OP_WGRAD, 0, launch_block1(st, b1, T, L.ci, B1_BWD_WGRAD, &blk));
+      LAUNCH(e, st, op_wgrad, 0, launch_block1(st, b1, T, L.ci, tan ? B1_TBWD_WGRAD : B1_BWD_WGRAD, &blk));
       if (adv) adv_add_seg(adv, L.off_w, 9 * L.ci * L.co, pl.wgpart, blk);
       else LAUNCH(e, st, OP_WGRAD_REDUCE, 0, launch_wgrad_reduce(st, pl.wgpart, blk, 9 * L.ci * L.co, T, g + L.off_w, P));
       continue;
     }
-    BnArgs ba{};
-    ba.z = A.z[l]; ba.mu = A.mu[l]; ba.rstd = A.rstd[l];
-    ba.gamma = theta + L.off_gamma; ba.beta = theta + L.off_beta; ba.pstride = P;
-    ba.dp = A.dp[l];
+    BnArgs ba = bn_args(e, A, tan, l, n, theta);
     ba.partial = pl.bnpart;
-    ba.n = n; ba.ho = L.ho; ba.wo = L.wo; ba.c = L.co;
-    ba.inv_m = 1.f / (float)mpix;
     int blk = 0;
     const bool bn_done = last_bn_done && l == nl - 1;
     if (!red_done[l] && !bn_done) {
       ba.fin = fin_of(e, T, 1.0, FIN_SUMS, g + L.off_gamma, P, g + L.off_beta, P);
-      LAUNCH(e, st, OP_BN_BWD_REDUCE, l, launch_bn_bwd_reduce(st, ba, T, L.pool, &blk));
+      LAUNCH(e, st, op_red, l, tan ? launch_bn_tan_bwd_reduce(st, ba, T, L.pool, &blk) : launch_bn_bwd_reduce(st, ba, T, L.pool, &blk));
       if (!ba.fin.counter)
         LAUNCH(e, st, OP_BN_FINALIZE, l, launch_bn_finalize(st, pl.bnpart, blk, T, L.co, 1.0, FIN_SUMS, g + L.off_gamma, P, g + L.off_beta, P));
     }
-    ba.dgamma = g + L.off_gamma; ba.dbeta = g + L.off_beta; ba.gstride = P;
-    ba.out = A.dz[l];
+    if (tan) { ba.rdgamma = g + L.off_gamma; ba.rdbeta = g + L.off_beta; ba.hstride = P; }
+    else { ba.dgamma = g + L.off_gamma; ba.dbeta = g + L.off_beta; ba.gstride = P; }
+    float* dz = tan ? tan->X.rdz[l] : A.dz[l];      // dz, or R{dz}
+    ba.out = dz;
     ba.amax_out = cell_bind(e, pl, ba.out);
-    LAUNCH(e, st, OP_BN_BWD_APPLY, l, launch_bn_bwd_apply(st, ba, T, L.pool));
+    LAUNCH(e, st, op_apply, l, tan ? launch_bn_tan_bwd_apply(st, ba, T, L.pool) : launch_bn_bwd_apply(st, ba, T, L.pool));
     WgradArgs wa{};
     wa.x[0] = l == 0 ? x0 : A.p[l - 1];
-    wa.dz[0] = A.dz[l];
+    wa.dz[0] = dz;
+    if (tan && l > 0) { wa.x[1] = tan->X.pd[l - 1]; wa.dz[1] = A.dz[l]; }
     if (l >= 1) {
       CELL(wa.x[0], (size_t)n * L.h * L.w * L.ci, wa.amax_x[0]);
       CELL(wa.dz[0], (size_t)n * L.ho * L.wo * L.co, wa.amax_dz[0]);
+      if (tan) {
+        CELL(wa.x[1], (size_t)n * L.h * L.w * L.ci, wa.amax_x[1]);
+        CELL(wa.dz[1], (size_t)n * L.ho * L.wo * L.co, wa.amax_dz[1]);
+      }
     }
     wa.g = geom(L, n);
     wa.mpix = mpix;
-    // The weight gradients of the hidden blocks run on the side stream beside the dgrad chain.  One fork per BLOCK is the default
-    // (fork_once = false); with one fork per PASS (mi_engine_set_overlap(e, 3); measured slower, profiles/r5/overlap_fork_ab.txt) they are held
-    // back until the last hidden block's dz exists and then issued together -- they overlap that block's dgrad and block 1's kernels --
-    // because every fork is an event record on the caller's stream, which idles it for ~7 us (tools/launch_floor.py: 25 such gaps per
-    // meta-iteration with one fork per block, at every task count; profiles/r5/launch_floor_cfg2_T*.txt).
-    auto issue_wgrad = [&](hipStream_t ws, WgradArgs& w, int wl) -> int {
-      const Layer& Lw = e->L[wl];
-      w.partial = adv ? pl.wgpart_l[wl] : (ws != st ? pl.wgpart_side : pl.wgpart);
-      int nch = 0;
-      LAUNCH(e, ws, OP_WGRAD, wl, launch_wgrad3x3(ws, w, T, 1, &nch));
-      if (adv) adv_add_seg(adv, Lw.off_w, 9 * Lw.ci * Lw.co, w.partial, nch);
-      else LAUNCH(e, ws, OP_WGRAD_REDUCE, wl, launch_wgrad_reduce(ws, w.partial, nch, 9 * Lw.ci * Lw.co, T, g + Lw.off_w, P));
-      return MI_OK;
-    };
-    if (l > 0 && e->overlap && e->fork_once) {
-      held[nheld] = wa; held_l[nheld++] = l;
-      if (l == 1) {
-        hipStream_t ws = side_fork(e, st, pl.half);
-        if (ws != st) forked = true;
-        for (int q = 0; q < nheld; ++q) { const int rc = issue_wgrad(ws, held[q], held_l[q]); if (rc) return rc; }
-        nheld = 0;
-      }
-    } else {
-      hipStream_t ws = l > 0 ? side_fork(e, st, pl.half) : st;
-      if (ws != st) forked = true;
-      const int rc = issue_wgrad(ws, wa, l);
-      if (rc) return rc;
-    }
+    // The weight gradients of the hidden blocks run on the side stream beside the dgrad chain, one fork per block.  Every fork is an event
+    // record on the caller's stream, which idles it for ~7 us (tools/launch_floor.py: 25 such gaps per meta-iteration, at every task
+    // count; profiles/r5/launch_floor_cfg2_T*.txt).
+    hipStream_t ws = l > 0 ? side_fork(e, st, pl.half) : st;
+    if (ws != st) forked = true;
+    const int rc = issue_wgrad(ws, wa, l);
+    if (rc) return rc;
     if (l > 0) {
       ConvArgs ca{};
-      ca.in[0] = A.dz[l];
-      ca.wt[0] = theta + L.off_w;
+      ca.in[0] = dz; ca.wt[0] = theta + L.off_w; ca.amax[0] = wa.amax_dz[0];
+      if (tan) { ca.in[1] = A.dz[l]; ca.wt[1] = tan->v + L.off_w; ca.amax[1] = wa.amax_dz[1]; }
       ca.wstride = P;
-      ca.out = A.dp[l - 1];
-      ca.amax[0] = wa.amax_dz[0];
+      ca.out = tan ? tan->X.dpd[tan->cur ^ 1] : A.dp[l - 1];
       ca.g = geom_dgrad(L, n);
       ca.mpix = n * L.h * L.w;
+      const int nterms = tan ? 2 : 1;
       const float* zh_lo = dgrad_carries_reduce(e, l) ? zh_at_argmax(e, A, l - 1) : nullptr;
-      if (zh_lo) {   // dgamma / dbeta of the block below in this kernel's epilogue
+      const float* zhd_lo = !tan ? nullptr : (l - 1 == 0 && e->fuse1) ? tan->X.zhdm : tan->X.zhdl[l - 1];
+      if (zh_lo && (!tan || zhd_lo)) {   // dgamma / dbeta (or their tangents) of the block below in this kernel's epilogue
         const Layer& L0 = e->L[l - 1];
         ca.bp = A.p[l - 1]; ca.bzh = zh_lo; ca.partial = pl.bnpart;
-        ca.barg = (l - 1 == 0 && e->fuse1 && e->bred_arg) ? A.arg0 : nullptr;
+        if (tan) { ca.bzhd = zhd_lo; ca.bdp = A.dp[l - 1]; }
+        ca.barg = (l - 1 == 0 && e->fuse1) ? A.arg0 : nullptr;   // block 1's argmax byte replaces the read of p
         ca.fin = fin_of(e, T, 1.0, FIN_SUMS, g + L0.off_gamma, P, g + L0.off_beta, P);
         int blk0 = 0;
-        LAUNCH(e, st, OP_DGRAD, l, launch_conv3x3(st, ca, T, 1, EPI_BRED, 1, &blk0));
+        LAUNCH(e, st, op_dgrad, l, launch_conv3x3(st, ca, T, nterms, EPI_BRED, 1, &blk0));
         if (!ca.fin.counter)
           LAUNCH(e, st, OP_BN_FINALIZE, l - 1, launch_bn_finalize(st, pl.bnpart, blk0, T, L0.co, 1.0, FIN_SUMS, g + L0.off_gamma, P, g + L0.off_beta, P));
         red_done[l - 1] = true;
       } else {
-        LAUNCH(e, st, OP_DGRAD, l, launch_conv3x3(st, ca, T, 1, EPI_NONE, 1, nullptr));
+        LAUNCH(e, st, op_dgrad, l, launch_conv3x3(st, ca, T, nterms, EPI_NONE, 1, nullptr));
       }
+      if (tan) tan->cur ^= 1;
     }
   }
   return side_join(e, st, pl.half, forked);
 }
 
-static void head_scratch(const mi_engine* e, HeadArgs& ha, float* hscr, int T, int n) {
-  ha.rdl = hscr;
-  ha.rowloss = hscr + (size_t)T * n * e->d.ways;
-  ha.rowhit = ha.rowloss + (size_t)T * n;
-}
-
 // Linear + CE on features f [T][n][feat]: loss/acc/logits, prob & dl saved, and (with_grad) dwl/dbl into g, df.
 static int head_pass(mi_engine* e, hipStream_t st, float* hscr, const float* f, const int32_t* y, int n, int T, const float* theta,
                      float* g, float* loss, float* acc, float* logits, float* prob, float* dl, float* df, bool with_grad) {
-  const size_t P = e->PS;
-  HeadArgs ha{};
-  ha.f = f;
-  ha.wl = theta + e->off_wl; ha.bl = theta + e->off_bl; ha.pstride = P;
-  ha.y = y; ha.loss = loss; ha.acc = acc; ha.logits = logits; ha.prob = prob; ha.dl = dl;
-  ha.dwl = with_grad ? g + e->off_wl : nullptr; ha.dbl = with_grad ? g + e->off_bl : nullptr; ha.gstride = P;
-  ha.df = with_grad ? df : nullptr;
-  ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
-  head_scratch(e, ha, hscr, T, n);
+  const HeadArgs ha = head_args_primal(e, hscr, f, y, n, T, theta, g, loss, acc, logits, prob, dl, df, with_grad);
   if (with_grad) HEAD_LDS(e, "head", n, ha.ways, 0);
   LAUNCH(e, st, OP_HEAD, 0, launch_head_fwd_bwd(st, ha, T, with_grad ? 1 : 0));
   return MI_OK;
@@ -951,28 +1042,9 @@ static int pass_fwd_bwd(mi_engine* e, hipStream_t st, Plan& pl, ActSet& A, const
   if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean(st, A.p[nl - 1], A.f, T * n, e->head_hw, e->head_c));
   if (with_grad && !adv) HIPCHK(e, hipMemsetAsync(g, 0, (size_t)T * e->PS * sizeof(float), st));
   if (fused_last) {   // the last block's BatchNorm + pooling, the head, its backward and that block's BatchNorm backward: one launch (tail.hip)
-    const Layer& L = e->L[nl - 1];
-    const size_t P = e->PS;
-    TailArgs ta{};
-    BnArgs& ba = ta.bn;
-    ba.z = A.z[nl - 1]; ba.mu = A.mu[nl - 1]; ba.rstd = A.rstd[nl - 1];
-    ba.gamma = theta + L.off_gamma; ba.beta = theta + L.off_beta; ba.pstride = P;
-    ba.dp = A.dp[nl - 1]; ba.out = A.dz[nl - 1];
-    ba.n = n; ba.ho = L.ho; ba.wo = L.wo; ba.c = L.co;
-    ba.inv_m = 1.f / (float)(n * L.ho * L.wo);
-    HeadArgs& ha = ta.hd;
-    ha.f = A.f;
-    ha.wl = theta + e->off_wl; ha.bl = theta + e->off_bl; ha.pstride = P;
-    ha.y = y; ha.loss = loss; ha.acc = acc; ha.logits = logits; ha.prob = A.prob; ha.dl = A.dl;
-    ha.dwl = with_grad ? g + e->off_wl : nullptr; ha.dbl = with_grad ? g + e->off_bl : nullptr; ha.gstride = P;
-    ha.df = with_grad ? A.df : nullptr;
-    ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
-    head_scratch(e, ha, pl.hscr, T, n);
-    ta.pooled = A.p[nl - 1];
-    ta.sum0 = with_grad ? g + L.off_gamma : nullptr; ta.sum1 = with_grad ? g + L.off_beta : nullptr; ta.sum_stride = P;
-    ta.with_grad = with_grad ? 1 : 0; ta.bwd_tasks = Tb;
-    tail_common(e, pl, ta);
-    LAUNCH(e, st, OP_HEAD, 0, launch_tail(st, ta, T, L.pool, 0));
+    const HeadArgs ha = head_args_primal(e, pl.hscr, A.f, y, n, T, theta, g, loss, acc, logits, A.prob, A.dl, A.df, with_grad);
+    const TailArgs ta = tail_args(e, pl, A, nullptr, ha, n, theta, g, with_grad, Tb);
+    LAUNCH(e, st, OP_HEAD, 0, launch_tail(st, ta, T, e->L[nl - 1].pool, 0));
     if (!with_grad || Tb == 0) return MI_OK;
     return trunk_backward(e, st, pl, A, x0, n, Tb, theta, g, gram, adv, true);
   }
@@ -989,243 +1061,30 @@ static int pass_hvp(mi_engine* e, hipStream_t st, Plan& pl, ActSet& A, const flo
                     const float* g, const float* v, float* hv, const double* gram = nullptr, const float* dl_fixed = nullptr,
                     float* ld_out = nullptr, AdvanceArgs* adv = nullptr, bool stats_ready = false) {
   const int nl = (int)e->L.size();
-  const size_t P = e->PS;  // task stride
   TanSet& X = pl.tan;
+  Tangent tan{v, g, hv, X};
   const bool fused_last = !dl_fixed && !ld_out && fused_last_ok(e, pl, n, T);   // tangent tail in one launch (tail.hip)
-  if (!adv) HIPCHK(e, hipMemsetAsync(hv, 0, (size_t)T * P * sizeof(float), st));
-  for (int l = 0; l < nl; ++l) {
-    const Layer& L = e->L[l];
-    const int mpix = n * L.ho * L.wo;
-    if (l == 0 && e->fuse1) {
-      B1Args b1 = b1_args(e, pl, A, x0, n, theta);
-      b1.wd = v + L.off_w; b1.vstride = P;
-      int blk = 0;
-      if (gram && stats_ready) {   // ... already formed by the advance launch that ended the previous pass
-      } else if (gram) {
-        LAUNCH(e, st, OP_GRAM_STATS, 0, launch_gram_stats(st, gram, T, L.ci, L.co, theta + L.off_w, P, v + L.off_w, P, 1.0 / (double)mpix, 1, X.m1[0], X.m2[0], A.mu[0], A.rstd[0]));
-      } else {
-        b1.fin = fin_of(e, T, 1.0 / (double)mpix, FIN_TSTATS, X.m1[0], L.co, X.m2[0], L.co);
-        LAUNCH(e, st, OP_TAN_CONV, 0, launch_block1(st, b1, T, L.ci, B1_TSTATS, &blk));
-        if (!b1.fin.counter)
-          LAUNCH(e, st, OP_BN_FINALIZE, 0, launch_bn_finalize(st, pl.bnpart, blk, T, L.co, 1.0 / (double)mpix, FIN_TSTATS, X.m1[0], L.co, X.m2[0], L.co));
-        b1.fin = FinArgs{};
-      }
-      b1.m1 = X.m1[0]; b1.m2 = X.m2[0];
-      b1.gammad = v + L.off_gamma; b1.betad = v + L.off_beta;
-      b1.out = X.pd[0];
-      b1.zh_out = A.zhm ? X.zhdm : nullptr;
-      if (A.zhm && A.arg0) {   // the forward pass kept zhat and the argmax: one conv with the direction's weights suffices
-        b1.arg_in = A.arg0; b1.zh_in = A.zhm;
-        b1.amax_out = cell_bind(e, pl, b1.out);
-        LAUNCH(e, st, OP_BN_TAN_FWD, 0, launch_block1(st, b1, T, L.ci, B1_TFWD_ARG, nullptr));
-      } else {
-        b1.amax_out = cell_bind(e, pl, b1.out);
-        LAUNCH(e, st, OP_BN_TAN_FWD, 0, launch_block1(st, b1, T, L.ci, B1_TFWD, nullptr));
-      }
-      continue;
-    }
-    ConvArgs ca{};
-    ca.in[0] = l == 0 ? x0 : A.p[l - 1];
-    ca.wt[0] = v + L.off_w;
-    if (l > 0) { ca.in[1] = X.pd[l - 1]; ca.wt[1] = theta + L.off_w; }
-    ca.wstride = P;
-    ca.out = X.zd[l];
-    ca.z = A.z[l]; ca.mu = A.mu[l]; ca.rstd = A.rstd[l];
-    ca.partial = pl.bnpart;
-    ca.g = geom(L, n);
-    ca.mpix = mpix;
-    int blk = 0;
-    ca.fin = fin_of(e, T, 1.0 / (double)mpix, FIN_TSTATS, X.m1[l], L.co, X.m2[l], L.co);
-    if (l >= 1) {
-      CELL(ca.in[0], (size_t)n * L.h * L.w * L.ci, ca.amax[0]);
-      CELL(ca.in[1], (size_t)n * L.h * L.w * L.ci, ca.amax[1]);
-    }
-    LAUNCH(e, st, OP_TAN_CONV, l, launch_conv3x3(st, ca, T, l > 0 ? 2 : 1, EPI_TSTATS, 0, &blk));
-    if (!ca.fin.counter)
-      LAUNCH(e, st, OP_BN_FINALIZE, l, launch_bn_finalize(st, pl.bnpart, blk, T, L.co, 1.0 / (double)mpix, FIN_TSTATS, X.m1[l], L.co, X.m2[l], L.co));
-    if (fused_last && l == nl - 1) break;
-    BnArgs ba{};
-    ba.z = A.z[l]; ba.zd = X.zd[l]; ba.mu = A.mu[l]; ba.rstd = A.rstd[l]; ba.m1 = X.m1[l]; ba.m2 = X.m2[l];
-    ba.gamma = theta + L.off_gamma; ba.beta = theta + L.off_beta; ba.pstride = P;
-    ba.gammad = v + L.off_gamma; ba.betad = v + L.off_beta; ba.vstride = P;
-    ba.out = X.pd[l];
-    ba.zh_out = A.zhl[l] ? X.zhdl[l] : nullptr;
-    ba.n = n; ba.ho = L.ho; ba.wo = L.wo; ba.c = L.co;
-    ba.amax_out = cell_bind(e, pl, ba.out);
-    LAUNCH(e, st, OP_BN_TAN_FWD, l, launch_bn_tan_fwd(st, ba, T, L.pool));
-  }
+  if (!adv) HIPCHK(e, hipMemsetAsync(hv, 0, (size_t)T * e->PS * sizeof(float), st));
+  const int rc = trunk_forward(e, st, pl, A, x0, n, T, theta, gram, stats_ready, fused_last, &tan);
+  if (rc) return rc;
   const float* fd = X.pd[nl - 1];
   if (e->d.head_mean_pool) {
     HIPCHK(e, launch_spatial_mean(st, X.pd[nl - 1], X.fd, T * n, e->head_hw, e->head_c));
     fd = X.fd;
   }
-  int cur = 0;
-  bool forked = false, red_done[9] = {false, false, false, false, false, false, false, false, false};
-  WgradArgs held[9]; int held_l[9], nheld = 0;                  // weight gradients held back for the pass's one fork of the side stream
-  HeadArgs ha{};
-  ha.f = A.f; ha.fd = fd;
-  ha.wl = theta + e->off_wl; ha.bl = theta + e->off_bl; ha.pstride = P;
-  ha.wld = v + e->off_wl; ha.bld = v + e->off_bl; ha.vstride = P;
+  HeadArgs ha = head_args(e, pl.hscr, A.f, theta, v, hv, e->d.head_mean_pool ? X.rdf : X.dpd[tan.cur], n, T);
+  ha.fd = fd;
   ha.prob = A.prob; ha.dl = A.dl;
   if (dl_fixed) { ha.dl = const_cast<float*>(dl_fixed); ha.fixed_dl = 1; ha.ld_out = ld_out; }
-  ha.dwl = hv + e->off_wl; ha.dbl = hv + e->off_bl; ha.gstride = P;
-  ha.df = e->d.head_mean_pool ? X.rdf : X.dpd[cur];
-  ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
-  head_scratch(e, ha, pl.hscr, T, n);
   if (fused_last) {   // tangent of the last block's BatchNorm + pooling, the head's tangent and the tangent of that block's BatchNorm backward
-    const Layer& L = e->L[nl - 1];
-    TailArgs ta{};
-    BnArgs& ba = ta.bn;
-    ba.z = A.z[nl - 1]; ba.zd = X.zd[nl - 1]; ba.mu = A.mu[nl - 1]; ba.rstd = A.rstd[nl - 1]; ba.m1 = X.m1[nl - 1]; ba.m2 = X.m2[nl - 1];
-    ba.gamma = theta + L.off_gamma; ba.beta = theta + L.off_beta; ba.pstride = P;
-    ba.gammad = v + L.off_gamma; ba.betad = v + L.off_beta; ba.vstride = P;
-    ba.dgamma = g + L.off_gamma; ba.dbeta = g + L.off_beta; ba.gstride = P;
-    ba.dp = A.dp[nl - 1]; ba.dpd = X.dpd[cur]; ba.out = X.rdz[nl - 1];
-    ba.n = n; ba.ho = L.ho; ba.wo = L.wo; ba.c = L.co;
-    ba.inv_m = 1.f / (float)(n * L.ho * L.wo);
-    ta.hd = ha;
-    ta.pooled = X.pd[nl - 1];
-    ta.sum0 = hv + L.off_gamma; ta.sum1 = hv + L.off_beta; ta.sum_stride = P;
-    ta.with_grad = 1; ta.bwd_tasks = T;
-    tail_common(e, pl, ta);
-    LAUNCH(e, st, OP_HEAD_TAN, 0, launch_tail(st, ta, T, L.pool, 1));
+    const TailArgs ta = tail_args(e, pl, A, &tan, ha, n, theta, hv, true, T);
+    LAUNCH(e, st, OP_HEAD_TAN, 0, launch_tail(st, ta, T, e->L[nl - 1].pool, 1));
   } else {
     HEAD_LDS(e, "head tangent", n, ha.ways, 1);
     LAUNCH(e, st, OP_HEAD_TAN, 0, launch_head_tangent(st, ha, T));
   }
-  if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean_bwd(st, X.rdf, X.dpd[cur], T * n, e->head_hw, e->head_c));
-  for (int l = nl - 1; l >= 0; --l) {
-    const Layer& L = e->L[l];
-    const int mpix = n * L.ho * L.wo;
-    const bool b1red_done = red_done[0];
-    if (l == 0 && e->fuse1) {
-      B1Args b1 = b1_args(e, pl, A, x0, n, theta);
-      b1.wd = v + L.off_w; b1.vstride = P;
-      b1.m1 = X.m1[0]; b1.m2 = X.m2[0];
-      b1.gammad = v + L.off_gamma; b1.betad = v + L.off_beta;
-      b1.dgamma = g + L.off_gamma; b1.dbeta = g + L.off_beta; b1.gstride = P;
-      b1.dp = A.dp[0]; b1.dpd = X.dpd[cur];
-      int blk = 0;
-      const FinArgs fin = fin_of(e, T, 1.0, FIN_SUMS, hv + L.off_gamma, P, hv + L.off_beta, P);
-      if (b1red_done) {
-      } else if (A.zhm) {
-        PoolRedArgs pr{A.p[0], A.zhm, X.zhdm, A.dp[0], X.dpd[cur], pl.bnpart, n * L.hp * L.wp, L.co, fin};
-        LAUNCH(e, st, OP_BN_TAN_BWD_REDUCE, 0, launch_pooled_reduce(st, pr, T, 1, &blk));
-      } else {
-        b1.fin = fin;
-        LAUNCH(e, st, OP_BN_TAN_BWD_REDUCE, 0, launch_block1(st, b1, T, L.ci, B1_TBWD_REDUCE, &blk));
-        b1.fin = FinArgs{};
-      }
-      if (!fin.counter && !b1red_done)
-        LAUNCH(e, st, OP_BN_FINALIZE, 0, launch_bn_finalize(st, pl.bnpart, blk, T, L.co, 1.0, FIN_SUMS, hv + L.off_gamma, P, hv + L.off_beta, P));
-      b1.rdgamma = hv + L.off_gamma; b1.rdbeta = hv + L.off_beta; b1.hstride = P;
-      if (gram && A.arg0 && sparse_wgrad_supported(L.wo, L.ci, L.co)) {
-        SparseWgArgs sw{};
-        sw.x = x0; sw.arg = A.arg0; sw.dp = A.dp[0]; sw.dpd = X.dpd[cur]; sw.rstd = A.rstd[0]; sw.m2 = X.m2[0];
-        sw.gamma = theta + L.off_gamma; sw.pstride = P; sw.gammad = v + L.off_gamma; sw.vstride = P;
-        sw.wpartial = pl.wgpart; sw.n = n; sw.hh = L.ho; sw.ww = L.wo; sw.co = L.co;
-        LAUNCH(e, st, OP_TAN_WGRAD, 0, launch_sparse_wgrad(st, sw, T, L.ci, 1, &blk));
-        GramWgArgs gw{};
-        gw.g = gram; gw.spartial = pl.wgpart; gw.nblk = blk; gw.w = theta + L.off_w; gw.wstride = P; gw.wd = v + L.off_w; gw.vstride = P;
-        gw.mu = A.mu[0]; gw.rstd = A.rstd[0]; gw.m1 = X.m1[0]; gw.m2 = X.m2[0];
-        gw.gamma = theta + L.off_gamma; gw.pstride = P; gw.gammad = v + L.off_gamma;
-        gw.dgamma = g + L.off_gamma; gw.dbeta = g + L.off_beta; gw.gstride = P;
-        gw.rdgamma = hv + L.off_gamma; gw.rdbeta = hv + L.off_beta; gw.hstride = P;
-        gw.out = hv + L.off_w; gw.ostride = P; gw.ci = L.ci; gw.co = L.co; gw.inv_m = 1.0 / (double)mpix;
-        if (adv) { adv->b1_wgrad = 1; adv->gw_tangent = 1; adv->gw = gw; }
-        else LAUNCH(e, st, OP_WGRAD_REDUCE, 0, launch_gram_wgrad(st, gw, T, 1));
-        continue;
-      }
-      LAUNCH(e, st, OP_TAN_WGRAD, 0, launch_block1(st, b1, T, L.ci, B1_TBWD_WGRAD, &blk));
-      if (adv) adv_add_seg(adv, L.off_w, 9 * L.ci * L.co, pl.wgpart, blk);
-      else LAUNCH(e, st, OP_WGRAD_REDUCE, 0, launch_wgrad_reduce(st, pl.wgpart, blk, 9 * L.ci * L.co, T, hv + L.off_w, P));
-      continue;
-    }
-    BnArgs ba{};
-    ba.z = A.z[l]; ba.zd = X.zd[l]; ba.mu = A.mu[l]; ba.rstd = A.rstd[l]; ba.m1 = X.m1[l]; ba.m2 = X.m2[l];
-    ba.gamma = theta + L.off_gamma; ba.beta = theta + L.off_beta; ba.pstride = P;
-    ba.gammad = v + L.off_gamma; ba.betad = v + L.off_beta; ba.vstride = P;
-    ba.dgamma = g + L.off_gamma; ba.dbeta = g + L.off_beta; ba.gstride = P;
-    ba.dp = A.dp[l]; ba.dpd = X.dpd[cur];
-    ba.partial = pl.bnpart;
-    ba.n = n; ba.ho = L.ho; ba.wo = L.wo; ba.c = L.co;
-    ba.inv_m = 1.f / (float)mpix;
-    int blk = 0;
-    const bool bn_done = fused_last && l == nl - 1;
-    if (!red_done[l] && !bn_done) {
-      ba.fin = fin_of(e, T, 1.0, FIN_SUMS, hv + L.off_gamma, P, hv + L.off_beta, P);
-      LAUNCH(e, st, OP_BN_TAN_BWD_REDUCE, l, launch_bn_tan_bwd_reduce(st, ba, T, L.pool, &blk));
-      if (!ba.fin.counter)
-        LAUNCH(e, st, OP_BN_FINALIZE, l, launch_bn_finalize(st, pl.bnpart, blk, T, L.co, 1.0, FIN_SUMS, hv + L.off_gamma, P, hv + L.off_beta, P));
-    }
-    ba.rdgamma = hv + L.off_gamma; ba.rdbeta = hv + L.off_beta; ba.hstride = P;
-    ba.out = X.rdz[l];
-    ba.amax_out = cell_bind(e, pl, ba.out);
-    LAUNCH(e, st, OP_BN_TAN_BWD_APPLY, l, launch_bn_tan_bwd_apply(st, ba, T, L.pool));
-    WgradArgs wa{};
-    wa.x[0] = l == 0 ? x0 : A.p[l - 1];
-    wa.dz[0] = X.rdz[l];
-    if (l > 0) { wa.x[1] = X.pd[l - 1]; wa.dz[1] = A.dz[l]; }
-    if (l >= 1) {
-      CELL(wa.x[0], (size_t)n * L.h * L.w * L.ci, wa.amax_x[0]);
-      CELL(wa.dz[0], (size_t)n * L.ho * L.wo * L.co, wa.amax_dz[0]);
-      CELL(wa.x[1], (size_t)n * L.h * L.w * L.ci, wa.amax_x[1]);
-      CELL(wa.dz[1], (size_t)n * L.ho * L.wo * L.co, wa.amax_dz[1]);
-    }
-    wa.g = geom(L, n);
-    wa.mpix = mpix;
-    // (one fork of the side stream per pass, as in the primal backward pass above)
-    auto issue_wgrad = [&](hipStream_t ws, WgradArgs& w, int wl) -> int {
-      const Layer& Lw = e->L[wl];
-      w.partial = adv ? pl.wgpart_l[wl] : (ws != st ? pl.wgpart_side : pl.wgpart);
-      int nch = 0;
-      LAUNCH(e, ws, OP_TAN_WGRAD, wl, launch_wgrad3x3(ws, w, T, wl > 0 ? 2 : 1, &nch));
-      if (adv) adv_add_seg(adv, Lw.off_w, 9 * Lw.ci * Lw.co, w.partial, nch);
-      else LAUNCH(e, ws, OP_WGRAD_REDUCE, wl, launch_wgrad_reduce(ws, w.partial, nch, 9 * Lw.ci * Lw.co, T, hv + Lw.off_w, P));
-      return MI_OK;
-    };
-    if (l > 0 && e->overlap && e->fork_once) {
-      held[nheld] = wa; held_l[nheld++] = l;
-      if (l == 1) {
-        hipStream_t ws = side_fork(e, st, pl.half);
-        if (ws != st) forked = true;
-        for (int q = 0; q < nheld; ++q) { const int rc = issue_wgrad(ws, held[q], held_l[q]); if (rc) return rc; }
-        nheld = 0;
-      }
-    } else {
-      hipStream_t ws = l > 0 ? side_fork(e, st, pl.half) : st;
-      if (ws != st) forked = true;
-      const int rc = issue_wgrad(ws, wa, l);
-      if (rc) return rc;
-    }
-    if (l > 0) {
-      ConvArgs ca{};
-      ca.in[0] = X.rdz[l]; ca.wt[0] = theta + L.off_w;
-      ca.in[1] = A.dz[l]; ca.wt[1] = v + L.off_w;
-      ca.amax[0] = wa.amax_dz[0]; ca.amax[1] = wa.amax_dz[1];
-      ca.wstride = P;
-      ca.out = X.dpd[cur ^ 1];
-      ca.g = geom_dgrad(L, n);
-      ca.mpix = n * L.h * L.w;
-      const float* zh_lo = dgrad_carries_reduce(e, l) ? zh_at_argmax(e, A, l - 1) : nullptr;
-      const float* zhd_lo = (l - 1 == 0 && e->fuse1) ? X.zhdm : X.zhdl[l - 1];
-      if (zh_lo && zhd_lo) {   // R{dgamma}, R{dbeta} of the block below in this kernel's epilogue
-        const Layer& L0 = e->L[l - 1];
-        ca.bp = A.p[l - 1]; ca.bzh = zh_lo; ca.bzhd = zhd_lo; ca.bdp = A.dp[l - 1]; ca.partial = pl.bnpart;
-        ca.barg = (l - 1 == 0 && e->fuse1 && e->bred_arg) ? A.arg0 : nullptr;
-        ca.fin = fin_of(e, T, 1.0, FIN_SUMS, hv + L0.off_gamma, P, hv + L0.off_beta, P);
-        int blk0 = 0;
-        LAUNCH(e, st, OP_TAN_DGRAD, l, launch_conv3x3(st, ca, T, 2, EPI_BRED, 1, &blk0));
-        if (!ca.fin.counter)
-          LAUNCH(e, st, OP_BN_FINALIZE, l - 1, launch_bn_finalize(st, pl.bnpart, blk0, T, L0.co, 1.0, FIN_SUMS, hv + L0.off_gamma, P, hv + L0.off_beta, P));
-        red_done[l - 1] = true;
-      } else {
-        LAUNCH(e, st, OP_TAN_DGRAD, l, launch_conv3x3(st, ca, T, 2, EPI_NONE, 1, nullptr));
-      }
-      cur ^= 1;
-    }
-  }
-  return side_join(e, st, pl.half, forked);
+  if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean_bwd(st, X.rdf, X.dpd[tan.cur], T * n, e->head_hw, e->head_c));
+  return trunk_backward(e, st, pl, A, x0, n, T, theta, hv, gram, adv, fused_last, &tan);
 }
 
 // The part of an advance launch that does not depend on the pass: sizes, strides, the never-written elements, block 1's geometry.
@@ -1273,11 +1132,12 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
   if (pl.gram_s)
     LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, pl.xs, T, ns, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part, pl.gram_s));
   const double* gq = pl.gram_q;          // (also for forward-only calls and tasks: the same query forward whether or not a backward half follows)
-  bool gq_side = false;
-  if (gq && gram_query_env() == 2 && e->overlap) {   // the query images' Gram matrix beside the inner loop
+  bool gq_side = false, gq_launched = false;
+  if (gq && e->overlap) {   // the query images' Gram matrix beside the inner loop (on `st` if the side stream cannot be had)
     hipStream_t ws = side_fork(e, st, pl.half);
     gq_side = ws != st;
     LAUNCH(e, ws, OP_GRAM, 0, launch_input_gram(ws, pl.xq, T, nq, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part_q, pl.gram_q));
+    gq_launched = true;
   }
   const bool stats0 = tail && pl.gram_s && K > 0;
   if (stats0) {   // block 1's statistics of the first support pass, from theta_0 (nothing folded, nothing written)
@@ -1307,8 +1167,8 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
   }
   float* thK = pl.theta + (size_t)K * TP;
   AdvanceArgs advq = advance_base(e, pl.lam);
-  if (gq && gq_side) { const int jrc = side_join(e, st, pl.half, true); if (jrc) return jrc; }
-  else if (gq) LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, pl.xq, T, nq, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part_q, pl.gram_q));
+  if (gq_side) { const int jrc = side_join(e, st, pl.half, true); if (jrc) return jrc; }
+  else if (gq && !gq_launched) LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, pl.xq, T, nq, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part_q, pl.gram_q));
   int rc = pass_fwd_bwd(e, st, pl, pl.qry, pl.xq, pl.yq, nq, T, thK, pl.lam, loss_out, acc_out, logits_out, with_grad != 0, gq,
                         (tail && with_grad) ? &advq : nullptr, false, Tg);
   if (rc) return rc;
@@ -1483,15 +1343,8 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const float* theta, 
   if (second_order) {
     for (int k = K - 1; k >= 0; --k) {
       HIPCHK(e, hipMemsetAsync(ap.hv, 0, TP * sizeof(float), st));
-      HeadArgs ha{};
-      ha.f = ap.fs; ha.fd = nullptr;
-      ha.wl = ap.theta + (size_t)k * TP + e->off_wl; ha.bl = ap.theta + (size_t)k * TP + e->off_bl; ha.pstride = e->PS;
-      ha.wld = ap.lam + e->off_wl; ha.bld = ap.lam + e->off_bl; ha.vstride = e->PS;
+      HeadArgs ha = head_args(e, ap.hscr, ap.fs, ap.theta + (size_t)k * TP, ap.lam, ap.hv, ap.rdf, n, T);   // (the features are fixed: no fd)
       ha.prob = ap.prob + k * pw; ha.dl = ap.dl + k * pw;
-      ha.dwl = ap.hv + e->off_wl; ha.dbl = ap.hv + e->off_bl; ha.gstride = e->PS;
-      ha.df = ap.rdf;
-      ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
-      head_scratch(e, ha, ap.hscr, T, n);
       HEAD_LDS(e, "head tangent", n, ha.ways, 1);
       LAUNCH(e, st, OP_HEAD_TAN, 0, launch_head_tangent(st, ha, T));
       LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, ap.dfs, ap.rdf, inner_lr, fsz, ap.dfs));   // dfs -= lr * R{df}
@@ -1523,7 +1376,11 @@ static int meta_batch_entry(MetaBatchFn fn, int which, mi_engine* e, void* strea
       (unsigned long long)shots, (unsigned long long)adapt_steps, (unsigned long long)lr_bits, (unsigned long long)second_order,
       (unsigned long long)with_grad, (unsigned long long)(uintptr_t)loss_out, (unsigned long long)(uintptr_t)acc_out,
       (unsigned long long)(uintptr_t)meta_grad_out, (unsigned long long)(uintptr_t)logits_out, (unsigned long long)(uintptr_t)workspace,
-      (unsigned long long)workspace_bytes, (unsigned long long)e->fuse1 + 2ull * e->gram1 + (1ull << 40) * e->gramq + 4ull * e->overlap + 8ull * e->fuse_fin + 16ull * e->fuse_b1red + 32ull * e->fuse_tail + 64ull * e->fork_once + 128ull * e->fuse_last + 256ull * kernel_selection_key()};
+      (unsigned long long)workspace_bytes,
+      // every engine switch and the kernel selection in an element of its own: nothing packed, nothing that can alias
+      (unsigned long long)e->fuse1, (unsigned long long)e->gram1, (unsigned long long)e->gramq, (unsigned long long)e->overlap,
+      (unsigned long long)e->fuse_fin, (unsigned long long)e->fuse_b1red, (unsigned long long)e->fuse_tail, (unsigned long long)e->fuse_last,
+      kernel_selection_key()};
   mi_engine::GraphEntry* ent = nullptr;
   for (auto& g : e->graphs)
     if (g.key == key) { ent = &g; break; }
@@ -1635,6 +1492,22 @@ static int learner_args(mi_engine* e, const float* theta, int theta_tasks, const
   return MI_OK;
 }
 
+// Forward over x with the gathered weights pl.theta, then the backward of s = sum(logits * dlogits) with the caller's cotangent: ds/dtheta
+// into g (engine layout, per task), the layer cotangents into A.
+static int learner_fwd_bwd(mi_engine* e, hipStream_t st, Plan& pl, ActSet& A, const float* x, const float* dlogits, int n, int tasks, float* g) {
+  const int nl = (int)e->L.size();
+  int rc = trunk_forward(e, st, pl, A, x, n, tasks, pl.theta);
+  if (rc) return rc;
+  if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean(st, A.p[nl - 1], A.f, tasks * n, e->head_hw, e->head_c));
+  HIPCHK(e, hipMemsetAsync(g, 0, (size_t)tasks * e->PS * sizeof(float), st));
+  HeadArgs ha = head_args(e, nullptr, A.f, pl.theta, nullptr, g, A.df, n, tasks);
+  ha.dl = const_cast<float*>(dlogits);
+  HEAD_LDS(e, "head backward", n, ha.ways, 0);
+  LAUNCH(e, st, OP_HEAD, 0, launch_head_grads(st, ha, tasks));
+  if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean_bwd(st, A.df, A.dp[nl - 1], tasks * n, e->head_hw, e->head_c));
+  return trunk_backward(e, st, pl, A, x, n, tasks, pl.theta, g);
+}
+
 extern "C" int mi_learner_forward(mi_engine* e, void* stream, const float* theta, int theta_tasks, const float* x, int tasks,
                                   int n, float* logits_out, int rep_layer, float* rep_out, void* workspace,
                                   size_t workspace_bytes) {
@@ -1669,27 +1542,11 @@ extern "C" int mi_learner_backward(mi_engine* e, void* stream, const float* thet
   ExportPause no_export(e);
   if (!dlogits || !grad_out) return fail(e, MI_ERR_ARG, "null dlogits / grad_out");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nl = (int)e->L.size();
-  ActSet& A = pl.qry;
   rc = plan_begin(e, st, pl);
   if (rc) return rc;
   LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, x, (size_t)tasks * n, e->d.in_channels, e->d.in_h, e->d.in_w, pl.xq));
   LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, theta, theta_tasks == 1 ? 0 : e->P, e->perm_dev, (int)e->P, (int)e->PS, tasks, pl.theta));
-  rc = trunk_forward(e, st, pl, A, pl.xq, n, tasks, pl.theta);
-  if (rc) return rc;
-  if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean(st, A.p[nl - 1], A.f, tasks * n, e->head_hw, e->head_c));
-  HIPCHK(e, hipMemsetAsync(pl.lam, 0, (size_t)tasks * e->PS * sizeof(float), st));
-  HeadArgs ha{};
-  ha.f = A.f;
-  ha.wl = pl.theta + e->off_wl; ha.bl = pl.theta + e->off_bl; ha.pstride = e->PS;
-  ha.dl = const_cast<float*>(dlogits);
-  ha.dwl = pl.lam + e->off_wl; ha.dbl = pl.lam + e->off_bl; ha.gstride = e->PS;
-  ha.df = A.df;
-  ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
-  HEAD_LDS(e, "head backward", n, ha.ways, 0);
-  LAUNCH(e, st, OP_HEAD, 0, launch_head_grads(st, ha, tasks));
-  if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean_bwd(st, A.df, A.dp[nl - 1], tasks * n, e->head_hw, e->head_c));
-  rc = trunk_backward(e, st, pl, A, pl.xq, n, tasks, pl.theta, pl.lam);
+  rc = learner_fwd_bwd(e, st, pl, pl.qry, pl.xq, dlogits, n, tasks, pl.lam);
   if (rc) return rc;
   if (theta_tasks == 1) {
     LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, pl.lam, e->perm_dev, (int)e->P, (int)e->PS, tasks, grad_out));
@@ -1726,29 +1583,14 @@ extern "C" int mi_learner_hvp(mi_engine* e, void* stream, const float* theta, in
   if (pl.bytes > workspace_bytes)
     return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes) + " bytes");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nl = (int)e->L.size();
   const size_t pstride = theta_tasks == 1 ? 0 : e->P;
   { const int brc = plan_begin(e, st, pl); if (brc) return brc; }
   ActSet& A = pl.sup[0];
   LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, x, (size_t)tasks * n, e->d.in_channels, e->d.in_h, e->d.in_w, pl.xs));
   LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, theta, pstride, e->perm_dev, (int)e->P, (int)e->PS, tasks, pl.theta));
   LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, v, pstride, e->perm_dev, (int)e->P, (int)e->PS, tasks, pl.lam));
-  int rc = trunk_forward(e, st, pl, A, pl.xs, n, tasks, pl.theta);
-  if (rc) return rc;
-  if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean(st, A.p[nl - 1], A.f, tasks * n, e->head_hw, e->head_c));
   // primal backward with the given cotangent: the tangent sweep needs its BatchNorm sums (g) and layer cotangents (A.dp)
-  HIPCHK(e, hipMemsetAsync(pl.g, 0, (size_t)tasks * e->PS * sizeof(float), st));
-  HeadArgs ha{};
-  ha.f = A.f;
-  ha.wl = pl.theta + e->off_wl; ha.bl = pl.theta + e->off_bl; ha.pstride = e->PS;
-  ha.dl = const_cast<float*>(dlogits);
-  ha.dwl = pl.g + e->off_wl; ha.dbl = pl.g + e->off_bl; ha.gstride = e->PS;
-  ha.df = A.df;
-  ha.n = n; ha.feat = e->feat; ha.ways = e->d.ways;
-  HEAD_LDS(e, "head backward", n, ha.ways, 0);
-  LAUNCH(e, st, OP_HEAD, 0, launch_head_grads(st, ha, tasks));
-  if (e->d.head_mean_pool) HIPCHK(e, launch_spatial_mean_bwd(st, A.df, A.dp[nl - 1], tasks * n, e->head_hw, e->head_c));
-  rc = trunk_backward(e, st, pl, A, pl.xs, n, tasks, pl.theta, pl.g);
+  int rc = learner_fwd_bwd(e, st, pl, A, pl.xs, dlogits, n, tasks, pl.g);
   if (rc) return rc;
   rc = pass_hvp(e, st, pl, A, pl.xs, n, tasks, pl.theta, pl.g, pl.lam, pl.hv, nullptr, dlogits, logits_dot_out);
   if (rc) return rc;
