@@ -172,7 +172,6 @@ _SIGS = {
     'mi_policy_destroy': (None, [C.c_void_p]),
     'mi_policy_last_error': (C.c_char_p, [C.c_void_p]),
     'mi_policy_param_count': (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
-    'mi_trpo_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     'mi_policy_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_size_t]),
     'mi_particles_rollout_scratch_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -180,10 +179,6 @@ _SIGS = {
                                        C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_size_t]),
     'mi_policy_adapt': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
-    'mi_trpo_surrogate': (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                         C.c_void_p, C.c_size_t]),
-    'mi_trpo_fvp': (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   C.c_size_t]),
     'mi_policy_set_fused_fvp': (C.c_int, [C.c_int]),
     'mi_debug_policy_sweep_stamps': (C.c_int, [C.c_void_p]),
     'mi_policy_learner_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
@@ -199,10 +194,6 @@ _SIGS = {
     'mi_conv_set_b16': (C.c_int, [C.c_int]),
     'mi_block1_set_split_bf16': (C.c_int, [C.c_int]),
     'mi_sparse_wgrad_set_split_bf16': (C.c_int, [C.c_int]),
-    'mi_trpo_general_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    'mi_trpo_kl_prepare': (C.c_int, [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]),
-    'mi_trpo_fvp_general': (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                           C.c_size_t]),
     'mi_policy_meta_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     'mi_policy_meta_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 +
                              [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -590,8 +590,10 @@ class _SurrogateContext:
             part = lambda k: dict(states=batch['states'][k * nT:(k + 1) * nT], actions=batch['actions'][k * nT:(k + 1) * nT],
                                   adv=advs[k * nT:(k + 1) * nT], count=batch['count'][k * nT:(k + 1) * nT],
                                   done=batch['dones'][k * nT:(k + 1) * nT])
-            sups = [part(k) for k in range(K)]
             self.qry = part(K)
+            # the K support replays are the batch's first K x tasks rows: [K, T, ...] views, no copy
+            rows = dict(states=batch['states'], actions=batch['actions'], adv=advs, count=batch['count'])
+            self.sup = {k: v[:K * nT].unflatten(0, (K, nT)) for k, v in rows.items()}
         else:
             host = _host_replays(flat)                               # one D2H copy per field
             sups = []
@@ -600,19 +602,17 @@ class _SurrogateContext:
                 sups.append(_pad(eps, [adv(e) for e in eps], S, A, dev))
             qry_eps = host[K * nT:]
             self.qry = _pad(qry_eps, [adv(e) for e in qry_eps], S, A, dev)
-        B = max([d['states'].shape[1] for d in sups] + [self.qry['states'].shape[1]])
-        for d in sups + [self.qry]:                              # one common padded length
-            if d['states'].shape[1] < B:
+            B = max(d['states'].shape[1] for d in sups + [self.qry])
+            for d in sups + [self.qry]:                          # one common padded length
                 pad = B - d['states'].shape[1]
-                d['states'] = torch.nn.functional.pad(d['states'], (0, 0, 0, pad))
-                d['actions'] = torch.nn.functional.pad(d['actions'], (0, 0, 0, pad))
-                d['adv'] = torch.nn.functional.pad(d['adv'], (0, pad))
-            for k in ('states', 'actions', 'adv'):
+                if pad:
+                    d['states'] = torch.nn.functional.pad(d['states'], (0, 0, 0, pad))
+                    d['actions'] = torch.nn.functional.pad(d['actions'], (0, 0, 0, pad))
+                    d['adv'] = torch.nn.functional.pad(d['adv'], (0, pad))
+            self.sup = {k: torch.stack([d[k] for d in sups]) for k in ('states', 'actions', 'adv', 'count')}       # [K, T, ...]
+        for d in (self.sup, self.qry):
+            for k in ('states', 'actions', 'adv', 'count'):
                 d[k] = d[k].contiguous()
-        if K == 1:
-            self.sup = sups[0]
-        else:
-            self.sup = {k: torch.stack([d[k] for d in sups]).contiguous() for k in ('states', 'actions', 'adv', 'count')}
         self.engine = policy.engine()
         # the stored old policies' parameters as ONE gather ([tasks, P], engine order: sigma first) and their scales from its first columns
         # (per-policy flat() / clamp / exp launches were ~80 of the ~100 launches of this constructor)
@@ -643,8 +643,7 @@ class _SurrogateContext:
         return tuple(out)
 
     def evaluate(self, theta, want_grad=False):
-        fn = self.engine.surrogate if self.steps == 1 else self.engine.surrogate_steps
-        loss, kl, grad = fn(theta, self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad)
+        loss, kl, grad = self.engine.surrogate(theta, self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad)
         if grad is None:
             loss, kl = self._allmean(loss, kl)
         else:
@@ -653,24 +652,18 @@ class _SurrogateContext:
 
     def prepare_general_kl(self, theta, want_grad=False):
         """ANIL-TRPO: the re-adapted policies differ from the stored old ones, the Fisher form does not apply; set up the exact
-        KL Hessian-vector product (mi_trpo_kl_prepare, mi_trpo_kl_prepare_steps for adapt_steps > 1) at the theta of the
-        preceding ``evaluate``.  Returns d mean KL / d theta if ``want_grad``."""
-        if self.steps == 1:
-            grad = self.engine.kl_prepare(theta, self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad)
-        else:
-            grad = self.engine.kl_prepare_steps(self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad)
+        KL Hessian-vector product (``PolicyEngine.kl_prepare``) at the theta of the preceding ``evaluate``.  ``theta`` is not
+        read: the engine kept it.  Returns d mean KL / d theta if ``want_grad``."""
+        grad = self.engine.kl_prepare(self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad)
         self.general = True
         return None if grad is None else self._allmean(grad)[0]
 
     def fvp(self, theta, v, damping=1e-5):
+        """The curvature product at the theta of the preceding ``evaluate`` (``theta`` is not read: the engine kept it)."""
         # the damping term is linear in v, so averaging the per-rank results keeps it exact
         if getattr(self, 'general', False):
-            if self.steps == 1:
-                return self._allmean(self.engine.fvp_general(theta, self.sup, self.qry, self.old_scale, self.inner_lr, damping, v))[0]
-            return self._allmean(self.engine.fvp_general_steps(self.sup, self.qry, self.old_scale, self.inner_lr, damping, v))[0]
-        if self.steps == 1:
-            return self._allmean(self.engine.fvp(theta, self.sup, self.qry, self.inner_lr, damping, v))[0]
-        return self._allmean(self.engine.fvp_steps(self.sup, self.qry, self.inner_lr, damping, v))[0]
+            return self._allmean(self.engine.fvp_general(self.sup, self.qry, self.old_scale, self.inner_lr, damping, v))[0]
+        return self._allmean(self.engine.fvp(self.sup, self.qry, self.inner_lr, damping, v))[0]
 
 
 def meta_surrogate_loss(iter_replays, iter_policies, policy, baseline, params, anil=False):
@@ -741,7 +734,7 @@ def meta_optimize_trpo(params, policy, baseline, iter_replays, iter_policies, an
         # The reference's surrogate replays the inner step with ALL parameters (clone_module(policy) has its body grads on,
         # rl.py:447-453) while the stored old policies were adapted head-only (rl.py:381-382): at the current parameters the new
         # policies differ from the old ones, KL's gradient is not zero, and trpo.hessian_vector_product(kl) is the exact Hessian
-        # of the mean KL including the third derivative of the inner loss (mi_trpo_fvp_general).
+        # of the mean KL including the third derivative of the inner loss (``PolicyEngine.fvp_general``).
         ctx.prepare_general_kl(theta)
     Fvp = lambda v: ctx.fvp(theta, v)
     step = conjugate_gradient(Fvp, grad)

@@ -12,9 +12,9 @@
 // replay.   grad_theta mean_t S_t = mean_t (I - lr H_t) grad S_t(theta'_t)          (H_t v: tangent sweep over the support pass)
 // At theta_old the adapted policy equals the stored old policy, KL's gradient is exactly zero, so
 //   Fvp(v) = mean_t (I - lr H_t) F_t (I - lr H_t) v + damping v,   F_t = J^T diag(1/(B D sigma^2), 2/D) J  (Gaussian Fisher).
-// The curvature product, by case:                      adapt_steps == 1                         adapt_steps > 1
-//   MAML-TRPO (new == old, Fisher form exact)          mi_trpo_surrogate / mi_trpo_fvp          mi_trpo_surrogate_steps / mi_trpo_fvp_steps
-//   ANIL-TRPO (new != old, exact Hessian of mean KL)   mi_trpo_kl_prepare / mi_trpo_fvp_general mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps
+// One set of entry points for any number K of inner updates (K = 1 of a supported ReLU policy takes the fused sweeps):
+//   MAML-TRPO (new == old, Fisher form exact)          mi_trpo_surrogate_steps / mi_trpo_fvp_steps
+//   ANIL-TRPO (new != old, exact Hessian of mean KL)   ... then mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps
 #include <string>
 #include <vector>
 #include <cmath>
@@ -495,53 +495,6 @@ static hipError_t gauss(hipStream_t st, int T, GaussArgs& a) {
   return hipGetLastError();
 }
 
-// ---- workspace of a TRPO context: everything mi_trpo_fvp re-uses after mi_trpo_surrogate
-struct TrpoPlan {
-  Acts sa, qa, ta;                      // support acts at theta, query acts at theta', tangent acts (scratch)
-  float *s_dmu, *s_d2, *s_d1, *s_coef;  // support primal cotangents
-  float *s_pre2, *s_pre1;               // ... before the phi' factor (tanh HVP)
-  float *q_dmu, *q_d2, *q_d1, *q_coef;
-  float *rdmu, *r2, *r1;                // tangent scratch
-  float *g, *thetap, *q, *hv, *u, *w, *tmpP;   // [T][P]
-  float *loss_t, *kl_t;
-  float* partial;                       // fused sweeps (policy_sweep.h): [T][slots][P] per-workgroup gradient partials
-  int spt, spw, slots, sweep_grid;
-  size_t bytes;
-};
-// geometry of the fused sweeps: slabs of 32 rows, a contiguous run of slabs per workgroup, one round of workgroups on 256 CUs
-static void sweep_geometry(int T, int B, int& spt, int& spw, int& slots, int& grid) {
-  spt = ceil_div(B, 32);
-  const int total = T * (spt + 1);      // virtual slabs: a marker in front of every task's slabs (policy_sweep.hip: what entering a task costs)
-  spw = ceil_div(total, 256);
-  grid = ceil_div(total, spw);
-  slots = ceil_div(spt + 1, spw) + 1;
-}
-static bool sweep_supported(const mi_policy* p) {
-  return policy_sweep_supported(p->act == ACT_RELU, p->H1, p->H2, p->S, p->A);
-}
-static void trpo_plan(const mi_policy* p, void* ws, int T, int B, TrpoPlan& pl) {
-  PBump b{reinterpret_cast<char*>(ws), 0};
-  const size_t TB = (size_t)T * B, TP = (size_t)T * p->P;
-  auto acts = [&](Acts& a) { a.h1 = b.f(TB * p->H1); a.h2 = b.f(TB * p->H2); a.mu = b.f(TB * p->A); };
-  acts(pl.sa); acts(pl.qa); acts(pl.ta);
-  pl.s_dmu = b.f(TB * p->A); pl.s_d2 = b.f(TB * p->H2); pl.s_d1 = b.f(TB * p->H1); pl.s_coef = b.f(TB);
-  pl.s_pre2 = b.f(TB * p->H2); pl.s_pre1 = b.f(TB * p->H1);
-  pl.q_dmu = b.f(TB * p->A); pl.q_d2 = b.f(TB * p->H2); pl.q_d1 = b.f(TB * p->H1); pl.q_coef = b.f(TB);
-  pl.rdmu = b.f(TB * p->A); pl.r2 = b.f(TB * p->H2); pl.r1 = b.f(TB * p->H1);
-  pl.g = b.f(TP); pl.thetap = b.f(TP); pl.q = b.f(TP); pl.hv = b.f(TP); pl.u = b.f(TP); pl.w = b.f(TP); pl.tmpP = b.f(TP);
-  pl.loss_t = b.f(T); pl.kl_t = b.f(T);
-  sweep_geometry(T, B, pl.spt, pl.spw, pl.slots, pl.sweep_grid);
-  pl.partial = sweep_supported(p) ? b.f((size_t)T * pl.slots * (p->P + 2)) : nullptr;
-  pl.bytes = align_up(b.off, 256);
-}
-extern "C" int mi_trpo_workspace_bytes(const mi_policy* p, int tasks, int batch, size_t* bytes) {
-  if (!p || !bytes || tasks < 1 || batch < 1) return MI_ERR_ARG;
-  TrpoPlan pl;
-  trpo_plan(p, nullptr, tasks, batch, pl);
-  *bytes = pl.bytes;
-  return MI_OK;
-}
-
 // loc = MLP(state) for acting / densities (policies.py:49-52); theta [P] shared (tstride 0) or per task (tstride = P).
 extern "C" int mi_policy_forward(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states, int tasks,
                                  int batch, float* loc_out, void* workspace, size_t workspace_bytes) {
@@ -560,151 +513,6 @@ extern "C" int mi_debug_policy_sweep_stamps(void* buf) { g_sweep_stamps = reinte
 // 0: the per-layer path (ablation / tests).
 extern "C" int mi_policy_set_fused_fvp(int on) { g_policy_fused_fvp = on ? 1 : 0; return MI_OK; }
 
-static SweepArgs sweep_base(const mi_policy* p, const TrpoPlan& pl, int T, int B) {
-  SweepArgs a{};
-  a.T = T; a.B = B; a.S = p->S; a.A = p->A; a.spt = pl.spt; a.spw = pl.spw; a.slots = pl.slots; a.partial = pl.partial;
-  a.pitch = (int)p->P + 2;
-  a.o_sigma = (int)p->o_sigma; a.o_w1 = (int)p->o_w1; a.o_b1 = (int)p->o_b1; a.o_w2 = (int)p->o_w2; a.o_b2 = (int)p->o_b2;
-  a.o_w3 = (int)p->o_w3; a.o_b3 = (int)p->o_b3; a.P = (int)p->P;
-  a.stamps = g_sweep_stamps;
-  return a;
-}
-
-// inner-loss HVP on the cached support pass: hv = H_t v for every task (v, hv: [T][P])
-static int support_hvp(mi_policy* p, hipStream_t st, TrpoPlan& pl, int T, int B, const float* theta, const float* s_states,
-                       const float* s_actions, const int32_t* s_count, const float* v, float* hv) {
-  PCHK(p, hipMemsetAsync(hv, 0, (size_t)T * p->P * sizeof(float), st));
-  int rc = mlp_tangent_forward(p, st, T, B, s_states, theta, 0, pl.sa, v, pl.ta);
-  if (rc) return rc;
-  GaussArgs ga{};
-  ga.mu = pl.sa.mu; ga.mud = pl.ta.mu; ga.rho = theta + p->o_sigma; ga.rstride = 0; ga.rhod = v + p->o_sigma; ga.vstride = p->P;
-  ga.act = s_actions; ga.count = s_count; ga.coef = pl.s_coef; ga.dmu = pl.rdmu; ga.drho = hv + p->o_sigma; ga.gstride = p->P;
-  ga.B = B; ga.A = p->A; ga.mode = G_TANGENT;
-  PCHK(p, gauss(st, T, ga));
-  return mlp_tangent_backward(p, st, T, B, s_states, theta, 0, pl.sa, pl.ta, v, pl.s_dmu, pl.s_d2, pl.s_d1, pl.s_pre2, pl.s_pre1, pl.rdmu,
-                              pl.r2, pl.r1, hv);
-}
-
-// trpo_update (rl.py:361-374) for a meta-batch: theta_out[t] = theta[t] - lr * grad_t(-mean(logp * adv)).  loss_out [T].
-extern "C" int mi_policy_adapt(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
-                               const float* actions, const float* adv, const int32_t* count, int tasks, int batch, float lr,
-                               int head_only, float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
-  if (!p || !theta || !states || !actions || !adv || !theta_out || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  TrpoPlan pl;
-  trpo_plan(p, workspace, tasks, batch, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes));
-  int rc = mlp_forward(p, st, tasks, batch, states, theta, tstride, pl.sa);
-  if (rc) return rc;
-  PCHK(p, hipMemsetAsync(pl.g, 0, (size_t)tasks * p->P * sizeof(float), st));
-  GaussArgs ga{};
-  ga.mu = pl.sa.mu; ga.rho = theta + p->o_sigma; ga.rstride = tstride; ga.act = actions; ga.adv = adv; ga.count = count;
-  ga.coef = pl.s_coef; ga.dmu = pl.s_dmu; ga.drho = pl.g + p->o_sigma; ga.gstride = p->P; ga.loss = loss_out ? loss_out : pl.loss_t;
-  ga.B = batch; ga.A = p->A; ga.mode = G_A2C;
-  PCHK(p, gauss(st, tasks, ga));
-  rc = mlp_backward(p, st, tasks, batch, states, theta, tstride, pl.sa, pl.s_dmu, pl.s_d2, pl.s_d1, pl.g, nullptr, nullptr, head_only != 0);
-  if (rc) return rc;
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)p->P, 256), tasks), dim3(256), 0, st, theta, tstride, pl.g, lr,
-                     (int)p->P, theta_out);
-  PCHK(p, hipGetLastError());
-  return MI_OK;
-}
-
-// meta_surrogate_loss (rl.py:441-473) at theta for `tasks` tasks with ONE second-order inner step on the support replay, and
-// optionally its gradient (rl.py:413-416).  Leaves everything mi_trpo_fvp needs in `workspace`.
-extern "C" int mi_trpo_surrogate(mi_policy* p, void* stream, const float* theta, const float* s_states, const float* s_actions,
-                                 const float* s_adv, const int32_t* s_count, const float* q_states, const float* q_actions,
-                                 const float* q_adv, const int32_t* q_count, const float* old_loc, const float* old_scale,
-                                 int tasks, int batch, float inner_lr, float* loss_out, float* kl_out, float* grad_out,
-                                 void* workspace, size_t workspace_bytes) {
-  if (!p || !theta || !s_states || !s_actions || !s_adv || !q_states || !q_actions || !q_adv || !old_loc || !old_scale ||
-      !loss_out || !kl_out || !workspace)
-    return pfail(p, MI_ERR_ARG, "null argument");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, B = batch;
-  const size_t P = p->P;
-  TrpoPlan pl;
-  trpo_plan(p, workspace, T, B, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes));
-  int rc = MI_OK;
-  const bool fused = g_policy_fused_fvp && sweep_supported(p) && pl.partial;
-  if (fused) {
-    // inner step and query pass as two PRIMAL sweeps (forward + loss + backward of a pass in one launch, leaving the activations and
-    // cotangents the Hessian-vector / Fisher sweeps read) instead of ~22 per-layer launches
-    SweepArgs sp = sweep_base(p, pl, T, B);
-    sp.x = s_states; sp.act = s_actions; sp.adv = s_adv; sp.count = s_count; sp.theta = theta; sp.tstride = 0; sp.surrogate = 0;
-    sp.h1_out = pl.sa.h1; sp.h2_out = pl.sa.h2; sp.mu_out = pl.sa.mu; sp.dmu_out = pl.s_dmu; sp.d2_out = pl.s_d2; sp.coef_out = pl.s_coef;
-    PCHK(p, launch_policy_sweep(st, sp, pl.sweep_grid, SW_PRIMAL));
-    FoldArgs f{};
-    f.partial = pl.partial; f.slots = pl.slots; f.spt = pl.spt; f.spw = pl.spw; f.T = T; f.P = (int)P; f.pitch = (int)P + 2; f.lr = inner_lr;
-    f.o_sigma = (int)p->o_sigma; f.A = p->A;
-    f.mode = 0; f.v = theta; f.out = pl.thetap;                     // theta'_t = theta - lr g_t
-    PCHK(p, launch_policy_sweep_fold(st, f, T));
-    SweepArgs sq = sweep_base(p, pl, T, B);
-    sq.x = q_states; sq.act = q_actions; sq.adv = q_adv; sq.count = q_count; sq.theta = pl.thetap; sq.tstride = P; sq.surrogate = 1;
-    sq.old_loc = old_loc; sq.old_scale = old_scale; sq.fwd_only = grad_out ? 0 : 1;
-    sq.h1_out = pl.qa.h1; sq.h2_out = pl.qa.h2; sq.mu_out = pl.qa.mu;
-    PCHK(p, launch_policy_sweep(st, sq, pl.sweep_grid, SW_PRIMAL));
-    f.mode = 3; f.out = grad_out ? pl.q : nullptr; f.loss_t = pl.loss_t; f.kl_t = pl.kl_t;      // q_t = grad S_t(theta'_t); per-task loss / KL
-    PCHK(p, launch_policy_sweep_fold(st, f, T));
-    hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, pl.loss_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, loss_out);
-    hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, pl.kl_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, kl_out);
-    PCHK(p, hipGetLastError());
-    if (!grad_out) return MI_OK;
-  } else {
-    // inner step on support at theta (shared)
-    rc = mlp_forward(p, st, T, B, s_states, theta, 0, pl.sa);
-    if (rc) return rc;
-    PCHK(p, hipMemsetAsync(pl.g, 0, (size_t)T * P * sizeof(float), st));
-    GaussArgs ga{};
-    ga.mu = pl.sa.mu; ga.rho = theta + p->o_sigma; ga.rstride = 0; ga.act = s_actions; ga.adv = s_adv; ga.count = s_count;
-    ga.coef = pl.s_coef; ga.dmu = pl.s_dmu; ga.drho = pl.g + p->o_sigma; ga.gstride = P; ga.loss = pl.loss_t;
-    ga.B = B; ga.A = p->A; ga.mode = G_A2C;
-    PCHK(p, gauss(st, T, ga));
-    rc = mlp_backward(p, st, T, B, s_states, theta, 0, pl.sa, pl.s_dmu, pl.s_d2, pl.s_d1, pl.g, pl.s_pre2, pl.s_pre1);
-    if (rc) return rc;
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, theta, (size_t)0, pl.g, inner_lr, (int)P,
-                       pl.thetap);
-    PCHK(p, hipGetLastError());
-    // query at theta'
-    rc = mlp_forward(p, st, T, B, q_states, pl.thetap, P, pl.qa);
-    if (rc) return rc;
-    PCHK(p, hipMemsetAsync(pl.q, 0, (size_t)T * P * sizeof(float), st));
-    GaussArgs gq{};
-    gq.mu = pl.qa.mu; gq.rho = pl.thetap + p->o_sigma; gq.rstride = P; gq.act = q_actions; gq.adv = q_adv; gq.count = q_count;
-    gq.old_loc = old_loc; gq.old_scale = old_scale; gq.coef = pl.q_coef; gq.dmu = pl.q_dmu; gq.drho = pl.q + p->o_sigma;
-    gq.gstride = P; gq.loss = pl.loss_t; gq.kl = pl.kl_t; gq.B = B; gq.A = p->A; gq.mode = G_SURROGATE;
-    PCHK(p, gauss(st, T, gq));
-    hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, pl.loss_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, loss_out);
-    hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, pl.kl_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, kl_out);
-    PCHK(p, hipGetLastError());
-    if (!grad_out) return MI_OK;
-    rc = mlp_backward(p, st, T, B, q_states, pl.thetap, P, pl.qa, pl.q_dmu, pl.q_d2, pl.q_d1, pl.q);   // q_t = grad S_t(theta'_t)
-    if (rc) return rc;
-  }
-  if (g_policy_fused_fvp && sweep_supported(p) && pl.partial) {
-    // (I - lr H_t) q_t as ONE fused sweep over the support pass (direction q_t per task) + fold, instead of ~10 per-layer launches
-    SweepArgs hs = sweep_base(p, pl, T, B);
-    hs.x = s_states; hs.act = s_actions; hs.h1 = pl.sa.h1; hs.h2 = pl.sa.h2; hs.mu = pl.sa.mu; hs.coef = pl.s_coef; hs.dmu = pl.s_dmu;
-    hs.d2 = pl.s_d2; hs.count = s_count; hs.theta = theta; hs.tstride = 0; hs.dir = pl.q; hs.dstride = P;
-    PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
-    FoldArgs f{};
-    f.partial = pl.partial; f.slots = pl.slots; f.spt = pl.spt; f.spw = pl.spw; f.T = T; f.P = (int)P; f.pitch = (int)P + 2; f.lr = inner_lr;
-    f.o_sigma = (int)p->o_sigma; f.A = p->A; f.mode = 2; f.out = pl.tmpP; f.w = pl.q;
-    PCHK(p, launch_policy_sweep_fold(st, f, T));
-  } else {
-    rc = support_hvp(p, st, pl, T, B, theta, s_states, s_actions, s_count, pl.q, pl.hv);
-    if (rc) return rc;
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.q, P, pl.hv, inner_lr, (int)P, pl.tmpP);
-  }
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.tmpP, T, (int)P, 1.f / (float)T,
-                     (const float*)nullptr, 0.f, grad_out);
-  PCHK(p, hipGetLastError());
-  return MI_OK;
-}
-
-// Fvp(v) = mean_t (I - lr H_t) F_t (I - lr H_t) v + damping v   (cherry trpo.hessian_vector_product of the mean KL at the point
-// where the adapted policy equals the old policy, rl.py:417).  Must follow mi_trpo_surrogate on the same workspace/arguments.
 // One recurrence of cherry.algorithms.trpo.conjugate_gradient (reference rl.py:418) on device vectors, in fp64, as ONE launch:
 //   alpha = rr_old / (p . Ap + eps);  x += alpha p;  r -= alpha Ap;  rr_new = r . r;  p = r + (rr_new / rr_old) p
 // (a dozen ATen launches and two rocBLAS dots per iteration otherwise: ~0.1 ms of each ~1 ms iteration).  One workgroup: the vectors
@@ -818,91 +626,6 @@ extern "C" int mi_cg_update_checked(void* stream, double* x, double* r, double* 
   if (!x || !r || !p || !ap || !rr || !p32 || n == 0 || tol < 0.0) return MI_ERR_ARG;
   hipLaunchKernelGGL(cg_update_kernel, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), x, r, p, ap, rr, p32, n, eps, tol);
   return hipGetLastError() == hipSuccess ? MI_OK : MI_ERR_HIP;
-}
-
-static int fused_fvp(mi_policy* p, hipStream_t st, TrpoPlan& pl, int T, int B, const float* theta, const float* s_states,
-                     const float* s_actions, const int32_t* s_count, const float* q_states, const int32_t* q_count, float inner_lr,
-                     float damping, const float* v, float* out) {
-  const int P = (int)p->P;
-  SweepArgs hs = sweep_base(p, pl, T, B);              // H_t over the support pass at theta
-  hs.x = s_states; hs.act = s_actions; hs.h1 = pl.sa.h1; hs.h2 = pl.sa.h2; hs.mu = pl.sa.mu; hs.coef = pl.s_coef; hs.dmu = pl.s_dmu;
-  hs.d2 = pl.s_d2; hs.count = s_count; hs.theta = theta; hs.tstride = 0;
-  FoldArgs f{};
-  f.partial = pl.partial; f.slots = pl.slots; f.spt = pl.spt; f.spw = pl.spw; f.T = T; f.P = P; f.pitch = P + 2; f.v = v; f.lr = inner_lr;
-  f.damping = damping; f.o_sigma = (int)p->o_sigma; f.A = p->A;
-  // A: u_t = v - lr H_t v
-  hs.dir = v; hs.dstride = 0;
-  PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
-  f.mode = 0; f.out = pl.u;
-  PCHK(p, launch_policy_sweep_fold(st, f, T));
-  // B: w_t = F_t u_t over the query pass at theta'_t
-  SweepArgs fs = sweep_base(p, pl, T, B);
-  fs.x = q_states; fs.h1 = pl.qa.h1; fs.h2 = pl.qa.h2; fs.count = q_count; fs.theta = pl.thetap; fs.tstride = P; fs.dir = pl.u; fs.dstride = P;
-  PCHK(p, launch_policy_sweep(st, fs, pl.sweep_grid, SW_FISHER));
-  f.mode = 1; f.out = pl.w; f.thetap = pl.thetap; f.u = pl.u;
-  PCHK(p, launch_policy_sweep_fold(st, f, T));
-  // C: out = mean_t (w_t - lr H_t w_t) + damping v
-  hs.dir = pl.w; hs.dstride = P;
-  PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
-  f.mode = 2; f.out = pl.tmpP; f.w = pl.w;
-  if (!p->fold_counters) {               // (once per policy object: the fold leaves the counters zero again)
-    const size_t nb = (size_t)ceil_div(P, 256) * sizeof(unsigned);
-    if (hipMalloc(reinterpret_cast<void**>(&p->fold_counters), nb) != hipSuccess) { p->fold_counters = nullptr; (void)hipGetLastError(); }
-    else PCHK(p, hipMemsetAsync(p->fold_counters, 0, nb, st));
-  }
-  if (p->fold_counters) {                // the mean over tasks + damping v by the last workgroup of every parameter block: no launch of its own
-    // The protocol needs the counters at zero when the fold starts; its last workgroup leaves them at zero.  A fold whose launch was
-    // refused leaves the flag set, and the next product re-zeroes (stream-ordered, 4 * ceil(P / 256) bytes) instead of waiting for a
-    // "last" workgroup that can no longer exist.  One stream per mi_policy at a time (include/mi_maml.h).
-    if (p->fold_dirty) PCHK(p, hipMemsetAsync(p->fold_counters, 0, (size_t)ceil_div(P, 256) * sizeof(unsigned), st));
-    p->fold_dirty = true;
-    f.counter = p->fold_counters; f.mean_out = out; f.inv_T = 1.f / (float)T;
-    PCHK(p, launch_policy_sweep_fold(st, f, T));
-    p->fold_dirty = false;
-    return MI_OK;
-  }
-  PCHK(p, launch_policy_sweep_fold(st, f, T));
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, pl.tmpP, T, P, 1.f / (float)T, v, damping, out);
-  PCHK(p, hipGetLastError());
-  return MI_OK;
-}
-
-extern "C" int mi_trpo_fvp(mi_policy* p, void* stream, const float* theta, const float* s_states, const float* s_actions,
-                           const int32_t* s_count, const float* q_states, const int32_t* q_count, int tasks, int batch,
-                           float inner_lr, float damping, const float* v, float* out, void* workspace, size_t workspace_bytes) {
-  if (!p || !theta || !v || !out || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, B = batch;
-  const size_t P = p->P;
-  TrpoPlan pl;
-  trpo_plan(p, workspace, T, B, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small");
-  if (g_policy_fused_fvp && sweep_supported(p) && pl.partial)
-    return fused_fvp(p, st, pl, T, B, theta, s_states, s_actions, s_count, q_states, q_count, inner_lr, damping, v, out);
-  // u_t = v - lr H_t v   (v broadcast to every task)
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (size_t)0, pl.tmpP, 0.f, (int)P, pl.u);
-  PCHK(p, hipGetLastError());
-  int rc = support_hvp(p, st, pl, T, B, theta, s_states, s_actions, s_count, pl.u, pl.hv);
-  if (rc) return rc;
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.u, P, pl.hv, inner_lr, (int)P, pl.u);
-  PCHK(p, hipGetLastError());
-  // w_t = F_t u_t : JVP on the query pass at theta', Gaussian Fisher cotangent, VJP
-  rc = mlp_tangent_forward(p, st, T, B, q_states, pl.thetap, P, pl.qa, pl.u, pl.ta);
-  if (rc) return rc;
-  PCHK(p, hipMemsetAsync(pl.w, 0, (size_t)T * P * sizeof(float), st));
-  GaussArgs gf{};
-  gf.mu = pl.qa.mu; gf.mud = pl.ta.mu; gf.rho = pl.thetap + p->o_sigma; gf.rstride = P; gf.rhod = pl.u + p->o_sigma; gf.vstride = P;
-  gf.count = q_count; gf.dmu = pl.rdmu; gf.drho = pl.w + p->o_sigma; gf.gstride = P; gf.B = B; gf.A = p->A; gf.mode = G_FISHER;
-  PCHK(p, gauss(st, T, gf));
-  rc = mlp_backward(p, st, T, B, q_states, pl.thetap, P, pl.qa, pl.rdmu, pl.r2, pl.r1, pl.w);
-  if (rc) return rc;
-  // out = mean_t (w_t - lr H_t w_t) + damping v
-  rc = support_hvp(p, st, pl, T, B, theta, s_states, s_actions, s_count, pl.w, pl.hv);
-  if (rc) return rc;
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.w, P, pl.hv, inner_lr, (int)P, pl.tmpP);
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.tmpP, T, (int)P, 1.f / (float)T, v, damping, out);
-  PCHK(p, hipGetLastError());
-  return MI_OK;
 }
 
 // =====================================================================================================================
@@ -1145,22 +868,50 @@ extern "C" int mi_policy_meta_workspace_bytes(const mi_policy* p, int tasks, int
   return MI_OK;
 }
 
-// One primal pass of the VPG / PPO / DiCE losses for all tasks at per-task parameters th [T][P]: forward, loss + cotangents
+// trpo_update (rl.py:361-374) for a meta-batch: theta_out[t] = theta[t] - lr * grad_t(-mean(logp * adv)).  loss_out [T].
+// Workspace: the plan of one kept update (mi_policy_meta_workspace_bytes(steps = 1, n_batches = 1, second_order = 1); the TRPO
+// workspaces start with it).
+extern "C" int mi_policy_adapt(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
+                               const float* actions, const float* adv, const int32_t* count, int tasks, int batch, float lr,
+                               int head_only, float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
+  if (!p || !theta || !states || !actions || !adv || !theta_out || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  MetaPlan pl;
+  meta_plan(p, workspace, tasks, batch, 1, 1, true, pl);
+  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes));
+  StepSet& s = pl.st[0];
+  int rc = mlp_forward(p, st, tasks, batch, states, theta, tstride, s.a);
+  if (rc) return rc;
+  PCHK(p, hipMemsetAsync(pl.g, 0, (size_t)tasks * p->P * sizeof(float), st));
+  GaussArgs ga{};
+  ga.mu = s.a.mu; ga.rho = theta + p->o_sigma; ga.rstride = tstride; ga.act = actions; ga.adv = adv; ga.count = count;
+  ga.coef = s.coef; ga.dmu = s.dmu; ga.drho = pl.g + p->o_sigma; ga.gstride = p->P; ga.loss = loss_out ? loss_out : pl.hv;
+  ga.B = batch; ga.A = p->A; ga.mode = G_A2C;
+  PCHK(p, gauss(st, tasks, ga));
+  rc = mlp_backward(p, st, tasks, batch, states, theta, tstride, s.a, s.dmu, s.d2, s.d1, pl.g, nullptr, nullptr, head_only != 0);
+  if (rc) return rc;
+  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)p->P, 256), tasks), dim3(256), 0, st, theta, tstride, pl.g, lr,
+                     (int)p->P, theta_out);
+  PCHK(p, hipGetLastError());
+  return MI_OK;
+}
+
+// One primal pass of the VPG / PPO / DiCE losses for all tasks at parameters th (stride ts floats per task: P, or 0 = shared): forward, loss + cotangents
 // (gauss2_kernel), backward into g [T][P].  Shared by mi_policy_meta_batch and mi_policy_update: same launches, same order.
-static int meta_primal(mi_policy* p, hipStream_t st, int T, int B, float clip, StepSet& s, const float* th, const float* states,
+static int meta_primal(mi_policy* p, hipStream_t st, int T, int B, float clip, StepSet& s, const float* th, size_t ts, const float* states,
                        const float* actions, const float* adv, const int32_t* count, int kind, const float* oldlp, int value_ratio_one,
                        float* g, float* loss, const float* done) {
   const size_t P = p->P, TP = (size_t)T * P;
-  int rc = mlp_forward(p, st, T, B, states, th, P, s.a);
+  int rc = mlp_forward(p, st, T, B, states, th, ts, s.a);
   if (rc) return rc;
   PCHK(p, hipMemsetAsync(g, 0, TP * sizeof(float), st));
   Gauss2Args ga{};
-  ga.mu = s.a.mu; ga.rho = th + p->o_sigma; ga.rstride = P; ga.act = actions; ga.adv = adv; ga.count = count; ga.oldlp = oldlp;
+  ga.mu = s.a.mu; ga.rho = th + p->o_sigma; ga.rstride = ts; ga.act = actions; ga.adv = adv; ga.count = count; ga.oldlp = oldlp;
   ga.coef = s.coef; ga.coef2 = s.coef2; ga.dmu = s.dmu; ga.drho = g + p->o_sigma; ga.gstride = P; ga.loss = loss; ga.clip = clip;
   ga.B = B; ga.A = p->A; ga.kind = kind; ga.mode = P_PRIMAL; ga.value_ratio_one = value_ratio_one; ga.done = done;
   hipLaunchKernelGGL(gauss2_kernel, dim3(T), dim3(256), 0, st, ga);
   PCHK(p, hipGetLastError());
-  return mlp_backward(p, st, T, B, states, th, P, s.a, s.dmu, s.d2, s.d1, g, s.pre2, s.pre1, false);
+  return mlp_backward(p, st, T, B, states, th, ts, s.a, s.dmu, s.d2, s.d1, g, s.pre2, s.pre1, false);
 }
 // old_log_probs = learner.log_prob(...) under no_grad (rl.py:282-283) at th [T][P] -> olp [T][B]
 static int meta_old_logp(mi_policy* p, hipStream_t st, int T, int B, StepSet& s, const float* th, const float* states,
@@ -1206,7 +957,7 @@ static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta
   PCHK(p, hipGetLastError());
   auto primal = [&](StepSet& s, const float* th, const float* states, const float* actions, const float* adv, const int32_t* count,
                     int kind, const float* oldlp, int value_ratio_one, float* g, float* loss, const float* done) -> int {
-    return meta_primal(p, st, T, B, clip, s, th, states, actions, adv, count, kind, oldlp, value_ratio_one, g, loss, done);
+    return meta_primal(p, st, T, B, clip, s, th, P, states, actions, adv, count, kind, oldlp, value_ratio_one, g, loss, done);
   };
   // ---- inner updates
   for (int k = 0; k < K; ++k) {
@@ -1367,7 +1118,7 @@ extern "C" int mi_policy_update(mi_policy* p, void* stream, const float* theta, 
     if (rc) return rc;
   }
   for (int e = 0; e < epochs; ++e) {
-    rc = meta_primal(p, st, T, B, clip, pl.s, theta_out, states, actions, adv, count, loss_kind, pl.oldlp, 0, pl.g,
+    rc = meta_primal(p, st, T, B, clip, pl.s, theta_out, P, states, actions, adv, count, loss_kind, pl.oldlp, 0, pl.g,
                      pl.loss_e + (size_t)e * T, done);
     if (rc) return rc;
     if (head_only)
@@ -1383,35 +1134,188 @@ extern "C" int mi_policy_update(mi_policy* p, void* stream, const float* theta, 
 }
 
 // =====================================================================================================================
-// MAML-TRPO with any number of inner updates (params['adapt_steps'] > 1): meta_surrogate_loss replays `steps` second-order
+// MAML-TRPO with any number K of inner updates (params['adapt_steps']): meta_surrogate_loss replays `steps` second-order
 // trpo_update calls, one per support replay (rl.py:447-453), before the surrogate / KL on the query replay.  With
 // J = d theta_K / d theta = prod_k (I - lr H_k(theta_k)):
 //   grad mean_t S_t = mean_t J_t^T grad S_t(theta_K)                 (adjoint recursion, as in mi_policy_meta_batch)
 //   Fvp(v)          = mean_t J_t^T F_t J_t v + damping v              (tangent recursion forward, Fisher at the query, adjoint back;
 //                                                                     exact where the adapted policy equals the stored old one)
-static int hvp_step(mi_policy* p, hipStream_t st, MetaPlan& pl, StepSet& s, int T, int B, const float* th, const float* xs,
-                    const float* as, const int32_t* cn, const float* v, float* hv) {
-  const size_t P = p->P;
-  PCHK(p, hipMemsetAsync(hv, 0, (size_t)T * P * sizeof(float), st));
-  int rc = mlp_tangent_forward(p, st, T, B, xs, th, P, s.a, v, pl.ta);
-  if (rc) return rc;
-  Gauss2Args gt{};
-  gt.mu = s.a.mu; gt.mud = pl.ta.mu; gt.rho = th + p->o_sigma; gt.rstride = P; gt.rhod = v + p->o_sigma; gt.vstride = P;
-  gt.act = as; gt.count = cn; gt.coef = s.coef; gt.coef2 = s.coef2; gt.dmu = pl.rdmu; gt.drho = hv + p->o_sigma; gt.gstride = P;
-  gt.B = B; gt.A = p->A; gt.mode = P_TANGENT;
-  hipLaunchKernelGGL(gauss2_kernel, dim3(T), dim3(256), 0, st, gt);
-  PCHK(p, hipGetLastError());
-  return mlp_tangent_backward(p, st, T, B, xs, th, P, s.a, pl.ta, v, s.dmu, s.d2, s.d1, s.pre2, s.pre1, pl.rdmu, pl.r2, pl.r1, hv);
+// K = 1 of a policy the fused sweeps support (policy_sweep.h) runs the same passes as sweeps + folds: a fast path that leaves
+// everything in the slots of the per-layer loop (StepSet 0, the query set, theta_0 and theta_1), not a second algorithm.
+struct StepsPlan : MetaPlan {
+  float *loss_t, *kl_t;                 // [T] per-task surrogate loss and KL
+  float* partial;                       // fused sweeps: [T][slots][P + 2] per-workgroup gradient partials (K = 1, supported policy)
+  int spt, spw, slots, sweep_grid;
+};
+// geometry of the fused sweeps: slabs of 32 rows, a contiguous run of slabs per workgroup, one round of workgroups on 256 CUs
+static void sweep_geometry(int T, int B, int& spt, int& spw, int& slots, int& grid) {
+  spt = ceil_div(B, 32);
+  const int total = T * (spt + 1);      // virtual slabs: a marker in front of every task's slabs (policy_sweep.hip: what entering a task costs)
+  spw = ceil_div(total, 256);
+  grid = ceil_div(total, spw);
+  slots = ceil_div(spt + 1, spw) + 1;
 }
-
+static bool sweep_supported(const mi_policy* p) {
+  return policy_sweep_supported(p->act == ACT_RELU, p->H1, p->H2, p->S, p->A);
+}
+static bool fused_steps(const mi_policy* p, int K) { return K == 1 && g_policy_fused_fvp && sweep_supported(p); }
+static void steps_plan(const mi_policy* p, void* ws, int T, int B, int K, StepsPlan& pl) {
+  meta_plan(p, ws, T, B, K, 1, true, pl);
+  PBump b{reinterpret_cast<char*>(ws), pl.bytes};
+  pl.loss_t = b.f((size_t)2 * T); pl.kl_t = ws ? pl.loss_t + T : nullptr;
+  sweep_geometry(T, B, pl.spt, pl.spw, pl.slots, pl.sweep_grid);
+  pl.partial = (K == 1 && sweep_supported(p)) ? b.f((size_t)T * pl.slots * (p->P + 2)) : nullptr;
+  pl.bytes = align_up(b.off, 256);
+}
 extern "C" int mi_trpo_steps_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, size_t* bytes) {
   if (!p || !bytes || tasks < 1 || batch < 1 || steps < 1) return MI_ERR_ARG;
-  MetaPlan pl;
-  meta_plan(p, nullptr, tasks, batch, steps, 1, true, pl);
-  *bytes = pl.bytes + align_up((size_t)2 * tasks * sizeof(float), 256);      // per-task loss and KL behind the plan
+  StepsPlan pl;
+  steps_plan(p, nullptr, tasks, batch, steps, pl);
+  *bytes = pl.bytes;
   return MI_OK;
 }
 
+// the support replays: [K][T][B][.] stacks, and replay k of them
+struct SupStack { const float *states, *actions, *adv; const int32_t* count; };
+struct SupRef { const float *xs, *as, *adv; const int32_t* cn; };
+static SupRef sup_at(const mi_policy* p, const SupStack& s, int T, int B, int k) {
+  const size_t TB = (size_t)T * B;
+  return {s.states + k * TB * p->S, s.actions + k * TB * p->A, s.adv ? s.adv + k * TB : nullptr,
+          s.count ? s.count + (size_t)k * T : nullptr};
+}
+
+// theta_k sits at pl.theta + k T P.  theta_0 is shared by all tasks: one row, read with stride 0 (per-task rows of the same values
+// would cost the dense kernels their shared weight reads); from k = 1 on every task has its own row.
+static size_t theta_stride(const mi_policy* p, int k) { return k == 0 ? 0 : p->P; }
+
+// inner-loss HVP on the cached pass of one update: hv = H_k v for every task (v, hv: [T][P]).  TRPO's inner loss is always A2C,
+// whose f'' is identically zero: the tangent of its cotangents is gauss_kernel's G_TANGENT, which reads no StepSet::coef2 (the
+// fused primal sweep does not write one; gauss2_kernel's P_TANGENT with coef2 == 0 gives the same numbers from three loops per row).
+static int hvp_step(mi_policy* p, hipStream_t st, MetaPlan& pl, StepSet& s, int T, int B, const float* th, size_t ts, const SupRef& r,
+                    const float* v, float* hv) {
+  const size_t P = p->P;
+  PCHK(p, hipMemsetAsync(hv, 0, (size_t)T * P * sizeof(float), st));
+  int rc = mlp_tangent_forward(p, st, T, B, r.xs, th, ts, s.a, v, pl.ta);
+  if (rc) return rc;
+  GaussArgs gt{};
+  gt.mu = s.a.mu; gt.mud = pl.ta.mu; gt.rho = th + p->o_sigma; gt.rstride = ts; gt.rhod = v + p->o_sigma; gt.vstride = P;
+  gt.act = r.as; gt.count = r.cn; gt.coef = s.coef; gt.dmu = pl.rdmu; gt.drho = hv + p->o_sigma; gt.gstride = P;
+  gt.B = B; gt.A = p->A; gt.mode = G_TANGENT;
+  PCHK(p, gauss(st, T, gt));
+  return mlp_tangent_backward(p, st, T, B, r.xs, th, ts, s.a, pl.ta, v, s.dmu, s.d2, s.d1, s.pre2, s.pre1, pl.rdmu, pl.r2, pl.r1, hv);
+}
+// x_t <- (I - lr H_k) x_t through the updates, in place on x [T][P] (pl.hv is scratch): k = 0 .. K-1 is J_t x, the tangent
+// recursion; transpose walks k = K-1 .. 0 and is J_t^T x, the adjoint recursion (every H_k is symmetric: only the order differs).
+static int jac_apply(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupStack& sup, int T, int B, int K, bool transpose, float lr,
+                     float* x) {
+  const size_t P = p->P, TP = (size_t)T * P;
+  for (int i = 0; i < K; ++i) {
+    const int k = transpose ? K - 1 - i : i;
+    int rc = hvp_step(p, st, pl, pl.st[k], T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), sup_at(p, sup, T, B, k), x, pl.hv);
+    if (rc) return rc;
+    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, x, P, pl.hv, lr, (int)P, x);
+    PCHK(p, hipGetLastError());
+  }
+  return MI_OK;
+}
+
+// ---- the fused sweeps of K = 1 (policy_sweep.h)
+static SweepArgs sweep_base(const mi_policy* p, const StepsPlan& pl, int T, int B) {
+  SweepArgs a{};
+  a.T = T; a.B = B; a.S = p->S; a.A = p->A; a.spt = pl.spt; a.spw = pl.spw; a.slots = pl.slots; a.partial = pl.partial;
+  a.pitch = (int)p->P + 2;
+  a.o_sigma = (int)p->o_sigma; a.o_w1 = (int)p->o_w1; a.o_b1 = (int)p->o_b1; a.o_w2 = (int)p->o_w2; a.o_b2 = (int)p->o_b2;
+  a.o_w3 = (int)p->o_w3; a.o_b3 = (int)p->o_b3; a.P = (int)p->P;
+  a.stamps = g_sweep_stamps;
+  return a;
+}
+// H_0 over the cached support pass at theta; the caller sets the direction
+static SweepArgs sweep_hvp_args(const mi_policy* p, const StepsPlan& pl, int T, int B, const SupRef& r) {
+  const StepSet& s = pl.st[0];
+  SweepArgs hs = sweep_base(p, pl, T, B);
+  hs.x = r.xs; hs.act = r.as; hs.h1 = s.a.h1; hs.h2 = s.a.h2; hs.mu = s.a.mu; hs.coef = s.coef; hs.dmu = s.dmu;
+  hs.d2 = s.d2; hs.count = r.cn; hs.theta = pl.theta; hs.tstride = 0;
+  return hs;
+}
+static FoldArgs fold_base(const mi_policy* p, const StepsPlan& pl, int T, float lr) {
+  FoldArgs f{};
+  f.partial = pl.partial; f.slots = pl.slots; f.spt = pl.spt; f.spw = pl.spw; f.T = T; f.P = (int)p->P; f.pitch = (int)p->P + 2; f.lr = lr;
+  f.o_sigma = (int)p->o_sigma; f.A = p->A;
+  return f;
+}
+
+// Inner update and query pass as two PRIMAL sweeps (forward + loss + backward of a pass in one launch) instead of ~22 per-layer
+// launches: theta_1, loss_t / kl_t and, with want_grad, lam = grad S_t(theta_1).
+static int fused_surrogate(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& r, const float* q_states, const float* q_actions,
+                           const float* q_adv, const int32_t* q_count, const float* old_loc, const float* old_scale, int T, int B,
+                           float inner_lr, bool want_grad) {
+  const size_t P = p->P;
+  float* th1 = pl.theta + (size_t)T * P;
+  // The pass lands where the per-layer loop keeps it (activations, dmu, d2, coef of StepSet 0), so a per-layer product or the
+  // general (ANIL) product finds it.  pre2 / pre1 are not written: only a tanh policy reads them (for ReLU they meet phi'' == 0),
+  // and the sweeps run ReLU policies only.
+  StepSet& s = pl.st[0];
+  SweepArgs sp = sweep_base(p, pl, T, B);
+  sp.x = r.xs; sp.act = r.as; sp.adv = r.adv; sp.count = r.cn; sp.theta = pl.theta; sp.tstride = 0; sp.surrogate = 0;
+  sp.h1_out = s.a.h1; sp.h2_out = s.a.h2; sp.mu_out = s.a.mu; sp.dmu_out = s.dmu; sp.d2_out = s.d2; sp.coef_out = s.coef;
+  PCHK(p, launch_policy_sweep(st, sp, pl.sweep_grid, SW_PRIMAL));
+  FoldArgs f = fold_base(p, pl, T, inner_lr);
+  f.mode = 0; f.v = pl.theta; f.out = th1;                        // theta_1 = theta - lr g_t
+  PCHK(p, launch_policy_sweep_fold(st, f, T));
+  SweepArgs sq = sweep_base(p, pl, T, B);
+  sq.x = q_states; sq.act = q_actions; sq.adv = q_adv; sq.count = q_count; sq.theta = th1; sq.tstride = P; sq.surrogate = 1;
+  sq.old_loc = old_loc; sq.old_scale = old_scale; sq.fwd_only = want_grad ? 0 : 1;
+  sq.h1_out = pl.q.a.h1; sq.h2_out = pl.q.a.h2; sq.mu_out = pl.q.a.mu;
+  PCHK(p, launch_policy_sweep(st, sq, pl.sweep_grid, SW_PRIMAL));
+  f.mode = 3; f.out = want_grad ? pl.lam : nullptr; f.loss_t = pl.loss_t; f.kl_t = pl.kl_t;      // per-task loss / KL
+  PCHK(p, launch_policy_sweep_fold(st, f, T));
+  return MI_OK;
+}
+
+// Fvp(v) as three sweeps + three folds:  A: u_t = v - lr H_t v,  B: w_t = F_t u_t,  C: out = mean_t (w_t - lr H_t w_t) + damping v
+static int fused_fvp(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& r, const float* q_states, const int32_t* q_count, int T,
+                     int B, float inner_lr, float damping, const float* v, float* out) {
+  const int P = (int)p->P;
+  float *th1 = pl.theta + (size_t)T * P, *u = pl.vmask, *w = pl.lam, *tmp = pl.hv;
+  SweepArgs hs = sweep_hvp_args(p, pl, T, B, r);
+  FoldArgs f = fold_base(p, pl, T, inner_lr);
+  f.v = v; f.damping = damping;
+  hs.dir = v; hs.dstride = 0;
+  PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
+  f.mode = 0; f.out = u;
+  PCHK(p, launch_policy_sweep_fold(st, f, T));
+  SweepArgs fs = sweep_base(p, pl, T, B);              // over the query pass at theta_1
+  fs.x = q_states; fs.h1 = pl.q.a.h1; fs.h2 = pl.q.a.h2; fs.count = q_count; fs.theta = th1; fs.tstride = P; fs.dir = u; fs.dstride = P;
+  PCHK(p, launch_policy_sweep(st, fs, pl.sweep_grid, SW_FISHER));
+  f.mode = 1; f.out = w; f.thetap = th1; f.u = u;
+  PCHK(p, launch_policy_sweep_fold(st, f, T));
+  hs.dir = w; hs.dstride = P;
+  PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
+  f.mode = 2; f.out = tmp; f.w = w;
+  if (!p->fold_counters) {               // (once per policy object: the fold leaves the counters zero again)
+    const size_t nb = (size_t)ceil_div(P, 256) * sizeof(unsigned);
+    if (hipMalloc(reinterpret_cast<void**>(&p->fold_counters), nb) != hipSuccess) { p->fold_counters = nullptr; (void)hipGetLastError(); }
+    else PCHK(p, hipMemsetAsync(p->fold_counters, 0, nb, st));
+  }
+  if (p->fold_counters) {                // the mean over tasks + damping v by the last workgroup of every parameter block: no launch of its own
+    // The protocol needs the counters at zero when the fold starts; its last workgroup leaves them at zero.  A fold whose launch was
+    // refused leaves the flag set, and the next product re-zeroes (stream-ordered, 4 * ceil(P / 256) bytes) instead of waiting for a
+    // "last" workgroup that can no longer exist.  One stream per mi_policy at a time (include/mi_maml.h).
+    if (p->fold_dirty) PCHK(p, hipMemsetAsync(p->fold_counters, 0, (size_t)ceil_div(P, 256) * sizeof(unsigned), st));
+    p->fold_dirty = true;
+    f.counter = p->fold_counters; f.mean_out = out; f.inv_T = 1.f / (float)T;
+    PCHK(p, launch_policy_sweep_fold(st, f, T));
+    p->fold_dirty = false;
+    return MI_OK;
+  }
+  PCHK(p, launch_policy_sweep_fold(st, f, T));
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, tmp, T, P, 1.f / (float)T, v, damping, out);
+  PCHK(p, hipGetLastError());
+  return MI_OK;
+}
+
+// meta_surrogate_loss (rl.py:441-473) at theta for `tasks` tasks with `steps` second-order inner updates on the support replays
+// ([steps][tasks][batch][.]), and optionally its gradient (rl.py:413-416).  Leaves everything the products need in `workspace`.
 extern "C" int mi_trpo_surrogate_steps(mi_policy* p, void* stream, const float* theta, int steps, const float* s_states,
                                        const float* s_actions, const float* s_adv, const int32_t* s_count, const float* q_states,
                                        const float* q_actions, const float* q_adv, const int32_t* q_count, const float* old_loc,
@@ -1422,91 +1326,88 @@ extern "C" int mi_trpo_surrogate_steps(mi_policy* p, void* stream, const float* 
     return pfail(p, MI_ERR_ARG, "null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch, K = steps;
-  const size_t P = p->P, TB = (size_t)T * B, TP = (size_t)T * P;
-  MetaPlan pl;
-  meta_plan(p, workspace, T, B, K, 1, true, pl);
-  size_t need = 0;
-  mi_trpo_steps_workspace_bytes(p, T, B, K, &need);
-  if (need > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need));
-  float* loss_t = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + pl.bytes);
-  float* kl_t = loss_t + T;
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, theta, (size_t)0, pl.g, 0.f, (int)P, pl.theta);
-  PCHK(p, hipGetLastError());
-  for (int k = 0; k < K; ++k) {                                   // trpo_update on support replay k (a2c loss, normalised advantages)
-    StepSet& s = pl.st[k];
-    float* th = pl.theta + (size_t)k * TP;
-    const float* xs = s_states + (size_t)k * TB * p->S;
-    const float* as = s_actions + (size_t)k * TB * p->A;
-    int rc = mlp_forward(p, st, T, B, xs, th, P, s.a);
-    if (rc) return rc;
-    PCHK(p, hipMemsetAsync(pl.g, 0, TP * sizeof(float), st));
-    Gauss2Args ga{};
-    ga.mu = s.a.mu; ga.rho = th + p->o_sigma; ga.rstride = P; ga.act = as; ga.adv = s_adv + (size_t)k * TB;
-    ga.count = s_count ? s_count + (size_t)k * T : nullptr; ga.coef = s.coef; ga.coef2 = s.coef2; ga.dmu = s.dmu;
-    ga.drho = pl.g + p->o_sigma; ga.gstride = P; ga.loss = pl.hv; ga.B = B; ga.A = p->A; ga.kind = MI_PLOSS_A2C; ga.mode = P_PRIMAL;
-    hipLaunchKernelGGL(gauss2_kernel, dim3(T), dim3(256), 0, st, ga);
-    PCHK(p, hipGetLastError());
-    rc = mlp_backward(p, st, T, B, xs, th, P, s.a, s.dmu, s.d2, s.d1, pl.g, s.pre2, s.pre1, false);
-    if (rc) return rc;
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, th, P, pl.g, inner_lr, (int)P, th + TP);
-    PCHK(p, hipGetLastError());
-  }
+  const size_t P = p->P, TP = (size_t)T * P;
+  StepsPlan pl;
+  steps_plan(p, workspace, T, B, K, pl);
+  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes));
+  const SupStack sup{s_states, s_actions, s_adv, s_count};
+  const bool fused = fused_steps(p, K);
   float* thK = pl.theta + (size_t)K * TP;
-  int rc = mlp_forward(p, st, T, B, q_states, thK, P, pl.q.a);
-  if (rc) return rc;
-  PCHK(p, hipMemsetAsync(pl.lam, 0, TP * sizeof(float), st));
-  GaussArgs gq{};
-  gq.mu = pl.q.a.mu; gq.rho = thK + p->o_sigma; gq.rstride = P; gq.act = q_actions; gq.adv = q_adv; gq.count = q_count;
-  gq.old_loc = old_loc; gq.old_scale = old_scale; gq.coef = pl.q.coef; gq.dmu = pl.q.dmu; gq.drho = pl.lam + p->o_sigma;
-  gq.gstride = P; gq.loss = loss_t; gq.kl = kl_t; gq.B = B; gq.A = p->A; gq.mode = G_SURROGATE;
-  PCHK(p, gauss(st, T, gq));
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, loss_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, loss_out);
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, kl_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, kl_out);
+  int rc = MI_OK;
+  // theta_0 (one row).  The products take no theta: they read this copy.
+  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), 1), dim3(256), 0, st, theta, (size_t)0, pl.g, 0.f, (int)P, pl.theta);
+  PCHK(p, hipGetLastError());
+  if (fused) {
+    rc = fused_surrogate(p, st, pl, sup_at(p, sup, T, B, 0), q_states, q_actions, q_adv, q_count, old_loc, old_scale, T, B, inner_lr,
+                         grad_out != nullptr);
+    if (rc) return rc;
+  } else {
+    for (int k = 0; k < K; ++k) {                                 // trpo_update on support replay k (a2c loss, normalised advantages)
+      const SupRef r = sup_at(p, sup, T, B, k);
+      float* th = pl.theta + (size_t)k * TP;
+      const size_t ts = theta_stride(p, k);
+      rc = meta_primal(p, st, T, B, 0.f, pl.st[k], th, ts, r.xs, r.as, r.adv, r.cn, MI_PLOSS_A2C, nullptr, 0, pl.g,
+                       pl.hv /* step loss: unused */, nullptr);
+      if (rc) return rc;
+      hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, th, ts, pl.g, inner_lr, (int)P, th + TP);
+      PCHK(p, hipGetLastError());
+    }
+    rc = mlp_forward(p, st, T, B, q_states, thK, P, pl.q.a);
+    if (rc) return rc;
+    PCHK(p, hipMemsetAsync(pl.lam, 0, TP * sizeof(float), st));
+    GaussArgs gq{};
+    gq.mu = pl.q.a.mu; gq.rho = thK + p->o_sigma; gq.rstride = P; gq.act = q_actions; gq.adv = q_adv; gq.count = q_count;
+    gq.old_loc = old_loc; gq.old_scale = old_scale; gq.coef = pl.q.coef; gq.dmu = pl.q.dmu; gq.drho = pl.lam + p->o_sigma;
+    gq.gstride = P; gq.loss = pl.loss_t; gq.kl = pl.kl_t; gq.B = B; gq.A = p->A; gq.mode = G_SURROGATE;
+    PCHK(p, gauss(st, T, gq));
+  }
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, pl.loss_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, loss_out);
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, pl.kl_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, kl_out);
   PCHK(p, hipGetLastError());
   if (!grad_out) return MI_OK;
-  rc = mlp_backward(p, st, T, B, q_states, thK, P, pl.q.a, pl.q.dmu, pl.q.d2, pl.q.d1, pl.lam);
-  if (rc) return rc;
-  for (int k = K - 1; k >= 0; --k) {
-    const float* th = pl.theta + (size_t)k * TP;
-    rc = hvp_step(p, st, pl, pl.st[k], T, B, th, s_states + (size_t)k * TB * p->S, s_actions + (size_t)k * TB * p->A,
-                  s_count ? s_count + (size_t)k * T : nullptr, pl.lam, pl.hv);
+  const float* gt = pl.lam;                                       // J_t^T grad S_t(theta_K)
+  if (fused) {                                                    // one HVP sweep along lam_t + fold, instead of ~10 per-layer launches
+    SweepArgs hs = sweep_hvp_args(p, pl, T, B, sup_at(p, sup, T, B, 0));
+    hs.dir = pl.lam; hs.dstride = P;
+    PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
+    FoldArgs f = fold_base(p, pl, T, inner_lr);
+    f.mode = 2; f.out = pl.hv; f.w = pl.lam;
+    PCHK(p, launch_policy_sweep_fold(st, f, T));
+    gt = pl.hv;
+  } else {
+    rc = mlp_backward(p, st, T, B, q_states, thK, P, pl.q.a, pl.q.dmu, pl.q.d2, pl.q.d1, pl.lam);
     if (rc) return rc;
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.lam, P, pl.hv, inner_lr, (int)P, pl.lam);
-    PCHK(p, hipGetLastError());
+    rc = jac_apply(p, st, pl, sup, T, B, K, true, inner_lr, pl.lam);
+    if (rc) return rc;
   }
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.lam, T, (int)P, 1.f / (float)T,
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gt, T, (int)P, 1.f / (float)T,
                      (const float*)nullptr, 0.f, grad_out);
   PCHK(p, hipGetLastError());
   return MI_OK;
 }
 
+// Fvp(v) = mean_t J_t^T F_t J_t v + damping v (cherry trpo.hessian_vector_product of the mean KL at the point where the adapted
+// policy equals the old policy, rl.py:417), at the theta of the preceding mi_trpo_surrogate_steps on this workspace and replays.
 extern "C" int mi_trpo_fvp_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
                                  const int32_t* s_count, const float* q_states, const int32_t* q_count, int tasks, int batch,
                                  float inner_lr, float damping, const float* v, float* out, void* workspace, size_t workspace_bytes) {
   if (!p || !s_states || !s_actions || !q_states || !v || !out || !workspace || steps < 1) return pfail(p, MI_ERR_ARG, "null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch, K = steps;
-  const size_t P = p->P, TB = (size_t)T * B, TP = (size_t)T * P;
-  MetaPlan pl;
-  meta_plan(p, workspace, T, B, K, 1, true, pl);
+  const size_t P = p->P, TP = (size_t)T * P;
+  StepsPlan pl;
+  steps_plan(p, workspace, T, B, K, pl);
   if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small");
-  auto sup = [&](int k, const float*& xs, const float*& as, const int32_t*& cn) {
-    xs = s_states + (size_t)k * TB * p->S; as = s_actions + (size_t)k * TB * p->A; cn = s_count ? s_count + (size_t)k * T : nullptr;
-  };
-  // u = J v : u <- u - lr H_k u, k = 0 .. K-1   (pl.vmask holds u)
+  const SupStack sup{s_states, s_actions, nullptr, s_count};
+  if (fused_steps(p, K)) return fused_fvp(p, st, pl, sup_at(p, sup, T, B, 0), q_states, q_count, T, B, inner_lr, damping, v, out);
+  // u = J v   (pl.vmask holds u)
   hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (size_t)0, pl.g, 0.f, (int)P, pl.vmask);
   PCHK(p, hipGetLastError());
-  for (int k = 0; k < K; ++k) {
-    const float *xs, *as; const int32_t* cn;
-    sup(k, xs, as, cn);
-    int rc = hvp_step(p, st, pl, pl.st[k], T, B, pl.theta + (size_t)k * TP, xs, as, cn, pl.vmask, pl.hv);
-    if (rc) return rc;
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.vmask, P, pl.hv, inner_lr, (int)P, pl.vmask);
-    PCHK(p, hipGetLastError());
-  }
+  int rc = jac_apply(p, st, pl, sup, T, B, K, false, inner_lr, pl.vmask);
+  if (rc) return rc;
   // w = F u at the query (Gaussian Fisher at new == old)
   float* thK = pl.theta + (size_t)K * TP;
-  int rc = mlp_tangent_forward(p, st, T, B, q_states, thK, P, pl.q.a, pl.vmask, pl.ta);
+  rc = mlp_tangent_forward(p, st, T, B, q_states, thK, P, pl.q.a, pl.vmask, pl.ta);
   if (rc) return rc;
   PCHK(p, hipMemsetAsync(pl.lam, 0, TP * sizeof(float), st));
   GaussArgs gf{};
@@ -1516,14 +1417,8 @@ extern "C" int mi_trpo_fvp_steps(mi_policy* p, void* stream, int steps, const fl
   rc = mlp_backward(p, st, T, B, q_states, thK, P, pl.q.a, pl.rdmu, pl.r2, pl.r1, pl.lam);
   if (rc) return rc;
   // out = mean_t J^T w + damping v
-  for (int k = K - 1; k >= 0; --k) {
-    const float *xs, *as; const int32_t* cn;
-    sup(k, xs, as, cn);
-    rc = hvp_step(p, st, pl, pl.st[k], T, B, pl.theta + (size_t)k * TP, xs, as, cn, pl.lam, pl.hv);
-    if (rc) return rc;
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.lam, P, pl.hv, inner_lr, (int)P, pl.lam);
-    PCHK(p, hipGetLastError());
-  }
+  rc = jac_apply(p, st, pl, sup, T, B, K, true, inner_lr, pl.lam);
+  if (rc) return rc;
   hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.lam, T, (int)P, 1.f / (float)T, v, damping, out);
   PCHK(p, hipGetLastError());
   return MI_OK;
@@ -1543,7 +1438,7 @@ extern "C" int mi_trpo_fvp_steps(mi_policy* p, void* stream, int steps, const fl
 //   dz_cv = phi' dh_cv + phi'' (z_v dh_c + z_c dh_v) + (phi''' z_c z_v + phi'' z_cv) dh,
 //   dW_cv = dz_cv^T h + dz_c^T h_v + dz_v^T h_c + dz^T h_cv,     dh_in_cv = dz_cv W + dz_c W_v + dz_v W_c
 // (tanh: phi' = 1 - h^2 =: p, phi'' = -2 h p, phi''' = p (6 h^2 - 2); ReLU: phi'' = phi''' = 0).  The c-tangent sweep depends on
-// the context only and is computed once (mi_trpo_kl_prepare); v-tangent and mixed sweeps run per product.  All dense products
+// the context only and is computed once (mi_trpo_kl_prepare_steps); v-tangent and mixed sweeps run per product.  All dense products
 // go through the same fp32 matrix-pipe kernels as above with up to four summed terms.
 struct EwArgs {
   const float* h;                         // stored activation of the layer
@@ -1689,37 +1584,9 @@ static void mix_plan(const mi_policy* p, PBump& b, size_t TB, MixSweep& m) {
   m.hcv1 = b.f(TB * p->H1); m.zcv2 = b.f(TB * p->H2); m.hcv2 = b.f(TB * p->H2); m.mucv = b.f(TB * p->A); m.rdmu_cv = b.f(TB * p->A);
   m.dh2cv = b.f(TB * p->H2); m.dz2cv = b.f(TB * p->H2); m.dh1cv = b.f(TB * p->H1); m.dz1cv = b.f(TB * p->H1);
 }
-struct GenPlan {
-  float *k_dmu, *k_d2, *k_d1, *k_pre2, *k_pre1;      // KL primal cotangents on the query pass at theta'
-  float* c;                                           // [T][P] grad KL_t(theta'_t)
-  TanSweep sc, sv;                                    // c-tangent (context) and v-tangent (per product) sweeps over the support pass
-  MixSweep mx;                                        // mixed (cv) sweep scratch
-  float *s3, *scr;                                    // [T][P]: third-order term, scratch
-  size_t bytes;
-};
-static void gen_plan(const mi_policy* p, void* ws, int T, int B, TrpoPlan& pl, GenPlan& gp) {
-  trpo_plan(p, ws, T, B, pl);
-  PBump b{reinterpret_cast<char*>(ws), pl.bytes};
-  const size_t TB = (size_t)T * B, TP = (size_t)T * p->P;
-  gp.k_dmu = b.f(TB * p->A); gp.k_d2 = b.f(TB * p->H2); gp.k_d1 = b.f(TB * p->H1); gp.k_pre2 = b.f(TB * p->H2); gp.k_pre1 = b.f(TB * p->H1);
-  gp.c = b.f(TP);
-  tan_plan(p, b, TB, gp.sc); tan_plan(p, b, TB, gp.sv);
-  mix_plan(p, b, TB, gp.mx);
-  gp.s3 = b.f(TP); gp.scr = b.f(TP);
-  gp.bytes = align_up(b.off, 256);
-}
-extern "C" int mi_trpo_general_workspace_bytes(const mi_policy* p, int tasks, int batch, size_t* bytes) {
-  if (!p || !bytes || tasks < 1 || batch < 1) return MI_ERR_ARG;
-  TrpoPlan pl; GenPlan gp;
-  gen_plan(p, nullptr, tasks, batch, pl, gp);
-  *bytes = gp.bytes;
-  return MI_OK;
-}
-
 // The cached primal pass a tangent sweep runs over: activations, cotangents (dmu, dz2; pre2 / pre1 before the phi' factor) and
-// dL/dlogp per sample -- TrpoPlan::sa of the one-step path or the StepSet of inner update k.
+// dL/dlogp per sample -- the StepSet of inner update k.
 struct PassRef { const float *h1, *h2, *mu, *dmu, *d2, *pre2, *pre1, *coef; };
-static PassRef pass_of(const TrpoPlan& pl) { return {pl.sa.h1, pl.sa.h2, pl.sa.mu, pl.s_dmu, pl.s_d2, pl.s_pre2, pl.s_pre1, pl.s_coef}; }
 static PassRef pass_of(const StepSet& s) { return {s.a.h1, s.a.h2, s.a.mu, s.dmu, s.d2, s.pre2, s.pre1, s.coef}; }
 
 // First-order tangent sweep over a cached support pass at theta (stride ts floats per task, 0 = shared) along direction d (stride
@@ -1783,91 +1650,8 @@ static int mixed_sweep(mi_policy* p, hipStream_t st, const PassRef& ps, int T, i
   return MI_OK;
 }
 
-// After mi_trpo_surrogate(theta, ...) on the same workspace: the KL cotangent pass on the query replay (c_t = grad KL_t at theta'_t)
-// and the c-tangent sweep over the support pass.  kl_grad_out (optional, [P]) = d mean_t KL_t / d theta = mean_t (I - lr H_t) c_t.
-extern "C" int mi_trpo_kl_prepare(mi_policy* p, void* stream, const float* theta, const float* s_states, const float* s_actions,
-                                  const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
-                                  const float* old_scale, int tasks, int batch, float inner_lr, float* kl_grad_out, void* workspace,
-                                  size_t workspace_bytes) {
-  if (!p || !theta || !s_states || !s_actions || !q_states || !old_loc || !old_scale || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, B = batch;
-  const size_t P = p->P;
-  TrpoPlan pl; GenPlan gp;
-  gen_plan(p, workspace, T, B, pl, gp);
-  if (gp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(gp.bytes));
-  PCHK(p, hipMemsetAsync(gp.c, 0, (size_t)T * P * sizeof(float), st));
-  GaussKlArgs gk{};
-  gk.mu = pl.qa.mu; gk.rho = pl.thetap + p->o_sigma; gk.rstride = P; gk.old_loc = old_loc; gk.old_scale = old_scale; gk.count = q_count;
-  gk.dmu = gp.k_dmu; gk.drho = gp.c + p->o_sigma; gk.gstride = P; gk.B = B; gk.A = p->A; gk.mode = KL_GRAD;
-  hipLaunchKernelGGL(gauss_kl_kernel, dim3(T), dim3(256), 0, st, gk);
-  PCHK(p, hipGetLastError());
-  int rc = mlp_backward(p, st, T, B, q_states, pl.thetap, P, pl.qa, gp.k_dmu, gp.k_d2, gp.k_d1, gp.c, gp.k_pre2, gp.k_pre1);
-  if (rc) return rc;
-  rc = tan_sweep(p, st, pass_of(pl), T, B, theta, 0, s_states, s_actions, s_count, gp.c, P, gp.sc, gp.scr);
-  if (rc || !kl_grad_out) return rc;
-  rc = support_hvp(p, st, pl, T, B, theta, s_states, s_actions, s_count, gp.c, pl.hv);
-  if (rc) return rc;
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, gp.c, P, pl.hv, inner_lr, (int)P, pl.tmpP);
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.tmpP, T, (int)P, 1.f / (float)T,
-                     (const float*)nullptr, 0.f, kl_grad_out);
-  PCHK(p, hipGetLastError());
-  return MI_OK;
-}
-
-// trpo.hessian_vector_product(mean KL, params, damping)(v) (rl.py:417) at the parameters of the preceding mi_trpo_surrogate +
-// mi_trpo_kl_prepare on this workspace, exact for new != old (ANIL-TRPO, rl/anil_trpo.py:129).
-extern "C" int mi_trpo_fvp_general(mi_policy* p, void* stream, const float* theta, const float* s_states, const float* s_actions,
-                                   const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
-                                   int tasks, int batch, float inner_lr, float damping, const float* v, float* out, void* workspace,
-                                   size_t workspace_bytes) {
-  if (!p || !theta || !s_states || !s_actions || !q_states || !old_scale || !v || !out || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, B = batch;
-  const size_t P = p->P;
-  TrpoPlan pl; GenPlan gp;
-  gen_plan(p, workspace, T, B, pl, gp);
-  if (gp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small");
-  // ---- u_t = J_t v
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (size_t)0, pl.tmpP, 0.f, (int)P, pl.u);
-  PCHK(p, hipGetLastError());
-  int rc = support_hvp(p, st, pl, T, B, theta, s_states, s_actions, s_count, pl.u, pl.hv);
-  if (rc) return rc;
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.u, P, pl.hv, inner_lr, (int)P, pl.u);
-  PCHK(p, hipGetLastError());
-  // ---- w_t = Hess KL_t(theta'_t) u_t: tangent forward on the query pass, exact output Hessian, tangent backward
-  rc = mlp_tangent_forward(p, st, T, B, q_states, pl.thetap, P, pl.qa, pl.u, pl.ta);
-  if (rc) return rc;
-  PCHK(p, hipMemsetAsync(pl.w, 0, (size_t)T * P * sizeof(float), st));
-  GaussKlArgs gh{};
-  gh.mu = pl.qa.mu; gh.rho = pl.thetap + p->o_sigma; gh.rstride = P; gh.old_scale = old_scale; gh.mud = pl.ta.mu;
-  gh.rhod = pl.u + p->o_sigma; gh.vstride = P; gh.count = q_count; gh.dmu = pl.rdmu; gh.drho = pl.w + p->o_sigma; gh.gstride = P;
-  gh.B = B; gh.A = p->A; gh.mode = KL_HESS;
-  hipLaunchKernelGGL(gauss_kl_kernel, dim3(T), dim3(256), 0, st, gh);
-  PCHK(p, hipGetLastError());
-  rc = mlp_tangent_backward(p, st, T, B, q_states, pl.thetap, P, pl.qa, pl.ta, pl.u, gp.k_dmu, gp.k_d2, gp.k_d1, gp.k_pre2, gp.k_pre1,
-                            pl.rdmu, pl.r2, pl.r1, pl.w);
-  if (rc) return rc;
-  // ---- r_t = J_t^T w_t  (left in pl.w)
-  rc = support_hvp(p, st, pl, T, B, theta, s_states, s_actions, s_count, pl.w, pl.hv);
-  if (rc) return rc;
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.w, P, pl.hv, inner_lr, (int)P, pl.w);
-  PCHK(p, hipGetLastError());
-  // ---- s3_t = T_t[v, c_t]: v-tangent sweep, then the mixed sweep
-  rc = tan_sweep(p, st, pass_of(pl), T, B, theta, 0, s_states, s_actions, s_count, v, 0, gp.sv, gp.scr);
-  if (rc) return rc;
-  PCHK(p, hipMemsetAsync(gp.s3, 0, (size_t)T * P * sizeof(float), st));
-  rc = mixed_sweep(p, st, pass_of(pl), T, B, theta, 0, s_states, s_actions, s_count, gp.c, P, v, 0, gp.sc, gp.sv, gp.mx, gp.s3);
-  if (rc) return rc;
-  // ---- out = mean_t (r_t - lr s3_t) + damping v
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.w, P, gp.s3, inner_lr, (int)P, pl.tmpP);
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.tmpP, T, (int)P, 1.f / (float)T, v, damping, out);
-  PCHK(p, hipGetLastError());
-  return MI_OK;
-}
-
 // =====================================================================================================================
-// The same exact Hessian-vector product of the mean KL with any number K of inner updates (rl/anil_trpo.py --adapt_steps K).
+// That product for any number K of inner updates (rl/anil_trpo.py --adapt_steps K).
 // theta_0 = theta, theta_{k+1} = theta_k - lr grad L_k(theta_k), H_k = Hess L_k(theta_k), T_k[a, b] = d/d eps H_k(theta_k + eps a) b,
 // c = grad KL_t(theta_K) on the query replay.  Differentiating the adjoint recursion of the KL gradient once more along v:
 //   context (mi_trpo_kl_prepare_steps):  lam_K = c,   lam_k = lam_{k+1} - lr H_k lam_{k+1},      grad mean KL = mean_t lam_0
@@ -1877,9 +1661,9 @@ extern "C" int mi_trpo_fvp_general(mi_policy* p, void* stream, const float* thet
 // which at K = 1 is the formula above.  A first-order tangent sweep over the cached pass of update k along a direction d leaves
 // every tangent the mixed sweep reads AND, through three weight-gradient products, H_k d itself: the context keeps one sweep per
 // update along lam_{k+1} (it yields lam_k on the way), a product keeps one per update along u_k (it yields u_{k+1}), and only
-// H_k rho_{k+1} needs a sweep of its own.  For k >= 1 theta_k, u_k and lam_{k+1} are per task (stride P).
-// Workspace: the MetaPlan prefix of mi_trpo_surrogate_steps (theta_k, the StepSet of every update, the query pass), then the
-// KL cotangents of the query pass, lam [K+1][T][P], u [K+1][T][P], 2 K tangent sweeps and the mixed-sweep scratch.
+// H_k rho_{k+1} needs a sweep of its own.  u_k and lam_{k+1} are per task (stride P), and so is theta_k for k >= 1 (theta_stride).
+// Workspace: the StepsPlan of mi_trpo_surrogate_steps as a prefix (theta_k, the StepSet of every update, the query pass, the
+// per-task loss / KL and the fused sweeps' partials), so the surrogate's passes are found where it left them; then the KL cotangents of the query pass, lam [K+1][T][P], u [K+1][T][P], 2 K tangent sweeps and the mixed-sweep scratch.
 struct GenStepsPlan {
   float *k_dmu, *k_d2, *k_d1, *k_pre2, *k_pre1;      // KL primal cotangents on the query pass at theta_K
   float *lam, *u;                                     // [K+1][T][P]
@@ -1888,10 +1672,9 @@ struct GenStepsPlan {
   MixSweep mx;
   size_t bytes;
 };
-static size_t trpo_steps_prefix_bytes(const MetaPlan& pl, int T) { return pl.bytes + align_up((size_t)2 * T * sizeof(float), 256); }
-static void gen_steps_plan(const mi_policy* p, void* ws, int T, int B, int K, MetaPlan& pl, GenStepsPlan& gp) {
-  meta_plan(p, ws, T, B, K, 1, true, pl);
-  PBump b{reinterpret_cast<char*>(ws), trpo_steps_prefix_bytes(pl, T)};       // past the per-task loss / KL of mi_trpo_surrogate_steps
+static void gen_steps_plan(const mi_policy* p, void* ws, int T, int B, int K, StepsPlan& pl, GenStepsPlan& gp) {
+  steps_plan(p, ws, T, B, K, pl);
+  PBump b{reinterpret_cast<char*>(ws), pl.bytes};
   const size_t TB = (size_t)T * B, TP = (size_t)T * p->P;
   gp.k_dmu = b.f(TB * p->A); gp.k_d2 = b.f(TB * p->H2); gp.k_d1 = b.f(TB * p->H1); gp.k_pre2 = b.f(TB * p->H2); gp.k_pre1 = b.f(TB * p->H1);
   gp.lam = b.f(TP * (K + 1)); gp.u = b.f(TP * (K + 1)); gp.rho = b.f(TP); gp.s3 = b.f(TP);
@@ -1903,7 +1686,7 @@ static void gen_steps_plan(const mi_policy* p, void* ws, int T, int B, int K, Me
 }
 extern "C" int mi_trpo_general_steps_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, size_t* bytes) {
   if (!p || !bytes || tasks < 1 || batch < 1 || steps < 1) return MI_ERR_ARG;
-  MetaPlan pl; GenStepsPlan gp;
+  StepsPlan pl; GenStepsPlan gp;
   gen_steps_plan(p, nullptr, tasks, batch, steps, pl, gp);
   *bytes = gp.bytes;
   return MI_OK;
@@ -1939,7 +1722,8 @@ static int steps_args(mi_policy* p, const char* fn, int steps, int tasks, int ba
 
 // After mi_trpo_surrogate_steps(theta, steps, ...) on the same workspace and replays: the KL cotangent pass on the query replay at
 // theta_K (into buffers of its own: the surrogate's query cotangents stay), lam_k for every k, and the tangent sweep of every
-// update along lam_{k+1}.  kl_grad_out (optional, [P]) = d mean_t KL_t / d theta = mean_t lam_0.
+// update along lam_{k+1}.  kl_grad_out (optional, [P]) = d mean_t KL_t / d theta = mean_t lam_0; without it lam_0 is not formed
+// (the products read lam_{k+1} only): update 0 gets its tangent sweep and no weight-gradient products.
 extern "C" int mi_trpo_kl_prepare_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
                                         const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
                                         const float* old_scale, int tasks, int batch, float inner_lr, float* kl_grad_out,
@@ -1949,10 +1733,11 @@ extern "C" int mi_trpo_kl_prepare_steps(mi_policy* p, void* stream, int steps, c
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch, K = steps;
-  const size_t P = p->P, TB = (size_t)T * B, TP = (size_t)T * P;
-  MetaPlan pl; GenStepsPlan gp;
+  const size_t P = p->P, TP = (size_t)T * P;
+  StepsPlan pl; GenStepsPlan gp;
   gen_steps_plan(p, workspace, T, B, K, pl, gp);
   if (gp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(gp.bytes));
+  const SupStack sup{s_states, s_actions, nullptr, s_count};
   const float* thK = pl.theta + (size_t)K * TP;
   float* lamK = gp.lam + (size_t)K * TP;
   PCHK(p, hipMemsetAsync(lamK, 0, TP * sizeof(float), st));
@@ -1965,14 +1750,15 @@ extern "C" int mi_trpo_kl_prepare_steps(mi_policy* p, void* stream, int steps, c
   if (rc) return rc;
   for (int k = K - 1; k >= 0; --k) {
     const float* lam1 = gp.lam + (size_t)(k + 1) * TP;
-    rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, P, s_states + (size_t)k * TB * p->S,
-                   s_actions + (size_t)k * TB * p->A, s_count ? s_count + (size_t)k * T : nullptr, lam1, P, gp.sc[k], pl.hv);
+    const SupRef r = sup_at(p, sup, T, B, k);
+    if (k == 0 && !kl_grad_out)      // (pl.hv takes the sweep's R{d L / d sigma}: scratch)
+      return tan_sweep(p, st, pass_of(pl.st[0]), T, B, pl.theta, theta_stride(p, 0), r.xs, r.as, r.cn, lam1, P, gp.sc[0], pl.hv);
+    rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), r.xs, r.as, r.cn, lam1, P, gp.sc[k], pl.hv);
     if (rc) return rc;
     hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, lam1, P, pl.hv, inner_lr, (int)P,
                        gp.lam + (size_t)k * TP);
     PCHK(p, hipGetLastError());
   }
-  if (!kl_grad_out) return MI_OK;
   hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gp.lam, T, (int)P, 1.f / (float)T,
                      (const float*)nullptr, 0.f, kl_grad_out);
   PCHK(p, hipGetLastError());
@@ -1991,21 +1777,18 @@ extern "C" int mi_trpo_fvp_general_steps(mi_policy* p, void* stream, int steps, 
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch, K = steps;
-  const size_t P = p->P, TB = (size_t)T * B, TP = (size_t)T * P;
-  MetaPlan pl; GenStepsPlan gp;
+  const size_t P = p->P, TP = (size_t)T * P;
+  StepsPlan pl; GenStepsPlan gp;
   gen_steps_plan(p, workspace, T, B, K, pl, gp);
   if (gp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(gp.bytes));
-  auto sup = [&](int k, const float*& xs, const float*& as, const int32_t*& cn) {
-    xs = s_states + (size_t)k * TB * p->S; as = s_actions + (size_t)k * TB * p->A; cn = s_count ? s_count + (size_t)k * T : nullptr;
-  };
+  const SupStack sup{s_states, s_actions, nullptr, s_count};
   // ---- u_0 = v for every task, u_{k+1} = u_k - lr H_k u_k; the sweep along u_k stays for the way back
   hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (size_t)0, pl.g, 0.f, (int)P, gp.u);
   PCHK(p, hipGetLastError());
   for (int k = 0; k < K; ++k) {
-    const float *xs, *as; const int32_t* cn;
-    sup(k, xs, as, cn);
+    const SupRef r = sup_at(p, sup, T, B, k);
     const float* uk = gp.u + (size_t)k * TP;
-    rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, P, xs, as, cn, uk, P, gp.sv[k], pl.hv);
+    rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), r.xs, r.as, r.cn, uk, P, gp.sv[k], pl.hv);
     if (rc) return rc;
     hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, uk, P, pl.hv, inner_lr, (int)P,
                        gp.u + (size_t)(k + 1) * TP);
@@ -2028,13 +1811,13 @@ extern "C" int mi_trpo_fvp_general_steps(mi_policy* p, void* stream, int steps, 
   if (rc) return rc;
   // ---- rho_k = rho_{k+1} - lr (H_k rho_{k+1} + T_k[u_k, lam_{k+1}])
   for (int k = K - 1; k >= 0; --k) {
-    const float *xs, *as; const int32_t* cn;
-    sup(k, xs, as, cn);
+    const SupRef r = sup_at(p, sup, T, B, k);
     const float* th = pl.theta + (size_t)k * TP;
-    rc = hvp_step(p, st, pl, pl.st[k], T, B, th, xs, as, cn, gp.rho, pl.hv);
+    const size_t ts = theta_stride(p, k);
+    rc = hvp_step(p, st, pl, pl.st[k], T, B, th, ts, r, gp.rho, pl.hv);
     if (rc) return rc;
     PCHK(p, hipMemsetAsync(gp.s3, 0, TP * sizeof(float), st));
-    rc = mixed_sweep(p, st, pass_of(pl.st[k]), T, B, th, P, xs, as, cn, gp.lam + (size_t)(k + 1) * TP, P, gp.u + (size_t)k * TP, P,
+    rc = mixed_sweep(p, st, pass_of(pl.st[k]), T, B, th, ts, r.xs, r.as, r.cn, gp.lam + (size_t)(k + 1) * TP, P, gp.u + (size_t)k * TP, P,
                      gp.sc[k], gp.sv[k], gp.mx, gp.s3);
     if (rc) return rc;
     hipLaunchKernelGGL(step_back_kernel, dim3((unsigned)((TP + 255) / 256)), dim3(256), 0, st, gp.rho, pl.hv, gp.s3, inner_lr, TP, gp.rho);

@@ -496,11 +496,11 @@ class PolicyEngine:
         if rc:
             raise _lib.MiError(f'libmi_maml policy error {rc}: {self.lib.mi_policy_last_error(self._h).decode()}')
 
-    def _workspace(self, T, B):
-        # the general (ANIL-TRPO) plan is a superset of the MAML-TRPO one with the same prefix: one buffer serves both, and a
-        # kl_prepare after surrogate finds the surrogate's cached passes where it left them
+    def _workspace(self, T, B, K=1):
+        # the ANIL-TRPO plan of K updates starts with the MAML-TRPO one (which forward and adapt fit into): one buffer serves all,
+        # and a kl_prepare after surrogate finds the surrogate's per-update passes where it left them
         b = C.c_size_t()
-        self._check(self.lib.mi_trpo_general_workspace_bytes(self._h, T, B, C.byref(b)))
+        self._check(self.lib.mi_trpo_general_steps_workspace_bytes(self._h, T, B, K, C.byref(b)))
         if self._ws is None or self._ws.numel() < b.value:
             self._ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
         return self._ws
@@ -576,34 +576,31 @@ class PolicyEngine:
                                              _ptr(adv), _ptr(count), T, B, float(lr), int(head_only), _ptr(out), _ptr(loss), _ptr(ws), ws.numel()))
         return out, loss
 
+    def _trpo_shapes(self, sup, qry, theta=None, old_loc=None, old_scale=None, v=None):
+        """(K, T, B) of a TRPO call, every array checked against them: the library sizes all its reads from these three numbers, so a
+        support replay without its leading [K] axis -- or any other mismatch -- would be read out of bounds on the device."""
+        shp = tuple(sup['states'].shape)
+        if len(shp) != 4 or shp[3] != self.S:
+            raise ValueError(f"sup['states'] must be [K, T, B, {self.S}] (the leading [K] axis also at K = 1), got {shp}")
+        K, T, B = shp[:3]
+        P, A = self.param_count, self.A
+        want = [("sup['actions']", sup['actions'], (K, T, B, A)), ("sup['count']", sup['count'], (K, T)),
+                ("qry['states']", qry['states'], (T, B, self.S)), ("qry['count']", qry['count'], (T,))]
+        if theta is not None:       # surrogate: the advantages and the query actions are read as well
+            want += [("sup['adv']", sup['adv'], (K, T, B)), ("qry['actions']", qry['actions'], (T, B, A)), ("qry['adv']", qry['adv'], (T, B)),
+                     ('theta', theta, (P,))]
+        want += [(n, x, s) for n, x, s in (('old_loc', old_loc, (T, B, A)), ('old_scale', old_scale, (T, A)), ('v', v, (P,))) if x is not None]
+        for name, x, s in want:
+            if tuple(x.shape) != s:
+                raise ValueError(f'{name} must be {list(s)} for K, T, B = {K}, {T}, {B}, got {list(x.shape)}')
+        return K, T, B
+
     @_on_device
     def surrogate(self, theta, sup, qry, old_loc, old_scale, inner_lr, want_grad):
-        """sup/qry: dicts with states [T,B,S], actions [T,B,A], adv [T,B], count [T] int32.  -> (loss, kl, grad or None)."""
-        T, B = sup['states'].shape[0], sup['states'].shape[1]
-        ws = self._workspace(T, B)
-        loss = torch.empty(1, device=self.device)
-        kl = torch.empty(1, device=self.device)
-        grad = torch.empty(self.param_count, device=self.device) if want_grad else None
-        self._check(self.lib.mi_trpo_surrogate(self._h, _stream(self.device), _ptr(theta), _ptr(sup['states']), _ptr(sup['actions']),
-                                               _ptr(sup['adv']), _ptr(sup['count']), _ptr(qry['states']), _ptr(qry['actions']),
-                                               _ptr(qry['adv']), _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B,
-                                               float(inner_lr), _ptr(loss), _ptr(kl), _ptr(grad), _ptr(ws), ws.numel()))
-        return loss, kl, grad
-
-    def _steps_ws(self, T, B, K):
-        # the ANIL-TRPO plan of K updates starts with the MAML-TRPO one: one buffer serves both, and a kl_prepare_steps after
-        # surrogate_steps finds the surrogate's per-update passes where it left them
-        b = C.c_size_t()
-        self._check(self.lib.mi_trpo_general_steps_workspace_bytes(self._h, T, B, K, C.byref(b)))
-        if self._ws is None or self._ws.numel() < b.value:
-            self._ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
-        return self._ws
-
-    @_on_device
-    def surrogate_steps(self, theta, sup, qry, old_loc, old_scale, inner_lr, want_grad):
-        """meta_surrogate_loss with K = sup['states'].shape[0] inner updates (sup arrays carry a leading [K] axis)."""
-        K, T, B = sup['states'].shape[0], sup['states'].shape[1], sup['states'].shape[2]
-        ws = self._steps_ws(T, B, K)
+        """meta_surrogate_loss with K = sup['states'].shape[0] inner updates.  sup: dict with states [K,T,B,S], actions [K,T,B,A],
+        adv [K,T,B], count [K,T] int32 (the leading [K] axis also at K = 1); qry: the same without it.  -> (loss, kl, grad or None)."""
+        K, T, B = self._trpo_shapes(sup, qry, theta=theta, old_loc=old_loc, old_scale=old_scale)
+        ws = self._workspace(T, B, K)
         loss = torch.empty(1, device=self.device)
         kl = torch.empty(1, device=self.device)
         grad = torch.empty(self.param_count, device=self.device) if want_grad else None
@@ -614,9 +611,10 @@ class PolicyEngine:
         return loss, kl, grad
 
     @_on_device
-    def fvp_steps(self, sup, qry, inner_lr, damping, v):
-        K, T, B = sup['states'].shape[0], sup['states'].shape[1], sup['states'].shape[2]
-        ws = self._steps_ws(T, B, K)
+    def fvp(self, sup, qry, inner_lr, damping, v):
+        """Fisher-vector product at the theta of the preceding ``surrogate`` call (same replays)."""
+        K, T, B = self._trpo_shapes(sup, qry, v=v)
+        ws = self._workspace(T, B, K)
         out = torch.empty(self.param_count, device=self.device)
         self._check(self.lib.mi_trpo_fvp_steps(self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']),
                                                _ptr(qry['states']), _ptr(qry['count']), T, B, float(inner_lr), float(damping),
@@ -624,11 +622,11 @@ class PolicyEngine:
         return out
 
     @_on_device
-    def kl_prepare_steps(self, sup, qry, old_loc, old_scale, inner_lr, want_grad=False):
-        """After ``surrogate_steps`` at the same theta and replays: the context of the exact KL Hessian-vector product for
+    def kl_prepare(self, sup, qry, old_loc, old_scale, inner_lr, want_grad=False):
+        """After ``surrogate`` at the same theta and replays: the context of the exact KL Hessian-vector product for
         new != old with K = sup['states'].shape[0] inner updates (ANIL-TRPO).  Returns d mean KL / d theta [P] if ``want_grad``."""
-        K, T, B = sup['states'].shape[0], sup['states'].shape[1], sup['states'].shape[2]
-        ws = self._steps_ws(T, B, K)
+        K, T, B = self._trpo_shapes(sup, qry, old_loc=old_loc, old_scale=old_scale)
+        ws = self._workspace(T, B, K)
         grad = torch.empty(self.param_count, device=self.device) if want_grad else None
         self._check(self.lib.mi_trpo_kl_prepare_steps(
             self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
@@ -636,10 +634,10 @@ class PolicyEngine:
         return grad
 
     @_on_device
-    def fvp_general_steps(self, sup, qry, old_scale, inner_lr, damping, v):
-        """Exact Hessian-vector product of the mean KL at the theta of the preceding ``surrogate_steps`` + ``kl_prepare_steps``."""
-        K, T, B = sup['states'].shape[0], sup['states'].shape[1], sup['states'].shape[2]
-        ws = self._steps_ws(T, B, K)
+    def fvp_general(self, sup, qry, old_scale, inner_lr, damping, v):
+        """Exact Hessian-vector product of the mean KL at the theta of the preceding ``surrogate`` + ``kl_prepare``."""
+        K, T, B = self._trpo_shapes(sup, qry, old_scale=old_scale, v=v)
+        ws = self._workspace(T, B, K)
         out = torch.empty(self.param_count, device=self.device)
         self._check(self.lib.mi_trpo_fvp_general_steps(
             self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
@@ -716,40 +714,6 @@ class PolicyEngine:
                                               _ptr(count), _ptr(done), T, B, kind, int(epochs), float(clip), float(lr), int(head_only),
                                               _ptr(out), _ptr(losses), _ptr(self._ws), self._ws.numel()))
         return out, losses
-
-    @_on_device
-    def kl_prepare(self, theta, sup, qry, old_loc, old_scale, inner_lr, want_grad=False):
-        """After ``surrogate`` at the same theta: the context of the exact KL Hessian-vector product for new != old (ANIL-TRPO).
-        Returns d mean KL / d theta [P] if ``want_grad``."""
-        T, B = sup['states'].shape[0], sup['states'].shape[1]
-        ws = self._workspace(T, B)
-        grad = torch.empty(self.param_count, device=self.device) if want_grad else None
-        self._check(self.lib.mi_trpo_kl_prepare(self._h, _stream(self.device), _ptr(theta), _ptr(sup['states']), _ptr(sup['actions']),
-                                                _ptr(sup['count']), _ptr(qry['states']), _ptr(qry['count']), _ptr(old_loc),
-                                                _ptr(old_scale), T, B, float(inner_lr), _ptr(grad), _ptr(ws), ws.numel()))
-        return grad
-
-    @_on_device
-    def fvp_general(self, theta, sup, qry, old_scale, inner_lr, damping, v):
-        """Exact Hessian-vector product of the mean KL at the theta of the preceding ``surrogate`` + ``kl_prepare`` calls."""
-        T, B = sup['states'].shape[0], sup['states'].shape[1]
-        ws = self._workspace(T, B)
-        out = torch.empty(self.param_count, device=self.device)
-        self._check(self.lib.mi_trpo_fvp_general(self._h, _stream(self.device), _ptr(theta), _ptr(sup['states']), _ptr(sup['actions']),
-                                                 _ptr(sup['count']), _ptr(qry['states']), _ptr(qry['count']), _ptr(old_scale), T, B,
-                                                 float(inner_lr), float(damping), _ptr(v.contiguous()), _ptr(out), _ptr(ws), ws.numel()))
-        return out
-
-    @_on_device
-    def fvp(self, theta, sup, qry, inner_lr, damping, v):
-        """Fisher-vector product at the theta of the preceding ``surrogate`` call (same batches)."""
-        T, B = sup['states'].shape[0], sup['states'].shape[1]
-        ws = self._workspace(T, B)
-        out = torch.empty(self.param_count, device=self.device)
-        self._check(self.lib.mi_trpo_fvp(self._h, _stream(self.device), _ptr(theta), _ptr(sup['states']), _ptr(sup['actions']),
-                                         _ptr(sup['count']), _ptr(qry['states']), _ptr(qry['count']), T, B, float(inner_lr),
-                                         float(damping), _ptr(v.contiguous()), _ptr(out), _ptr(ws), ws.numel()))
-        return out
 
     # ------------------------------------------------------------------------------------------------- step-wise learner
     def _learner_workspace(self, T, B):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Counterpart of the reference's ``rl/anil_trpo.py`` (:104-129) on Particles2D: ``DiagNormalPolicyANIL`` (tanh body, linear head),
 ``fast_adapt_trpo(..., anil=True, first_order=True)`` with the body under no_grad during the inner updates, and
-``meta_optimize_trpo(..., anil=True)`` -- whose KL Hessian-vector product is exact for new != old (mi_trpo_fvp_general;
-mi_trpo_fvp_general_steps with ``--adapt_steps`` > 1).
+``meta_optimize_trpo(..., anil=True)`` -- whose KL Hessian-vector product is exact for new != old
+(``PolicyEngine.fvp_general``, for any ``--adapt_steps``).
 
     python -m exploring_meta_amd.rl.anil_trpo --meta_batch_size 20 --num_iterations 5 [--adapt_steps 2] [--rollout device]
 """

@@ -513,7 +513,7 @@ typedef struct {
  * anything else is MI_ERR_ARG with a text in mi_policy_last_error(NULL), and *out is left alone.  Every mi_policy_* / mi_trpo_* entry
  * below takes every policy of this domain (mi_particles_rollout alone is narrower: see there).
  * Which kernels run: a policy with hidden1 == hidden2 == 100, ReLU, state_size <= 4 (any action_size) takes the fused sweeps of
- * csrc/policy_sweep.h in mi_trpo_surrogate and mi_trpo_fvp (mi_policy_set_fused_fvp(0) switches them off).  Every other shape, and every
+ * csrc/policy_sweep.h in mi_trpo_surrogate_steps and mi_trpo_fvp_steps at steps == 1 (mi_policy_set_fused_fvp(0) switches them off).  Every other shape, and every
  * other entry point at any shape, runs the per-layer kernels of csrc/policy.hip: one dense product per layer and pass for all tasks
  * (operand loads of 16 bytes where the reduction width is a multiple of 4 and at least 16, of 8 bytes where it and its half are even and
  * the operands 8-byte aligned, scalar otherwise) and one weight-gradient launch per layer with the bias as column I of an (I + 1)-wide
@@ -522,9 +522,9 @@ int mi_policy_create(const mi_policy_desc* desc, int device, mi_policy** out);
 void mi_policy_destroy(mi_policy* p);
 const char* mi_policy_last_error(const mi_policy* p);
 int mi_policy_param_count(const mi_policy* p, size_t* n);
-int mi_trpo_workspace_bytes(const mi_policy* p, int tasks, int batch, size_t* bytes);
 
-/* density(state).loc (policies.py:49-52) for acting; theta shared (tstride 0) or one vector per task (tstride = P). */
+/* density(state).loc (policies.py:49-52) for acting; theta shared (tstride 0) or one vector per task (tstride = P).  A workspace that
+ * serves mi_policy_adapt (below) serves this call. */
 int mi_policy_forward(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states, int tasks, int batch,
                       float* loc_out, void* workspace, size_t workspace_bytes);
 
@@ -553,28 +553,16 @@ int mi_particles_rollout(mi_policy* p, void* stream, const float* theta, size_t 
                          int32_t* count, int32_t* ep_len, float* noise_out, void* scratch, size_t scratch_bytes);
 /* trpo_update (rl.py:361-374): theta_out[t] = theta[t] - lr * grad_t( a2c.policy_loss = -mean(log_prob * advantages) ).
  * head_only != 0: the hidden layers run under no_grad (DiagNormalPolicyANIL.turn_off_body_grads, policies.py:100-106,
- * rl.py:381-382), so only sigma and the last Linear are updated (learn2learn maml_update skips None gradients). */
+ * rl.py:381-382), so only sigma and the last Linear are updated (learn2learn maml_update skips None gradients).
+ * Workspace: mi_policy_meta_workspace_bytes(steps = 1, n_batches = 1, second_order = 1) bytes; every mi_trpo_*_workspace_bytes is
+ * at least that. */
 int mi_policy_adapt(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states, const float* actions,
                     const float* adv, const int32_t* count, int tasks, int batch, float lr, int head_only, float* theta_out,
                     float* loss_out, void* workspace, size_t workspace_bytes);
-/* meta_surrogate_loss (rl.py:441-473) with one second-order inner step per task: mean surrogate loss, mean KL(new||old),
- * and (grad_out != NULL) the gradient w.r.t. theta (rl.py:413-416).  old_loc [tasks,batch,A], old_scale [tasks,A] are the
- * stored adapted policies' densities on the query states.  Leaves the context mi_trpo_fvp needs in `workspace`. */
-int mi_trpo_surrogate(mi_policy* p, void* stream, const float* theta, const float* s_states, const float* s_actions,
-                      const float* s_adv, const int32_t* s_count, const float* q_states, const float* q_actions,
-                      const float* q_adv, const int32_t* q_count, const float* old_loc, const float* old_scale, int tasks,
-                      int batch, float inner_lr, float* loss_out, float* kl_out, float* grad_out, void* workspace,
-                      size_t workspace_bytes);
-/* trpo.hessian_vector_product(old_kl, params, damping)(v) (rl.py:417) at the parameters mi_trpo_surrogate was last called
- * with on this workspace (where the adapted policies equal the stored old policies).
- * Calls on ONE mi_policy are ordered by the caller (one stream at a time): the fused product keeps a few arrival counters in device
- * memory owned by the policy object (its last fold also takes the mean over tasks; they are zero between launches). */
-int mi_trpo_fvp(mi_policy* p, void* stream, const float* theta, const float* s_states, const float* s_actions,
-                const int32_t* s_count, const float* q_states, const int32_t* q_count, int tasks, int batch, float inner_lr,
-                float damping, const float* v, float* out, void* workspace, size_t workspace_bytes);
-/* 1 (default): mi_trpo_fvp of a supported policy (ReLU, 100-wide hidden layers: the reference's DiagNormalPolicy defaults,
- * policies.py:30-37) runs as three fused sweeps over the stored passes + three folds (csrc/policy_sweep.h) instead of ~34 per-layer
- * launches; 0: the per-layer path.  Process-wide ablation / test switch; results agree to fp32 rounding. */
+/* 1 (default): mi_trpo_surrogate_steps / mi_trpo_fvp_steps with steps == 1 of a supported policy (ReLU, 100-wide hidden layers: the
+ * reference's DiagNormalPolicy defaults, policies.py:30-37) run as fused sweeps over the stored passes + folds (csrc/policy_sweep.h:
+ * a product is three of each instead of ~34 per-layer launches); 0: the per-layer path.  Process-wide ablation / test switch; results
+ * agree to fp32 rounding. */
 int mi_policy_set_fused_fvp(int on);
 /* Step-wise policy learner (csrc/policy_learner.hip): the mean loc = MLP(theta; states) as a twice-differentiable unit, the policy-side
  * mirror of mi_learner_backward / mi_learner_hvp (learn2learn `learner.adapt(loss)` on a policy: reference misc_scripts/cl_rl.py:71-75).
@@ -659,20 +647,8 @@ int mi_sparse_wgrad_set_split_bf16(int on);
  * the body under no_grad (rl.py:381-382) while meta_surrogate_loss re-adapts clone_module(policy) with every parameter
  * (rl.py:447-453), so at the current parameters new != old and trpo.hessian_vector_product(kl) (rl.py:417) is the EXACT Hessian
  * of the mean KL:  mean_t [ J_t^T Hess KL_t(theta'_t) J_t v - lr T_t[v, grad KL_t(theta'_t)] ] + damping v,  T_t = the third
- * derivative of the inner loss (second-order tangent sweep, policy.hip).
- *   mi_trpo_general_workspace_bytes: workspace for the three calls below (a superset of mi_trpo_workspace_bytes; use it for
- *     mi_trpo_surrogate as well).
- *   mi_trpo_kl_prepare: after mi_trpo_surrogate(theta, ...) on the same workspace; kl_grad_out (or NULL) [P] = d mean KL / d theta.
- *   mi_trpo_fvp_general: the product, any number of times after the two calls above. */
-int mi_trpo_general_workspace_bytes(const mi_policy* p, int tasks, int batch, size_t* bytes);
-int mi_trpo_kl_prepare(mi_policy* p, void* stream, const float* theta, const float* s_states, const float* s_actions,
-                       const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
-                       const float* old_scale, int tasks, int batch, float inner_lr, float* kl_grad_out, void* workspace,
-                       size_t workspace_bytes);
-int mi_trpo_fvp_general(mi_policy* p, void* stream, const float* theta, const float* s_states, const float* s_actions,
-                        const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale, int tasks,
-                        int batch, float inner_lr, float damping, const float* v, float* out, void* workspace,
-                        size_t workspace_bytes);
+ * derivative of the inner loss (second-order tangent sweep, policy.hip): mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps
+ * below, for any number of inner updates. */
 
 /* MAML inner loop of the policy with K updates and the VPG / PPO losses, all tasks per call (core_functions/rl.py:
  * fast_adapt_vpg :231-255 with vpg_a2c_loss :209-228 (dice=False), fast_adapt_ppo :267-318; drivers rl/maml_ppo.py, anil_ppo.py).
@@ -724,10 +700,16 @@ int mi_policy_update(mi_policy* p, void* stream, const float* theta, size_t tstr
                      const float* adv, const int32_t* count, const float* done, int tasks, int batch, int loss_kind, int epochs,
                      float clip, float lr, int head_only, float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes);
 
-/* MAML-TRPO with `steps` >= 1 inner updates (params['adapt_steps'], one support replay per update, rl.py:447-453): the
- * generalisation of mi_trpo_surrogate / mi_trpo_fvp.  Support arrays carry a leading [steps] axis:
+/* MAML-TRPO with `steps` >= 1 inner updates (params['adapt_steps'], one support replay per update, rl.py:447-453).
+ * mi_trpo_surrogate_steps: meta_surrogate_loss (rl.py:441-473) with `steps` second-order inner updates per task: mean surrogate loss,
+ * mean KL(new||old), and (grad_out != NULL) the gradient w.r.t. theta (rl.py:413-416).  old_loc [tasks,batch,A], old_scale [tasks,A]
+ * are the stored adapted policies' densities on the query states.  Support arrays carry a leading [steps] axis (also at steps == 1):
  * s_states [steps,tasks,batch,S], s_actions [steps,tasks,batch,A], s_adv [steps,tasks,batch], s_count [steps,tasks].
- * mi_trpo_fvp_steps must follow mi_trpo_surrogate_steps on the same workspace and replays (it re-uses the saved passes). */
+ * mi_trpo_fvp_steps: trpo.hessian_vector_product(old_kl, params, damping)(v) (rl.py:417) where the adapted policies equal the stored
+ * old ones.  It takes no theta: it must follow mi_trpo_surrogate_steps on the same workspace and replays, and works at the theta of
+ * that call (the surrogate keeps a copy next to the saved passes).
+ * Calls on ONE mi_policy are ordered by the caller (one stream at a time): the fused product keeps a few arrival counters in device
+ * memory owned by the policy object (its last fold also takes the mean over tasks; they are zero between launches). */
 int mi_trpo_steps_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, size_t* bytes);
 int mi_trpo_surrogate_steps(mi_policy* p, void* stream, const float* theta, int steps, const float* s_states,
                             const float* s_actions, const float* s_adv, const int32_t* s_count, const float* q_states,
@@ -738,8 +720,8 @@ int mi_trpo_fvp_steps(mi_policy* p, void* stream, int steps, const float* s_stat
                       const float* q_states, const int32_t* q_count, int tasks, int batch, float inner_lr, float damping,
                       const float* v, float* out, void* workspace, size_t workspace_bytes);
 
-/* ANIL-TRPO with `steps` >= 1 inner updates (rl/anil_trpo.py --adapt_steps K): the exact Hessian of the mean KL for new != old,
- * the generalisation of mi_trpo_kl_prepare / mi_trpo_fvp_general.  With theta_{k+1} = theta_k - lr grad L_k(theta_k),
+/* ANIL-TRPO with `steps` >= 1 inner updates (rl/anil_trpo.py --adapt_steps K): the exact Hessian of the mean KL for new != old
+ * (see above).  With theta_{k+1} = theta_k - lr grad L_k(theta_k),
  * H_k = Hess L_k(theta_k), T_k the third derivative of L_k at theta_k and c = grad KL_t(theta_K):
  *   lam_K = c, lam_k = lam_{k+1} - lr H_k lam_{k+1};   u_0 = v, u_{k+1} = u_k - lr H_k u_k;   rho_K = Hess KL_t(theta_K) u_K,
  *   rho_k = rho_{k+1} - lr H_k rho_{k+1} - lr T_k[u_k, lam_{k+1}];   product = mean_t rho_0 + damping v.
@@ -747,7 +729,7 @@ int mi_trpo_fvp_steps(mi_policy* p, void* stream, int steps, const float* s_stat
  *   mi_trpo_general_steps_workspace_bytes: workspace for the two calls below AND for mi_trpo_surrogate_steps / mi_trpo_fvp_steps
  *     (it starts with the plan mi_trpo_steps_workspace_bytes reports); it keeps two tangent sweeps per inner update.
  *   mi_trpo_kl_prepare_steps: after mi_trpo_surrogate_steps(theta, steps, ...) on the same workspace and replays; the surrogate's
- *     own query cotangents are left alone.  kl_grad_out (or NULL) [P] = d mean KL / d theta = mean_t lam_0.
+ *     own query cotangents are left alone.  kl_grad_out (or NULL: lam_0 is then not formed) [P] = d mean KL / d theta = mean_t lam_0.
  *   mi_trpo_fvp_general_steps: the product, any number of times after the two calls above.
  * steps, tasks, batch >= 1 (MI_ERR_ARG otherwise, before any HIP call).  The number of launches depends on `steps` only. */
 int mi_trpo_general_steps_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, size_t* bytes);

@@ -16,7 +16,7 @@ from exploring_meta_amd import core_functions as cf
 from exploring_meta_amd.core_functions.rl import _SurrogateContext
 from oracle import rl_ref as RL
 from gpu_utils import rel_err, report
-from test_gpu_rl import PARAMS, _theta64, _policy, _policy_tanh, _anil_policy, _replays_tanh
+from test_gpu_rl import PARAMS, _theta64, _policy, _policy_tanh, _anil_policy
 
 pytestmark = pytest.mark.gpu
 
@@ -128,28 +128,6 @@ def test_general_kl_hvp_steps_batched_equals_task_by_task():
     report('general_kl_hvp_steps_batched_vs_single', kl_grad_rel=eg, hvp_rel=eh, task_spread=spread)
     assert spread > 1e-2                 # the tasks' products differ: a stride taken as shared would show
     assert eg < 1e-5 and eh < 1e-5
-
-
-def test_general_kl_steps_entry_points_at_one_step_equal_the_one_step_path():
-    """steps = 1 through mi_trpo_surrogate_steps / mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps equals mi_trpo_surrogate /
-    mi_trpo_kl_prepare / mi_trpo_fvp_general on the same inputs.  tanh: every third-derivative term is live, and both routes run
-    the same per-layer kernels (a ReLU policy's one-step surrogate goes through the fused sweeps, another summation order)."""
-    theta, replays, olds = _replays_tanh(anil=True)
-    pol = _policy_tanh(theta)
-    ctx = _SurrogateContext(replays, [_policy_tanh(o) for o in olds], pol, cf.LinearValue(2, 2), PARAMS)
-    assert ctx.steps == 1
-    th, eng = pol.flat(), ctx.engine
-    v = torch.randn(th.shape, generator=torch.Generator().manual_seed(5), dtype=torch.float64).float().cuda()
-    eng.surrogate(th, ctx.sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, True)
-    g1 = eng.kl_prepare(th, ctx.sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, want_grad=True).cpu().numpy()
-    h1 = eng.fvp_general(th, ctx.sup, ctx.qry, ctx.old_scale, ctx.inner_lr, 1e-5, v).cpu().numpy()
-    sup = {k: ctx.sup[k].unsqueeze(0).contiguous() for k in ('states', 'actions', 'adv', 'count')}
-    eng.surrogate_steps(th, sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, True)
-    gs = eng.kl_prepare_steps(sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, want_grad=True).cpu().numpy()
-    hs = eng.fvp_general_steps(sup, ctx.qry, ctx.old_scale, ctx.inner_lr, 1e-5, v).cpu().numpy()
-    eg, eh = rel_err(gs, g1), rel_err(hs, h1)
-    report('general_kl_steps_at_one_step', kl_grad_rel=eg, hvp_rel=eh)
-    assert eg < 1e-6 and eh < 1e-6
 
 
 def test_meta_optimize_anil_trpo_two_steps_matches_oracle():

@@ -114,25 +114,18 @@ def test_adapt(name, head_only):
 
 def _trpo(name, K, case):
     """surrogate (loss, KL, gradient), a line-search evaluation at a displaced theta, and the product of the mean KL's Hessian with two
-    directions: `fisher` (old = the adapted policy: mi_trpo_fvp*) or `general` (old = the head-only adapted policy: mi_trpo_kl_prepare* +
-    mi_trpo_fvp_general*), through the one-step entry points (K = 1) or the *_steps ones (K = 2)."""
+    directions: `fisher` (old = the adapted policy: mi_trpo_fvp_steps) or `general` (old = the head-only adapted policy:
+    mi_trpo_kl_prepare_steps + mi_trpo_fvp_general_steps), with K = 1 or 2 inner updates on the first K support replays."""
     inp, ref, eng, dev = _setup(name)
     r = ref['trpo', K, case]
     th, qry = dev['theta'], dev['qry']
     old_loc, old_scale = _f(r['old_loc']), _f(r['old_scale'])
-    if K == 1:
-        sup = dev['sup0']
-        surrogate = lambda x, g: eng.surrogate(x, sup, qry, old_loc, old_scale, LR, g)
-        fvp = lambda v: eng.fvp(th, sup, qry, LR, DAMPING, v)
-        prepare = lambda: eng.kl_prepare(th, sup, qry, old_loc, old_scale, LR, want_grad=True)
-        fvp_general = lambda v: eng.fvp_general(th, sup, qry, old_scale, LR, DAMPING, v)
-    else:
-        sup = {k: dev['sup'][k] for k in ('states', 'actions', 'adv', 'count')}
-        assert sup['states'].shape[0] == K
-        surrogate = lambda x, g: eng.surrogate_steps(x, sup, qry, old_loc, old_scale, LR, g)
-        fvp = lambda v: eng.fvp_steps(sup, qry, LR, DAMPING, v)
-        prepare = lambda: eng.kl_prepare_steps(sup, qry, old_loc, old_scale, LR, want_grad=True)
-        fvp_general = lambda v: eng.fvp_general_steps(sup, qry, old_scale, LR, DAMPING, v)
+    sup = {k: dev['sup'][k][:K].contiguous() for k in ('states', 'actions', 'adv', 'count')}
+    assert sup['states'].shape[0] == K
+    surrogate = lambda x, g: eng.surrogate(x, sup, qry, old_loc, old_scale, LR, g)
+    fvp = lambda v: eng.fvp(sup, qry, LR, DAMPING, v)
+    prepare = lambda: eng.kl_prepare(sup, qry, old_loc, old_scale, LR, want_grad=True)
+    fvp_general = lambda v: eng.fvp_general(sup, qry, old_scale, LR, DAMPING, v)
     lc, kc, _ = surrogate(dev['cand'], False)                       # the line search's call: values only
     lc, kc = float(lc), float(kc)
     loss, kl, grad = surrogate(th, True)                            # back at theta: the products below read its passes
@@ -271,12 +264,13 @@ def test_sigma_below_the_clamp():
     old_theta, _ = eng.adapt(th, b['states'], b['actions'], b['adv'], b['count'], lr)
     old_loc = eng.forward(old_theta, qry['states'])
     old_scale = torch.exp(torch.clamp(old_theta[:, :inp['A']], min=float(np.log(1e-6)))).contiguous()
-    sloss, skl, _ = eng.surrogate(th, b, qry, old_loc, old_scale, lr, True)
+    sup = {k: b[k].unsqueeze(0) for k in ('states', 'actions', 'adv', 'count')}      # the support replays carry the leading [K] axis
+    sloss, skl, _ = eng.surrogate(th, sup, qry, old_loc, old_scale, lr, True)
     assert bool(torch.isfinite(sloss).all()) and bool(torch.isfinite(skl).all())
     ol64, os64 = o.adapted_density(theta, [s0], inp['qry'], lr=lr)
     r = o.surrogate(theta, [s0], inp['qry'], ol64, os64, lr=lr)
     vs = PO.directions(inp, r['grad'])
-    hv = [eng.fvp(th, b, qry, lr, DAMPING, _f(v)).clone() for v in vs]
+    hv = [eng.fvp(sup, qry, lr, DAMPING, _f(v)).clone() for v in vs]
     torch.cuda.synchronize()
     eh = []
     for h, v in zip(hv, vs):

@@ -320,7 +320,7 @@ def _anil_policy(theta):
 def test_general_kl_hvp_matches_autograd(act):
     """ANIL-TRPO (rl/anil_trpo.py:129, rl.py:409-473 with anil=True): the old policies were adapted head-only, the surrogate
     re-adapts every parameter, so new != old and trpo.hessian_vector_product(kl) is the exact Hessian of the mean KL --
-    J^T Hess KL J v - lr T[v, grad KL] with the third derivative of the inner loss (mi_trpo_kl_prepare / mi_trpo_fvp_general).
+    J^T Hess KL J v - lr T[v, grad KL] with the third derivative of the inner loss (mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps).
     Checked against double-backward autograd of the oracle's meta_surrogate_loss: the KL value, its gradient and Hessian-vector
     products along a random and a structured direction."""
     activation = torch.tanh if act == 'tanh' else torch.relu
@@ -351,7 +351,7 @@ def test_general_kl_hvp_matches_autograd(act):
     ctx = _SurrogateContext(replays, old_pols, pol, cf.LinearValue(2, 2), PARAMS)
     th = pol.flat()
     l32, k32, _ = ctx.evaluate(th, want_grad=True)
-    g32 = ctx.engine.kl_prepare(th, ctx.sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, want_grad=True)
+    g32 = ctx.engine.kl_prepare(ctx.sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, want_grad=True)
     ctx.general = True
     errs = [rel_err(ctx.fvp(th, v.float().cuda()).cpu().numpy(), r.numpy()) for v, r in zip(vs, refs)]
     # the Fisher form (valid only at new == old) must NOT reproduce these products: the third-order and cotangent terms matter
@@ -1019,7 +1019,8 @@ def test_fused_fvp_sweeps_match_the_per_layer_path_and_the_oracle(case):
     if case == 'ragged_counts':          # shorten some tasks' valid rows: the rows behind count are padding to every kernel
         for d in (ctx.sup, ctx.qry):
             c = d['count'].clone()
-            c[0], c[2] = 97, 33
+            row = c[0] if d is ctx.sup else c          # the support counts carry the leading [K] axis
+            row[0], row[2] = 97, 33
             d['count'] = c.contiguous()
     th = pol.flat()
     g = torch.Generator(device='cuda').manual_seed(11)
@@ -1091,6 +1092,7 @@ def test_fused_policy_sweeps_other_state_and_action_widths(S, A, T, B):
         return d
 
     sup, qry = replay(), replay()
+    sup = {k: x.unsqueeze(0) for k, x in sup.items()}                              # the support replays carry the leading [K] axis
     old_loc = (0.3 * rnd(T, B, A)).contiguous()
     old_scale = (0.5 + torch.rand(T, A, device='cuda', generator=g)).contiguous()
     v = [rnd(P) for _ in range(3)]
@@ -1099,7 +1101,7 @@ def test_fused_policy_sweeps_other_state_and_action_widths(S, A, T, B):
         for fused in (0, 1):
             lib.mi_policy_set_fused_fvp(fused)
             loss, kl, grad = eng.surrogate(theta, sup, qry, old_loc, old_scale, 0.1, True)
-            fv = [eng.fvp(theta, sup, qry, 0.1, 1e-5, x).clone() for x in v]
+            fv = [eng.fvp(sup, qry, 0.1, 1e-5, x).clone() for x in v]
             l2, k2, _ = eng.surrogate(theta + 0.01, sup, qry, old_loc, old_scale, 0.1, False)
             torch.cuda.synchronize()
             out[fused] = (float(loss), float(kl), grad.clone(), fv, float(l2), float(k2))

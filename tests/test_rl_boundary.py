@@ -64,7 +64,9 @@ class FakeEngine:
         T = qry['states'].shape[0]
         loss, kl = 0.0, 0.0
         for t in range(T):
-            new, _ = self._inner(th, sup['states'][t], sup['actions'][t], sup['adv'][t], int(sup['count'][t]), lr, False, True)
+            new = th
+            for k in range(sup['states'].shape[0]):              # the support replays carry a leading [K] axis
+                new, _ = self._inner(new, sup['states'][k, t], sup['actions'][k, t], sup['adv'][k, t], int(sup['count'][k, t]), lr, False, True)
             n = int(qry['count'][t])
             loc, scale = RL.policy_loc_scale(self._p(new), qry['states'][t, :n].double(), self.act)
             ol, os_ = old_loc[t, :n].double(), old_scale[t].double()
@@ -79,13 +81,13 @@ class FakeEngine:
         th = theta.double().clone().requires_grad_(True)
         loss, kl = self._surr(th, sup, qry, old_loc, old_scale, inner_lr)
         grad = torch.autograd.grad(loss, th)[0].float() if want_grad else None
-        self._ctx = (sup, qry, old_loc, old_scale)
+        self._ctx = (theta, old_loc, old_scale)                  # the products work at the theta of the last surrogate call
         return loss.detach().float().reshape(1), kl.detach().float().reshape(1), grad
 
     @torch.enable_grad()
-    def fvp(self, theta, sup, qry, inner_lr, damping, v):
-        th = theta.double().clone().requires_grad_(True)
-        _, kl = self._surr(th, sup, qry, self._ctx[2], self._ctx[3], inner_lr)
+    def fvp(self, sup, qry, inner_lr, damping, v):
+        th = self._ctx[0].double().clone().requires_grad_(True)
+        _, kl = self._surr(th, sup, qry, self._ctx[1], self._ctx[2], inner_lr)
         (g,) = torch.autograd.grad(kl, th, create_graph=True)
         (h,) = torch.autograd.grad(torch.dot(g, v.double()), th)
         return (h + damping * v.double()).float()

@@ -28,7 +28,7 @@ def _free_port():
 
 class _CpuPolicyEngine:
     """The calls _SurrogateContext makes on PolicyEngine (forward / surrogate / fvp), restated with autograd in fp64 on padded
-    [T, B, *] batches with per-task row counts."""
+    [T, B, *] batches with per-task row counts (the support batch with its leading [K] axis, K = 1 here)."""
 
     def __init__(self, RL, shapes):
         self.RL, self.shapes = RL, shapes
@@ -52,6 +52,8 @@ class _CpuPolicyEngine:
         RL = self.RL
         loss, kl = 0.0, 0.0
         T = qry['states'].shape[0]
+        assert sup['states'].shape[0] == 1
+        sup = {k: v[0] for k, v in sup.items()}
         for t in range(T):
             p = self._named(theta)
             ns, nq = int(sup['count'][t]), int(qry['count'][t])
@@ -71,11 +73,11 @@ class _CpuPolicyEngine:
         th = theta.double().clone().requires_grad_(True)
         loss, kl = self._loss_kl(th, sup, qry, old_loc, old_scale, inner_lr)
         grad = torch.autograd.grad(loss, th)[0].float() if want_grad else None
-        self._last = (sup, qry, old_loc, old_scale, inner_lr)
+        self._last = (theta, old_loc, old_scale)                 # the products work at the theta of the last surrogate call
         return loss.detach().float().view(1), kl.detach().float().view(1), grad
 
-    def fvp(self, theta, sup, qry, inner_lr, damping, v):
-        _, _, old_loc, old_scale, _ = self._last
+    def fvp(self, sup, qry, inner_lr, damping, v):
+        theta, old_loc, old_scale = self._last
         th = theta.double().clone().requires_grad_(True)
         _, kl = self._loss_kl(th, sup, qry, old_loc, old_scale, inner_lr)
         g = torch.autograd.grad(kl, th, create_graph=True)[0]
@@ -136,6 +138,7 @@ def _run(rank, world, port, out_path):
     prl.set_device(torch.device('cpu'))
     out = prl.meta_optimize_trpo(PARAMS, pol, prl.LinearValue(2, 2), replays[a:b], old_pols)
     v = torch.sin(torch.arange(flat0.numel(), dtype=torch.float32))
+    out['context'].evaluate(flat0)       # a product works at the theta of the preceding evaluate: back from the line search's last candidate
     fv = out['fvp'](v)
     if world > 1:
         gathered = [torch.zeros_like(flat0) for _ in range(world)]

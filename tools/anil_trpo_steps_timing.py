@@ -3,8 +3,8 @@
 100 steps, device rollouts): milliseconds per kl_prepare, per Hessian-vector product and per whole meta_optimize_trpo(anil=True), the
 launches of one product and the workspace bytes.
 
-K = 1 runs mi_trpo_kl_prepare / mi_trpo_fvp_general (the yardstick: a K-step product does about K times its sweeps); K > 1 runs
-mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps.  `steps_entry_K1` is K = 1 through the K-step entry points.
+Every K runs mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps; K = 1 is the yardstick (a K-step product does about K times its
+sweeps).
 
 Every figure is the median of --repeats wall-clock samples fenced with torch.cuda.synchronize(), after one untimed call.  The
 launches of one product (kernels, and memcpy / memset nodes separately) are counted under torch.profiler; where the profiler records no
@@ -63,7 +63,7 @@ def count_launches(fn):
     return (kernels, copies) if kernels else (None, None)
 
 
-def one_case(K, repeats, dev, steps_entry=False, count=True):
+def one_case(K, repeats, dev, count=True):
     p = dict(anil_trpo.params, meta_batch_size=TASKS, adapt_batch_size=EPISODES, max_path_length=PATH, adapt_steps=K)
     torch.manual_seed(p['seed'])
     policy = cf.DiagNormalPolicyANIL(2, 2, p['fc_neurons']).to(dev)
@@ -76,35 +76,23 @@ def one_case(K, repeats, dev, steps_entry=False, count=True):
     v = torch.randn(theta.shape, generator=torch.Generator().manual_seed(5)).to(dev)
     T, B = ctx.qry['states'].shape[0], ctx.qry['states'].shape[1]
     ws = C.c_size_t()
-    if K == 1 and steps_entry:                                     # one update through the K-step entry points
-        sup = {k: ctx.sup[k].unsqueeze(0).contiguous() for k in ('states', 'actions', 'adv', 'count')}
-        evaluate = lambda: eng.surrogate_steps(theta, sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr, True)
-        prepare = lambda: eng.kl_prepare_steps(sup, ctx.qry, ctx.old_loc, ctx.old_scale, ctx.inner_lr)
-        product = lambda: eng.fvp_general_steps(sup, ctx.qry, ctx.old_scale, ctx.inner_lr, 1e-5, v)
-    else:
-        evaluate = lambda: ctx.evaluate(theta, want_grad=True)
-        prepare = lambda: ctx.prepare_general_kl(theta)
-        product = lambda: ctx.fvp(theta, v)
-    if K == 1 and not steps_entry:
-        eng._check(eng.lib.mi_trpo_general_workspace_bytes(eng._h, T, B, C.byref(ws)))
-    else:
-        eng._check(eng.lib.mi_trpo_general_steps_workspace_bytes(eng._h, T, B, K, C.byref(ws)))
-    evaluate()
-    prep = median_ms(prepare, repeats)
+    eng._check(eng.lib.mi_trpo_general_steps_workspace_bytes(eng._h, T, B, K, C.byref(ws)))
+    ctx.evaluate(theta, want_grad=True)
+    prep = median_ms(lambda: ctx.prepare_general_kl(theta), repeats)
+    product = lambda: ctx.fvp(theta, v)
     prod = median_ms(product, repeats)
     kernels, copies = count_launches(product) if count else (None, None)
-    row = dict(adapt_steps=K, entry='steps' if (K > 1 or steps_entry) else 'one_step', tasks=T, batch=B, repeats=repeats,
+    row = dict(adapt_steps=K, tasks=T, batch=B, repeats=repeats,
                kl_prepare_ms=dict(median=round(prep[0], 3), min=round(prep[1], 3), max=round(prep[2], 3)),
                product_ms=dict(median=round(prod[0], 3), min=round(prod[1], 3), max=round(prod[2], 3)),
                product_launches=dict(kernels=kernels, copies=copies), workspace_bytes=int(ws.value))
-    if not steps_entry:
-        flat0 = policy.flat().clone()
+    flat0 = policy.flat().clone()
 
-        def whole():
-            policy.load_flat(flat0)                                # every sample starts from the same parameters
-            cf.meta_optimize_trpo(p, policy, baseline, replays, olds, anil=True)
-        m = median_ms(whole, max(3, repeats // 4))
-        row['meta_optimize_ms'] = dict(median=round(m[0], 2), min=round(m[1], 2), max=round(m[2], 2))
+    def whole():
+        policy.load_flat(flat0)                                # every sample starts from the same parameters
+        cf.meta_optimize_trpo(p, policy, baseline, replays, olds, anil=True)
+    m = median_ms(whole, max(3, repeats // 4))
+    row['meta_optimize_ms'] = dict(median=round(m[0], 2), min=round(m[1], 2), max=round(m[2], 2))
     return row
 
 
@@ -120,13 +108,11 @@ def main():
     rows = []
     for K in args.adapt_steps:
         rows.append(one_case(K, args.repeats, dev, count=not args.no_count))
-        if K == 1:
-            rows.append(one_case(1, args.repeats, dev, steps_entry=True, count=not args.no_count))
-    base = next((r['product_ms']['median'] for r in rows if r['entry'] == 'one_step'), None)
+    base = next((r['product_ms']['median'] for r in rows if r['adapt_steps'] == 1), None)
     for r in rows:
         r['product_vs_K_one_step'] = None if base is None else round(r['product_ms']['median'] / (r['adapt_steps'] * base), 2)
-        print(f"K {r['adapt_steps']} ({r['entry']}): kl_prepare {r['kl_prepare_ms']['median']:.3f} ms | product {r['product_ms']['median']:.3f} ms "
-              f"(x{r['product_vs_K_one_step']} of K one-step products) | meta_optimize {r.get('meta_optimize_ms', {}).get('median')} ms | "
+        print(f"K {r['adapt_steps']}: kl_prepare {r['kl_prepare_ms']['median']:.3f} ms | product {r['product_ms']['median']:.3f} ms "
+              f"(x{r['product_vs_K_one_step']} of K products at K = 1) | meta_optimize {r.get('meta_optimize_ms', {}).get('median')} ms | "
               f"launches {r['product_launches']} | workspace {r['workspace_bytes'] / 2 ** 20:.1f} MiB")
     print(json.dumps(rows))
 
