@@ -56,9 +56,11 @@ _warned_no_success = [False]
 
 
 def get_ep_successes(episodes, path_length):
-    """reference rl.py:59-72: the number of episodes of the replay with at least one success flag; ``success`` reshaped
-    (path_length, -1).T puts one episode per row (the reference's runner interleaves its workers' steps).  Without a success
-    record the reference prints 'No success metric registered!' and counts 0 -- here the notice is printed once per process."""
+    """reference rl.py:59-72: the number of rows of ``success`` reshaped (path_length, -1).T that hold at least one success flag.
+    The reference's runner flattens its replay episode by episode (runner.py ``flatten_episodes``), so that reshape does NOT put
+    one episode per row: row j collects the steps j, j + episodes, j + 2 episodes, ... of the flat replay.  This is a quirk of
+    the reference, reproduced here as it is (an all-success episode 0 next to an episode 1 without any counts 2).  Without a
+    success record the reference prints 'No success metric registered!' and counts 0 -- here the notice is printed once per process."""
     suc = _as_replay(episodes).get('success')
     if suc is None:
         if not _warned_no_success[0]:
@@ -156,9 +158,7 @@ def normalize(x, epsilon=1e-8):
     return (x - x.mean()) / (x.std(ddof=1) + epsilon) if x.size > 1 else x
 
 
-def _advantages(ep, baseline, gamma, tau, update_vf=True):
-    adv = compute_advantages(baseline, tau, gamma, ep['rewards'], ep['dones'], ep['states'], ep['next_states'], update_vf)
-    return normalize(adv)
+_ch_normalize = normalize                                      # (``_batch_advantages`` has a switch of that name)
 
 
 def _host_replays(replay_list):
@@ -363,29 +363,28 @@ def _stacked_flat_parameters(policies, dev):
     return out
 
 
-def _advantages_device(batch, baseline, gamma, tau):
-    """compute_advantages + ch.normalize (rl.py:95-110,355) of every replay of a device batch in one launch; the baseline is left
-    fitted to the LAST replay, as after the reference's replay-by-replay walk."""
-    from ..engine import gae_advantages
-    adv, wts = gae_advantages(batch['states'], batch['next_states'], batch['rewards'], batch['dones'], batch['count'], gamma, tau,
-                              baseline.reg, normalize=True, want_weights=True)
-    baseline._weight_dev = wts[-1]
-    return adv
+def _replay_batch(replay_list, S, A, dev):
+    """``_device_batch`` that remembers the replays it came from (key 'replays'): the host walk of ``_batch_advantages`` reads their
+    own arrays, not the fp32 batch."""
+    batch = _device_batch(replay_list, S, A, dev)
+    batch['replays'] = replay_list
+    return batch
 
 
-def _replay_on_device(ep, baseline, gamma, tau, S, A, dev, normalize=True, update_vf=True):
-    """One replay as a device batch with its advantages: {states [1,B,S], actions, adv [1,B], count, done} (mi_gae_advantages;
-    update_vf=False evaluates the baseline as last fitted, rl.py:401)."""
-    from ..engine import gae_advantages
-    b = _device_batch([ep], S, A, dev)
-    weights = None
-    if not update_vf:
-        weights = baseline._weight_dev if baseline._weight_dev is not None else torch.from_numpy(np.ascontiguousarray(baseline.weight)).reshape(1, -1)
-    adv, wts = gae_advantages(b['states'], b['next_states'], b['rewards'], b['dones'], b['count'], gamma, tau, baseline.reg,
-                              normalize=normalize, want_weights=True, weights=weights)
-    if update_vf:
-        baseline._weight_dev = wts[-1]
-    return dict(states=b['states'], actions=b['actions'], adv=adv, count=b['count'], done=b['dones'])
+def _stack_batches(sups, qry):
+    """Padded support batches and the query batch, each with its advantages under 'adv' -> (sup, qry) as the engine takes them:
+    sup {states [N,R,B,S], actions [N,R,B,A], adv [N,R,B], done [N,R,B], count [N,R]} (None without support batches), qry the
+    same without the N axis, at their common padded length B -- a shorter batch gets zero rows appended.  Batches of device
+    rollouts have one length: nothing is padded there and the query's tensors are returned as they lie."""
+    B = max(b['states'].shape[1] for b in sups + [qry])
+
+    def fit(b):
+        n = B - b['states'].shape[1]
+        pad = lambda t: t if n == 0 else torch.nn.functional.pad(t, [0, 0] * (t.dim() - 2) + [0, n])
+        return dict(states=pad(b['states']), actions=pad(b['actions']), adv=pad(b['adv']), done=pad(b['dones']), count=b['count'])
+
+    sups, qry = [fit(b) for b in sups], fit(qry)
+    return ({k: torch.stack([b[k] for b in sups]) for k in qry} if sups else None), qry
 
 
 def _gae_max_rows(S):
@@ -397,42 +396,48 @@ def _gae_on_device(dev, S, rows):
     return torch.device(dev).type == 'cuda' and 0 < rows <= _gae_max_rows(S)
 
 
-def _pad(eps_list, advs, S, A, dev):
-    """List of replays (one per task) -> padded device batch {states [T,B,S], actions, adv, count}: assembled on the host, one
-    upload per field."""
-    T = len(eps_list)
-    B = max(int(e['states'].shape[0]) for e in eps_list)
-    if advs and torch.is_tensor(advs[0]) and advs[0].is_cuda:      # advantages already on the device (mi_gae_advantages): stay there
-        b = _device_batch(eps_list, S, A, dev)
-        adv = torch.stack([torch.nn.functional.pad(a.reshape(-1).float(), (0, B - a.numel())) for a in advs]).contiguous()
-        return dict(states=b['states'], actions=b['actions'], adv=adv, count=b['count'], done=b['dones'])
-    st, ac = np.zeros((T, B, S), np.float32), np.zeros((T, B, A), np.float32)
-    ad, cnt, dn = np.zeros((T, B), np.float32), np.zeros(T, np.int32), np.zeros((T, B), np.float32)
-    for t, (e, a) in enumerate(zip(eps_list, advs)):
-        n = int(e['states'].shape[0])
-        st[t, :n] = _np(e['states']).reshape(n, S)
-        ac[t, :n] = _np(e['actions']).reshape(n, A)
-        ad[t, :n] = np.asarray(a, dtype=np.float32).reshape(-1)
-        if 'dones' in e:
-            dn[t, :n] = _np(e['dones']).reshape(n)
-        cnt[t] = n
-    up = lambda x: torch.from_numpy(x).to(dev)
-    return dict(states=up(st), actions=up(ac), adv=up(ad), count=up(cnt), done=up(dn))
+def _batch_advantages(batch, baseline, gamma, tau, normalize=True, fit=True, weights=None):
+    """compute_advantages (+ ch.normalize) (rl.py:95-110,355) of every replay of a padded batch -> (adv [R, B] fp32 on the batch's
+    device, the fitted baseline weights [R, 2S+4] fp64 or None).  THE place that chooses between mi_gae_advantages (one launch for
+    all replays) and the host numpy walk (replays the kernel cannot hold, no GPU).  ``fit``: re-fit the baseline per replay, which
+    leaves it fitted to the LAST one as after the reference's replay-by-replay walk; False evaluates with ``weights`` [R, 2S+4]
+    (each replay its own) or, without them, with the baseline as last fitted (update_vf=False, rl.py:401).  The host walk reads the
+    replays the batch came from (``_replay_batch``; the rows of the batch itself where it carries none) in fp64."""
+    R, B, S = batch['states'].shape
+    dev = batch['states'].device
+    if _gae_on_device(dev, S, B):
+        from ..engine import gae_advantages
+        if not fit and weights is None:
+            weights = baseline._weight_dev if baseline._weight_dev is not None else torch.from_numpy(np.ascontiguousarray(baseline.weight))
+            weights = weights.reshape(1, -1).expand(R, -1)
+        adv, wts = gae_advantages(batch['states'], batch['next_states'], batch['rewards'], batch['dones'], batch['count'], gamma, tau,
+                                  baseline.reg, normalize=normalize, want_weights=True, weights=None if fit else weights)
+        if fit:
+            baseline._weight_dev = wts[-1]
+        return adv, wts
+    if weights is not None:
+        raise ValueError('per-replay baseline weights are taken by mi_gae_advantages only')
+    replays = batch.get('replays') or [_replay_rows(batch, i, n) for i, n in enumerate(batch['count'].tolist())]
+    adv = np.zeros((R, B), np.float32)
+    for i, ep in enumerate(_host_replays(replays)):
+        a = compute_advantages(baseline, tau, gamma, ep['rewards'], ep['dones'], ep['states'], ep['next_states'], fit)
+        adv[i, :a.shape[0]] = (_ch_normalize(a) if normalize else a).reshape(-1)
+    return torch.from_numpy(adv).to(dev), None
 
 
 # ---------------------------------------------------------------------------------------------- reference functions
 def trpo_a2c_loss(episodes, learner, baseline, gamma, tau, update_vf=True):
     """reference rl.py:346-358: -mean(log_prob * normalised advantages).  A value with the bare policy (the gradient path is trpo_update);
     ``learner.log_prob`` of a ``MAML`` wrapper carries a graph while grad mode is on (core_functions/maml.py), and so does this loss."""
-    episodes = _as_replay(episodes)
-    dev = learner.sigma.device
-    if _gae_on_device(dev, learner.input_size, int(episodes['states'].shape[0])):
-        b = _replay_on_device(episodes, baseline, gamma, tau, learner.input_size, learner.output_size, dev, update_vf=update_vf)
-        lp = learner.log_prob(b['states'][0], b['actions'][0])
-        return -(lp * b['adv'][0].reshape(-1, 1).to(lp)).mean()
-    adv = _advantages(episodes, baseline, gamma, tau, update_vf)
-    lp = learner.log_prob(episodes['states'].to(dev), episodes['actions'].to(dev))
-    return -(lp * torch.from_numpy(adv).to(lp)).mean()
+    b = _replay_batch([_as_replay(episodes)], learner.input_size, learner.output_size, learner.sigma.device)
+    adv, _ = _batch_advantages(b, baseline, gamma, tau, fit=update_vf)
+    lp = learner.log_prob(b['states'][0], b['actions'][0])
+    return -(lp * adv[0].reshape(-1, 1).to(lp)).mean()
+
+
+def _trpo_step(eng, inner_lr, head_only):
+    """``step`` of the adapt loop for TRPO: mi_policy_adapt."""
+    return lambda theta, b, adv: eng.adapt(theta, b['states'], b['actions'], adv, b['count'], inner_lr, head_only=head_only)[0]
 
 
 def trpo_update(episodes, learner, baseline, inner_lr, gamma, tau, anil=False, first_order=False):
@@ -440,40 +445,69 @@ def trpo_update(episodes, learner, baseline, inner_lr, gamma, tau, anil=False, f
     second-order dependence on the original parameters is handled inside meta_optimize_trpo's fused calls)."""
     # anil only sets allow_unused (rl.py:371): which parameters move is decided by the policy's own switch -- with
     # DiagNormalPolicyANIL.turn_off_body_grads() the body's gradients are None and maml_update leaves it unchanged.
-    episodes = _as_replay(episodes)
-    head_only = bool(getattr(learner, 'features_no_grad', False))
-    eng = learner.engine()
-    dev = learner.sigma.device
-    if _gae_on_device(dev, learner.input_size, int(episodes['states'].shape[0])):
-        batch = _replay_on_device(episodes, baseline, gamma, tau, learner.input_size, learner.output_size, dev)
-    else:
-        batch = _pad([episodes], [_advantages(episodes, baseline, gamma, tau)], learner.input_size, learner.output_size, dev)
-    theta_new, _ = eng.adapt(learner.flat(), batch['states'], batch['actions'], batch['adv'], batch['count'], inner_lr,
-                             head_only=head_only)
+    b = _replay_batch([_as_replay(episodes)], learner.input_size, learner.output_size, learner.sigma.device)
+    adv, _ = _batch_advantages(b, baseline, gamma, tau)
+    step = _trpo_step(learner.engine(), inner_lr, bool(getattr(learner, 'features_no_grad', False)))
     new = deepcopy(learner)
-    new.load_flat(theta_new[0])
+    new.load_flat(step(learner.flat(), b, adv)[0])
     return new
+
+
+def _adapt_loop(run, step, theta, steps, baseline, gamma, tau, normalize, keep_views=False):
+    """THE adapt loop of fast_adapt_trpo / _vpg / _ppo and their ``*_tasks`` forms: ``steps`` support steps -- ``run(k, theta)`` rolls
+    out a padded batch with the parameters so far ([P] shared, or [R, P]), its advantages are taken with the baseline re-fitted
+    (``_batch_advantages``, ``normalize`` as given), ``step(theta, batch, adv)`` returns the updated parameters [R, P] -- and the
+    query run.  Returns (theta after the last step, the support batches with their advantages under 'adv', the query batch, the
+    baseline weights [R, 2S+4] of the last fit or None, and with ``keep_views`` per replay row the ``Replay`` views of its runs --
+    one read of the row counts per run, the only synchronisation of the loop -- else None)."""
+    sups, wts, views = [], None, None
+    for k in range(steps + 1):
+        batch = run(k, theta)
+        if keep_views:
+            counts = batch['count'].tolist()
+            views = views or [[] for _ in counts]
+            for i, n in enumerate(counts):
+                views[i].append(_replay_rows(batch, i, n))
+        if k == steps:
+            return theta, sups, batch, wts, views
+        batch['adv'], wts = _batch_advantages(batch, baseline, gamma, tau, normalize=normalize)
+        sups.append(batch)
+        theta = step(theta, batch, batch['adv'])
+
+
+class _TaskWalk:
+    """``run`` of the adapt loop for ONE task and any runner with ``run(policy, episodes)``: run 0 acts with ``actor`` itself, run k
+    with a copy of the previous actor that holds theta_k.  ``before_query(actor)`` is called ahead of the last run (ANIL switches
+    the body gradients back on there, rl.py:395-396).  Keeps what the runner returned (``replays``) and the last actor (``current``)."""
+
+    def __init__(self, task, actor, params, before_query=None):
+        self.task, self.current, self.before_query = task, actor, before_query
+        self.steps, self.episodes, self.replays = params['adapt_steps'], params['adapt_batch_size'], []
+
+    def __call__(self, k, theta):
+        if k:
+            self.current = deepcopy(self.current)
+            self.current.load_flat(theta[0])
+        if k == self.steps and self.before_query is not None:
+            self.before_query(self.current)
+        self.replays.append(self.task.run(self.current, episodes=self.episodes))
+        pol = _unwrap(self.current)
+        return _replay_batch([_as_replay(self.replays[-1])], pol.input_size, pol.output_size, pol.sigma.device)
 
 
 def fast_adapt_trpo(task, learner, baseline, params, anil=False, first_order=False, render=False):
     """reference rl.py:377-406.  ``task.run(policy, episodes=n)`` returns a replay (dict or cherry-style object, ``_as_replay``).
     ``learner``: the policy itself or a ``MAML`` wrapper around it (rl/anil_trpo.py:84 wraps; rl.py:382,396 reach the policy as
     ``learner.module``)."""
-    task_replay = []
     if anil:                                                   # rl.py:381-382
         _unwrap(learner).turn_off_body_grads()
-    for step in range(params['adapt_steps']):
-        support_episodes = task.run(learner, episodes=params['adapt_batch_size'])
-        task_replay.append(support_episodes)
-        learner = trpo_update(support_episodes, learner, baseline, params['inner_lr'], params['gamma'], params['tau'],
-                              anil=anil, first_order=first_order)
-    if anil:                                                   # rl.py:395-396
-        _unwrap(learner).turn_on_body_grads()
-    query_episodes = task.run(learner, episodes=params['adapt_batch_size'])
-    task_replay.append(query_episodes)
-    valid_loss = trpo_a2c_loss(query_episodes, learner, baseline, params['gamma'], params['tau'], update_vf=False)
-    query_rew = _as_replay(query_episodes)['rewards'].sum().item() / params['adapt_batch_size']                    # rl.py:403
-    query_success_rate = get_ep_successes(query_episodes, params.get('max_path_length')) / params['adapt_batch_size']  # rl.py:404
+    walk = _TaskWalk(task, learner, params, (lambda actor: _unwrap(actor).turn_on_body_grads()) if anil else None)
+    step = _trpo_step(learner.engine(), params['inner_lr'], bool(getattr(learner, 'features_no_grad', False)))
+    _adapt_loop(walk, step, learner.flat(), params['adapt_steps'], baseline, params['gamma'], params['tau'], True)
+    learner, task_replay = walk.current, walk.replays
+    valid_loss = trpo_a2c_loss(task_replay[-1], learner, baseline, params['gamma'], params['tau'], update_vf=False)
+    query_rew = _as_replay(task_replay[-1])['rewards'].sum().item() / params['adapt_batch_size']                    # rl.py:403
+    query_success_rate = get_ep_successes(task_replay[-1], params.get('max_path_length')) / params['adapt_batch_size']  # rl.py:404
     return learner, valid_loss, task_replay, query_rew, query_success_rate
 
 
@@ -511,6 +545,30 @@ def rollout_tasks(policies_or_theta, goals, ids, seed, episodes, max_path_length
     return [_replay_rows(out, i, n) for i, n in enumerate(out['count'].tolist())]
 
 
+def _rollout_run(name, pol, goals, params, seed, first_id, stride=None):
+    """``run`` of the adapt loop for ALL tasks on device rollouts -> (tasks, run): run k is ONE mi_particles_rollout call with the
+    tasks' parameters so far, task i under rollout id ``_task_rollout_ids(...)[k][i]``.  The goals and the ids of all
+    (adapt_steps + 1) x tasks runs travel once, in kernel arguments (no pageable copy, no synchronisation).  Replays longer than
+    mi_gae_advantages takes are refused up front: ``name`` keeps them on the device."""
+    from ..engine import upload_int32, _as_i32
+    eng, dev = pol.engine(), pol.sigma.device
+    goals = np.ascontiguousarray(np.asarray(goals, dtype=np.float32).reshape(-1, 2))
+    T, K, E, L = goals.shape[0], params['adapt_steps'], params['adapt_batch_size'], params['max_path_length']
+    if T < 1:
+        raise ValueError(f'{name}: no goals')
+    if not _gae_on_device(dev, pol.input_size, E * L):
+        raise ValueError(f'{name} keeps replays of {E} x {L} rows on the device; mi_gae_advantages takes at most '
+                         f'{_gae_max_rows(pol.input_size)} rows')
+    goals_dev = upload_int32(goals.view(np.int32).reshape(-1).tolist(), dev).view(torch.float32).view(T, 2)
+    halves = []
+    for row in _task_rollout_ids(int(first_id), T, K, stride):
+        for r in row:
+            r &= 2 ** 64 - 1
+            halves += [_as_i32(r & 0xffffffff), _as_i32(r >> 32)]
+    ids = upload_int32(halves, dev).view(torch.int64).view(K + 1, T)
+    return T, lambda k, theta: eng.rollout(theta, goals_dev, ids[k], seed, E, L)
+
+
 def fast_adapt_trpo_tasks(goals, policy, baseline, params, seed, first_id, anil=False, first_order=False):
     """``fast_adapt_trpo`` (reference rl.py:377-406) for ALL tasks of a meta-batch at once on device rollouts: per adapt step one
     rollout call, one mi_gae_advantages launch and one mi_policy_adapt call over all tasks, then one query rollout with per-task
@@ -518,53 +576,33 @@ def fast_adapt_trpo_tasks(goals, policy, baseline, params, seed, first_id, anil=
     run k (the support steps, then the query) uses rollout id ``first_id + i * (adapt_steps + 1) + k`` -- what task i gets from
     ``fast_adapt_trpo`` with ``Particles2DRunner(goal, L, rollout='device', seed=seed, first_id=first_id + i * (adapt_steps + 1))``.
     ``baseline`` is left as after that task-by-task walk: fitted to the last task's last support replay."""
-    from ..engine import gae_advantages
     pol = _unwrap(policy)
-    eng, dev = pol.engine(), pol.sigma.device
-    goals = np.asarray(goals, dtype=np.float32).reshape(-1, 2)
-    T, K, E, L = goals.shape[0], params['adapt_steps'], params['adapt_batch_size'], params['max_path_length']
-    S, A = pol.input_size, pol.output_size
-    if not _gae_on_device(dev, S, E * L):
-        raise ValueError(f'fast_adapt_trpo_tasks keeps replays of {E} x {L} rows on the device; mi_gae_advantages takes at most '
-                         f'{_gae_max_rows(S)} rows')
+    T, run = _rollout_run('fast_adapt_trpo_tasks', pol, goals, params, seed, first_id)
+    eng, A, E = pol.engine(), pol.output_size, params['adapt_batch_size']
     gamma, tau = params['gamma'], params['tau']
     if anil:                                                   # rl.py:381-382: the inner loop moves the head only
         pol.turn_off_body_grads()
     head_only = bool(getattr(pol, 'features_no_grad', False))
     if anil:                                                   # rl.py:395-396
         pol.turn_on_body_grads()
-    theta, wts = pol.flat(), None
-    replays = [[] for _ in range(T)]
-    for k in range(K + 1):
-        out = eng.rollout(theta, goals, [first_id + i * (K + 1) + k for i in range(T)], seed, E, L)
-        counts = out['count'].tolist()                         # (the one synchronisation of the step)
-        for i, n in enumerate(counts):
-            replays[i].append(_replay_rows(out, i, n))
-        if k == K:
-            break
-        adv, wts = gae_advantages(out['states'], out['next_states'], out['rewards'], out['dones'], out['count'], gamma, tau, baseline.reg,
-                                  normalize=True, want_weights=True)
-        theta, _ = eng.adapt(theta, out['states'], out['actions'], adv, out['count'], params['inner_lr'], head_only=head_only)
+    theta, _, out, wts, replays = _adapt_loop(run, _trpo_step(eng, params['inner_lr'], head_only), pol.flat(), params['adapt_steps'],
+                                              baseline, gamma, tau, True, keep_views=True)
     # the query replay's loss with each task's own baseline, as fitted to its last support replay (update_vf=False, rl.py:401)
-    if wts is None:
-        wts = torch.from_numpy(np.ascontiguousarray(baseline.weight)).reshape(1, -1).repeat(T, 1)
-    else:
-        baseline._weight_dev = wts[-1]
-    adv = gae_advantages(out['states'], out['next_states'], out['rewards'], out['dones'], out['count'], gamma, tau, baseline.reg,
-                         normalize=True, weights=wts)
+    adv, _ = _batch_advantages(out, baseline, gamma, tau, fit=False, weights=wts)
     thetas = theta if theta.dim() == 2 else theta.unsqueeze(0).expand(T, -1)
     loc = eng.forward(theta, out['states'])
     scale = torch.exp(torch.clamp(thetas[:, :A], min=float(np.log(1e-6))))
     query_rew = (out['rewards'].sum(dim=1) / E).tolist()
     results = []
-    for i, n in enumerate(counts):
+    for i, task_replay in enumerate(replays):
+        n = task_replay[-1]['states'].shape[0]
         learner = deepcopy(pol)
         learner.load_flat(thetas[i].contiguous())
         # trpo_a2c_loss's own expressions on the task's rows (rl.py:346-358)
         lp = torch.distributions.Normal(loc=loc[i, :n], scale=scale[i]).log_prob(out['actions'][i, :n]).mean(dim=1, keepdim=True)
         valid_loss = -(lp * adv[i, :n].reshape(-1, 1)).mean()
-        suc = get_ep_successes(replays[i][-1], params.get('max_path_length')) / E
-        results.append((learner, valid_loss, replays[i], query_rew[i], suc))
+        suc = get_ep_successes(task_replay[-1], params.get('max_path_length')) / E
+        results.append((learner, valid_loss, task_replay, query_rew[i], suc))
     return results
 
 
@@ -579,40 +617,17 @@ class _SurrogateContext:
         if K < 1 or any(len(r) != K + 1 for r in iter_replays):
             raise ValueError('every task needs the same number (>= 1) of support replays plus one query replay')
         self.steps = K
-        adv = lambda e: _advantages(e, baseline, params['gamma'], params['tau'])
         nT = len(iter_replays)
         flat = [r[k] for k in range(K + 1) for r in iter_replays]                    # [k][task]
-        if _gae_on_device(dev, S, max(int(r['states'].shape[0]) for r in flat)):
-            # advantages of all (K + 1) x tasks replays in ONE launch, the batch assembled on the device (the reference re-fits the
-            # baseline and re-runs GAE per task and replay on the CPU at every evaluation of the surrogate, rl.py:444-465)
-            batch = _device_batch(flat, S, A, dev)
-            advs = _advantages_device(batch, baseline, params['gamma'], params['tau'])
-            part = lambda k: dict(states=batch['states'][k * nT:(k + 1) * nT], actions=batch['actions'][k * nT:(k + 1) * nT],
-                                  adv=advs[k * nT:(k + 1) * nT], count=batch['count'][k * nT:(k + 1) * nT],
-                                  done=batch['dones'][k * nT:(k + 1) * nT])
-            self.qry = part(K)
-            # the K support replays are the batch's first K x tasks rows: [K, T, ...] views, no copy
-            rows = dict(states=batch['states'], actions=batch['actions'], adv=advs, count=batch['count'])
-            self.sup = {k: v[:K * nT].unflatten(0, (K, nT)) for k, v in rows.items()}
-        else:
-            host = _host_replays(flat)                               # one D2H copy per field
-            sups = []
-            for k in range(K):                                       # the reference walks task by task, replay by replay;
-                eps = host[k * nT:(k + 1) * nT]                      # the baseline is re-fitted per replay, so the order is immaterial
-                sups.append(_pad(eps, [adv(e) for e in eps], S, A, dev))
-            qry_eps = host[K * nT:]
-            self.qry = _pad(qry_eps, [adv(e) for e in qry_eps], S, A, dev)
-            B = max(d['states'].shape[1] for d in sups + [self.qry])
-            for d in sups + [self.qry]:                          # one common padded length
-                pad = B - d['states'].shape[1]
-                if pad:
-                    d['states'] = torch.nn.functional.pad(d['states'], (0, 0, 0, pad))
-                    d['actions'] = torch.nn.functional.pad(d['actions'], (0, 0, 0, pad))
-                    d['adv'] = torch.nn.functional.pad(d['adv'], (0, pad))
-            self.sup = {k: torch.stack([d[k] for d in sups]) for k in ('states', 'actions', 'adv', 'count')}       # [K, T, ...]
-        for d in (self.sup, self.qry):
-            for k in ('states', 'actions', 'adv', 'count'):
-                d[k] = d[k].contiguous()
+        # advantages of all (K + 1) x tasks replays in ONE launch, the batch assembled on the device (the reference re-fits the
+        # baseline and re-runs GAE per task and replay on the CPU at every evaluation of the surrogate, rl.py:444-465); the order
+        # of the replays is immaterial to them, the baseline being re-fitted per replay
+        batch = _replay_batch(flat, S, A, dev)
+        advs, _ = _batch_advantages(batch, baseline, params['gamma'], params['tau'])
+        rows = dict(states=batch['states'], actions=batch['actions'], adv=advs, count=batch['count'], done=batch['dones'])
+        self.qry = {k: v[K * nT:] for k, v in rows.items()}
+        # the K support replays are the batch's first K x tasks rows: [K, T, ...] views, no copy (leading rows: contiguous as they lie)
+        self.sup = {k: v[:K * nT].unflatten(0, (K, nT)) for k, v in rows.items() if k != 'done'}
         self.engine = policy.engine()
         # the stored old policies' parameters as ONE gather ([tasks, P], engine order: sigma first) and their scales from its first columns
         # (per-policy flat() / clamp / exp launches were ~80 of the ~100 launches of this constructor)
@@ -793,85 +808,49 @@ class _PolicyMetaLoss(torch.autograd.Function):
         return (None, None, None) + tuple(outs)
 
 
-def _stack(replays, advs, S, A, dev):
-    """Support replays of ONE task -> {states [NB,1,B,S], ...} with a common padded length."""
-    batches = [_pad([e], [a], S, A, dev) for e, a in zip(replays, advs)]
-    B = max(b['states'].shape[1] for b in batches)
-    def padto(t, dim):
-        n = B - t.shape[dim]
-        if n == 0:
-            return t
-        pad = [0, 0] * (t.dim() - 1 - dim) + [0, n]
-        return torch.nn.functional.pad(t, pad)
-    out = {k: torch.stack([padto(b[k], 1) if k != 'count' else b[k] for b in batches]).contiguous()
-           for k in ('states', 'actions', 'adv', 'count', 'done')}
-    return out, B
-
-
-def _replay_meta(pol, support, sup_adv, query, q_adv, inner_lr, loss, clip, epochs, anil, first_order, with_grad):
-    """One task through mi_policy_meta_batch: (validation loss [1], adapted theta [P], grad [P] or None)."""
-    S, A, dev = pol.input_size, pol.output_size, pol.sigma.device
-    sup, B1 = _stack(support, sup_adv, S, A, dev) if support else (None, 0)
-    qry = _pad([query], [q_adv], S, A, dev)
-    B = max(B1, qry['states'].shape[1])
-    def fit(d, dim):
-        for k in ('states', 'actions', 'adv', 'done'):
-            n = B - d[k].shape[dim]
-            if n:
-                pad = [0, 0] * (d[k].dim() - 1 - dim) + [0, n]
-                d[k] = torch.nn.functional.pad(d[k], pad).contiguous()
-        return d
-    if sup is not None:
-        sup = fit(sup, 2)
-    qry = fit(qry, 1)
-    step_batch = [b for b in range(len(support)) for _ in range(epochs)]
-    lt, th, g = pol.engine().meta_batch(pol.flat(), sup, qry, step_batch, inner_lr, loss=loss, clip=clip, head_only=anil,
-                                        first_order=first_order, with_grad=with_grad)
-    return lt, th[0], g
-
-
-def _adapt_and_validate(task, learner, baseline, params, algo, anil, first_order, dice=False):
-    pol = _unwrap(learner)
-    gamma, tau = params['gamma'], params['tau']
+def _adapt_and_validate(run, pol, baseline, params, algo, anil, first_order, dice, keep_views=False):
+    """fast_adapt_vpg / fast_adapt_ppo (reference rl.py:231-255,267-318) for the R replay rows ``run`` rolls out -- all tasks of a
+    meta-batch (``_rollout_run``) or one (``_TaskWalk``): the adapt loop with one mi_policy_update call per step (``ppo_epochs``
+    epochs for PPO), the query's advantages (fitted like the others; normalised for PPO only, vpg_a2c_loss does not, rl.py:217),
+    then ONE mi_policy_meta_batch call from the shared parameters over the support batches and the query.  Returns (the summed
+    validation loss, 0-dim, whose ``.backward()`` accumulates the summed meta-gradient; the losses [R]; the adapted parameters the
+    query was rolled out with, [R, P] or the shared [P] without adapt steps; the query batch; the ``Replay`` views or None)."""
+    eng = pol.engine()
+    gamma, tau, lr = params['gamma'], params['tau'], params['inner_lr']
     epochs = params['ppo_epochs'] if algo == 'ppo' else 1
     clip = params.get('ppo_clip_ratio', 0.1)
     kind = 'ppo' if algo == 'ppo' else ('dice' if dice else 'a2c')
-
-    def adv_of(ep):
-        n = int(ep['states'].shape[0])
-        if _gae_on_device(pol.sigma.device, pol.input_size, n):         # stays on the device: [n] fp32
-            return _replay_on_device(ep, baseline, gamma, tau, pol.input_size, pol.output_size, pol.sigma.device,
-                                     normalize=(algo == 'ppo'))['adv'][0, :n]
-        a = compute_advantages(baseline, tau, gamma, ep['rewards'], ep['dones'], ep['states'], ep['next_states'])
-        return normalize(a) if algo == 'ppo' else a                     # vpg_a2c_loss does not normalise (rl.py:217)
-
-    if anil:
-        pol.turn_off_body_grads()
-    support, sup_adv, current = [], [], pol
-    for step in range(params['adapt_steps']):
-        ep = _as_replay(task.run(current, episodes=params['adapt_batch_size']))
-        support.append(ep)
-        sup_adv.append(adv_of(ep))
-        # parameters after the updates so far (the rollouts of the next step / the query need them); value of the loss unused
-        _, theta_k, _ = _replay_meta(pol, support, sup_adv, ep, sup_adv[-1], params['inner_lr'], kind, clip, epochs, anil, first_order, False)
-        current = deepcopy(pol)
-        current.load_flat(theta_k)
-    if anil:
-        pol.turn_on_body_grads()
-    query = _as_replay(task.run(current, episodes=params['adapt_batch_size']))
+    step = lambda theta, b, adv: eng.update(theta, b['states'], b['actions'], adv, b['count'], lr, loss=kind, epochs=epochs, clip=clip,
+                                            done=b['dones'] if kind == 'dice' else None, head_only=bool(anil))[0]
+    theta0 = pol.flat()
+    theta, sups, qry, _, views = _adapt_loop(run, step, theta0, params['adapt_steps'], baseline, gamma, tau, algo == 'ppo', keep_views)
+    qry['adv'], _ = _batch_advantages(qry, baseline, gamma, tau, normalize=(algo == 'ppo'))
+    sup, engine_qry = _stack_batches(sups, qry)
+    step_batch = [b for b in range(len(sups)) for _ in range(epochs)]
     need = torch.is_grad_enabled() and any(q.requires_grad for q in pol.parameters())
-    lt, _, grad = _replay_meta(pol, support, sup_adv, query, adv_of(query), params['inner_lr'], kind, clip, epochs, anil, first_order, need)
+    lt, _, grad = eng.meta_batch(theta0, sup, engine_qry, step_batch, lr, loss=kind, clip=clip, head_only=bool(anil), first_order=first_order,
+                                 with_grad=need)
+    total = lt.sum()
     if need:
         eparams = pol._engine_params()
-        valid_loss = _PolicyMetaLoss.apply(lt[0], grad, [q.shape for q in eparams], *eparams)
-    else:
-        valid_loss = lt[0]
+        total = _PolicyMetaLoss.apply(total, grad, [q.shape for q in eparams], *eparams)
+    return total, lt, theta, qry, views
+
+
+def _adapt_task_walk(task, learner, baseline, params, algo, anil, first_order, dice=False):
+    """``_adapt_and_validate`` for one task and any runner -> (valid_loss, query reward, success rate)."""
+    pol = _unwrap(learner)
+    if anil:
+        pol.turn_off_body_grads()
+    walk = _TaskWalk(task, pol, params, (lambda actor: pol.turn_on_body_grads()) if anil else None)
+    valid_loss, _, _, _, _ = _adapt_and_validate(walk, pol, baseline, params, algo, anil, first_order, dice)
+    query = _as_replay(walk.replays[-1])
     rew = query['rewards'].sum().item() / params['adapt_batch_size']
     suc = get_ep_successes(query, params.get('max_path_length')) / params['adapt_batch_size']                          # rl.py:252,315
     # learn2learn's learner.adapt updates the learner in place; here the base module is shared by every clone, so the adapted
     # parameters are handed over on the side (evaluate() below acts with them)
     try:
-        learner._adapted_policy = current
+        learner._adapted_policy = walk.current
     except Exception:
         pass
     return valid_loss, rew, suc
@@ -882,7 +861,7 @@ def fast_adapt_vpg(task, learner, baseline, params, anil=False, first_order=Fals
     gradient (second order unless first_order) into the policy's parameters.  ``dice`` (not a parameter of the reference's
     fast_adapt_vpg, whose calls leave vpg_a2c_loss at dice=False): every vpg_a2c_loss of the adaptation -- the adapt losses and
     the validation loss -- uses the DiCE objective of rl.py:219-226."""
-    return _adapt_and_validate(task, learner, baseline, params, 'vpg', anil, first_order, dice=dice)
+    return _adapt_task_walk(task, learner, baseline, params, 'vpg', anil, first_order, dice=dice)
 
 
 def vpg_a2c_loss(episodes, learner, baseline, gamma, tau, dice=False):
@@ -903,7 +882,7 @@ def vpg_a2c_loss(episodes, learner, baseline, gamma, tau, dice=False):
 
 def fast_adapt_ppo(task, learner, baseline, params, anil=False, render=False):
     """reference rl.py:267-318: ppo_epochs clipped-surrogate updates per adapt step (second order, as learner.adapt defaults)."""
-    return _adapt_and_validate(task, learner, baseline, params, 'ppo', anil, False)
+    return _adapt_task_walk(task, learner, baseline, params, 'ppo', anil, False)
 
 
 def single_ppo_update(episodes, learner, baseline, params, anil=False):
@@ -912,14 +891,9 @@ def single_ppo_update(episodes, learner, baseline, params, anil=False):
     parameters are updated in place -- step size ``learner.lr`` (the MAML wrapper's, as ``learner.adapt`` uses it) or
     ``params['inner_lr']`` -- and the loss before the update is returned.  As in ``trpo_update``, ``anil`` only allows unused
     parameters (rl.py:335); whether the body moves is the policy's own switch (``turn_off_body_grads``)."""
-    episodes = _as_replay(episodes)
     pol = _unwrap(learner)
-    S, A, dev = pol.input_size, pol.output_size, pol.sigma.device
-    gamma, tau = params['gamma'], params['tau']
-    if _gae_on_device(dev, S, int(episodes['states'].shape[0])):
-        b = _replay_on_device(episodes, baseline, gamma, tau, S, A, dev)
-    else:
-        b = _pad([episodes], [_advantages(episodes, baseline, gamma, tau)], S, A, dev)
+    b = _replay_batch([_as_replay(episodes)], pol.input_size, pol.output_size, pol.sigma.device)
+    b['adv'], _ = _batch_advantages(b, baseline, params['gamma'], params['tau'])
     lr = learner.lr if isinstance(getattr(learner, 'lr', None), (int, float)) else params['inner_lr']
     theta, loss = pol.engine().update(pol.flat(), b['states'], b['actions'], b['adv'], b['count'], lr, loss='ppo', epochs=1,
                                       clip=params.get('ppo_clip_ratio', 0.1), head_only=bool(getattr(pol, 'features_no_grad', False)))
@@ -947,61 +921,14 @@ def _task_rollout_ids(first_id, tasks, adapt_steps, stride=None):
 
 
 def _adapt_tasks(goals, policy, baseline, params, seed, first_id, algo, anil, first_order, dice, want_replays, stride=None):
-    from ..engine import gae_advantages, upload_int32, _as_i32
+    """``_adapt_and_validate`` for all tasks on device rollouts -> ``AdaptedTasks``."""
     pol = _unwrap(policy)
-    eng, dev = pol.engine(), pol.sigma.device
-    goals = np.ascontiguousarray(np.asarray(goals, dtype=np.float32).reshape(-1, 2))
-    T, K, E, L = goals.shape[0], params['adapt_steps'], params['adapt_batch_size'], params['max_path_length']
-    S, A = pol.input_size, pol.output_size
-    name = 'fast_adapt_ppo_tasks' if algo == 'ppo' else 'fast_adapt_vpg_tasks'
-    if T < 1:
-        raise ValueError(f'{name}: no goals')
-    if not _gae_on_device(dev, S, E * L):
-        raise ValueError(f'{name} keeps replays of {E} x {L} rows on the device; mi_gae_advantages takes at most '
-                         f'{_gae_max_rows(S)} rows')
-    gamma, tau, lr = params['gamma'], params['tau'], params['inner_lr']
-    epochs = params['ppo_epochs'] if algo == 'ppo' else 1
-    clip = params.get('ppo_clip_ratio', 0.1)
-    kind = 'ppo' if algo == 'ppo' else ('dice' if dice else 'a2c')
-    # goals and the ids of all (K + 1) x T runs travel once, in kernel arguments (no pageable copy, no synchronisation)
-    goals_dev = upload_int32(goals.view(np.int32).reshape(-1).tolist(), dev).view(torch.float32).view(T, 2)
-    halves = []
-    for row in _task_rollout_ids(int(first_id), T, K, stride):
-        for r in row:
-            r &= 2 ** 64 - 1
-            halves += [_as_i32(r & 0xffffffff), _as_i32(r >> 32)]
-    ids = upload_int32(halves, dev).view(torch.int64).view(K + 1, T)
-    theta0 = pol.flat()
-    theta, sups = theta0, []
-    replays = [[] for _ in range(T)] if want_replays else None
-    for k in range(K + 1):
-        out = eng.rollout(theta, goals_dev, ids[k], seed, E, L)
-        if want_replays:                                       # (the one synchronisation of the run)
-            for i, n in enumerate(out['count'].tolist()):
-                replays[i].append(_replay_rows(out, i, n))
-        # always fitted, the query included (_adapt_and_validate); vpg_a2c_loss does not normalise (rl.py:217)
-        adv, wts = gae_advantages(out['states'], out['next_states'], out['rewards'], out['dones'], out['count'], gamma, tau, baseline.reg,
-                                  normalize=(algo == 'ppo'), want_weights=True)
-        batch = dict(states=out['states'], actions=out['actions'], adv=adv, count=out['count'], done=out['dones'])
-        if k == K:
-            break
-        sups.append(batch)
-        theta, _ = eng.update(theta, out['states'], out['actions'], adv, out['count'], lr, loss=kind, epochs=epochs, clip=clip,
-                              done=out['dones'] if kind == 'dice' else None, head_only=bool(anil))
-    baseline._weight_dev = wts[-1]                             # as after the task-by-task walk: the last task's query replay
-    sup = {key: torch.stack([b[key] for b in sups]) for key in ('states', 'actions', 'adv', 'count', 'done')} if K else None
-    step_batch = [b for b in range(K) for _ in range(epochs)]
-    need = torch.is_grad_enabled() and any(q.requires_grad for q in pol.parameters())
-    lt, _, grad = eng.meta_batch(theta0, sup, batch, step_batch, lr, loss=kind, clip=clip, head_only=bool(anil), first_order=first_order,
-                                 with_grad=need)
-    total = lt.sum()
-    if need:
-        eparams = pol._engine_params()
-        total = _PolicyMetaLoss.apply(total, grad, [q.shape for q in eparams], *eparams)
+    T, run = _rollout_run('fast_adapt_ppo_tasks' if algo == 'ppo' else 'fast_adapt_vpg_tasks', pol, goals, params, seed, first_id, stride)
+    total, lt, theta, qry, replays = _adapt_and_validate(run, pol, baseline, params, algo, anil, first_order, dice, want_replays)
     thetas = theta if theta.dim() == 2 else theta.unsqueeze(0).expand(T, -1)
-    reward = out['rewards'].sum(dim=1) / E
+    reward = qry['rewards'].sum(dim=1) / params['adapt_batch_size']
     # the device rollout records no success signal: what get_ep_successes counts for such replays (rl.py:69-71)
-    success = torch.zeros(T, device=dev)
+    success = torch.zeros(T, device=pol.sigma.device)
     return AdaptedTasks(total, lt, reward, success, thetas, replays)
 
 

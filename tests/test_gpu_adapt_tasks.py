@@ -2,7 +2,10 @@
 1. mi_policy_update against mi_policy_meta_batch (bit-identical from shared parameters), per-task starts against single-row calls,
    head_only, the loss before the first update;
 2. fast_adapt_vpg_tasks / fast_adapt_ppo_tasks against the task-by-task walk (fast_adapt_vpg / fast_adapt_ppo with per-task device
-   runners): replays bit for bit, losses, parameters, rewards, summed gradient, baseline, slices of the goals;
+   runners): replays bit for bit, losses, parameters, rewards, summed gradient, baseline, slices of the goals.  Walk and batched
+   call are ONE implementation (core_functions.rl._adapt_and_validate, the walk with one replay row per call), so this checks that
+   its results do not depend on how the tasks are batched; what the walk computed before it became that one-task case is held by
+   tests/test_gpu_adapt_walk_parity.py;
 3. the same calls against the fp64 oracle (oracle/rl_ref.py replay_vpg / replay_ppo) on the replays they returned;
 4. the maml_ppo driver with --batch_tasks, evaluate(rollout='device'), single_ppo_update.
 Replaces (reference): the per-task loops of core_functions/rl.py:231-255,267-336 and rl/maml_ppo.py:100-131."""

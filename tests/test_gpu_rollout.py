@@ -1,7 +1,9 @@
 """mi_particles_rollout on the GPU: the noise against its numpy restatement, the exact structure of the packed
 replay re-derived from the device's own outputs, every step teacher-forced against the fp64 oracle (tests/rollout_oracle.py),
 termination and packing on hand-made policies, bitwise independence of the tasks of a call, and the layers above it -- the device
-mode of Particles2DRunner, fast_adapt_trpo_tasks against the task-by-task walk, and the maml_trpo driver.
+mode of Particles2DRunner, fast_adapt_trpo_tasks against the task-by-task walk (both run core_functions.rl._adapt_loop, the walk
+with one replay row per call: the comparison checks that the result does not depend on how the tasks are batched), and the maml_trpo
+driver.
 Replaces (reference): core_functions/runner.py + learn2learn's Particles2D, whose rollouts the reference steps on the host."""
 from copy import deepcopy
 
