@@ -15,22 +15,30 @@ misc_scripts/cl_rl.py:71-75: ``learner.adapt(vpg_a2c_loss(episodes, learner, ...
 run on the fast weights through ``mi_policy_forward`` / ``mi_policy_vjp`` / ``mi_policy_hvp`` whenever a graph is wanted (grad mode
 on and parameters that require grad) or the learner has been adapted.  ``learner(state)`` samples and never builds a graph; a
 learner that was never adapted acts through the bare policy exactly as before.
+
+``lr`` is a number (the reference's scalar step, today's scalar fused call) or an ``InnerLR`` (inner_lr.py): step sizes per tensor /
+per entry / per inner step, learnable or not.  A learnable ``InnerLR`` is a submodule, so its values are among ``maml.parameters()``
+(learn2learn ``MetaSGD``).  ``allow_nograd=True`` gives parameters with ``requires_grad=False`` the step 0, in the fused call and in
+``adapt`` (learn2learn's ``adapt`` skips them).
 """
 import copy
 
 
 import torch
 
+from .inner_lr import InnerLR
+
 
 class MAML(torch.nn.Module):
     def __init__(self, model, lr, first_order=False, allow_unused=None, allow_nograd=False):
         super().__init__()
         self.module = model
-        self.lr = lr
+        self.lr = lr                       # a number, or an InnerLR (a submodule: parameters when learnable, a buffer otherwise)
         self.first_order = first_order
         self.allow_nograd = allow_nograd
         self.allow_unused = allow_nograd if allow_unused is None else allow_unused
         self.__dict__['_fast'] = None      # flat fast weights of a step-wise learner (plain tensor, not a Parameter)
+        self.__dict__['_steps_done'] = 0   # inner steps this learner has taken (selects the row of per-step sizes)
 
     def __getattr__(self, attr):
         try:
@@ -43,6 +51,28 @@ class MAML(torch.nn.Module):
         if self.__dict__['_fast'] is None:
             self.__dict__['_fast'] = self.module.flat_parameters()
         return self.__dict__['_fast']
+
+    def lr_flat(self):
+        """None while the step size is one number for every parameter (the scalar fused call); else the step sizes [steps, P] in
+        ``parameters()`` order: an ``InnerLR``'s, with zeros for parameters that do not require grad under ``allow_nograd``."""
+        lr = self.lr
+        nograd = [n for n, p in self.module.named_parameters() if not p.requires_grad] if self.allow_nograd else []
+        if isinstance(lr, InnerLR):
+            return lr.flat(also_frozen=nograd)
+        if not nograd:
+            return None
+        return torch.cat([torch.full((p.numel(),), 0.0 if not p.requires_grad else float(lr), dtype=torch.float32, device=p.device)
+                          for p in self.module.parameters()]).unsqueeze(0)
+
+    def _step_lr(self):
+        """The step size(s) of this learner's next ``adapt``: the number, or the row of ``lr_flat`` for the step it is at."""
+        flat = self.lr_flat()
+        if flat is None:
+            return self.lr
+        k = self.__dict__['_steps_done']
+        if flat.shape[0] > 1 and k >= flat.shape[0]:
+            raise RuntimeError(f'this learner holds step sizes for {flat.shape[0]} inner steps and has taken {k}')
+        return flat[k if flat.shape[0] > 1 else 0]
 
     def _is_policy(self):
         return hasattr(self.module, 'density') and hasattr(self.module, 'flat_parameters')
@@ -107,6 +137,7 @@ class MAML(torch.nn.Module):
             allow_nograd = self.allow_nograd
         c = MAML(self.module, lr=self.lr, first_order=first_order, allow_unused=allow_unused, allow_nograd=allow_nograd)
         c.__dict__['_fast'] = self.__dict__['_fast']
+        c.__dict__['_steps_done'] = self.__dict__['_steps_done']
         return c
 
     def adapt(self, loss, first_order=None, allow_unused=None, allow_nograd=None):
@@ -130,12 +161,14 @@ class MAML(torch.nn.Module):
             gs = torch.autograd.grad(loss, params, retain_graph=second_order, create_graph=second_order, allow_unused=bool(allow_unused))
             g = torch.cat([(torch.zeros_like(p) if gi is None else gi).reshape(-1) for p, gi in zip(params, gs)])
             self.__dict__['_fast'] = self.module.flat_parameters() - self.lr * g
+            self.__dict__['_steps_done'] += 1
             return
         theta = self.fast_weights()
         if not theta.requires_grad:
             raise RuntimeError('learner.adapt needs parameters that require grad')
         (g,) = torch.autograd.grad(loss, theta, retain_graph=second_order, create_graph=second_order, allow_unused=bool(allow_unused))
-        self.__dict__['_fast'] = theta if g is None else theta - self.lr * g
+        self.__dict__['_fast'] = theta if g is None else theta - self._step_lr() * g
+        self.__dict__['_steps_done'] += 1
 
     def get_rep(self, input_d):
         """reference core_functions/maml.py:15-16"""

@@ -63,6 +63,51 @@ class _FusedFastAdapt(torch.autograd.Function):
         return (None,) * 9 + tuple(outs)
 
 
+class _FusedFastAdaptLR(torch.autograd.Function):
+    """`_FusedFastAdapt` with one step size per parameter (mi_meta_batch_maml_lr): ``lr_flat`` [steps, P] is an input of the function, and
+    ``backward`` hands autograd the step-size gradient next to the meta-gradient (``InnerLR.flat`` carries it to the stored values)."""
+
+    @staticmethod
+    def forward(ctx, engine, data, labels, shots, steps, first_order, need_grad, need_lr_grad, grad_tasks, lr_flat, *params):
+        theta = torch.cat([p.detach().reshape(-1) for p in params]).float().contiguous()
+        lr_vec = lr_flat.detach().float().contiguous()
+        if lr_vec.shape[0] not in (1, max(int(steps), 1)):
+            raise ValueError(f'the learner holds step sizes for {lr_vec.shape[0]} inner steps, the call adapts for {steps}')
+        T = data.shape[0]
+        gt = T if grad_tasks is None else int(grad_tasks)
+        ctx.deferred = None
+        if need_grad and DEFERRED_OUTER_BACKWARD:
+            ctx.deferred = (engine, theta, data, labels, shots, steps, lr_vec, first_order, gt, need_lr_grad)
+            need_grad = False
+        loss, acc, grad, lr_grad, _ = engine.meta_batch_lr(theta, data, labels, shots, steps, lr_vec, first_order=first_order,
+                                                           grad_tasks=gt if need_grad else 0, want_lr_grad=need_grad and need_lr_grad)
+        ctx.shapes = [p.shape for p in params]
+        empty = torch.empty(0, device=data.device)
+        ctx.save_for_backward(grad if grad is not None else empty, lr_grad if lr_grad is not None else empty)
+        ctx.mark_non_differentiable(loss, acc)
+        return loss[:gt].sum(), loss, acc
+
+    @staticmethod
+    def backward(ctx, gsum, gloss, gacc):
+        grad, lr_grad = ctx.saved_tensors
+        if ctx.deferred is not None:
+            engine, theta, data, labels, shots, steps, lr_vec, first_order, gt, need_lr_grad = ctx.deferred
+            _, _, grad, lr_grad, _ = engine.meta_batch_lr(theta, data, labels, shots, steps, lr_vec, first_order=first_order, grad_tasks=gt,
+                                                          want_lr_grad=need_lr_grad)
+            if lr_grad is None:
+                lr_grad = grad.new_empty(0)
+        if grad.numel() == 0:
+            raise RuntimeError('fast_adapt was run without gradients (torch.no_grad or nothing requires grad)')
+        outs, off = [], 0
+        for shp in ctx.shapes:
+            n = 1
+            for d in shp:
+                n *= d
+            outs.append((grad[off:off + n] * gsum).reshape(shp))
+            off += n
+        return (None,) * 9 + (lr_grad * gsum if lr_grad.numel() else None,) + tuple(outs)
+
+
 def meta_batch_adapt(learner, data, labels, adaptation_steps, shots, ways, first_order=None, grad_tasks=None):
     """Batched entry: data [T, 2*shots*ways, C, H, W], labels [T, 2*shots*ways] on the GPU.
     Returns (loss_sum, loss[T], acc[T]); ``loss_sum.backward()`` accumulates the SUM over tasks of d valid_loss/d theta
@@ -79,6 +124,11 @@ def meta_batch_adapt(learner, data, labels, adaptation_steps, shots, ways, first
     if spec.ways != ways:
         raise ValueError(f'model has {spec.ways} outputs but ways={ways}')
     data = data.reshape(data.shape[0], data.shape[1], spec.in_channels, spec.in_h, spec.in_w).float().contiguous()
+    lr_flat = learner.lr_flat() if isinstance(learner, MAML) else None
+    if lr_flat is not None:          # step sizes per parameter (InnerLR, allow_nograd): the vector call
+        need_lr = torch.is_grad_enabled() and lr_flat.requires_grad
+        return _FusedFastAdaptLR.apply(model.engine(), data, labels.contiguous(), shots, adaptation_steps, fo, need or need_lr, need_lr,
+                                       grad_tasks, lr_flat, *params)
     return _FusedFastAdapt.apply(model.engine(), data, labels.contiguous(), shots, adaptation_steps, lr, fo, need, grad_tasks, *params)
 
 

@@ -417,6 +417,10 @@ struct TanSet {
 struct Plan {
   float *theta, *g, *lam, *hv;
   float* lam2;          // fused tail: the adjoint recursion ping-pongs between lam and lam2 (the advance launch must not update in place)
+  // per-parameter step sizes (mi_meta_batch_maml_lr), else nullptr: the step sizes in engine layout [lr_steps][PS]; second order: the
+  // direction lr_k * lam_{k+1} of the Hessian-vector passes [T][PS], twice (ping-pong, like lam / lam2), and the products g_k * lam_{k+1}
+  // [K][T][PS] the step-size gradient sums
+  float *lrv = nullptr, *dir = nullptr, *dir2 = nullptr, *prod = nullptr;
   float *xs, *xq;
   int32_t *ys, *yq;
   std::vector<ActSet> sup;
@@ -479,7 +483,8 @@ static unsigned long long kernel_selection_key() {
   return (unsigned long long)form + 4ull * (unsigned)conv_b16() + 16ull * (unsigned)block1_split_form() + 64ull * (unsigned)sparse_wgrad_split_form() + 128ull * (unsigned long long)mask;
 }
 
-static void make_plan(const mi_engine* e, void* ws, int T, int ns, int nq, int K, int second_order, Plan& pl) {
+static void make_plan(const mi_engine* e, void* ws, int T, int ns, int nq, int K, int second_order, Plan& pl, int lr_steps = 0,
+                      int want_lr_grad = 0) {
   Bump b{reinterpret_cast<char*>(ws), 0};
   const int nl = (int)e->L.size();
   const size_t TP = (size_t)T * e->PS;
@@ -576,6 +581,14 @@ static void make_plan(const mi_engine* e, void* ws, int T, int ns, int nq, int K
   // every call with the form then in force, so a caller that switches forms is asked for the larger workspace by the size check)
   pl.cells = conv_operand_form() == 2 ? b.take<unsigned>((size_t)pl.cell_cap * T * MI_CELL_WORDS) : nullptr;
   pl.cell_T = T;
+  if (lr_steps > 0) {      // (behind everything else: the scalar call's layout is the prefix)
+    pl.lrv = b.take<float>((size_t)lr_steps * e->PS);
+    if (second_order && K > 0) {
+      pl.dir = b.take<float>(TP);
+      pl.dir2 = b.take<float>(TP);
+      if (want_lr_grad) pl.prod = b.take<float>(TP * K);
+    }
+  }
   pl.bytes = align_up(b.off, 256);
 }
 
@@ -633,6 +646,16 @@ extern "C" int mi_workspace_bytes(const mi_engine* e, int tasks, int ways, int s
   if (!e || !bytes || tasks < 1 || ways < 1 || shots < 1 || adapt_steps < 0) return MI_ERR_ARG;
   Plan pl;
   make_plan(e, nullptr, tasks, ways * shots, ways * shots, adapt_steps, second_order, pl);
+  *bytes = pl.bytes;
+  return MI_OK;
+}
+
+extern "C" int mi_workspace_bytes_lr(const mi_engine* e, int tasks, int ways, int shots, int adapt_steps, int second_order, int lr_steps,
+                                     int want_lr_grad, size_t* bytes) {
+  if (!e || !bytes || tasks < 1 || ways < 1 || shots < 1 || adapt_steps < 0) return MI_ERR_ARG;
+  if (lr_steps != 1 && (adapt_steps == 0 || lr_steps != adapt_steps)) return MI_ERR_ARG;
+  Plan pl;
+  make_plan(e, nullptr, tasks, ways * shots, ways * shots, adapt_steps, second_order, pl, lr_steps, want_lr_grad);
   *bytes = pl.bytes;
   return MI_OK;
 }
@@ -1103,10 +1126,15 @@ static AdvanceArgs advance_base(const mi_engine* e, float* g) {
 // grad_tasks: the first grad_tasks of the `tasks` tasks are TRAIN tasks (query backward, second-order adjoint recursion, summed into
 // meta_grad_out); the rest are VALIDATION tasks of the same meta-iteration (reference maml_vision.py:117-124: the same clone +
 // fast_adapt without backward), whose K support steps and query forward run in the SAME launches as the train tasks'.
+// lrc != nullptr (mi_meta_batch_maml_lr): one step size per parameter, D_k = diag(lr_k), lr_k = row (lr_steps == 1 ? 0 : k) of lr_vec:
+//   theta_{k+1} = theta_k - D_k g_k;   lam_k = lam_{k+1} - H_k (D_k lam_{k+1});   lr_grad_k = -sum_t g_k * lam_{k+1}
+// The Hessian-vector pass over support step k is driven with dir = D_k lam_{k+1} (block 1's tangent statistics included) and the update is
+// lam_k = lam_{k+1} - 1 * H dir.  lrc == nullptr: the scalar call, the same launches and arithmetic as before.
+struct LrCall { const float* lr_vec; int lr_steps; float* lr_grad_out; };
 static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
                                 int tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order, int grad_tasks,
                                 float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
-                                void* workspace, size_t workspace_bytes) {
+                                void* workspace, size_t workspace_bytes, const LrCall* lrc) {
   if (!e) return fail(nullptr, MI_ERR_ARG, "null engine");
   if (!theta || !data || !labels || !loss_out || !acc_out || !workspace) return fail(e, MI_ERR_ARG, "null pointer argument");
   const int with_grad = grad_tasks > 0;
@@ -1119,7 +1147,7 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
   const int so = (second_order && with_grad) ? 1 : 0;
   e->export_pass = 0;
   Plan pl;
-  make_plan(e, workspace, T, ns, nq, K, so, pl);
+  make_plan(e, workspace, T, ns, nq, K, so, pl, lrc ? lrc->lr_steps : 0, lrc && lrc->lr_grad_out);
   if (pl.bytes > workspace_bytes)
     return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes) + " bytes");
   const size_t TP = (size_t)T * e->PS;
@@ -1129,6 +1157,9 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
   { const int brc = plan_begin(e, st, pl); if (brc) return brc; }
   LAUNCH(e, st, OP_MISC, 0, launch_prepare_batch(st, data, labels, T, 2 * ns, e->d.in_channels, e->d.in_h, e->d.in_w, pl.xs, pl.xq, pl.ys, pl.yq));
   LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, theta, 0, e->perm_dev, (int)e->P, (int)e->PS, T, pl.theta));
+  // the step sizes in engine layout, once per call (padding entries zero): row k of lr_of is D_k
+  if (lrc) LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, lrc->lr_vec, e->P, e->perm_dev, (int)e->P, (int)e->PS, lrc->lr_steps, pl.lrv));
+  auto lr_of = [&](int k) { return pl.lrv + (lrc->lr_steps == 1 ? 0 : (size_t)k * e->PS); };
   if (pl.gram_s)
     LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, pl.xs, T, ns, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part, pl.gram_s));
   const double* gq = pl.gram_q;          // (also for forward-only calls and tasks: the same query forward whether or not a backward half follows)
@@ -1156,11 +1187,14 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
     if (rc) return rc;
     if (tail) {   // g_k finished, theta_{k+1} = theta_k - lr g_k, and block 1's statistics of the next support pass
       adv.a = th; adv.out = th + TP; adv.alpha = inner_lr;
+      if (lrc) adv.lr = lr_of(k);
       if (pl.gram_s && k + 1 < K) {
         ActSet& An = so ? pl.sup[k + 1] : pl.sup[0];
         adv.stats = 1; adv.gram = pl.gram_s; adv.out0 = An.mu[0]; adv.out1 = An.rstd[0]; adv.inv_m = inv_m0;
       }
       LAUNCH(e, st, OP_MISC, 2, launch_advance(st, adv, T));
+    } else if (lrc) {
+      LAUNCH(e, st, OP_MISC, 2, launch_axpy_vec(st, th, gk, lr_of(k), (int)e->PS, T, th + TP));
     } else {
       LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, th, gk, inner_lr, TP, th + TP));
     }
@@ -1183,28 +1217,43 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
     a.stats = 2; a.gram = pl.gram_s; a.sw = pl.theta + (size_t)k * TP + L0.off_w; a.swstride = e->PS;
     a.mu_in = pl.sup[k].mu[0]; a.rstd_in = pl.sup[k].rstd[0]; a.out0 = pl.tan.m1[0]; a.out1 = pl.tan.m2[0]; a.inv_m = inv_m0;
   };
+  // vector form: the launch that finishes lam_{k+1} also leaves dir = D_k lam_{k+1} (the direction of the Hessian-vector pass over support
+  // step k, into the buffer the pass that has just run was NOT driven with) and the products g_k * lam_{k+1}
+  float *dir_cur = pl.dir, *dir_nxt = pl.dir2;
+  auto vector_extras = [&](AdvanceArgs& a, int k) {
+    a.dlr = lr_of(k); a.dir = dir_nxt;
+    if (pl.prod) { a.dg = pl.g + (size_t)k * TP; a.prod = pl.prod + (size_t)k * TP; }
+    float* t = dir_cur; dir_cur = dir_nxt; dir_nxt = t;
+  };
   if (tail) {   // lam = grad L_query(theta_K) finished (folds only)
     if (so && K > 0 && pl.gram_s) tangent_stats(advq, K - 1);
+    if (lrc && so && K > 0) vector_extras(advq, K - 1);
     LAUNCH(e, st, OP_MISC, 2, launch_advance(st, advq, Tg));
   }
   float *lam_cur = pl.lam, *lam_nxt = pl.lam2;
   if (so) {
     for (int k = K - 1; k >= 0; --k) {
       if (tr) HIPCHK(e, launch_scatter_tasks(st, lam_cur, e->perm_dev, (int)e->P, (int)e->PS, T, e->trace + (size_t)(2 * K + 1 + k) * TPr));
+      if (lrc && !tail) {   // the separate launches of the vector form: dir = D_k lam, the products; below lam -= 1 * H dir
+        LAUNCH(e, st, OP_MISC, 2, launch_scale_vec(st, lam_cur, lr_of(k), (int)e->PS, Tg, dir_cur));
+        if (pl.prod) LAUNCH(e, st, OP_MISC, 2, launch_product(st, pl.g + (size_t)k * TP, lam_cur, (int)e->PS, Tg, pl.prod + (size_t)k * TP));
+      }
+      const float* v = lrc ? dir_cur : lam_cur;
       AdvanceArgs adv = advance_base(e, pl.hv);
-      rc = pass_hvp(e, st, pl, pl.sup[k], pl.xs, ns, Tg, pl.theta + (size_t)k * TP, pl.g + (size_t)k * TP, lam_cur, pl.hv, pl.gram_s, nullptr, nullptr,
+      rc = pass_hvp(e, st, pl, pl.sup[k], pl.xs, ns, Tg, pl.theta + (size_t)k * TP, pl.g + (size_t)k * TP, v, pl.hv, pl.gram_s, nullptr, nullptr,
                     tail ? &adv : nullptr, tail);
       if (rc) return rc;
       if (tail) {   // H lam finished, lam' = lam - lr H lam (into the other buffer: the row workgroups of the advance launch read lam's
                     // block-1 entries while others write lam'), and the tangent statistics of the next Hessian-vector pass
-        adv.a = lam_cur; adv.out = lam_nxt; adv.alpha = inner_lr;
+        adv.a = lam_cur; adv.out = lam_nxt; adv.alpha = lrc ? 1.f : inner_lr;
         if (k > 0 && pl.gram_s) tangent_stats(adv, k - 1);
+        if (lrc && k > 0) vector_extras(adv, k - 1);
         LAUNCH(e, st, OP_MISC, 2, launch_advance(st, adv, Tg));
         float* t = lam_cur; lam_cur = lam_nxt; lam_nxt = t;
         if (tr) HIPCHK(e, launch_scatter_tasks(st, pl.hv, e->perm_dev, (int)e->P, (int)e->PS, T, e->trace + (size_t)(3 * K + 1 + k) * TPr));
       } else {
         if (tr) HIPCHK(e, launch_scatter_tasks(st, pl.hv, e->perm_dev, (int)e->P, (int)e->PS, T, e->trace + (size_t)(3 * K + 1 + k) * TPr));
-        LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, lam_cur, pl.hv, inner_lr, (size_t)Tg * e->PS, lam_cur));
+        LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, lam_cur, pl.hv, lrc ? 1.f : inner_lr, (size_t)Tg * e->PS, lam_cur));
       }
     }
   }
@@ -1215,6 +1264,10 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
       HIPCHK(e, launch_scatter_tasks(st, pl.g + (size_t)k * TP, e->perm_dev, (int)e->P, (int)e->PS, T, e->trace + (size_t)(K + 1 + k) * TPr));
   }
   LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, lam_cur, e->perm_dev, (int)e->P, (int)e->PS, Tg, meta_grad_out));
+  // lr_grad = -sum_t g_k * lam_{k+1} in the reference's order (second order: the stored products; first order: lam is the constant pl.lam)
+  if (lrc && lrc->lr_grad_out)
+    LAUNCH(e, st, OP_MISC, 3, launch_lr_grad_fold(st, so ? pl.prod : nullptr, pl.g, pl.lam, e->perm_dev, (int)e->P, (int)e->PS, T, Tg, K,
+                                                  lrc->lr_steps, lrc->lr_grad_out));
   return MI_OK;
 }
 
@@ -1298,7 +1351,7 @@ extern "C" int mi_anil_workspace_bytes(const mi_engine* e, int tasks, int ways, 
 static int meta_batch_anil_impl(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
                                 int tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order,
                                 int with_grad, float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
-                                void* workspace, size_t workspace_bytes) {
+                                void* workspace, size_t workspace_bytes, const LrCall*) {
   if (!e) return fail(nullptr, MI_ERR_ARG, "null engine");
   if (!theta || !data || !labels || !loss_out || !acc_out || !workspace) return fail(e, MI_ERR_ARG, "null pointer argument");
   if (with_grad && !meta_grad_out) return fail(e, MI_ERR_ARG, "meta_grad_out is NULL but with_grad != 0");
@@ -1360,14 +1413,14 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const float* theta, 
 
 // ---- graph replay of the two fused calls
 typedef int (*MetaBatchFn)(mi_engine*, void*, const float*, const float*, const int64_t*, int, int, int, int, float, int, int, float*,
-                           float*, float*, float*, void*, size_t);
+                           float*, float*, float*, void*, size_t, const LrCall*);
 static int meta_batch_entry(MetaBatchFn fn, int which, mi_engine* e, void* stream, const float* theta, const float* data,
                             const int64_t* labels, int tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order,
                             int with_grad, float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out, void* workspace,
-                            size_t workspace_bytes) {
+                            size_t workspace_bytes, const LrCall* lrc = nullptr) {
   if (!e || !e->graph_on || e->prof_on || e->trace || e->bn_export || !stream)     // (capture is not permitted on the legacy default stream)
     return fn(e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, inner_lr, second_order, with_grad, loss_out, acc_out,
-              meta_grad_out, logits_out, workspace, workspace_bytes);
+              meta_grad_out, logits_out, workspace, workspace_bytes, lrc);
   unsigned lr_bits;
   memcpy(&lr_bits, &inner_lr, sizeof lr_bits);
   const std::vector<unsigned long long> key = {
@@ -1380,7 +1433,10 @@ static int meta_batch_entry(MetaBatchFn fn, int which, mi_engine* e, void* strea
       // every engine switch and the kernel selection in an element of its own: nothing packed, nothing that can alias
       (unsigned long long)e->fuse1, (unsigned long long)e->gram1, (unsigned long long)e->gramq, (unsigned long long)e->overlap,
       (unsigned long long)e->fuse_fin, (unsigned long long)e->fuse_b1red, (unsigned long long)e->fuse_tail, (unsigned long long)e->fuse_last,
-      kernel_selection_key()};
+      kernel_selection_key(),
+      // the step-size buffers of mi_meta_batch_maml_lr (their VALUES are read on the device at every replay)
+      (unsigned long long)(uintptr_t)(lrc ? lrc->lr_vec : nullptr), (unsigned long long)(lrc ? lrc->lr_steps : 0),
+      (unsigned long long)(uintptr_t)(lrc ? lrc->lr_grad_out : nullptr)};
   mi_engine::GraphEntry* ent = nullptr;
   for (auto& g : e->graphs)
     if (g.key == key) { ent = &g; break; }
@@ -1399,12 +1455,12 @@ static int meta_batch_entry(MetaBatchFn fn, int which, mi_engine* e, void* strea
     e->graphs.back().key = key;
     e->graphs.back().seen = 1;
     return fn(e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, inner_lr, second_order, with_grad, loss_out, acc_out,
-              meta_grad_out, logits_out, workspace, workspace_bytes);
+              meta_grad_out, logits_out, workspace, workspace_bytes, lrc);
   }
   // second sight: capture the launch sequence (nothing executes), instantiate, launch
   HIPCHK(e, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
   const int rc = fn(e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, inner_lr, second_order, with_grad, loss_out, acc_out,
-                    meta_grad_out, logits_out, workspace, workspace_bytes);
+                    meta_grad_out, logits_out, workspace, workspace_bytes, lrc);
   hipGraph_t graph = nullptr;
   const hipError_t ce = hipStreamEndCapture(st, &graph);
   if (rc != MI_OK || ce != hipSuccess || !graph) {
@@ -1440,6 +1496,24 @@ extern "C" int mi_meta_batch_maml_tv(mi_engine* e, void* stream, const float* th
   if (grad_tasks < 0 || grad_tasks > tasks) return fail(e, MI_ERR_ARG, "grad_tasks must be in 0..tasks");
   return meta_batch_entry(meta_batch_maml_impl, 0, e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, inner_lr,
                           second_order, grad_tasks, loss_out, acc_out, meta_grad_out, logits_out, workspace, workspace_bytes);
+}
+// mi_meta_batch_maml_tv with one step size per parameter (and per inner step when lr_steps == adapt_steps), read from device memory, and
+// the gradient of the summed query loss with respect to them (include/mi_maml.h).
+extern "C" int mi_meta_batch_maml_lr(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels, int tasks,
+                                     int grad_tasks, int ways, int shots, int adapt_steps, const float* lr_vec, int lr_steps,
+                                     int second_order, float* loss_out, float* acc_out, float* meta_grad_out, float* lr_grad_out,
+                                     float* logits_out, void* workspace, size_t workspace_bytes) {
+  if (grad_tasks < 0 || grad_tasks > tasks) return fail(e, MI_ERR_ARG, "grad_tasks must be in 0..tasks");
+  // (here, not in the implementation: before the graph cache and any HIP call)
+  if (lr_steps != 1 && (adapt_steps <= 0 || lr_steps != adapt_steps))
+    return fail(e, MI_ERR_ARG, "lr_steps = " + std::to_string(lr_steps) + " must be 1 or adapt_steps = " + std::to_string(adapt_steps) +
+                                   (adapt_steps == 0 ? " (without inner steps: 1)" : ""));
+  if (!lr_vec) return fail(e, MI_ERR_ARG, "lr_vec is NULL: mi_meta_batch_maml_lr takes lr_steps * P step sizes on the device");
+  if (lr_grad_out && grad_tasks == 0)
+    return fail(e, MI_ERR_ARG, "lr_grad_out given but grad_tasks = 0: the step-size gradient is summed over the train tasks");
+  const LrCall lrc{lr_vec, lr_steps, lr_grad_out};
+  return meta_batch_entry(meta_batch_maml_impl, 2, e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, 0.f, second_order,
+                          grad_tasks, loss_out, acc_out, meta_grad_out, logits_out, workspace, workspace_bytes, &lrc);
 }
 extern "C" int mi_meta_batch_anil(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
                                   int tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order,

@@ -733,6 +733,29 @@ __device__ __forceinline__ bool advance_arrive(unsigned* counter, unsigned arriv
   return last;
 }
 
+// VEC (mi_meta_batch_maml_lr): one step size per parameter, out = a - lr[e] * g, and -- where the launch finishes an adjoint vector lam_j --
+// the direction dir = lr_{j-1} * lam_j of the next Hessian-vector pass and the products g_{j-1} * lam_j of the step-size gradient, written by
+// the thread that finishes the element.  The tangent statistics (stats == 2) are then those of dir, whose block-1 entries take the same
+// write-through stores as out.  The scalar instantiation is the kernel as it was.
+template <bool VEC>
+__device__ __forceinline__ void advance_vec_tail(const AdvanceArgs& a, int task, unsigned e, float fin, bool through) {
+  if constexpr (VEC) {
+    if (a.dir) {
+      const float d = a.dlr[e] * fin;
+      float* dp = a.dir + (size_t)task * a.ostride + e;
+      if (through) __hip_atomic_store(dp, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else *dp = d;
+      if (a.prod) a.prod[(size_t)task * a.ostride + e] = a.dg[(size_t)task * a.gstride + e] * fin;
+    }
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ float advance_step(const AdvanceArgs& a, unsigned e) {
+  if constexpr (VEC) return a.lr ? a.lr[e] : a.alpha;
+  return a.alpha;
+}
+
+template <bool VEC>
 __global__ __launch_bounds__(1024) void advance_kernel(AdvanceArgs a, int ng, int kp, int S, int nchunk_wg, unsigned arrivals) {
   extern __shared__ double sm[];
   const int task = blockIdx.y, tid = threadIdx.x;
@@ -759,12 +782,15 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceArgs a, int ng, in
         if (in_w1 && !a.out) __hip_atomic_store(g_t + e, gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else g_t[e] = gv;
       }
+      float fin = gv;
       if (a.out) {
-        const float res = a.a[(size_t)task * a.ostride + e] - a.alpha * gv;
+        const float res = a.a[(size_t)task * a.ostride + e] - advance_step<VEC>(a, e) * gv;
         float* o = a.out + (size_t)task * a.ostride + e;
         if (in_w1) __hip_atomic_store(o, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else *o = res;
+        fin = res;
       }
+      advance_vec_tail<VEC>(a, task, e, fin, in_w1);
     }
     // (uniform per workgroup) does this chunk hold any of block 1's weights while no row workgroups exist?
     const unsigned lo = blockIdx.x * (unsigned)epw, hi = lo + (unsigned)epw;
@@ -793,12 +819,15 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceArgs a, int ng, in
       float* g_t = a.g + (size_t)task * a.gstride;
       if (a.stats && !a.out) __hip_atomic_store(g_t + e, gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       else g_t[e] = gv;
+      float fin = gv;
       if (a.out) {
-        const float res = a.a[(size_t)task * a.ostride + e] - a.alpha * gv;
+        const float res = a.a[(size_t)task * a.ostride + e] - advance_step<VEC>(a, e) * gv;
         float* o = a.out + (size_t)task * a.ostride + e;
         if (a.stats) __hip_atomic_store(o, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else *o = res;
+        fin = res;
       }
+      advance_vec_tail<VEC>(a, task, e, fin, a.stats != 0);
     }
     contributor = a.stats != 0;
   }
@@ -812,8 +841,10 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceArgs a, int ng, in
   double* qd = vs + (tangent ? kp * co : 0);
   __syncthreads();                                         // (dpart is dead)
   for (int e = tid; e < ng * ng; e += 1024) gs[e] = a.gram[(size_t)task * ng * ng + e];
+  const float* fin_t = res_t;
+  if constexpr (VEC) { if (a.dir) fin_t = a.dir + (size_t)task * a.ostride; }      // the direction of the next Hessian-vector pass
   for (int e = tid; e < kp * co; e += 1024) {
-    const double fin = (double)__hip_atomic_load(res_t + w1_lo + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double fin = (double)__hip_atomic_load(fin_t + w1_lo + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (tangent) {
       ws[e] = (double)a.sw[(size_t)task * a.swstride + e];
       vs[e] = fin;
@@ -989,7 +1020,14 @@ hipError_t launch_advance(hipStream_t st, const AdvanceArgs& a_in, int tasks) {
   size_t smem = 4160 + (size_t)1024 * sizeof(double);
   if (a.stats) smem = 4160 + ((size_t)ng * ng + (size_t)(a.stats == 2 ? 3 : 2) * kp * a.co) * sizeof(double);
   if (smem < 4160 + (size_t)1024 * sizeof(double)) smem = 4160 + (size_t)1024 * sizeof(double);
-  hipLaunchKernelGGL(advance_kernel, dim3(nchunk_wg + nrow_wg, tasks), dim3(1024), smem, st, a, ng, kp, S, nchunk_wg, arrivals);
+  if (a.lr || a.dir) {
+    if (a.dir && (!a.dlr || (a.prod && !a.dg))) return hipErrorInvalidValue;
+    // the row workgroups read the direction this pass was driven with (gw.wd, gammad): the new one goes to another buffer
+    if (a.dir && a.b1_wgrad && a.gw_tangent && a.dir + a.off_w1 == a.gw.wd) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(advance_kernel<true>, dim3(nchunk_wg + nrow_wg, tasks), dim3(1024), smem, st, a, ng, kp, S, nchunk_wg, arrivals);
+  } else {
+    hipLaunchKernelGGL(advance_kernel<false>, dim3(nchunk_wg + nrow_wg, tasks), dim3(1024), smem, st, a, ng, kp, S, nchunk_wg, arrivals);
+  }
   return hipGetLastError();
 }
 

@@ -202,6 +202,11 @@ struct AdvanceArgs {
   const float *mu_in, *rstd_in;              // stats == 2
   float *out0, *out1; double inv_m;          // mean / rstd  (stats == 2: m1 / m2), [T][co]
   unsigned* counter;                         // stats != 0: one zero-initialised arrival counter per task (left at zero)
+  // Per-parameter step sizes (mi_meta_batch_maml_lr).  Any of these set selects the kernel's vector instantiation; all null: the scalar one.
+  const float* lr;                           // [n] step sizes of THIS update, shared by the tasks: out = a - lr[e] * g (null: alpha)
+  const float* dlr; float* dir;              // the launch finishes an adjoint vector lam_j (out, or g when out == nullptr): dir[task][e] =
+                                             // dlr[e] * lam_j[e], the direction of the next Hessian-vector pass [T][ostride]; stats == 2 then reads dir
+  const float* dg; float* prod;              // ... and prod[task][e] = dg[task][e] * lam_j[e] (dg = g_{j-1} [T][gstride]; prod [T][ostride], or null)
 };
 hipError_t launch_advance(hipStream_t st, const AdvanceArgs& a, int tasks);
 
@@ -281,6 +286,14 @@ hipError_t launch_scatter_tasks(hipStream_t st, const float* g, const int32_t* p
 hipError_t launch_nhwc_to_nchw(hipStream_t st, const float* src, size_t images, int c, int h, int w, float* dst);
 hipError_t launch_scatter_sum(hipStream_t st, const float* lam, const int32_t* perm, int p, int pstride, int tasks, float* out_ref);
 hipError_t launch_axpy(hipStream_t st, const float* a, const float* b, float alpha, size_t n, float* out);
+// per-parameter step sizes (lr [pstride], shared by the tasks; vectors [tasks][pstride]):  out = a - lr * b;  out = lr * x;  out = a * b
+hipError_t launch_axpy_vec(hipStream_t st, const float* a, const float* b, const float* lr, int pstride, int tasks, float* out);
+hipError_t launch_scale_vec(hipStream_t st, const float* x, const float* lr, int pstride, int tasks, float* out);
+hipError_t launch_product(hipStream_t st, const float* a, const float* b, int pstride, int tasks, float* out);
+// out_ref[s][perm[i]] = -sum over the steps k of s (all K when lr_steps == 1, else k == s), then over tasks t < grad_tasks, of
+// prod[k][t][i] (prod != nullptr) or g[k][t][i] * lam[t][i] (first order): fp32 products, one fp64 chain in that fixed order, rounded once
+hipError_t launch_lr_grad_fold(hipStream_t st, const float* prod, const float* g, const float* lam, const int32_t* perm, int p, int pstride,
+                               int tasks, int grad_tasks, int steps, int lr_steps, float* out_ref);
 hipError_t launch_stream_copy(hipStream_t st, const void* src, void* dst, size_t bytes);
 hipError_t launch_amax(hipStream_t st, const float* x, size_t per_task, int tasks, unsigned* cell);   // cells [T][MI_CELL_WORDS] (mi_common.h) |= exponent bits of max |x[task]|
 const unsigned* standalone_amax(hipStream_t st, int slot, const float* x, size_t per_task, int tasks, hipError_t* err);

@@ -138,6 +138,43 @@ __global__ void axpy_kernel(const float* __restrict__ a, const float* __restrict
   if (i < n) out[i] = a[i] - alpha * b[i];
 }
 
+// The same update with one step size per parameter, shared by the tasks (mi_meta_batch_maml_lr without the one-launch advance):
+// out[t][i] = a[t][i] - lr[i] * b[t][i], the direction of a Hessian-vector pass dir = lr * lam, and the products g * lam the
+// step-size gradient sums.  Separate multiply and subtract, as in axpy_kernel.
+__global__ void axpy_vec_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ lr, int pstride,
+                                size_t n, float* __restrict__ out) {
+  const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o < n) out[o] = a[o] - lr[o % pstride] * b[o];
+}
+__global__ void scale_vec_kernel(const float* __restrict__ x, const float* __restrict__ lr, int pstride, size_t n, float* __restrict__ out) {
+  const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o < n) out[o] = lr[o % pstride] * x[o];
+}
+__global__ void product_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n, float* __restrict__ out) {
+  const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o < n) out[o] = a[o] * b[o];
+}
+
+// lr_grad[s][perm[i]] = -sum_k sum_t g_k[t][i] * lam_{k+1}[t][i]: the products are fp32 (stored by the advance launches, or formed here
+// from g and the constant lam of a first-order call), their sum is one fp64 chain over (step, task) in that order, rounded once.
+// grid (ceil(p / 256), lr_steps).
+__global__ void lr_grad_fold_kernel(const float* __restrict__ prod, const float* __restrict__ g, const float* __restrict__ lam,
+                                    const int32_t* __restrict__ perm, int p, int pstride, int tasks, int grad_tasks, int steps,
+                                    int lr_steps, float* __restrict__ out_ref) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p) return;
+  const int s = blockIdx.y;
+  const int k0 = lr_steps == 1 ? 0 : s, k1 = lr_steps == 1 ? steps : s + 1;
+  double acc = 0.0;
+  for (int k = k0; k < k1; ++k)
+    for (int t = 0; t < grad_tasks; ++t) {
+      const size_t o = ((size_t)k * tasks + t) * pstride + i;
+      const float pr = prod ? prod[o] : g[o] * lam[(size_t)t * pstride + i];
+      acc += (double)pr;
+    }
+  out_ref[(size_t)s * p + perm[i]] = (float)(0.0 - acc);
+}
+
 // Streaming copy: the build's own measurement of the HBM roofline (bench.py times it in the same run as the engine kernels;
 // SURVEY.md 8d "measured HBM roofline").  One workgroup per CU, 4 x 16 bytes per lane in flight, non-temporal both ways:
 // the fastest of the grid x unroll x temporal variants measured on MI355X (6.08 TB/s; hipMemcpy D2D 5.18 TB/s).
@@ -231,6 +268,27 @@ hipError_t launch_scatter_sum(hipStream_t st, const float* lam, const int32_t* p
 }
 hipError_t launch_axpy(hipStream_t st, const float* a, const float* b, float alpha, size_t n, float* out) {
   hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, b, alpha, n, out);
+  return hipGetLastError();
+}
+hipError_t launch_axpy_vec(hipStream_t st, const float* a, const float* b, const float* lr, int pstride, int tasks, float* out) {
+  const size_t n = (size_t)tasks * pstride;
+  hipLaunchKernelGGL(axpy_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, b, lr, pstride, n, out);
+  return hipGetLastError();
+}
+hipError_t launch_scale_vec(hipStream_t st, const float* x, const float* lr, int pstride, int tasks, float* out) {
+  const size_t n = (size_t)tasks * pstride;
+  hipLaunchKernelGGL(scale_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, lr, pstride, n, out);
+  return hipGetLastError();
+}
+hipError_t launch_product(hipStream_t st, const float* a, const float* b, int pstride, int tasks, float* out) {
+  const size_t n = (size_t)tasks * pstride;
+  hipLaunchKernelGGL(product_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, b, n, out);
+  return hipGetLastError();
+}
+hipError_t launch_lr_grad_fold(hipStream_t st, const float* prod, const float* g, const float* lam, const int32_t* perm, int p, int pstride,
+                               int tasks, int grad_tasks, int steps, int lr_steps, float* out_ref) {
+  hipLaunchKernelGGL(lr_grad_fold_kernel, dim3(ceil_div(p, 256), lr_steps), dim3(256), 0, st, prod, g, lam, perm, p, pstride, tasks,
+                     grad_tasks, steps, lr_steps, out_ref);
   return hipGetLastError();
 }
 hipError_t launch_stream_copy(hipStream_t st, const void* src, void* dst, size_t bytes) {

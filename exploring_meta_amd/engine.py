@@ -267,6 +267,59 @@ class MetaEngine:
         return loss, acc, grad, logits
 
     @_on_device
+    def meta_batch_lr(self, theta, data, labels, shots, adapt_steps, lr_vec, first_order=False, grad_tasks=None, want_lr_grad=False,
+                      return_logits=False):
+        """`meta_batch` with one inner-loop step size per parameter (mi_meta_batch_maml_lr): lr_vec [P] or [1, P] (one vector for every
+        inner step) or [adapt_steps, P] (one per step), fp32 on the engine's device, parameters() order.  Its values are read on the
+        device by every call, graph replays included.  grad_tasks = None: every task is a train task; 0: evaluation only.
+        Returns (loss[T], acc[T], meta_grad[P] or None, lr_grad [lr_steps, P] or None, logits or None); lr_grad (``want_lr_grad``) is
+        the gradient of the summed query loss of the train tasks with respect to lr_vec."""
+        s = self.spec
+        T = data.shape[0]
+        n2 = 2 * shots * s.ways
+        if tuple(data.shape) != (T, n2, s.in_channels, s.in_h, s.in_w) and \
+                not (s.in_channels == 1 and data.numel() == T * n2 * s.in_h * s.in_w):
+            raise ValueError(f'data shape {tuple(data.shape)} does not match [T, {n2}, {s.in_channels}, {s.in_h}, {s.in_w}]')
+        if tuple(labels.shape) != (T, n2):
+            raise ValueError(f'labels shape {tuple(labels.shape)} != {(T, n2)}')
+        if theta.numel() != self.param_count:
+            raise ValueError(f'theta has {theta.numel()} elements, the model has {self.param_count}')
+        for t, dt in ((theta, torch.float32), (data, torch.float32), (labels, torch.int64), (lr_vec, torch.float32)):
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                raise ValueError('theta/data/lr_vec must be contiguous fp32 CUDA tensors and labels contiguous int64 CUDA')
+        # the library sizes its reads of lr_vec from lr_steps and P: a buffer of another size is refused here, before any launch
+        if lr_vec.numel() % self.param_count != 0 or lr_vec.numel() == 0 or lr_vec.dim() > 2 or \
+                (lr_vec.dim() == 2 and lr_vec.shape[1] != self.param_count):
+            raise _lib.MiError(f'libmi_maml error -1: lr_vec has shape {tuple(lr_vec.shape)}, expected [P], [1, P] or [adapt_steps, P] '
+                               f'with P = {self.param_count}')
+        lr_steps = lr_vec.numel() // self.param_count
+        if grad_tasks is None:
+            grad_tasks = T
+        if not 0 <= grad_tasks <= T:
+            raise ValueError(f'grad_tasks must be in 0..{T}, got {grad_tasks}')
+        with_grad = grad_tasks > 0
+        so = (not first_order) and with_grad
+        b = C.c_size_t()
+        if self.lib.mi_workspace_bytes_lr(self._h, T, s.ways, shots, adapt_steps, int(so), lr_steps, int(bool(want_lr_grad)), C.byref(b)):
+            raise _lib.MiError(f'libmi_maml error -1: lr_steps = {lr_steps} must be 1 or adapt_steps = {adapt_steps}')
+        ws = self._workspace(b.value)
+        loss, acc, grad, logits = self._outputs('maml_lr', T, shots * s.ways, with_grad, return_logits)
+        lr_grad = None
+        if want_lr_grad:
+            if getattr(self, '_graph', False):
+                key = ('lr_grad', T, lr_steps)
+                if key not in self._persist:
+                    self._persist[key] = torch.empty(lr_steps, self.param_count, dtype=torch.float32, device=self.device)
+                lr_grad = self._persist[key]
+            else:
+                lr_grad = torch.empty(lr_steps, self.param_count, dtype=torch.float32, device=self.device)
+        rc = self._fused_call(self.lib.mi_meta_batch_maml_lr, _ptr(theta), _ptr(data), _ptr(labels), T, int(grad_tasks), s.ways, shots,
+                              adapt_steps, _ptr(lr_vec), lr_steps, int(not first_order), _ptr(loss), _ptr(acc), _ptr(grad), _ptr(lr_grad),
+                              _ptr(logits), _ptr(ws), ws.numel())
+        _lib.check(rc, self._h)
+        return loss, acc, grad, lr_grad, logits
+
+    @_on_device
     def meta_batch_anil(self, theta, data, labels, shots, adapt_steps, inner_lr, first_order=False, with_grad=True,
                         return_logits=False):
         """ANIL (reference vision/anil_vision.py:116-122): theta = [features.parameters()..., head.weight, head.bias] flat;

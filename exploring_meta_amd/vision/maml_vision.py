@@ -18,7 +18,7 @@ import random
 import numpy as np
 import torch
 
-from ..core_functions import MAML, MiniImagenetCNN, OmniglotCNN, evaluate, meta_batch_adapt
+from ..core_functions import MAML, InnerLR, MiniImagenetCNN, OmniglotCNN, evaluate, meta_batch_adapt
 from ..core_functions.vision_models import RunningStatsFold
 from ..sharding import init_process_group, reduce_meta_batch, shard_range
 from ..utils import synthetic
@@ -45,6 +45,16 @@ class SyntheticTasks:
         return torch.from_numpy(d), torch.from_numpy(l)
 
 
+def inner_lr_of(model, p):
+    """The ``lr`` argument of ``MAML`` for these parameters: the plain number (the reference's run) unless one of
+    --inner_lr_per / --learn_inner_lr / --per_step_lr / --freeze asks for step sizes per parameter."""
+    per, learn, per_step, freeze = p.get('inner_lr_per', 'scalar'), p.get('learn_inner_lr', False), p.get('per_step_lr', False), \
+        tuple(p.get('freeze') or ())
+    if per == 'scalar' and not learn and not per_step and not freeze:
+        return p['inner_lr']
+    return InnerLR(model, p['inner_lr'], per=per, steps=max(p['adapt_steps'], 1) if per_step else 1, learnable=learn, frozen=freeze)
+
+
 def run(dataset, p, first_order=False, log=print):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -55,7 +65,7 @@ def run(dataset, p, first_order=False, log=print):
     random.seed(p['seed']); np.random.seed(p['seed']); torch.manual_seed(p['seed']); torch.cuda.manual_seed(p['seed'])
     device = torch.device('cuda', local)
     model = (OmniglotCNN(p['ways']) if dataset == 'omni' else MiniImagenetCNN(p['ways'])).to(device)
-    maml = MAML(model, lr=p['inner_lr'], first_order=first_order)
+    maml = MAML(model, lr=inner_lr_of(model, p), first_order=first_order)
     opt = torch.optim.Adam(maml.parameters(), p['outer_lr'])
     loss = torch.nn.CrossEntropyLoss(reduction='mean')
     T = p['meta_batch_size']
@@ -117,18 +127,35 @@ def run(dataset, p, first_order=False, log=print):
         torch.distributed.destroy_process_group()
     if save_dir and rank == 0:
         torch.save(model.state_dict(), os.path.join(save_dir, 'model.pt'))       # utils/experiment.py:85-87
+        if isinstance(maml.lr, InnerLR):
+            torch.save(maml.lr.state_dict(), os.path.join(save_dir, 'inner_lr.pt'))
     return model, metrics
 
 
-if __name__ == '__main__':
+def build_parser():
     parser = argparse.ArgumentParser(description='MAML on Vision (MI355X engine)')
     parser.add_argument('--dataset', type=str, default='min', help='omni or min')
     for k, v in params.items():
         parser.add_argument(f'--{k}', type=type(v), default=v)
     parser.add_argument('--first_order', action='store_true')
     parser.add_argument('--save_dir', type=str, default='', help='write model_checkpoints/model_<it>.pt every save_every iterations and model.pt at the end (reference state_dict keys)')
-    args = parser.parse_args()
-    for k in params:
-        params[k] = getattr(args, k)
-    params['save_dir'] = args.save_dir
+    parser.add_argument('--inner_lr_per', choices=('scalar', 'tensor', 'parameter'), default='scalar',
+                        help='one inner step size per model, per parameter tensor or per entry')
+    parser.add_argument('--learn_inner_lr', action='store_true', help='the inner step sizes are meta-learned with the model (MetaSGD)')
+    parser.add_argument('--per_step_lr', action='store_true', help='one set of step sizes per inner step')
+    parser.add_argument('--freeze', nargs='+', default=[], metavar='PREFIX', help="parameter-name prefixes that are not adapted (e.g. 'base.0.')")
+    return parser
+
+
+def params_of(args):
+    """The run's parameter dict from parsed flags (the defaults are the reference's run)."""
+    p = {k: getattr(args, k) for k in params}
+    p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
+             freeze=list(args.freeze))
+    return p
+
+
+if __name__ == '__main__':
+    args = build_parser().parse_args()
+    params.update(params_of(args))
     run(args.dataset, params, first_order=args.first_order)

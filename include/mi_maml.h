@@ -138,6 +138,33 @@ int mi_meta_batch_maml_tv(mi_engine* e, void* stream, const float* theta, const 
                           float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
                           void* workspace, size_t workspace_bytes);
 
+/* mi_meta_batch_maml_tv with one inner-loop step size PER PARAMETER, optionally per inner step, and the gradient of the summed query
+ * loss with respect to those step sizes (layer freezing = step 0, per-tensor steps, learn2learn MetaSGD's learnable steps).  With
+ * D_k = diag(lr_k), lr_k = row (lr_steps == 1 ? 0 : k) of lr_vec:
+ *   theta_{k+1} = theta_k - D_k g_k,                      g_k = grad L_support(theta_k)
+ *   lam_K       = grad L_query(theta_K)
+ *   second order:  lam_k = lam_{k+1} - H_k (D_k lam_{k+1})          first order:  lam_k = lam_K
+ *   meta_grad   = sum_t lam_0           lr_grad_k = -sum_t g_k * lam_{k+1}   (lr_steps == 1: summed over k as well)
+ *   lr_vec      [lr_steps, P]  device memory, the reference's parameter order; any finite value is a legal step (negative ones occur with
+ *                              learnable steps).  The VALUES are read on the device by every call -- also by a graph replay: a caller may
+ *                              update the buffer in place between calls.
+ *   lr_steps    1 (one vector for every step) or adapt_steps (one per step; with adapt_steps == 0 only 1)
+ *   lr_grad_out [lr_steps, P]  SUM over the grad_tasks train tasks, like meta_grad_out, or NULL.  fp32 products, summed over steps and
+ *                              tasks in one fixed-order fp64 chain rounded once: bitwise reproducible from call to call.  Entries of a
+ *                              step size that is 0 are in general NOT 0; conv-bias entries are exact zeros (g is).
+ * Everything else as mi_meta_batch_maml_tv.  MI_ERR_ARG before any launch: lr_steps not 1 / adapt_steps, lr_vec NULL, lr_grad_out given
+ * with grad_tasks == 0.  A uniform vector computes theta_k, the loss, accuracy and logits of the scalar call bit for bit, and its
+ * first-order meta-gradient; the second-order recursion drives the Hessian-vector pass with D_k lam instead of scaling its result, which
+ * is the same number only up to rounding unless the step is a power of two.  Launches: those of the scalar call + 1 (the step sizes into
+ * engine layout) + 1 with lr_grad_out (fold and scatter); without the one-launch advance, second order, per inner step + 1 (the direction)
+ * + 1 with lr_grad_out (the products).  Workspace: mi_workspace_bytes_lr. */
+int mi_workspace_bytes_lr(const mi_engine* e, int tasks, int ways, int shots, int adapt_steps, int second_order, int lr_steps,
+                          int want_lr_grad, size_t* bytes);
+int mi_meta_batch_maml_lr(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
+                          int tasks, int grad_tasks, int ways, int shots, int adapt_steps, const float* lr_vec, int lr_steps,
+                          int second_order, float* loss_out, float* acc_out, float* meta_grad_out, float* lr_grad_out,
+                          float* logits_out, void* workspace, size_t workspace_bytes);
+
 /* Ablation / test switch: 1 (default) = every pass of mi_meta_batch_maml ends in ONE "advance" launch (weight-gradient partial folds,
  * block 1's Gram-matrix assembly, p <- p - lr g of learn2learn's maml_update / the adjoint recursion, the next pass's Gram statistics);
  * 0 = the separate launches (reduce_partials x3, gram_wgrad, axpy, gram_stats, a memset).  Bit-identical results. */

@@ -1,0 +1,102 @@
+"""Oracle (TEST INFRASTRUCTURE) for per-parameter inner-loop step sizes: the autograd restatement of oracle/vision_ref.py
+(prepare_batch, model_forward, clone_params) with the update ``v - lr[name][step] * g`` instead of ``v - lr * g``, the step sizes
+being leaves, so that autograd gives the gradient of the summed query loss with respect to them.  Plus the closed form the engine
+implements, for the host test that pins one against the other."""
+from collections import OrderedDict
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from exploring_meta_amd.utils import synthetic
+from oracle import vision_ref as R
+
+
+def lr_vector(spec, base, steps, seed, frozen=('base.0.',)):
+    """[steps, P] fp32 step sizes in parameters() order: base * U(0.5, 1.5) per entry (a pure function of the seed), 0 on the
+    tensors whose name starts with one of ``frozen``."""
+    shapes = R.param_shapes(spec)
+    P = sum(int(np.prod(s)) for s in shapes.values())
+    v = (base * (0.5 + synthetic.hash_uniform(seed, (steps, P)))).astype(np.float32)
+    off = 0
+    for name, shp in shapes.items():
+        n = int(np.prod(shp))
+        if any(name.startswith(pre) for pre in frozen):
+            v[:, off:off + n] = 0.0
+        off += n
+    return v
+
+
+def lr_dict(spec, flat, dtype):
+    """name -> [steps, *shape] leaves (requires_grad) from a flat [steps, P] array."""
+    out, off = OrderedDict(), 0
+    flat = torch.as_tensor(np.asarray(flat)).to(dtype)
+    for name, shp in R.param_shapes(spec).items():
+        n = int(np.prod(shp))
+        out[name] = flat[:, off:off + n].reshape((flat.shape[0],) + tuple(shp)).clone().requires_grad_(True)
+        off += n
+    return out
+
+
+def _row(lr, name, k):
+    t = lr[name]
+    return t[k if t.shape[0] > 1 else 0]
+
+
+def meta_batch(theta, spec, datas, labelss, K, shots, ways, lr_flat, first_order, dtype=torch.float64):
+    """The reference's train half (maml_meta_batch) with per-parameter steps.  Returns numpy (losses [T], accs [T], meta_grad [P],
+    lr_grad [steps, P], logits list, adapted parameters of every task [T, P])."""
+    so = not first_order
+    leaves = OrderedDict((k, v.detach().to(dtype).clone().requires_grad_(True)) for k, v in theta.items())
+    lr = lr_dict(spec, lr_flat, dtype)
+    losses, accs, logits, fast = [], [], [], []
+    for data, labels in zip(datas, labelss):
+        p = R.clone_params(leaves)
+        ad, al, ed, el = R.prepare_batch(data.to(dtype), labels, shots, ways)
+        for k in range(K):
+            loss = F.cross_entropy(R.model_forward(ad, p, spec), al)
+            gs = torch.autograd.grad(loss, list(p.values()), retain_graph=so, create_graph=so)
+            p = OrderedDict((n, v - _row(lr, n, k) * g) for (n, v), g in zip(p.items(), gs))
+        pred = R.model_forward(ed, p, spec)
+        vl = F.cross_entropy(pred, el)
+        vl.backward()
+        losses.append(vl.detach())
+        accs.append(R.accuracy(pred, el))
+        logits.append(pred.detach().double().numpy())
+        fast.append(R.flatten_params(p).detach().double().numpy())
+    g = R.flatten_params(OrderedDict((k, v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()))
+    steps = next(iter(lr.values())).shape[0]
+    lg = torch.cat([(v.grad if v.grad is not None else torch.zeros_like(v)).reshape(steps, -1) for v in lr.values()], dim=1)
+    return (torch.stack(losses).double().numpy(), torch.stack(accs).numpy(), g.double().numpy(), lg.double().numpy(), logits,
+            np.stack(fast))
+
+
+def closed_form(theta, spec, datas, labelss, K, shots, ways, lr_flat, first_order, dtype=torch.float64):
+    """meta_grad = sum_t lam_0 and lr_grad_k = -sum_t g_k * lam_{k+1} with lam_K = grad L_query(theta_K) and, second order,
+    lam_k = lam_{k+1} - H_k (D_k lam_{k+1}) (first order: lam_k = lam_K) -- every Hessian-vector product by double backward."""
+    names = list(theta.keys())
+    lrs = lr_dict(spec, lr_flat, dtype)
+    steps = next(iter(lrs.values())).shape[0]
+    P = sum(v.numel() for v in theta.values())
+    meta, lrg = torch.zeros(P, dtype=dtype), torch.zeros(steps, P, dtype=dtype)
+    flat = lambda ts: torch.cat([t.reshape(-1) for t in ts])
+    for data, labels in zip(datas, labelss):
+        ad, al, ed, el = R.prepare_batch(data.to(dtype), labels, shots, ways)
+        th = [OrderedDict((k, v.detach().to(dtype).clone().requires_grad_(True)) for k, v in theta.items())]
+        gs = []
+        for k in range(K):
+            loss = F.cross_entropy(R.model_forward(ad, th[k], spec), al)
+            g = torch.autograd.grad(loss, list(th[k].values()), create_graph=True)
+            gs.append(g)
+            th.append(OrderedDict((n, (v - _row(lrs, n, k) * gi).detach().requires_grad_(True)) for (n, v), gi in zip(th[k].items(), g)))
+        lq = F.cross_entropy(R.model_forward(ed, th[K], spec), el)
+        lam = [x.detach() for x in torch.autograd.grad(lq, list(th[K].values()))]
+        for k in range(K - 1, -1, -1):
+            row = k if steps > 1 else 0
+            lrg[row] -= flat([gi.detach() * li for gi, li in zip(gs[k], lam)])
+            if not first_order:
+                d = [_row(lrs, n, k).detach() * li for n, li in zip(names, lam)]
+                hv = torch.autograd.grad(gs[k], list(th[k].values()), grad_outputs=d, allow_unused=True)
+                lam = [li - (h if h is not None else torch.zeros_like(li)) for li, h in zip(lam, hv)]
+        meta += flat(lam)
+    return meta.double().numpy(), lrg.double().numpy()
