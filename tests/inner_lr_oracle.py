@@ -12,12 +12,18 @@ from exploring_meta_amd.utils import synthetic
 from oracle import vision_ref as R
 
 
-def lr_vector(spec, base, steps, seed, frozen=('base.0.',)):
+def lr_vector(spec, base, steps, seed, frozen=('base.0.',), negative=0.0):
     """[steps, P] fp32 step sizes in parameters() order: base * U(0.5, 1.5) per entry (a pure function of the seed), 0 on the
-    tensors whose name starts with one of ``frozen``."""
+    tensors whose name starts with one of ``frozen``.  ``negative``: the share of the other entries whose sign is flipped (a
+    hashed subset, a pure function of the seed too; 0 leaves every entry as it was) -- a learnt step size can cross zero."""
     shapes = R.param_shapes(spec)
     P = sum(int(np.prod(s)) for s in shapes.values())
     v = (base * (0.5 + synthetic.hash_uniform(seed, (steps, P)))).astype(np.float32)
+    if negative:
+        # (stream 2 of the seed: with the Mini-ImageNet net at K = 2, base 0.4, seed 5 and a quarter negative, the subsets of streams 1 and 4 put
+        # a pooling decision of tasks 0, 1 on a tie even for the fp32 oracle -- 1.4e-3 and 5e-2 from fp64 in lr_grad; this one: 2.7e-4)
+        flip = synthetic.hash_uniform(seed, (steps, P), stream=2) < negative
+        v[flip] = -v[flip]
     off = 0
     for name, shp in shapes.items():
         n = int(np.prod(shp))

@@ -35,6 +35,88 @@ def test_maml_vision_driver_writes_reference_checkpoints(tmp_path, golden_small)
         assert float(sd[f'base.{i}.normalize.running_mean'].abs().max()) > 0 and float((sd[f'base.{i}.normalize.running_var'] - 1).abs().max()) > 0
 
 
+LEARNT_LR = dict(ways=5, shots=1, adapt_steps=2, inner_lr=0.4, inner_lr_per='tensor', learn_inner_lr=True, per_step_lr=True, freeze=['base.0.'])
+
+
+def test_maml_vision_driver_learns_step_sizes(tmp_path):
+    """--inner_lr_per tensor --learn_inner_lr --per_step_lr --freeze base.0. --save_dir: Adam steps InnerLR.values with the model (the
+    saved values moved, so they were among maml.parameters()), the frozen tensors' columns keep the initial 0.4 bit for bit, and
+    inner_lr.pt loads into an InnerLR of the same construction.  A conv bias is followed by batch-statistics BatchNorm, which cancels it:
+    its gradient is identically zero (the engine writes 0), so is the gradient of its step size, and Adam leaves that column where it
+    was -- every OTHER column has moved after three iterations."""
+    import math
+    import numpy as np
+    from exploring_meta_amd.vision import maml_vision
+    p = dict(maml_vision.params, meta_batch_size=4, num_iterations=3, save_dir=str(tmp_path), **LEARNT_LR)
+    logs = []
+    model, metrics = maml_vision.run('omni', p, first_order=False, log=logs.append)
+    assert len(logs) == 3 and all(math.isfinite(v) for v in metrics.values()) and 0.0 <= metrics['test_acc'] <= 1.0
+    assert all(torch.isfinite(q).all() for q in model.parameters())
+    sd = torch.load(tmp_path / 'inner_lr.pt', map_location='cpu')
+    assert list(sd.keys()) == ['values']
+    fresh = maml_vision.inner_lr_of(maml_vision.OmniglotCNN(5), p)
+    assert fresh.learnable and torch.all(fresh.values == 0.4)
+    fresh.load_state_dict(sd)
+    names = [n for n, _ in model.named_parameters()]
+    values = fresh.values.detach().numpy()
+    assert values.shape == (2, len(names)) and np.isfinite(values).all()
+    for i, name in enumerate(names):
+        col = values[:, i]
+        if name.startswith('base.0.') or name.endswith('conv.bias'):
+            assert np.all(col == np.float32(0.4)), (name, col)
+        else:
+            assert np.all(col != np.float32(0.4)), (name, col)
+    assert sum(n.startswith('base.0.') for n in names) == 4 and sum(n.endswith('conv.bias') for n in names) == 4
+    flat, off = fresh.flat().detach().numpy(), 0
+    for name, q in model.named_parameters():                     # what the next call would adapt with: zeros on block 1
+        assert np.all((flat[:, off:off + q.numel()] == 0) == name.startswith('base.0.')), name
+        off += q.numel()
+
+
+def test_meta_batch_adapt_leaves_the_step_size_gradient_of_the_fused_call():
+    """One iteration as the driver builds it without checkpoints: train tasks 0, 1 and their validation tasks in ONE meta_batch_adapt call
+    (grad_tasks = 2).  The .grad left on InnerLR.values is the per-tensor sum of the lr_grad of a direct meta_batch_lr(grad_tasks = 2) on the
+    same inputs -- another summation order, so within numel 2^-24 sum |lr_grad| of that tensor -- zero on the frozen tensors; the model's .grad
+    is that call's meta-gradient bit for bit."""
+    import numpy as np
+    from exploring_meta_amd import core_functions as cf
+    from exploring_meta_amd.vision import maml_vision
+    p = dict(maml_vision.params, meta_batch_size=2, outer_lr=1e-4, **LEARNT_LR)
+    torch.manual_seed(p['seed'])
+    model = maml_vision.OmniglotCNN(5).cuda()
+    il = maml_vision.inner_lr_of(model, p)
+    with torch.no_grad():                                        # distinct step sizes per tensor and step (0.4 everywhere hides a mix-up)
+        il.values.mul_(torch.linspace(0.5, 1.5, il.values.numel(), device='cuda').reshape(il.values.shape))
+    maml = cf.MAML(model, lr=il)
+    assert any(q is il.values for q in maml.parameters())
+    ids = [0, 1]
+    d, l = maml_vision.SyntheticTasks('omni', 5, 1, 0).sample_batch(ids)
+    dv, lv = maml_vision.SyntheticTasks('omni', 5, 1, 10 ** 6).sample_batch([10 ** 6 + i for i in ids])
+    data, labels = torch.cat([d, dv]).cuda(), torch.cat([l, lv]).cuda()
+    total, losses, accs = cf.meta_batch_adapt(maml.clone(), data, labels, p['adapt_steps'], 1, 5, grad_tasks=2)
+    total.backward()
+    assert losses.shape == (4,) and torch.equal(total.detach(), losses[:2].sum())
+    spec = model.spec()
+    theta = torch.cat([q.detach().reshape(-1) for q in model.parameters()]).float().contiguous()
+    x = data.reshape(4, data.shape[1], spec.in_channels, spec.in_h, spec.in_w).float().contiguous()
+    _, _, grad, lr_grad, _ = model.engine().meta_batch_lr(theta, x, labels.contiguous(), 1, p['adapt_steps'], il.flat().detach().contiguous(),
+                                                          grad_tasks=2, want_lr_grad=True)
+    torch.cuda.synchronize()
+    assert torch.equal(torch.cat([q.grad.reshape(-1) for q in model.parameters()]), grad)
+    lg, got, off = lr_grad.double().cpu().numpy(), il.values.grad.cpu().numpy(), 0
+    assert got.shape == (2, len(list(model.parameters())))
+    for i, (name, q) in enumerate(model.named_parameters()):
+        part = lg[:, off:off + q.numel()]
+        off += q.numel()
+        if name.startswith('base.0.'):
+            assert np.all(got[:, i] == 0), name                  # frozen: a gradient exists, none reaches the stored value
+            assert name.endswith('conv.bias') or np.abs(part).sum() > 0, name
+            continue
+        bound = q.numel() * 2.0 ** -24 * np.abs(part).sum(1)
+        assert np.all(np.abs(got[:, i] - part.sum(1)) <= bound), (name, got[:, i], part.sum(1), bound)
+        assert name.endswith('conv.bias') or np.all(got[:, i] != 0), name
+
+
 def test_anil_vision_driver_writes_reference_checkpoints(tmp_path):
     """ANIL --save_dir: the reference calls save_model_checkpoint(features, 'features_<it+1>') -> model_checkpoints/
     model_features_<it+1>.pt / model_head_<it+1>.pt (utils/experiment.py:89-90, anil_vision.py:151-153) and, after the loop,

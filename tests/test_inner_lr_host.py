@@ -157,3 +157,27 @@ def test_closed_form_equals_fp64_autograd(K, first_order, per_step):
     assert clg.shape == (K if per_step else 1, g.size)
     frozen = lr[0] == 0
     assert frozen.any() and np.abs(lg[0][frozen]).sum() > 0            # a step of 0 does not make its gradient 0
+
+
+def test_negative_share_of_the_step_sizes_and_its_closed_form():
+    """lr_vector(negative=q) flips the sign of a hashed share q of the non-frozen entries and nothing else (0: the vector as it was, bit
+    for bit), and the closed form still equals fp64 autograd on such a vector (a learnt step size can cross zero): the net, tasks and
+    bars of test_closed_form_equals_fp64_autograd, K = 2, one vector per step."""
+    ways, shots, tasks, K = 5, 1, [0, 1], 2
+    spec = R.omniglot_spec(ways)
+    plain = O.lr_vector(spec, 0.4, K, 5)
+    assert np.array_equal(O.lr_vector(spec, 0.4, K, 5, negative=0), plain) and (plain >= 0).all()
+    lr = O.lr_vector(spec, 0.4, K, 5, negative=0.25)
+    assert lr.dtype == np.float32 and np.array_equal(np.abs(lr), plain)
+    live = plain != 0
+    share = (lr[live] < 0).mean()
+    assert 0.24 < share < 0.26, share                  # ~1.1e5 live entries per row: 0.25 +- 5 sigma is +- 0.005
+    assert np.array_equal(lr, O.lr_vector(spec, 0.4, K, 5, negative=0.25))          # a pure function of its arguments
+    assert not np.array_equal(lr[0] < 0, lr[1] < 0)                                 # the steps draw their signs independently
+    theta = model_params(spec, 11)
+    datas, labels = task_tensors('omni', tasks, ways, shots)
+    _, _, g, lg, _, _ = O.meta_batch(theta, spec, datas, labels, K, shots, ways, lr, False)
+    cg, clg = O.closed_form(theta, spec, datas, labels, K, shots, ways, lr, False)
+    assert rel_err(cg, g) <= 1e-12 and rel_err(clg, lg) <= 1e-12
+    _, _, g_plain, _, _, _ = O.meta_batch(theta, spec, datas, labels, K, shots, ways, plain, False)
+    assert rel_err(g, g_plain) > 1e-3                  # the signs reach the result
