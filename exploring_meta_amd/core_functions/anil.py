@@ -6,6 +6,7 @@ import torch
 
 from ..engine import MetaEngine, ModelSpec
 from .maml import MAML
+from .vision import flat_theta, split_grad
 from .vision_models import ConvBase
 
 _engines = {}
@@ -23,8 +24,7 @@ def _find_convbase(features):
 class _FusedAnil(torch.autograd.Function):
     @staticmethod
     def forward(ctx, engine, data, labels, shots, steps, lr, first_order, need_grad, *params):
-        theta = torch.cat([p.detach().reshape(-1) for p in params]).float().contiguous()
-        loss, acc, grad, _ = engine.meta_batch_anil(theta, data, labels, shots, steps, lr, first_order=first_order,
+        loss, acc, grad, _ = engine.meta_batch_anil(flat_theta(params), data, labels, shots, steps, lr, first_order=first_order,
                                                     with_grad=need_grad)
         ctx.shapes = [p.shape for p in params]
         ctx.save_for_backward(grad if grad is not None else torch.empty(0, device=data.device))
@@ -38,12 +38,7 @@ class _FusedAnil(torch.autograd.Function):
         (grad,) = ctx.saved_tensors
         if grad.numel() == 0:
             raise RuntimeError('fast_adapt was run without gradients (torch.no_grad or no parameter requires grad)')
-        outs, off = [], 0
-        for shp in ctx.shapes:
-            n = int(torch.Size(shp).numel())
-            outs.append((grad[off:off + n] * gsum).reshape(shp))
-            off += n
-        return (None,) * 8 + tuple(outs)
+        return (None,) * 8 + split_grad(grad, ctx.shapes, gsum)
 
 
 def anil_engine(features, ways, in_h, device):

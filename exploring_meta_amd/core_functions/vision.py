@@ -4,7 +4,6 @@ import os
 
 import torch
 
-from ..engine import flatten_parameters
 from .maml import MAML
 
 
@@ -23,67 +22,48 @@ def _check_loss(loss):
 DEFERRED_OUTER_BACKWARD = os.environ.get('MI_MAML_DEFERRED_BACKWARD', '0') == '1'
 
 
+def flat_theta(params):
+    """The parameters as the engine's theta: one flat fp32 vector in the given order."""
+    return torch.cat([p.detach().reshape(-1) for p in params]).float().contiguous()
+
+
+def split_grad(grad, shapes, scale):
+    """The flat gradient times `scale`, back in the parameters' shapes."""
+    outs, off = [], 0
+    for shp in shapes:
+        n = shp.numel()
+        outs.append((grad[off:off + n] * scale).reshape(shp))
+        off += n
+    return tuple(outs)
+
+
 class _FusedFastAdapt(torch.autograd.Function):
-    """T tasks through mi_meta_batch_maml.  The meta-gradient is produced together with the loss (the outer backward is
-    part of the fused call); ``backward`` hands it to autograd so ``eval_loss.backward()`` accumulates into ``.grad``."""
+    """T tasks through mi_meta_batch_maml_tv, or mi_meta_batch_maml_lr when the step sizes come per parameter: ``lr`` is the number, or
+    ``lr_flat`` [steps, P] an input of the function.  The meta-gradient is produced together with the loss (the outer backward is part
+    of the fused call); ``backward`` hands it to autograd so ``eval_loss.backward()`` accumulates into ``.grad``, the step-size gradient
+    next to it (``InnerLR.flat`` carries it to the stored values)."""
 
     @staticmethod
-    def forward(ctx, engine, data, labels, shots, steps, lr, first_order, need_grad, grad_tasks, *params):
-        theta = torch.cat([p.detach().reshape(-1) for p in params]).float().contiguous()
-        ctx.deferred = None
-        gt = None if grad_tasks is None else int(grad_tasks)
-        if need_grad and DEFERRED_OUTER_BACKWARD:
-            ctx.deferred = (engine, theta, data, labels, shots, steps, lr, first_order, gt)
-            need_grad = False
-        loss, acc, grad, _ = engine.meta_batch(theta, data, labels, shots, steps, lr, first_order=first_order,
-                                               with_grad=need_grad, grad_tasks=gt if need_grad else None)
-        ctx.shapes = [p.shape for p in params]
-        ctx.per_task = None
-        ctx.save_for_backward(grad if grad is not None else torch.empty(0, device=data.device))
-        # Only the SUM carries the meta-gradient (the engine reduces over tasks inside the fused call): the per-task losses are
-        # values, so `losses.mean().backward()` fails loudly instead of stepping on zeros.
-        ctx.mark_non_differentiable(loss, acc)
-        return (loss.sum() if gt is None else loss[:gt].sum()), loss, acc
-
-    @staticmethod
-    def backward(ctx, gsum, gloss, gacc):
-        (grad,) = ctx.saved_tensors
-        if ctx.deferred is not None:
-            engine, theta, data, labels, shots, steps, lr, first_order, gt = ctx.deferred
-            grad = engine.meta_batch(theta, data, labels, shots, steps, lr, first_order=first_order, with_grad=True, grad_tasks=gt)[2]
-        if grad.numel() == 0:
-            raise RuntimeError('fast_adapt was run without gradients (torch.no_grad or no parameter requires grad)')
-        outs, off = [], 0
-        for shp in ctx.shapes:
-            n = 1
-            for d in shp:
-                n *= d
-            outs.append((grad[off:off + n] * gsum).reshape(shp))
-            off += n
-        return (None,) * 9 + tuple(outs)
-
-
-class _FusedFastAdaptLR(torch.autograd.Function):
-    """`_FusedFastAdapt` with one step size per parameter (mi_meta_batch_maml_lr): ``lr_flat`` [steps, P] is an input of the function, and
-    ``backward`` hands autograd the step-size gradient next to the meta-gradient (``InnerLR.flat`` carries it to the stored values)."""
-
-    @staticmethod
-    def forward(ctx, engine, data, labels, shots, steps, first_order, need_grad, need_lr_grad, grad_tasks, lr_flat, *params):
-        theta = torch.cat([p.detach().reshape(-1) for p in params]).float().contiguous()
-        lr_vec = lr_flat.detach().float().contiguous()
-        if lr_vec.shape[0] not in (1, max(int(steps), 1)):
+    def forward(ctx, engine, data, labels, shots, steps, lr, first_order, need_grad, need_lr_grad, grad_tasks, lr_flat, *params):
+        theta = flat_theta(params)
+        lr_vec = None if lr_flat is None else lr_flat.detach().float().contiguous()
+        if lr_vec is not None and lr_vec.shape[0] not in (1, max(int(steps), 1)):
             raise ValueError(f'the learner holds step sizes for {lr_vec.shape[0]} inner steps, the call adapts for {steps}')
-        T = data.shape[0]
-        gt = T if grad_tasks is None else int(grad_tasks)
-        ctx.deferred = None
-        if need_grad and DEFERRED_OUTER_BACKWARD:
-            ctx.deferred = (engine, theta, data, labels, shots, steps, lr_vec, first_order, gt, need_lr_grad)
-            need_grad = False
-        loss, acc, grad, lr_grad, _ = engine.meta_batch_lr(theta, data, labels, shots, steps, lr_vec, first_order=first_order,
-                                                           grad_tasks=gt if need_grad else 0, want_lr_grad=need_grad and need_lr_grad)
+        gt = data.shape[0] if grad_tasks is None else int(grad_tasks)
+
+        def call(with_grad):
+            """(loss, acc, grad, lr_grad) of the fused call, evaluation only or with the gradients."""
+            if lr_vec is None:
+                return engine.meta_batch(theta, data, labels, shots, steps, lr, first_order=first_order, grad_tasks=gt if with_grad else 0)[:3] + (None,)
+            return engine.meta_batch_lr(theta, data, labels, shots, steps, lr_vec, first_order=first_order, grad_tasks=gt if with_grad else 0,
+                                        want_lr_grad=with_grad and need_lr_grad)[:4]
+        ctx.deferred = call if need_grad and DEFERRED_OUTER_BACKWARD else None
+        loss, acc, grad, lr_grad = call(need_grad and ctx.deferred is None)
         ctx.shapes = [p.shape for p in params]
         empty = torch.empty(0, device=data.device)
         ctx.save_for_backward(grad if grad is not None else empty, lr_grad if lr_grad is not None else empty)
+        # Only the SUM carries the meta-gradient (the engine reduces over tasks inside the fused call): the per-task losses are
+        # values, so `losses.mean().backward()` fails loudly instead of stepping on zeros.
         ctx.mark_non_differentiable(loss, acc)
         return loss[:gt].sum(), loss, acc
 
@@ -91,21 +71,11 @@ class _FusedFastAdaptLR(torch.autograd.Function):
     def backward(ctx, gsum, gloss, gacc):
         grad, lr_grad = ctx.saved_tensors
         if ctx.deferred is not None:
-            engine, theta, data, labels, shots, steps, lr_vec, first_order, gt, need_lr_grad = ctx.deferred
-            _, _, grad, lr_grad, _ = engine.meta_batch_lr(theta, data, labels, shots, steps, lr_vec, first_order=first_order, grad_tasks=gt,
-                                                          want_lr_grad=need_lr_grad)
-            if lr_grad is None:
-                lr_grad = grad.new_empty(0)
+            _, _, grad, lr_grad = ctx.deferred(True)
+            lr_grad = grad.new_empty(0) if lr_grad is None else lr_grad
         if grad.numel() == 0:
-            raise RuntimeError('fast_adapt was run without gradients (torch.no_grad or nothing requires grad)')
-        outs, off = [], 0
-        for shp in ctx.shapes:
-            n = 1
-            for d in shp:
-                n *= d
-            outs.append((grad[off:off + n] * gsum).reshape(shp))
-            off += n
-        return (None,) * 9 + (lr_grad * gsum if lr_grad.numel() else None,) + tuple(outs)
+            raise RuntimeError('fast_adapt was run without gradients (torch.no_grad or no parameter requires grad)')
+        return (None,) * 10 + (lr_grad * gsum if lr_grad.numel() else None,) + split_grad(grad, ctx.shapes, gsum)
 
 
 def meta_batch_adapt(learner, data, labels, adaptation_steps, shots, ways, first_order=None, grad_tasks=None):
@@ -125,11 +95,10 @@ def meta_batch_adapt(learner, data, labels, adaptation_steps, shots, ways, first
         raise ValueError(f'model has {spec.ways} outputs but ways={ways}')
     data = data.reshape(data.shape[0], data.shape[1], spec.in_channels, spec.in_h, spec.in_w).float().contiguous()
     lr_flat = learner.lr_flat() if isinstance(learner, MAML) else None
-    if lr_flat is not None:          # step sizes per parameter (InnerLR, allow_nograd): the vector call
-        need_lr = torch.is_grad_enabled() and lr_flat.requires_grad
-        return _FusedFastAdaptLR.apply(model.engine(), data, labels.contiguous(), shots, adaptation_steps, fo, need or need_lr, need_lr,
-                                       grad_tasks, lr_flat, *params)
-    return _FusedFastAdapt.apply(model.engine(), data, labels.contiguous(), shots, adaptation_steps, lr, fo, need, grad_tasks, *params)
+    # step sizes per parameter (InnerLR, allow_nograd): the vector call, whose step sizes may want a gradient too
+    need_lr = lr_flat is not None and torch.is_grad_enabled() and lr_flat.requires_grad
+    return _FusedFastAdapt.apply(model.engine(), data, labels.contiguous(), shots, adaptation_steps, lr, fo, need or need_lr, need_lr, grad_tasks,
+                                 lr_flat, *params)
 
 
 def fast_adapt(batch, learner, loss, adaptation_steps, shots, ways, device, features=None):

@@ -5,6 +5,7 @@
 //   theta_0 = theta;  for k < K:  g_k = grad L_support(theta_k);  theta_{k+1} = theta_k - alpha g_k      (l2l MAML.adapt)
 //   lam = grad L_query(theta_K);   second order:  for k = K-1..0:  lam <- lam - alpha * H_support(theta_k) lam
 //   meta_grad = sum_t lam_t.        H v is a forward-over-reverse tangent sweep over the SAVED step-k activations.
+#include <array>
 #include <string>
 #include <vector>
 #include <cstdio>
@@ -26,6 +27,7 @@ struct Layer {
   size_t off_gamma, off_beta, off_w, off_b;
 };
 
+typedef std::array<unsigned long long, 30> GraphKey;   // graph_key(): what a captured fused call depends on
 struct mi_engine {
   mi_model_desc d;
   int device;
@@ -69,7 +71,7 @@ struct mi_engine {
   // launch-bound few-image configurations need (cfg1: 75 launches in 0.6 ms).  First sight of a signature runs eagerly (kernel
   // attributes, lazily created streams), the second is captured, later ones replay.
   bool graph_on = false;
-  struct GraphEntry { std::vector<unsigned long long> key; hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; int seen = 0; };
+  struct GraphEntry { GraphKey key; hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; int seen = 0; };
   std::vector<GraphEntry> graphs;
   // BatchNorm batch statistics of every forward pass (mi_engine_set_bn_export): what torch.nn.BatchNorm2d's running_mean / running_var
   // update consumes.  Layout [pass][T][2][sum of channels over the blocks]: batch mean, biased batch variance.
@@ -483,8 +485,74 @@ static unsigned long long kernel_selection_key() {
   return (unsigned long long)form + 4ull * (unsigned)conv_b16() + 16ull * (unsigned)block1_split_form() + 64ull * (unsigned)sparse_wgrad_split_form() + 128ull * (unsigned long long)mask;
 }
 
-static void make_plan(const mi_engine* e, void* ws, int T, int ns, int nq, int K, int second_order, Plan& pl, int lr_steps = 0,
-                      int want_lr_grad = 0) {
+// The sizes a plan depends on: T tasks, ns support / nq query images each, K inner steps; second_order: the K support passes are kept and
+// a tangent set is planned; lr_steps > 0: the step-size-vector call's buffers (want_lr_grad: its products too).  Every size query and the call
+// it sizes build their shape with the same helper below, so the two cannot disagree.
+struct PlanShape { int T, ns, nq, K, second_order, lr_steps, want_lr_grad; };
+static PlanShape maml_shape(int tasks, int ways, int shots, int K, int second_order, int lr_steps, int want_lr_grad) {
+  return PlanShape{tasks, ways * shots, ways * shots, K, second_order, lr_steps, want_lr_grad};
+}
+static PlanShape forward_shape(int tasks, int n) { return PlanShape{tasks, n, n, 0, 0, 0, 0}; }   // plain forward, learner forward / backward
+static PlanShape hvp_shape(int tasks, int n) { return PlanShape{tasks, n, n, 1, 1, 0, 0}; }       // mi_learner_hvp: one kept pass + tangent set
+
+// What both plans (the fused MAML call's and ANIL's) end with, for passes over n images of each of T tasks: the BatchNorm and weight-gradient
+// partials (per_block: one more weight-gradient buffer per block, for the fused tail), block 1's input Gram matrices over ng images (gram:
+// the plan's own rule for when they pay; gram_q: the query set's too) and the fp16 cells (pl.cell_cap of them).  The plans differ in those
+// conditions and in where the cells lie: behind the Gram buffers and whatever `between` takes (the MAML call's tangent set, which is sized
+// with the largest pooled activation, handed to it), or in front of them (cells_first: ANIL).
+template <class Between>
+static void plan_partials(const mi_engine* e, Bump& b, Plan& pl, int T, int n, bool per_block, bool gram, int ng, bool gram_q, bool cells_first,
+                          Between between) {
+  const int nl = (int)e->L.size();
+  size_t bnp = 0, wgp = 0, pmax = 0;
+  for (int l = 0; l < nl; ++l) {
+    const Layer& L = e->L[l];
+    const ConvGeom gg = geom(L, n);
+    int blk = conv_max_blocks_per_task(gg);
+    const int bb = bn_blocks_per_task(n, L.ho, L.wo, L.co, L.pool, 1);
+    if (bb > blk) blk = bb;
+    const size_t need = (size_t)T * blk * 2 * L.co;
+    if (need > bnp) bnp = need;
+    size_t w = wgrad_partial_floats(gg, T);
+    if (l == 0 && e->fuse1) {
+      int bpt = block1_blocks_per_task(n, L.ho, L.wo, L.co, T);
+      const int sb = sparse_wgrad_blocks_per_task(n, L.ho, L.wo, L.co, T);
+      if (sb > bpt) bpt = sb;
+      w = (size_t)T * bpt * 9 * L.ci * L.co;
+    }
+    if (w > wgp) wgp = w;
+    const size_t ps = (size_t)T * n * L.hp * L.wp * L.co;
+    if (ps > pmax) pmax = ps;
+  }
+  pl.bnpart = b.take<double>(bnp);
+  pl.wgpart = b.take<float>(wgp);
+  pl.wgpart_side = b.take<float>(wgp);
+  for (int l = 0; l < 8; ++l) pl.wgpart_l[l] = nullptr;
+  for (int l = 0; per_block && l < nl; ++l) {
+    if (l == 0 && e->fuse1) { pl.wgpart_l[0] = pl.wgpart; continue; }     // block 1's sparse partials: consumed inside the same advance launch
+    pl.wgpart_l[l] = b.take<float>(wgrad_partial_floats(geom(e->L[l], n), T));
+  }
+  // (reserved only while the fp16 operand form is selected -- 4 KB per tensor and task, ~20 MB at cfg2; the workspace size is recomputed by
+  // every call with the form then in force, so a caller that switches forms is asked for the larger workspace by the size check)
+  auto cells = [&] {
+    pl.cells = conv_operand_form() == 2 ? b.take<unsigned>((size_t)pl.cell_cap * T * MI_CELL_WORDS) : nullptr;
+    pl.cell_T = T;
+  };
+  if (cells_first) cells();
+  pl.gram_part = pl.gram_s = pl.gram_q = pl.gram_part_q = nullptr;
+  if (gram && e->fuse1 && e->gram1 && gram_supported(e->L[0].w, e->L[0].ci)) {
+    pl.gram_part = b.take<double>(gram_partial_doubles(T, ng, e->L[0].h, e->L[0].ci));
+    pl.gram_s = b.take<double>(gram_doubles(T, e->L[0].ci));
+    if (gram_q) {
+      pl.gram_q = b.take<double>(gram_doubles(T, e->L[0].ci));
+      pl.gram_part_q = b.take<double>(gram_partial_doubles(T, ng, e->L[0].h, e->L[0].ci));
+    }
+  }
+  if (!cells_first) { between(pmax); cells(); }
+}
+
+static void make_plan(const mi_engine* e, void* ws, const PlanShape& s, Plan& pl) {
+  const int T = s.T, ns = s.ns, nq = s.nq, K = s.K, second_order = s.second_order;
   Bump b{reinterpret_cast<char*>(ws), 0};
   const int nl = (int)e->L.size();
   const size_t TP = (size_t)T * e->PS;
@@ -500,58 +568,19 @@ static void make_plan(const mi_engine* e, void* ws, int T, int ns, int nq, int K
   pl.yq = b.take<int32_t>((size_t)T * nq);
   pl.tmp_loss = b.take<float>(T);
   pl.tmp_acc = b.take<float>(T);
-  pl.hscr = b.take<float>((size_t)T * (ns > nq ? ns : nq) * (e->d.ways + 2));
-  {
-    const int nmx = ns > nq ? ns : nq;
-    pl.tail_wpart = b.take<float>(tail_wpart_floats(T, e->feat, e->d.ways));
-    pl.tail_bpart = b.take<double>(tail_bpart_doubles(T, e->L.back().co));
-    pl.tail_scr = b.take<float>(tail_scr_floats(T, nmx, e->d.ways));
-  }
+  const int nmax = ns > nq ? ns : nq;      // (partial buffers and scratch are sized for the larger of support / query passes)
+  pl.hscr = b.take<float>((size_t)T * nmax * (e->d.ways + 2));
+  pl.tail_wpart = b.take<float>(tail_wpart_floats(T, e->feat, e->d.ways));
+  pl.tail_bpart = b.take<double>(tail_bpart_doubles(T, e->L.back().co));
+  pl.tail_scr = b.take<float>(tail_scr_floats(T, nmax, e->d.ways));
   const int nsets = (second_order && K > 0) ? K : 1;
   pl.sup.resize(nsets);
   for (int k = 0; k < nsets; ++k) plan_actset(e, b, pl.sup[k], T, ns, true);
   plan_actset(e, b, pl.qry, T, nq, true);
-  // partial buffers (sized for the larger of support / query passes)
-  const int nmax = ns > nq ? ns : nq;
-  size_t bnp = 0, wgp = 0, zmax = 0, pmax = 0;
-  for (int l = 0; l < nl; ++l) {
-    const Layer& L = e->L[l];
-    const ConvGeom gg = geom(L, nmax);
-    int blk = conv_max_blocks_per_task(gg);
-    const int bb = bn_blocks_per_task(nmax, L.ho, L.wo, L.co, L.pool, 1);
-    if (bb > blk) blk = bb;
-    const size_t need = (size_t)T * blk * 2 * L.co;
-    if (need > bnp) bnp = need;
-    size_t w = wgrad_partial_floats(gg, T);
-    if (l == 0 && e->fuse1) {
-      int bpt = block1_blocks_per_task(nmax, L.ho, L.wo, L.co, T);
-      const int sb = sparse_wgrad_blocks_per_task(nmax, L.ho, L.wo, L.co, T);
-      if (sb > bpt) bpt = sb;
-      w = (size_t)T * bpt * 9 * L.ci * L.co;
-    }
-    if (w > wgp) wgp = w;
-    const size_t zs = (l == 0 && e->fuse1) ? 0 : (size_t)T * nmax * L.ho * L.wo * L.co, ps = (size_t)T * nmax * L.hp * L.wp * L.co;
-    if (zs > zmax) zmax = zs;
-    if (ps > pmax) pmax = ps;
-  }
-  pl.bnpart = b.take<double>(bnp);
-  pl.wgpart = b.take<float>(wgp);
-  pl.wgpart_side = b.take<float>(wgp);
-  for (int l = 0; l < 8; ++l) pl.wgpart_l[l] = nullptr;
-  for (int l = 0; l < nl; ++l) {
-    if (l == 0 && e->fuse1) { pl.wgpart_l[0] = pl.wgpart; continue; }     // block 1's sparse partials: consumed inside the same advance launch
-    pl.wgpart_l[l] = b.take<float>(wgrad_partial_floats(geom(e->L[l], nmax), T));
-  }
-  pl.gram_part = pl.gram_s = pl.gram_q = pl.gram_part_q = nullptr;
-  if (e->fuse1 && e->gram1 && gram_supported(e->L[0].w, e->L[0].ci) && (K >= 2 || (K >= 1 && second_order))) {   // the support set is swept at least twice
-    pl.gram_part = b.take<double>(gram_partial_doubles(T, ns, e->L[0].h, e->L[0].ci));
-    pl.gram_s = b.take<double>(gram_doubles(T, e->L[0].ci));
-    if (e->gramq && nq == ns) {
-      pl.gram_q = b.take<double>(gram_doubles(T, e->L[0].ci));
-      pl.gram_part_q = b.take<double>(gram_partial_doubles(T, nq, e->L[0].h, e->L[0].ci));
-    }
-  }
-  if (second_order && K > 0) {
+  pl.cell_cap = 8 + (K + 1) * 2 * nl + K * 4 * nl + 4 * nl;      // p and dz per block and pass, pd and R{dz} per Hessian-vector pass, spare
+  const bool swept_twice = K >= 2 || (K >= 1 && second_order);   // the support set is swept at least twice: its Gram matrix pays
+  plan_partials(e, b, pl, T, nmax, true, swept_twice, ns, e->gramq && nq == ns, false, [&](size_t pmax) {
+    if (!(second_order && K > 0)) return;
     TanSet& X = pl.tan;
     for (int l = 0; l < nl; ++l) {
       const Layer& L = e->L[l];
@@ -575,21 +604,31 @@ static void make_plan(const mi_engine* e, void* ws, int T, int ns, int nq, int K
       X.fd = nullptr;
       X.rdf = nullptr;
     }
-  }
-  pl.cell_cap = 8 + (K + 1) * 2 * nl + K * 4 * nl + 4 * nl;      // p and dz per block and pass, pd and R{dz} per Hessian-vector pass, spare
-  // (reserved only while the fp16 operand form is selected -- 4 KB per tensor and task, ~20 MB at cfg2; the workspace size is recomputed by
-  // every call with the form then in force, so a caller that switches forms is asked for the larger workspace by the size check)
-  pl.cells = conv_operand_form() == 2 ? b.take<unsigned>((size_t)pl.cell_cap * T * MI_CELL_WORDS) : nullptr;
-  pl.cell_T = T;
-  if (lr_steps > 0) {      // (behind everything else: the scalar call's layout is the prefix)
-    pl.lrv = b.take<float>((size_t)lr_steps * e->PS);
+  });
+  if (s.lr_steps > 0) {      // (behind everything else: the scalar call's layout is the prefix)
+    pl.lrv = b.take<float>((size_t)s.lr_steps * e->PS);
     if (second_order && K > 0) {
       pl.dir = b.take<float>(TP);
       pl.dir2 = b.take<float>(TP);
-      if (want_lr_grad) pl.prod = b.take<float>(TP * K);
+      if (s.want_lr_grad) pl.prod = b.take<float>(TP * K);
     }
   }
   pl.bytes = align_up(b.off, 256);
+}
+
+// The plan of shape s laid into the caller's workspace, or the error that names the size it needs.
+static int plan_in(mi_engine* e, void* workspace, size_t workspace_bytes, const PlanShape& s, Plan& pl) {
+  make_plan(e, workspace, s, pl);
+  if (pl.bytes > workspace_bytes)
+    return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes) + " bytes");
+  return MI_OK;
+}
+
+static int plan_bytes(const mi_engine* e, const PlanShape& s, size_t* bytes) {      // ... and that size alone (the mi_*_workspace_bytes queries)
+  Plan pl;
+  make_plan(e, nullptr, s, pl);
+  *bytes = pl.bytes;
+  return MI_OK;
 }
 
 // ---- fp16 operand form: the largest-magnitude cell of every tensor a convolution reads
@@ -633,7 +672,7 @@ extern "C" int mi_debug_plan_offsets(const mi_engine* e, int tasks, int ways, in
   if (!e || !out) return MI_ERR_ARG;
   Plan pl;
   char* base = reinterpret_cast<char*>(4096);
-  make_plan(e, base, tasks, ways * shots, ways * shots, adapt_steps, second_order, pl);
+  make_plan(e, base, maml_shape(tasks, ways, shots, adapt_steps, second_order, 0, 0), pl);
   auto off = [&](const void* p) { return (size_t)(reinterpret_cast<const char*>(p) - base); };
   out[0] = off(pl.theta); out[1] = off(pl.g); out[2] = off(pl.xs); out[3] = off(pl.sup[0].p[0]); out[4] = off(pl.sup[0].dp[0]);
   out[5] = off(pl.sup[0].mu[0]); out[6] = off(pl.sup[0].rstd[0]); out[7] = off(pl.sup[0].p[1]); out[8] = off(pl.qry.p[0]);
@@ -641,23 +680,20 @@ extern "C" int mi_debug_plan_offsets(const mi_engine* e, int tasks, int ways, in
   return MI_OK;
 }
 
+// The step-size-vector call takes one row of step sizes for every inner step, or one per inner step (without inner steps: one row).
+static bool lr_steps_ok(int lr_steps, int adapt_steps) { return lr_steps == 1 || (adapt_steps > 0 && lr_steps == adapt_steps); }
+
 extern "C" int mi_workspace_bytes(const mi_engine* e, int tasks, int ways, int shots, int adapt_steps, int second_order,
                                   size_t* bytes) {
   if (!e || !bytes || tasks < 1 || ways < 1 || shots < 1 || adapt_steps < 0) return MI_ERR_ARG;
-  Plan pl;
-  make_plan(e, nullptr, tasks, ways * shots, ways * shots, adapt_steps, second_order, pl);
-  *bytes = pl.bytes;
-  return MI_OK;
+  return plan_bytes(e, maml_shape(tasks, ways, shots, adapt_steps, second_order, 0, 0), bytes);
 }
 
 extern "C" int mi_workspace_bytes_lr(const mi_engine* e, int tasks, int ways, int shots, int adapt_steps, int second_order, int lr_steps,
                                      int want_lr_grad, size_t* bytes) {
   if (!e || !bytes || tasks < 1 || ways < 1 || shots < 1 || adapt_steps < 0) return MI_ERR_ARG;
-  if (lr_steps != 1 && (adapt_steps == 0 || lr_steps != adapt_steps)) return MI_ERR_ARG;
-  Plan pl;
-  make_plan(e, nullptr, tasks, ways * shots, ways * shots, adapt_steps, second_order, pl, lr_steps, want_lr_grad);
-  *bytes = pl.bytes;
-  return MI_OK;
+  if (!lr_steps_ok(lr_steps, adapt_steps)) return MI_ERR_ARG;
+  return plan_bytes(e, maml_shape(tasks, ways, shots, adapt_steps, second_order, lr_steps, want_lr_grad), bytes);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1123,43 +1159,67 @@ static AdvanceArgs advance_base(const mi_engine* e, float* g) {
   return a;
 }
 
+// One fused call as the entry points receive it: what mi_meta_batch_maml / _tv / _lr / _anil fill from their arguments and hand through the
+// graph cache (meta_batch_entry) to the implementation.  grad_tasks = 0: evaluation only (the with_grad flag of mi_meta_batch_maml and
+// mi_meta_batch_anil is grad_tasks = tasks or 0).  lr_vec == nullptr: the scalar step inner_lr; else the step sizes on the device.
+enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2 };
+struct MetaCall {
+  MetaAlgo algo;
+  const float* theta; const float* data; const int64_t* labels;
+  int tasks, grad_tasks, ways, shots, adapt_steps, second_order;
+  float inner_lr;
+  const float* lr_vec; int lr_steps; float* lr_grad_out;
+  float *loss_out, *acc_out, *meta_grad_out, *logits_out;
+  void* workspace; size_t workspace_bytes;
+};
+
+// Every check of a fused call that needs no plan: before the graph cache and before any HIP call.
+static int check_call(mi_engine* e, const MetaCall& c) {
+  if (!e) return fail(nullptr, MI_ERR_ARG, "null engine");
+  if (c.grad_tasks < 0 || c.grad_tasks > c.tasks) return fail(e, MI_ERR_ARG, "grad_tasks must be in 0..tasks");
+  if (c.algo == ALGO_MAML_LR) {
+    if (!lr_steps_ok(c.lr_steps, c.adapt_steps))
+      return fail(e, MI_ERR_ARG, "lr_steps = " + std::to_string(c.lr_steps) + " must be 1 or adapt_steps = " + std::to_string(c.adapt_steps) +
+                                     (c.adapt_steps == 0 ? " (without inner steps: 1)" : ""));
+    if (!c.lr_vec) return fail(e, MI_ERR_ARG, "lr_vec is NULL: mi_meta_batch_maml_lr takes lr_steps * P step sizes on the device");
+    if (c.lr_grad_out && c.grad_tasks == 0)
+      return fail(e, MI_ERR_ARG, "lr_grad_out given but grad_tasks = 0: the step-size gradient is summed over the train tasks");
+  }
+  if (!c.theta || !c.data || !c.labels || !c.loss_out || !c.acc_out || !c.workspace) return fail(e, MI_ERR_ARG, "null pointer argument");
+  if (c.grad_tasks > 0 && !c.meta_grad_out) return fail(e, MI_ERR_ARG, "meta_grad_out is NULL but a gradient was asked for");
+  if (c.algo == ALGO_ANIL && e->d.head_mean_pool)
+    return fail(e, MI_ERR_ARG, "ANIL features are flattened (view(-1, fc_neurons)), not mean-pooled");
+  if (c.tasks < 1 || c.shots < 1 || c.adapt_steps < 0) return fail(e, MI_ERR_ARG, "tasks/shots must be >= 1, adapt_steps >= 0");
+  if (c.ways != e->d.ways) return fail(e, MI_ERR_ARG, "ways differs from the engine's classifier width");
+  return MI_OK;
+}
+
 // grad_tasks: the first grad_tasks of the `tasks` tasks are TRAIN tasks (query backward, second-order adjoint recursion, summed into
 // meta_grad_out); the rest are VALIDATION tasks of the same meta-iteration (reference maml_vision.py:117-124: the same clone +
 // fast_adapt without backward), whose K support steps and query forward run in the SAME launches as the train tasks'.
-// lrc != nullptr (mi_meta_batch_maml_lr): one step size per parameter, D_k = diag(lr_k), lr_k = row (lr_steps == 1 ? 0 : k) of lr_vec:
+// c.lr_vec != nullptr (mi_meta_batch_maml_lr): one step size per parameter, D_k = diag(lr_k), lr_k = row (lr_steps == 1 ? 0 : k) of lr_vec:
 //   theta_{k+1} = theta_k - D_k g_k;   lam_k = lam_{k+1} - H_k (D_k lam_{k+1});   lr_grad_k = -sum_t g_k * lam_{k+1}
 // The Hessian-vector pass over support step k is driven with dir = D_k lam_{k+1} (block 1's tangent statistics included) and the update is
-// lam_k = lam_{k+1} - 1 * H dir.  lrc == nullptr: the scalar call, the same launches and arithmetic as before.
-struct LrCall { const float* lr_vec; int lr_steps; float* lr_grad_out; };
-static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
-                                int tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order, int grad_tasks,
-                                float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
-                                void* workspace, size_t workspace_bytes, const LrCall* lrc) {
-  if (!e) return fail(nullptr, MI_ERR_ARG, "null engine");
-  if (!theta || !data || !labels || !loss_out || !acc_out || !workspace) return fail(e, MI_ERR_ARG, "null pointer argument");
-  const int with_grad = grad_tasks > 0;
-  if (with_grad && !meta_grad_out) return fail(e, MI_ERR_ARG, "meta_grad_out is NULL but a gradient was asked for");
-  if (tasks < 1 || shots < 1 || adapt_steps < 0) return fail(e, MI_ERR_ARG, "tasks/shots must be >= 1, adapt_steps >= 0");
-  if (grad_tasks < 0 || grad_tasks > tasks) return fail(e, MI_ERR_ARG, "grad_tasks must be in 0..tasks");
-  if (ways != e->d.ways) return fail(e, MI_ERR_ARG, "ways differs from the engine's classifier width");
+// lam_k = lam_{k+1} - 1 * H dir.  c.lr_vec == nullptr: the scalar call, the same launches and arithmetic as before.
+static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, Tg = grad_tasks, K = adapt_steps, ns = ways * shots, nq = ways * shots;
-  const int so = (second_order && with_grad) ? 1 : 0;
+  const int T = c.tasks, Tg = c.grad_tasks, K = c.adapt_steps, with_grad = Tg > 0, so = (c.second_order && with_grad) ? 1 : 0;
+  const float inner_lr = c.inner_lr;
   e->export_pass = 0;
   Plan pl;
-  make_plan(e, workspace, T, ns, nq, K, so, pl, lrc ? lrc->lr_steps : 0, lrc && lrc->lr_grad_out);
-  if (pl.bytes > workspace_bytes)
-    return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes) + " bytes");
+  const int prc = plan_in(e, c.workspace, c.workspace_bytes, maml_shape(T, c.ways, c.shots, K, so, c.lr_vec ? c.lr_steps : 0, c.lr_grad_out != nullptr), pl);
+  if (prc) return prc;
+  const int ns = c.ways * c.shots, nq = ns;
   const size_t TP = (size_t)T * e->PS;
   const Layer& L0 = e->L[0];
   const bool tail = e->fuse_tail && e->counters && T <= 65535 /* launch_advance puts the tasks on grid.y */ && T <= mi_engine::kMaxCounterTasks && 1024 % L0.co == 0;
   const double inv_m0 = 1.0 / ((double)ns * L0.ho * L0.wo);
   { const int brc = plan_begin(e, st, pl); if (brc) return brc; }
-  LAUNCH(e, st, OP_MISC, 0, launch_prepare_batch(st, data, labels, T, 2 * ns, e->d.in_channels, e->d.in_h, e->d.in_w, pl.xs, pl.xq, pl.ys, pl.yq));
-  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, theta, 0, e->perm_dev, (int)e->P, (int)e->PS, T, pl.theta));
+  LAUNCH(e, st, OP_MISC, 0, launch_prepare_batch(st, c.data, c.labels, T, 2 * ns, e->d.in_channels, e->d.in_h, e->d.in_w, pl.xs, pl.xq, pl.ys, pl.yq));
+  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, c.theta, 0, e->perm_dev, (int)e->P, (int)e->PS, T, pl.theta));
   // the step sizes in engine layout, once per call (padding entries zero): row k of lr_of is D_k
-  if (lrc) LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, lrc->lr_vec, e->P, e->perm_dev, (int)e->P, (int)e->PS, lrc->lr_steps, pl.lrv));
-  auto lr_of = [&](int k) { return pl.lrv + (lrc->lr_steps == 1 ? 0 : (size_t)k * e->PS); };
+  if (c.lr_vec) LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, c.lr_vec, e->P, e->perm_dev, (int)e->P, (int)e->PS, c.lr_steps, pl.lrv));
+  auto lr_of = [&](int k) { return pl.lrv + (c.lr_steps == 1 ? 0 : (size_t)k * e->PS); };
   if (pl.gram_s)
     LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, pl.xs, T, ns, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part, pl.gram_s));
   const double* gq = pl.gram_q;          // (also for forward-only calls and tasks: the same query forward whether or not a backward half follows)
@@ -1187,13 +1247,13 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
     if (rc) return rc;
     if (tail) {   // g_k finished, theta_{k+1} = theta_k - lr g_k, and block 1's statistics of the next support pass
       adv.a = th; adv.out = th + TP; adv.alpha = inner_lr;
-      if (lrc) adv.lr = lr_of(k);
+      if (c.lr_vec) adv.lr = lr_of(k);
       if (pl.gram_s && k + 1 < K) {
         ActSet& An = so ? pl.sup[k + 1] : pl.sup[0];
         adv.stats = 1; adv.gram = pl.gram_s; adv.out0 = An.mu[0]; adv.out1 = An.rstd[0]; adv.inv_m = inv_m0;
       }
       LAUNCH(e, st, OP_MISC, 2, launch_advance(st, adv, T));
-    } else if (lrc) {
+    } else if (c.lr_vec) {
       LAUNCH(e, st, OP_MISC, 2, launch_axpy_vec(st, th, gk, lr_of(k), (int)e->PS, T, th + TP));
     } else {
       LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, th, gk, inner_lr, TP, th + TP));
@@ -1203,7 +1263,7 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
   AdvanceArgs advq = advance_base(e, pl.lam);
   if (gq_side) { const int jrc = side_join(e, st, pl.half, true); if (jrc) return jrc; }
   else if (gq && !gq_launched) LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, pl.xq, T, nq, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part_q, pl.gram_q));
-  int rc = pass_fwd_bwd(e, st, pl, pl.qry, pl.xq, pl.yq, nq, T, thK, pl.lam, loss_out, acc_out, logits_out, with_grad != 0, gq,
+  int rc = pass_fwd_bwd(e, st, pl, pl.qry, pl.xq, pl.yq, nq, T, thK, pl.lam, c.loss_out, c.acc_out, c.logits_out, with_grad != 0, gq,
                         (tail && with_grad) ? &advq : nullptr, false, Tg);
   if (rc) return rc;
   if (!with_grad) return MI_OK;
@@ -1227,33 +1287,33 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
   };
   if (tail) {   // lam = grad L_query(theta_K) finished (folds only)
     if (so && K > 0 && pl.gram_s) tangent_stats(advq, K - 1);
-    if (lrc && so && K > 0) vector_extras(advq, K - 1);
+    if (c.lr_vec && so && K > 0) vector_extras(advq, K - 1);
     LAUNCH(e, st, OP_MISC, 2, launch_advance(st, advq, Tg));
   }
   float *lam_cur = pl.lam, *lam_nxt = pl.lam2;
   if (so) {
     for (int k = K - 1; k >= 0; --k) {
       if (tr) HIPCHK(e, launch_scatter_tasks(st, lam_cur, e->perm_dev, (int)e->P, (int)e->PS, T, e->trace + (size_t)(2 * K + 1 + k) * TPr));
-      if (lrc && !tail) {   // the separate launches of the vector form: dir = D_k lam, the products; below lam -= 1 * H dir
+      if (c.lr_vec && !tail) {   // the separate launches of the vector form: dir = D_k lam, the products; below lam -= 1 * H dir
         LAUNCH(e, st, OP_MISC, 2, launch_scale_vec(st, lam_cur, lr_of(k), (int)e->PS, Tg, dir_cur));
         if (pl.prod) LAUNCH(e, st, OP_MISC, 2, launch_product(st, pl.g + (size_t)k * TP, lam_cur, (int)e->PS, Tg, pl.prod + (size_t)k * TP));
       }
-      const float* v = lrc ? dir_cur : lam_cur;
+      const float* v = c.lr_vec ? dir_cur : lam_cur;
       AdvanceArgs adv = advance_base(e, pl.hv);
       rc = pass_hvp(e, st, pl, pl.sup[k], pl.xs, ns, Tg, pl.theta + (size_t)k * TP, pl.g + (size_t)k * TP, v, pl.hv, pl.gram_s, nullptr, nullptr,
                     tail ? &adv : nullptr, tail);
       if (rc) return rc;
       if (tail) {   // H lam finished, lam' = lam - lr H lam (into the other buffer: the row workgroups of the advance launch read lam's
                     // block-1 entries while others write lam'), and the tangent statistics of the next Hessian-vector pass
-        adv.a = lam_cur; adv.out = lam_nxt; adv.alpha = lrc ? 1.f : inner_lr;
+        adv.a = lam_cur; adv.out = lam_nxt; adv.alpha = c.lr_vec ? 1.f : inner_lr;
         if (k > 0 && pl.gram_s) tangent_stats(adv, k - 1);
-        if (lrc && k > 0) vector_extras(adv, k - 1);
+        if (c.lr_vec && k > 0) vector_extras(adv, k - 1);
         LAUNCH(e, st, OP_MISC, 2, launch_advance(st, adv, Tg));
         float* t = lam_cur; lam_cur = lam_nxt; lam_nxt = t;
         if (tr) HIPCHK(e, launch_scatter_tasks(st, pl.hv, e->perm_dev, (int)e->P, (int)e->PS, T, e->trace + (size_t)(3 * K + 1 + k) * TPr));
       } else {
         if (tr) HIPCHK(e, launch_scatter_tasks(st, pl.hv, e->perm_dev, (int)e->P, (int)e->PS, T, e->trace + (size_t)(3 * K + 1 + k) * TPr));
-        LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, lam_cur, pl.hv, lrc ? 1.f : inner_lr, (size_t)Tg * e->PS, lam_cur));
+        LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, lam_cur, pl.hv, c.lr_vec ? 1.f : inner_lr, (size_t)Tg * e->PS, lam_cur));
       }
     }
   }
@@ -1263,11 +1323,11 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const float* theta, 
     for (int k = 0; k < K; ++k)
       HIPCHK(e, launch_scatter_tasks(st, pl.g + (size_t)k * TP, e->perm_dev, (int)e->P, (int)e->PS, T, e->trace + (size_t)(K + 1 + k) * TPr));
   }
-  LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, lam_cur, e->perm_dev, (int)e->P, (int)e->PS, Tg, meta_grad_out));
+  LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, lam_cur, e->perm_dev, (int)e->P, (int)e->PS, Tg, c.meta_grad_out));
   // lr_grad = -sum_t g_k * lam_{k+1} in the reference's order (second order: the stored products; first order: lam is the constant pl.lam)
-  if (lrc && lrc->lr_grad_out)
+  if (c.lr_vec && c.lr_grad_out)
     LAUNCH(e, st, OP_MISC, 3, launch_lr_grad_fold(st, so ? pl.prod : nullptr, pl.g, pl.lam, e->perm_dev, (int)e->P, (int)e->PS, T, Tg, K,
-                                                  lrc->lr_steps, lrc->lr_grad_out));
+                                                  c.lr_steps, c.lr_grad_out));
   return MI_OK;
 }
 
@@ -1309,34 +1369,9 @@ static void make_anil_plan(const mi_engine* e, void* ws, int T, int n, int K, An
   ap.tmp_loss = b.take<float>(T);
   ap.tmp_acc = b.take<float>(T);
   ap.hscr = b.take<float>((size_t)T * n * (e->d.ways + 2));
-  size_t bnp = 0, wgp = 0;
-  for (const Layer& L : e->L) {
-    const ConvGeom gg = geom(L, 2 * n);
-    int blk = conv_max_blocks_per_task(gg);
-    const int bb = bn_blocks_per_task(2 * n, L.ho, L.wo, L.co, L.pool, 1);
-    if (bb > blk) blk = bb;
-    const size_t need = (size_t)T * blk * 2 * L.co;
-    if (need > bnp) bnp = need;
-    size_t w = wgrad_partial_floats(gg, T);
-    if (&L == &e->L[0] && e->fuse1) {
-      int bpt = block1_blocks_per_task(2 * n, L.ho, L.wo, L.co, T);
-      const int sb = sparse_wgrad_blocks_per_task(2 * n, L.ho, L.wo, L.co, T);
-      if (sb > bpt) bpt = sb;
-      w = (size_t)T * bpt * 9 * L.ci * L.co;
-    }
-    if (w > wgp) wgp = w;
-  }
-  ap.scratch.bnpart = b.take<double>(bnp);
-  ap.scratch.wgpart = b.take<float>(wgp);
-  ap.scratch.wgpart_side = b.take<float>(wgp);
-  ap.scratch.gram_part = ap.scratch.gram_s = nullptr;
   ap.scratch.cell_cap = 8 + 4 * (int)e->L.size();
-  ap.scratch.cells = conv_operand_form() == 2 ? b.take<unsigned>((size_t)ap.scratch.cell_cap * T * MI_CELL_WORDS) : nullptr;
-  ap.scratch.cell_T = T;
-  if (e->fuse1 && e->gram1 && gram_supported(e->L[0].w, e->L[0].ci)) {   // statistics + weight gradient of block 1 from the Gram matrix
-    ap.scratch.gram_part = b.take<double>(gram_partial_doubles(T, 2 * n, e->L[0].h, e->L[0].ci));
-    ap.scratch.gram_s = b.take<double>(gram_doubles(T, e->L[0].ci));
-  }
+  // (block 1's statistics and weight gradient come from the Gram matrix of all 2n images whenever the engine can form it)
+  plan_partials(e, b, ap.scratch, T, 2 * n, false, true, 2 * n, false, true, [](size_t) {});
   ap.bytes = align_up(b.off, 256);
 }
 
@@ -1348,26 +1383,19 @@ extern "C" int mi_anil_workspace_bytes(const mi_engine* e, int tasks, int ways, 
   return MI_OK;
 }
 
-static int meta_batch_anil_impl(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
-                                int tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order,
-                                int with_grad, float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
-                                void* workspace, size_t workspace_bytes, const LrCall*) {
-  if (!e) return fail(nullptr, MI_ERR_ARG, "null engine");
-  if (!theta || !data || !labels || !loss_out || !acc_out || !workspace) return fail(e, MI_ERR_ARG, "null pointer argument");
-  if (with_grad && !meta_grad_out) return fail(e, MI_ERR_ARG, "meta_grad_out is NULL but with_grad != 0");
-  if (e->d.head_mean_pool) return fail(e, MI_ERR_ARG, "ANIL features are flattened (view(-1, fc_neurons)), not mean-pooled");
-  if (tasks < 1 || shots < 1 || adapt_steps < 0 || ways != e->d.ways) return fail(e, MI_ERR_ARG, "bad tasks/shots/steps/ways");
+static int meta_batch_anil_impl(mi_engine* e, void* stream, const MetaCall& c) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, K = adapt_steps, n = ways * shots, nl = (int)e->L.size();
+  const int T = c.tasks, K = c.adapt_steps, n = c.ways * c.shots, nl = (int)e->L.size(), with_grad = c.grad_tasks > 0;
+  const float inner_lr = c.inner_lr;
   AnilPlan ap;
-  make_anil_plan(e, workspace, T, n, K, ap);
-  if (ap.bytes > workspace_bytes)
+  make_anil_plan(e, c.workspace, T, n, K, ap);
+  if (ap.bytes > c.workspace_bytes)
     return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(ap.bytes) + " bytes");
   const size_t TP = (size_t)T * e->PS, fsz = (size_t)T * n * e->feat, pw = (size_t)T * n * e->d.ways;
-  LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, data, (size_t)T * 2 * n, e->d.in_channels, e->d.in_h, e->d.in_w, ap.x));
-  LAUNCH(e, st, OP_MISC, 0, launch_split_labels(st, labels, T, 2 * n, ap.ys, ap.yq));
-  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, theta, 0, e->perm_dev, (int)e->P, (int)e->PS, T, ap.theta));
-  const double* gram = (with_grad && workspace) ? ap.scratch.gram_s : nullptr;       // pays off only with a backward pass
+  LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, c.data, (size_t)T * 2 * n, e->d.in_channels, e->d.in_h, e->d.in_w, ap.x));
+  LAUNCH(e, st, OP_MISC, 0, launch_split_labels(st, c.labels, T, 2 * n, ap.ys, ap.yq));
+  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, c.theta, 0, e->perm_dev, (int)e->P, (int)e->PS, T, ap.theta));
+  const double* gram = with_grad ? ap.scratch.gram_s : nullptr;       // pays off only with a backward pass
   if (gram)
     LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, ap.x, T, 2 * n, e->L[0].h, e->L[0].w, e->L[0].ci, ap.scratch.gram_part, ap.scratch.gram_s));
   int rc = plan_begin(e, st, ap.scratch);
@@ -1389,11 +1417,11 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const float* theta, 
   }
   float* thK = ap.theta + (size_t)K * TP;
   if (with_grad) HIPCHK(e, hipMemsetAsync(ap.lam, 0, TP * sizeof(float), st));
-  rc = head_pass(e, st, ap.hscr, ap.fq, ap.yq, n, T, thK, ap.lam, loss_out, acc_out, logits_out, ap.prob + K * pw, ap.dl + K * pw, ap.dfq,
+  rc = head_pass(e, st, ap.hscr, ap.fq, ap.yq, n, T, thK, ap.lam, c.loss_out, c.acc_out, c.logits_out, ap.prob + K * pw, ap.dl + K * pw, ap.dfq,
                  with_grad != 0);
   if (rc || !with_grad) return rc;
   HIPCHK(e, hipMemsetAsync(ap.dfs, 0, fsz * sizeof(float), st));
-  if (second_order) {
+  if (c.second_order) {
     for (int k = K - 1; k >= 0; --k) {
       HIPCHK(e, hipMemsetAsync(ap.hv, 0, TP * sizeof(float), st));
       HeadArgs ha = head_args(e, ap.hscr, ap.fs, ap.theta + (size_t)k * TP, ap.lam, ap.hv, ap.rdf, n, T);   // (the features are fixed: no fd)
@@ -1407,36 +1435,33 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const float* theta, 
   LAUNCH(e, st, OP_MISC, 4, launch_interleave_rows(st, ap.dfs, ap.dfq, T, n, e->feat, ap.act.dp[nl - 1]));
   rc = trunk_backward(e, st, ap.scratch, ap.act, ap.x, 2 * n, T, ap.theta, ap.lam, gram);  // trunk grads join the head part in lam
   if (rc) return rc;
-  LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, ap.lam, e->perm_dev, (int)e->P, (int)e->PS, T, meta_grad_out));
+  LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, ap.lam, e->perm_dev, (int)e->P, (int)e->PS, T, c.meta_grad_out));
   return MI_OK;
 }
 
-// ---- graph replay of the two fused calls
-typedef int (*MetaBatchFn)(mi_engine*, void*, const float*, const float*, const int64_t*, int, int, int, int, float, int, int, float*,
-                           float*, float*, float*, void*, size_t, const LrCall*);
-static int meta_batch_entry(MetaBatchFn fn, int which, mi_engine* e, void* stream, const float* theta, const float* data,
-                            const int64_t* labels, int tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order,
-                            int with_grad, float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out, void* workspace,
-                            size_t workspace_bytes, const LrCall* lrc = nullptr) {
-  if (!e || !e->graph_on || e->prof_on || e->trace || e->bn_export || !stream)     // (capture is not permitted on the legacy default stream)
-    return fn(e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, inner_lr, second_order, with_grad, loss_out, acc_out,
-              meta_grad_out, logits_out, workspace, workspace_bytes, lrc);
+// ---- graph replay of the fused calls
+// What a captured graph depends on, field by field (never the struct's bytes: its padding is indeterminate): two calls whose keys are equal
+// make the same launches with the same arguments.  Every engine switch and the kernel selection in an element of its own: nothing packed,
+// nothing that can alias.  The step sizes' VALUES are read on the device at every replay, like theta's.
+static GraphKey graph_key(const mi_engine* e, void* stream, const MetaCall& c) {
+  typedef unsigned long long u;
   unsigned lr_bits;
-  memcpy(&lr_bits, &inner_lr, sizeof lr_bits);
-  const std::vector<unsigned long long> key = {
-      (unsigned long long)which, (unsigned long long)(uintptr_t)stream, (unsigned long long)(uintptr_t)theta,
-      (unsigned long long)(uintptr_t)data, (unsigned long long)(uintptr_t)labels, (unsigned long long)tasks, (unsigned long long)ways,
-      (unsigned long long)shots, (unsigned long long)adapt_steps, (unsigned long long)lr_bits, (unsigned long long)second_order,
-      (unsigned long long)with_grad, (unsigned long long)(uintptr_t)loss_out, (unsigned long long)(uintptr_t)acc_out,
-      (unsigned long long)(uintptr_t)meta_grad_out, (unsigned long long)(uintptr_t)logits_out, (unsigned long long)(uintptr_t)workspace,
-      (unsigned long long)workspace_bytes,
-      // every engine switch and the kernel selection in an element of its own: nothing packed, nothing that can alias
-      (unsigned long long)e->fuse1, (unsigned long long)e->gram1, (unsigned long long)e->gramq, (unsigned long long)e->overlap,
-      (unsigned long long)e->fuse_fin, (unsigned long long)e->fuse_b1red, (unsigned long long)e->fuse_tail, (unsigned long long)e->fuse_last,
-      kernel_selection_key(),
-      // the step-size buffers of mi_meta_batch_maml_lr (their VALUES are read on the device at every replay)
-      (unsigned long long)(uintptr_t)(lrc ? lrc->lr_vec : nullptr), (unsigned long long)(lrc ? lrc->lr_steps : 0),
-      (unsigned long long)(uintptr_t)(lrc ? lrc->lr_grad_out : nullptr)};
+  memcpy(&lr_bits, &c.inner_lr, sizeof lr_bits);
+  return GraphKey{(u)c.algo, (u)(uintptr_t)stream, (u)(uintptr_t)c.theta, (u)(uintptr_t)c.data, (u)(uintptr_t)c.labels, (u)c.tasks,
+                  (u)c.grad_tasks, (u)c.ways, (u)c.shots, (u)c.adapt_steps, (u)c.second_order, (u)lr_bits, (u)(uintptr_t)c.lr_vec,
+                  (u)c.lr_steps, (u)(uintptr_t)c.lr_grad_out, (u)(uintptr_t)c.loss_out, (u)(uintptr_t)c.acc_out,
+                  (u)(uintptr_t)c.meta_grad_out, (u)(uintptr_t)c.logits_out, (u)(uintptr_t)c.workspace, (u)c.workspace_bytes,
+                  (u)e->fuse1, (u)e->gram1, (u)e->gramq, (u)e->overlap, (u)e->fuse_fin, (u)e->fuse_b1red, (u)e->fuse_tail, (u)e->fuse_last,
+                  kernel_selection_key()};
+}
+
+static int meta_batch_entry(mi_engine* e, void* stream, const MetaCall& c) {
+  const int crc = check_call(e, c);
+  if (crc) return crc;
+  const auto fn = c.algo == ALGO_ANIL ? meta_batch_anil_impl : meta_batch_maml_impl;
+  if (!e->graph_on || e->prof_on || e->trace || e->bn_export || !stream)     // (capture is not permitted on the legacy default stream)
+    return fn(e, stream, c);
+  const GraphKey key = graph_key(e, stream, c);
   mi_engine::GraphEntry* ent = nullptr;
   for (auto& g : e->graphs)
     if (g.key == key) { ent = &g; break; }
@@ -1454,13 +1479,11 @@ static int meta_batch_entry(MetaBatchFn fn, int which, mi_engine* e, void* strea
     e->graphs.push_back(mi_engine::GraphEntry{});
     e->graphs.back().key = key;
     e->graphs.back().seen = 1;
-    return fn(e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, inner_lr, second_order, with_grad, loss_out, acc_out,
-              meta_grad_out, logits_out, workspace, workspace_bytes, lrc);
+    return fn(e, stream, c);
   }
   // second sight: capture the launch sequence (nothing executes), instantiate, launch
   HIPCHK(e, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-  const int rc = fn(e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, inner_lr, second_order, with_grad, loss_out, acc_out,
-                    meta_grad_out, logits_out, workspace, workspace_bytes, lrc);
+  const int rc = fn(e, stream, c);
   hipGraph_t graph = nullptr;
   const hipError_t ce = hipStreamEndCapture(st, &graph);
   if (rc != MI_OK || ce != hipSuccess || !graph) {
@@ -1484,8 +1507,9 @@ extern "C" int mi_meta_batch_maml(mi_engine* e, void* stream, const float* theta
                                   int tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order,
                                   int with_grad, float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
                                   void* workspace, size_t workspace_bytes) {
-  return meta_batch_entry(meta_batch_maml_impl, 0, e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, inner_lr,
-                          second_order, with_grad ? tasks : 0, loss_out, acc_out, meta_grad_out, logits_out, workspace, workspace_bytes);
+  return meta_batch_entry(e, stream, MetaCall{ALGO_MAML, theta, data, labels, tasks, with_grad ? tasks : 0, ways, shots, adapt_steps,
+                                              second_order, inner_lr, nullptr, 0, nullptr, loss_out, acc_out, meta_grad_out, logits_out,
+                                              workspace, workspace_bytes});
 }
 // Train and validation halves of one meta-iteration in the same launches (reference maml_vision.py:102-124): the first grad_tasks
 // tasks are the train tasks (their summed meta-gradient goes to meta_grad_out), the rest are adapted and scored only.
@@ -1493,9 +1517,9 @@ extern "C" int mi_meta_batch_maml_tv(mi_engine* e, void* stream, const float* th
                                      int tasks, int grad_tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order,
                                      float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
                                      void* workspace, size_t workspace_bytes) {
-  if (grad_tasks < 0 || grad_tasks > tasks) return fail(e, MI_ERR_ARG, "grad_tasks must be in 0..tasks");
-  return meta_batch_entry(meta_batch_maml_impl, 0, e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, inner_lr,
-                          second_order, grad_tasks, loss_out, acc_out, meta_grad_out, logits_out, workspace, workspace_bytes);
+  return meta_batch_entry(e, stream, MetaCall{ALGO_MAML, theta, data, labels, tasks, grad_tasks, ways, shots, adapt_steps, second_order,
+                                              inner_lr, nullptr, 0, nullptr, loss_out, acc_out, meta_grad_out, logits_out, workspace,
+                                              workspace_bytes});
 }
 // mi_meta_batch_maml_tv with one step size per parameter (and per inner step when lr_steps == adapt_steps), read from device memory, and
 // the gradient of the summed query loss with respect to them (include/mi_maml.h).
@@ -1503,51 +1527,29 @@ extern "C" int mi_meta_batch_maml_lr(mi_engine* e, void* stream, const float* th
                                      int grad_tasks, int ways, int shots, int adapt_steps, const float* lr_vec, int lr_steps,
                                      int second_order, float* loss_out, float* acc_out, float* meta_grad_out, float* lr_grad_out,
                                      float* logits_out, void* workspace, size_t workspace_bytes) {
-  if (grad_tasks < 0 || grad_tasks > tasks) return fail(e, MI_ERR_ARG, "grad_tasks must be in 0..tasks");
-  // (here, not in the implementation: before the graph cache and any HIP call)
-  if (lr_steps != 1 && (adapt_steps <= 0 || lr_steps != adapt_steps))
-    return fail(e, MI_ERR_ARG, "lr_steps = " + std::to_string(lr_steps) + " must be 1 or adapt_steps = " + std::to_string(adapt_steps) +
-                                   (adapt_steps == 0 ? " (without inner steps: 1)" : ""));
-  if (!lr_vec) return fail(e, MI_ERR_ARG, "lr_vec is NULL: mi_meta_batch_maml_lr takes lr_steps * P step sizes on the device");
-  if (lr_grad_out && grad_tasks == 0)
-    return fail(e, MI_ERR_ARG, "lr_grad_out given but grad_tasks = 0: the step-size gradient is summed over the train tasks");
-  const LrCall lrc{lr_vec, lr_steps, lr_grad_out};
-  return meta_batch_entry(meta_batch_maml_impl, 2, e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, 0.f, second_order,
-                          grad_tasks, loss_out, acc_out, meta_grad_out, logits_out, workspace, workspace_bytes, &lrc);
+  return meta_batch_entry(e, stream, MetaCall{ALGO_MAML_LR, theta, data, labels, tasks, grad_tasks, ways, shots, adapt_steps, second_order,
+                                              0.f, lr_vec, lr_steps, lr_grad_out, loss_out, acc_out, meta_grad_out, logits_out, workspace,
+                                              workspace_bytes});
 }
 extern "C" int mi_meta_batch_anil(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
                                   int tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order,
                                   int with_grad, float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
                                   void* workspace, size_t workspace_bytes) {
-  return meta_batch_entry(meta_batch_anil_impl, 1, e, stream, theta, data, labels, tasks, ways, shots, adapt_steps, inner_lr,
-                          second_order, with_grad, loss_out, acc_out, meta_grad_out, logits_out, workspace, workspace_bytes);
+  return meta_batch_entry(e, stream, MetaCall{ALGO_ANIL, theta, data, labels, tasks, with_grad ? tasks : 0, ways, shots, adapt_steps,
+                                              second_order, inner_lr, nullptr, 0, nullptr, loss_out, acc_out, meta_grad_out, logits_out,
+                                              workspace, workspace_bytes});
 }
 
 // Plain forward of the classifier (BatchNorm in train mode, i.e. statistics of the n images of each task batch), no
 // adaptation: `learner(x)` / `model(x)` of the reference (vision_models.py:51-55,107-110).
 extern "C" int mi_forward_logits(mi_engine* e, void* stream, const float* theta, const float* x, int tasks, int n,
                                  float* logits_out, void* workspace, size_t workspace_bytes) {
-  if (!e) return fail(nullptr, MI_ERR_ARG, "null engine");
-  if (!theta || !x || !logits_out || !workspace || tasks < 1 || n < 1) return fail(e, MI_ERR_ARG, "bad forward arguments");
-  ExportPause no_export(e);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  Plan pl;
-  make_plan(e, workspace, tasks, n, n, 0, 0, pl);
-  if (pl.bytes > workspace_bytes)
-    return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes) + " bytes");
-  { const int brc = plan_begin(e, st, pl); if (brc) return brc; }
-  LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, x, (size_t)tasks * n, e->d.in_channels, e->d.in_h, e->d.in_w, pl.xq));
-  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, theta, 0, e->perm_dev, (int)e->P, (int)e->PS, tasks, pl.theta));
-  HIPCHK(e, hipMemsetAsync(pl.yq, 0, (size_t)tasks * n * sizeof(int32_t), st));
-  return pass_fwd_bwd(e, st, pl, pl.qry, pl.xq, pl.yq, n, tasks, pl.theta, pl.lam, pl.tmp_loss, pl.tmp_acc, logits_out, false);
+  return mi_learner_forward(e, stream, theta, 1, x, tasks, n, logits_out, 0, nullptr, workspace, workspace_bytes);   // its shared-theta case
 }
 
 extern "C" int mi_forward_workspace_bytes(const mi_engine* e, int tasks, int n, size_t* bytes) {
   if (!e || !bytes || tasks < 1 || n < 1) return MI_ERR_ARG;
-  Plan pl;
-  make_plan(e, nullptr, tasks, n, n, 0, 0, pl);
-  *bytes = pl.bytes;
-  return MI_OK;
+  return plan_bytes(e, forward_shape(tasks, n), bytes);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1555,14 +1557,31 @@ extern "C" int mi_forward_workspace_bytes(const mi_engine* e, int tasks, int n, 
 // misc_scripts/cl_vision.py:56-66, misc_scripts/rc_vision.py:66-86, core_functions/maml.py:15-19).  The fast weights live
 // with the caller (theta [theta_tasks][P], reference order); forward and backward are two stateless calls, the backward
 // re-runs the forward into the workspace instead of keeping activations alive between calls.
-static int learner_args(mi_engine* e, const float* theta, int theta_tasks, const float* x, int tasks, int n, void* workspace,
-                        size_t workspace_bytes, Plan& pl) {
+// What the three learner calls open with: the checks, the plan of shape s in the workspace, plan_begin, x as NHWC in the plan's image
+// buffer `ximg` (pl.xq, or pl.xs for the kept pass of mi_learner_hvp) and the weights gathered into pl.theta.  `bad`: what is wrong with the
+// call's own arguments, or nullptr.
+static int learner_begin(mi_engine* e, hipStream_t st, const float* theta, int theta_tasks, const float* x, int tasks, int n, const char* bad,
+                         void* workspace, size_t workspace_bytes, const PlanShape& s, Plan& pl, float* Plan::*ximg) {
   if (!e) return fail(nullptr, MI_ERR_ARG, "null engine");
   if (!theta || !x || !workspace || tasks < 1 || n < 1) return fail(e, MI_ERR_ARG, "bad learner arguments");
   if (theta_tasks != 1 && theta_tasks != tasks) return fail(e, MI_ERR_ARG, "theta_tasks must be 1 (shared) or == tasks");
-  make_plan(e, workspace, tasks, n, n, 0, 0, pl);
-  if (pl.bytes > workspace_bytes)
-    return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes) + " bytes");
+  if (bad) return fail(e, MI_ERR_ARG, bad);
+  int rc = plan_in(e, workspace, workspace_bytes, s, pl);
+  if (rc) return rc;
+  rc = plan_begin(e, st, pl);
+  if (rc) return rc;
+  LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, x, (size_t)tasks * n, e->d.in_channels, e->d.in_h, e->d.in_w, pl.*ximg));
+  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, theta, theta_tasks == 1 ? 0 : e->P, e->perm_dev, (int)e->P, (int)e->PS, tasks, pl.theta));
+  return MI_OK;
+}
+// ... and what the two that return gradients end with: g (engine layout, per task) to the caller's [theta_tasks][P], summed over the tasks
+// when they share one theta.
+static int learner_scatter(mi_engine* e, hipStream_t st, const float* g, int theta_tasks, int tasks, float* out) {
+  if (theta_tasks == 1) {
+    LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, g, e->perm_dev, (int)e->P, (int)e->PS, tasks, out));
+  } else {
+    LAUNCH(e, st, OP_MISC, 3, launch_scatter_tasks(st, g, e->perm_dev, (int)e->P, (int)e->PS, tasks, out));
+  }
   return MI_OK;
 }
 
@@ -1586,17 +1605,12 @@ extern "C" int mi_learner_forward(mi_engine* e, void* stream, const float* theta
                                   int n, float* logits_out, int rep_layer, float* rep_out, void* workspace,
                                   size_t workspace_bytes) {
   Plan pl;
-  int rc = learner_args(e, theta, theta_tasks, x, tasks, n, workspace, workspace_bytes, pl);
-  if (rc) return rc;
-  ExportPause no_export(e);
-  const int nl = (int)e->L.size();
-  if (rep_out && (rep_layer < 1 || rep_layer > nl)) return fail(e, MI_ERR_ARG, "rep_layer must be in 1..layers");
-  if (!logits_out && !rep_out) return fail(e, MI_ERR_ARG, "nothing to compute: logits_out and rep_out are both NULL");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  rc = plan_begin(e, st, pl);
+  const char* bad = (e && rep_out && (rep_layer < 1 || rep_layer > (int)e->L.size())) ? "rep_layer must be in 1..layers"
+                    : (!logits_out && !rep_out) ? "nothing to compute: logits_out and rep_out are both NULL" : nullptr;
+  ExportPause no_export(e);
+  int rc = learner_begin(e, st, theta, theta_tasks, x, tasks, n, bad, workspace, workspace_bytes, forward_shape(tasks, n), pl, &Plan::xq);
   if (rc) return rc;
-  LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, x, (size_t)tasks * n, e->d.in_channels, e->d.in_h, e->d.in_w, pl.xq));
-  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, theta, theta_tasks == 1 ? 0 : e->P, e->perm_dev, (int)e->P, (int)e->PS, tasks, pl.theta));
   HIPCHK(e, hipMemsetAsync(pl.yq, 0, (size_t)tasks * n * sizeof(int32_t), st));
   rc = pass_fwd_bwd(e, st, pl, pl.qry, pl.xq, pl.yq, n, tasks, pl.theta, pl.lam, pl.tmp_loss, pl.tmp_acc, logits_out, false);
   if (rc) return rc;
@@ -1611,23 +1625,14 @@ extern "C" int mi_learner_backward(mi_engine* e, void* stream, const float* thet
                                    const float* dlogits, int tasks, int n, float* grad_out, void* workspace,
                                    size_t workspace_bytes) {
   Plan pl;
-  int rc = learner_args(e, theta, theta_tasks, x, tasks, n, workspace, workspace_bytes, pl);
-  if (rc) return rc;
-  ExportPause no_export(e);
-  if (!dlogits || !grad_out) return fail(e, MI_ERR_ARG, "null dlogits / grad_out");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  rc = plan_begin(e, st, pl);
+  ExportPause no_export(e);
+  int rc = learner_begin(e, st, theta, theta_tasks, x, tasks, n, (!dlogits || !grad_out) ? "null dlogits / grad_out" : nullptr, workspace,
+                         workspace_bytes, forward_shape(tasks, n), pl, &Plan::xq);
   if (rc) return rc;
-  LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, x, (size_t)tasks * n, e->d.in_channels, e->d.in_h, e->d.in_w, pl.xq));
-  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, theta, theta_tasks == 1 ? 0 : e->P, e->perm_dev, (int)e->P, (int)e->PS, tasks, pl.theta));
   rc = learner_fwd_bwd(e, st, pl, pl.qry, pl.xq, dlogits, n, tasks, pl.lam);
   if (rc) return rc;
-  if (theta_tasks == 1) {
-    LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, pl.lam, e->perm_dev, (int)e->P, (int)e->PS, tasks, grad_out));
-  } else {
-    LAUNCH(e, st, OP_MISC, 3, launch_scatter_tasks(st, pl.lam, e->perm_dev, (int)e->P, (int)e->PS, tasks, grad_out));
-  }
-  return MI_OK;
+  return learner_scatter(e, st, pl.lam, theta_tasks, tasks, grad_out);
 }
 
 // Double backward of the step-wise learner: with s(theta) = sum(logits(theta) * dlogits) and g = ds/dtheta (mi_learner_backward),
@@ -1638,42 +1643,27 @@ extern "C" int mi_learner_backward(mi_engine* e, void* stream, const float* thet
 // and an ordinary mi_learner_backward, by the chain rule autograd already applies.
 extern "C" int mi_learner_hvp_workspace_bytes(const mi_engine* e, int tasks, int n, size_t* bytes) {
   if (!e || !bytes || tasks < 1 || n < 1) return MI_ERR_ARG;
-  Plan pl;
-  make_plan(e, nullptr, tasks, n, n, 1, 1, pl);
-  *bytes = pl.bytes;
-  return MI_OK;
+  return plan_bytes(e, hvp_shape(tasks, n), bytes);
 }
 
 extern "C" int mi_learner_hvp(mi_engine* e, void* stream, const float* theta, int theta_tasks, const float* x, const float* dlogits,
                               const float* v, int tasks, int n, float* grad_theta_out, float* logits_dot_out, void* workspace,
                               size_t workspace_bytes) {
-  if (!e) return fail(nullptr, MI_ERR_ARG, "null engine");
-  if (!theta || !x || !dlogits || !v || !grad_theta_out || !logits_dot_out || !workspace || tasks < 1 || n < 1)
-    return fail(e, MI_ERR_ARG, "bad mi_learner_hvp arguments");
-  if (theta_tasks != 1 && theta_tasks != tasks) return fail(e, MI_ERR_ARG, "theta_tasks must be 1 (shared) or == tasks");
-  ExportPause no_export(e);
   Plan pl;
-  make_plan(e, workspace, tasks, n, n, 1, 1, pl);
-  if (pl.bytes > workspace_bytes)
-    return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes) + " bytes");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const size_t pstride = theta_tasks == 1 ? 0 : e->P;
-  { const int brc = plan_begin(e, st, pl); if (brc) return brc; }
+  ExportPause no_export(e);
+  int rc = learner_begin(e, st, theta, theta_tasks, x, tasks, n,
+                         (!dlogits || !v || !grad_theta_out || !logits_dot_out) ? "bad mi_learner_hvp arguments" : nullptr, workspace,
+                         workspace_bytes, hvp_shape(tasks, n), pl, &Plan::xs);
+  if (rc) return rc;
   ActSet& A = pl.sup[0];
-  LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, x, (size_t)tasks * n, e->d.in_channels, e->d.in_h, e->d.in_w, pl.xs));
-  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, theta, pstride, e->perm_dev, (int)e->P, (int)e->PS, tasks, pl.theta));
-  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, v, pstride, e->perm_dev, (int)e->P, (int)e->PS, tasks, pl.lam));
+  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, v, theta_tasks == 1 ? 0 : e->P, e->perm_dev, (int)e->P, (int)e->PS, tasks, pl.lam));
   // primal backward with the given cotangent: the tangent sweep needs its BatchNorm sums (g) and layer cotangents (A.dp)
-  int rc = learner_fwd_bwd(e, st, pl, A, pl.xs, dlogits, n, tasks, pl.g);
+  rc = learner_fwd_bwd(e, st, pl, A, pl.xs, dlogits, n, tasks, pl.g);
   if (rc) return rc;
   rc = pass_hvp(e, st, pl, A, pl.xs, n, tasks, pl.theta, pl.g, pl.lam, pl.hv, nullptr, dlogits, logits_dot_out);
   if (rc) return rc;
-  if (theta_tasks == 1) {
-    LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, pl.hv, e->perm_dev, (int)e->P, (int)e->PS, tasks, grad_theta_out));
-  } else {
-    LAUNCH(e, st, OP_MISC, 3, launch_scatter_tasks(st, pl.hv, e->perm_dev, (int)e->P, (int)e->PS, tasks, grad_theta_out));
-  }
-  return MI_OK;
+  return learner_scatter(e, st, pl.hv, theta_tasks, tasks, grad_theta_out);
 }
 
 extern "C" int mi_adam_step(void* stream, float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n,

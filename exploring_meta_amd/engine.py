@@ -177,6 +177,14 @@ class MetaEngine:
         cur.wait_stream(gs)
         return rc
 
+    def _persistent(self, key, make):
+        """make(): fresh tensors, or (graph mode, where a replay writes where the captured call wrote) the persistent ones under `key`."""
+        if not getattr(self, '_graph', False):
+            return make()
+        if key not in self._persist:
+            self._persist[key] = make()
+        return self._persist[key]
+
     def _outputs(self, kind, T, nlog, with_grad, return_logits):
         """(loss, acc, grad, logits) buffers of one fused call: fresh tensors, or the persistent set of this shape in graph mode."""
         def fresh():
@@ -186,12 +194,7 @@ class MetaEngine:
             buf = torch.empty(P + 2 * T, dtype=torch.float32, device=self.device)
             return (buf[P:P + T], buf[P + T:], buf[:P] if with_grad else None,
                     torch.empty(T, nlog, self.spec.ways, dtype=torch.float32, device=self.device) if return_logits else None)
-        if not getattr(self, '_graph', False):
-            return fresh()
-        key = (kind, T, nlog, bool(with_grad), bool(return_logits))
-        if key not in self._persist:
-            self._persist[key] = fresh()
-        return self._persist[key]
+        return self._persistent((kind, T, nlog, bool(with_grad), bool(return_logits)), fresh)
 
     def set_bn_export(self, tasks=0, passes=0):
         """mi_engine_set_bn_export: while on, every fused call also leaves the BatchNorm batch statistics of each of its forward
@@ -232,6 +235,60 @@ class MetaEngine:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def _check_batch(self, theta, data, labels, shots, lr_vec=None, flat_data=True):
+        """Shapes, dtypes and contiguity of a fused call's tensors; returns T.  flat_data: one-channel images may come without the
+        channel axis."""
+        s = self.spec
+        T = data.shape[0]
+        n2 = 2 * shots * s.ways
+        if tuple(data.shape) != (T, n2, s.in_channels, s.in_h, s.in_w) and \
+                not (flat_data and s.in_channels == 1 and data.numel() == T * n2 * s.in_h * s.in_w):
+            raise ValueError(f'data shape {tuple(data.shape)} does not match [T, {n2}, {s.in_channels}, {s.in_h}, {s.in_w}]')
+        if tuple(labels.shape) != (T, n2):
+            raise ValueError(f'labels shape {tuple(labels.shape)} != {(T, n2)}')
+        if theta.numel() != self.param_count:
+            raise ValueError(f'theta has {theta.numel()} elements, the model has {self.param_count}')
+        for t, dt in ((theta, torch.float32), (data, torch.float32), (labels, torch.int64)) + (((lr_vec, torch.float32),) if lr_vec is not None else ()):
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                raise ValueError('theta/data/lr_vec must be contiguous fp32 CUDA tensors and labels contiguous int64 CUDA')
+        return T
+
+    def _maml_call(self, theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, first_order, grad_tasks, want_lr_grad, return_logits):
+        """mi_meta_batch_maml_tv, or mi_meta_batch_maml_lr when the step sizes are a vector.  Returns (loss, acc, grad, lr_grad, logits)."""
+        s = self.spec
+        T = self._check_batch(theta, data, labels, shots, lr_vec)
+        if lr_vec is not None:
+            # the library sizes its reads of lr_vec from lr_steps and P: a buffer of another size is refused here, before any launch
+            if lr_vec.numel() % self.param_count != 0 or lr_vec.numel() == 0 or lr_vec.dim() > 2 or \
+                    (lr_vec.dim() == 2 and lr_vec.shape[1] != self.param_count):
+                raise _lib.MiError(f'libmi_maml error -1: lr_vec has shape {tuple(lr_vec.shape)}, expected [P], [1, P] or [adapt_steps, P] '
+                                   f'with P = {self.param_count}')
+            lr_steps = lr_vec.numel() // self.param_count
+        if not 0 <= grad_tasks <= T:
+            raise ValueError(f'grad_tasks must be in 0..{T}, got {grad_tasks}')
+        with_grad = grad_tasks > 0
+        so = (not first_order) and with_grad
+        b = C.c_size_t(0 if lr_vec is not None else self.workspace_bytes(T, shots, adapt_steps, so))
+        if lr_vec is not None and self.lib.mi_workspace_bytes_lr(self._h, T, s.ways, shots, adapt_steps, int(so), lr_steps,
+                                                                 int(bool(want_lr_grad)), C.byref(b)):
+            raise _lib.MiError(f'libmi_maml error -1: lr_steps = {lr_steps} must be 1 or adapt_steps = {adapt_steps}')
+        ws = self._workspace(b.value)
+        loss, acc, grad, logits = self._outputs('maml' if lr_vec is None else 'maml_lr', T, shots * s.ways, with_grad, return_logits)
+        head = (_ptr(theta), _ptr(data), _ptr(labels), T, int(grad_tasks), s.ways, shots, adapt_steps)
+        tail = (_ptr(logits), _ptr(ws), ws.numel())
+        lr_grad = None
+        if lr_vec is None:
+            rc = self._fused_call(self.lib.mi_meta_batch_maml_tv, *head, float(inner_lr), int(not first_order), _ptr(loss), _ptr(acc), _ptr(grad),
+                                  *tail)
+        else:
+            if want_lr_grad:
+                lr_grad = self._persistent(('lr_grad', T, lr_steps),
+                                           lambda: torch.empty(lr_steps, self.param_count, dtype=torch.float32, device=self.device))
+            rc = self._fused_call(self.lib.mi_meta_batch_maml_lr, *head, _ptr(lr_vec), lr_steps, int(not first_order), _ptr(loss), _ptr(acc),
+                                  _ptr(grad), _ptr(lr_grad), *tail)
+        _lib.check(rc, self._h)
+        return loss, acc, grad, lr_grad, logits
+
     @_on_device
     def meta_batch(self, theta, data, labels, shots, adapt_steps, inner_lr, first_order=False, with_grad=True,
                    return_logits=False, grad_tasks=None):
@@ -239,31 +296,10 @@ class MetaEngine:
         int64.  Returns (loss[T], acc[T], meta_grad[P] summed over tasks or None, logits [T, S*W, ways] or None).
         grad_tasks = G (0 < G < T): the first G tasks are the meta-iteration's TRAIN tasks (the meta-gradient is summed over them), the
         other T - G its VALIDATION tasks, adapted and scored in the same launches without a backward half (maml_vision.py:117-124)."""
-        s = self.spec
-        T = data.shape[0]
-        n2 = 2 * shots * s.ways
-        if tuple(data.shape) != (T, n2, s.in_channels, s.in_h, s.in_w) and \
-                not (s.in_channels == 1 and data.numel() == T * n2 * s.in_h * s.in_w):
-            raise ValueError(f'data shape {tuple(data.shape)} does not match [T, {n2}, {s.in_channels}, {s.in_h}, {s.in_w}]')
-        if tuple(labels.shape) != (T, n2):
-            raise ValueError(f'labels shape {tuple(labels.shape)} != {(T, n2)}')
-        if theta.numel() != self.param_count:
-            raise ValueError(f'theta has {theta.numel()} elements, the model has {self.param_count}')
-        for t, dt in ((theta, torch.float32), (data, torch.float32), (labels, torch.int64)):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise ValueError('theta/data must be contiguous fp32 CUDA tensors and labels contiguous int64 CUDA')
         if grad_tasks is None:
-            grad_tasks = T if with_grad else 0
-        if not 0 <= grad_tasks <= T:
-            raise ValueError(f'grad_tasks must be in 0..{T}, got {grad_tasks}')
-        with_grad = grad_tasks > 0
-        so = (not first_order) and with_grad
-        ws = self._workspace(self.workspace_bytes(T, shots, adapt_steps, so))
-        loss, acc, grad, logits = self._outputs('maml', T, shots * s.ways, with_grad, return_logits)
-        rc = self._fused_call(self.lib.mi_meta_batch_maml_tv, _ptr(theta), _ptr(data), _ptr(labels), T, int(grad_tasks), s.ways, shots,
-                              adapt_steps, float(inner_lr), int(not first_order), _ptr(loss),
-                              _ptr(acc), _ptr(grad), _ptr(logits), _ptr(ws), ws.numel())
-        _lib.check(rc, self._h)
+            grad_tasks = data.shape[0] if with_grad else 0
+        loss, acc, grad, _, logits = self._maml_call(theta, data, labels, shots, adapt_steps, inner_lr, None, first_order, grad_tasks, False,
+                                                     return_logits)
         return loss, acc, grad, logits
 
     @_on_device
@@ -274,50 +310,8 @@ class MetaEngine:
         device by every call, graph replays included.  grad_tasks = None: every task is a train task; 0: evaluation only.
         Returns (loss[T], acc[T], meta_grad[P] or None, lr_grad [lr_steps, P] or None, logits or None); lr_grad (``want_lr_grad``) is
         the gradient of the summed query loss of the train tasks with respect to lr_vec."""
-        s = self.spec
-        T = data.shape[0]
-        n2 = 2 * shots * s.ways
-        if tuple(data.shape) != (T, n2, s.in_channels, s.in_h, s.in_w) and \
-                not (s.in_channels == 1 and data.numel() == T * n2 * s.in_h * s.in_w):
-            raise ValueError(f'data shape {tuple(data.shape)} does not match [T, {n2}, {s.in_channels}, {s.in_h}, {s.in_w}]')
-        if tuple(labels.shape) != (T, n2):
-            raise ValueError(f'labels shape {tuple(labels.shape)} != {(T, n2)}')
-        if theta.numel() != self.param_count:
-            raise ValueError(f'theta has {theta.numel()} elements, the model has {self.param_count}')
-        for t, dt in ((theta, torch.float32), (data, torch.float32), (labels, torch.int64), (lr_vec, torch.float32)):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise ValueError('theta/data/lr_vec must be contiguous fp32 CUDA tensors and labels contiguous int64 CUDA')
-        # the library sizes its reads of lr_vec from lr_steps and P: a buffer of another size is refused here, before any launch
-        if lr_vec.numel() % self.param_count != 0 or lr_vec.numel() == 0 or lr_vec.dim() > 2 or \
-                (lr_vec.dim() == 2 and lr_vec.shape[1] != self.param_count):
-            raise _lib.MiError(f'libmi_maml error -1: lr_vec has shape {tuple(lr_vec.shape)}, expected [P], [1, P] or [adapt_steps, P] '
-                               f'with P = {self.param_count}')
-        lr_steps = lr_vec.numel() // self.param_count
-        if grad_tasks is None:
-            grad_tasks = T
-        if not 0 <= grad_tasks <= T:
-            raise ValueError(f'grad_tasks must be in 0..{T}, got {grad_tasks}')
-        with_grad = grad_tasks > 0
-        so = (not first_order) and with_grad
-        b = C.c_size_t()
-        if self.lib.mi_workspace_bytes_lr(self._h, T, s.ways, shots, adapt_steps, int(so), lr_steps, int(bool(want_lr_grad)), C.byref(b)):
-            raise _lib.MiError(f'libmi_maml error -1: lr_steps = {lr_steps} must be 1 or adapt_steps = {adapt_steps}')
-        ws = self._workspace(b.value)
-        loss, acc, grad, logits = self._outputs('maml_lr', T, shots * s.ways, with_grad, return_logits)
-        lr_grad = None
-        if want_lr_grad:
-            if getattr(self, '_graph', False):
-                key = ('lr_grad', T, lr_steps)
-                if key not in self._persist:
-                    self._persist[key] = torch.empty(lr_steps, self.param_count, dtype=torch.float32, device=self.device)
-                lr_grad = self._persist[key]
-            else:
-                lr_grad = torch.empty(lr_steps, self.param_count, dtype=torch.float32, device=self.device)
-        rc = self._fused_call(self.lib.mi_meta_batch_maml_lr, _ptr(theta), _ptr(data), _ptr(labels), T, int(grad_tasks), s.ways, shots,
-                              adapt_steps, _ptr(lr_vec), lr_steps, int(not first_order), _ptr(loss), _ptr(acc), _ptr(grad), _ptr(lr_grad),
-                              _ptr(logits), _ptr(ws), ws.numel())
-        _lib.check(rc, self._h)
-        return loss, acc, grad, lr_grad, logits
+        return self._maml_call(theta, data, labels, shots, adapt_steps, None, lr_vec, first_order,
+                               data.shape[0] if grad_tasks is None else grad_tasks, want_lr_grad, return_logits)
 
     @_on_device
     def meta_batch_anil(self, theta, data, labels, shots, adapt_steps, inner_lr, first_order=False, with_grad=True,
@@ -325,15 +319,7 @@ class MetaEngine:
         """ANIL (reference vision/anil_vision.py:116-122): theta = [features.parameters()..., head.weight, head.bias] flat;
         the trunk sees all 2*shots*ways images of a task at once, only the head is adapted.  Same returns as meta_batch."""
         s = self.spec
-        T = data.shape[0]
-        n2 = 2 * shots * s.ways
-        if tuple(data.shape) != (T, n2, s.in_channels, s.in_h, s.in_w) or tuple(labels.shape) != (T, n2):
-            raise ValueError(f'data/labels shapes {tuple(data.shape)}/{tuple(labels.shape)} do not match T x {n2} task rows')
-        if theta.numel() != self.param_count:
-            raise ValueError(f'theta has {theta.numel()} elements, trunk + head have {self.param_count}')
-        for t, dt in ((theta, torch.float32), (data, torch.float32), (labels, torch.int64)):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise ValueError('theta/data must be contiguous fp32 CUDA tensors and labels contiguous int64 CUDA')
+        T = self._check_batch(theta, data, labels, shots, flat_data=False)
         b = C.c_size_t()
         _lib.check(self.lib.mi_anil_workspace_bytes(self._h, T, s.ways, shots, adapt_steps, C.byref(b)), self._h)
         ws = self._workspace(b.value)

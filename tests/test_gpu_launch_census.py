@@ -3,7 +3,8 @@
 The equivalence tests compare results; this one pins the launch sequence's make-up, so that a change of the engine's host code (csrc/engine.hip)
 that adds, drops or relabels a launch shows even where the results survive it.  The table holds counts only and was recorded once, with
 tools/record_launch_census.py, from a build of the commit BEFORE the primal and tangent sweeps were folded into one (MI_MAML_LIB selects the
-library): never from the code under test.  Counts do not depend on the device's size.  Profiling runs every call eagerly (no graph replay)."""
+library), the rows of the step-size-vector call (maml_lr_*) from the commit before the fused calls got one call descriptor: never from the
+code under test.  Counts do not depend on the device's size.  Profiling runs every call eagerly (no graph replay)."""
 import json
 import os
 from collections import OrderedDict
@@ -26,6 +27,11 @@ def _maml(net='min', shots=1, K=2, tasks=(0, 1, 2), first_order=False, with_grad
                 grad_tasks=grad_tasks, switches=switches)
 
 
+def _maml_lr(lr_steps=1, want_lr_grad=False, first_order=False, **switches):
+    """The step-size-vector call on the default MAML case's batch: 0.4 * U(0.5, 1.5) per entry."""
+    return dict(kind='maml_lr', lr_steps=lr_steps, want_lr_grad=want_lr_grad, first_order=first_order, switches=switches)
+
+
 # The smallest cases that reach every branch of trunk_forward / trunk_backward (5-way throughout).
 CASES = OrderedDict([
     # default MAML: mini-ImageNet net, 1-shot, K = 2, tasks 0..2
@@ -45,6 +51,11 @@ CASES = OrderedDict([
     # Omniglot net: stride 2, mean-pooled head
     ('omniglot', _maml(net='omni', K=1, tasks=(0, 1))),
     ('anil', dict(kind='anil', shots=1, K=2, tasks=[0, 1])),
+    ('maml_lr_default', _maml_lr()),
+    ('maml_lr_grad', _maml_lr(want_lr_grad=True)),
+    ('maml_lr_per_step_grad', _maml_lr(lr_steps=2, want_lr_grad=True)),
+    ('maml_lr_fused_tail_0_grad', _maml_lr(want_lr_grad=True, set_fused_tail=0)),
+    ('maml_lr_first_order_grad', _maml_lr(want_lr_grad=True, first_order=True)),
 ] + [(f'learner_{how}_{call}', dict(kind='learner', call=call, per_task_theta=how == 'per_task_theta'))
      for how in ('shared_theta', 'per_task_theta') for call in ('forward', 'backward', 'hvp')])
 
@@ -74,6 +85,19 @@ def run_case(case, trace=False):
         out.update(loss=loss, acc=acc, grad=grad, logits=logits)
         if tr:
             out.update(('trace_' + k, v) for k, v in tr.items())
+    elif case['kind'] == 'maml_lr':   # mini-ImageNet net, 1-shot, K = 2, tasks 0..2
+        eng = MetaEngine(ModelSpec.mini_imagenet(WAYS))
+        for name, value in case['switches'].items():
+            getattr(eng, name)(value)
+        theta = R.flatten_params(OrderedDict((k, torch.from_numpy(v)) for k, v in
+                                             synthetic.ref_init_weights(R.param_shapes(R.mini_imagenet_spec(WAYS)), 11).items())).float().cuda()
+        data, labels = synthetic.make_meta_batch('min', [0, 1, 2], WAYS, 1)
+        lr_vec = torch.from_numpy(0.4 * (0.5 + synthetic.hash_uniform(5, (case['lr_steps'], eng.param_count)))).float().cuda()
+        eng.profile(True)
+        loss, acc, grad, lr_grad, logits = eng.meta_batch_lr(theta, torch.from_numpy(data).cuda(), torch.from_numpy(labels).cuda(), 1, 2, lr_vec,
+                                                             first_order=case['first_order'], want_lr_grad=case['want_lr_grad'],
+                                                             return_logits=True)
+        out.update(loss=loss, acc=acc, grad=grad, lr_grad=lr_grad, logits=logits)
     elif case['kind'] == 'anil':
         eng = MetaEngine(ModelSpec.anil(WAYS))
         base = dict(kind='min', in_shape=(3, 84, 84), base=R.convbase_spec(64, 3, True))

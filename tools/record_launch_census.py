@@ -6,6 +6,9 @@ from the code under test:
     git worktree add /tmp/before <commit> && make -C /tmp/before/exploring_meta_amd/csrc -j16
     MI_MAML_LIB=/tmp/before/exploring_meta_amd/csrc/libmi_maml.so python tools/record_launch_census.py [out.json]
 
+A third argument keeps the rows of an existing table and records only the cases whose names start with it (`... out.json maml_lr`): rows
+that judged earlier changes are not re-recorded when cases are added.
+
 Needs the GPU (the counts come from the engine's own per-launch profiling)."""
 import json
 import os
@@ -18,7 +21,12 @@ sys.path[:0] = [REPO, os.path.join(REPO, 'tests')]
 def main():
     import test_gpu_launch_census as census
     out = sys.argv[1] if len(sys.argv) > 1 else census.TABLE
-    table = {name: census.run_case(case)[0] for name, case in census.CASES.items()}
+    only = sys.argv[2] if len(sys.argv) > 2 else ''
+    table = {}
+    if only:
+        with open(census.TABLE) as f:
+            table = json.load(f)
+    table.update((name, census.run_case(case)[0]) for name, case in census.CASES.items() if name.startswith(only))
     with open(out, 'w') as f:
         json.dump(table, f, indent=1, sort_keys=True)
         f.write('\n')
