@@ -54,15 +54,42 @@ class MAML(torch.nn.Module):
 
     def lr_flat(self):
         """None while the step size is one number for every parameter (the scalar fused call); else the step sizes [steps, P] in
-        ``parameters()`` order: an ``InnerLR``'s, with zeros for parameters that do not require grad under ``allow_nograd``."""
+        ``parameters()`` order (around a policy: the engine's order, ``_engine_order``): an ``InnerLR``'s, with zeros for parameters
+        that do not require grad under ``allow_nograd``."""
         lr = self.lr
         nograd = [n for n, p in self.module.named_parameters() if not p.requires_grad] if self.allow_nograd else []
         if isinstance(lr, InnerLR):
-            return lr.flat(also_frozen=nograd)
+            return self._engine_order(lr.flat(also_frozen=nograd))
         if not nograd:
             return None
-        return torch.cat([torch.full((p.numel(),), 0.0 if not p.requires_grad else float(lr), dtype=torch.float32, device=p.device)
-                          for p in self.module.parameters()]).unsqueeze(0)
+        return self._engine_order(torch.cat([torch.full((p.numel(),), 0.0 if not p.requires_grad else float(lr), dtype=torch.float32,
+                                                        device=p.device) for p in self.module.parameters()]).unsqueeze(0))
+
+    def _engine_order(self, flat):
+        """Around a policy the step sizes leave in the ENGINE's parameter order (``_engine_params()``: sigma first), which is the order
+        of the fast weights and of the fused policy calls.  ``InnerLR.flat()`` follows ``named_parameters()``; for ``DiagNormalPolicy`` and
+        ``DiagNormalPolicyANIL`` that is the same order (a module's own parameters, ``sigma``, come before its children's), and nothing is
+        moved.  A policy that registers its parameters in another order (``sigma`` held by a child module, say) gets one differentiable
+        gather with an index built once from ``_engine_params()``, so gradients still reach ``InnerLR.values``.  Other modules: unchanged."""
+        if not self._is_policy():
+            return flat
+        perm = self.__dict__.get('_lr_perm')
+        if perm is None:
+            start, off = {}, 0
+            for p in self.module.parameters():
+                start[id(p)] = off
+                off += p.numel()
+            perm = torch.cat([torch.arange(start[id(q)], start[id(q)] + q.numel()) for q in self.module._engine_params()])
+            if perm.numel() != off:
+                raise RuntimeError(f'the policy has {off} parameters, its engine order names {perm.numel()}')
+            if torch.equal(perm, torch.arange(off)):
+                perm = False                              # DiagNormalPolicy(.ANIL): the two orders agree
+            self.__dict__['_lr_perm'] = perm
+        if perm is False:
+            return flat
+        if perm.device != flat.device:
+            perm = self.__dict__['_lr_perm'] = perm.to(flat.device)
+        return flat.index_select(1, perm)
 
     def _step_lr(self):
         """The step size(s) of this learner's next ``adapt``: the number, or the row of ``lr_flat`` for the step it is at."""
@@ -160,7 +187,7 @@ class MAML(torch.nn.Module):
             params = self.module._engine_params()
             gs = torch.autograd.grad(loss, params, retain_graph=second_order, create_graph=second_order, allow_unused=bool(allow_unused))
             g = torch.cat([(torch.zeros_like(p) if gi is None else gi).reshape(-1) for p, gi in zip(params, gs)])
-            self.__dict__['_fast'] = self.module.flat_parameters() - self.lr * g
+            self.__dict__['_fast'] = self.module.flat_parameters() - self._step_lr() * g
             self.__dict__['_steps_done'] += 1
             return
         theta = self.fast_weights()

@@ -437,7 +437,7 @@ def trpo_a2c_loss(episodes, learner, baseline, gamma, tau, update_vf=True):
 
 def _trpo_step(eng, inner_lr, head_only):
     """``step`` of the adapt loop for TRPO: mi_policy_adapt."""
-    return lambda theta, b, adv: eng.adapt(theta, b['states'], b['actions'], adv, b['count'], inner_lr, head_only=head_only)[0]
+    return lambda theta, b, adv, k=0: eng.adapt(theta, b['states'], b['actions'], adv, b['count'], inner_lr, head_only=head_only)[0]
 
 
 def trpo_update(episodes, learner, baseline, inner_lr, gamma, tau, anil=False, first_order=False):
@@ -445,6 +445,7 @@ def trpo_update(episodes, learner, baseline, inner_lr, gamma, tau, anil=False, f
     second-order dependence on the original parameters is handled inside meta_optimize_trpo's fused calls)."""
     # anil only sets allow_unused (rl.py:371): which parameters move is decided by the policy's own switch -- with
     # DiagNormalPolicyANIL.turn_off_body_grads() the body's gradients are None and maml_update leaves it unchanged.
+    _refuse_lr_vector(learner, 'trpo_update')
     b = _replay_batch([_as_replay(episodes)], learner.input_size, learner.output_size, learner.sigma.device)
     adv, _ = _batch_advantages(b, baseline, gamma, tau)
     step = _trpo_step(learner.engine(), inner_lr, bool(getattr(learner, 'features_no_grad', False)))
@@ -456,7 +457,7 @@ def trpo_update(episodes, learner, baseline, inner_lr, gamma, tau, anil=False, f
 def _adapt_loop(run, step, theta, steps, baseline, gamma, tau, normalize, keep_views=False):
     """THE adapt loop of fast_adapt_trpo / _vpg / _ppo and their ``*_tasks`` forms: ``steps`` support steps -- ``run(k, theta)`` rolls
     out a padded batch with the parameters so far ([P] shared, or [R, P]), its advantages are taken with the baseline re-fitted
-    (``_batch_advantages``, ``normalize`` as given), ``step(theta, batch, adv)`` returns the updated parameters [R, P] -- and the
+    (``_batch_advantages``, ``normalize`` as given), ``step(theta, batch, adv, k)`` returns the updated parameters [R, P] -- and the
     query run.  Returns (theta after the last step, the support batches with their advantages under 'adv', the query batch, the
     baseline weights [R, 2S+4] of the last fit or None, and with ``keep_views`` per replay row the ``Replay`` views of its runs --
     one read of the row counts per run, the only synchronisation of the loop -- else None)."""
@@ -472,7 +473,7 @@ def _adapt_loop(run, step, theta, steps, baseline, gamma, tau, normalize, keep_v
             return theta, sups, batch, wts, views
         batch['adv'], wts = _batch_advantages(batch, baseline, gamma, tau, normalize=normalize)
         sups.append(batch)
-        theta = step(theta, batch, batch['adv'])
+        theta = step(theta, batch, batch['adv'], k)
 
 
 class _TaskWalk:
@@ -499,6 +500,7 @@ def fast_adapt_trpo(task, learner, baseline, params, anil=False, first_order=Fal
     """reference rl.py:377-406.  ``task.run(policy, episodes=n)`` returns a replay (dict or cherry-style object, ``_as_replay``).
     ``learner``: the policy itself or a ``MAML`` wrapper around it (rl/anil_trpo.py:84 wraps; rl.py:382,396 reach the policy as
     ``learner.module``)."""
+    _refuse_lr_vector(learner, 'fast_adapt_trpo')
     if anil:                                                   # rl.py:381-382
         _unwrap(learner).turn_off_body_grads()
     walk = _TaskWalk(task, learner, params, (lambda actor: _unwrap(actor).turn_on_body_grads()) if anil else None)
@@ -576,6 +578,7 @@ def fast_adapt_trpo_tasks(goals, policy, baseline, params, seed, first_id, anil=
     run k (the support steps, then the query) uses rollout id ``first_id + i * (adapt_steps + 1) + k`` -- what task i gets from
     ``fast_adapt_trpo`` with ``Particles2DRunner(goal, L, rollout='device', seed=seed, first_id=first_id + i * (adapt_steps + 1))``.
     ``baseline`` is left as after that task-by-task walk: fitted to the last task's last support replay."""
+    _refuse_lr_vector(policy, 'fast_adapt_trpo_tasks')
     pol = _unwrap(policy)
     T, run = _rollout_run('fast_adapt_trpo_tasks', pol, goals, params, seed, first_id)
     eng, A, E = pol.engine(), pol.output_size, params['adapt_batch_size']
@@ -742,6 +745,7 @@ def _conjugate_gradient_device(Ax, b, num_iterations, tol, eps):
 def meta_optimize_trpo(params, policy, baseline, iter_replays, iter_policies, anil=False):
     """reference rl.py:409-438: CG step direction from the Fisher-vector product of the mean KL, then backtracking line
     search on (surrogate loss, KL); updates ``policy`` in place.  Returns diagnostics."""
+    _refuse_lr_vector(policy, 'meta_optimize_trpo')
     ctx = _SurrogateContext(iter_replays, iter_policies, policy, baseline, params)
     theta = policy.flat()
     old_loss, old_kl, grad = ctx.evaluate(theta, want_grad=True)
@@ -808,26 +812,70 @@ class _PolicyMetaLoss(torch.autograd.Function):
         return (None, None, None) + tuple(outs)
 
 
-def _adapt_and_validate(run, pol, baseline, params, algo, anil, first_order, dice, keep_views=False):
+def _policy_lr_vector(learner):
+    """The step sizes [rows, P] (engine order, connected to a learnable ``InnerLR``) of a ``MAML`` wrapper that holds more than one
+    number for its policy; None for everything else -- the bare policy, a wrapper with a number: ``params['inner_lr']`` is the step."""
+    if not (hasattr(learner, 'lr_flat') and hasattr(learner, 'module')):
+        return None
+    return learner.lr_flat()
+
+
+def _lr_step_rows(lr_rows, adapt_steps):
+    """The row of the step-size table each adapt step reads: its own with one row per adapt step, row 0 with one row for all."""
+    if lr_rows not in (1, adapt_steps):
+        raise ValueError(f'the learner holds step sizes for {lr_rows} inner steps; adapt_steps is {adapt_steps} '
+                         '(InnerLR(steps=...) must be 1 or adapt_steps)')
+    return [s if lr_rows > 1 else 0 for s in range(adapt_steps)]
+
+
+def _refuse_lr_vector(learner, name):
+    """TRPO's outer step is a trust region over theta alone and its fused calls take one number: no silent fall-back to it."""
+    if _policy_lr_vector(learner) is not None:
+        raise ValueError(f"{name}: per-parameter inner-loop step sizes (an InnerLR, or allow_nograd) are taken by the VPG / PPO / DiCE "
+                         "calls only; the TRPO calls adapt with the one number params['inner_lr'] -- wrap the policy as MAML(policy, lr=number)")
+
+
+def _adapt_and_validate(run, pol, baseline, params, algo, anil, first_order, dice, keep_views=False, learner=None):
     """fast_adapt_vpg / fast_adapt_ppo (reference rl.py:231-255,267-318) for the R replay rows ``run`` rolls out -- all tasks of a
     meta-batch (``_rollout_run``) or one (``_TaskWalk``): the adapt loop with one mi_policy_update call per step (``ppo_epochs``
     epochs for PPO), the query's advantages (fitted like the others; normalised for PPO only, vpg_a2c_loss does not, rl.py:217),
     then ONE mi_policy_meta_batch call from the shared parameters over the support batches and the query.  Returns (the summed
     validation loss, 0-dim, whose ``.backward()`` accumulates the summed meta-gradient; the losses [R]; the adapted parameters the
-    query was rolled out with, [R, P] or the shared [P] without adapt steps; the query batch; the ``Replay`` views or None)."""
+    query was rolled out with, [R, P] or the shared [P] without adapt steps; the query batch; the ``Replay`` views or None).
+    ``learner``: what the caller was handed.  A ``MAML`` wrapper with per-parameter step sizes (``_policy_lr_vector``) takes the vector
+    calls (mi_policy_update_lr / mi_policy_meta_batch_lr): adapt step s reads row s of an ``InnerLR`` with ``steps == adapt_steps``,
+    row 0 of one with ``steps == 1`` (PPO's epochs share their adapt step's row), and ``.backward()`` also fills ``InnerLR.values.grad``."""
     eng = pol.engine()
     gamma, tau, lr = params['gamma'], params['tau'], params['inner_lr']
     epochs = params['ppo_epochs'] if algo == 'ppo' else 1
     clip = params.get('ppo_clip_ratio', 0.1)
     kind = 'ppo' if algo == 'ppo' else ('dice' if dice else 'a2c')
-    step = lambda theta, b, adv: eng.update(theta, b['states'], b['actions'], adv, b['count'], lr, loss=kind, epochs=epochs, clip=clip,
-                                            done=b['dones'] if kind == 'dice' else None, head_only=bool(anil))[0]
+    lrv = _policy_lr_vector(learner)
+    if lrv is None:
+        step = lambda theta, b, adv, k: eng.update(theta, b['states'], b['actions'], adv, b['count'], lr, loss=kind, epochs=epochs, clip=clip,
+                                                   done=b['dones'] if kind == 'dice' else None, head_only=bool(anil))[0]
+    else:
+        step_row = _lr_step_rows(lrv.shape[0], params['adapt_steps'])
+        rows = lrv.detach().to(pol.sigma.device, torch.float32).contiguous()
+        step = lambda theta, b, adv, k: eng.update(theta, b['states'], b['actions'], adv, b['count'], rows[step_row[k]], loss=kind, epochs=epochs,
+                                                   clip=clip, done=b['dones'] if kind == 'dice' else None, head_only=bool(anil))[0]
     theta0 = pol.flat()
     theta, sups, qry, _, views = _adapt_loop(run, step, theta0, params['adapt_steps'], baseline, gamma, tau, algo == 'ppo', keep_views)
     qry['adv'], _ = _batch_advantages(qry, baseline, gamma, tau, normalize=(algo == 'ppo'))
     sup, engine_qry = _stack_batches(sups, qry)
     step_batch = [b for b in range(len(sups)) for _ in range(epochs)]
     need = torch.is_grad_enabled() and any(q.requires_grad for q in pol.parameters())
+    if lrv is not None:
+        need_lr = torch.is_grad_enabled() and lrv.requires_grad
+        lt, _, grad, lr_grad = eng.meta_batch_lr(theta0, sup, engine_qry, step_batch, rows, [step_row[b] for b in step_batch], loss=kind,
+                                                 clip=clip, head_only=bool(anil), first_order=first_order, with_grad=need or need_lr,
+                                                 want_lr_grad=need_lr)
+        total = lt.sum()
+        if need or need_lr:                                    # the step tensor is one more differentiable input: lr_grad * gout
+            eparams = pol._engine_params() + ([lrv] if need_lr else [])
+            flat = torch.cat([grad, lr_grad.reshape(-1)]) if need_lr else grad
+            total = _PolicyMetaLoss.apply(total, flat, [q.shape for q in eparams], *eparams)
+        return total, lt, theta, qry, views
     lt, _, grad = eng.meta_batch(theta0, sup, engine_qry, step_batch, lr, loss=kind, clip=clip, head_only=bool(anil), first_order=first_order,
                                  with_grad=need)
     total = lt.sum()
@@ -843,7 +891,7 @@ def _adapt_task_walk(task, learner, baseline, params, algo, anil, first_order, d
     if anil:
         pol.turn_off_body_grads()
     walk = _TaskWalk(task, pol, params, (lambda actor: pol.turn_on_body_grads()) if anil else None)
-    valid_loss, _, _, _, _ = _adapt_and_validate(walk, pol, baseline, params, algo, anil, first_order, dice)
+    valid_loss, _, _, _, _ = _adapt_and_validate(walk, pol, baseline, params, algo, anil, first_order, dice, learner=learner)
     query = _as_replay(walk.replays[-1])
     rew = query['rewards'].sum().item() / params['adapt_batch_size']
     suc = get_ep_successes(query, params.get('max_path_length')) / params['adapt_batch_size']                          # rl.py:252,315
@@ -924,7 +972,7 @@ def _adapt_tasks(goals, policy, baseline, params, seed, first_id, algo, anil, fi
     """``_adapt_and_validate`` for all tasks on device rollouts -> ``AdaptedTasks``."""
     pol = _unwrap(policy)
     T, run = _rollout_run('fast_adapt_ppo_tasks' if algo == 'ppo' else 'fast_adapt_vpg_tasks', pol, goals, params, seed, first_id, stride)
-    total, lt, theta, qry, replays = _adapt_and_validate(run, pol, baseline, params, algo, anil, first_order, dice, want_replays)
+    total, lt, theta, qry, replays = _adapt_and_validate(run, pol, baseline, params, algo, anil, first_order, dice, want_replays, learner=policy)
     thetas = theta if theta.dim() == 2 else theta.unsqueeze(0).expand(T, -1)
     reward = qry['rewards'].sum(dim=1) / params['adapt_batch_size']
     # the device rollout records no success signal: what get_ep_successes counts for such replays (rl.py:69-71)

@@ -831,6 +831,66 @@ __global__ void head_mask_kernel(float* __restrict__ v, int p, int body_lo, int 
   if (i >= body_lo && i < body_hi) v[(size_t)blockIdx.y * p + i] = 0.f;
 }
 
+// ---- per-parameter step sizes (mi_policy_meta_batch_lr / mi_policy_update_lr): per-element kernels over [T][P], one thread per entry,
+// grid (ceil(P / 256), T).  lr is ONE row [P] of the step-size table; [body_lo, body_hi) is the head mask of head_only (the entries whose
+// step is 0 whatever lr holds; body_lo = body_hi without head_only).
+// out[t][i] = a[t*astride + i] - lr[i] * g[t][i], a separate multiply and subtract like axpy_bcast_kernel's; an entry whose step is exactly 0
+// (or masked) passes through bitwise.  a may be out (in place: mi_policy_update_lr), so neither is __restrict__.
+__global__ void lr_advance_kernel(const float* a, size_t astride, const float* __restrict__ g, const float* __restrict__ lr, int p, int body_lo,
+                                  int body_hi, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p) return;
+  const size_t t = blockIdx.y;
+  const float d = (i >= body_lo && i < body_hi) ? 0.f : lr[i];
+  const float av = a[t * astride + i];
+  out[t * p + i] = d == 0.f ? av : av - d * g[t * p + i];
+}
+// One adjoint advance: lam_k = lam_{k+1} - mask_m(hv) in place (hv NULL: lam is lam_K as the query pass left it), and for the update
+// below it (lr NULL: there is none) dir = d_{k-1} (.) lam_k, the direction of its tangent pass, and prod = m (.) g_{k-1} (.) lam_k, its
+// term of lr_grad (prod NULL: not wanted).  Masked and zero-step entries of dir, masked entries of prod, are exact zeros.
+__global__ void lr_adjoint_kernel(float* __restrict__ lam, const float* __restrict__ hv, const float* __restrict__ lr,
+                                  const float* __restrict__ g, int p, int body_lo, int body_hi, float* __restrict__ dir,
+                                  float* __restrict__ prod) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p) return;
+  const size_t o = (size_t)blockIdx.y * p + i;
+  const bool masked = i >= body_lo && i < body_hi;
+  float l = lam[o];
+  if (hv && !masked) {
+    l = l - hv[o];
+    lam[o] = l;
+  }
+  if (!lr) return;
+  const float d = masked ? 0.f : lr[i];
+  dir[o] = d == 0.f ? 0.f : d * l;
+  if (prod) prod[o] = masked ? 0.f : g[o] * l;
+}
+// lr_grad[r][i] = -(sum over the updates k of row r, ascending, and within an update over the tasks, ascending, of m g_k lam_{k+1}): ONE
+// fp64 chain per entry in that fixed order, rounded once -- bitwise reproducible, no atomics.  prod [K][T][P] holds the fp32 products of a
+// second-order call (lr_adjoint_kernel); a first-order call has lam_{k+1} = lam_K for every k and passes prod NULL: the same fp32 product
+// g[k][t][i] * lam[t][i] is formed here.  Grid (ceil(P / 256), lr_rows).  The rows travel as a kernel argument (no copy, no host sync).
+#define MI_POLICY_LR_MAX_STEPS 256
+#define MI_POLICY_LR_MAX_ROWS 65535   // the fold's gridDim.y
+struct LrRows { int32_t row[MI_POLICY_LR_MAX_STEPS]; };
+__global__ void lr_fold_kernel(const float* __restrict__ prod, const float* __restrict__ g, const float* __restrict__ lam, LrRows rows, int K,
+                               int T, int p, int body_lo, int body_hi, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p) return;
+  const int r = blockIdx.y;
+  double acc = 0.0;
+  if (!(i >= body_lo && i < body_hi)) {
+    for (int k = 0; k < K; ++k) {
+      if (rows.row[k] != r) continue;
+      for (int t = 0; t < T; ++t) {
+        const size_t o = ((size_t)k * T + t) * p + i;
+        const float v = prod ? prod[o] : g[o] * lam[(size_t)t * p + i];
+        acc += (double)v;
+      }
+    }
+  }
+  out[(size_t)r * p + i] = (float)(0.0 - acc);
+}
+
 struct StepSet { Acts a; float *dmu, *d2, *d1, *pre2, *pre1, *coef, *coef2; };
 struct MetaPlan {
   std::vector<StepSet> st;          // per inner update (second order) or one shared set
@@ -865,6 +925,37 @@ extern "C" int mi_policy_meta_workspace_bytes(const mi_policy* p, int tasks, int
   MetaPlan pl;
   meta_plan(p, nullptr, tasks, batch, steps, n_batches, second_order != 0, pl);
   *bytes = pl.bytes;
+  return MI_OK;
+}
+
+// The step-size-vector form of the call (mi_policy_meta_batch_lr).  Its plan lies BEHIND the scalar plan, whose offsets do not move: the
+// gradient of every update g [K][T][P] (the scalar call keeps one) and, second order, the products prod [K][T][P] -- both only when lr_grad
+// is wanted.  The tangent direction dir lies in the scalar plan's vmask slot.
+struct LrCall {
+  const float* vec;                 // device [rows][P]
+  int rows;
+  const int32_t* step_row;          // host [steps], or NULL = all 0
+  float* grad_out;                  // device [rows][P], or NULL
+  const char* fn;                   // the entry's name, for the argument errors
+};
+struct LrPlan { float *g, *prod; size_t bytes; };
+static void lr_plan(const mi_policy* p, void* ws, size_t scalar_bytes, int T, int K, bool so, bool want_lr_grad, LrPlan& lp) {
+  PBump b{reinterpret_cast<char*>(ws), scalar_bytes};
+  const size_t TP = (size_t)T * p->P;
+  lp.g = want_lr_grad ? b.f(TP * (K > 0 ? K : 1)) : nullptr;
+  lp.prod = want_lr_grad && so ? b.f(TP * (K > 0 ? K : 1)) : nullptr;
+  lp.bytes = align_up(b.off, 256);
+}
+extern "C" int mi_policy_meta_lr_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, int n_batches, int second_order,
+                                                 int lr_rows, int want_lr_grad, size_t* bytes) {
+  if (!p || !bytes || tasks < 1 || batch < 1 || steps < 0 || steps > MI_POLICY_LR_MAX_STEPS || n_batches < 0 || lr_rows < 1 ||
+      lr_rows > MI_POLICY_LR_MAX_ROWS)
+    return MI_ERR_ARG;
+  MetaPlan pl;
+  meta_plan(p, nullptr, tasks, batch, steps, n_batches, second_order != 0, pl);
+  LrPlan lp;
+  lr_plan(p, nullptr, pl.bytes, tasks, steps, second_order != 0, want_lr_grad != 0, lp);
+  *bytes = lp.bytes;
   return MI_OK;
 }
 
@@ -929,27 +1020,35 @@ static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta
                                   const int32_t* step_new_old, int n_batches, const float* s_states, const float* s_actions,
                                   const float* s_adv, const int32_t* s_count, const float* s_done, const float* q_states,
                                   const float* q_actions, const float* q_adv, const int32_t* q_count, const float* q_done, int tasks,
-                                  int batch, int loss_kind, float clip, float inner_lr, int head_only, int second_order,
-                                  int with_grad, float* loss_out, float* theta_out, float* grad_out, void* workspace,
+                                  int batch, int loss_kind, float clip, float inner_lr, const LrCall* lrc, int head_only,
+                                  int second_order, int with_grad, float* loss_out, float* theta_out, float* grad_out, void* workspace,
                                   size_t workspace_bytes) {
-  if (!p || !theta || !q_states || !q_actions || !q_adv || !loss_out || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
-  if (steps > 0 && (!step_batch || !s_states || !s_actions || !s_adv || n_batches < 1)) return pfail(p, MI_ERR_ARG, "support batches missing");
+  // lrc: the step-size-vector form (mi_policy_meta_batch_lr), whose texts name the entry; NULL: the scalar entries, texts as they were
+  const std::string fn = lrc ? std::string(lrc->fn) + ": " : std::string();
+  if (!p || !theta || !q_states || !q_actions || !q_adv || !loss_out || !workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
+  if (steps > 0 && (!step_batch || !s_states || !s_actions || !s_adv || n_batches < 1)) return pfail(p, MI_ERR_ARG, fn + "support batches missing");
   if (loss_kind != MI_PLOSS_A2C && loss_kind != MI_PLOSS_PPO && loss_kind != MI_PLOSS_DICE)
-    return pfail(p, MI_ERR_ARG, "loss_kind must be MI_PLOSS_A2C, MI_PLOSS_PPO or MI_PLOSS_DICE");
+    return pfail(p, MI_ERR_ARG, fn + "loss_kind must be MI_PLOSS_A2C, MI_PLOSS_PPO or MI_PLOSS_DICE");
   if (loss_kind == MI_PLOSS_DICE && (!q_done || (steps > 0 && !s_done)))
-    return pfail(p, MI_ERR_ARG, "the DiCE objective needs the episode-end flags of every replay (s_done / q_done)");
-  if (loss_kind == MI_PLOSS_PPO && steps > 0 && !step_new_old) return pfail(p, MI_ERR_ARG, "PPO needs step_new_old");
-  if (with_grad && !grad_out) return pfail(p, MI_ERR_ARG, "grad_out is NULL but with_grad != 0");
+    return pfail(p, MI_ERR_ARG, fn + "the DiCE objective needs the episode-end flags of every replay (s_done / q_done)");
+  if (loss_kind == MI_PLOSS_PPO && steps > 0 && !step_new_old) return pfail(p, MI_ERR_ARG, fn + "PPO needs step_new_old");
+  if (with_grad && !grad_out) return pfail(p, MI_ERR_ARG, fn + "grad_out is NULL but with_grad != 0");
   for (int k = 0; k < steps; ++k)
-    if (step_batch[k] < 0 || step_batch[k] >= n_batches) return pfail(p, MI_ERR_ARG, "step_batch entry out of range");
+    if (step_batch[k] < 0 || step_batch[k] >= n_batches) return pfail(p, MI_ERR_ARG, fn + "step_batch entry out of range");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch, K = steps;
   const size_t P = p->P, TB = (size_t)T * B, TP = (size_t)T * P;
   const bool so = second_order && with_grad;
   MetaPlan pl;
   meta_plan(p, workspace, T, B, K, n_batches, so, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes));
+  LrPlan lp{nullptr, nullptr, pl.bytes};
+  if (lrc) lr_plan(p, workspace, pl.bytes, T, K, so, lrc->grad_out != nullptr, lp);
+  if (lp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(lp.bytes));
   const int body_lo = (int)p->o_w1, body_hi = (int)p->o_w3;          // W1, b1, W2, b2
+  const dim3 pgrid(ceil_div((int)P, 256), T);
+  const int m_lo = head_only ? body_lo : 0, m_hi = head_only ? body_hi : 0;      // the vector kernels fold the head mask in
+  auto lr_row = [&](int k) { return lrc->vec + (size_t)(lrc->step_row ? lrc->step_row[k] : 0) * P; };
+  auto g_of = [&](int k) { return lp.g ? lp.g + (size_t)k * TP : pl.g; };         // kept per update when lr_grad is wanted
   auto mask = [&](float* v) {
     if (head_only) hipLaunchKernelGGL(head_mask_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (int)P, body_lo, body_hi);
   };
@@ -973,11 +1072,15 @@ static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta
       int rc = meta_old_logp(p, st, T, B, s, th, xs, as, cn, olp);
       if (rc) return rc;
     }
-    int rc = primal(s, th, xs, as, ad, cn, loss_kind, olp, 0, pl.g, pl.hv /* scratch for the step loss */,
+    int rc = primal(s, th, xs, as, ad, cn, loss_kind, olp, 0, g_of(k), pl.hv /* scratch for the step loss */,
                     s_done ? s_done + (size_t)bi * TB : nullptr);
     if (rc) return rc;
-    mask(pl.g);
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, th, P, pl.g, inner_lr, (int)P, th + TP);
+    if (lrc) {
+      hipLaunchKernelGGL(lr_advance_kernel, pgrid, dim3(256), 0, st, th, P, g_of(k), lr_row(k), (int)P, m_lo, m_hi, th + TP);
+    } else {
+      mask(pl.g);
+      hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, th, P, pl.g, inner_lr, (int)P, th + TP);
+    }
     PCHK(p, hipGetLastError());
   }
   float* thK = pl.theta + (size_t)K * TP;
@@ -989,6 +1092,17 @@ static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta
   if (!with_grad) return MI_OK;
   // ---- adjoint recursion through the updates
   if (so) {
+    // the vector form drives the tangent pass of update k with dir = d_k (.) lam_{k+1} (in vmask) and subtracts H_k dir as it comes: the
+    // advance that finishes lam_{k+1} also writes the dir (and the lr_grad products) of update k
+    auto adjoint = [&](const float* hv, int k) {      // k: the update whose dir / prod to write, -1 = none
+      hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, pl.lam, hv, k >= 0 ? lr_row(k) : (const float*)nullptr,
+                         k >= 0 ? (const float*)g_of(k) : (const float*)nullptr, (int)P, m_lo, m_hi, pl.vmask,
+                         k >= 0 && lp.prod ? lp.prod + (size_t)k * TP : (float*)nullptr);
+    };
+    if (lrc && K > 0) {
+      adjoint(nullptr, K - 1);
+      PCHK(p, hipGetLastError());
+    }
     for (int k = K - 1; k >= 0; --k) {
       StepSet& s = pl.st[k];
       const float* th = pl.theta + (size_t)k * TP;
@@ -997,8 +1111,10 @@ static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta
       const float* as = s_actions + (size_t)bi * TB * p->A;
       const int32_t* cn = s_count ? s_count + (size_t)bi * T : nullptr;
       // v = [mask] lam ; hv = H_k v
-      PCHK(p, hipMemcpyAsync(pl.vmask, pl.lam, TP * sizeof(float), hipMemcpyDeviceToDevice, st));
-      mask(pl.vmask);
+      if (!lrc) {
+        PCHK(p, hipMemcpyAsync(pl.vmask, pl.lam, TP * sizeof(float), hipMemcpyDeviceToDevice, st));
+        mask(pl.vmask);
+      }
       PCHK(p, hipMemsetAsync(pl.hv, 0, TP * sizeof(float), st));
       rc = mlp_tangent_forward(p, st, T, B, xs, th, P, s.a, pl.vmask, pl.ta);
       if (rc) return rc;
@@ -1014,13 +1130,24 @@ static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta
       PCHK(p, hipGetLastError());
       rc = mlp_tangent_backward(p, st, T, B, xs, th, P, s.a, pl.ta, pl.vmask, s.dmu, s.d2, s.d1, s.pre2, s.pre1, pl.rdmu, pl.r2, pl.r1, pl.hv);
       if (rc) return rc;
-      mask(pl.hv);      // the body sat under no_grad during the update: no path from theta_{k+1} back into it
-      hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.lam, P, pl.hv, inner_lr, (int)P, pl.lam);
+      if (lrc) {
+        adjoint(pl.hv, k - 1);
+      } else {
+        mask(pl.hv);      // the body sat under no_grad during the update: no path from theta_{k+1} back into it
+        hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.lam, P, pl.hv, inner_lr, (int)P, pl.lam);
+      }
       PCHK(p, hipGetLastError());
     }
   }
   hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.lam, T, (int)P, 1.f, (const float*)nullptr, 0.f, grad_out);
   PCHK(p, hipGetLastError());
+  if (lrc && lrc->grad_out) {       // first order: lam_{k+1} = lam_K for every k, still in pl.lam; the fold forms the products itself
+    LrRows rows;
+    for (int k = 0; k < MI_POLICY_LR_MAX_STEPS; ++k) rows.row[k] = k < K && lrc->step_row ? lrc->step_row[k] : 0;
+    hipLaunchKernelGGL(lr_fold_kernel, dim3(ceil_div((int)P, 256), lrc->rows), dim3(256), 0, st, (const float*)lp.prod, (const float*)lp.g,
+                       (const float*)pl.lam, rows, K, T, (int)P, m_lo, m_hi, lrc->grad_out);
+    PCHK(p, hipGetLastError());
+  }
   return MI_OK;
 }
 
@@ -1032,7 +1159,7 @@ extern "C" int mi_policy_meta_batch(mi_policy* p, void* stream, const float* the
                                     float* theta_out, float* grad_out, void* workspace, size_t workspace_bytes) {
   if (loss_kind == MI_PLOSS_DICE) return pfail(p, MI_ERR_ARG, "MI_PLOSS_DICE needs the episode-end flags: call mi_policy_meta_batch_dones");
   return policy_meta_batch_impl(p, stream, theta, steps, step_batch, step_new_old, n_batches, s_states, s_actions, s_adv, s_count, nullptr,
-                                q_states, q_actions, q_adv, q_count, nullptr, tasks, batch, loss_kind, clip, inner_lr, head_only,
+                                q_states, q_actions, q_adv, q_count, nullptr, tasks, batch, loss_kind, clip, inner_lr, nullptr, head_only,
                                 second_order, with_grad, loss_out, theta_out, grad_out, workspace, workspace_bytes);
 }
 // The same with the replays' episode-end flags (cherry `dones`: s_done [n_batches, tasks, batch], q_done [tasks, batch]; 1 at
@@ -1045,7 +1172,34 @@ extern "C" int mi_policy_meta_batch_dones(mi_policy* p, void* stream, const floa
                                           int second_order, int with_grad, float* loss_out, float* theta_out, float* grad_out,
                                           void* workspace, size_t workspace_bytes) {
   return policy_meta_batch_impl(p, stream, theta, steps, step_batch, step_new_old, n_batches, s_states, s_actions, s_adv, s_count, s_done,
-                                q_states, q_actions, q_adv, q_count, q_done, tasks, batch, loss_kind, clip, inner_lr, head_only,
+                                q_states, q_actions, q_adv, q_count, q_done, tasks, batch, loss_kind, clip, inner_lr, nullptr, head_only,
+                                second_order, with_grad, loss_out, theta_out, grad_out, workspace, workspace_bytes);
+}
+// The step-size-vector form (include/mi_maml.h): the same implementation with lr_vec; every check of its own comes before any HIP call.
+extern "C" int mi_policy_meta_batch_lr(mi_policy* p, void* stream, const float* theta, int steps, const int32_t* step_batch,
+                                       const int32_t* step_new_old, const int32_t* step_lr_row, int n_batches, const float* s_states,
+                                       const float* s_actions, const float* s_adv, const int32_t* s_count, const float* s_done,
+                                       const float* q_states, const float* q_actions, const float* q_adv, const int32_t* q_count,
+                                       const float* q_done, int tasks, int batch, int loss_kind, float clip, const float* lr_vec, int lr_rows,
+                                       int head_only, int second_order, int with_grad, float* loss_out, float* theta_out, float* grad_out,
+                                       float* lr_grad_out, void* workspace, size_t workspace_bytes) {
+  const std::string fn = "mi_policy_meta_batch_lr: ";
+  if (!p) return pfail(nullptr, MI_ERR_ARG, fn + "null policy handle");
+  if (!lr_vec) return pfail(p, MI_ERR_ARG, fn + "lr_vec is NULL");
+  if (lr_rows < 1 || lr_rows > MI_POLICY_LR_MAX_ROWS)
+    return pfail(p, MI_ERR_ARG, fn + "lr_rows " + std::to_string(lr_rows) + " (must be 1.." + std::to_string(MI_POLICY_LR_MAX_ROWS) + ")");
+  if (tasks < 1) return pfail(p, MI_ERR_ARG, fn + "tasks " + std::to_string(tasks) + " (must be >= 1)");
+  if (batch < 1) return pfail(p, MI_ERR_ARG, fn + "batch " + std::to_string(batch) + " (must be >= 1)");
+  if (steps < 0 || steps > MI_POLICY_LR_MAX_STEPS)
+    return pfail(p, MI_ERR_ARG, fn + "steps " + std::to_string(steps) + " (must be 0.." + std::to_string(MI_POLICY_LR_MAX_STEPS) + ")");
+  for (int k = 0; step_lr_row && k < steps; ++k)
+    if (step_lr_row[k] < 0 || step_lr_row[k] >= lr_rows)
+      return pfail(p, MI_ERR_ARG, fn + "step_lr_row[" + std::to_string(k) + "] " + std::to_string(step_lr_row[k]) + " (must be 0.." +
+                                      std::to_string(lr_rows - 1) + ")");
+  if (lr_grad_out && !with_grad) return pfail(p, MI_ERR_ARG, fn + "lr_grad_out given but with_grad == 0");
+  const LrCall lrc{lr_vec, lr_rows, step_lr_row, lr_grad_out, "mi_policy_meta_batch_lr"};
+  return policy_meta_batch_impl(p, stream, theta, steps, step_batch, step_new_old, n_batches, s_states, s_actions, s_adv, s_count, s_done,
+                                q_states, q_actions, q_adv, q_count, q_done, tasks, batch, loss_kind, clip, 0.f, &lrc, head_only,
                                 second_order, with_grad, loss_out, theta_out, grad_out, workspace, workspace_bytes);
 }
 
@@ -1074,12 +1228,12 @@ __global__ void update_loss_transpose_kernel(const float* __restrict__ in, int E
   out[(size_t)t * E + e] = in[i];
 }
 #define MI_UPDATE_MAX_EPOCHS 64
-static int update_args(mi_policy* p, int tasks, int batch, int epochs) {
-  if (!p) return pfail(nullptr, MI_ERR_ARG, "mi_policy_update: null policy handle");
-  if (tasks < 1) return pfail(p, MI_ERR_ARG, "mi_policy_update: tasks " + std::to_string(tasks) + " (must be >= 1)");
-  if (batch < 1) return pfail(p, MI_ERR_ARG, "mi_policy_update: batch " + std::to_string(batch) + " (must be >= 1)");
+static int update_args(mi_policy* p, const std::string& fn, int tasks, int batch, int epochs) {
+  if (!p) return pfail(nullptr, MI_ERR_ARG, fn + "null policy handle");
+  if (tasks < 1) return pfail(p, MI_ERR_ARG, fn + "tasks " + std::to_string(tasks) + " (must be >= 1)");
+  if (batch < 1) return pfail(p, MI_ERR_ARG, fn + "batch " + std::to_string(batch) + " (must be >= 1)");
   if (epochs < 1 || epochs > MI_UPDATE_MAX_EPOCHS)
-    return pfail(p, MI_ERR_ARG, "mi_policy_update: epochs " + std::to_string(epochs) + " (must be 1.." + std::to_string(MI_UPDATE_MAX_EPOCHS) + ")");
+    return pfail(p, MI_ERR_ARG, fn + "epochs " + std::to_string(epochs) + " (must be 1.." + std::to_string(MI_UPDATE_MAX_EPOCHS) + ")");
   return MI_OK;
 }
 extern "C" int mi_policy_update_workspace_bytes(const mi_policy* p, int tasks, int batch, size_t* bytes) {
@@ -1089,27 +1243,29 @@ extern "C" int mi_policy_update_workspace_bytes(const mi_policy* p, int tasks, i
   *bytes = pl.bytes;
   return MI_OK;
 }
-extern "C" int mi_policy_update(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
-                                const float* actions, const float* adv, const int32_t* count, const float* done, int tasks,
-                                int batch, int loss_kind, int epochs, float clip, float lr, int head_only, float* theta_out,
-                                float* loss_out, void* workspace, size_t workspace_bytes) {
-  int rc = update_args(p, tasks, batch, epochs);
+// vector: mi_policy_update_lr -- the step of every epoch is lr_vec [P] (one row of the step-size table) in place of the number lr
+static int policy_update_impl(mi_policy* p, const std::string& fn, void* stream, const float* theta, size_t tstride, const float* states,
+                              const float* actions, const float* adv, const int32_t* count, const float* done, int tasks, int batch,
+                              int loss_kind, int epochs, float clip, float lr, bool vector, const float* lr_vec, int head_only,
+                              float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
+  int rc = update_args(p, fn, tasks, batch, epochs);
   if (rc) return rc;
-  if (!theta || !states || !actions || !adv || !theta_out || !workspace) return pfail(p, MI_ERR_ARG, "mi_policy_update: null argument");
+  if (vector && !lr_vec) return pfail(p, MI_ERR_ARG, fn + "lr_vec is NULL");
+  if (!theta || !states || !actions || !adv || !theta_out || !workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
   if (loss_kind != MI_PLOSS_A2C && loss_kind != MI_PLOSS_PPO && loss_kind != MI_PLOSS_DICE)
-    return pfail(p, MI_ERR_ARG, "mi_policy_update: loss_kind " + std::to_string(loss_kind) + " (must be MI_PLOSS_A2C, MI_PLOSS_PPO or MI_PLOSS_DICE)");
+    return pfail(p, MI_ERR_ARG, fn + "loss_kind " + std::to_string(loss_kind) + " (must be MI_PLOSS_A2C, MI_PLOSS_PPO or MI_PLOSS_DICE)");
   if (loss_kind == MI_PLOSS_DICE && !done)
-    return pfail(p, MI_ERR_ARG, "mi_policy_update: loss_kind MI_PLOSS_DICE needs the episode-end flags (done is NULL)");
+    return pfail(p, MI_ERR_ARG, fn + "loss_kind MI_PLOSS_DICE needs the episode-end flags (done is NULL)");
   if (tstride != 0 && tstride != p->P)
-    return pfail(p, MI_ERR_ARG, "mi_policy_update: tstride " + std::to_string(tstride) + " (must be 0 or P = " + std::to_string(p->P) + ")");
+    return pfail(p, MI_ERR_ARG, fn + "tstride " + std::to_string(tstride) + " (must be 0 or P = " + std::to_string(p->P) + ")");
   if (tstride == 0 && tasks > 1 && theta == theta_out)
-    return pfail(p, MI_ERR_ARG, "mi_policy_update: theta_out may alias theta only with tstride = P");
+    return pfail(p, MI_ERR_ARG, fn + "theta_out may alias theta only with tstride = P");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch;
   const size_t P = p->P;
   UpdatePlan pl;
   update_plan(p, workspace, T, B, epochs, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "mi_policy_update: workspace too small: need " + std::to_string(pl.bytes));
+  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(pl.bytes));
   const dim3 pgrid(ceil_div((int)P, 256), T);
   hipLaunchKernelGGL(axpy_bcast_kernel, pgrid, dim3(256), 0, st, theta, tstride, pl.g, 0.f, (int)P, theta_out);      // u_0
   PCHK(p, hipGetLastError());
@@ -1121,9 +1277,14 @@ extern "C" int mi_policy_update(mi_policy* p, void* stream, const float* theta, 
     rc = meta_primal(p, st, T, B, clip, pl.s, theta_out, P, states, actions, adv, count, loss_kind, pl.oldlp, 0, pl.g,
                      pl.loss_e + (size_t)e * T, done);
     if (rc) return rc;
-    if (head_only)
-      hipLaunchKernelGGL(head_mask_kernel, pgrid, dim3(256), 0, st, pl.g, (int)P, (int)p->o_w1, (int)p->o_w3);
-    hipLaunchKernelGGL(axpy_bcast_kernel, pgrid, dim3(256), 0, st, theta_out, P, pl.g, lr, (int)P, theta_out);   // in place, elementwise
+    if (vector) {                                             // the head mask folded into the advance, as in mi_policy_meta_batch_lr
+      hipLaunchKernelGGL(lr_advance_kernel, pgrid, dim3(256), 0, st, (const float*)theta_out, P, (const float*)pl.g, lr_vec, (int)P,
+                         head_only ? (int)p->o_w1 : 0, head_only ? (int)p->o_w3 : 0, theta_out);
+    } else {
+      if (head_only)
+        hipLaunchKernelGGL(head_mask_kernel, pgrid, dim3(256), 0, st, pl.g, (int)P, (int)p->o_w1, (int)p->o_w3);
+      hipLaunchKernelGGL(axpy_bcast_kernel, pgrid, dim3(256), 0, st, theta_out, P, pl.g, lr, (int)P, theta_out);   // in place, elementwise
+    }
     PCHK(p, hipGetLastError());
   }
   if (loss_out) {
@@ -1131,6 +1292,20 @@ extern "C" int mi_policy_update(mi_policy* p, void* stream, const float* theta, 
     PCHK(p, hipGetLastError());
   }
   return MI_OK;
+}
+extern "C" int mi_policy_update(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
+                                const float* actions, const float* adv, const int32_t* count, const float* done, int tasks,
+                                int batch, int loss_kind, int epochs, float clip, float lr, int head_only, float* theta_out,
+                                float* loss_out, void* workspace, size_t workspace_bytes) {
+  return policy_update_impl(p, "mi_policy_update: ", stream, theta, tstride, states, actions, adv, count, done, tasks, batch, loss_kind,
+                            epochs, clip, lr, false, nullptr, head_only, theta_out, loss_out, workspace, workspace_bytes);
+}
+extern "C" int mi_policy_update_lr(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
+                                   const float* actions, const float* adv, const int32_t* count, const float* done, int tasks,
+                                   int batch, int loss_kind, int epochs, float clip, const float* lr_vec, int head_only,
+                                   float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
+  return policy_update_impl(p, "mi_policy_update_lr: ", stream, theta, tstride, states, actions, adv, count, done, tasks, batch, loss_kind,
+                            epochs, clip, 0.f, true, lr_vec, head_only, theta_out, loss_out, workspace, workspace_bytes);
 }
 
 // =====================================================================================================================

@@ -727,11 +727,60 @@ class PolicyEngine:
         return loss_t, theta_out, grad
 
     @_on_device
+    def meta_batch_lr(self, theta, sup, qry, step_batch, lr_vec, step_lr_row=None, loss='a2c', clip=0.1, step_new_old=None, head_only=False,
+                      first_order=False, with_grad=True, want_lr_grad=True):
+        """``meta_batch`` with per-parameter step sizes (mi_policy_meta_batch_lr): lr_vec [rows, P] (or [P]) fp32 in the engine's
+        parameter order, update k reads row step_lr_row[k] (None: row 0).  Returns (loss [T], theta_adapted [T,P], grad [P] summed over
+        tasks or None, lr_grad [rows, P] = d sum_t loss / d lr_vec or None).  ``want_lr_grad`` needs ``with_grad``; loss='dice' takes
+        the replays' 'done' like ``meta_batch``."""
+        K = len(step_batch)
+        T, B = qry['states'].shape[0], qry['states'].shape[1]
+        NB = sup['states'].shape[0] if K else 0
+        kind = {'a2c': 0, 'ppo': 1, 'dice': 2}[loss]
+        P = self.param_count
+        lr_vec = lr_vec.detach()
+        if lr_vec.dim() == 1:
+            lr_vec = lr_vec.unsqueeze(0)
+        if lr_vec.dim() != 2 or lr_vec.shape[1] != P or lr_vec.dtype != torch.float32 or not lr_vec.is_cuda:
+            raise ValueError(f'lr_vec must be fp32 on the GPU, [rows, P] with P={P}, got {tuple(lr_vec.shape)} {lr_vec.dtype}')
+        lr_vec = lr_vec.contiguous()
+        rows = lr_vec.shape[0]
+        if step_lr_row is not None and len(step_lr_row) != K:
+            raise ValueError(f'step_lr_row holds {len(step_lr_row)} rows for {K} updates')
+        want_lr_grad = bool(want_lr_grad and with_grad)
+        sb = (C.c_int32 * max(K, 1))(*[int(x) for x in step_batch])
+        if step_new_old is None:
+            step_new_old = [1 if (k == 0 or step_batch[k] != step_batch[k - 1]) else 0 for k in range(K)]
+        sn = (C.c_int32 * max(K, 1))(*[int(x) for x in step_new_old])
+        sr = None if step_lr_row is None else (C.c_int32 * max(K, 1))(*[int(x) for x in step_lr_row])
+        if loss == 'dice' and ('done' not in qry or (K and 'done' not in sup)):
+            raise ValueError("loss='dice' needs the episode-end flags of every replay (key 'done', float32, like 'adv')")
+        b = C.c_size_t()
+        self._check(self.lib.mi_policy_meta_lr_workspace_bytes(self._h, T, B, K, NB, int(not first_order and with_grad), rows,
+                                                                int(want_lr_grad), C.byref(b)))
+        if self._ws is None or self._ws.numel() < b.value:
+            self._ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
+        loss_t = torch.empty(T, device=self.device)
+        theta_out = torch.empty(T, P, device=self.device)
+        grad = torch.empty(P, device=self.device) if with_grad else None
+        lr_grad = torch.empty(rows, P, device=self.device) if want_lr_grad else None
+        g = lambda d, k: _ptr(d[k].contiguous()) if d is not None and K else C.c_void_p(0)
+        dice = loss == 'dice'
+        self._check(self.lib.mi_policy_meta_batch_lr(
+            self._h, _stream(self.device), _ptr(theta.contiguous()), K, sb, sn, sr, NB, g(sup, 'states'), g(sup, 'actions'), g(sup, 'adv'),
+            g(sup, 'count'), g(sup, 'done') if dice else None, _ptr(qry['states'].contiguous()), _ptr(qry['actions'].contiguous()),
+            _ptr(qry['adv'].contiguous()), _ptr(qry['count'].contiguous()), _ptr(qry['done'].contiguous()) if dice else None, T, B, kind,
+            float(clip), _ptr(lr_vec), rows, int(head_only), int(not first_order), int(with_grad), _ptr(loss_t), _ptr(theta_out), _ptr(grad),
+            _ptr(lr_grad), _ptr(self._ws), self._ws.numel()))
+        return loss_t, theta_out, grad, lr_grad
+
+    @_on_device
     def update(self, theta, states, actions, adv, count, lr, loss='a2c', epochs=1, clip=0.1, done=None, head_only=False):
         """mi_policy_update: ``epochs`` plain updates of every task's parameters on its own replay (the inner update of
         fast_adapt_vpg / fast_adapt_ppo, reference rl.py:231-255,267-318; single_ppo_update, rl.py:319-336).  theta [P] (shared) or
         [T, P]; states [T,B,S], actions [T,B,A], adv [T,B], count [T] int32 or None, done [T,B] (loss='dice').  PPO takes the old
-        log-probabilities once, at the parameters the call starts from.  Returns (theta_out [T, P], loss [T, epochs]: the loss
+        log-probabilities once, at the parameters the call starts from.  ``lr``: a number, or a [P] fp32 tensor of per-parameter step
+        sizes in the engine's order (mi_policy_update_lr).  Returns (theta_out [T, P], loss [T, epochs]: the loss
         before each update).  No host synchronisation; the number of launches does not depend on T."""
         T, B = states.shape[0], states.shape[1]
         kind = {'a2c': 0, 'ppo': 1, 'dice': 2}[loss]
@@ -749,6 +798,14 @@ class PolicyEngine:
         stride = 0 if theta.dim() == 1 else self.param_count
         c = lambda t: None if t is None else t.contiguous()
         theta, states, actions, adv, count, done = c(theta), c(states), c(actions), c(adv), c(count), c(done)
+        if torch.is_tensor(lr):
+            lr = lr.detach()
+            if tuple(lr.shape) != (self.param_count,) or lr.dtype != torch.float32 or not lr.is_cuda:
+                raise ValueError(f'lr must be a number or an fp32 [P] tensor on the GPU with P={self.param_count}, got {tuple(lr.shape)} {lr.dtype}')
+            self._check(self.lib.mi_policy_update_lr(self._h, _stream(self.device), _ptr(theta), stride, _ptr(states), _ptr(actions), _ptr(adv),
+                                                     _ptr(count), _ptr(done), T, B, kind, int(epochs), float(clip), _ptr(lr.contiguous()),
+                                                     int(head_only), _ptr(out), _ptr(losses), _ptr(self._ws), self._ws.numel()))
+            return out, losses
         self._check(self.lib.mi_policy_update(self._h, _stream(self.device), _ptr(theta), stride, _ptr(states), _ptr(actions), _ptr(adv),
                                               _ptr(count), _ptr(done), T, B, kind, int(epochs), float(clip), float(lr), int(head_only),
                                               _ptr(out), _ptr(losses), _ptr(self._ws), self._ws.numel()))

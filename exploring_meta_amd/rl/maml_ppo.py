@@ -12,7 +12,12 @@ With ``--rollout device --batch_tasks`` a rank adapts its whole slice of the tas
 (``fast_adapt_ppo_tasks``: per adapt step one rollout, one advantage launch and one mi_policy_update call over all tasks, then one
 mi_policy_meta_batch call for the losses and the summed gradient), with the rollout ids the task loop uses.
 
+``--inner_lr_per tensor|parameter``, ``--learn_inner_lr``, ``--per_step_lr`` and ``--freeze PREFIX ...`` (the vision driver's flags) build
+``MAML(net, lr=InnerLR(...))``: one inner step size per tensor / entry / adapt step, meta-learned with the policy, tensors frozen by name
+prefix; the fused calls are then mi_policy_update_lr / mi_policy_meta_batch_lr.  The defaults build ``MAML(net, lr=inner_lr)``.
+
     python -m exploring_meta_amd.rl.maml_ppo --meta_batch_size 20 --num_iterations 5 [--anil] [--rollout device [--batch_tasks]]
+                                             [--inner_lr_per tensor --learn_inner_lr [--per_step_lr] [--freeze mean.0.]]
 """
 import argparse
 import os
@@ -21,7 +26,7 @@ import random
 import numpy as np
 import torch
 
-from ..core_functions import (MAML, DiagNormalPolicy, DiagNormalPolicyANIL, LinearValue, Particles2DRunner, fast_adapt_ppo,
+from ..core_functions import (MAML, DiagNormalPolicy, DiagNormalPolicyANIL, InnerLR, LinearValue, Particles2DRunner, fast_adapt_ppo,
                               fast_adapt_ppo_tasks, set_device)
 from ..sharding import init_process_group, shard_range
 
@@ -29,6 +34,17 @@ params = {
     'ppo_epochs': 3, 'ppo_clip_ratio': 0.1, 'inner_lr': 0.01, 'max_path_length': 100, 'adapt_steps': 1, 'adapt_batch_size': 20,
     'meta_batch_size': 20, 'outer_lr': 0.01, 'activation': 'tanh', 'tau': 1.0, 'gamma': 0.99, 'num_iterations': 10, 'seed': 42,
 }
+
+
+def inner_lr_of(net, p):
+    """The ``lr`` argument of ``MAML`` for these parameters: the plain number (the reference's run) unless one of --inner_lr_per /
+    --learn_inner_lr / --per_step_lr / --freeze asks for step sizes per parameter (the vision driver's flags; prefixes name the
+    policy's parameters: 'mean.0.', 'body.0.', 'head.', 'sigma')."""
+    per, learn, per_step, freeze = p.get('inner_lr_per', 'scalar'), p.get('learn_inner_lr', False), p.get('per_step_lr', False), \
+        tuple(p.get('freeze') or ())
+    if per == 'scalar' and not learn and not per_step and not freeze:
+        return p['inner_lr']
+    return InnerLR(net, p['inner_lr'], per=per, steps=max(p['adapt_steps'], 1) if per_step else 1, learnable=learn, frozen=freeze)
 
 
 def run(p, anil=False, log=print, rollout=None, batch_tasks=False):
@@ -48,7 +64,9 @@ def run(p, anil=False, log=print, rollout=None, batch_tasks=False):
     gen = torch.Generator(device=dev).manual_seed(p['seed'] + rank)
     baseline = LinearValue(2, 2)
     net = DiagNormalPolicyANIL(2, 2, 100) if anil else DiagNormalPolicy(2, 2, activation=p['activation'])
-    policy = MAML(net.to(dev), lr=p['inner_lr'])
+    net = net.to(dev)
+    # a learnable InnerLR is a submodule of the wrapper: Adam and the all-reduce below carry its values with policy.parameters()
+    policy = MAML(net, lr=inner_lr_of(net, p))
     meta_optimizer = torch.optim.Adam(policy.parameters(), lr=p['outer_lr'])
     T = p['meta_batch_size']
     lo, hi = shard_range(T, rank, world)
@@ -97,9 +115,15 @@ if __name__ == '__main__':
                         help='host: Python loop over the steps, torch-generator noise; device: one mi_particles_rollout call per run of a task')
     parser.add_argument('--batch_tasks', action='store_true',
                         help='adapt all tasks of a rank in one batched call per adapt step (needs --rollout device)')
+    parser.add_argument('--inner_lr_per', choices=('scalar', 'tensor', 'parameter'), default='scalar',
+                        help='one inner step size per model, per parameter tensor or per entry')
+    parser.add_argument('--learn_inner_lr', action='store_true', help='the inner step sizes are meta-learned with the policy (MetaSGD)')
+    parser.add_argument('--per_step_lr', action='store_true', help='one set of step sizes per adapt step')
+    parser.add_argument('--freeze', nargs='+', default=[], metavar='PREFIX', help="parameter-name prefixes that are not adapted (e.g. 'mean.0.')")
     args = parser.parse_args()
     if args.batch_tasks and args.rollout != 'device':
         parser.error('--batch_tasks needs --rollout device')
     for k in params:
         params[k] = getattr(args, k)
+    params.update(inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr, freeze=list(args.freeze))
     run(params, anil=args.anil, rollout=args.rollout, batch_tasks=args.batch_tasks)

@@ -727,6 +727,40 @@ int mi_policy_update(mi_policy* p, void* stream, const float* theta, size_t tstr
                      const float* adv, const int32_t* count, const float* done, int tasks, int batch, int loss_kind, int epochs,
                      float clip, float lr, int head_only, float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes);
 
+/* The two calls above with per-parameter inner-loop step sizes (learn2learn MetaSGD beside MAML; core_functions/inner_lr.py): lr_vec
+ * [lr_rows][P] on the device, in the engine's parameter order (sigma, W1, b1, W2, b2, W3, b3), shared by all tasks; update k reads row
+ * step_lr_row[k] (host array; NULL = every update reads row 0).  With m the head mask of head_only (1 on sigma, W3, b3, else 0; all ones
+ * without head_only) and d_k = lr_vec[row(k)] (.) m:
+ *   theta_{k+1} = theta_k - d_k (.) g_k,   g_k = grad L_k(theta_k)       (an entry whose step is exactly 0 passes through bitwise)
+ *   lam_K = grad L_query(theta_K);   second order: lam_k = lam_{k+1} - mask_m(H_k (d_k (.) lam_{k+1}));   first order: lam_k = lam_K
+ *   grad_out = SUM_t lam_0;   lr_grad_out[r] = - SUM_{k: row(k) = r} SUM_t m (.) g_k (.) lam_{k+1}      (NULL: not computed)
+ * -- d loss / d lr_vec, the MetaSGD gradient: at a frozen (zero-step) entry it is in general not 0; under head_only the body entries are
+ * exact zeros.  lr_grad_out is one fp64 chain per entry over the updates of its row, ascending, and within an update over the tasks,
+ * ascending, rounded once: bitwise reproducible.  steps == 0: exact zeros.  A uniform lr_vec is the scalar call up to rounding, bit for bit
+ * in loss_out, theta_out and the first-order grad_out, and in the second-order grad_out when the step is a power of two (the tangent pass
+ * is driven with d (.) lam where the scalar call scales H lam afterwards).  The same implementation as the scalar calls: their launches with
+ * the vector advance in place of the scalar one (head mask folded in), one launch per update of the adjoint recursion in place of copy +
+ * mask + mask + advance, one more at its start, and one for lr_grad_out; the count does not depend on `tasks`.  A task's theta_out /
+ * loss_out do not depend on the other tasks.  mi_policy_update_lr takes ONE row lr_vec [P] for every epoch of the call; from shared
+ * parameters its theta_out is bit-identical to mi_policy_meta_batch_lr(steps = epochs, with_grad = 0) on the same replay and row; its
+ * workspace is mi_policy_update_workspace_bytes.  s_done / q_done as in mi_policy_meta_batch_dones (NULL unless MI_PLOSS_DICE).
+ * Workspace: mi_policy_meta_lr_workspace_bytes -- the scalar plan, then g per update and (second order) the products, both only when
+ * want_lr_grad.  MI_ERR_ARG with a text naming the entry and the value, before any HIP call: lr_vec NULL, lr_rows outside 1..65535, steps outside
+ * 0..256, a step_lr_row entry outside 0..lr_rows-1, lr_grad_out with with_grad == 0, and every check of the scalar entries. */
+int mi_policy_meta_lr_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, int n_batches, int second_order, int lr_rows,
+                                      int want_lr_grad, size_t* bytes);
+int mi_policy_meta_batch_lr(mi_policy* p, void* stream, const float* theta, int steps, const int32_t* step_batch,
+                            const int32_t* step_new_old, const int32_t* step_lr_row, int n_batches, const float* s_states,
+                            const float* s_actions, const float* s_adv, const int32_t* s_count, const float* s_done,
+                            const float* q_states, const float* q_actions, const float* q_adv, const int32_t* q_count,
+                            const float* q_done, int tasks, int batch, int loss_kind, float clip, const float* lr_vec, int lr_rows,
+                            int head_only, int second_order, int with_grad, float* loss_out, float* theta_out, float* grad_out,
+                            float* lr_grad_out, void* workspace, size_t workspace_bytes);
+int mi_policy_update_lr(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states, const float* actions,
+                        const float* adv, const int32_t* count, const float* done, int tasks, int batch, int loss_kind, int epochs,
+                        float clip, const float* lr_vec, int head_only, float* theta_out, float* loss_out, void* workspace,
+                        size_t workspace_bytes);
+
 /* MAML-TRPO with `steps` >= 1 inner updates (params['adapt_steps'], one support replay per update, rl.py:447-453).
  * mi_trpo_surrogate_steps: meta_surrogate_loss (rl.py:441-473) with `steps` second-order inner updates per task: mean surrogate loss,
  * mean KL(new||old), and (grad_out != NULL) the gradient w.r.t. theta (rl.py:413-416).  old_loc [tasks,batch,A], old_scale [tasks,A]
