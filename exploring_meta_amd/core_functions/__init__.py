@@ -1,5 +1,5 @@
 """Mirror of the reference's ``core_functions`` package for the vision MAML/ANIL hot path."""
-from .vision import fast_adapt, accuracy, evaluate, meta_batch_adapt
+from .vision import fast_adapt, accuracy, evaluate, meta_batch_adapt, meta_batch_adapt_steps, evaluate_steps, msl_weights
 from .vision_models import OmniglotCNN, MiniImagenetCNN, ConvBase, ConvBlock
 from .maml import MAML
 from .inner_lr import InnerLR

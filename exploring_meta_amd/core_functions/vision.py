@@ -101,6 +101,81 @@ def meta_batch_adapt(learner, data, labels, adaptation_steps, shots, ways, first
                                  lr_flat, *params)
 
 
+def msl_weights(K, epoch, msl_epochs):
+    """The per-step loss importance vector of MAML++ (Antoniou et al., 2019) for K inner steps: uniform 1/K at epoch 0, then the K - 1
+    non-final weights decay linearly to the floor 0.03/K over ``msl_epochs`` epochs while the final one takes what they give up.
+    Returns K floats that sum to 1 (w_1 .. w_K: the weight of the query loss after 1 .. K steps)."""
+    K = int(K)
+    if K < 1 or msl_epochs <= 0:
+        raise ValueError('msl_weights needs K >= 1 and msl_epochs > 0')
+    decay, floor = 1.0 / (K * msl_epochs), 0.03 / K
+    w = [max(1.0 / K - epoch * decay, floor)] * (K - 1)
+    return w + [min(1.0 / K + epoch * (K - 1) * decay, 1.0 - (K - 1) * floor)]
+
+
+class _FusedFastAdaptSteps(torch.autograd.Function):
+    """``_FusedFastAdapt`` through mi_meta_batch_maml_steps: the query loss and accuracy after every inner step, and the multi-step loss
+    J = sum_t sum_j w_j L_query,t(theta_j) as the value that carries the gradients.  ``step_w`` [steps] lives on the device."""
+
+    @staticmethod
+    def forward(ctx, engine, data, labels, shots, steps, lr, first_order, need_grad, need_lr_grad, grad_tasks, step_w, lr_flat, *params):
+        theta = flat_theta(params)
+        lr_vec = None if lr_flat is None else lr_flat.detach().float().contiguous()
+        if lr_vec is not None and lr_vec.shape[0] not in (1, max(int(steps), 1)):
+            raise ValueError(f'the learner holds step sizes for {lr_vec.shape[0]} inner steps, the call adapts for {steps}')
+        gt = data.shape[0] if grad_tasks is None else int(grad_tasks)
+
+        def call(with_grad):
+            return engine.meta_batch_steps(theta, data, labels, shots, steps, step_w, inner_lr=lr if lr_vec is None else None, lr_vec=lr_vec,
+                                           first_order=first_order, grad_tasks=gt if with_grad else 0,
+                                           want_lr_grad=with_grad and need_lr_grad and lr_vec is not None)[:4]
+        ctx.deferred = call if need_grad and DEFERRED_OUTER_BACKWARD else None
+        loss, acc, grad, lr_grad = call(need_grad and ctx.deferred is None)
+        ctx.shapes = [p.shape for p in params]
+        empty = torch.empty(0, device=data.device)
+        ctx.save_for_backward(grad if grad is not None else empty, lr_grad if lr_grad is not None else empty)
+        ctx.mark_non_differentiable(loss, acc)       # (values: only the objective carries the gradients, as in _FusedFastAdapt)
+        return (step_w.unsqueeze(1) * loss[1:, :gt]).sum(), loss, acc
+
+    @staticmethod
+    def backward(ctx, gsum, gloss, gacc):
+        grad, lr_grad = ctx.saved_tensors
+        if ctx.deferred is not None:
+            _, _, grad, lr_grad = ctx.deferred(True)
+            lr_grad = grad.new_empty(0) if lr_grad is None else lr_grad
+        if grad.numel() == 0:
+            raise RuntimeError('meta_batch_adapt_steps was run without gradients (torch.no_grad or no parameter requires grad)')
+        return (None,) * 11 + (lr_grad * gsum if lr_grad.numel() else None,) + split_grad(grad, ctx.shapes, gsum)
+
+
+def meta_batch_adapt_steps(learner, data, labels, adaptation_steps, shots, ways, step_weights=None, first_order=None, grad_tasks=None):
+    """``meta_batch_adapt`` with the query set scored after 0, 1, .., adaptation_steps inner steps in the one fused call, and the
+    multi-step loss as the outer objective.  ``step_weights``: the K weights w_1 .. w_K of the query loss after 1 .. K steps (``msl_weights``;
+    a list, or an fp32 tensor already on the device, which a caller may anneal in place); None: (0, .., 0, 1), the final loss only.
+    Returns (objective, losses [K + 1, T], accs [K + 1, T]): objective = sum over the train tasks of sum_j w_j losses[j], and
+    ``objective.backward()`` fills the base parameters' ``.grad`` (and a learnable ``InnerLR``'s) exactly as ``meta_batch_adapt`` does;
+    under ``torch.no_grad()`` the call scores only.  losses and accs are plain values; row K is what ``meta_batch_adapt`` returns."""
+    model = learner.module if isinstance(learner, MAML) else learner
+    fo = learner.first_order if first_order is None and isinstance(learner, MAML) else bool(first_order)
+    lr = learner.lr
+    params = list(model.parameters())
+    need = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    spec = model.spec()
+    if spec.ways != ways:
+        raise ValueError(f'model has {spec.ways} outputs but ways={ways}')
+    engine = model.engine()
+    K = int(adaptation_steps)
+    if step_weights is None:
+        step_weights = [0.0] * (K - 1) + [1.0]
+    if not torch.is_tensor(step_weights):
+        step_weights = torch.tensor([float(w) for w in step_weights], dtype=torch.float32, device=data.device)
+    data = data.reshape(data.shape[0], data.shape[1], spec.in_channels, spec.in_h, spec.in_w).float().contiguous()
+    lr_flat = learner.lr_flat() if isinstance(learner, MAML) else None
+    need_lr = lr_flat is not None and torch.is_grad_enabled() and lr_flat.requires_grad
+    return _FusedFastAdaptSteps.apply(engine, data, labels.contiguous(), shots, K, lr, fo, need or need_lr, need_lr, grad_tasks,
+                                      step_weights, lr_flat, *params)
+
+
 def fast_adapt(batch, learner, loss, adaptation_steps, shots, ways, device, features=None):
     """Same signature/returns as the reference (vision.py:6-18): (valid_loss, valid_accuracy) as 0-dim tensors;
     ``valid_loss.backward()`` accumulates the (second-order unless learner.first_order) meta-gradient into the base
@@ -141,3 +216,18 @@ def evaluate(params, test_tasks, model, loss, device, features=None):
             meta_test_accuracy /= params['meta_batch_size']
     print('Meta Test Accuracy', meta_test_accuracy)
     return meta_test_accuracy
+
+
+def evaluate_steps(params, test_tasks, model, loss, device):
+    """``evaluate`` per adaptation step: the mean query accuracy of params['meta_batch_size'] test tasks after 0, 1, ..,
+    params['adapt_steps'] inner steps -- a list of adapt_steps + 1 floats, entry K being what ``evaluate`` returns -- from ONE fused
+    call (the tasks are sampled in ``evaluate``'s order; the inner loop runs once, not once per step count)."""
+    _check_loss(loss)
+    batches = [test_tasks.sample() for _ in range(params['meta_batch_size'])]
+    with torch.no_grad():
+        data = torch.stack([b[0] for b in batches]).to(device)
+        labels = torch.stack([b[1] for b in batches]).to(device)
+        _, _, accs = meta_batch_adapt_steps(model.clone(), data, labels, params['adapt_steps'], params['shots'], params['ways'])
+        per_step = [a.item() for a in accs.mean(dim=1)]
+    print('Meta Test Accuracy per step', per_step)
+    return per_step

@@ -27,7 +27,7 @@ struct Layer {
   size_t off_gamma, off_beta, off_w, off_b;
 };
 
-typedef std::array<unsigned long long, 30> GraphKey;   // graph_key(): what a captured fused call depends on
+typedef std::array<unsigned long long, 31> GraphKey;   // graph_key(): what a captured fused call depends on
 struct mi_engine {
   mi_model_desc d;
   int device;
@@ -423,6 +423,7 @@ struct Plan {
   // direction lr_k * lam_{k+1} of the Hessian-vector passes [T][PS], twice (ping-pong, like lam / lam2), and the products g_k * lam_{k+1}
   // [K][T][PS] the step-size gradient sums
   float *lrv = nullptr, *dir = nullptr, *dir2 = nullptr, *prod = nullptr;
+  float* qg = nullptr;  // multi-step loss (mi_meta_batch_maml_steps) with a gradient: the query gradients q_1..q_K [K][T][PS], else nullptr
   float *xs, *xq;
   int32_t *ys, *yq;
   std::vector<ActSet> sup;
@@ -488,12 +489,13 @@ static unsigned long long kernel_selection_key() {
 // The sizes a plan depends on: T tasks, ns support / nq query images each, K inner steps; second_order: the K support passes are kept and
 // a tangent set is planned; lr_steps > 0: the step-size-vector call's buffers (want_lr_grad: its products too).  Every size query and the call
 // it sizes build their shape with the same helper below, so the two cannot disagree.
-struct PlanShape { int T, ns, nq, K, second_order, lr_steps, want_lr_grad; };
-static PlanShape maml_shape(int tasks, int ways, int shots, int K, int second_order, int lr_steps, int want_lr_grad) {
-  return PlanShape{tasks, ways * shots, ways * shots, K, second_order, lr_steps, want_lr_grad};
+// steps (mi_meta_batch_maml_steps): 0 = not that call, 1 = its query passes at every theta_j, forward only, 2 = with their gradients.
+struct PlanShape { int T, ns, nq, K, second_order, lr_steps, want_lr_grad, steps; };
+static PlanShape maml_shape(int tasks, int ways, int shots, int K, int second_order, int lr_steps, int want_lr_grad, int steps = 0) {
+  return PlanShape{tasks, ways * shots, ways * shots, K, second_order, lr_steps, want_lr_grad, steps};
 }
-static PlanShape forward_shape(int tasks, int n) { return PlanShape{tasks, n, n, 0, 0, 0, 0}; }   // plain forward, learner forward / backward
-static PlanShape hvp_shape(int tasks, int n) { return PlanShape{tasks, n, n, 1, 1, 0, 0}; }       // mi_learner_hvp: one kept pass + tangent set
+static PlanShape forward_shape(int tasks, int n) { return PlanShape{tasks, n, n, 0, 0, 0, 0, 0}; }   // plain forward, learner forward / backward
+static PlanShape hvp_shape(int tasks, int n) { return PlanShape{tasks, n, n, 1, 1, 0, 0, 0}; }       // mi_learner_hvp: one kept pass + tangent set
 
 // What both plans (the fused MAML call's and ANIL's) end with, for passes over n images of each of T tasks: the BatchNorm and weight-gradient
 // partials (per_block: one more weight-gradient buffer per block, for the fused tail), block 1's input Gram matrices over ng images (gram:
@@ -578,6 +580,7 @@ static void make_plan(const mi_engine* e, void* ws, const PlanShape& s, Plan& pl
   for (int k = 0; k < nsets; ++k) plan_actset(e, b, pl.sup[k], T, ns, true);
   plan_actset(e, b, pl.qry, T, nq, true);
   pl.cell_cap = 8 + (K + 1) * 2 * nl + K * 4 * nl + 4 * nl;      // p and dz per block and pass, pd and R{dz} per Hessian-vector pass, spare
+  if (s.steps) pl.cell_cap += K * 2 * nl;                        // ... and of the K further query passes
   const bool swept_twice = K >= 2 || (K >= 1 && second_order);   // the support set is swept at least twice: its Gram matrix pays
   plan_partials(e, b, pl, T, nmax, true, swept_twice, ns, e->gramq && nq == ns, false, [&](size_t pmax) {
     if (!(second_order && K > 0)) return;
@@ -611,8 +614,11 @@ static void make_plan(const mi_engine* e, void* ws, const PlanShape& s, Plan& pl
       pl.dir = b.take<float>(TP);
       pl.dir2 = b.take<float>(TP);
       if (s.want_lr_grad) pl.prod = b.take<float>(TP * K);
+    } else if (s.steps == 2 && s.want_lr_grad) {      // first order with the multi-step loss: lam_{k+1} differs from step to step
+      pl.prod = b.take<float>(TP * K);
     }
   }
+  if (s.steps == 2) pl.qg = b.take<float>(TP * K);
   pl.bytes = align_up(b.off, 256);
 }
 
@@ -694,6 +700,17 @@ extern "C" int mi_workspace_bytes_lr(const mi_engine* e, int tasks, int ways, in
   if (!e || !bytes || tasks < 1 || ways < 1 || shots < 1 || adapt_steps < 0) return MI_ERR_ARG;
   if (!lr_steps_ok(lr_steps, adapt_steps)) return MI_ERR_ARG;
   return plan_bytes(e, maml_shape(tasks, ways, shots, adapt_steps, second_order, lr_steps, want_lr_grad), bytes);
+}
+
+// mi_meta_batch_maml_steps: lr_steps = 0 for the scalar step, else as mi_workspace_bytes_lr; grad_tasks as the call's (0: no query gradients kept).
+static PlanShape steps_shape(int tasks, int grad_tasks, int ways, int shots, int K, int second_order, int lr_steps, int want_lr_grad) {
+  return maml_shape(tasks, ways, shots, K, (second_order && grad_tasks > 0) ? 1 : 0, lr_steps, want_lr_grad, grad_tasks > 0 ? 2 : 1);
+}
+extern "C" int mi_workspace_bytes_steps(const mi_engine* e, int tasks, int grad_tasks, int ways, int shots, int adapt_steps, int second_order,
+                                        int lr_steps, int want_lr_grad, size_t* bytes) {
+  if (!e || !bytes || tasks < 1 || grad_tasks < 0 || grad_tasks > tasks || ways < 1 || shots < 1 || adapt_steps < 1) return MI_ERR_ARG;
+  if (lr_steps != 0 && !lr_steps_ok(lr_steps, adapt_steps)) return MI_ERR_ARG;
+  return plan_bytes(e, steps_shape(tasks, grad_tasks, ways, shots, adapt_steps, second_order, lr_steps, want_lr_grad), bytes);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1162,7 +1179,9 @@ static AdvanceArgs advance_base(const mi_engine* e, float* g) {
 // One fused call as the entry points receive it: what mi_meta_batch_maml / _tv / _lr / _anil fill from their arguments and hand through the
 // graph cache (meta_batch_entry) to the implementation.  grad_tasks = 0: evaluation only (the with_grad flag of mi_meta_batch_maml and
 // mi_meta_batch_anil is grad_tasks = tasks or 0).  lr_vec == nullptr: the scalar step inner_lr; else the step sizes on the device.
-enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2 };
+// ALGO_MAML_STEPS (mi_meta_batch_maml_steps): step_w = the K weights of the multi-step loss on the device, and loss_out / acc_out / logits_out
+// are the per-step outputs, row j of K + 1 holding what the plain call writes for theta_j.  lr_vec may be null (scalar step) or not.
+enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS = 3 };
 struct MetaCall {
   MetaAlgo algo;
   const float* theta; const float* data; const int64_t* labels;
@@ -1171,13 +1190,20 @@ struct MetaCall {
   const float* lr_vec; int lr_steps; float* lr_grad_out;
   float *loss_out, *acc_out, *meta_grad_out, *logits_out;
   void* workspace; size_t workspace_bytes;
+  const float* step_w = nullptr;
 };
 
 // Every check of a fused call that needs no plan: before the graph cache and before any HIP call.
 static int check_call(mi_engine* e, const MetaCall& c) {
   if (!e) return fail(nullptr, MI_ERR_ARG, "null engine");
   if (c.grad_tasks < 0 || c.grad_tasks > c.tasks) return fail(e, MI_ERR_ARG, "grad_tasks must be in 0..tasks");
-  if (c.algo == ALGO_MAML_LR) {
+  if (c.algo == ALGO_MAML_STEPS) {
+    if (c.adapt_steps < 1) return fail(e, MI_ERR_ARG, "mi_meta_batch_maml_steps needs adapt_steps >= 1: its weights are those of theta_1 .. theta_K");
+    if (!c.step_w) return fail(e, MI_ERR_ARG, "step_w is NULL: mi_meta_batch_maml_steps takes adapt_steps weights on the device");
+    if (e->trace) return fail(e, MI_ERR_ARG, "the debug trace does not cover mi_meta_batch_maml_steps");
+    if (!c.lr_vec && c.lr_grad_out) return fail(e, MI_ERR_ARG, "lr_grad_out given without lr_vec");
+  }
+  if (c.algo == ALGO_MAML_LR || (c.algo == ALGO_MAML_STEPS && c.lr_vec)) {
     if (!lr_steps_ok(c.lr_steps, c.adapt_steps))
       return fail(e, MI_ERR_ARG, "lr_steps = " + std::to_string(c.lr_steps) + " must be 1 or adapt_steps = " + std::to_string(c.adapt_steps) +
                                      (c.adapt_steps == 0 ? " (without inner steps: 1)" : ""));
@@ -1207,7 +1233,10 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
   const float inner_lr = c.inner_lr;
   e->export_pass = 0;
   Plan pl;
-  const int prc = plan_in(e, c.workspace, c.workspace_bytes, maml_shape(T, c.ways, c.shots, K, so, c.lr_vec ? c.lr_steps : 0, c.lr_grad_out != nullptr), pl);
+  const bool msl = c.algo == ALGO_MAML_STEPS;      // query passes at every theta_j, the multi-step loss's terms in the adjoint recursion
+  const int prc = plan_in(e, c.workspace, c.workspace_bytes,
+                          msl ? steps_shape(T, Tg, c.ways, c.shots, K, so, c.lr_vec ? c.lr_steps : 0, c.lr_grad_out != nullptr)
+                              : maml_shape(T, c.ways, c.shots, K, so, c.lr_vec ? c.lr_steps : 0, c.lr_grad_out != nullptr), pl);
   if (prc) return prc;
   const int ns = c.ways * c.shots, nq = ns;
   const size_t TP = (size_t)T * e->PS;
@@ -1224,7 +1253,10 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
     LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, pl.xs, T, ns, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part, pl.gram_s));
   const double* gq = pl.gram_q;          // (also for forward-only calls and tasks: the same query forward whether or not a backward half follows)
   bool gq_side = false, gq_launched = false;
-  if (gq && e->overlap) {   // the query images' Gram matrix beside the inner loop (on `st` if the side stream cannot be had)
+  if (gq && msl) {          // needed at once: theta_0 is scored before the first support pass
+    LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, pl.xq, T, nq, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part_q, pl.gram_q));
+    gq_launched = true;
+  } else if (gq && e->overlap) {   // the query images' Gram matrix beside the inner loop (on `st` if the side stream cannot be had)
     hipStream_t ws = side_fork(e, st, pl.half);
     gq_side = ws != st;
     LAUNCH(e, ws, OP_GRAM, 0, launch_input_gram(ws, pl.xq, T, nq, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part_q, pl.gram_q));
@@ -1237,7 +1269,22 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
     a0.stats = 1; a0.gram = pl.gram_s; a0.out0 = pl.sup[0].mu[0]; a0.out1 = pl.sup[0].rstd[0]; a0.inv_m = inv_m0;
     LAUNCH(e, st, OP_MISC, 2, launch_advance(st, a0, T));
   }
+  // The steps call: the query set at theta_j, j < K, with the launches of the final query pass below and the same activation set; train tasks
+  // take the backward half for j >= 1 and leave q_j finished in pl.qg[j - 1].  No BatchNorm export: the call exports the passes the plain call does.
+  const size_t TL = (size_t)T * nq * c.ways;
+  auto query_at = [&](int j) -> int {
+    const bool bwd = with_grad && j >= 1;
+    float* qj = bwd ? pl.qg + (size_t)(j - 1) * TP : pl.lam;
+    AdvanceArgs aq = advance_base(e, qj);
+    ExportPause pause(e);
+    const int qrc = pass_fwd_bwd(e, st, pl, pl.qry, pl.xq, pl.yq, nq, T, pl.theta + (size_t)j * TP, qj, c.loss_out + (size_t)j * T, c.acc_out + (size_t)j * T,
+                                 c.logits_out ? c.logits_out + (size_t)j * TL : nullptr, bwd, gq, (tail && bwd) ? &aq : nullptr, false, Tg);
+    if (qrc) return qrc;
+    if (tail && bwd) LAUNCH(e, st, OP_MISC, 2, launch_advance(st, aq, Tg));
+    return MI_OK;
+  };
   for (int k = 0; k < K; ++k) {
+    if (msl) { const int qrc = query_at(k); if (qrc) return qrc; }
     ActSet& A = so ? pl.sup[k] : pl.sup[0];
     float* th = pl.theta + (size_t)k * TP;
     float* gk = pl.g + (size_t)k * TP;
@@ -1260,13 +1307,21 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
     }
   }
   float* thK = pl.theta + (size_t)K * TP;
-  AdvanceArgs advq = advance_base(e, pl.lam);
+  // the steps call with the fused tail: q_K is finished in pl.qg[K - 1] and lam_K = w_K q_K goes to pl.lam (AdvanceArgs::inj_w); without it the
+  // pass writes pl.lam and one elementwise launch scales it
+  const bool msl_adv = msl && tail && with_grad;
+  float* gK = msl_adv ? pl.qg + (size_t)(K - 1) * TP : pl.lam;
+  AdvanceArgs advq = advance_base(e, gK);
+  if (msl_adv) { advq.out = pl.lam; advq.inj_w = c.step_w + (K - 1); }
+  float *loss_K = c.loss_out, *acc_K = c.acc_out, *logits_K = c.logits_out;
+  if (msl) { loss_K += (size_t)K * T; acc_K += (size_t)K * T; if (logits_K) logits_K += (size_t)K * TL; }
   if (gq_side) { const int jrc = side_join(e, st, pl.half, true); if (jrc) return jrc; }
   else if (gq && !gq_launched) LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, pl.xq, T, nq, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part_q, pl.gram_q));
-  int rc = pass_fwd_bwd(e, st, pl, pl.qry, pl.xq, pl.yq, nq, T, thK, pl.lam, c.loss_out, c.acc_out, c.logits_out, with_grad != 0, gq,
+  int rc = pass_fwd_bwd(e, st, pl, pl.qry, pl.xq, pl.yq, nq, T, thK, gK, loss_K, acc_K, logits_K, with_grad != 0, gq,
                         (tail && with_grad) ? &advq : nullptr, false, Tg);
   if (rc) return rc;
   if (!with_grad) return MI_OK;
+  if (msl && !tail) LAUNCH(e, st, OP_MISC, 2, launch_scale_dev(st, pl.lam, c.step_w + (K - 1), (size_t)Tg * e->PS));
   // debug trace layout (floats): theta [K+1][T][P] | g [K][T][P] | lam_in [K][T][P] | hv [K][T][P], reference parameter order
   const size_t TPr = (size_t)T * e->P;
   const bool tr = e->trace && e->trace_floats >= (size_t)(4 * K + 1) * TPr;
@@ -1306,6 +1361,7 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
       if (tail) {   // H lam finished, lam' = lam - lr H lam (into the other buffer: the row workgroups of the advance launch read lam's
                     // block-1 entries while others write lam'), and the tangent statistics of the next Hessian-vector pass
         adv.a = lam_cur; adv.out = lam_nxt; adv.alpha = c.lr_vec ? 1.f : inner_lr;
+        if (msl && k > 0) { adv.inj_w = c.step_w + (k - 1); adv.inj = pl.qg + (size_t)(k - 1) * TP; }      // lam_k takes w_k q_k
         if (k > 0 && pl.gram_s) tangent_stats(adv, k - 1);
         if (c.lr_vec && k > 0) vector_extras(adv, k - 1);
         LAUNCH(e, st, OP_MISC, 2, launch_advance(st, adv, Tg));
@@ -1314,7 +1370,13 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
       } else {
         if (tr) HIPCHK(e, launch_scatter_tasks(st, pl.hv, e->perm_dev, (int)e->P, (int)e->PS, T, e->trace + (size_t)(3 * K + 1 + k) * TPr));
         LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, lam_cur, pl.hv, c.lr_vec ? 1.f : inner_lr, (size_t)Tg * e->PS, lam_cur));
+        if (msl && k > 0) LAUNCH(e, st, OP_MISC, 2, launch_fma_dev(st, lam_cur, pl.qg + (size_t)(k - 1) * TP, c.step_w + (k - 1), (size_t)Tg * e->PS));
       }
+    }
+  } else if (msl) {   // first order: lam_k = sum_{j >= max(k, 1)} w_j q_j, the products g_k * lam_{k+1} of the step-size gradient on the way down
+    for (int k = K - 1; k >= 0; --k) {
+      if (pl.prod) LAUNCH(e, st, OP_MISC, 2, launch_product(st, pl.g + (size_t)k * TP, pl.lam, (int)e->PS, Tg, pl.prod + (size_t)k * TP));
+      if (k > 0) LAUNCH(e, st, OP_MISC, 2, launch_fma_dev(st, pl.lam, pl.qg + (size_t)(k - 1) * TP, c.step_w + (k - 1), (size_t)Tg * e->PS));
     }
   }
   if (tr) {
@@ -1326,7 +1388,7 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
   LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, lam_cur, e->perm_dev, (int)e->P, (int)e->PS, Tg, c.meta_grad_out));
   // lr_grad = -sum_t g_k * lam_{k+1} in the reference's order (second order: the stored products; first order: lam is the constant pl.lam)
   if (c.lr_vec && c.lr_grad_out)
-    LAUNCH(e, st, OP_MISC, 3, launch_lr_grad_fold(st, so ? pl.prod : nullptr, pl.g, pl.lam, e->perm_dev, (int)e->P, (int)e->PS, T, Tg, K,
+    LAUNCH(e, st, OP_MISC, 3, launch_lr_grad_fold(st, (so || msl) ? pl.prod : nullptr, pl.g, pl.lam, e->perm_dev, (int)e->P, (int)e->PS, T, Tg, K,
                                                   c.lr_steps, c.lr_grad_out));
   return MI_OK;
 }
@@ -1452,7 +1514,7 @@ static GraphKey graph_key(const mi_engine* e, void* stream, const MetaCall& c) {
                   (u)c.lr_steps, (u)(uintptr_t)c.lr_grad_out, (u)(uintptr_t)c.loss_out, (u)(uintptr_t)c.acc_out,
                   (u)(uintptr_t)c.meta_grad_out, (u)(uintptr_t)c.logits_out, (u)(uintptr_t)c.workspace, (u)c.workspace_bytes,
                   (u)e->fuse1, (u)e->gram1, (u)e->gramq, (u)e->overlap, (u)e->fuse_fin, (u)e->fuse_b1red, (u)e->fuse_tail, (u)e->fuse_last,
-                  kernel_selection_key()};
+                  kernel_selection_key(), (u)(uintptr_t)c.step_w};
 }
 
 static int meta_batch_entry(mi_engine* e, void* stream, const MetaCall& c) {
@@ -1530,6 +1592,17 @@ extern "C" int mi_meta_batch_maml_lr(mi_engine* e, void* stream, const float* th
   return meta_batch_entry(e, stream, MetaCall{ALGO_MAML_LR, theta, data, labels, tasks, grad_tasks, ways, shots, adapt_steps, second_order,
                                               0.f, lr_vec, lr_steps, lr_grad_out, loss_out, acc_out, meta_grad_out, logits_out, workspace,
                                               workspace_bytes});
+}
+// mi_meta_batch_maml_tv / _lr with the query set scored at every theta_j and the multi-step loss sum_j step_w[j - 1] L_query(theta_j) as the
+// outer objective (include/mi_maml.h).
+extern "C" int mi_meta_batch_maml_steps(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels, int tasks,
+                                        int grad_tasks, int ways, int shots, int adapt_steps, float inner_lr, const float* lr_vec, int lr_steps,
+                                        const float* step_w, int second_order, float* loss_steps_out, float* acc_steps_out, float* meta_grad_out,
+                                        float* lr_grad_out, float* logits_steps_out, void* workspace, size_t workspace_bytes) {
+  MetaCall c{ALGO_MAML_STEPS, theta, data, labels, tasks, grad_tasks, ways, shots, adapt_steps, second_order, lr_vec ? 0.f : inner_lr, lr_vec,
+             lr_vec ? lr_steps : 0, lr_grad_out, loss_steps_out, acc_steps_out, meta_grad_out, logits_steps_out, workspace, workspace_bytes};
+  c.step_w = step_w;
+  return meta_batch_entry(e, stream, c);
 }
 extern "C" int mi_meta_batch_anil(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
                                   int tasks, int ways, int shots, int adapt_steps, float inner_lr, int second_order,

@@ -207,6 +207,11 @@ struct AdvanceArgs {
   const float* dlr; float* dir;              // the launch finishes an adjoint vector lam_j (out, or g when out == nullptr): dir[task][e] =
                                              // dlr[e] * lam_j[e], the direction of the next Hessian-vector pass [T][ostride]; stats == 2 then reads dir
   const float* dg; float* prod;              // ... and prod[task][e] = dg[task][e] * lam_j[e] (dg = g_{j-1} [T][gstride]; prod [T][ostride], or null)
+  // Multi-step loss (mi_meta_batch_maml_steps).  inj_w set selects the kernel's injecting instantiation (the vector one plus this term).
+  const float* inj_w;                        // ONE weight on the device, read by every thread that finishes an element
+  const float* inj;                          // out != nullptr: out = fmaf(*inj_w, inj[task][e], a - step * g), inj [T][ostride] (a query gradient q_j);
+                                             // out == nullptr: the finished g itself is scaled, g = *inj_w * g (lam_K = w_K q_K).  Either way the
+                                             // term is in before dir, prod and the statistics are formed, and under the same write-through stores
 };
 hipError_t launch_advance(hipStream_t st, const AdvanceArgs& a, int tasks);
 
@@ -290,6 +295,9 @@ hipError_t launch_axpy(hipStream_t st, const float* a, const float* b, float alp
 hipError_t launch_axpy_vec(hipStream_t st, const float* a, const float* b, const float* lr, int pstride, int tasks, float* out);
 hipError_t launch_scale_vec(hipStream_t st, const float* x, const float* lr, int pstride, int tasks, float* out);
 hipError_t launch_product(hipStream_t st, const float* a, const float* b, int pstride, int tasks, float* out);
+// multi-step loss without the one-launch advance, one weight *w on the device:  x = *w * x;  x = fmaf(*w, q, x)  (x, q [n])
+hipError_t launch_scale_dev(hipStream_t st, float* x, const float* w, size_t n);
+hipError_t launch_fma_dev(hipStream_t st, float* x, const float* q, const float* w, size_t n);
 // out_ref[s][perm[i]] = -sum over the steps k of s (all K when lr_steps == 1, else k == s), then over tasks t < grad_tasks, of
 // prod[k][t][i] (prod != nullptr) or g[k][t][i] * lam[t][i] (first order): fp32 products, one fp64 chain in that fixed order, rounded once
 hipError_t launch_lr_grad_fold(hipStream_t st, const float* prod, const float* g, const float* lam, const int32_t* perm, int p, int pstride,

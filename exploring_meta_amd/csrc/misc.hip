@@ -155,6 +155,17 @@ __global__ void product_kernel(const float* __restrict__ a, const float* __restr
   if (o < n) out[o] = a[o] * b[o];
 }
 
+// Multi-step loss (mi_meta_batch_maml_steps) where no advance launch carries the term: lam_K = w_K q_K and lam_k += w_k q_k, the weight
+// read on the device.  fmaf: a zero weight leaves x as it was (up to the sign of a zero), a weight of one leaves w * x = x.
+__global__ void scale_dev_kernel(float* __restrict__ x, const float* __restrict__ w, size_t n) {
+  const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o < n) x[o] = *w * x[o];
+}
+__global__ void fma_dev_kernel(float* __restrict__ x, const float* __restrict__ q, const float* __restrict__ w, size_t n) {
+  const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o < n) x[o] = fmaf(*w, q[o], x[o]);
+}
+
 // lr_grad[s][perm[i]] = -sum_k sum_t g_k[t][i] * lam_{k+1}[t][i]: the products are fp32 (stored by the advance launches, or formed here
 // from g and the constant lam of a first-order call), their sum is one fp64 chain over (step, task) in that order, rounded once.
 // grid (ceil(p / 256), lr_steps).
@@ -283,6 +294,14 @@ hipError_t launch_scale_vec(hipStream_t st, const float* x, const float* lr, int
 hipError_t launch_product(hipStream_t st, const float* a, const float* b, int pstride, int tasks, float* out) {
   const size_t n = (size_t)tasks * pstride;
   hipLaunchKernelGGL(product_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, b, n, out);
+  return hipGetLastError();
+}
+hipError_t launch_scale_dev(hipStream_t st, float* x, const float* w, size_t n) {
+  hipLaunchKernelGGL(scale_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, w, n);
+  return hipGetLastError();
+}
+hipError_t launch_fma_dev(hipStream_t st, float* x, const float* q, const float* w, size_t n) {
+  hipLaunchKernelGGL(fma_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, q, w, n);
   return hipGetLastError();
 }
 hipError_t launch_lr_grad_fold(hipStream_t st, const float* prod, const float* g, const float* lam, const int32_t* perm, int p, int pstride,

@@ -253,10 +253,19 @@ class MetaEngine:
                 raise ValueError('theta/data/lr_vec must be contiguous fp32 CUDA tensors and labels contiguous int64 CUDA')
         return T
 
-    def _maml_call(self, theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, first_order, grad_tasks, want_lr_grad, return_logits):
-        """mi_meta_batch_maml_tv, or mi_meta_batch_maml_lr when the step sizes are a vector.  Returns (loss, acc, grad, lr_grad, logits)."""
+    def _maml_call(self, theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, first_order, grad_tasks, want_lr_grad, return_logits,
+                   step_w=None):
+        """mi_meta_batch_maml_tv, or mi_meta_batch_maml_lr when the step sizes are a vector, or -- step_w given -- mi_meta_batch_maml_steps
+        with either kind of step (loss, acc and logits then carry a leading axis of adapt_steps + 1).  Returns (loss, acc, grad, lr_grad, logits)."""
         s = self.spec
         T = self._check_batch(theta, data, labels, shots, lr_vec)
+        if step_w is not None:
+            # the library reads adapt_steps floats at step_w on the device: anything else is refused here, before any launch
+            if adapt_steps < 1:
+                raise _lib.MiError('libmi_maml error -1: meta_batch_steps needs adapt_steps >= 1')
+            if not torch.is_tensor(step_w) or step_w.dtype != torch.float32 or not step_w.is_cuda or step_w.device != theta.device or \
+                    not step_w.is_contiguous() or tuple(step_w.shape) != (adapt_steps,):
+                raise _lib.MiError(f'libmi_maml error -1: step_w must be a contiguous fp32 tensor of shape ({adapt_steps},) on {theta.device}')
         if lr_vec is not None:
             # the library sizes its reads of lr_vec from lr_steps and P: a buffer of another size is refused here, before any launch
             if lr_vec.numel() % self.param_count != 0 or lr_vec.numel() == 0 or lr_vec.dim() > 2 or \
@@ -268,11 +277,18 @@ class MetaEngine:
             raise ValueError(f'grad_tasks must be in 0..{T}, got {grad_tasks}')
         with_grad = grad_tasks > 0
         so = (not first_order) and with_grad
-        b = C.c_size_t(0 if lr_vec is not None else self.workspace_bytes(T, shots, adapt_steps, so))
-        if lr_vec is not None and self.lib.mi_workspace_bytes_lr(self._h, T, s.ways, shots, adapt_steps, int(so), lr_steps,
+        b = C.c_size_t(0 if lr_vec is not None or step_w is not None else self.workspace_bytes(T, shots, adapt_steps, so))
+        if step_w is not None:
+            if self.lib.mi_workspace_bytes_steps(self._h, T, int(grad_tasks), s.ways, shots, adapt_steps, int(so),
+                                                 lr_steps if lr_vec is not None else 0, int(bool(want_lr_grad)), C.byref(b)):
+                raise _lib.MiError(f'libmi_maml error -1: lr_steps must be 1 or adapt_steps = {adapt_steps}')
+        elif lr_vec is not None and self.lib.mi_workspace_bytes_lr(self._h, T, s.ways, shots, adapt_steps, int(so), lr_steps,
                                                                  int(bool(want_lr_grad)), C.byref(b)):
             raise _lib.MiError(f'libmi_maml error -1: lr_steps = {lr_steps} must be 1 or adapt_steps = {adapt_steps}')
         ws = self._workspace(b.value)
+        if step_w is not None:
+            return self._steps_call(theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, first_order, grad_tasks, want_lr_grad,
+                                    return_logits, step_w, T, ws)
         loss, acc, grad, logits = self._outputs('maml' if lr_vec is None else 'maml_lr', T, shots * s.ways, with_grad, return_logits)
         head = (_ptr(theta), _ptr(data), _ptr(labels), T, int(grad_tasks), s.ways, shots, adapt_steps)
         tail = (_ptr(logits), _ptr(ws), ws.numel())
@@ -288,6 +304,41 @@ class MetaEngine:
                                   _ptr(grad), _ptr(lr_grad), *tail)
         _lib.check(rc, self._h)
         return loss, acc, grad, lr_grad, logits
+
+    def _steps_call(self, theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, first_order, grad_tasks, want_lr_grad, return_logits,
+                    step_w, T, ws):
+        """The C call of `_maml_call` for mi_meta_batch_maml_steps: per-step outputs [adapt_steps + 1, T, ...]."""
+        s, K1 = self.spec, adapt_steps + 1
+        with_grad = grad_tasks > 0
+        lr_steps = 0 if lr_vec is None else lr_vec.numel() // self.param_count
+
+        def fresh():
+            return (torch.empty(K1, T, dtype=torch.float32, device=self.device), torch.empty(K1, T, dtype=torch.float32, device=self.device),
+                    torch.empty(self.param_count, dtype=torch.float32, device=self.device) if with_grad else None,
+                    torch.empty(K1, T, shots * s.ways, s.ways, dtype=torch.float32, device=self.device) if return_logits else None)
+        loss, acc, grad, logits = self._persistent(('steps', lr_vec is None, K1, T, shots * s.ways, with_grad, bool(return_logits)), fresh)
+        lr_grad = None
+        if lr_vec is not None and want_lr_grad:
+            lr_grad = self._persistent(('lr_grad_steps', T, lr_steps),
+                                       lambda: torch.empty(lr_steps, self.param_count, dtype=torch.float32, device=self.device))
+        rc = self._fused_call(self.lib.mi_meta_batch_maml_steps, _ptr(theta), _ptr(data), _ptr(labels), T, int(grad_tasks), s.ways, shots,
+                              adapt_steps, float(inner_lr) if lr_vec is None else 0.0, _ptr(lr_vec), lr_steps, _ptr(step_w),
+                              int(not first_order), _ptr(loss), _ptr(acc), _ptr(grad), _ptr(lr_grad), _ptr(logits), _ptr(ws), ws.numel())
+        _lib.check(rc, self._h)
+        return loss, acc, grad, lr_grad, logits
+
+    @_on_device
+    def meta_batch_steps(self, theta, data, labels, shots, adapt_steps, step_w, inner_lr=None, lr_vec=None, first_order=False, grad_tasks=None,
+                         want_lr_grad=False, return_logits=False):
+        """`meta_batch` / `meta_batch_lr` with the query set scored after 0, 1, .., adapt_steps inner steps in the one call, and the
+        multi-step loss sum_j step_w[j - 1] * L_query(theta_j) as the outer objective (mi_meta_batch_maml_steps).  step_w [adapt_steps]
+        fp32 on the engine's device, read there by every call, graph replays included: annealing it in place recaptures nothing.
+        inner_lr (a number) or lr_vec (as in `meta_batch_lr`).  grad_tasks = None: every task is a train task; 0: evaluation only.
+        Returns (loss [K + 1, T], acc [K + 1, T], meta_grad [P] or None, lr_grad or None, logits [K + 1, T, S*W, ways] or None)."""
+        if (inner_lr is None) == (lr_vec is None):
+            raise ValueError('meta_batch_steps takes exactly one of inner_lr and lr_vec')
+        return self._maml_call(theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, first_order,
+                               data.shape[0] if grad_tasks is None else grad_tasks, want_lr_grad, return_logits, step_w=step_w)
 
     @_on_device
     def meta_batch(self, theta, data, labels, shots, adapt_steps, inner_lr, first_order=False, with_grad=True,

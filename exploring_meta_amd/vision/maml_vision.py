@@ -18,7 +18,7 @@ import random
 import numpy as np
 import torch
 
-from ..core_functions import MAML, InnerLR, MiniImagenetCNN, OmniglotCNN, evaluate, meta_batch_adapt
+from ..core_functions import MAML, InnerLR, MiniImagenetCNN, OmniglotCNN, evaluate, meta_batch_adapt, meta_batch_adapt_steps, msl_weights
 from ..core_functions.vision_models import RunningStatsFold
 from ..sharding import init_process_group, reduce_meta_batch, shard_range
 from ..utils import synthetic
@@ -76,6 +76,19 @@ def run(dataset, p, first_order=False, log=print):
     save_dir = p.get('save_dir') or ''
     if save_dir and rank == 0:
         os.makedirs(os.path.join(save_dir, 'model_checkpoints'), exist_ok=True)
+    msl_its = int(p.get('msl_iterations', 0)) if p.get('multi_step_loss') and p['adapt_steps'] >= 1 else 0
+    step_w = torch.zeros(max(p['adapt_steps'], 1), device=device)      # annealed in place: the engine reads the weights on the device
+
+    def adapt(it, data, labels, grad_tasks=None):
+        """One fused call for these tasks: the multi-step loss of MAML++ while it < --msl_iterations (--multi_step_loss), else the plain call.
+        (objective, losses [T], accs [T]) -- the logged loss and accuracy are those of the last step either way."""
+        if it >= msl_its or not torch.is_grad_enabled():
+            return meta_batch_adapt(maml.clone(), data, labels, p['adapt_steps'], p['shots'], p['ways'], grad_tasks=grad_tasks)
+        step_w.copy_(torch.tensor(msl_weights(p['adapt_steps'], it, msl_its)))
+        total, losses, accs = meta_batch_adapt_steps(maml.clone(), data, labels, p['adapt_steps'], p['shots'], p['ways'], step_weights=step_w,
+                                                     grad_tasks=grad_tasks)
+        return total, losses[-1], accs[-1]
+
     for it in range(p['num_iterations']):
         opt.zero_grad()
         ids = list(range(it * T + lo, it * T + hi))
@@ -88,13 +101,12 @@ def run(dataset, p, first_order=False, log=print):
             d, l = train.sample_batch(ids)
             dv, lv = valid.sample_batch([10 ** 6 + i for i in ids])
             n = len(ids)
-            total, losses, accs = meta_batch_adapt(maml.clone(), torch.cat([d, dv]).to(device), torch.cat([l, lv]).to(device),
-                                                   p['adapt_steps'], p['shots'], p['ways'], grad_tasks=n)
+            total, losses, accs = adapt(it, torch.cat([d, dv]).to(device), torch.cat([l, lv]).to(device), grad_tasks=n)
             total.backward()                                                 # accumulates the SUM over this rank's train tasks
             sums = [losses[:n].sum(), accs[:n].sum(), losses[n:].sum(), accs[n:].sum()]
         elif ids:                                # with checkpoints: two calls, so that the BatchNorm buffers fold in the reference's call order
             d, l = train.sample_batch(ids)
-            total, losses, accs = meta_batch_adapt(maml.clone(), d.to(device), l.to(device), p['adapt_steps'], p['shots'], p['ways'])
+            total, losses, accs = adapt(it, d.to(device), l.to(device))
             total.backward()                                                 # accumulates the SUM over this rank's tasks
             fold.collect(0)
             with torch.no_grad():
@@ -144,6 +156,10 @@ def build_parser():
     parser.add_argument('--learn_inner_lr', action='store_true', help='the inner step sizes are meta-learned with the model (MetaSGD)')
     parser.add_argument('--per_step_lr', action='store_true', help='one set of step sizes per inner step')
     parser.add_argument('--freeze', nargs='+', default=[], metavar='PREFIX', help="parameter-name prefixes that are not adapted (e.g. 'base.0.')")
+    parser.add_argument('--multi_step_loss', action='store_true',
+                        help='MAML++ multi-step loss: the outer objective weights the query loss after every inner step (msl_weights)')
+    parser.add_argument('--msl_iterations', type=int, default=0, metavar='N',
+                        help='iterations over which the multi-step weights anneal to the final step; from iteration N on the plain call runs')
     return parser
 
 
@@ -151,11 +167,17 @@ def params_of(args):
     """The run's parameter dict from parsed flags (the defaults are the reference's run)."""
     p = {k: getattr(args, k) for k in params}
     p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
-             freeze=list(args.freeze))
+             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations)
     return p
 
 
+def main(argv=None, log=print):
+    """Parse the flags and run; returns (model, metrics of the last iteration)."""
+    args = build_parser().parse_args(argv)
+    p = dict(params)
+    p.update(params_of(args))
+    return run(args.dataset, p, first_order=args.first_order, log=log)
+
+
 if __name__ == '__main__':
-    args = build_parser().parse_args()
-    params.update(params_of(args))
-    run(args.dataset, params, first_order=args.first_order)
+    main()

@@ -165,6 +165,30 @@ int mi_meta_batch_maml_lr(mi_engine* e, void* stream, const float* theta, const 
                           int second_order, float* loss_out, float* acc_out, float* meta_grad_out, float* lr_grad_out,
                           float* logits_out, void* workspace, size_t workspace_bytes);
 
+/* mi_meta_batch_maml_tv (lr_vec NULL: the scalar step inner_lr) or mi_meta_batch_maml_lr (lr_vec, lr_steps as there) with the query set
+ * scored at EVERY theta_j, j = 0..adapt_steps, inside the one call, and the multi-step loss of MAML++ (Antoniou et al., 2019) as the outer
+ * objective:  J = sum_{t < grad_tasks} sum_{j = 1..K} step_w[j - 1] L_query,t(theta_j).  With q_j = grad L_query(theta_j):
+ *   second order:  lam_K = w_K q_K,   lam_k = lam_{k+1} - H_k (D_k lam_{k+1}) + w_k q_k  (k = K-1..1),   lam_0 = lam_1 - H_0 (D_0 lam_1)
+ *   first order:   lam_k = sum_{j >= max(k, 1)} w_j q_j
+ *   meta_grad = sum_t lam_0,   lr_grad_k = -sum_t g_k * lam_{k+1}
+ *   step_w           [adapt_steps]  device memory, fp32; theta_0 is scored but carries no weight.  Like lr_vec the VALUES are read on the
+ *                                   device by every call, graph replays included: annealing the weights in place never recaptures.
+ *   loss_steps_out   [adapt_steps + 1, tasks]   mean query loss at theta_j; acc_steps_out likewise
+ *   logits_steps_out [adapt_steps + 1, tasks, ways * shots, ways] or NULL
+ * The query passes at theta_j, j < K, make the launches of the final query pass with the same activation set and the same query Gram
+ * matrix; train tasks take their backward half for j >= 1, validation tasks and j = 0 the forward half only, and with grad_tasks == 0 no
+ * backward half runs.  They never write the BatchNorm export: mi_engine_set_bn_export sees the adapt_steps + 1 passes of the plain call.
+ * The weighted terms are added as fmaf(w, q, x) behind the unchanged update expression: step_w = (0, .., 0, 1) returns the plain call's
+ * last-step loss, accuracy, logits, meta_grad and lr_grad bit for bit.  MI_ERR_ARG before any launch: adapt_steps < 1, step_w NULL,
+ * lr_grad_out without lr_vec, a debug trace being set, and what the plain calls refuse.  Workspace: mi_workspace_bytes_steps (lr_steps = 0
+ * for the scalar step): the plain call's plan plus, with grad_tasks > 0, adapt_steps * tasks gradient-shaped vectors (the q_j). */
+int mi_workspace_bytes_steps(const mi_engine* e, int tasks, int grad_tasks, int ways, int shots, int adapt_steps, int second_order,
+                             int lr_steps, int want_lr_grad, size_t* bytes);
+int mi_meta_batch_maml_steps(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels, int tasks,
+                             int grad_tasks, int ways, int shots, int adapt_steps, float inner_lr, const float* lr_vec, int lr_steps,
+                             const float* step_w, int second_order, float* loss_steps_out, float* acc_steps_out, float* meta_grad_out,
+                             float* lr_grad_out, float* logits_steps_out, void* workspace, size_t workspace_bytes);
+
 /* Ablation / test switch: 1 (default) = every pass of mi_meta_batch_maml ends in ONE "advance" launch (weight-gradient partial folds,
  * block 1's Gram-matrix assembly, p <- p - lr g of learn2learn's maml_update / the adjoint recursion, the next pass's Gram statistics);
  * 0 = the separate launches (reduce_partials x3, gram_wgrad, axpy, gram_stats, a memset).  Bit-identical results. */
