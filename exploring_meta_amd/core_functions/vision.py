@@ -218,16 +218,21 @@ def evaluate(params, test_tasks, model, loss, device, features=None):
     return meta_test_accuracy
 
 
-def evaluate_steps(params, test_tasks, model, loss, device):
+def evaluate_steps(params, test_tasks, model, loss, device, features=None):
     """``evaluate`` per adaptation step: the mean query accuracy of params['meta_batch_size'] test tasks after 0, 1, ..,
     params['adapt_steps'] inner steps -- a list of adapt_steps + 1 floats, entry K being what ``evaluate`` returns -- from ONE fused
-    call (the tasks are sampled in ``evaluate``'s order; the inner loop runs once, not once per step count)."""
+    call (the tasks are sampled in ``evaluate``'s order; the inner loop runs once, not once per step count).  ``features``: the ANIL
+    trunk (``model`` is then the head's ``MAML``): one batched mi_meta_batch_anil_steps call."""
     _check_loss(loss)
     batches = [test_tasks.sample() for _ in range(params['meta_batch_size'])]
     with torch.no_grad():
         data = torch.stack([b[0] for b in batches]).to(device)
         labels = torch.stack([b[1] for b in batches]).to(device)
-        _, _, accs = meta_batch_adapt_steps(model.clone(), data, labels, params['adapt_steps'], params['shots'], params['ways'])
+        if features is None:
+            _, _, accs = meta_batch_adapt_steps(model.clone(), data, labels, params['adapt_steps'], params['shots'], params['ways'])
+        else:
+            from .anil import meta_batch_adapt_anil_steps
+            _, _, accs = meta_batch_adapt_anil_steps(model.clone(), features, data, labels, params['adapt_steps'], params['shots'], params['ways'])
         per_step = [a.item() for a in accs.mean(dim=1)]
     print('Meta Test Accuracy per step', per_step)
     return per_step

@@ -1181,7 +1181,10 @@ static AdvanceArgs advance_base(const mi_engine* e, float* g) {
 // mi_meta_batch_anil is grad_tasks = tasks or 0).  lr_vec == nullptr: the scalar step inner_lr; else the step sizes on the device.
 // ALGO_MAML_STEPS (mi_meta_batch_maml_steps): step_w = the K weights of the multi-step loss on the device, and loss_out / acc_out / logits_out
 // are the per-step outputs, row j of K + 1 holding what the plain call writes for theta_j.  lr_vec may be null (scalar step) or not.
-enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS = 3 };
+// ALGO_ANIL_LR / ALGO_ANIL_STEPS (mi_meta_batch_anil_lr / _steps): the same fields read by meta_batch_anil_impl; lr_vec and lr_grad_out are
+// [lr_steps][Ph] (the head's entries only), grad_tasks is tasks or 0.
+enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS = 3, ALGO_ANIL_LR = 4, ALGO_ANIL_STEPS = 5 };
+static bool is_anil(MetaAlgo a) { return a == ALGO_ANIL || a == ALGO_ANIL_LR || a == ALGO_ANIL_STEPS; }
 struct MetaCall {
   MetaAlgo algo;
   const float* theta; const float* data; const int64_t* labels;
@@ -1211,9 +1214,33 @@ static int check_call(mi_engine* e, const MetaCall& c) {
     if (c.lr_grad_out && c.grad_tasks == 0)
       return fail(e, MI_ERR_ARG, "lr_grad_out given but grad_tasks = 0: the step-size gradient is summed over the train tasks");
   }
+  if (c.algo == ALGO_ANIL_STEPS) {
+    if (c.adapt_steps < 1)
+      return fail(e, MI_ERR_ARG, "mi_meta_batch_anil_steps needs adapt_steps >= 1, got " + std::to_string(c.adapt_steps) + ": its weights are those of theta_1 .. theta_K");
+    if (!c.step_w) return fail(e, MI_ERR_ARG, "step_w is NULL: mi_meta_batch_anil_steps takes adapt_steps weights on the device");
+    if (!c.lr_vec && c.lr_grad_out) return fail(e, MI_ERR_ARG, "mi_meta_batch_anil_steps: lr_grad_out given without lr_vec");
+  }
+  if (c.algo == ALGO_ANIL_LR || c.algo == ALGO_ANIL_STEPS) {
+    const char* who = c.algo == ALGO_ANIL_LR ? "mi_meta_batch_anil_lr" : "mi_meta_batch_anil_steps";
+    if (e->trace) return fail(e, MI_ERR_ARG, std::string("the debug trace does not cover ") + who);
+    if (c.algo == ALGO_ANIL_LR && !c.lr_vec)
+      return fail(e, MI_ERR_ARG, "lr_vec is NULL: mi_meta_batch_anil_lr takes lr_steps * (ways * fc + ways) step sizes on the device");
+    if (c.lr_vec) {
+      if (!lr_steps_ok(c.lr_steps, c.adapt_steps))
+        return fail(e, MI_ERR_ARG, std::string(who) + ": lr_steps = " + std::to_string(c.lr_steps) + " must be 1 or adapt_steps = " +
+                                       std::to_string(c.adapt_steps) + (c.adapt_steps == 0 ? " (without inner steps: 1)" : ""));
+      if (c.lr_grad_out && c.grad_tasks == 0)
+        return fail(e, MI_ERR_ARG, std::string(who) + ": lr_grad_out given but with_grad = 0: the step-size gradient comes with the meta-gradient");
+    }
+    if (c.ways == e->d.ways && c.shots >= 1) {      // (the plain call meets these limits at the launch; here they come first)
+      const int n = c.ways * c.shots;
+      if (c.adapt_steps > 0 || c.grad_tasks > 0) HEAD_LDS(e, who, n, c.ways, 0);
+      if (c.adapt_steps > 0 && c.grad_tasks > 0 && c.second_order) HEAD_LDS(e, who, n, c.ways, 1);
+    }
+  }
   if (!c.theta || !c.data || !c.labels || !c.loss_out || !c.acc_out || !c.workspace) return fail(e, MI_ERR_ARG, "null pointer argument");
   if (c.grad_tasks > 0 && !c.meta_grad_out) return fail(e, MI_ERR_ARG, "meta_grad_out is NULL but a gradient was asked for");
-  if (c.algo == ALGO_ANIL && e->d.head_mean_pool)
+  if (is_anil(c.algo) && e->d.head_mean_pool)
     return fail(e, MI_ERR_ARG, "ANIL features are flattened (view(-1, fc_neurons)), not mean-pooled");
   if (c.tasks < 1 || c.shots < 1 || c.adapt_steps < 0) return fail(e, MI_ERR_ARG, "tasks/shots must be >= 1, adapt_steps >= 0");
   if (c.ways != e->d.ways) return fail(e, MI_ERR_ARG, "ways differs from the engine's classifier width");
@@ -1445,15 +1472,72 @@ extern "C" int mi_anil_workspace_bytes(const mi_engine* e, int tasks, int ways, 
   return MI_OK;
 }
 
+// What mi_meta_batch_anil_lr / _steps keep BEHIND the plain plan (whose offsets do not move).  Head-shaped vectors are compact:
+// [ways * feat weights | ways biases] at a per-task stride of hs = Ph rounded up to 64 floats, the alignment the head has inside theta.
+struct AnilExt {
+  float* lrh;    // [lr_steps][hs]   step sizes in engine layout                              (vector step)
+  float* dir;    // [T][hs]          D_k lam_{k+1}, the direction of the next head tangent    (vector step, second order)
+  float* qg;     // [K][T][hs]       q_j = grad_theta L_q(theta_j) in slot j - 1, j < K        (steps call with a gradient)
+  float* dqt;    // [T][n][feat]     dL_q/df_q of the query pass that has just run             (steps call with a gradient)
+  float* prod;   // [K][T][hs]       g_k * lam_{k+1}                                           (lr_grad_out, unless lam is one constant)
+  size_t hs, bytes;
+};
+static size_t anil_head_stride(const mi_engine* e) { return align_up(e->P - e->off_wl, 64); }
+static void make_anil_ext(const mi_engine* e, void* ws, size_t plain_bytes, int T, int n, int K, bool with_grad, bool so, int lr_steps,
+                          bool want_lr_grad, bool steps, AnilExt& ax) {
+  Bump b{reinterpret_cast<char*>(ws), plain_bytes};
+  ax = AnilExt{};
+  ax.hs = anil_head_stride(e);
+  const size_t th = (size_t)T * ax.hs;
+  if (lr_steps > 0) ax.lrh = b.take<float>((size_t)lr_steps * ax.hs);
+  if (lr_steps > 0 && with_grad && so && K > 0) ax.dir = b.take<float>(th);
+  if (steps && with_grad) {
+    if (K > 1) ax.qg = b.take<float>(th * (K - 1));
+    ax.dqt = b.take<float>((size_t)T * n * e->feat);
+  }
+  if (lr_steps > 0 && with_grad && want_lr_grad && K > 0 && (so || steps)) ax.prod = b.take<float>(th * K);
+  ax.bytes = align_up(b.off, 256);
+}
+
+// One workspace query for both entries.  lr_steps = 0: the scalar step (the steps call only); step_outputs: 0 = mi_meta_batch_anil_lr,
+// 1 = mi_meta_batch_anil_steps.
+extern "C" int mi_anil_workspace_bytes_steps(const mi_engine* e, int tasks, int ways, int shots, int adapt_steps, int with_grad, int second_order,
+                                             int lr_steps, int want_lr_grad, int step_outputs, size_t* bytes) {
+  if (!e || !bytes || tasks < 1 || ways < 1 || shots < 1 || adapt_steps < 0 || lr_steps < 0) return MI_ERR_ARG;
+  if (lr_steps != 0 && !lr_steps_ok(lr_steps, adapt_steps)) return MI_ERR_ARG;
+  if (lr_steps == 0 && !step_outputs) return MI_ERR_ARG;
+  AnilPlan ap;
+  make_anil_plan(e, nullptr, tasks, ways * shots, adapt_steps, ap);
+  AnilExt ax;
+  make_anil_ext(e, nullptr, ap.bytes, tasks, ways * shots, adapt_steps, with_grad != 0, with_grad && second_order, lr_steps, want_lr_grad != 0,
+                step_outputs != 0, ax);
+  *bytes = ax.bytes;
+  return MI_OK;
+}
+
+// c.lr_vec / c.step_w (mi_meta_batch_anil_lr / _steps; `ext` below), per task with D_k = diag(lr_k) or inner_lr * I:
+//   theta_{k+1} = theta_k - D_k g_k;   q_j = grad_theta L_q(theta_j), dq_j = dL_q(theta_j)/df_q;   df_q = sum_j w_j dq_j
+//   second order:  lam_K = w_K q_K;  lam_k = lam_{k+1} - H_k (D_k lam_{k+1}) + w_k q_k;  df_s = -sum_k R_{D_k lam_{k+1}}{dL_s/df_s}(theta_k)
+//   first order:   lam_k = sum_{j >= max(k, 1)} w_j q_j;  df_s = 0
+//   lr_grad_k = -sum_t g_k * lam_{k+1}
+// (without step_w: w = (0, .., 0, 1) and only theta_K is scored).  The head launches are the plain call's; the elementwise work between
+// them runs on the head slice only (anil_steps.hip).  With neither, `ext` is false and the launches are exactly the plain call's.
 static int meta_batch_anil_impl(mi_engine* e, void* stream, const MetaCall& c) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = c.tasks, K = c.adapt_steps, n = c.ways * c.shots, nl = (int)e->L.size(), with_grad = c.grad_tasks > 0;
   const float inner_lr = c.inner_lr;
+  const bool ext = c.lr_vec || c.step_w, msl = c.step_w != nullptr, so = c.second_order && with_grad;
   AnilPlan ap;
   make_anil_plan(e, c.workspace, T, n, K, ap);
-  if (ap.bytes > c.workspace_bytes)
-    return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(ap.bytes) + " bytes");
+  AnilExt ax{};
+  if (ext) make_anil_ext(e, c.workspace, ap.bytes, T, n, K, with_grad != 0, so, c.lr_vec ? c.lr_steps : 0, c.lr_grad_out != nullptr, msl, ax);
+  if ((ext ? ax.bytes : ap.bytes) > c.workspace_bytes)
+    return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(ext ? ax.bytes : ap.bytes) + " bytes");
   const size_t TP = (size_t)T * e->PS, fsz = (size_t)T * n * e->feat, pw = (size_t)T * n * e->d.ways;
+  const int Ph = (int)(e->P - e->off_wl), hbase = (int)e->off_wl;      // the head's entries of a parameter-shaped vector: [hbase, hbase + Ph)
+  const size_t hb = (size_t)e->d.ways * e->feat;                       // the bias inside a compact head-shaped vector
+  const int32_t* hperm = e->perm_dev + e->off_wl;
+  auto lr_of = [&](int k) { return ax.lrh + (c.lr_steps == 1 ? 0 : (size_t)k * ax.hs); };
   LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, c.data, (size_t)T * 2 * n, e->d.in_channels, e->d.in_h, e->d.in_w, ap.x));
   LAUNCH(e, st, OP_MISC, 0, launch_split_labels(st, c.labels, T, 2 * n, ap.ys, ap.yq));
   LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, c.theta, 0, e->perm_dev, (int)e->P, (int)e->PS, T, ap.theta));
@@ -1468,22 +1552,73 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const MetaCall& c) {
   rc = export_bn_stats(e, st, ap.act, T);
   if (rc) return rc;
   LAUNCH(e, st, OP_MISC, 4, launch_split_rows(st, ap.act.p[nl - 1], T, 2 * n, e->feat, ap.fs, ap.fq));
+  if (c.lr_vec) LAUNCH(e, st, OP_MISC, 1, launch_anil_gather_lr(st, c.lr_vec, hperm, hbase, Ph, (int)ax.hs, c.lr_steps, ax.lrh));
+  if (msl && with_grad) HIPCHK(e, hipMemsetAsync(ap.dfq, 0, fsz * sizeof(float), st));
+  // The steps call: the query set at theta_j with the launch of the final query pass (row j of the outputs; prob / dl in the final pass's
+  // slot, which no tangent pass reads).  With a gradient and j >= 1: q_j into its slot (j = K: lam's head entries), dq_j into ax.dqt, and
+  // df_q += w_j dq_j with the weight read on the device.
+  auto query_at = [&](int j) -> int {
+    const bool bwd = with_grad && j >= 1;
+    HeadArgs ha = head_args_primal(e, ap.hscr, ap.fq, ap.yq, n, T, ap.theta + (size_t)j * TP, ap.lam, c.loss_out + (size_t)j * T,
+                                   c.acc_out + (size_t)j * T, c.logits_out ? c.logits_out + (size_t)j * pw : nullptr, ap.prob + K * pw,
+                                   ap.dl + K * pw, ax.dqt, bwd);
+    if (bwd && j < K) { ha.dwl = ax.qg + (size_t)(j - 1) * T * ax.hs; ha.dbl = ha.dwl + hb; ha.gstride = ax.hs; }
+    if (bwd) HEAD_LDS(e, "head", n, ha.ways, 0);
+    LAUNCH(e, st, OP_HEAD, 0, launch_head_fwd_bwd(st, ha, T, bwd ? 1 : 0));
+    if (bwd) LAUNCH(e, st, OP_MISC, 2, launch_fma_dev(st, ap.dfq, ax.dqt, c.step_w + (j - 1), fsz));
+    return MI_OK;
+  };
   for (int k = 0; k < K; ++k) {                                                    // head-only inner loop
+    if (msl) { rc = query_at(k); if (rc) return rc; }
     float* th = ap.theta + (size_t)k * TP;
     float* gk = ap.g + (size_t)k * TP;
-    HIPCHK(e, hipMemsetAsync(gk, 0, TP * sizeof(float), st));
+    if (!ext) HIPCHK(e, hipMemsetAsync(gk, 0, TP * sizeof(float), st));             // (ext: only the head's entries are read, and the head writes them all)
     rc = head_pass(e, st, ap.hscr, ap.fs, ap.ys, n, T, th, gk, ap.tmp_loss, ap.tmp_acc, nullptr, ap.prob + k * pw, ap.dl + k * pw,
                    nullptr, true);
     if (rc) return rc;
-    LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, th, gk, inner_lr, TP, th + TP));
+    if (ext)   // theta_{k+1}'s head entries: the trunk runs on theta_0 alone
+      LAUNCH(e, st, OP_MISC, 2, launch_anil_advance(st, th + hbase, gk + hbase, e->PS, c.lr_vec ? lr_of(k) : nullptr, inner_lr, Ph, T, th + TP + hbase));
+    else
+      LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, th, gk, inner_lr, TP, th + TP));
   }
   float* thK = ap.theta + (size_t)K * TP;
   if (with_grad) HIPCHK(e, hipMemsetAsync(ap.lam, 0, TP * sizeof(float), st));
-  rc = head_pass(e, st, ap.hscr, ap.fq, ap.yq, n, T, thK, ap.lam, c.loss_out, c.acc_out, c.logits_out, ap.prob + K * pw, ap.dl + K * pw, ap.dfq,
-                 with_grad != 0);
+  if (msl) rc = query_at(K);
+  else rc = head_pass(e, st, ap.hscr, ap.fq, ap.yq, n, T, thK, ap.lam, c.loss_out, c.acc_out, c.logits_out, ap.prob + K * pw, ap.dl + K * pw, ap.dfq,
+                      with_grad != 0);
   if (rc || !with_grad) return rc;
   HIPCHK(e, hipMemsetAsync(ap.dfs, 0, fsz * sizeof(float), st));
-  if (c.second_order) {
+  if (ext) {
+    // every launch below finishes lam_k on the head slice and leaves what step k - 1 needs: dir = D_{k-1} lam_k, prod_{k-1} = g_{k-1} * lam_k
+    auto adjoint = [&](int k, bool hessian) -> int {
+      AnilAdjArgs a{};
+      a.lam = ap.lam + hbase; a.lstride = e->PS; a.cstride = ax.hs; a.ph = Ph; a.tasks = T;
+      a.alpha = c.lr_vec ? 1.f : inner_lr;
+      if (hessian) { a.hv = ap.hv + hbase; a.dfs = ap.dfs; a.rdf = ap.rdf; a.fcount = fsz; }
+      if (msl && k == K) a.w = c.step_w + (K - 1);                                                       // lam_K = w_K q_K
+      else if (msl && k >= 1) { a.w = c.step_w + (k - 1); a.inj = ax.qg + (size_t)(k - 1) * T * ax.hs; }   // lam_k takes w_k q_k
+      if (k >= 1 && ax.dir) { a.lr = lr_of(k - 1); a.dir = ax.dir; }
+      if (k >= 1 && ax.prod) { a.g = ap.g + (size_t)(k - 1) * TP + hbase; a.prod = ax.prod + (size_t)(k - 1) * T * ax.hs; }
+      if (!a.hv && !a.w && !a.lr && !a.prod) return MI_OK;            // nothing to do (the vector call's lam_K without a successor)
+      LAUNCH(e, st, OP_MISC, 2, launch_anil_adjoint(st, a));
+      return MI_OK;
+    };
+    rc = adjoint(K, false);
+    if (rc) return rc;
+    for (int k = K - 1; k >= 0; --k) {
+      if (so) {
+        HeadArgs ha = head_args(e, ap.hscr, ap.fs, ap.theta + (size_t)k * TP, c.lr_vec ? nullptr : ap.lam, ap.hv, ap.rdf, n, T);
+        if (c.lr_vec) { ha.wld = ax.dir; ha.bld = ax.dir + hb; ha.vstride = ax.hs; }
+        ha.prob = ap.prob + k * pw; ha.dl = ap.dl + k * pw;
+        HEAD_LDS(e, "head tangent", n, ha.ways, 1);
+        LAUNCH(e, st, OP_HEAD_TAN, 0, launch_head_tangent(st, ha, T));
+        rc = adjoint(k, true);
+      } else if (msl && k >= 1) {
+        rc = adjoint(k, false);       // first order: lam_k = lam_{k+1} + w_k q_k
+      }
+      if (rc) return rc;
+    }
+  } else if (c.second_order) {
     for (int k = K - 1; k >= 0; --k) {
       HIPCHK(e, hipMemsetAsync(ap.hv, 0, TP * sizeof(float), st));
       HeadArgs ha = head_args(e, ap.hscr, ap.fs, ap.theta + (size_t)k * TP, ap.lam, ap.hv, ap.rdf, n, T);   // (the features are fixed: no fd)
@@ -1498,6 +1633,11 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const MetaCall& c) {
   rc = trunk_backward(e, st, ap.scratch, ap.act, ap.x, 2 * n, T, ap.theta, ap.lam, gram);  // trunk grads join the head part in lam
   if (rc) return rc;
   LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, ap.lam, e->perm_dev, (int)e->P, (int)e->PS, T, c.meta_grad_out));
+  // lr_grad in head.parameters() order: the stored products, or (first order, final loss only) g_k times the one constant lam, whose head
+  // entries the trunk backward has left as they were
+  if (c.lr_vec && c.lr_grad_out)
+    LAUNCH(e, st, OP_MISC, 3, launch_anil_lr_fold(st, ax.prod, ax.hs, ap.g + hbase, ap.lam + hbase, e->PS, hperm, hbase, Ph, T, K, c.lr_steps,
+                                                  c.lr_grad_out));
   return MI_OK;
 }
 
@@ -1520,7 +1660,7 @@ static GraphKey graph_key(const mi_engine* e, void* stream, const MetaCall& c) {
 static int meta_batch_entry(mi_engine* e, void* stream, const MetaCall& c) {
   const int crc = check_call(e, c);
   if (crc) return crc;
-  const auto fn = c.algo == ALGO_ANIL ? meta_batch_anil_impl : meta_batch_maml_impl;
+  const auto fn = is_anil(c.algo) ? meta_batch_anil_impl : meta_batch_maml_impl;
   if (!e->graph_on || e->prof_on || e->trace || e->bn_export || !stream)     // (capture is not permitted on the legacy default stream)
     return fn(e, stream, c);
   const GraphKey key = graph_key(e, stream, c);
@@ -1611,6 +1751,30 @@ extern "C" int mi_meta_batch_anil(mi_engine* e, void* stream, const float* theta
   return meta_batch_entry(e, stream, MetaCall{ALGO_ANIL, theta, data, labels, tasks, with_grad ? tasks : 0, ways, shots, adapt_steps,
                                               second_order, inner_lr, nullptr, 0, nullptr, loss_out, acc_out, meta_grad_out, logits_out,
                                               workspace, workspace_bytes});
+}
+
+// mi_meta_batch_anil with one step size per head parameter (and per inner step when lr_steps == adapt_steps), read from device memory, and
+// the gradient of the summed query loss with respect to them (include/mi_maml.h).
+extern "C" int mi_meta_batch_anil_lr(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels, int tasks,
+                                     int ways, int shots, int adapt_steps, const float* lr_vec, int lr_steps, int second_order, int with_grad,
+                                     float* loss_out, float* acc_out, float* meta_grad_out, float* lr_grad_out, float* logits_out,
+                                     void* workspace, size_t workspace_bytes) {
+  return meta_batch_entry(e, stream, MetaCall{ALGO_ANIL_LR, theta, data, labels, tasks, with_grad ? tasks : 0, ways, shots, adapt_steps,
+                                              second_order, 0.f, lr_vec, lr_steps, lr_grad_out, loss_out, acc_out, meta_grad_out, logits_out,
+                                              workspace, workspace_bytes});
+}
+// mi_meta_batch_anil / _anil_lr with the query set scored at every theta_j and the multi-step loss sum_j step_w[j - 1] L_query(theta_j) as
+// the outer objective (include/mi_maml.h).
+extern "C" int mi_meta_batch_anil_steps(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels, int tasks,
+                                        int ways, int shots, int adapt_steps, float inner_lr, const float* lr_vec, int lr_steps,
+                                        const float* step_w, int second_order, int with_grad, float* loss_steps_out, float* acc_steps_out,
+                                        float* meta_grad_out, float* lr_grad_out, float* logits_steps_out, void* workspace,
+                                        size_t workspace_bytes) {
+  MetaCall c{ALGO_ANIL_STEPS, theta, data, labels, tasks, with_grad ? tasks : 0, ways, shots, adapt_steps, second_order, lr_vec ? 0.f : inner_lr,
+             lr_vec, lr_vec ? lr_steps : 0, lr_grad_out, loss_steps_out, acc_steps_out, meta_grad_out, logits_steps_out, workspace,
+             workspace_bytes};
+  c.step_w = step_w;
+  return meta_batch_entry(e, stream, c);
 }
 
 // Plain forward of the classifier (BatchNorm in train mode, i.e. statistics of the n images of each task batch), no

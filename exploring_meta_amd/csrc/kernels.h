@@ -302,6 +302,24 @@ hipError_t launch_fma_dev(hipStream_t st, float* x, const float* q, const float*
 // prod[k][t][i] (prod != nullptr) or g[k][t][i] * lam[t][i] (first order): fp32 products, one fp64 chain in that fixed order, rounded once
 hipError_t launch_lr_grad_fold(hipStream_t st, const float* prod, const float* g, const float* lam, const int32_t* perm, int p, int pstride,
                                int tasks, int grad_tasks, int steps, int lr_steps, float* out_ref);
+// The vector-step / multi-step-loss ANIL calls (anil_steps.hip): elementwise work on the head slice [tasks][ph] of vectors whose pointers
+// are already advanced to the head's first entry.  lstride: per-task stride of parameter-shaped vectors (lam, hv, g); cstride: of the
+// compact head-shaped ones (dir, inj, prod).
+struct AnilAdjArgs {
+  float* lam; const float* hv; const float* g; size_t lstride;   // lam in place; hv null: no Hessian term; g: only with prod
+  float alpha;                                                   // lam -= alpha * hv and dfs -= alpha * rdf
+  const float* inj; const float* w;                              // inj: lam = fmaf(*w, inj, lam); w alone: lam = *w * lam (device weight)
+  const float* lr; float* dir; float* prod; size_t cstride;      // lr [ph]: dir = lr * lam; prod = g * lam (either may be null)
+  float* dfs; const float* rdf; size_t fcount;                   // rdf null: none
+  int ph, tasks;
+};
+hipError_t launch_anil_gather_lr(hipStream_t st, const float* lr_ref, const int32_t* perm, int base, int ph, int ostride, int rows,
+                                 float* lr_eng);
+hipError_t launch_anil_advance(hipStream_t st, const float* th, const float* g, size_t pstride, const float* lr, float alpha, int ph,
+                               int tasks, float* out);
+hipError_t launch_anil_adjoint(hipStream_t st, const AnilAdjArgs& a);
+hipError_t launch_anil_lr_fold(hipStream_t st, const float* prod, size_t cstride, const float* g, const float* lam, size_t pstride,
+                               const int32_t* perm, int base, int ph, int tasks, int steps, int lr_steps, float* out_ref);
 hipError_t launch_stream_copy(hipStream_t st, const void* src, void* dst, size_t bytes);
 hipError_t launch_amax(hipStream_t st, const float* x, size_t per_task, int tasks, unsigned* cell);   // cells [T][MI_CELL_WORDS] (mi_common.h) |= exponent bits of max |x[task]|
 const unsigned* standalone_amax(hipStream_t st, int slot, const float* x, size_t per_task, int tasks, hipError_t* err);

@@ -381,6 +381,89 @@ class MetaEngine:
         _lib.check(rc, self._h)
         return loss, acc, grad, logits
 
+    def head_param_count(self):
+        """Ph = ways * fc_neurons + ways: the entries of the ANIL head (the last two tensors of `param_shapes`)."""
+        (_, ws), (_, bs) = self.spec.param_shapes()[-2:]
+        return ws[0] * ws[1] + bs[0]
+
+    def _anil_call(self, theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, step_w, first_order, with_grad, want_lr_grad, return_logits):
+        """mi_meta_batch_anil_lr (step_w None) or mi_meta_batch_anil_steps (loss, acc and logits then carry a leading axis of
+        adapt_steps + 1).  Returns (loss, acc, grad, lr_grad, logits)."""
+        s, K, Ph = self.spec, int(adapt_steps), self.head_param_count()
+        T = self._check_batch(theta, data, labels, shots, flat_data=False)
+        steps = step_w is not None
+
+        def refuse(name, t, shape_text, ok_shape):
+            # the library sizes its reads of lr_vec / step_w from the call's integers: anything else is refused here, before any launch
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_cuda or t.device != theta.device or not t.is_contiguous() or \
+                    not ok_shape:
+                shape = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+                raise _lib.MiError(f'libmi_maml error -1: {name} must be a contiguous fp32 tensor of shape {shape_text} on {theta.device}, '
+                                   f'got {shape}')
+        if steps:
+            if K < 1:
+                raise _lib.MiError(f'libmi_maml error -1: meta_batch_anil_steps needs adapt_steps >= 1, got {K}')
+            refuse('step_w', step_w, f'({K},)', torch.is_tensor(step_w) and tuple(step_w.shape) == (K,))
+        lr_steps = 0
+        if lr_vec is not None:
+            ok = torch.is_tensor(lr_vec) and lr_vec.dim() in (1, 2) and lr_vec.shape[-1] == Ph and \
+                (lr_vec.dim() == 1 or lr_vec.shape[0] in (1, max(K, 1)))
+            refuse('lr_vec', lr_vec, f'[{Ph}], [1, {Ph}] or [{max(K, 1)}, {Ph}] (Ph = ways * fc_neurons + ways)', ok)
+            lr_steps = lr_vec.numel() // Ph
+        so = (not first_order) and with_grad
+        want_lr_grad = bool(want_lr_grad) and lr_vec is not None and bool(with_grad)
+        b = C.c_size_t()
+        _lib.check(self.lib.mi_anil_workspace_bytes_steps(self._h, T, s.ways, shots, K, int(bool(with_grad)), int(so), lr_steps,
+                                                          int(want_lr_grad), int(steps), C.byref(b)), self._h)
+        ws = self._workspace(b.value)
+        nlog = shots * s.ways
+        if steps:
+            def fresh():
+                return (torch.empty(K + 1, T, dtype=torch.float32, device=self.device), torch.empty(K + 1, T, dtype=torch.float32, device=self.device),
+                        torch.empty(self.param_count, dtype=torch.float32, device=self.device) if with_grad else None,
+                        torch.empty(K + 1, T, nlog, s.ways, dtype=torch.float32, device=self.device) if return_logits else None)
+            loss, acc, grad, logits = self._persistent(('anil_steps', lr_vec is None, K + 1, T, nlog, bool(with_grad), bool(return_logits)), fresh)
+        else:
+            loss, acc, grad, logits = self._outputs('anil_lr', T, nlog, with_grad, return_logits)
+        lr_grad = None
+        if want_lr_grad:
+            lr_grad = self._persistent(('anil_lr_grad', steps, T, lr_steps), lambda: torch.empty(lr_steps, Ph, dtype=torch.float32, device=self.device))
+        head = (_ptr(theta), _ptr(data), _ptr(labels), T, s.ways, shots, K)
+        tail = (_ptr(loss), _ptr(acc), _ptr(grad), _ptr(lr_grad), _ptr(logits), _ptr(ws), ws.numel())
+        if steps:
+            rc = self._fused_call(self.lib.mi_meta_batch_anil_steps, *head, float(inner_lr) if lr_vec is None else 0.0, _ptr(lr_vec), lr_steps,
+                                  _ptr(step_w), int(not first_order), int(bool(with_grad)), *tail)
+        else:
+            rc = self._fused_call(self.lib.mi_meta_batch_anil_lr, *head, _ptr(lr_vec), lr_steps, int(not first_order), int(bool(with_grad)), *tail)
+        _lib.check(rc, self._h)
+        return loss, acc, grad, lr_grad, logits
+
+    @_on_device
+    def meta_batch_anil_lr(self, theta, data, labels, shots, adapt_steps, lr_vec, first_order=False, with_grad=True, want_lr_grad=False,
+                           return_logits=False):
+        """`meta_batch_anil` with one inner-loop step size per head parameter (mi_meta_batch_anil_lr): lr_vec [Ph], [1, Ph] or
+        [adapt_steps, Ph] with Ph = ways * fc_neurons + ways, fp32 on the engine's device, in the order of ``head.parameters()`` (weight,
+        bias).  Its values are read on the device by every call, graph replays included.
+        Returns (loss[T], acc[T], meta_grad[P] or None, lr_grad [lr_steps, Ph] or None, logits or None)."""
+        if lr_vec is None:
+            raise _lib.MiError('libmi_maml error -1: lr_vec is None: meta_batch_anil_lr takes the step sizes of the head on the device')
+        return self._anil_call(theta, data, labels, shots, adapt_steps, None, lr_vec, None, first_order, with_grad, want_lr_grad, return_logits)
+
+    @_on_device
+    def meta_batch_anil_steps(self, theta, data, labels, shots, adapt_steps, step_w, inner_lr=None, lr_vec=None, first_order=False, with_grad=True,
+                              want_lr_grad=False, return_logits=False):
+        """`meta_batch_anil` / `meta_batch_anil_lr` with the query set scored after 0, 1, .., adapt_steps head steps in the one call (the
+        trunk still runs once), and the multi-step loss sum_j step_w[j - 1] * L_query(theta_j) as the outer objective
+        (mi_meta_batch_anil_steps).  step_w [adapt_steps] fp32 on the engine's device, read there by every call, graph replays included.
+        Exactly one of inner_lr (a number) and lr_vec (as in `meta_batch_anil_lr`).
+        Returns (loss [K + 1, T], acc [K + 1, T], meta_grad [P] or None, lr_grad or None, logits [K + 1, T, S*W, ways] or None)."""
+        if (inner_lr is None) == (lr_vec is None):
+            raise ValueError('meta_batch_anil_steps takes exactly one of inner_lr and lr_vec')
+        if step_w is None:
+            raise _lib.MiError('libmi_maml error -1: step_w is None: meta_batch_anil_steps takes adapt_steps weights on the device')
+        return self._anil_call(theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, step_w, first_order, with_grad, want_lr_grad,
+                               return_logits)
+
     @_on_device
     def forward_logits(self, theta, x):
         """Plain forward (no adaptation): x [T, n, C, H, W] -> logits [T, n, ways]; BatchNorm uses each batch's statistics."""

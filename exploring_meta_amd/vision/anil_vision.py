@@ -17,11 +17,11 @@ import random
 import numpy as np
 import torch
 
-from ..core_functions import MAML, ConvBase
-from ..core_functions.anil import anil_engine, meta_batch_adapt_anil
+from ..core_functions import MAML, ConvBase, InnerLR, msl_weights
+from ..core_functions.anil import anil_engine, meta_batch_adapt_anil, meta_batch_adapt_anil_steps
 from ..core_functions.vision_models import RunningStatsFold
 from ..sharding import init_process_group, reduce_meta_batch, shard_range
-from .maml_vision import SyntheticTasks
+from .maml_vision import SyntheticTasks, inner_lr_of
 
 params = {
     "ways": 5, "shots": 5, "outer_lr": 0.003, "inner_lr": 0.5, "adapt_steps": 1, "meta_batch_size": 32,
@@ -40,8 +40,10 @@ class Lambda(torch.nn.Module):
         return self.fn(x)
 
 
-def build(dataset, ways, inner_lr, device):
-    """features / head exactly as the reference constructs them (anil_vision.py:40-43,86-94)."""
+def build(dataset, ways, inner_lr, device, p=None):
+    """features / head exactly as the reference constructs them (anil_vision.py:40-43,86-94).  p: the run's parameters when the flags
+    --inner_lr_per / --learn_inner_lr / --per_step_lr / --freeze ask for step sizes per head parameter (an ``InnerLR`` over the head's
+    ``weight`` / ``bias``, as in vision.maml_vision); else the plain number."""
     if dataset == 'omni':
         fc_neurons = 128
         features = ConvBase(output_size=64, hidden=32, channels=1, max_pool=False)
@@ -49,7 +51,8 @@ def build(dataset, ways, inner_lr, device):
         fc_neurons = 1600
         features = ConvBase(output_size=64, channels=3, max_pool=True)
     features = torch.nn.Sequential(features, Lambda(lambda x: x.view(-1, fc_neurons))).to(device)
-    head = MAML(torch.nn.Linear(fc_neurons, ways), lr=inner_lr).to(device)
+    linear = torch.nn.Linear(fc_neurons, ways).to(device)
+    head = MAML(linear, lr=inner_lr if p is None else inner_lr_of(linear, p)).to(device)
     return features, head
 
 
@@ -62,8 +65,10 @@ def run(dataset, p, log=print):
         init_process_group(local)
     random.seed(p['seed']); np.random.seed(p['seed']); torch.manual_seed(p['seed']); torch.cuda.manual_seed(p['seed'])
     device = torch.device('cuda', local)
-    features, head = build(dataset, p['ways'], p['inner_lr'], device)
-    all_parameters = list(features.parameters()) + list(head.parameters())           # anil_vision.py:97
+    features, head = build(dataset, p['ways'], p['inner_lr'], device, p)
+    # anil_vision.py:97; head.parameters() includes a learnable InnerLR's values (a submodule of MAML), so they are stepped by the
+    # optimiser and all-reduced with the rest
+    all_parameters = list(features.parameters()) + list(head.parameters())
     opt = torch.optim.Adam(all_parameters, lr=p['outer_lr'])
     T = p['meta_batch_size']
     lo, hi = shard_range(T, rank, world)
@@ -73,6 +78,19 @@ def run(dataset, p, log=print):
     save_dir = p.get('save_dir') or ''
     if save_dir and rank == 0:
         os.makedirs(os.path.join(save_dir, 'model_checkpoints'), exist_ok=True)
+    msl_its = int(p.get('msl_iterations', 0)) if p.get('multi_step_loss') and p['adapt_steps'] >= 1 else 0
+    step_w = torch.zeros(max(p['adapt_steps'], 1), device=device)      # annealed in place: the engine reads the weights on the device
+
+    def adapt(it, data, labels):
+        """One fused call: the multi-step loss while it < --msl_iterations (--multi_step_loss), else the plain call.  The logged loss and
+        accuracy are those of the last step either way."""
+        if it >= msl_its or not torch.is_grad_enabled():
+            return meta_batch_adapt_anil(head.clone(), features, data, labels, p['adapt_steps'], p['shots'], p['ways'])
+        step_w.copy_(torch.tensor(msl_weights(p['adapt_steps'], it, msl_its)))
+        total, losses, accs = meta_batch_adapt_anil_steps(head.clone(), features, data, labels, p['adapt_steps'], p['shots'], p['ways'],
+                                                          step_weights=step_w)
+        return total, losses[-1], accs[-1]
+
     for it in range(p['num_iterations']):
         opt.zero_grad()
         ids = list(range(it * T + lo, it * T + hi))
@@ -83,8 +101,7 @@ def run(dataset, p, log=print):
             fold = RunningStatsFold(eng, features[0], eng.spec, T, lo, hi, 1, 2 * p['ways'] * p['shots'])
         if ids:
             d, l = train.sample_batch(ids)
-            total, losses, accs = meta_batch_adapt_anil(head.clone(), features, d.to(device), l.to(device), p['adapt_steps'],
-                                                        p['shots'], p['ways'])
+            total, losses, accs = adapt(it, d.to(device), l.to(device))
             total.backward()
             if fold:
                 fold.collect(0)
@@ -119,19 +136,50 @@ def run(dataset, p, log=print):
     if rank == 0 and save_dir:                                                        # anil_vision.py:163-164
         torch.save(features.state_dict(), os.path.join(save_dir, 'features.pt'))
         torch.save(head.state_dict(), os.path.join(save_dir, 'head.pt'))
+        if isinstance(head.lr, InnerLR):
+            torch.save(head.lr.state_dict(), os.path.join(save_dir, 'inner_lr.pt'))
     if world > 1:
         torch.distributed.destroy_process_group()
     return (features, head), metrics
 
 
-if __name__ == '__main__':
+def build_parser():
     parser = argparse.ArgumentParser(description='ANIL on Vision (MI355X engine)')
     parser.add_argument('--dataset', type=str, default='min', help='omni or min')
     for k, v in params.items():
         parser.add_argument(f'--{k}', type=type(v), default=v)
-    parser.add_argument('--save_dir', type=str, default='', help='write model_checkpoints/model_{features,head}_<it+1>.pt every save_every iterations and features.pt / head.pt at the end')
-    args = parser.parse_args()
-    for k in params:
-        params[k] = getattr(args, k)
-    params['save_dir'] = args.save_dir
-    run(args.dataset, params)
+    parser.add_argument('--save_dir', type=str, default='', help='write model_checkpoints/model_{features,head}_<it+1>.pt every save_every iterations and features.pt / head.pt (/ inner_lr.pt) at the end')
+    parser.add_argument('--inner_lr_per', choices=('scalar', 'tensor', 'parameter'), default='scalar',
+                        help="one inner step size for the head, per tensor of it ('weight', 'bias') or per entry")
+    parser.add_argument('--learn_inner_lr', action='store_true', help='the inner step sizes are meta-learned with the model (MetaSGD)')
+    parser.add_argument('--per_step_lr', action='store_true', help='one set of step sizes per inner step')
+    parser.add_argument('--freeze', nargs='+', default=[], metavar='PREFIX', help="prefixes of the head's parameter names that are not adapted ('weight', 'bias')")
+    parser.add_argument('--multi_step_loss', action='store_true',
+                        help='MAML++ multi-step loss: the outer objective weights the query loss after every head step (msl_weights)')
+    parser.add_argument('--msl_iterations', type=int, default=0, metavar='N',
+                        help='iterations over which the multi-step weights anneal to the final step; from iteration N on the plain call runs')
+    return parser
+
+
+def parse_args(argv=None):
+    return build_parser().parse_args(argv)
+
+
+def params_of(args):
+    """The run's parameter dict from parsed flags (the defaults are the reference's run)."""
+    p = {k: getattr(args, k) for k in params}
+    p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
+             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations)
+    return p
+
+
+def main(argv=None, log=print):
+    """Parse the flags and run; returns ((features, head), metrics of the last iteration)."""
+    args = parse_args(argv)
+    p = dict(params)
+    p.update(params_of(args))
+    return run(args.dataset, p, log=log)
+
+
+if __name__ == '__main__':
+    main()

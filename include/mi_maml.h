@@ -218,6 +218,50 @@ int mi_meta_batch_anil(mi_engine* e, void* stream, const float* theta, const flo
                        float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
                        void* workspace, size_t workspace_bytes);
 
+/* mi_meta_batch_anil with one inner-loop step size per HEAD parameter, optionally per inner step, and the gradient of the summed query
+ * loss with respect to them (freezing the head's weight or bias = step 0, per-tensor steps, learnable steps); and the same call, scalar
+ * or vector step, with the query set scored at EVERY theta_j and the multi-step loss as the outer objective.  Per task, phi = trunk,
+ * theta = head (W, b), Ph = ways * fc_neurons + ways, D_k = diag(lr_k) with lr_k = row (lr_steps == 1 ? 0 : k) of lr_vec (scalar step:
+ * D_k = inner_lr * I); the trunk runs once on all 2n images and is split into f_s, f_q as in mi_meta_batch_anil:
+ *   theta_{k+1} = theta_k - D_k g_k,                      g_k = grad_theta L_s(theta_k; f_s)
+ *   q_j = grad_theta L_q(theta_j; f_q),  dq_j = dL_q(theta_j)/df_q,     J = sum_t sum_{j = 1..K} w_j L_q,t(theta_j)
+ *   second order:  lam_K = w_K q_K,   lam_k = lam_{k+1} - H_k (D_k lam_{k+1}) + w_k q_k  (k = K-1..1),   lam_0 = lam_1 - H_0 (D_0 lam_1)
+ *                  df_s  = -sum_k R_{D_k lam_{k+1}}{ dL_s/df_s }(theta_k)
+ *   first order:   lam_k = sum_{j >= max(k, 1)} w_j q_j,   df_s = 0
+ *   df_q = sum_j w_j dq_j;   head part of meta_grad = sum_t lam_0;   trunk part = ONE trunk backward from the interleaved [df_s, df_q]
+ *   lr_grad_k [Ph] = -sum_t g_k * lam_{k+1}          (lr_steps == 1: summed over k as well)
+ * mi_meta_batch_anil_lr is the case w = (0, .., 0, 1) with the plain call's outputs.  The head tangent pass is driven with D_k lam and the
+ * update is lam - 1 * (H dir), as in mi_meta_batch_maml_lr.
+ *   lr_vec      [lr_steps, Ph]  device memory, the order of head.parameters(): weight [ways, fc_neurons] in the reference's
+ *                               view(-1, fc_neurons) column order, then bias; the engine applies the column permutation it applies to
+ *                               theta's head weight.  The VALUES are read on the device by every call, graph replays included.  An entry
+ *                               whose step is exactly 0 keeps its parameter bit for bit.
+ *   lr_steps    1 or adapt_steps (with adapt_steps == 0 only 1); 0 with lr_vec == NULL in the steps call (the scalar step inner_lr)
+ *   step_w      [adapt_steps]   device memory, fp32, read on the device like lr_vec; theta_0 is scored but carries no weight
+ *   lr_grad_out [lr_steps, Ph]  sum over the tasks, in lr_vec's order, or NULL.  fp32 products, one fixed-order fp64 chain over the
+ *                               updates of a row ascending and the tasks ascending, rounded once: bitwise reproducible.
+ *   loss_steps_out / acc_steps_out [adapt_steps + 1, tasks], logits_steps_out [adapt_steps + 1, tasks, ways * shots, ways] or NULL:
+ *                               row j is what mi_meta_batch_anil writes with adapt_steps = j.
+ * The head forward / backward / tangent launches are those of mi_meta_batch_anil; the elementwise work between them touches the head's
+ * Ph entries per task, not the whole parameter vector.  A uniform lr_vec gives the plain call's loss, accuracy, logits and first-order
+ * meta-gradient bit for bit, and its second-order one when the step is a power of two; step_w = (0, .., 0, 1) with the scalar step gives
+ * the plain call in row adapt_steps and in meta_grad_out.  The BatchNorm export sees the one trunk pass.  MI_ERR_ARG before any HIP call:
+ * lr_vec NULL in _lr, lr_steps not 1 / adapt_steps, lr_grad_out with with_grad == 0 or without lr_vec, step_w NULL or adapt_steps < 1 in
+ * _steps, a debug trace being set, and what mi_meta_batch_anil refuses (a mean-pooled head; ways * shots beyond the head's LDS limits).
+ * Launches on top of mi_meta_batch_anil's (K = adapt_steps), never a function of tasks: see DESIGN.md section 23.
+ * Workspace: mi_anil_workspace_bytes_steps, one query for both entries (lr_steps = 0: scalar step; step_outputs 0: _lr, 1: _steps): the
+ * plain plan at unchanged offsets, and behind it the step sizes in engine layout, the direction, the q_j, one dq and the products. */
+int mi_anil_workspace_bytes_steps(const mi_engine* e, int tasks, int ways, int shots, int adapt_steps, int with_grad, int second_order,
+                                  int lr_steps, int want_lr_grad, int step_outputs, size_t* bytes);
+int mi_meta_batch_anil_lr(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels, int tasks,
+                          int ways, int shots, int adapt_steps, const float* lr_vec, int lr_steps, int second_order, int with_grad,
+                          float* loss_out, float* acc_out, float* meta_grad_out, float* lr_grad_out, float* logits_out,
+                          void* workspace, size_t workspace_bytes);
+int mi_meta_batch_anil_steps(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels, int tasks,
+                             int ways, int shots, int adapt_steps, float inner_lr, const float* lr_vec, int lr_steps, const float* step_w,
+                             int second_order, int with_grad, float* loss_steps_out, float* acc_steps_out, float* meta_grad_out,
+                             float* lr_grad_out, float* logits_steps_out, void* workspace, size_t workspace_bytes);
+
 /* Plain classifier forward, no adaptation: `learner(x)` / `model(x)` (vision_models.py:51-55,107-110), BatchNorm in train
  * mode over the n images of each of the `tasks` batches.  x [tasks, n, C, H, W] NCHW; logits_out [tasks, n, ways]. */
 int mi_forward_workspace_bytes(const mi_engine* e, int tasks, int n, size_t* bytes);
