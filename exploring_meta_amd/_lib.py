@@ -237,6 +237,20 @@ _SIGS = {
                                  [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]),
     'mi_trpo_fvp_general_steps': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
                                   [C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    'mi_policy_adapt_lr': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    'mi_trpo_steps_lr_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    'mi_trpo_surrogate_steps_lr': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 10 +
+                                   [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_size_t]),
+    'mi_trpo_fvp_steps_lr': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
+                             [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    'mi_trpo_general_steps_lr_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    'mi_trpo_kl_prepare_steps_lr': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 +
+                                    [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    'mi_trpo_fvp_general_steps_lr': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                     [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t]),
     'mi_profile_enable': (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     'mi_profile_kinds': (C.c_int, []),
     'mi_profile_op_name': (C.c_char_p, [C.c_int]),

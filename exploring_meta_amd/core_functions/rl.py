@@ -435,9 +435,27 @@ def trpo_a2c_loss(episodes, learner, baseline, gamma, tau, update_vf=True):
     return -(lp * adv[0].reshape(-1, 1).to(lp)).mean()
 
 
-def _trpo_step(eng, inner_lr, head_only):
-    """``step`` of the adapt loop for TRPO: mi_policy_adapt."""
-    return lambda theta, b, adv, k=0: eng.adapt(theta, b['states'], b['actions'], adv, b['count'], inner_lr, head_only=head_only)[0]
+def _trpo_step(eng, inner_lr, head_only, table=None, step_row=None):
+    """``step`` of the adapt loop for TRPO: mi_policy_adapt, or with a step-size ``table`` [rows, P] (``_trpo_lr_table``)
+    mi_policy_adapt_lr with the row ``step_row[k]`` of adapt step k."""
+    if table is None:
+        return lambda theta, b, adv, k=0: eng.adapt(theta, b['states'], b['actions'], adv, b['count'], inner_lr, head_only=head_only)[0]
+    return lambda theta, b, adv, k=0: eng.adapt(theta, b['states'], b['actions'], adv, b['count'], table[step_row[k]], head_only=head_only)[0]
+
+
+def _trpo_lr_table(learner, name):
+    """The FIXED step-size table [rows, P] (fp32, engine order, on the policy's device) of a ``MAML`` wrapper that holds more than one
+    number -- a non-learnable ``InnerLR``, or a number with ``allow_nograd`` around a policy with frozen parameters; None for the bare
+    policy or a wrapper with one number (``params['inner_lr']`` is the step).  Steps that require grad are refused: TRPO's outer step is
+    a trust region over theta alone, and their gradient would have to enter the KL's curvature product as well."""
+    lrv = _policy_lr_vector(learner)
+    if lrv is None:
+        return None
+    if lrv.requires_grad:
+        raise ValueError(f"{name}: per-parameter inner-loop step sizes (an InnerLR, or allow_nograd) are taken by the VPG / PPO / DiCE "
+                         "calls only; the TRPO calls adapt with the one number params['inner_lr'] -- wrap the policy as MAML(policy, lr=number)"
+                         " -- or with FIXED steps: an InnerLR(learnable=False) is accepted, a learnable one is not")
+    return lrv.detach().to(_unwrap(learner).sigma.device, torch.float32).contiguous()
 
 
 def trpo_update(episodes, learner, baseline, inner_lr, gamma, tau, anil=False, first_order=False):
@@ -445,12 +463,19 @@ def trpo_update(episodes, learner, baseline, inner_lr, gamma, tau, anil=False, f
     second-order dependence on the original parameters is handled inside meta_optimize_trpo's fused calls)."""
     # anil only sets allow_unused (rl.py:371): which parameters move is decided by the policy's own switch -- with
     # DiagNormalPolicyANIL.turn_off_body_grads() the body's gradients are None and maml_update leaves it unchanged.
-    _refuse_lr_vector(learner, 'trpo_update')
+    table = _trpo_lr_table(learner, 'trpo_update')
     b = _replay_batch([_as_replay(episodes)], learner.input_size, learner.output_size, learner.sigma.device)
     adv, _ = _batch_advantages(b, baseline, gamma, tau)
-    step = _trpo_step(learner.engine(), inner_lr, bool(getattr(learner, 'features_no_grad', False)))
+    row = 0
+    if table is not None and table.shape[0] > 1:              # the row the step-wise learner's ``adapt`` would read
+        row = int(getattr(learner, '_steps_done', 0))
+        if row >= table.shape[0]:
+            raise ValueError(f'trpo_update: this learner holds step sizes for {table.shape[0]} inner steps and has taken {row}')
+    step = _trpo_step(learner.engine(), inner_lr, bool(getattr(learner, 'features_no_grad', False)), table, [row])
     new = deepcopy(learner)
     new.load_flat(step(learner.flat(), b, adv)[0])
+    if table is not None:
+        new.__dict__['_steps_done'] = row + 1
     return new
 
 
@@ -500,11 +525,12 @@ def fast_adapt_trpo(task, learner, baseline, params, anil=False, first_order=Fal
     """reference rl.py:377-406.  ``task.run(policy, episodes=n)`` returns a replay (dict or cherry-style object, ``_as_replay``).
     ``learner``: the policy itself or a ``MAML`` wrapper around it (rl/anil_trpo.py:84 wraps; rl.py:382,396 reach the policy as
     ``learner.module``)."""
-    _refuse_lr_vector(learner, 'fast_adapt_trpo')
+    table = _trpo_lr_table(learner, 'fast_adapt_trpo')
+    step_row = None if table is None else _lr_step_rows(table.shape[0], params['adapt_steps'])
     if anil:                                                   # rl.py:381-382
         _unwrap(learner).turn_off_body_grads()
     walk = _TaskWalk(task, learner, params, (lambda actor: _unwrap(actor).turn_on_body_grads()) if anil else None)
-    step = _trpo_step(learner.engine(), params['inner_lr'], bool(getattr(learner, 'features_no_grad', False)))
+    step = _trpo_step(learner.engine(), params['inner_lr'], bool(getattr(learner, 'features_no_grad', False)), table, step_row)
     _adapt_loop(walk, step, learner.flat(), params['adapt_steps'], baseline, params['gamma'], params['tau'], True)
     learner, task_replay = walk.current, walk.replays
     valid_loss = trpo_a2c_loss(task_replay[-1], learner, baseline, params['gamma'], params['tau'], update_vf=False)
@@ -578,7 +604,8 @@ def fast_adapt_trpo_tasks(goals, policy, baseline, params, seed, first_id, anil=
     run k (the support steps, then the query) uses rollout id ``first_id + i * (adapt_steps + 1) + k`` -- what task i gets from
     ``fast_adapt_trpo`` with ``Particles2DRunner(goal, L, rollout='device', seed=seed, first_id=first_id + i * (adapt_steps + 1))``.
     ``baseline`` is left as after that task-by-task walk: fitted to the last task's last support replay."""
-    _refuse_lr_vector(policy, 'fast_adapt_trpo_tasks')
+    table = _trpo_lr_table(policy, 'fast_adapt_trpo_tasks')
+    step_row = None if table is None else _lr_step_rows(table.shape[0], params['adapt_steps'])
     pol = _unwrap(policy)
     T, run = _rollout_run('fast_adapt_trpo_tasks', pol, goals, params, seed, first_id)
     eng, A, E = pol.engine(), pol.output_size, params['adapt_batch_size']
@@ -588,8 +615,8 @@ def fast_adapt_trpo_tasks(goals, policy, baseline, params, seed, first_id, anil=
     head_only = bool(getattr(pol, 'features_no_grad', False))
     if anil:                                                   # rl.py:395-396
         pol.turn_on_body_grads()
-    theta, _, out, wts, replays = _adapt_loop(run, _trpo_step(eng, params['inner_lr'], head_only), pol.flat(), params['adapt_steps'],
-                                              baseline, gamma, tau, True, keep_views=True)
+    theta, _, out, wts, replays = _adapt_loop(run, _trpo_step(eng, params['inner_lr'], head_only, table, step_row), pol.flat(),
+                                              params['adapt_steps'], baseline, gamma, tau, True, keep_views=True)
     # the query replay's loss with each task's own baseline, as fitted to its last support replay (update_vf=False, rl.py:401)
     adv, _ = _batch_advantages(out, baseline, gamma, tau, fit=False, weights=wts)
     thetas = theta if theta.dim() == 2 else theta.unsqueeze(0).expand(T, -1)
@@ -642,7 +669,12 @@ class _SurrogateContext:
             thetas = torch.stack([p.flat() for p in iter_policies])
         self.old_loc = self.engine.forward(thetas, self.qry['states'])
         self.old_scale = torch.exp(torch.clamp(thetas[:, :A], min=float(np.log(1e-6)))).contiguous()
-        self.inner_lr = params['inner_lr']
+        # the step of every engine call: the number, or the fixed step-size table of a MAML wrapper (``_trpo_lr_table``) with the row
+        # each update reads.  The surrogate re-adapts with the table as it is (the reference replays the inner step with every
+        # parameter, rl.py:447-453), whatever head mask the stored old policies were adapted with.
+        table = _trpo_lr_table(policy, 'meta_surrogate_loss')
+        self.inner_lr = params['inner_lr'] if table is None else table
+        self.lr_rows = {} if table is None else {'step_lr_row': _lr_step_rows(table.shape[0], K)}     # (only the table's calls name the rows)
 
     # Multi-GPU (TRPO): every rank holds a shard of the task list; the mean over tasks of (loss, kl, grad) and
     # of each Fisher-vector product is completed by one small all-reduce per evaluation (RCCL; 42 KB for the 2x100 policy).
@@ -661,7 +693,8 @@ class _SurrogateContext:
         return tuple(out)
 
     def evaluate(self, theta, want_grad=False):
-        loss, kl, grad = self.engine.surrogate(theta, self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad)
+        loss, kl, grad = self.engine.surrogate(theta, self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad,
+                                               **self.lr_rows)
         if grad is None:
             loss, kl = self._allmean(loss, kl)
         else:
@@ -672,7 +705,7 @@ class _SurrogateContext:
         """ANIL-TRPO: the re-adapted policies differ from the stored old ones, the Fisher form does not apply; set up the exact
         KL Hessian-vector product (``PolicyEngine.kl_prepare``) at the theta of the preceding ``evaluate``.  ``theta`` is not
         read: the engine kept it.  Returns d mean KL / d theta if ``want_grad``."""
-        grad = self.engine.kl_prepare(self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad)
+        grad = self.engine.kl_prepare(self.sup, self.qry, self.old_loc, self.old_scale, self.inner_lr, want_grad, **self.lr_rows)
         self.general = True
         return None if grad is None else self._allmean(grad)[0]
 
@@ -680,8 +713,8 @@ class _SurrogateContext:
         """The curvature product at the theta of the preceding ``evaluate`` (``theta`` is not read: the engine kept it)."""
         # the damping term is linear in v, so averaging the per-rank results keeps it exact
         if getattr(self, 'general', False):
-            return self._allmean(self.engine.fvp_general(self.sup, self.qry, self.old_scale, self.inner_lr, damping, v))[0]
-        return self._allmean(self.engine.fvp(self.sup, self.qry, self.inner_lr, damping, v))[0]
+            return self._allmean(self.engine.fvp_general(self.sup, self.qry, self.old_scale, self.inner_lr, damping, v, **self.lr_rows))[0]
+        return self._allmean(self.engine.fvp(self.sup, self.qry, self.inner_lr, damping, v, **self.lr_rows))[0]
 
 
 def meta_surrogate_loss(iter_replays, iter_policies, policy, baseline, params, anil=False):
@@ -745,7 +778,7 @@ def _conjugate_gradient_device(Ax, b, num_iterations, tol, eps):
 def meta_optimize_trpo(params, policy, baseline, iter_replays, iter_policies, anil=False):
     """reference rl.py:409-438: CG step direction from the Fisher-vector product of the mean KL, then backtracking line
     search on (surrogate loss, KL); updates ``policy`` in place.  Returns diagnostics."""
-    _refuse_lr_vector(policy, 'meta_optimize_trpo')
+    _trpo_lr_table(policy, 'meta_optimize_trpo')            # (a learnable wrapper is refused under this function's name)
     ctx = _SurrogateContext(iter_replays, iter_policies, policy, baseline, params)
     theta = policy.flat()
     old_loss, old_kl, grad = ctx.evaluate(theta, want_grad=True)
@@ -1070,7 +1103,9 @@ def evaluate(algo, env, policy, baseline, params, anil=False, render=False, gene
                 fast_adapt_ppo(task, learner, baseline, params)
                 adapted = learner._adapted_policy
             else:
-                adapted, _, _, _, _ = fast_adapt_trpo(task, _unwrap(learner), baseline, params, anil=anil)
+                # (a wrapper with a fixed step-size table adapts with it; any other learner as the bare policy, as before)
+                actor = learner if _trpo_lr_table(learner, 'evaluate_trpo') is not None else _unwrap(learner)
+                adapted, _, _, _, _ = fast_adapt_trpo(task, actor, baseline, params, anil=anil)
         query = _as_replay(task.run(adapted, episodes=params['adapt_batch_size']))    # rl.py:181-184
         tasks_rewards.append(query['rewards'].sum().item() / params['adapt_batch_size'])
         tasks_success.append(get_ep_successes(query, params.get('max_path_length')) / params['adapt_batch_size'])

@@ -15,6 +15,17 @@
 // One set of entry points for any number K of inner updates (K = 1 of a supported ReLU policy takes the fused sweeps):
 //   MAML-TRPO (new == old, Fisher form exact)          mi_trpo_surrogate_steps / mi_trpo_fvp_steps
 //   ANIL-TRPO (new != old, exact Hessian of mean KL)   ... then mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps
+// Each of them also takes a FIXED step-size table in place of the number lr (mi_policy_adapt_lr, mi_trpo_*_steps_lr: the same
+// implementation with an LrCall; the scalar entries pass none and launch what they launched before).  lr_vec [rows][P] in the order
+// above, shared by all tasks; update k reads row step_lr_row[k] = d_k (mi_policy_adapt_lr's head_only: times the head mask):
+//   theta_{k+1} = theta_k - d_k (.) g_k                       J_k = I - D_k H_k
+//   tangent  (J_k u):      u_{k+1} = u_k - d_k (.) (H_k u_k)
+//   adjoint  (J_k^T lam):  lam_k   = lam_{k+1} - H_k (d_k (.) lam_{k+1})
+//   surrogate gradient = mean_t lam_0, lam_K = grad S_t(theta_K);    Fisher form (new == old) = mean_t J^T F_t J v + damping v
+//   exact KL Hessian:  rho_K = Hess KL_t(theta_K) u_K,
+//                      rho_k = rho_{k+1} - H_k (d_k (.) rho_{k+1}) - T_k[u_k, d_k (.) lam_{k+1}],    product = mean_t rho_0 + damping v
+// With one number the tangent and the adjoint recursion are the same operation (jac_apply's order flag); with a vector they are not:
+// D H on the adjoint side is wrong.  The adjoint side drives its tangent pass with d (.) x and subtracts what comes back.
 #include <string>
 #include <vector>
 #include <cmath>
@@ -848,8 +859,10 @@ __global__ void lr_advance_kernel(const float* a, size_t astride, const float* _
 // One adjoint advance: lam_k = lam_{k+1} - mask_m(hv) in place (hv NULL: lam is lam_K as the query pass left it), and for the update
 // below it (lr NULL: there is none) dir = d_{k-1} (.) lam_k, the direction of its tangent pass, and prod = m (.) g_{k-1} (.) lam_k, its
 // term of lr_grad (prod NULL: not wanted).  Masked and zero-step entries of dir, masked entries of prod, are exact zeros.
-__global__ void lr_adjoint_kernel(float* __restrict__ lam, const float* __restrict__ hv, const float* __restrict__ lr,
-                                  const float* __restrict__ g, int p, int body_lo, int body_hi, float* __restrict__ dir,
+// The TRPO recursions (mi_trpo_*_steps_lr) use the same launch: lam_k may go to a buffer of its own (out != lam: every entry is
+// written), and the general product's rho_k = rho_{k+1} - (hv + s3) subtracts the third-derivative term with it (s3 NULL: none).
+__global__ void lr_adjoint_kernel(const float* lam, const float* __restrict__ hv, const float* __restrict__ s3, const float* __restrict__ lr,
+                                  const float* __restrict__ g, int p, int body_lo, int body_hi, float* out, float* __restrict__ dir,
                                   float* __restrict__ prod) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p) return;
@@ -857,8 +870,10 @@ __global__ void lr_adjoint_kernel(float* __restrict__ lam, const float* __restri
   const bool masked = i >= body_lo && i < body_hi;
   float l = lam[o];
   if (hv && !masked) {
-    l = l - hv[o];
-    lam[o] = l;
+    l = s3 ? l - (hv[o] + s3[o]) : l - hv[o];
+    out[o] = l;
+  } else if (out != lam) {
+    out[o] = l;
   }
   if (!lr) return;
   const float d = masked ? 0.f : lr[i];
@@ -962,14 +977,17 @@ extern "C" int mi_policy_meta_lr_workspace_bytes(const mi_policy* p, int tasks, 
 // trpo_update (rl.py:361-374) for a meta-batch: theta_out[t] = theta[t] - lr * grad_t(-mean(logp * adv)).  loss_out [T].
 // Workspace: the plan of one kept update (mi_policy_meta_workspace_bytes(steps = 1, n_batches = 1, second_order = 1); the TRPO
 // workspaces start with it).
-extern "C" int mi_policy_adapt(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
-                               const float* actions, const float* adv, const int32_t* count, int tasks, int batch, float lr,
-                               int head_only, float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
-  if (!p || !theta || !states || !actions || !adv || !theta_out || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
+// lr_vec: mi_policy_adapt_lr -- ONE row [P] of the step-size table in place of the number lr; the head mask of head_only is folded into
+// the advance (lr_advance_kernel), and an entry whose step is exactly 0 leaves with the bits of theta.
+static int policy_adapt_impl(mi_policy* p, const std::string& fn, void* stream, const float* theta, size_t tstride, const float* states,
+                             const float* actions, const float* adv, const int32_t* count, int tasks, int batch, float lr,
+                             const float* lr_vec, int head_only, float* theta_out, float* loss_out, void* workspace,
+                             size_t workspace_bytes) {
+  if (!p || !theta || !states || !actions || !adv || !theta_out || !workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   MetaPlan pl;
   meta_plan(p, workspace, tasks, batch, 1, 1, true, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes));
+  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(pl.bytes));
   StepSet& s = pl.st[0];
   int rc = mlp_forward(p, st, tasks, batch, states, theta, tstride, s.a);
   if (rc) return rc;
@@ -981,10 +999,20 @@ extern "C" int mi_policy_adapt(mi_policy* p, void* stream, const float* theta, s
   PCHK(p, gauss(st, tasks, ga));
   rc = mlp_backward(p, st, tasks, batch, states, theta, tstride, s.a, s.dmu, s.d2, s.d1, pl.g, nullptr, nullptr, head_only != 0);
   if (rc) return rc;
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)p->P, 256), tasks), dim3(256), 0, st, theta, tstride, pl.g, lr,
-                     (int)p->P, theta_out);
+  if (lr_vec)
+    hipLaunchKernelGGL(lr_advance_kernel, dim3(ceil_div((int)p->P, 256), tasks), dim3(256), 0, st, theta, tstride, (const float*)pl.g, lr_vec,
+                       (int)p->P, head_only ? (int)p->o_w1 : 0, head_only ? (int)p->o_w3 : 0, theta_out);
+  else
+    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)p->P, 256), tasks), dim3(256), 0, st, theta, tstride, pl.g, lr,
+                       (int)p->P, theta_out);
   PCHK(p, hipGetLastError());
   return MI_OK;
+}
+extern "C" int mi_policy_adapt(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
+                               const float* actions, const float* adv, const int32_t* count, int tasks, int batch, float lr,
+                               int head_only, float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
+  return policy_adapt_impl(p, std::string(), stream, theta, tstride, states, actions, adv, count, tasks, batch, lr, nullptr, head_only,
+                           theta_out, loss_out, workspace, workspace_bytes);
 }
 
 // One primal pass of the VPG / PPO / DiCE losses for all tasks at parameters th (stride ts floats per task: P, or 0 = shared): forward, loss + cotangents
@@ -1095,8 +1123,9 @@ static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta
     // the vector form drives the tangent pass of update k with dir = d_k (.) lam_{k+1} (in vmask) and subtracts H_k dir as it comes: the
     // advance that finishes lam_{k+1} also writes the dir (and the lr_grad products) of update k
     auto adjoint = [&](const float* hv, int k) {      // k: the update whose dir / prod to write, -1 = none
-      hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, pl.lam, hv, k >= 0 ? lr_row(k) : (const float*)nullptr,
-                         k >= 0 ? (const float*)g_of(k) : (const float*)nullptr, (int)P, m_lo, m_hi, pl.vmask,
+      hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)pl.lam, hv, (const float*)nullptr,
+                         k >= 0 ? lr_row(k) : (const float*)nullptr,
+                         k >= 0 ? (const float*)g_of(k) : (const float*)nullptr, (int)P, m_lo, m_hi, pl.lam, pl.vmask,
                          k >= 0 && lp.prod ? lp.prod + (size_t)k * TP : (float*)nullptr);
     };
     if (lrc && K > 0) {
@@ -1381,9 +1410,36 @@ static int hvp_step(mi_policy* p, hipStream_t st, MetaPlan& pl, StepSet& s, int 
 }
 // x_t <- (I - lr H_k) x_t through the updates, in place on x [T][P] (pl.hv is scratch): k = 0 .. K-1 is J_t x, the tangent
 // recursion; transpose walks k = K-1 .. 0 and is J_t^T x, the adjoint recursion (every H_k is symmetric: only the order differs).
+// With a step-size table (lrc; d_k = the row of update k) the two are different operations:
+//   tangent    x <- x - d_k (.) (H_k x)                          (lr_advance_kernel in place)
+//   adjoint    x <- x - H_k (d_k (.) x)                          the tangent pass is driven with dir = d_k (.) x (in pl.g, idle once the
+//              inner updates are done), and the launch that finishes x for update k also writes the dir of update k - 1 (lr_adjoint_kernel)
+static const float* trpo_lr_row(const LrCall* lrc, int k, size_t P) { return lrc->vec + (size_t)(lrc->step_row ? lrc->step_row[k] : 0) * P; }
 static int jac_apply(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupStack& sup, int T, int B, int K, bool transpose, float lr,
-                     float* x) {
+                     const LrCall* lrc, float* x) {
   const size_t P = p->P, TP = (size_t)T * P;
+  if (lrc) {
+    const dim3 pgrid(ceil_div((int)P, 256), T);
+    const float* none = nullptr;
+    if (transpose) {
+      hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)x, none, none, trpo_lr_row(lrc, K - 1, P), none, (int)P, 0, 0,
+                         x, pl.g, (float*)nullptr);
+      PCHK(p, hipGetLastError());
+    }
+    for (int i = 0; i < K; ++i) {
+      const int k = transpose ? K - 1 - i : i;
+      int rc = hvp_step(p, st, pl, pl.st[k], T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), sup_at(p, sup, T, B, k),
+                        transpose ? pl.g : x, pl.hv);
+      if (rc) return rc;
+      if (transpose)
+        hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)x, (const float*)pl.hv, none,
+                           k > 0 ? trpo_lr_row(lrc, k - 1, P) : none, none, (int)P, 0, 0, x, pl.g, (float*)nullptr);
+      else
+        hipLaunchKernelGGL(lr_advance_kernel, pgrid, dim3(256), 0, st, (const float*)x, P, (const float*)pl.hv, trpo_lr_row(lrc, k, P), (int)P, 0, 0, x);
+      PCHK(p, hipGetLastError());
+    }
+    return MI_OK;
+  }
   for (int i = 0; i < K; ++i) {
     const int k = transpose ? K - 1 - i : i;
     int rc = hvp_step(p, st, pl, pl.st[k], T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), sup_at(p, sup, T, B, k), x, pl.hv);
@@ -1412,9 +1468,11 @@ static SweepArgs sweep_hvp_args(const mi_policy* p, const StepsPlan& pl, int T, 
   hs.d2 = s.d2; hs.count = r.cn; hs.theta = pl.theta; hs.tstride = 0;
   return hs;
 }
-static FoldArgs fold_base(const mi_policy* p, const StepsPlan& pl, int T, float lr) {
+// lrv: the row [P] of the step-size table the one update reads (NULL: the number lr)
+static FoldArgs fold_base(const mi_policy* p, const StepsPlan& pl, int T, float lr, const float* lrv = nullptr) {
   FoldArgs f{};
   f.partial = pl.partial; f.slots = pl.slots; f.spt = pl.spt; f.spw = pl.spw; f.T = T; f.P = (int)p->P; f.pitch = (int)p->P + 2; f.lr = lr;
+  f.lrv = lrv;
   f.o_sigma = (int)p->o_sigma; f.A = p->A;
   return f;
 }
@@ -1423,7 +1481,7 @@ static FoldArgs fold_base(const mi_policy* p, const StepsPlan& pl, int T, float 
 // launches: theta_1, loss_t / kl_t and, with want_grad, lam = grad S_t(theta_1).
 static int fused_surrogate(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& r, const float* q_states, const float* q_actions,
                            const float* q_adv, const int32_t* q_count, const float* old_loc, const float* old_scale, int T, int B,
-                           float inner_lr, bool want_grad) {
+                           float inner_lr, const float* lrv, bool want_grad) {
   const size_t P = p->P;
   float* th1 = pl.theta + (size_t)T * P;
   // The pass lands where the per-layer loop keeps it (activations, dmu, d2, coef of StepSet 0), so a per-layer product or the
@@ -1434,8 +1492,8 @@ static int fused_surrogate(mi_policy* p, hipStream_t st, StepsPlan& pl, const Su
   sp.x = r.xs; sp.act = r.as; sp.adv = r.adv; sp.count = r.cn; sp.theta = pl.theta; sp.tstride = 0; sp.surrogate = 0;
   sp.h1_out = s.a.h1; sp.h2_out = s.a.h2; sp.mu_out = s.a.mu; sp.dmu_out = s.dmu; sp.d2_out = s.d2; sp.coef_out = s.coef;
   PCHK(p, launch_policy_sweep(st, sp, pl.sweep_grid, SW_PRIMAL));
-  FoldArgs f = fold_base(p, pl, T, inner_lr);
-  f.mode = 0; f.v = pl.theta; f.out = th1;                        // theta_1 = theta - lr g_t
+  FoldArgs f = fold_base(p, pl, T, inner_lr, lrv);
+  f.mode = 0; f.v = pl.theta; f.out = th1;                        // theta_1 = theta - lr g_t   (vector: - d (.) g_t)
   PCHK(p, launch_policy_sweep_fold(st, f, T));
   SweepArgs sq = sweep_base(p, pl, T, B);
   sq.x = q_states; sq.act = q_actions; sq.adv = q_adv; sq.count = q_count; sq.theta = th1; sq.tstride = P; sq.surrogate = 1;
@@ -1443,17 +1501,20 @@ static int fused_surrogate(mi_policy* p, hipStream_t st, StepsPlan& pl, const Su
   sq.h1_out = pl.q.a.h1; sq.h2_out = pl.q.a.h2; sq.mu_out = pl.q.a.mu;
   PCHK(p, launch_policy_sweep(st, sq, pl.sweep_grid, SW_PRIMAL));
   f.mode = 3; f.out = want_grad ? pl.lam : nullptr; f.loss_t = pl.loss_t; f.kl_t = pl.kl_t;      // per-task loss / KL
+  f.dout = want_grad && lrv ? pl.g : nullptr;                     // d (.) lam: the direction of the gradient's HVP sweep
   PCHK(p, launch_policy_sweep_fold(st, f, T));
   return MI_OK;
 }
 
 // Fvp(v) as three sweeps + three folds:  A: u_t = v - lr H_t v,  B: w_t = F_t u_t,  C: out = mean_t (w_t - lr H_t w_t) + damping v
+// With a step row d (lrv):  A: u_t = v - d (.) H_t v,  B: w_t = F_t u_t and d (.) w_t (same fold, into pl.g),  C: sweep along d (.) w_t,
+// out = mean_t (w_t - H_t (d (.) w_t)) + damping v -- the same six launches.
 static int fused_fvp(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& r, const float* q_states, const int32_t* q_count, int T,
-                     int B, float inner_lr, float damping, const float* v, float* out) {
+                     int B, float inner_lr, const float* lrv, float damping, const float* v, float* out) {
   const int P = (int)p->P;
   float *th1 = pl.theta + (size_t)T * P, *u = pl.vmask, *w = pl.lam, *tmp = pl.hv;
   SweepArgs hs = sweep_hvp_args(p, pl, T, B, r);
-  FoldArgs f = fold_base(p, pl, T, inner_lr);
+  FoldArgs f = fold_base(p, pl, T, inner_lr, lrv);
   f.v = v; f.damping = damping;
   hs.dir = v; hs.dstride = 0;
   PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
@@ -1462,9 +1523,9 @@ static int fused_fvp(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& 
   SweepArgs fs = sweep_base(p, pl, T, B);              // over the query pass at theta_1
   fs.x = q_states; fs.h1 = pl.q.a.h1; fs.h2 = pl.q.a.h2; fs.count = q_count; fs.theta = th1; fs.tstride = P; fs.dir = u; fs.dstride = P;
   PCHK(p, launch_policy_sweep(st, fs, pl.sweep_grid, SW_FISHER));
-  f.mode = 1; f.out = w; f.thetap = th1; f.u = u;
+  f.mode = 1; f.out = w; f.thetap = th1; f.u = u; f.dout = lrv ? pl.g : nullptr;
   PCHK(p, launch_policy_sweep_fold(st, f, T));
-  hs.dir = w; hs.dstride = P;
+  hs.dir = lrv ? pl.g : w; hs.dstride = P;
   PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
   f.mode = 2; f.out = tmp; f.w = w;
   if (!p->fold_counters) {               // (once per policy object: the fold leaves the counters zero again)
@@ -1491,20 +1552,22 @@ static int fused_fvp(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& 
 
 // meta_surrogate_loss (rl.py:441-473) at theta for `tasks` tasks with `steps` second-order inner updates on the support replays
 // ([steps][tasks][batch][.]), and optionally its gradient (rl.py:413-416).  Leaves everything the products need in `workspace`.
-extern "C" int mi_trpo_surrogate_steps(mi_policy* p, void* stream, const float* theta, int steps, const float* s_states,
-                                       const float* s_actions, const float* s_adv, const int32_t* s_count, const float* q_states,
-                                       const float* q_actions, const float* q_adv, const int32_t* q_count, const float* old_loc,
-                                       const float* old_scale, int tasks, int batch, float inner_lr, float* loss_out,
-                                       float* kl_out, float* grad_out, void* workspace, size_t workspace_bytes) {
+// lrc: the step-size-vector entries (mi_trpo_*_steps_lr), whose texts name the entry; NULL: the scalar entries, launches and texts as they were.
+static int trpo_surrogate_impl(mi_policy* p, void* stream, const float* theta, int steps, const float* s_states,
+                               const float* s_actions, const float* s_adv, const int32_t* s_count, const float* q_states,
+                               const float* q_actions, const float* q_adv, const int32_t* q_count, const float* old_loc,
+                               const float* old_scale, int tasks, int batch, float inner_lr, const LrCall* lrc, float* loss_out,
+                               float* kl_out, float* grad_out, void* workspace, size_t workspace_bytes) {
+  const std::string fn = lrc ? std::string(lrc->fn) + ": " : std::string();
   if (!p || !theta || !s_states || !s_actions || !s_adv || !q_states || !q_actions || !q_adv || !old_loc || !old_scale || !loss_out ||
       !kl_out || !workspace || steps < 1)
-    return pfail(p, MI_ERR_ARG, "null argument");
+    return pfail(p, MI_ERR_ARG, fn + "null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch, K = steps;
   const size_t P = p->P, TP = (size_t)T * P;
   StepsPlan pl;
   steps_plan(p, workspace, T, B, K, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(pl.bytes));
+  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(pl.bytes));
   const SupStack sup{s_states, s_actions, s_adv, s_count};
   const bool fused = fused_steps(p, K);
   float* thK = pl.theta + (size_t)K * TP;
@@ -1514,7 +1577,7 @@ extern "C" int mi_trpo_surrogate_steps(mi_policy* p, void* stream, const float* 
   PCHK(p, hipGetLastError());
   if (fused) {
     rc = fused_surrogate(p, st, pl, sup_at(p, sup, T, B, 0), q_states, q_actions, q_adv, q_count, old_loc, old_scale, T, B, inner_lr,
-                         grad_out != nullptr);
+                         lrc ? trpo_lr_row(lrc, 0, P) : nullptr, grad_out != nullptr);
     if (rc) return rc;
   } else {
     for (int k = 0; k < K; ++k) {                                 // trpo_update on support replay k (a2c loss, normalised advantages)
@@ -1524,7 +1587,11 @@ extern "C" int mi_trpo_surrogate_steps(mi_policy* p, void* stream, const float* 
       rc = meta_primal(p, st, T, B, 0.f, pl.st[k], th, ts, r.xs, r.as, r.adv, r.cn, MI_PLOSS_A2C, nullptr, 0, pl.g,
                        pl.hv /* step loss: unused */, nullptr);
       if (rc) return rc;
-      hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, th, ts, pl.g, inner_lr, (int)P, th + TP);
+      if (lrc)
+        hipLaunchKernelGGL(lr_advance_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, (const float*)th, ts, (const float*)pl.g,
+                           trpo_lr_row(lrc, k, P), (int)P, 0, 0, th + TP);
+      else
+        hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, th, ts, pl.g, inner_lr, (int)P, th + TP);
       PCHK(p, hipGetLastError());
     }
     rc = mlp_forward(p, st, T, B, q_states, thK, P, pl.q.a);
@@ -1543,16 +1610,16 @@ extern "C" int mi_trpo_surrogate_steps(mi_policy* p, void* stream, const float* 
   const float* gt = pl.lam;                                       // J_t^T grad S_t(theta_K)
   if (fused) {                                                    // one HVP sweep along lam_t + fold, instead of ~10 per-layer launches
     SweepArgs hs = sweep_hvp_args(p, pl, T, B, sup_at(p, sup, T, B, 0));
-    hs.dir = pl.lam; hs.dstride = P;
+    hs.dir = lrc ? pl.g : pl.lam; hs.dstride = P;                 // (vector: d (.) lam, written by the fold that finished lam)
     PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
-    FoldArgs f = fold_base(p, pl, T, inner_lr);
+    FoldArgs f = fold_base(p, pl, T, inner_lr, lrc ? trpo_lr_row(lrc, 0, P) : nullptr);
     f.mode = 2; f.out = pl.hv; f.w = pl.lam;
     PCHK(p, launch_policy_sweep_fold(st, f, T));
     gt = pl.hv;
   } else {
     rc = mlp_backward(p, st, T, B, q_states, thK, P, pl.q.a, pl.q.dmu, pl.q.d2, pl.q.d1, pl.lam);
     if (rc) return rc;
-    rc = jac_apply(p, st, pl, sup, T, B, K, true, inner_lr, pl.lam);
+    rc = jac_apply(p, st, pl, sup, T, B, K, true, inner_lr, lrc, pl.lam);
     if (rc) return rc;
   }
   hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gt, T, (int)P, 1.f / (float)T,
@@ -1560,25 +1627,79 @@ extern "C" int mi_trpo_surrogate_steps(mi_policy* p, void* stream, const float* 
   PCHK(p, hipGetLastError());
   return MI_OK;
 }
+extern "C" int mi_trpo_surrogate_steps(mi_policy* p, void* stream, const float* theta, int steps, const float* s_states,
+                                       const float* s_actions, const float* s_adv, const int32_t* s_count, const float* q_states,
+                                       const float* q_actions, const float* q_adv, const int32_t* q_count, const float* old_loc,
+                                       const float* old_scale, int tasks, int batch, float inner_lr, float* loss_out,
+                                       float* kl_out, float* grad_out, void* workspace, size_t workspace_bytes) {
+  return trpo_surrogate_impl(p, stream, theta, steps, s_states, s_actions, s_adv, s_count, q_states, q_actions, q_adv, q_count, old_loc,
+                             old_scale, tasks, batch, inner_lr, nullptr, loss_out, kl_out, grad_out, workspace, workspace_bytes);
+}
+// The checks the step-size-vector entries make of their own arguments, before any HIP call (fn: the entry's name)
+static int trpo_lr_args(mi_policy* p, const char* name, const float* lr_vec, int lr_rows, const int32_t* step_lr_row, int steps, int tasks,
+                        int batch) {
+  const std::string fn = std::string(name) + ": ";
+  if (!p) return pfail(nullptr, MI_ERR_ARG, fn + "null policy handle");
+  if (!lr_vec) return pfail(p, MI_ERR_ARG, fn + "lr_vec is NULL");
+  if (lr_rows < 1 || lr_rows > MI_POLICY_LR_MAX_ROWS)
+    return pfail(p, MI_ERR_ARG, fn + "lr_rows " + std::to_string(lr_rows) + " (must be 1.." + std::to_string(MI_POLICY_LR_MAX_ROWS) + ")");
+  if (steps < 1) return pfail(p, MI_ERR_ARG, fn + "steps " + std::to_string(steps) + " (must be >= 1)");
+  if (tasks < 1) return pfail(p, MI_ERR_ARG, fn + "tasks " + std::to_string(tasks) + " (must be >= 1)");
+  if (batch < 1) return pfail(p, MI_ERR_ARG, fn + "batch " + std::to_string(batch) + " (must be >= 1)");
+  for (int k = 0; step_lr_row && k < steps; ++k)
+    if (step_lr_row[k] < 0 || step_lr_row[k] >= lr_rows)
+      return pfail(p, MI_ERR_ARG, fn + "step_lr_row[" + std::to_string(k) + "] " + std::to_string(step_lr_row[k]) + " (must be 0.." +
+                                      std::to_string(lr_rows - 1) + ")");
+  return MI_OK;
+}
+extern "C" int mi_policy_adapt_lr(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
+                                  const float* actions, const float* adv, const int32_t* count, int tasks, int batch, const float* lr_vec,
+                                  int head_only, float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
+  int rc = trpo_lr_args(p, "mi_policy_adapt_lr", lr_vec, 1, nullptr, 1, tasks, batch);
+  if (rc) return rc;
+  return policy_adapt_impl(p, "mi_policy_adapt_lr: ", stream, theta, tstride, states, actions, adv, count, tasks, batch, 0.f, lr_vec, head_only,
+                           theta_out, loss_out, workspace, workspace_bytes);
+}
+// The fused sweeps and the per-layer recursions take their extra direction d (.) x in the plan's g slot, idle once the inner updates are
+// done: the MAML-TRPO plan does not grow.
+extern "C" int mi_trpo_steps_lr_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, int lr_rows, size_t* bytes) {
+  if (lr_rows < 1 || lr_rows > MI_POLICY_LR_MAX_ROWS) return MI_ERR_ARG;
+  return mi_trpo_steps_workspace_bytes(p, tasks, batch, steps, bytes);
+}
+extern "C" int mi_trpo_surrogate_steps_lr(mi_policy* p, void* stream, const float* theta, int steps, const float* s_states,
+                                          const float* s_actions, const float* s_adv, const int32_t* s_count, const float* q_states,
+                                          const float* q_actions, const float* q_adv, const int32_t* q_count, const float* old_loc,
+                                          const float* old_scale, int tasks, int batch, const float* lr_vec, int lr_rows,
+                                          const int32_t* step_lr_row, float* loss_out, float* kl_out, float* grad_out, void* workspace,
+                                          size_t workspace_bytes) {
+  int rc = trpo_lr_args(p, "mi_trpo_surrogate_steps_lr", lr_vec, lr_rows, step_lr_row, steps, tasks, batch);
+  if (rc) return rc;
+  const LrCall lrc{lr_vec, lr_rows, step_lr_row, nullptr, "mi_trpo_surrogate_steps_lr"};
+  return trpo_surrogate_impl(p, stream, theta, steps, s_states, s_actions, s_adv, s_count, q_states, q_actions, q_adv, q_count, old_loc,
+                             old_scale, tasks, batch, 0.f, &lrc, loss_out, kl_out, grad_out, workspace, workspace_bytes);
+}
 
 // Fvp(v) = mean_t J_t^T F_t J_t v + damping v (cherry trpo.hessian_vector_product of the mean KL at the point where the adapted
 // policy equals the old policy, rl.py:417), at the theta of the preceding mi_trpo_surrogate_steps on this workspace and replays.
-extern "C" int mi_trpo_fvp_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
-                                 const int32_t* s_count, const float* q_states, const int32_t* q_count, int tasks, int batch,
-                                 float inner_lr, float damping, const float* v, float* out, void* workspace, size_t workspace_bytes) {
-  if (!p || !s_states || !s_actions || !q_states || !v || !out || !workspace || steps < 1) return pfail(p, MI_ERR_ARG, "null argument");
+static int trpo_fvp_impl(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                         const int32_t* s_count, const float* q_states, const int32_t* q_count, int tasks, int batch,
+                         float inner_lr, const LrCall* lrc, float damping, const float* v, float* out, void* workspace,
+                         size_t workspace_bytes) {
+  const std::string fn = lrc ? std::string(lrc->fn) + ": " : std::string();
+  if (!p || !s_states || !s_actions || !q_states || !v || !out || !workspace || steps < 1) return pfail(p, MI_ERR_ARG, fn + "null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch, K = steps;
   const size_t P = p->P, TP = (size_t)T * P;
   StepsPlan pl;
   steps_plan(p, workspace, T, B, K, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small");
+  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small");
   const SupStack sup{s_states, s_actions, nullptr, s_count};
-  if (fused_steps(p, K)) return fused_fvp(p, st, pl, sup_at(p, sup, T, B, 0), q_states, q_count, T, B, inner_lr, damping, v, out);
+  if (fused_steps(p, K))
+    return fused_fvp(p, st, pl, sup_at(p, sup, T, B, 0), q_states, q_count, T, B, inner_lr, lrc ? trpo_lr_row(lrc, 0, P) : nullptr, damping, v, out);
   // u = J v   (pl.vmask holds u)
   hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (size_t)0, pl.g, 0.f, (int)P, pl.vmask);
   PCHK(p, hipGetLastError());
-  int rc = jac_apply(p, st, pl, sup, T, B, K, false, inner_lr, pl.vmask);
+  int rc = jac_apply(p, st, pl, sup, T, B, K, false, inner_lr, lrc, pl.vmask);
   if (rc) return rc;
   // w = F u at the query (Gaussian Fisher at new == old)
   float* thK = pl.theta + (size_t)K * TP;
@@ -1592,11 +1713,27 @@ extern "C" int mi_trpo_fvp_steps(mi_policy* p, void* stream, int steps, const fl
   rc = mlp_backward(p, st, T, B, q_states, thK, P, pl.q.a, pl.rdmu, pl.r2, pl.r1, pl.lam);
   if (rc) return rc;
   // out = mean_t J^T w + damping v
-  rc = jac_apply(p, st, pl, sup, T, B, K, true, inner_lr, pl.lam);
+  rc = jac_apply(p, st, pl, sup, T, B, K, true, inner_lr, lrc, pl.lam);
   if (rc) return rc;
   hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.lam, T, (int)P, 1.f / (float)T, v, damping, out);
   PCHK(p, hipGetLastError());
   return MI_OK;
+}
+extern "C" int mi_trpo_fvp_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                 const int32_t* s_count, const float* q_states, const int32_t* q_count, int tasks, int batch,
+                                 float inner_lr, float damping, const float* v, float* out, void* workspace, size_t workspace_bytes) {
+  return trpo_fvp_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, tasks, batch, inner_lr, nullptr, damping, v, out,
+                       workspace, workspace_bytes);
+}
+extern "C" int mi_trpo_fvp_steps_lr(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                    const int32_t* s_count, const float* q_states, const int32_t* q_count, int tasks, int batch,
+                                    const float* lr_vec, int lr_rows, const int32_t* step_lr_row, float damping, const float* v, float* out,
+                                    void* workspace, size_t workspace_bytes) {
+  int rc = trpo_lr_args(p, "mi_trpo_fvp_steps_lr", lr_vec, lr_rows, step_lr_row, steps, tasks, batch);
+  if (rc) return rc;
+  const LrCall lrc{lr_vec, lr_rows, step_lr_row, nullptr, "mi_trpo_fvp_steps_lr"};
+  return trpo_fvp_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, tasks, batch, 0.f, &lrc, damping, v, out, workspace,
+                       workspace_bytes);
 }
 
 // =====================================================================================================================
@@ -1889,6 +2026,22 @@ __global__ void step_back_kernel(const float* a, const float* __restrict__ h, co
   if (i < n) out[i] = a[i] - alpha * (h[i] + s3[i]);
 }
 
+// The step-size-vector form keeps ONE more array behind the scalar plan, whose offsets do not move: dlam [K][T][P], row k = d_k (.) lam_{k+1},
+// the direction of the context's sweep of update k and the second argument of T_k in every product.
+static float* gen_lr_plan(const mi_policy* p, void* ws, const GenStepsPlan& gp, int T, int K, size_t& bytes) {
+  PBump b{reinterpret_cast<char*>(ws), gp.bytes};
+  float* dlam = b.f((size_t)T * p->P * K);
+  bytes = align_up(b.off, 256);
+  return dlam;
+}
+extern "C" int mi_trpo_general_steps_lr_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, int lr_rows, size_t* bytes) {
+  if (!p || !bytes || tasks < 1 || batch < 1 || steps < 1 || lr_rows < 1 || lr_rows > MI_POLICY_LR_MAX_ROWS) return MI_ERR_ARG;
+  StepsPlan pl; GenStepsPlan gp;
+  gen_steps_plan(p, nullptr, tasks, batch, steps, pl, gp);
+  (void)gen_lr_plan(p, nullptr, gp, tasks, steps, *bytes);
+  return MI_OK;
+}
+
 static int steps_args(mi_policy* p, const char* fn, int steps, int tasks, int batch) {
   if (steps < 1 || tasks < 1 || batch < 1)
     return pfail(p, MI_ERR_ARG, std::string(fn) + ": steps, tasks and batch must be >= 1");
@@ -1899,19 +2052,24 @@ static int steps_args(mi_policy* p, const char* fn, int steps, int tasks, int ba
 // theta_K (into buffers of its own: the surrogate's query cotangents stay), lam_k for every k, and the tangent sweep of every
 // update along lam_{k+1}.  kl_grad_out (optional, [P]) = d mean_t KL_t / d theta = mean_t lam_0; without it lam_0 is not formed
 // (the products read lam_{k+1} only): update 0 gets its tangent sweep and no weight-gradient products.
-extern "C" int mi_trpo_kl_prepare_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
-                                        const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
-                                        const float* old_scale, int tasks, int batch, float inner_lr, float* kl_grad_out,
-                                        void* workspace, size_t workspace_bytes) {
-  if (!p || !s_states || !s_actions || !q_states || !old_loc || !old_scale || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
-  int rc = steps_args(p, "mi_trpo_kl_prepare_steps", steps, tasks, batch);
+// Vector form (lrc):  lam_k = lam_{k+1} - H_k (d_k (.) lam_{k+1}).  The sweep of update k runs along dlam_k = d_k (.) lam_{k+1}, which the launch
+// that finished lam_{k+1} wrote (lr_adjoint_kernel), and stays for the products like the scalar one.
+static int trpo_kl_prepare_impl(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
+                                const float* old_scale, int tasks, int batch, float inner_lr, const LrCall* lrc, float* kl_grad_out,
+                                void* workspace, size_t workspace_bytes) {
+  const std::string fn = lrc ? std::string(lrc->fn) + ": " : std::string();
+  if (!p || !s_states || !s_actions || !q_states || !old_loc || !old_scale || !workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
+  int rc = steps_args(p, lrc ? lrc->fn : "mi_trpo_kl_prepare_steps", steps, tasks, batch);
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch, K = steps;
   const size_t P = p->P, TP = (size_t)T * P;
   StepsPlan pl; GenStepsPlan gp;
   gen_steps_plan(p, workspace, T, B, K, pl, gp);
-  if (gp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(gp.bytes));
+  size_t need = gp.bytes;
+  float* dlam = lrc ? gen_lr_plan(p, workspace, gp, T, K, need) : nullptr;
+  if (need > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(need));
   const SupStack sup{s_states, s_actions, nullptr, s_count};
   const float* thK = pl.theta + (size_t)K * TP;
   float* lamK = gp.lam + (size_t)K * TP;
@@ -1923,15 +2081,27 @@ extern "C" int mi_trpo_kl_prepare_steps(mi_policy* p, void* stream, int steps, c
   PCHK(p, hipGetLastError());
   rc = mlp_backward(p, st, T, B, q_states, thK, P, pl.q.a, gp.k_dmu, gp.k_d2, gp.k_d1, lamK, gp.k_pre2, gp.k_pre1);
   if (rc) return rc;
+  const dim3 pgrid(ceil_div((int)P, 256), T);
+  const float* none = nullptr;
+  if (lrc) {
+    hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)lamK, none, none, trpo_lr_row(lrc, K - 1, P), none, (int)P, 0, 0,
+                       lamK, dlam + (size_t)(K - 1) * TP, (float*)nullptr);
+    PCHK(p, hipGetLastError());
+  }
   for (int k = K - 1; k >= 0; --k) {
     const float* lam1 = gp.lam + (size_t)(k + 1) * TP;
+    const float* dir = lrc ? dlam + (size_t)k * TP : lam1;
     const SupRef r = sup_at(p, sup, T, B, k);
     if (k == 0 && !kl_grad_out)      // (pl.hv takes the sweep's R{d L / d sigma}: scratch)
-      return tan_sweep(p, st, pass_of(pl.st[0]), T, B, pl.theta, theta_stride(p, 0), r.xs, r.as, r.cn, lam1, P, gp.sc[0], pl.hv);
-    rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), r.xs, r.as, r.cn, lam1, P, gp.sc[k], pl.hv);
+      return tan_sweep(p, st, pass_of(pl.st[0]), T, B, pl.theta, theta_stride(p, 0), r.xs, r.as, r.cn, dir, P, gp.sc[0], pl.hv);
+    rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), r.xs, r.as, r.cn, dir, P, gp.sc[k], pl.hv);
     if (rc) return rc;
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, lam1, P, pl.hv, inner_lr, (int)P,
-                       gp.lam + (size_t)k * TP);
+    if (lrc)
+      hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, lam1, (const float*)pl.hv, none, k > 0 ? trpo_lr_row(lrc, k - 1, P) : none,
+                         none, (int)P, 0, 0, gp.lam + (size_t)k * TP, k > 0 ? dlam + (size_t)(k - 1) * TP : (float*)nullptr, (float*)nullptr);
+    else
+      hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, lam1, P, pl.hv, inner_lr, (int)P,
+                         gp.lam + (size_t)k * TP);
     PCHK(p, hipGetLastError());
   }
   hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gp.lam, T, (int)P, 1.f / (float)T,
@@ -1939,24 +2109,48 @@ extern "C" int mi_trpo_kl_prepare_steps(mi_policy* p, void* stream, int steps, c
   PCHK(p, hipGetLastError());
   return MI_OK;
 }
+extern "C" int mi_trpo_kl_prepare_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                        const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
+                                        const float* old_scale, int tasks, int batch, float inner_lr, float* kl_grad_out,
+                                        void* workspace, size_t workspace_bytes) {
+  return trpo_kl_prepare_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, old_loc, old_scale, tasks, batch, inner_lr,
+                              nullptr, kl_grad_out, workspace, workspace_bytes);
+}
+extern "C" int mi_trpo_kl_prepare_steps_lr(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                           const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
+                                           const float* old_scale, int tasks, int batch, const float* lr_vec, int lr_rows,
+                                           const int32_t* step_lr_row, float* kl_grad_out, void* workspace, size_t workspace_bytes) {
+  int rc = trpo_lr_args(p, "mi_trpo_kl_prepare_steps_lr", lr_vec, lr_rows, step_lr_row, steps, tasks, batch);
+  if (rc) return rc;
+  const LrCall lrc{lr_vec, lr_rows, step_lr_row, nullptr, "mi_trpo_kl_prepare_steps_lr"};
+  return trpo_kl_prepare_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, old_loc, old_scale, tasks, batch, 0.f, &lrc,
+                              kl_grad_out, workspace, workspace_bytes);
+}
 
 // trpo.hessian_vector_product(mean KL, params, damping)(v) (rl.py:417) at the parameters of the preceding
 // mi_trpo_surrogate_steps + mi_trpo_kl_prepare_steps on this workspace; any number of calls.  11 + 36 K kernels and 1 + 3 K
 // memsets, whatever the number of tasks.
-extern "C" int mi_trpo_fvp_general_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
-                                         const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
-                                         int tasks, int batch, float inner_lr, float damping, const float* v, float* out,
-                                         void* workspace, size_t workspace_bytes) {
-  if (!p || !s_states || !s_actions || !q_states || !old_scale || !v || !out || !workspace) return pfail(p, MI_ERR_ARG, "null argument");
-  int rc = steps_args(p, "mi_trpo_fvp_general_steps", steps, tasks, batch);
+// Vector form (lrc):  u_{k+1} = u_k - d_k (.) (H_k u_k);   rho_k = rho_{k+1} - (H_k (d_k (.) rho_{k+1}) + T_k[u_k, d_k (.) lam_{k+1}]):  the stored
+// sweeps run along u_k and along dlam_k, the sweep of its own along d_k (.) rho_{k+1} (in pl.g, written by the launch that finished rho_{k+1}).
+static int trpo_fvp_general_impl(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                 const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
+                                 int tasks, int batch, float inner_lr, const LrCall* lrc, float damping, const float* v, float* out,
+                                 void* workspace, size_t workspace_bytes) {
+  const std::string fn = lrc ? std::string(lrc->fn) + ": " : std::string();
+  if (!p || !s_states || !s_actions || !q_states || !old_scale || !v || !out || !workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
+  int rc = steps_args(p, lrc ? lrc->fn : "mi_trpo_fvp_general_steps", steps, tasks, batch);
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = tasks, B = batch, K = steps;
   const size_t P = p->P, TP = (size_t)T * P;
   StepsPlan pl; GenStepsPlan gp;
   gen_steps_plan(p, workspace, T, B, K, pl, gp);
-  if (gp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(gp.bytes));
+  size_t need = gp.bytes;
+  const float* dlam = lrc ? gen_lr_plan(p, workspace, gp, T, K, need) : nullptr;
+  if (need > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(need));
   const SupStack sup{s_states, s_actions, nullptr, s_count};
+  const dim3 pgrid(ceil_div((int)P, 256), T);
+  const float* none = nullptr;
   // ---- u_0 = v for every task, u_{k+1} = u_k - lr H_k u_k; the sweep along u_k stays for the way back
   hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (size_t)0, pl.g, 0.f, (int)P, gp.u);
   PCHK(p, hipGetLastError());
@@ -1965,8 +2159,12 @@ extern "C" int mi_trpo_fvp_general_steps(mi_policy* p, void* stream, int steps, 
     const float* uk = gp.u + (size_t)k * TP;
     rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), r.xs, r.as, r.cn, uk, P, gp.sv[k], pl.hv);
     if (rc) return rc;
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, uk, P, pl.hv, inner_lr, (int)P,
-                       gp.u + (size_t)(k + 1) * TP);
+    if (lrc)
+      hipLaunchKernelGGL(lr_advance_kernel, pgrid, dim3(256), 0, st, uk, P, (const float*)pl.hv, trpo_lr_row(lrc, k, P), (int)P, 0, 0,
+                         gp.u + (size_t)(k + 1) * TP);
+    else
+      hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, uk, P, pl.hv, inner_lr, (int)P,
+                         gp.u + (size_t)(k + 1) * TP);
     PCHK(p, hipGetLastError());
   }
   // ---- rho_K = Hess KL_t(theta_K) u_K: tangent forward on the query pass, exact output Hessian, tangent backward
@@ -1985,20 +2183,46 @@ extern "C" int mi_trpo_fvp_general_steps(mi_policy* p, void* stream, int steps, 
                             pl.r2, pl.r1, gp.rho);
   if (rc) return rc;
   // ---- rho_k = rho_{k+1} - lr (H_k rho_{k+1} + T_k[u_k, lam_{k+1}])
+  if (lrc) {
+    hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)gp.rho, none, none, trpo_lr_row(lrc, K - 1, P), none, (int)P, 0, 0,
+                       gp.rho, pl.g, (float*)nullptr);
+    PCHK(p, hipGetLastError());
+  }
   for (int k = K - 1; k >= 0; --k) {
     const SupRef r = sup_at(p, sup, T, B, k);
     const float* th = pl.theta + (size_t)k * TP;
     const size_t ts = theta_stride(p, k);
-    rc = hvp_step(p, st, pl, pl.st[k], T, B, th, ts, r, gp.rho, pl.hv);
+    rc = hvp_step(p, st, pl, pl.st[k], T, B, th, ts, r, lrc ? pl.g : gp.rho, pl.hv);
     if (rc) return rc;
     PCHK(p, hipMemsetAsync(gp.s3, 0, TP * sizeof(float), st));
-    rc = mixed_sweep(p, st, pass_of(pl.st[k]), T, B, th, ts, r.xs, r.as, r.cn, gp.lam + (size_t)(k + 1) * TP, P, gp.u + (size_t)k * TP, P,
-                     gp.sc[k], gp.sv[k], gp.mx, gp.s3);
+    rc = mixed_sweep(p, st, pass_of(pl.st[k]), T, B, th, ts, r.xs, r.as, r.cn, lrc ? dlam + (size_t)k * TP : gp.lam + (size_t)(k + 1) * TP, P,
+                     gp.u + (size_t)k * TP, P, gp.sc[k], gp.sv[k], gp.mx, gp.s3);
     if (rc) return rc;
-    hipLaunchKernelGGL(step_back_kernel, dim3((unsigned)((TP + 255) / 256)), dim3(256), 0, st, gp.rho, pl.hv, gp.s3, inner_lr, TP, gp.rho);
+    if (lrc)
+      hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)gp.rho, (const float*)pl.hv, (const float*)gp.s3,
+                         k > 0 ? trpo_lr_row(lrc, k - 1, P) : none, none, (int)P, 0, 0, gp.rho, pl.g, (float*)nullptr);
+    else
+      hipLaunchKernelGGL(step_back_kernel, dim3((unsigned)((TP + 255) / 256)), dim3(256), 0, st, gp.rho, pl.hv, gp.s3, inner_lr, TP, gp.rho);
     PCHK(p, hipGetLastError());
   }
   hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gp.rho, T, (int)P, 1.f / (float)T, v, damping, out);
   PCHK(p, hipGetLastError());
   return MI_OK;
+}
+extern "C" int mi_trpo_fvp_general_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                         const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
+                                         int tasks, int batch, float inner_lr, float damping, const float* v, float* out,
+                                         void* workspace, size_t workspace_bytes) {
+  return trpo_fvp_general_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, old_scale, tasks, batch, inner_lr, nullptr,
+                               damping, v, out, workspace, workspace_bytes);
+}
+extern "C" int mi_trpo_fvp_general_steps_lr(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                            const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
+                                            int tasks, int batch, const float* lr_vec, int lr_rows, const int32_t* step_lr_row, float damping,
+                                            const float* v, float* out, void* workspace, size_t workspace_bytes) {
+  int rc = trpo_lr_args(p, "mi_trpo_fvp_general_steps_lr", lr_vec, lr_rows, step_lr_row, steps, tasks, batch);
+  if (rc) return rc;
+  const LrCall lrc{lr_vec, lr_rows, step_lr_row, nullptr, "mi_trpo_fvp_general_steps_lr"};
+  return trpo_fvp_general_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, old_scale, tasks, batch, 0.f, &lrc, damping,
+                               v, out, workspace, workspace_bytes);
 }

@@ -58,6 +58,10 @@ struct SweepArgs {
 //   mode 2 (after C): out[t][p] = w[t][p] - lr sum    (then the mean over tasks + damping v: by the last workgroup of a parameter block
 //                     when FoldArgs::counter is set, by the caller's mean_tasks launch otherwise)
 //   mode 3 (primal)  : out[t][p] = sum (the pass's gradient); loss_t[t], kl_t[t] = the two extra slots
+// Per-parameter step sizes (FoldArgs::lrv, one row [P] of the step-size table d; NULL = the number lr): the tangent side stays an
+// elementwise product, u = v - d (.) sum (mode 0), but the adjoint side is w - H (d (.) w): the fold that finishes w (mode 1) or lam
+// (mode 3) also writes dout[t][p] = d[p] out[t][p] in the same launch, the following HVP sweep runs along dout, and the closing fold
+// (mode 2) is w - sum.  An entry whose step is exactly 0 passes through bitwise (mode 0) and gives an exact 0 in dout.
 struct FoldArgs {
   const float* partial; int slots, spt, spw, T, P, pitch;
   float *loss_t, *kl_t;    // mode 3: per-task loss / KL sums of a primal sweep
@@ -66,6 +70,8 @@ struct FoldArgs {
   const float* thetap;     // [T][P]   (mode 1: rho of theta')
   const float* u;          // [T][P]   (mode 1: direction)
   float lr, damping;
+  const float* lrv;        // [P] the update's row of the step-size table (NULL: the number lr)
+  float* dout;             // [T][P]  (modes 1 and 3 with lrv: d (.) out, the direction of the next HVP sweep; NULL: not wanted)
   int o_sigma, A;
   float* out;
   int mode;

@@ -712,7 +712,8 @@ __global__ __launch_bounds__(256) void policy_sweep_fold_mean_kernel(FoldArgs f)
   const bool act = p < f.P;
   if (act) {
     const float s = sweep_fold_sum(f, t, p);
-    __hip_atomic_store(f.out + (size_t)t * f.P + p, f.w[(size_t)t * f.P + p] - f.lr * s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const float wv = f.w[(size_t)t * f.P + p];           // (step-size vector: the sweep ran along d (.) w, nothing is left to scale)
+    __hip_atomic_store(f.out + (size_t)t * f.P + p, f.lrv ? wv - s : wv - f.lr * s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -749,17 +750,22 @@ __global__ __launch_bounds__(256) void policy_sweep_fold_kernel(FoldArgs f) {
   }
   const int t = blockIdx.y;
   const float s = sweep_fold_sum(f, t, p);
+  const float d = f.lrv ? f.lrv[p] : 0.f;
   if (f.mode == 0) {
-    f.out[(size_t)t * f.P + p] = f.v[p] - f.lr * s;
+    if (f.lrv) f.out[(size_t)t * f.P + p] = d == 0.f ? f.v[p] : f.v[p] - d * s;
+    else f.out[(size_t)t * f.P + p] = f.v[p] - f.lr * s;
   } else if (f.mode == 2) {
-    f.out[(size_t)t * f.P + p] = f.w[(size_t)t * f.P + p] - f.lr * s;
+    const float wv = f.w[(size_t)t * f.P + p];
+    f.out[(size_t)t * f.P + p] = f.lrv ? wv - s : wv - f.lr * s;
   } else if (f.mode == 3) {
     if (f.out) f.out[(size_t)t * f.P + p] = s;
+    if (f.lrv && f.dout) f.dout[(size_t)t * f.P + p] = d == 0.f ? 0.f : d * s;
   } else {
     float o = s;
     if (p >= f.o_sigma && p < f.o_sigma + f.A)
       o = f.thetap[(size_t)t * f.P + p] > LOG_EPS ? 2.f * f.u[(size_t)t * f.P + p] / (float)f.A : 0.f;
     f.out[(size_t)t * f.P + p] = o;
+    if (f.lrv && f.dout) f.dout[(size_t)t * f.P + p] = d == 0.f ? 0.f : d * o;
   }
 }
 

@@ -669,11 +669,15 @@ class PolicyEngine:
         if rc:
             raise _lib.MiError(f'libmi_maml policy error {rc}: {self.lib.mi_policy_last_error(self._h).decode()}')
 
-    def _workspace(self, T, B, K=1):
+    def _workspace(self, T, B, K=1, lr_rows=0):
         # the ANIL-TRPO plan of K updates starts with the MAML-TRPO one (which forward and adapt fit into): one buffer serves all,
-        # and a kl_prepare after surrogate finds the surrogate's per-update passes where it left them
+        # and a kl_prepare after surrogate finds the surrogate's per-update passes where it left them.  lr_rows: the step-size-vector
+        # calls, whose plan is the same one with one more array behind it
         b = C.c_size_t()
-        self._check(self.lib.mi_trpo_general_steps_workspace_bytes(self._h, T, B, K, C.byref(b)))
+        if lr_rows:
+            self._check(self.lib.mi_trpo_general_steps_lr_workspace_bytes(self._h, T, B, K, lr_rows, C.byref(b)))
+        else:
+            self._check(self.lib.mi_trpo_general_steps_workspace_bytes(self._h, T, B, K, C.byref(b)))
         if self._ws is None or self._ws.numel() < b.value:
             self._ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
         return self._ws
@@ -737,14 +741,46 @@ class PolicyEngine:
             _ptr(out['ep_len']), _ptr(out.get('noise')), _ptr(ws), ws.numel() if ws is not None else 0))
         return out
 
+    def _lr_table(self, lr, K, step_lr_row):
+        """The step of a TRPO call: None for a number (the scalar entries), else (lr_vec [rows, P] fp32 contiguous on the device, rows,
+        the int32 array of the K updates' rows or None = row 0 for all) for a [rows, P] / [P] tensor in the engine's parameter order."""
+        if not torch.is_tensor(lr):
+            if step_lr_row is not None:
+                raise ValueError('step_lr_row goes with a step-size tensor, not with a number')
+            return None
+        P = self.param_count
+        lr = lr.detach()
+        if lr.dim() == 1:
+            lr = lr.unsqueeze(0)
+        if lr.dim() != 2 or lr.shape[1] != P or lr.shape[0] < 1 or lr.dtype != torch.float32 or not lr.is_cuda:
+            raise ValueError(f'the step must be a number or an fp32 tensor on the GPU, [rows, P] or [P] with P={P}, got {tuple(lr.shape)} {lr.dtype}')
+        rows = lr.shape[0]
+        if step_lr_row is None:
+            if rows != 1:
+                raise ValueError(f'a step-size table of {rows} rows needs step_lr_row (the row each of the {K} updates reads)')
+            return lr.contiguous(), rows, None
+        if len(step_lr_row) != K:
+            raise ValueError(f'step_lr_row holds {len(step_lr_row)} rows for {K} updates')
+        return lr.contiguous(), rows, (C.c_int32 * max(K, 1))(*[int(x) for x in step_lr_row])
+
     @_on_device
     def adapt(self, theta, states, actions, adv, count, lr, head_only=False):
-        """trpo_update for T tasks: returns (theta_out [T, P], loss [T]).  head_only: ANIL inner loop (body under no_grad)."""
+        """trpo_update for T tasks: returns (theta_out [T, P], loss [T]).  head_only: ANIL inner loop (body under no_grad).  ``lr``: a
+        number, or a [P] fp32 tensor of per-parameter step sizes in the engine's order (mi_policy_adapt_lr; an entry whose step is 0
+        keeps the bits of theta)."""
         T, B = states.shape[0], states.shape[1]
         ws = self._workspace(T, B)
         out = torch.empty(T, self.param_count, device=self.device)
         loss = torch.empty(T, device=self.device)
         stride = 0 if theta.dim() == 1 else self.param_count
+        if torch.is_tensor(lr):
+            if lr.dim() != 1:
+                raise ValueError(f'lr must be a number or ONE row [P] of step sizes, got {tuple(lr.shape)}')
+            vec = self._lr_table(lr, 1, None)[0]
+            self._check(self.lib.mi_policy_adapt_lr(self._h, _stream(self.device), _ptr(theta.contiguous()), stride, _ptr(states), _ptr(actions),
+                                                    _ptr(adv), _ptr(count), T, B, _ptr(vec), int(head_only), _ptr(out), _ptr(loss), _ptr(ws),
+                                                    ws.numel()))
+            return out, loss
         self._check(self.lib.mi_policy_adapt(self._h, _stream(self.device), _ptr(theta.contiguous()), stride, _ptr(states), _ptr(actions),
                                              _ptr(adv), _ptr(count), T, B, float(lr), int(head_only), _ptr(out), _ptr(loss), _ptr(ws), ws.numel()))
         return out, loss
@@ -769,14 +805,23 @@ class PolicyEngine:
         return K, T, B
 
     @_on_device
-    def surrogate(self, theta, sup, qry, old_loc, old_scale, inner_lr, want_grad):
+    def surrogate(self, theta, sup, qry, old_loc, old_scale, inner_lr, want_grad, step_lr_row=None):
         """meta_surrogate_loss with K = sup['states'].shape[0] inner updates.  sup: dict with states [K,T,B,S], actions [K,T,B,A],
-        adv [K,T,B], count [K,T] int32 (the leading [K] axis also at K = 1); qry: the same without it.  -> (loss, kl, grad or None)."""
+        adv [K,T,B], count [K,T] int32 (the leading [K] axis also at K = 1); qry: the same without it.  -> (loss, kl, grad or None).
+        ``inner_lr``: a number, or (here and in ``fvp`` / ``kl_prepare`` / ``fvp_general``, which must be given the same) a [rows, P] / [P]
+        fp32 tensor of fixed per-parameter step sizes in the engine's order, update k reading row ``step_lr_row[k]`` (None: one row)."""
         K, T, B = self._trpo_shapes(sup, qry, theta=theta, old_loc=old_loc, old_scale=old_scale)
-        ws = self._workspace(T, B, K)
+        tab = self._lr_table(inner_lr, K, step_lr_row)
+        ws = self._workspace(T, B, K, tab[1] if tab else 0)
         loss = torch.empty(1, device=self.device)
         kl = torch.empty(1, device=self.device)
         grad = torch.empty(self.param_count, device=self.device) if want_grad else None
+        if tab:
+            self._check(self.lib.mi_trpo_surrogate_steps_lr(
+                self._h, _stream(self.device), _ptr(theta), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['adv']), _ptr(sup['count']),
+                _ptr(qry['states']), _ptr(qry['actions']), _ptr(qry['adv']), _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B,
+                _ptr(tab[0]), tab[1], tab[2], _ptr(loss), _ptr(kl), _ptr(grad), _ptr(ws), ws.numel()))
+            return loss, kl, grad
         self._check(self.lib.mi_trpo_surrogate_steps(
             self._h, _stream(self.device), _ptr(theta), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['adv']), _ptr(sup['count']),
             _ptr(qry['states']), _ptr(qry['actions']), _ptr(qry['adv']), _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B,
@@ -784,34 +829,53 @@ class PolicyEngine:
         return loss, kl, grad
 
     @_on_device
-    def fvp(self, sup, qry, inner_lr, damping, v):
-        """Fisher-vector product at the theta of the preceding ``surrogate`` call (same replays)."""
+    def fvp(self, sup, qry, inner_lr, damping, v, step_lr_row=None):
+        """Fisher-vector product at the theta of the preceding ``surrogate`` call (same replays, same step)."""
         K, T, B = self._trpo_shapes(sup, qry, v=v)
-        ws = self._workspace(T, B, K)
+        tab = self._lr_table(inner_lr, K, step_lr_row)
+        ws = self._workspace(T, B, K, tab[1] if tab else 0)
         out = torch.empty(self.param_count, device=self.device)
+        if tab:
+            self._check(self.lib.mi_trpo_fvp_steps_lr(self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']),
+                                                      _ptr(sup['count']), _ptr(qry['states']), _ptr(qry['count']), T, B, _ptr(tab[0]), tab[1],
+                                                      tab[2], float(damping), _ptr(v.contiguous()), _ptr(out), _ptr(ws), ws.numel()))
+            return out
         self._check(self.lib.mi_trpo_fvp_steps(self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']),
                                                _ptr(qry['states']), _ptr(qry['count']), T, B, float(inner_lr), float(damping),
                                                _ptr(v.contiguous()), _ptr(out), _ptr(ws), ws.numel()))
         return out
 
     @_on_device
-    def kl_prepare(self, sup, qry, old_loc, old_scale, inner_lr, want_grad=False):
+    def kl_prepare(self, sup, qry, old_loc, old_scale, inner_lr, want_grad=False, step_lr_row=None):
         """After ``surrogate`` at the same theta and replays: the context of the exact KL Hessian-vector product for
         new != old with K = sup['states'].shape[0] inner updates (ANIL-TRPO).  Returns d mean KL / d theta [P] if ``want_grad``."""
         K, T, B = self._trpo_shapes(sup, qry, old_loc=old_loc, old_scale=old_scale)
-        ws = self._workspace(T, B, K)
+        tab = self._lr_table(inner_lr, K, step_lr_row)
+        ws = self._workspace(T, B, K, tab[1] if tab else 0)
         grad = torch.empty(self.param_count, device=self.device) if want_grad else None
+        if tab:
+            self._check(self.lib.mi_trpo_kl_prepare_steps_lr(
+                self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
+                _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B, _ptr(tab[0]), tab[1], tab[2], _ptr(grad), _ptr(ws), ws.numel()))
+            return grad
         self._check(self.lib.mi_trpo_kl_prepare_steps(
             self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
             _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B, float(inner_lr), _ptr(grad), _ptr(ws), ws.numel()))
         return grad
 
     @_on_device
-    def fvp_general(self, sup, qry, old_scale, inner_lr, damping, v):
+    def fvp_general(self, sup, qry, old_scale, inner_lr, damping, v, step_lr_row=None):
         """Exact Hessian-vector product of the mean KL at the theta of the preceding ``surrogate`` + ``kl_prepare``."""
         K, T, B = self._trpo_shapes(sup, qry, old_scale=old_scale, v=v)
-        ws = self._workspace(T, B, K)
+        tab = self._lr_table(inner_lr, K, step_lr_row)
+        ws = self._workspace(T, B, K, tab[1] if tab else 0)
         out = torch.empty(self.param_count, device=self.device)
+        if tab:
+            self._check(self.lib.mi_trpo_fvp_general_steps_lr(
+                self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
+                _ptr(qry['count']), _ptr(old_scale), T, B, _ptr(tab[0]), tab[1], tab[2], float(damping), _ptr(v.contiguous()), _ptr(out),
+                _ptr(ws), ws.numel()))
+            return out
         self._check(self.lib.mi_trpo_fvp_general_steps(
             self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
             _ptr(qry['count']), _ptr(old_scale), T, B, float(inner_lr), float(damping), _ptr(v.contiguous()), _ptr(out), _ptr(ws),

@@ -871,6 +871,49 @@ int mi_trpo_fvp_general_steps(mi_policy* p, void* stream, int steps, const float
                               int tasks, int batch, float inner_lr, float damping, const float* v, float* out, void* workspace,
                               size_t workspace_bytes);
 
+/* The TRPO calls with per-parameter inner-loop step sizes (fixed: TRPO's outer step is a trust region over theta alone, the steps get
+ * no gradient).  Each entry is its scalar namesake with `const float* lr_vec, int lr_rows, const int32_t* step_lr_row` where that takes
+ * `float inner_lr`: lr_vec [lr_rows][P] on the device in the parameter order (sigma, W1, b1, W2, b2, W3, b3), shared by all tasks;
+ * update k reads row step_lr_row[k] (host array [steps]; NULL: row 0 for every update).  With d_k that row,
+ *   theta_{k+1} = theta_k - d_k (.) g_k                     J_k = I - D_k H_k
+ *   tangent  (J_k u):      u_{k+1} = u_k - d_k (.) (H_k u_k)
+ *   adjoint  (J_k^T lam):  lam_k   = lam_{k+1} - H_k (d_k (.) lam_{k+1})            (NOT lam - d (.) (H lam): D H is not symmetric)
+ *   surrogate gradient = mean_t lam_0 with lam_K = grad S_t(theta_K);   Fisher form (new == old) = mean_t J^T F_t J v + damping v
+ *   exact KL Hessian:  rho_K = Hess KL_t(theta_K) u_K,
+ *                      rho_k = rho_{k+1} - H_k (d_k (.) rho_{k+1}) - T_k[u_k, d_k (.) lam_{k+1}],   product = mean_t rho_0 + damping v
+ * An entry whose step is exactly 0 (a frozen tensor) leaves theta_K with the bits of theta, yet still receives the cross-Hessian terms.
+ * The same implementation as the scalar entries (which are its lr_vec == NULL case and launch what they launched before): the fused
+ * sweeps at steps == 1 of a supported policy -- the fold that finishes w = F u (or lam) also writes d (.) w for the next sweep, no launch
+ * is added -- the per-layer path otherwise; the number of launches depends on `steps` only.
+ *   mi_policy_adapt_lr: mi_policy_adapt with ONE row lr_vec [P]; head_only multiplies it by the head mask.
+ *   mi_trpo_steps_lr_workspace_bytes: equals mi_trpo_steps_workspace_bytes (the extra direction lives in a slot of that plan that is
+ *     idle once the inner updates are done).  mi_trpo_general_steps_lr_workspace_bytes: the scalar plan, offsets unmoved, then
+ *     [steps][tasks][P] floats (d_k (.) lam_{k+1}); it serves every *_lr call and every scalar call.
+ * Argument errors are MI_ERR_ARG before any HIP call, outputs untouched, with a text naming the entry and the value: lr_vec NULL,
+ * lr_rows < 1, a step_lr_row entry outside 0..lr_rows-1, steps / tasks / batch < 1, and the scalar entries' own checks. */
+int mi_policy_adapt_lr(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states, const float* actions,
+                       const float* adv, const int32_t* count, int tasks, int batch, const float* lr_vec, int head_only,
+                       float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes);
+int mi_trpo_steps_lr_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, int lr_rows, size_t* bytes);
+int mi_trpo_surrogate_steps_lr(mi_policy* p, void* stream, const float* theta, int steps, const float* s_states,
+                               const float* s_actions, const float* s_adv, const int32_t* s_count, const float* q_states,
+                               const float* q_actions, const float* q_adv, const int32_t* q_count, const float* old_loc,
+                               const float* old_scale, int tasks, int batch, const float* lr_vec, int lr_rows,
+                               const int32_t* step_lr_row, float* loss_out, float* kl_out, float* grad_out, void* workspace,
+                               size_t workspace_bytes);
+int mi_trpo_fvp_steps_lr(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions, const int32_t* s_count,
+                         const float* q_states, const int32_t* q_count, int tasks, int batch, const float* lr_vec, int lr_rows,
+                         const int32_t* step_lr_row, float damping, const float* v, float* out, void* workspace, size_t workspace_bytes);
+int mi_trpo_general_steps_lr_workspace_bytes(const mi_policy* p, int tasks, int batch, int steps, int lr_rows, size_t* bytes);
+int mi_trpo_kl_prepare_steps_lr(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
+                                const float* old_scale, int tasks, int batch, const float* lr_vec, int lr_rows,
+                                const int32_t* step_lr_row, float* kl_grad_out, void* workspace, size_t workspace_bytes);
+int mi_trpo_fvp_general_steps_lr(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
+                                 const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
+                                 int tasks, int batch, const float* lr_vec, int lr_rows, const int32_t* step_lr_row, float damping,
+                                 const float* v, float* out, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
