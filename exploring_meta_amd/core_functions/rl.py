@@ -438,9 +438,8 @@ def trpo_a2c_loss(episodes, learner, baseline, gamma, tau, update_vf=True):
 def _trpo_step(eng, inner_lr, head_only, table=None, step_row=None):
     """``step`` of the adapt loop for TRPO: mi_policy_adapt, or with a step-size ``table`` [rows, P] (``_trpo_lr_table``)
     mi_policy_adapt_lr with the row ``step_row[k]`` of adapt step k."""
-    if table is None:
-        return lambda theta, b, adv, k=0: eng.adapt(theta, b['states'], b['actions'], adv, b['count'], inner_lr, head_only=head_only)[0]
-    return lambda theta, b, adv, k=0: eng.adapt(theta, b['states'], b['actions'], adv, b['count'], table[step_row[k]], head_only=head_only)[0]
+    return lambda theta, b, adv, k=0: eng.adapt(theta, b['states'], b['actions'], adv, b['count'],
+                                                inner_lr if table is None else table[step_row[k]], head_only=head_only)[0]
 
 
 def _trpo_lr_table(learner, name):
@@ -884,37 +883,29 @@ def _adapt_and_validate(run, pol, baseline, params, algo, anil, first_order, dic
     clip = params.get('ppo_clip_ratio', 0.1)
     kind = 'ppo' if algo == 'ppo' else ('dice' if dice else 'a2c')
     lrv = _policy_lr_vector(learner)
-    if lrv is None:
-        step = lambda theta, b, adv, k: eng.update(theta, b['states'], b['actions'], adv, b['count'], lr, loss=kind, epochs=epochs, clip=clip,
-                                                   done=b['dones'] if kind == 'dice' else None, head_only=bool(anil))[0]
-    else:
+    if lrv is not None:
         step_row = _lr_step_rows(lrv.shape[0], params['adapt_steps'])
         rows = lrv.detach().to(pol.sigma.device, torch.float32).contiguous()
-        step = lambda theta, b, adv, k: eng.update(theta, b['states'], b['actions'], adv, b['count'], rows[step_row[k]], loss=kind, epochs=epochs,
-                                                   clip=clip, done=b['dones'] if kind == 'dice' else None, head_only=bool(anil))[0]
+    lr_of = lambda k: lr if lrv is None else rows[step_row[k]]          # the step of adapt step k: the number, or its row of the table
+    step = lambda theta, b, adv, k: eng.update(theta, b['states'], b['actions'], adv, b['count'], lr_of(k), loss=kind, epochs=epochs, clip=clip,
+                                               done=b['dones'] if kind == 'dice' else None, head_only=bool(anil))[0]
     theta0 = pol.flat()
     theta, sups, qry, _, views = _adapt_loop(run, step, theta0, params['adapt_steps'], baseline, gamma, tau, algo == 'ppo', keep_views)
     qry['adv'], _ = _batch_advantages(qry, baseline, gamma, tau, normalize=(algo == 'ppo'))
     sup, engine_qry = _stack_batches(sups, qry)
     step_batch = [b for b in range(len(sups)) for _ in range(epochs)]
     need = torch.is_grad_enabled() and any(q.requires_grad for q in pol.parameters())
-    if lrv is not None:
-        need_lr = torch.is_grad_enabled() and lrv.requires_grad
-        lt, _, grad, lr_grad = eng.meta_batch_lr(theta0, sup, engine_qry, step_batch, rows, [step_row[b] for b in step_batch], loss=kind,
-                                                 clip=clip, head_only=bool(anil), first_order=first_order, with_grad=need or need_lr,
-                                                 want_lr_grad=need_lr)
-        total = lt.sum()
-        if need or need_lr:                                    # the step tensor is one more differentiable input: lr_grad * gout
-            eparams = pol._engine_params() + ([lrv] if need_lr else [])
-            flat = torch.cat([grad, lr_grad.reshape(-1)]) if need_lr else grad
-            total = _PolicyMetaLoss.apply(total, flat, [q.shape for q in eparams], *eparams)
-        return total, lt, theta, qry, views
-    lt, _, grad = eng.meta_batch(theta0, sup, engine_qry, step_batch, lr, loss=kind, clip=clip, head_only=bool(anil), first_order=first_order,
-                                 with_grad=need)
+    need_lr = lrv is not None and torch.is_grad_enabled() and lrv.requires_grad
+    kw = dict(loss=kind, clip=clip, head_only=bool(anil), first_order=first_order, with_grad=need or need_lr)
+    if lrv is None:
+        (lt, _, grad), lr_grad = eng.meta_batch(theta0, sup, engine_qry, step_batch, lr, **kw), None
+    else:
+        lt, _, grad, lr_grad = eng.meta_batch_lr(theta0, sup, engine_qry, step_batch, rows, [step_row[b] for b in step_batch], want_lr_grad=need_lr, **kw)
     total = lt.sum()
-    if need:
-        eparams = pol._engine_params()
-        total = _PolicyMetaLoss.apply(total, grad, [q.shape for q in eparams], *eparams)
+    if need or need_lr:                                        # the step tensor is one more differentiable input: lr_grad * gout
+        eparams = pol._engine_params() + ([lrv] if need_lr else [])
+        flat = torch.cat([grad, lr_grad.reshape(-1)]) if need_lr else grad
+        total = _PolicyMetaLoss.apply(total, flat, [q.shape for q in eparams], *eparams)
     return total, lt, theta, qry, views
 
 

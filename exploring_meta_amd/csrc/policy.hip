@@ -16,7 +16,7 @@
 //   MAML-TRPO (new == old, Fisher form exact)          mi_trpo_surrogate_steps / mi_trpo_fvp_steps
 //   ANIL-TRPO (new != old, exact Hessian of mean KL)   ... then mi_trpo_kl_prepare_steps / mi_trpo_fvp_general_steps
 // Each of them also takes a FIXED step-size table in place of the number lr (mi_policy_adapt_lr, mi_trpo_*_steps_lr: the same
-// implementation with an LrCall; the scalar entries pass none and launch what they launched before).  lr_vec [rows][P] in the order
+// implementation: its PolicyStep holds the table; the launches differ in step_advance and AdjointWalk only).  lr_vec [rows][P] in the order
 // above, shared by all tasks; update k reads row step_lr_row[k] = d_k (mi_policy_adapt_lr's head_only: times the head mask):
 //   theta_{k+1} = theta_k - d_k (.) g_k                       J_k = I - D_k H_k
 //   tangent  (J_k u):      u_{k+1} = u_k - d_k (.) (H_k u_k)
@@ -29,6 +29,7 @@
 #include <string>
 #include <vector>
 #include <cmath>
+#include <climits>
 #include "mi_common.h"
 #include "../../include/mi_maml.h"
 
@@ -906,6 +907,104 @@ __global__ void lr_fold_kernel(const float* __restrict__ prod, const float* __re
   out[(size_t)r * p + i] = (float)(0.0 - acc);
 }
 
+// out = a - alpha (h + s3): one step of the general product's rho recursion in one launch (out may be a)
+__global__ void step_back_kernel(const float* a, const float* __restrict__ h, const float* __restrict__ s3, float alpha, size_t n, float* out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = a[i] - alpha * (h[i] + s3[i]);
+}
+// ---- THE description of a call's inner-loop step, from the extern "C" entry to the launches: the number lr, or the step-size table
+// (vec != NULL; update k reads row step_row[k] = d_k).  The two forms launch different kernels in step_advance and AdjointWalk only.
+struct PolicyStep {
+  float lr = 0.f;                   // the number
+  const float* vec = nullptr; int rows = 0;       // device [rows][P], the table; NULL: the number
+  const int32_t* step_row = nullptr;      // host [steps], or NULL = all 0
+  float* lr_grad_out = nullptr;     // device [rows][P], or NULL (mi_policy_meta_batch_lr)
+  size_t P = 0;                     // (check_table fills it in)
+  const char* fn = nullptr;         // the entry's name in the error texts; NULL: the scalar entries whose texts carry none
+  bool table() const { return vec != nullptr; }
+  const float* row(int k) const { return vec ? vec + (size_t)(step_row ? step_row[k] : 0) * P : nullptr; }
+  std::string prefix() const { return fn ? std::string(fn) + ": " : std::string(); }
+};
+struct StepsRule { int lo, hi; bool first; };      // an entry's range of `steps` (INT_MAX: unbounded); first: checked ahead of tasks / batch
+static const StepsRule META_STEPS{0, MI_POLICY_LR_MAX_STEPS, false}, TRPO_STEPS{1, INT_MAX, true}, ONE_STEP{1, 1, true};
+// The checks a step-size-table entry makes of the table it put into `s`, before any HIP call: the texts and the order they always had
+static int check_table(mi_policy* p, PolicyStep& s, int steps, const StepsRule& r, int tasks, int batch) {
+  const std::string fn = s.prefix();
+  if (!p) return pfail(nullptr, MI_ERR_ARG, fn + "null policy handle");
+  if (!s.vec) return pfail(p, MI_ERR_ARG, fn + "lr_vec is NULL");
+  if (s.rows < 1 || s.rows > MI_POLICY_LR_MAX_ROWS)
+    return pfail(p, MI_ERR_ARG, fn + "lr_rows " + std::to_string(s.rows) + " (must be 1.." + std::to_string(MI_POLICY_LR_MAX_ROWS) + ")");
+  const std::string range = r.hi == INT_MAX ? ">= " + std::to_string(r.lo) : std::to_string(r.lo) + ".." + std::to_string(r.hi);
+  const bool steps_bad = steps < r.lo || steps > r.hi;
+  if (r.first && steps_bad) return pfail(p, MI_ERR_ARG, fn + "steps " + std::to_string(steps) + " (must be " + range + ")");
+  if (tasks < 1) return pfail(p, MI_ERR_ARG, fn + "tasks " + std::to_string(tasks) + " (must be >= 1)");
+  if (batch < 1) return pfail(p, MI_ERR_ARG, fn + "batch " + std::to_string(batch) + " (must be >= 1)");
+  if (steps_bad) return pfail(p, MI_ERR_ARG, fn + "steps " + std::to_string(steps) + " (must be " + range + ")");
+  for (int k = 0; s.step_row && k < steps; ++k)
+    if (s.step_row[k] < 0 || s.step_row[k] >= s.rows)
+      return pfail(p, MI_ERR_ARG, fn + "step_lr_row[" + std::to_string(k) + "] " + std::to_string(s.step_row[k]) + " (must be 0.." +
+                                      std::to_string(s.rows - 1) + ")");
+  s.P = p->P;
+  return MI_OK;
+}
+// Advance of update k for all tasks: out[t] = a[t] - d_k (.) g[t]  (a: stride astride floats per task, 0 = shared; out may be a).  Table:
+// lr_advance_kernel, head mask folded in.  Number: head_mask_kernel on g (not if `g_masked`: mlp_backward(head_only) left the zeros), axpy_bcast_kernel.
+static int step_advance(mi_policy* p, hipStream_t st, int T, const PolicyStep& s, int k, bool head_only, bool g_masked, const float* a,
+                        size_t astride, float* g, float* out) {
+  const int P = (int)p->P, lo = (int)p->o_w1, hi = (int)p->o_w3;          // the body: W1, b1, W2, b2
+  const dim3 grid(ceil_div(P, 256), T);
+  if (s.table()) {
+    hipLaunchKernelGGL(lr_advance_kernel, grid, dim3(256), 0, st, a, astride, (const float*)g, s.row(k), P, head_only ? lo : 0,
+                       head_only ? hi : 0, out);
+  } else {
+    if (head_only && !g_masked) hipLaunchKernelGGL(head_mask_kernel, grid, dim3(256), 0, st, g, P, lo, hi);
+    hipLaunchKernelGGL(axpy_bcast_kernel, grid, dim3(256), 0, st, a, astride, (const float*)g, s.lr, P, out);
+  }
+  PCHK(p, hipGetLastError());
+  return MI_OK;
+}
+// One adjoint recursion through the updates K-1 .. 0 on [T][P] vectors:  x_k = x_{k+1} - H_k (d_k (.) x_{k+1}) [- s3].  The walk that owns it
+// computes hv = H_k (.) itself (gauss2 tangent pass, hvp_step, sweep_hvp, mixed_sweep); this owns what differs between the forms:
+//   table   seed() writes dir = d_{K-1} (.) x_K, the HVP of update k is driven with dir, back() finishes x_k and writes the dir (and the
+//           lr_grad product g_{k-1} (.) x_k) of update k - 1 in the same launch (lr_adjoint_kernel)
+//   number  the HVP is driven with x itself (meta-batch, `copy_dir`: with a head-masked copy of it in dir); back() is [head mask on hv +]
+//           axpy_bcast_kernel, or step_back_kernel where a third-derivative term s3 comes with hv
+struct AdjointWalk {
+  mi_policy* p; hipStream_t st; int T; const PolicyStep& step;
+  bool head_only, copy_dir;
+  dim3 grid() const { return dim3(ceil_div((int)p->P, 256), T); }
+  int seed(int K, float* x, const float* g, float* dir, float* prod) const {
+    if (!step.table() || K < 1) return MI_OK;
+    hipLaunchKernelGGL(lr_adjoint_kernel, grid(), dim3(256), 0, st, (const float*)x, (const float*)nullptr, (const float*)nullptr,
+                       step.row(K - 1), g, (int)p->P, head_only ? (int)p->o_w1 : 0, head_only ? (int)p->o_w3 : 0, x, dir, prod);
+    PCHK(p, hipGetLastError());
+    return MI_OK;
+  }
+  // *with: the buffer the HVP of the next update down is driven with
+  int drive(const float* x, float* dir, const float** with) const {
+    *with = step.table() || copy_dir ? dir : x;
+    if (step.table() || !copy_dir) return MI_OK;
+    PCHK(p, hipMemcpyAsync(dir, x, (size_t)T * p->P * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (head_only) hipLaunchKernelGGL(head_mask_kernel, grid(), dim3(256), 0, st, dir, (int)p->P, (int)p->o_w1, (int)p->o_w3);
+    return MI_OK;
+  }
+  // x_k -> out (may be x) from x = x_{k+1} and hv (+ s3); g, dir, prod: of update k - 1 (table form; k == 0 has none below it)
+  int back(int k, const float* x, float* hv, const float* s3, const float* g, float* out, float* dir, float* prod) const {
+    const size_t TP = (size_t)T * p->P;
+    if (step.table()) {
+      hipLaunchKernelGGL(lr_adjoint_kernel, grid(), dim3(256), 0, st, x, (const float*)hv, s3, k > 0 ? step.row(k - 1) : (const float*)nullptr,
+                         g, (int)p->P, head_only ? (int)p->o_w1 : 0, head_only ? (int)p->o_w3 : 0, out, dir, prod);
+    } else if (s3) {
+      hipLaunchKernelGGL(step_back_kernel, dim3((unsigned)((TP + 255) / 256)), dim3(256), 0, st, x, (const float*)hv, s3, step.lr, TP, out);
+    } else {
+      if (head_only) hipLaunchKernelGGL(head_mask_kernel, grid(), dim3(256), 0, st, hv, (int)p->P, (int)p->o_w1, (int)p->o_w3);
+      hipLaunchKernelGGL(axpy_bcast_kernel, grid(), dim3(256), 0, st, x, p->P, (const float*)hv, step.lr, (int)p->P, out);
+    }
+    PCHK(p, hipGetLastError());
+    return MI_OK;
+  }
+};
+
 struct StepSet { Acts a; float *dmu, *d2, *d1, *pre2, *pre1, *coef, *coef2; };
 struct MetaPlan {
   std::vector<StepSet> st;          // per inner update (second order) or one shared set
@@ -916,14 +1015,15 @@ struct MetaPlan {
   float* oldlp;                     // [n_batches][T][B]
   size_t bytes;
 };
+static void step_set_plan(const mi_policy* p, PBump& b, size_t TB, StepSet& s) {      // (also the one set of mi_policy_update's plan)
+  s.a.h1 = b.f(TB * p->H1); s.a.h2 = b.f(TB * p->H2); s.a.mu = b.f(TB * p->A);
+  s.dmu = b.f(TB * p->A); s.d2 = b.f(TB * p->H2); s.d1 = b.f(TB * p->H1); s.pre2 = b.f(TB * p->H2); s.pre1 = b.f(TB * p->H1);
+  s.coef = b.f(TB); s.coef2 = b.f(TB);
+}
 static void meta_plan(const mi_policy* p, void* ws, int T, int B, int K, int nb, bool keep_all, MetaPlan& pl) {
   PBump b{reinterpret_cast<char*>(ws), 0};
   const size_t TB = (size_t)T * B, TP = (size_t)T * p->P;
-  auto set = [&](StepSet& s) {
-    s.a.h1 = b.f(TB * p->H1); s.a.h2 = b.f(TB * p->H2); s.a.mu = b.f(TB * p->A);
-    s.dmu = b.f(TB * p->A); s.d2 = b.f(TB * p->H2); s.d1 = b.f(TB * p->H1); s.pre2 = b.f(TB * p->H2); s.pre1 = b.f(TB * p->H1);
-    s.coef = b.f(TB); s.coef2 = b.f(TB);
-  };
+  auto set = [&](StepSet& s) { step_set_plan(p, b, TB, s); };
   pl.st.resize(keep_all ? (K > 0 ? K : 1) : 1);
   for (auto& s : pl.st) set(s);
   set(pl.q);
@@ -946,13 +1046,6 @@ extern "C" int mi_policy_meta_workspace_bytes(const mi_policy* p, int tasks, int
 // The step-size-vector form of the call (mi_policy_meta_batch_lr).  Its plan lies BEHIND the scalar plan, whose offsets do not move: the
 // gradient of every update g [K][T][P] (the scalar call keeps one) and, second order, the products prod [K][T][P] -- both only when lr_grad
 // is wanted.  The tangent direction dir lies in the scalar plan's vmask slot.
-struct LrCall {
-  const float* vec;                 // device [rows][P]
-  int rows;
-  const int32_t* step_row;          // host [steps], or NULL = all 0
-  float* grad_out;                  // device [rows][P], or NULL
-  const char* fn;                   // the entry's name, for the argument errors
-};
 struct LrPlan { float *g, *prod; size_t bytes; };
 static void lr_plan(const mi_policy* p, void* ws, size_t scalar_bytes, int T, int K, bool so, bool want_lr_grad, LrPlan& lp) {
   PBump b{reinterpret_cast<char*>(ws), scalar_bytes};
@@ -974,45 +1067,62 @@ extern "C" int mi_policy_meta_lr_workspace_bytes(const mi_policy* p, int tasks, 
   return MI_OK;
 }
 
+// ---- What an extern "C" entry hands its implementation: named fields, filled one by one, in place of 20-30 positional arguments.
+// the support replays: [K][T][B][.] stacks (adapt / update, and the query: the one replay), and replay k of them
+struct SupStack { const float *states, *actions, *adv; const int32_t* count; const float* done; };
+struct SupRef { const float *xs, *as, *adv; const int32_t* cn; };
+static SupRef sup_at(const mi_policy* p, const SupStack& s, int T, int B, int k) {
+  const size_t TB = (size_t)T * B;
+  return {s.states + k * TB * p->S, s.actions + k * TB * p->A, s.adv ? s.adv + k * TB : nullptr,
+          s.count ? s.count + (size_t)k * T : nullptr};
+}
+// Every entry of this file that takes a step fills the fields it has: update's epochs are `steps`; grad_out is also kl_prepare's
+// kl_grad_out, `out` a curvature product.
+struct PolicyCall {
+  void* stream; const float* theta; size_t tstride;
+  int steps; const int32_t *step_batch, *step_new_old; int n_batches;
+  SupStack sup, qry; const float *old_loc, *old_scale;
+  int tasks, batch, loss_kind; float clip;
+  PolicyStep step;
+  int head_only, second_order, with_grad;
+  float damping; const float* v;
+  float *loss_out, *kl_out, *theta_out, *grad_out, *out;
+  void* workspace; size_t workspace_bytes;
+};
+
 // trpo_update (rl.py:361-374) for a meta-batch: theta_out[t] = theta[t] - lr * grad_t(-mean(logp * adv)).  loss_out [T].
 // Workspace: the plan of one kept update (mi_policy_meta_workspace_bytes(steps = 1, n_batches = 1, second_order = 1); the TRPO
 // workspaces start with it).
-// lr_vec: mi_policy_adapt_lr -- ONE row [P] of the step-size table in place of the number lr; the head mask of head_only is folded into
+// mi_policy_adapt_lr: ONE row [P] of the step-size table in place of the number lr; the head mask of head_only is folded into
 // the advance (lr_advance_kernel), and an entry whose step is exactly 0 leaves with the bits of theta.
-static int policy_adapt_impl(mi_policy* p, const std::string& fn, void* stream, const float* theta, size_t tstride, const float* states,
-                             const float* actions, const float* adv, const int32_t* count, int tasks, int batch, float lr,
-                             const float* lr_vec, int head_only, float* theta_out, float* loss_out, void* workspace,
-                             size_t workspace_bytes) {
-  if (!p || !theta || !states || !actions || !adv || !theta_out || !workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+static int policy_adapt_impl(mi_policy* p, const PolicyCall& c) {
+  const std::string fn = c.step.prefix();
+  const int T = c.tasks, B = c.batch;
+  if (!p || !c.theta || !c.sup.states || !c.sup.actions || !c.sup.adv || !c.theta_out || !c.workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
   MetaPlan pl;
-  meta_plan(p, workspace, tasks, batch, 1, 1, true, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(pl.bytes));
+  meta_plan(p, c.workspace, T, B, 1, 1, true, pl);
+  if (pl.bytes > c.workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(pl.bytes));
   StepSet& s = pl.st[0];
-  int rc = mlp_forward(p, st, tasks, batch, states, theta, tstride, s.a);
+  int rc = mlp_forward(p, st, T, B, c.sup.states, c.theta, c.tstride, s.a);
   if (rc) return rc;
-  PCHK(p, hipMemsetAsync(pl.g, 0, (size_t)tasks * p->P * sizeof(float), st));
+  PCHK(p, hipMemsetAsync(pl.g, 0, (size_t)T * p->P * sizeof(float), st));
   GaussArgs ga{};
-  ga.mu = s.a.mu; ga.rho = theta + p->o_sigma; ga.rstride = tstride; ga.act = actions; ga.adv = adv; ga.count = count;
-  ga.coef = s.coef; ga.dmu = s.dmu; ga.drho = pl.g + p->o_sigma; ga.gstride = p->P; ga.loss = loss_out ? loss_out : pl.hv;
-  ga.B = batch; ga.A = p->A; ga.mode = G_A2C;
-  PCHK(p, gauss(st, tasks, ga));
-  rc = mlp_backward(p, st, tasks, batch, states, theta, tstride, s.a, s.dmu, s.d2, s.d1, pl.g, nullptr, nullptr, head_only != 0);
+  ga.mu = s.a.mu; ga.rho = c.theta + p->o_sigma; ga.rstride = c.tstride; ga.act = c.sup.actions; ga.adv = c.sup.adv; ga.count = c.sup.count;
+  ga.coef = s.coef; ga.dmu = s.dmu; ga.drho = pl.g + p->o_sigma; ga.gstride = p->P; ga.loss = c.loss_out ? c.loss_out : pl.hv;
+  ga.B = B; ga.A = p->A; ga.mode = G_A2C;
+  PCHK(p, gauss(st, T, ga));
+  rc = mlp_backward(p, st, T, B, c.sup.states, c.theta, c.tstride, s.a, s.dmu, s.d2, s.d1, pl.g, nullptr, nullptr, c.head_only != 0);
   if (rc) return rc;
-  if (lr_vec)
-    hipLaunchKernelGGL(lr_advance_kernel, dim3(ceil_div((int)p->P, 256), tasks), dim3(256), 0, st, theta, tstride, (const float*)pl.g, lr_vec,
-                       (int)p->P, head_only ? (int)p->o_w1 : 0, head_only ? (int)p->o_w3 : 0, theta_out);
-  else
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)p->P, 256), tasks), dim3(256), 0, st, theta, tstride, pl.g, lr,
-                       (int)p->P, theta_out);
-  PCHK(p, hipGetLastError());
-  return MI_OK;
+  return step_advance(p, st, T, c.step, 0, c.head_only != 0, true, c.theta, c.tstride, pl.g, c.theta_out);
 }
 extern "C" int mi_policy_adapt(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
                                const float* actions, const float* adv, const int32_t* count, int tasks, int batch, float lr,
                                int head_only, float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
-  return policy_adapt_impl(p, std::string(), stream, theta, tstride, states, actions, adv, count, tasks, batch, lr, nullptr, head_only,
-                           theta_out, loss_out, workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.theta = theta; c.tstride = tstride; c.sup = {states, actions, adv, count, nullptr}; c.tasks = tasks; c.batch = batch;
+  c.step.lr = lr; c.head_only = head_only; c.theta_out = theta_out; c.loss_out = loss_out; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  return policy_adapt_impl(p, c);
 }
 
 // One primal pass of the VPG / PPO / DiCE losses for all tasks at parameters th (stride ts floats per task: P, or 0 = shared): forward, loss + cotangents
@@ -1044,137 +1154,104 @@ static int meta_old_logp(mi_policy* p, hipStream_t st, int T, int B, StepSet& s,
   return MI_OK;
 }
 
-static int policy_meta_batch_impl(mi_policy* p, void* stream, const float* theta, int steps, const int32_t* step_batch,
-                                  const int32_t* step_new_old, int n_batches, const float* s_states, const float* s_actions,
-                                  const float* s_adv, const int32_t* s_count, const float* s_done, const float* q_states,
-                                  const float* q_actions, const float* q_adv, const int32_t* q_count, const float* q_done, int tasks,
-                                  int batch, int loss_kind, float clip, float inner_lr, const LrCall* lrc, int head_only,
-                                  int second_order, int with_grad, float* loss_out, float* theta_out, float* grad_out, void* workspace,
-                                  size_t workspace_bytes) {
-  // lrc: the step-size-vector form (mi_policy_meta_batch_lr), whose texts name the entry; NULL: the scalar entries, texts as they were
-  const std::string fn = lrc ? std::string(lrc->fn) + ": " : std::string();
-  if (!p || !theta || !q_states || !q_actions || !q_adv || !loss_out || !workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
-  if (steps > 0 && (!step_batch || !s_states || !s_actions || !s_adv || n_batches < 1)) return pfail(p, MI_ERR_ARG, fn + "support batches missing");
-  if (loss_kind != MI_PLOSS_A2C && loss_kind != MI_PLOSS_PPO && loss_kind != MI_PLOSS_DICE)
+static int policy_meta_batch_impl(mi_policy* p, const PolicyCall& c) {
+  const PolicyStep& step = c.step;
+  const std::string fn = step.prefix();
+  const bool head_only = c.head_only != 0;
+  if (!p || !c.theta || !c.qry.states || !c.qry.actions || !c.qry.adv || !c.loss_out || !c.workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
+  if (c.steps > 0 && (!c.step_batch || !c.sup.states || !c.sup.actions || !c.sup.adv || c.n_batches < 1)) return pfail(p, MI_ERR_ARG, fn + "support batches missing");
+  if (c.loss_kind != MI_PLOSS_A2C && c.loss_kind != MI_PLOSS_PPO && c.loss_kind != MI_PLOSS_DICE)
     return pfail(p, MI_ERR_ARG, fn + "loss_kind must be MI_PLOSS_A2C, MI_PLOSS_PPO or MI_PLOSS_DICE");
-  if (loss_kind == MI_PLOSS_DICE && (!q_done || (steps > 0 && !s_done)))
+  if (c.loss_kind == MI_PLOSS_DICE && (!c.qry.done || (c.steps > 0 && !c.sup.done)))
     return pfail(p, MI_ERR_ARG, fn + "the DiCE objective needs the episode-end flags of every replay (s_done / q_done)");
-  if (loss_kind == MI_PLOSS_PPO && steps > 0 && !step_new_old) return pfail(p, MI_ERR_ARG, fn + "PPO needs step_new_old");
-  if (with_grad && !grad_out) return pfail(p, MI_ERR_ARG, fn + "grad_out is NULL but with_grad != 0");
-  for (int k = 0; k < steps; ++k)
-    if (step_batch[k] < 0 || step_batch[k] >= n_batches) return pfail(p, MI_ERR_ARG, fn + "step_batch entry out of range");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, B = batch, K = steps;
+  if (c.loss_kind == MI_PLOSS_PPO && c.steps > 0 && !c.step_new_old) return pfail(p, MI_ERR_ARG, fn + "PPO needs step_new_old");
+  if (c.with_grad && !c.grad_out) return pfail(p, MI_ERR_ARG, fn + "grad_out is NULL but with_grad != 0");
+  for (int k = 0; k < c.steps; ++k)
+    if (c.step_batch[k] < 0 || c.step_batch[k] >= c.n_batches) return pfail(p, MI_ERR_ARG, fn + "step_batch entry out of range");
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+  const int T = c.tasks, B = c.batch, K = c.steps;
   const size_t P = p->P, TB = (size_t)T * B, TP = (size_t)T * P;
-  const bool so = second_order && with_grad;
+  const bool so = c.second_order && c.with_grad;
   MetaPlan pl;
-  meta_plan(p, workspace, T, B, K, n_batches, so, pl);
+  meta_plan(p, c.workspace, T, B, K, c.n_batches, so, pl);
   LrPlan lp{nullptr, nullptr, pl.bytes};
-  if (lrc) lr_plan(p, workspace, pl.bytes, T, K, so, lrc->grad_out != nullptr, lp);
-  if (lp.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(lp.bytes));
-  const int body_lo = (int)p->o_w1, body_hi = (int)p->o_w3;          // W1, b1, W2, b2
-  const dim3 pgrid(ceil_div((int)P, 256), T);
-  const int m_lo = head_only ? body_lo : 0, m_hi = head_only ? body_hi : 0;      // the vector kernels fold the head mask in
-  auto lr_row = [&](int k) { return lrc->vec + (size_t)(lrc->step_row ? lrc->step_row[k] : 0) * P; };
+  if (step.table()) lr_plan(p, c.workspace, pl.bytes, T, K, so, step.lr_grad_out != nullptr, lp);
+  if (lp.bytes > c.workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(lp.bytes));
   auto g_of = [&](int k) { return lp.g ? lp.g + (size_t)k * TP : pl.g; };         // kept per update when lr_grad is wanted
-  auto mask = [&](float* v) {
-    if (head_only) hipLaunchKernelGGL(head_mask_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (int)P, body_lo, body_hi);
-  };
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, theta, (size_t)0, pl.g, 0.f, (int)P, pl.theta);
+  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, c.theta, (size_t)0, pl.g, 0.f, (int)P, pl.theta);
   PCHK(p, hipGetLastError());
-  auto primal = [&](StepSet& s, const float* th, const float* states, const float* actions, const float* adv, const int32_t* count,
-                    int kind, const float* oldlp, int value_ratio_one, float* g, float* loss, const float* done) -> int {
-    return meta_primal(p, st, T, B, clip, s, th, P, states, actions, adv, count, kind, oldlp, value_ratio_one, g, loss, done);
-  };
   // ---- inner updates
   for (int k = 0; k < K; ++k) {
     StepSet& s = so ? pl.st[k] : pl.st[0];
     float* th = pl.theta + (size_t)k * TP;
-    const int bi = step_batch[k];
-    const float* xs = s_states + (size_t)bi * TB * p->S;
-    const float* as = s_actions + (size_t)bi * TB * p->A;
-    const float* ad = s_adv + (size_t)bi * TB;
-    const int32_t* cn = s_count ? s_count + (size_t)bi * T : nullptr;
+    const int bi = c.step_batch[k];
+    const float* xs = c.sup.states + (size_t)bi * TB * p->S;
+    const float* as = c.sup.actions + (size_t)bi * TB * p->A;
+    const float* ad = c.sup.adv + (size_t)bi * TB;
+    const int32_t* cn = c.sup.count ? c.sup.count + (size_t)bi * T : nullptr;
     float* olp = pl.oldlp + (size_t)bi * TB;
-    if (loss_kind == MI_PLOSS_PPO && step_new_old[k]) {       // old_log_probs = learner.log_prob(...) under no_grad (rl.py:282-283)
+    if (c.loss_kind == MI_PLOSS_PPO && c.step_new_old[k]) {       // old_log_probs = learner.log_prob(...) under no_grad (rl.py:282-283)
       int rc = meta_old_logp(p, st, T, B, s, th, xs, as, cn, olp);
       if (rc) return rc;
     }
-    int rc = primal(s, th, xs, as, ad, cn, loss_kind, olp, 0, g_of(k), pl.hv /* scratch for the step loss */,
-                    s_done ? s_done + (size_t)bi * TB : nullptr);
+    int rc = meta_primal(p, st, T, B, c.clip, s, th, P, xs, as, ad, cn, c.loss_kind, olp, 0, g_of(k), pl.hv /* scratch: the step loss */,
+                    c.sup.done ? c.sup.done + (size_t)bi * TB : nullptr);
     if (rc) return rc;
-    if (lrc) {
-      hipLaunchKernelGGL(lr_advance_kernel, pgrid, dim3(256), 0, st, th, P, g_of(k), lr_row(k), (int)P, m_lo, m_hi, th + TP);
-    } else {
-      mask(pl.g);
-      hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, th, P, pl.g, inner_lr, (int)P, th + TP);
-    }
-    PCHK(p, hipGetLastError());
+    rc = step_advance(p, st, T, step, k, head_only, false, th, P, g_of(k), th + TP);
+    if (rc) return rc;
   }
   float* thK = pl.theta + (size_t)K * TP;
-  if (theta_out) PCHK(p, hipMemcpyAsync(theta_out, thK, TP * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (c.theta_out) PCHK(p, hipMemcpyAsync(c.theta_out, thK, TP * sizeof(float), hipMemcpyDeviceToDevice, st));
   // ---- query loss: VPG = a2c loss; PPO = ppo loss against the adapted policy itself (ratio == 1: value -mean(A), gradient of A2C form)
-  int rc = primal(pl.q, thK, q_states, q_actions, q_adv, q_count, loss_kind == MI_PLOSS_DICE ? MI_PLOSS_DICE : MI_PLOSS_A2C, nullptr,
-                  loss_kind == MI_PLOSS_PPO ? 1 : 0, pl.lam, loss_out, q_done);
+  int rc = meta_primal(p, st, T, B, c.clip, pl.q, thK, P, c.qry.states, c.qry.actions, c.qry.adv, c.qry.count, c.loss_kind == MI_PLOSS_DICE ? MI_PLOSS_DICE : MI_PLOSS_A2C, nullptr,
+                  c.loss_kind == MI_PLOSS_PPO ? 1 : 0, pl.lam, c.loss_out, c.qry.done);
   if (rc) return rc;
-  if (!with_grad) return MI_OK;
-  // ---- adjoint recursion through the updates
+  if (!c.with_grad) return MI_OK;
+  // ---- adjoint recursion through the updates: the tangent pass of update k is driven with v = d_k (.) lam_{k+1} (table) or the masked
+  // lam_{k+1} (number), in vmask; the table form also keeps the lr_grad products of every update
   if (so) {
-    // the vector form drives the tangent pass of update k with dir = d_k (.) lam_{k+1} (in vmask) and subtracts H_k dir as it comes: the
-    // advance that finishes lam_{k+1} also writes the dir (and the lr_grad products) of update k
-    auto adjoint = [&](const float* hv, int k) {      // k: the update whose dir / prod to write, -1 = none
-      hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)pl.lam, hv, (const float*)nullptr,
-                         k >= 0 ? lr_row(k) : (const float*)nullptr,
-                         k >= 0 ? (const float*)g_of(k) : (const float*)nullptr, (int)P, m_lo, m_hi, pl.lam, pl.vmask,
-                         k >= 0 && lp.prod ? lp.prod + (size_t)k * TP : (float*)nullptr);
-    };
-    if (lrc && K > 0) {
-      adjoint(nullptr, K - 1);
-      PCHK(p, hipGetLastError());
-    }
+    const AdjointWalk adj{p, st, T, step, head_only, true};
+    auto g_or_none = [&](int k) { return k >= 0 ? (const float*)g_of(k) : (const float*)nullptr; };
+    auto prod_of = [&](int k) { return k >= 0 && lp.prod ? lp.prod + (size_t)k * TP : (float*)nullptr; };
+    rc = adj.seed(K, pl.lam, g_or_none(K - 1), pl.vmask, prod_of(K - 1));
+    if (rc) return rc;
     for (int k = K - 1; k >= 0; --k) {
       StepSet& s = pl.st[k];
       const float* th = pl.theta + (size_t)k * TP;
-      const int bi = step_batch[k];
-      const float* xs = s_states + (size_t)bi * TB * p->S;
-      const float* as = s_actions + (size_t)bi * TB * p->A;
-      const int32_t* cn = s_count ? s_count + (size_t)bi * T : nullptr;
-      // v = [mask] lam ; hv = H_k v
-      if (!lrc) {
-        PCHK(p, hipMemcpyAsync(pl.vmask, pl.lam, TP * sizeof(float), hipMemcpyDeviceToDevice, st));
-        mask(pl.vmask);
-      }
+      const int bi = c.step_batch[k];
+      const float* xs = c.sup.states + (size_t)bi * TB * p->S;
+      const float* as = c.sup.actions + (size_t)bi * TB * p->A;
+      const int32_t* cn = c.sup.count ? c.sup.count + (size_t)bi * T : nullptr;
+      const float* v;                                        // hv = H_k v
+      rc = adj.drive(pl.lam, pl.vmask, &v);
+      if (rc) return rc;
       PCHK(p, hipMemsetAsync(pl.hv, 0, TP * sizeof(float), st));
-      rc = mlp_tangent_forward(p, st, T, B, xs, th, P, s.a, pl.vmask, pl.ta);
+      rc = mlp_tangent_forward(p, st, T, B, xs, th, P, s.a, v, pl.ta);
       if (rc) return rc;
       Gauss2Args gt{};
-      gt.mu = s.a.mu; gt.mud = pl.ta.mu; gt.rho = th + p->o_sigma; gt.rstride = P; gt.rhod = pl.vmask + p->o_sigma; gt.vstride = P;
+      gt.mu = s.a.mu; gt.mud = pl.ta.mu; gt.rho = th + p->o_sigma; gt.rstride = P; gt.rhod = v + p->o_sigma; gt.vstride = P;
       gt.act = as; gt.count = cn; gt.coef = s.coef; gt.coef2 = s.coef2; gt.dmu = pl.rdmu; gt.drho = pl.hv + p->o_sigma; gt.gstride = P;
       gt.B = B; gt.A = p->A; gt.mode = P_TANGENT;
-      if (loss_kind == MI_PLOSS_DICE) {                      // the episode recurrences couple the samples of a replay
-        gt.kind = MI_PLOSS_DICE; gt.done = s_done + (size_t)bi * TB; gt.adv = s_adv + (size_t)bi * TB;
+      if (c.loss_kind == MI_PLOSS_DICE) {                      // the episode recurrences couple the samples of a replay
+        gt.kind = MI_PLOSS_DICE; gt.done = c.sup.done + (size_t)bi * TB; gt.adv = c.sup.adv + (size_t)bi * TB;
         gt.scratch = pl.oldlp + (size_t)bi * TB;             // free: old log-probs exist only for PPO
       }
       hipLaunchKernelGGL(gauss2_kernel, dim3(T), dim3(256), 0, st, gt);
       PCHK(p, hipGetLastError());
-      rc = mlp_tangent_backward(p, st, T, B, xs, th, P, s.a, pl.ta, pl.vmask, s.dmu, s.d2, s.d1, s.pre2, s.pre1, pl.rdmu, pl.r2, pl.r1, pl.hv);
+      rc = mlp_tangent_backward(p, st, T, B, xs, th, P, s.a, pl.ta, v, s.dmu, s.d2, s.d1, s.pre2, s.pre1, pl.rdmu, pl.r2, pl.r1, pl.hv);
       if (rc) return rc;
-      if (lrc) {
-        adjoint(pl.hv, k - 1);
-      } else {
-        mask(pl.hv);      // the body sat under no_grad during the update: no path from theta_{k+1} back into it
-        hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, pl.lam, P, pl.hv, inner_lr, (int)P, pl.lam);
-      }
-      PCHK(p, hipGetLastError());
+      // (head_only: the body sat under no_grad during the update, no path from theta_{k+1} back into it)
+      rc = adj.back(k, pl.lam, pl.hv, nullptr, g_or_none(k - 1), pl.lam, pl.vmask, prod_of(k - 1));
+      if (rc) return rc;
     }
   }
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.lam, T, (int)P, 1.f, (const float*)nullptr, 0.f, grad_out);
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.lam, T, (int)P, 1.f, (const float*)nullptr, 0.f, c.grad_out);
   PCHK(p, hipGetLastError());
-  if (lrc && lrc->grad_out) {       // first order: lam_{k+1} = lam_K for every k, still in pl.lam; the fold forms the products itself
+  if (step.lr_grad_out) {           // first order: lam_{k+1} = lam_K for every k, still in pl.lam; the fold forms the products itself
     LrRows rows;
-    for (int k = 0; k < MI_POLICY_LR_MAX_STEPS; ++k) rows.row[k] = k < K && lrc->step_row ? lrc->step_row[k] : 0;
-    hipLaunchKernelGGL(lr_fold_kernel, dim3(ceil_div((int)P, 256), lrc->rows), dim3(256), 0, st, (const float*)lp.prod, (const float*)lp.g,
-                       (const float*)pl.lam, rows, K, T, (int)P, m_lo, m_hi, lrc->grad_out);
+    for (int k = 0; k < MI_POLICY_LR_MAX_STEPS; ++k) rows.row[k] = k < K && step.step_row ? step.step_row[k] : 0;
+    hipLaunchKernelGGL(lr_fold_kernel, dim3(ceil_div((int)P, 256), step.rows), dim3(256), 0, st, (const float*)lp.prod, (const float*)lp.g,
+                       (const float*)pl.lam, rows, K, T, (int)P, head_only ? (int)p->o_w1 : 0, head_only ? (int)p->o_w3 : 0, step.lr_grad_out);
     PCHK(p, hipGetLastError());
   }
   return MI_OK;
@@ -1187,9 +1264,13 @@ extern "C" int mi_policy_meta_batch(mi_policy* p, void* stream, const float* the
                                     float inner_lr, int head_only, int second_order, int with_grad, float* loss_out,
                                     float* theta_out, float* grad_out, void* workspace, size_t workspace_bytes) {
   if (loss_kind == MI_PLOSS_DICE) return pfail(p, MI_ERR_ARG, "MI_PLOSS_DICE needs the episode-end flags: call mi_policy_meta_batch_dones");
-  return policy_meta_batch_impl(p, stream, theta, steps, step_batch, step_new_old, n_batches, s_states, s_actions, s_adv, s_count, nullptr,
-                                q_states, q_actions, q_adv, q_count, nullptr, tasks, batch, loss_kind, clip, inner_lr, nullptr, head_only,
-                                second_order, with_grad, loss_out, theta_out, grad_out, workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.theta = theta; c.steps = steps; c.step_batch = step_batch; c.step_new_old = step_new_old; c.n_batches = n_batches;
+  c.sup = {s_states, s_actions, s_adv, s_count, nullptr}; c.qry = {q_states, q_actions, q_adv, q_count, nullptr}; c.tasks = tasks; c.batch = batch;
+  c.loss_kind = loss_kind; c.clip = clip; c.head_only = head_only; c.second_order = second_order; c.with_grad = with_grad;
+  c.loss_out = loss_out; c.theta_out = theta_out; c.grad_out = grad_out; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.step.lr = inner_lr;
+  return policy_meta_batch_impl(p, c);
 }
 // The same with the replays' episode-end flags (cherry `dones`: s_done [n_batches, tasks, batch], q_done [tasks, batch]; 1 at
 // the last step of every episode): required by MI_PLOSS_DICE, ignored by the other losses.
@@ -1200,9 +1281,13 @@ extern "C" int mi_policy_meta_batch_dones(mi_policy* p, void* stream, const floa
                                           int tasks, int batch, int loss_kind, float clip, float inner_lr, int head_only,
                                           int second_order, int with_grad, float* loss_out, float* theta_out, float* grad_out,
                                           void* workspace, size_t workspace_bytes) {
-  return policy_meta_batch_impl(p, stream, theta, steps, step_batch, step_new_old, n_batches, s_states, s_actions, s_adv, s_count, s_done,
-                                q_states, q_actions, q_adv, q_count, q_done, tasks, batch, loss_kind, clip, inner_lr, nullptr, head_only,
-                                second_order, with_grad, loss_out, theta_out, grad_out, workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.theta = theta; c.steps = steps; c.step_batch = step_batch; c.step_new_old = step_new_old; c.n_batches = n_batches;
+  c.sup = {s_states, s_actions, s_adv, s_count, s_done}; c.qry = {q_states, q_actions, q_adv, q_count, q_done}; c.tasks = tasks; c.batch = batch;
+  c.loss_kind = loss_kind; c.clip = clip; c.head_only = head_only; c.second_order = second_order; c.with_grad = with_grad;
+  c.loss_out = loss_out; c.theta_out = theta_out; c.grad_out = grad_out; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.step.lr = inner_lr;
+  return policy_meta_batch_impl(p, c);
 }
 // The step-size-vector form (include/mi_maml.h): the same implementation with lr_vec; every check of its own comes before any HIP call.
 extern "C" int mi_policy_meta_batch_lr(mi_policy* p, void* stream, const float* theta, int steps, const int32_t* step_batch,
@@ -1212,24 +1297,16 @@ extern "C" int mi_policy_meta_batch_lr(mi_policy* p, void* stream, const float* 
                                        const float* q_done, int tasks, int batch, int loss_kind, float clip, const float* lr_vec, int lr_rows,
                                        int head_only, int second_order, int with_grad, float* loss_out, float* theta_out, float* grad_out,
                                        float* lr_grad_out, void* workspace, size_t workspace_bytes) {
-  const std::string fn = "mi_policy_meta_batch_lr: ";
-  if (!p) return pfail(nullptr, MI_ERR_ARG, fn + "null policy handle");
-  if (!lr_vec) return pfail(p, MI_ERR_ARG, fn + "lr_vec is NULL");
-  if (lr_rows < 1 || lr_rows > MI_POLICY_LR_MAX_ROWS)
-    return pfail(p, MI_ERR_ARG, fn + "lr_rows " + std::to_string(lr_rows) + " (must be 1.." + std::to_string(MI_POLICY_LR_MAX_ROWS) + ")");
-  if (tasks < 1) return pfail(p, MI_ERR_ARG, fn + "tasks " + std::to_string(tasks) + " (must be >= 1)");
-  if (batch < 1) return pfail(p, MI_ERR_ARG, fn + "batch " + std::to_string(batch) + " (must be >= 1)");
-  if (steps < 0 || steps > MI_POLICY_LR_MAX_STEPS)
-    return pfail(p, MI_ERR_ARG, fn + "steps " + std::to_string(steps) + " (must be 0.." + std::to_string(MI_POLICY_LR_MAX_STEPS) + ")");
-  for (int k = 0; step_lr_row && k < steps; ++k)
-    if (step_lr_row[k] < 0 || step_lr_row[k] >= lr_rows)
-      return pfail(p, MI_ERR_ARG, fn + "step_lr_row[" + std::to_string(k) + "] " + std::to_string(step_lr_row[k]) + " (must be 0.." +
-                                      std::to_string(lr_rows - 1) + ")");
-  if (lr_grad_out && !with_grad) return pfail(p, MI_ERR_ARG, fn + "lr_grad_out given but with_grad == 0");
-  const LrCall lrc{lr_vec, lr_rows, step_lr_row, lr_grad_out, "mi_policy_meta_batch_lr"};
-  return policy_meta_batch_impl(p, stream, theta, steps, step_batch, step_new_old, n_batches, s_states, s_actions, s_adv, s_count, s_done,
-                                q_states, q_actions, q_adv, q_count, q_done, tasks, batch, loss_kind, clip, 0.f, &lrc, head_only,
-                                second_order, with_grad, loss_out, theta_out, grad_out, workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.theta = theta; c.steps = steps; c.step_batch = step_batch; c.step_new_old = step_new_old; c.n_batches = n_batches;
+  c.sup = {s_states, s_actions, s_adv, s_count, s_done}; c.qry = {q_states, q_actions, q_adv, q_count, q_done}; c.tasks = tasks; c.batch = batch;
+  c.loss_kind = loss_kind; c.clip = clip; c.head_only = head_only; c.second_order = second_order; c.with_grad = with_grad;
+  c.loss_out = loss_out; c.theta_out = theta_out; c.grad_out = grad_out; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.step.vec = lr_vec; c.step.rows = lr_rows; c.step.step_row = step_lr_row; c.step.lr_grad_out = lr_grad_out; c.step.fn = "mi_policy_meta_batch_lr";
+  int rc = check_table(p, c.step, steps, META_STEPS, tasks, batch);
+  if (rc) return rc;
+  if (lr_grad_out && !with_grad) return pfail(p, MI_ERR_ARG, c.step.prefix() + "lr_grad_out given but with_grad == 0");
+  return policy_meta_batch_impl(p, c);
 }
 
 // =====================================================================================================================
@@ -1242,10 +1319,7 @@ struct UpdatePlan { StepSet s; float *g, *loss_e, *oldlp; size_t bytes; };
 static void update_plan(const mi_policy* p, void* ws, int T, int B, int E, UpdatePlan& pl) {
   PBump b{reinterpret_cast<char*>(ws), 0};
   const size_t TB = (size_t)T * B, TP = (size_t)T * p->P;
-  StepSet& s = pl.s;
-  s.a.h1 = b.f(TB * p->H1); s.a.h2 = b.f(TB * p->H2); s.a.mu = b.f(TB * p->A);
-  s.dmu = b.f(TB * p->A); s.d2 = b.f(TB * p->H2); s.d1 = b.f(TB * p->H1); s.pre2 = b.f(TB * p->H2); s.pre1 = b.f(TB * p->H1);
-  s.coef = b.f(TB); s.coef2 = b.f(TB);
+  step_set_plan(p, b, TB, pl.s);
   pl.g = b.f(TP); pl.loss_e = b.f((size_t)E * T); pl.oldlp = b.f(TB);
   pl.bytes = align_up(b.off, 256);
 }
@@ -1272,52 +1346,41 @@ extern "C" int mi_policy_update_workspace_bytes(const mi_policy* p, int tasks, i
   *bytes = pl.bytes;
   return MI_OK;
 }
-// vector: mi_policy_update_lr -- the step of every epoch is lr_vec [P] (one row of the step-size table) in place of the number lr
-static int policy_update_impl(mi_policy* p, const std::string& fn, void* stream, const float* theta, size_t tstride, const float* states,
-                              const float* actions, const float* adv, const int32_t* count, const float* done, int tasks, int batch,
-                              int loss_kind, int epochs, float clip, float lr, bool vector, const float* lr_vec, int head_only,
-                              float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
-  int rc = update_args(p, fn, tasks, batch, epochs);
-  if (rc) return rc;
-  if (vector && !lr_vec) return pfail(p, MI_ERR_ARG, fn + "lr_vec is NULL");
-  if (!theta || !states || !actions || !adv || !theta_out || !workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
-  if (loss_kind != MI_PLOSS_A2C && loss_kind != MI_PLOSS_PPO && loss_kind != MI_PLOSS_DICE)
-    return pfail(p, MI_ERR_ARG, fn + "loss_kind " + std::to_string(loss_kind) + " (must be MI_PLOSS_A2C, MI_PLOSS_PPO or MI_PLOSS_DICE)");
-  if (loss_kind == MI_PLOSS_DICE && !done)
+// c.sup: the one replay; c.steps: the epochs; the step of every epoch is the number, or (mi_policy_update_lr) row 0 of a one-row table
+static int policy_update_impl(mi_policy* p, const PolicyCall& c) {
+  const std::string fn = c.step.prefix();
+  const int T = c.tasks, B = c.batch;
+  int rc = MI_OK;
+  if (!c.theta || !c.sup.states || !c.sup.actions || !c.sup.adv || !c.theta_out || !c.workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
+  if (c.loss_kind != MI_PLOSS_A2C && c.loss_kind != MI_PLOSS_PPO && c.loss_kind != MI_PLOSS_DICE)
+    return pfail(p, MI_ERR_ARG, fn + "loss_kind " + std::to_string(c.loss_kind) + " (must be MI_PLOSS_A2C, MI_PLOSS_PPO or MI_PLOSS_DICE)");
+  if (c.loss_kind == MI_PLOSS_DICE && !c.sup.done)
     return pfail(p, MI_ERR_ARG, fn + "loss_kind MI_PLOSS_DICE needs the episode-end flags (done is NULL)");
-  if (tstride != 0 && tstride != p->P)
-    return pfail(p, MI_ERR_ARG, fn + "tstride " + std::to_string(tstride) + " (must be 0 or P = " + std::to_string(p->P) + ")");
-  if (tstride == 0 && tasks > 1 && theta == theta_out)
+  if (c.tstride != 0 && c.tstride != p->P)
+    return pfail(p, MI_ERR_ARG, fn + "tstride " + std::to_string(c.tstride) + " (must be 0 or P = " + std::to_string(p->P) + ")");
+  if (c.tstride == 0 && T > 1 && c.theta == c.theta_out)
     return pfail(p, MI_ERR_ARG, fn + "theta_out may alias theta only with tstride = P");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, B = batch;
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
   const size_t P = p->P;
   UpdatePlan pl;
-  update_plan(p, workspace, T, B, epochs, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(pl.bytes));
+  update_plan(p, c.workspace, T, B, c.steps, pl);
+  if (pl.bytes > c.workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(pl.bytes));
   const dim3 pgrid(ceil_div((int)P, 256), T);
-  hipLaunchKernelGGL(axpy_bcast_kernel, pgrid, dim3(256), 0, st, theta, tstride, pl.g, 0.f, (int)P, theta_out);      // u_0
+  hipLaunchKernelGGL(axpy_bcast_kernel, pgrid, dim3(256), 0, st, c.theta, c.tstride, pl.g, 0.f, (int)P, c.theta_out);      // u_0
   PCHK(p, hipGetLastError());
-  if (loss_kind == MI_PLOSS_PPO) {                            // old log-probs once, at u_0 (rl.py:280-290)
-    rc = meta_old_logp(p, st, T, B, pl.s, theta_out, states, actions, count, pl.oldlp);
+  if (c.loss_kind == MI_PLOSS_PPO) {                            // old log-probs once, at u_0 (rl.py:280-290)
+    rc = meta_old_logp(p, st, T, B, pl.s, c.theta_out, c.sup.states, c.sup.actions, c.sup.count, pl.oldlp);
     if (rc) return rc;
   }
-  for (int e = 0; e < epochs; ++e) {
-    rc = meta_primal(p, st, T, B, clip, pl.s, theta_out, P, states, actions, adv, count, loss_kind, pl.oldlp, 0, pl.g,
-                     pl.loss_e + (size_t)e * T, done);
+  for (int e = 0; e < c.steps; ++e) {
+    rc = meta_primal(p, st, T, B, c.clip, pl.s, c.theta_out, P, c.sup.states, c.sup.actions, c.sup.adv, c.sup.count, c.loss_kind, pl.oldlp, 0, pl.g,
+                     pl.loss_e + (size_t)e * T, c.sup.done);
     if (rc) return rc;
-    if (vector) {                                             // the head mask folded into the advance, as in mi_policy_meta_batch_lr
-      hipLaunchKernelGGL(lr_advance_kernel, pgrid, dim3(256), 0, st, (const float*)theta_out, P, (const float*)pl.g, lr_vec, (int)P,
-                         head_only ? (int)p->o_w1 : 0, head_only ? (int)p->o_w3 : 0, theta_out);
-    } else {
-      if (head_only)
-        hipLaunchKernelGGL(head_mask_kernel, pgrid, dim3(256), 0, st, pl.g, (int)P, (int)p->o_w1, (int)p->o_w3);
-      hipLaunchKernelGGL(axpy_bcast_kernel, pgrid, dim3(256), 0, st, theta_out, P, pl.g, lr, (int)P, theta_out);   // in place, elementwise
-    }
-    PCHK(p, hipGetLastError());
+    rc = step_advance(p, st, T, c.step, 0, c.head_only != 0, false, c.theta_out, P, pl.g, c.theta_out);      // in place, elementwise
+    if (rc) return rc;
   }
-  if (loss_out) {
-    hipLaunchKernelGGL(update_loss_transpose_kernel, dim3(ceil_div(epochs * T, 256)), dim3(256), 0, st, pl.loss_e, epochs, T, loss_out);
+  if (c.loss_out) {
+    hipLaunchKernelGGL(update_loss_transpose_kernel, dim3(ceil_div(c.steps * T, 256)), dim3(256), 0, st, pl.loss_e, c.steps, T, c.loss_out);
     PCHK(p, hipGetLastError());
   }
   return MI_OK;
@@ -1326,15 +1389,26 @@ extern "C" int mi_policy_update(mi_policy* p, void* stream, const float* theta, 
                                 const float* actions, const float* adv, const int32_t* count, const float* done, int tasks,
                                 int batch, int loss_kind, int epochs, float clip, float lr, int head_only, float* theta_out,
                                 float* loss_out, void* workspace, size_t workspace_bytes) {
-  return policy_update_impl(p, "mi_policy_update: ", stream, theta, tstride, states, actions, adv, count, done, tasks, batch, loss_kind,
-                            epochs, clip, lr, false, nullptr, head_only, theta_out, loss_out, workspace, workspace_bytes);
+  int rc = update_args(p, "mi_policy_update: ", tasks, batch, epochs);
+  if (rc) return rc;
+  PolicyCall c{};
+  c.stream = stream; c.theta = theta; c.tstride = tstride; c.sup = {states, actions, adv, count, done}; c.tasks = tasks; c.batch = batch;
+  c.loss_kind = loss_kind; c.steps = epochs; c.clip = clip; c.head_only = head_only; c.theta_out = theta_out; c.loss_out = loss_out;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.step.lr = lr; c.step.fn = "mi_policy_update";
+  return policy_update_impl(p, c);
 }
 extern "C" int mi_policy_update_lr(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
                                    const float* actions, const float* adv, const int32_t* count, const float* done, int tasks,
                                    int batch, int loss_kind, int epochs, float clip, const float* lr_vec, int head_only,
                                    float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
-  return policy_update_impl(p, "mi_policy_update_lr: ", stream, theta, tstride, states, actions, adv, count, done, tasks, batch, loss_kind,
-                            epochs, clip, 0.f, true, lr_vec, head_only, theta_out, loss_out, workspace, workspace_bytes);
+  int rc = update_args(p, "mi_policy_update_lr: ", tasks, batch, epochs);
+  if (rc) return rc;
+  PolicyCall c{};
+  c.stream = stream; c.theta = theta; c.tstride = tstride; c.sup = {states, actions, adv, count, done}; c.tasks = tasks; c.batch = batch;
+  c.loss_kind = loss_kind; c.steps = epochs; c.clip = clip; c.head_only = head_only; c.theta_out = theta_out; c.loss_out = loss_out;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.step.vec = lr_vec; c.step.rows = 1; c.step.fn = "mi_policy_update_lr";
+  rc = check_table(p, c.step, 1, ONE_STEP, tasks, batch);
+  return rc ? rc : policy_update_impl(p, c);
 }
 
 // =====================================================================================================================
@@ -1379,15 +1453,6 @@ extern "C" int mi_trpo_steps_workspace_bytes(const mi_policy* p, int tasks, int 
   return MI_OK;
 }
 
-// the support replays: [K][T][B][.] stacks, and replay k of them
-struct SupStack { const float *states, *actions, *adv; const int32_t* count; };
-struct SupRef { const float *xs, *as, *adv; const int32_t* cn; };
-static SupRef sup_at(const mi_policy* p, const SupStack& s, int T, int B, int k) {
-  const size_t TB = (size_t)T * B;
-  return {s.states + k * TB * p->S, s.actions + k * TB * p->A, s.adv ? s.adv + k * TB : nullptr,
-          s.count ? s.count + (size_t)k * T : nullptr};
-}
-
 // theta_k sits at pl.theta + k T P.  theta_0 is shared by all tasks: one row, read with stride 0 (per-task rows of the same values
 // would cost the dense kernels their shared weight reads); from k = 1 on every task has its own row.
 static size_t theta_stride(const mi_policy* p, int k) { return k == 0 ? 0 : p->P; }
@@ -1410,42 +1475,23 @@ static int hvp_step(mi_policy* p, hipStream_t st, MetaPlan& pl, StepSet& s, int 
 }
 // x_t <- (I - lr H_k) x_t through the updates, in place on x [T][P] (pl.hv is scratch): k = 0 .. K-1 is J_t x, the tangent
 // recursion; transpose walks k = K-1 .. 0 and is J_t^T x, the adjoint recursion (every H_k is symmetric: only the order differs).
-// With a step-size table (lrc; d_k = the row of update k) the two are different operations:
-//   tangent    x <- x - d_k (.) (H_k x)                          (lr_advance_kernel in place)
-//   adjoint    x <- x - H_k (d_k (.) x)                          the tangent pass is driven with dir = d_k (.) x (in pl.g, idle once the
-//              inner updates are done), and the launch that finishes x for update k also writes the dir of update k - 1 (lr_adjoint_kernel)
-static const float* trpo_lr_row(const LrCall* lrc, int k, size_t P) { return lrc->vec + (size_t)(lrc->step_row ? lrc->step_row[k] : 0) * P; }
-static int jac_apply(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupStack& sup, int T, int B, int K, bool transpose, float lr,
-                     const LrCall* lrc, float* x) {
+// With a step-size table (d_k = the row of update k) the two are different operations:
+//   tangent    x <- x - d_k (.) (H_k x)                          (step_advance in place)
+//   adjoint    x <- x - H_k (d_k (.) x)                          (AdjointWalk; dir = d_k (.) x in pl.g, idle once the inner updates are done)
+static int jac_apply(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupStack& sup, int T, int B, int K, bool transpose,
+                     const PolicyStep& step, float* x) {
   const size_t P = p->P, TP = (size_t)T * P;
-  if (lrc) {
-    const dim3 pgrid(ceil_div((int)P, 256), T);
-    const float* none = nullptr;
-    if (transpose) {
-      hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)x, none, none, trpo_lr_row(lrc, K - 1, P), none, (int)P, 0, 0,
-                         x, pl.g, (float*)nullptr);
-      PCHK(p, hipGetLastError());
-    }
-    for (int i = 0; i < K; ++i) {
-      const int k = transpose ? K - 1 - i : i;
-      int rc = hvp_step(p, st, pl, pl.st[k], T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), sup_at(p, sup, T, B, k),
-                        transpose ? pl.g : x, pl.hv);
-      if (rc) return rc;
-      if (transpose)
-        hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)x, (const float*)pl.hv, none,
-                           k > 0 ? trpo_lr_row(lrc, k - 1, P) : none, none, (int)P, 0, 0, x, pl.g, (float*)nullptr);
-      else
-        hipLaunchKernelGGL(lr_advance_kernel, pgrid, dim3(256), 0, st, (const float*)x, P, (const float*)pl.hv, trpo_lr_row(lrc, k, P), (int)P, 0, 0, x);
-      PCHK(p, hipGetLastError());
-    }
-    return MI_OK;
-  }
+  const AdjointWalk adj{p, st, T, step, false, false};
+  int rc = transpose ? adj.seed(K, x, nullptr, pl.g, nullptr) : MI_OK;
+  if (rc) return rc;
   for (int i = 0; i < K; ++i) {
     const int k = transpose ? K - 1 - i : i;
-    int rc = hvp_step(p, st, pl, pl.st[k], T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), sup_at(p, sup, T, B, k), x, pl.hv);
+    const float* v = x;
+    if (transpose && (rc = adj.drive(x, pl.g, &v))) return rc;
+    rc = hvp_step(p, st, pl, pl.st[k], T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), sup_at(p, sup, T, B, k), v, pl.hv);
     if (rc) return rc;
-    hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, x, P, pl.hv, lr, (int)P, x);
-    PCHK(p, hipGetLastError());
+    rc = transpose ? adj.back(k, x, pl.hv, nullptr, nullptr, x, pl.g, nullptr) : step_advance(p, st, T, step, k, false, false, x, P, pl.hv, x);
+    if (rc) return rc;
   }
   return MI_OK;
 }
@@ -1468,20 +1514,19 @@ static SweepArgs sweep_hvp_args(const mi_policy* p, const StepsPlan& pl, int T, 
   hs.d2 = s.d2; hs.count = r.cn; hs.theta = pl.theta; hs.tstride = 0;
   return hs;
 }
-// lrv: the row [P] of the step-size table the one update reads (NULL: the number lr)
-static FoldArgs fold_base(const mi_policy* p, const StepsPlan& pl, int T, float lr, const float* lrv = nullptr) {
+// the fold takes the number, or (lrv) the row [P] of the step-size table the one update reads
+static FoldArgs fold_base(const mi_policy* p, const StepsPlan& pl, int T, const PolicyStep& step) {
   FoldArgs f{};
-  f.partial = pl.partial; f.slots = pl.slots; f.spt = pl.spt; f.spw = pl.spw; f.T = T; f.P = (int)p->P; f.pitch = (int)p->P + 2; f.lr = lr;
-  f.lrv = lrv;
+  f.partial = pl.partial; f.slots = pl.slots; f.spt = pl.spt; f.spw = pl.spw; f.T = T; f.P = (int)p->P; f.pitch = (int)p->P + 2; f.lr = step.lr;
+  f.lrv = step.row(0);
   f.o_sigma = (int)p->o_sigma; f.A = p->A;
   return f;
 }
 
 // Inner update and query pass as two PRIMAL sweeps (forward + loss + backward of a pass in one launch) instead of ~22 per-layer
 // launches: theta_1, loss_t / kl_t and, with want_grad, lam = grad S_t(theta_1).
-static int fused_surrogate(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& r, const float* q_states, const float* q_actions,
-                           const float* q_adv, const int32_t* q_count, const float* old_loc, const float* old_scale, int T, int B,
-                           float inner_lr, const float* lrv, bool want_grad) {
+static int fused_surrogate(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& r, const PolicyCall& c, bool want_grad) {
+  const int T = c.tasks, B = c.batch;
   const size_t P = p->P;
   float* th1 = pl.theta + (size_t)T * P;
   // The pass lands where the per-layer loop keeps it (activations, dmu, d2, coef of StepSet 0), so a per-layer product or the
@@ -1492,40 +1537,39 @@ static int fused_surrogate(mi_policy* p, hipStream_t st, StepsPlan& pl, const Su
   sp.x = r.xs; sp.act = r.as; sp.adv = r.adv; sp.count = r.cn; sp.theta = pl.theta; sp.tstride = 0; sp.surrogate = 0;
   sp.h1_out = s.a.h1; sp.h2_out = s.a.h2; sp.mu_out = s.a.mu; sp.dmu_out = s.dmu; sp.d2_out = s.d2; sp.coef_out = s.coef;
   PCHK(p, launch_policy_sweep(st, sp, pl.sweep_grid, SW_PRIMAL));
-  FoldArgs f = fold_base(p, pl, T, inner_lr, lrv);
+  FoldArgs f = fold_base(p, pl, T, c.step);
   f.mode = 0; f.v = pl.theta; f.out = th1;                        // theta_1 = theta - lr g_t   (vector: - d (.) g_t)
   PCHK(p, launch_policy_sweep_fold(st, f, T));
   SweepArgs sq = sweep_base(p, pl, T, B);
-  sq.x = q_states; sq.act = q_actions; sq.adv = q_adv; sq.count = q_count; sq.theta = th1; sq.tstride = P; sq.surrogate = 1;
-  sq.old_loc = old_loc; sq.old_scale = old_scale; sq.fwd_only = want_grad ? 0 : 1;
+  sq.x = c.qry.states; sq.act = c.qry.actions; sq.adv = c.qry.adv; sq.count = c.qry.count; sq.theta = th1; sq.tstride = P; sq.surrogate = 1;
+  sq.old_loc = c.old_loc; sq.old_scale = c.old_scale; sq.fwd_only = want_grad ? 0 : 1;
   sq.h1_out = pl.q.a.h1; sq.h2_out = pl.q.a.h2; sq.mu_out = pl.q.a.mu;
   PCHK(p, launch_policy_sweep(st, sq, pl.sweep_grid, SW_PRIMAL));
   f.mode = 3; f.out = want_grad ? pl.lam : nullptr; f.loss_t = pl.loss_t; f.kl_t = pl.kl_t;      // per-task loss / KL
-  f.dout = want_grad && lrv ? pl.g : nullptr;                     // d (.) lam: the direction of the gradient's HVP sweep
+  f.dout = want_grad && c.step.table() ? pl.g : nullptr;          // d (.) lam: the direction of the gradient's HVP sweep
   PCHK(p, launch_policy_sweep_fold(st, f, T));
   return MI_OK;
 }
 
 // Fvp(v) as three sweeps + three folds:  A: u_t = v - lr H_t v,  B: w_t = F_t u_t,  C: out = mean_t (w_t - lr H_t w_t) + damping v
-// With a step row d (lrv):  A: u_t = v - d (.) H_t v,  B: w_t = F_t u_t and d (.) w_t (same fold, into pl.g),  C: sweep along d (.) w_t,
+// With a step row d:  A: u_t = v - d (.) H_t v,  B: w_t = F_t u_t and d (.) w_t (same fold, into pl.g),  C: sweep along d (.) w_t,
 // out = mean_t (w_t - H_t (d (.) w_t)) + damping v -- the same six launches.
-static int fused_fvp(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& r, const float* q_states, const int32_t* q_count, int T,
-                     int B, float inner_lr, const float* lrv, float damping, const float* v, float* out) {
-  const int P = (int)p->P;
+static int fused_fvp(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& r, const PolicyCall& c) {
+  const int T = c.tasks, B = c.batch, P = (int)p->P;
   float *th1 = pl.theta + (size_t)T * P, *u = pl.vmask, *w = pl.lam, *tmp = pl.hv;
   SweepArgs hs = sweep_hvp_args(p, pl, T, B, r);
-  FoldArgs f = fold_base(p, pl, T, inner_lr, lrv);
-  f.v = v; f.damping = damping;
-  hs.dir = v; hs.dstride = 0;
+  FoldArgs f = fold_base(p, pl, T, c.step);
+  f.v = c.v; f.damping = c.damping;
+  hs.dir = c.v; hs.dstride = 0;
   PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
   f.mode = 0; f.out = u;
   PCHK(p, launch_policy_sweep_fold(st, f, T));
   SweepArgs fs = sweep_base(p, pl, T, B);              // over the query pass at theta_1
-  fs.x = q_states; fs.h1 = pl.q.a.h1; fs.h2 = pl.q.a.h2; fs.count = q_count; fs.theta = th1; fs.tstride = P; fs.dir = u; fs.dstride = P;
+  fs.x = c.qry.states; fs.h1 = pl.q.a.h1; fs.h2 = pl.q.a.h2; fs.count = c.qry.count; fs.theta = th1; fs.tstride = P; fs.dir = u; fs.dstride = P;
   PCHK(p, launch_policy_sweep(st, fs, pl.sweep_grid, SW_FISHER));
-  f.mode = 1; f.out = w; f.thetap = th1; f.u = u; f.dout = lrv ? pl.g : nullptr;
+  f.mode = 1; f.out = w; f.thetap = th1; f.u = u; f.dout = c.step.table() ? pl.g : nullptr;
   PCHK(p, launch_policy_sweep_fold(st, f, T));
-  hs.dir = lrv ? pl.g : w; hs.dstride = P;
+  hs.dir = c.step.table() ? pl.g : w; hs.dstride = P;
   PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
   f.mode = 2; f.out = tmp; f.w = w;
   if (!p->fold_counters) {               // (once per policy object: the fold leaves the counters zero again)
@@ -1539,91 +1583,80 @@ static int fused_fvp(mi_policy* p, hipStream_t st, StepsPlan& pl, const SupRef& 
     // "last" workgroup that can no longer exist.  One stream per mi_policy at a time (include/mi_maml.h).
     if (p->fold_dirty) PCHK(p, hipMemsetAsync(p->fold_counters, 0, (size_t)ceil_div(P, 256) * sizeof(unsigned), st));
     p->fold_dirty = true;
-    f.counter = p->fold_counters; f.mean_out = out; f.inv_T = 1.f / (float)T;
+    f.counter = p->fold_counters; f.mean_out = c.out; f.inv_T = 1.f / (float)T;
     PCHK(p, launch_policy_sweep_fold(st, f, T));
     p->fold_dirty = false;
     return MI_OK;
   }
   PCHK(p, launch_policy_sweep_fold(st, f, T));
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, tmp, T, P, 1.f / (float)T, v, damping, out);
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, tmp, T, P, 1.f / (float)T, c.v, c.damping, c.out);
   PCHK(p, hipGetLastError());
   return MI_OK;
 }
 
 // meta_surrogate_loss (rl.py:441-473) at theta for `tasks` tasks with `steps` second-order inner updates on the support replays
 // ([steps][tasks][batch][.]), and optionally its gradient (rl.py:413-416).  Leaves everything the products need in `workspace`.
-// lrc: the step-size-vector entries (mi_trpo_*_steps_lr), whose texts name the entry; NULL: the scalar entries, launches and texts as they were.
-static int trpo_surrogate_impl(mi_policy* p, void* stream, const float* theta, int steps, const float* s_states,
-                               const float* s_actions, const float* s_adv, const int32_t* s_count, const float* q_states,
-                               const float* q_actions, const float* q_adv, const int32_t* q_count, const float* old_loc,
-                               const float* old_scale, int tasks, int batch, float inner_lr, const LrCall* lrc, float* loss_out,
-                               float* kl_out, float* grad_out, void* workspace, size_t workspace_bytes) {
-  const std::string fn = lrc ? std::string(lrc->fn) + ": " : std::string();
-  if (!p || !theta || !s_states || !s_actions || !s_adv || !q_states || !q_actions || !q_adv || !old_loc || !old_scale || !loss_out ||
-      !kl_out || !workspace || steps < 1)
+static int trpo_surrogate_impl(mi_policy* p, const PolicyCall& c) {
+  const std::string fn = c.step.prefix();
+  if (!p || !c.theta || !c.sup.states || !c.sup.actions || !c.sup.adv || !c.qry.states || !c.qry.actions || !c.qry.adv || !c.old_loc || !c.old_scale || !c.loss_out ||
+      !c.kl_out || !c.workspace || c.steps < 1)
     return pfail(p, MI_ERR_ARG, fn + "null argument");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, B = batch, K = steps;
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+  const int T = c.tasks, B = c.batch, K = c.steps;
   const size_t P = p->P, TP = (size_t)T * P;
   StepsPlan pl;
-  steps_plan(p, workspace, T, B, K, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(pl.bytes));
-  const SupStack sup{s_states, s_actions, s_adv, s_count};
+  steps_plan(p, c.workspace, T, B, K, pl);
+  if (pl.bytes > c.workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(pl.bytes));
   const bool fused = fused_steps(p, K);
   float* thK = pl.theta + (size_t)K * TP;
   int rc = MI_OK;
   // theta_0 (one row).  The products take no theta: they read this copy.
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), 1), dim3(256), 0, st, theta, (size_t)0, pl.g, 0.f, (int)P, pl.theta);
+  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), 1), dim3(256), 0, st, c.theta, (size_t)0, pl.g, 0.f, (int)P, pl.theta);
   PCHK(p, hipGetLastError());
   if (fused) {
-    rc = fused_surrogate(p, st, pl, sup_at(p, sup, T, B, 0), q_states, q_actions, q_adv, q_count, old_loc, old_scale, T, B, inner_lr,
-                         lrc ? trpo_lr_row(lrc, 0, P) : nullptr, grad_out != nullptr);
+    rc = fused_surrogate(p, st, pl, sup_at(p, c.sup, T, B, 0), c, c.grad_out != nullptr);
     if (rc) return rc;
   } else {
     for (int k = 0; k < K; ++k) {                                 // trpo_update on support replay k (a2c loss, normalised advantages)
-      const SupRef r = sup_at(p, sup, T, B, k);
+      const SupRef r = sup_at(p, c.sup, T, B, k);
       float* th = pl.theta + (size_t)k * TP;
       const size_t ts = theta_stride(p, k);
       rc = meta_primal(p, st, T, B, 0.f, pl.st[k], th, ts, r.xs, r.as, r.adv, r.cn, MI_PLOSS_A2C, nullptr, 0, pl.g,
                        pl.hv /* step loss: unused */, nullptr);
       if (rc) return rc;
-      if (lrc)
-        hipLaunchKernelGGL(lr_advance_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, (const float*)th, ts, (const float*)pl.g,
-                           trpo_lr_row(lrc, k, P), (int)P, 0, 0, th + TP);
-      else
-        hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, th, ts, pl.g, inner_lr, (int)P, th + TP);
-      PCHK(p, hipGetLastError());
+      rc = step_advance(p, st, T, c.step, k, false, false, th, ts, pl.g, th + TP);
+      if (rc) return rc;
     }
-    rc = mlp_forward(p, st, T, B, q_states, thK, P, pl.q.a);
+    rc = mlp_forward(p, st, T, B, c.qry.states, thK, P, pl.q.a);
     if (rc) return rc;
     PCHK(p, hipMemsetAsync(pl.lam, 0, TP * sizeof(float), st));
     GaussArgs gq{};
-    gq.mu = pl.q.a.mu; gq.rho = thK + p->o_sigma; gq.rstride = P; gq.act = q_actions; gq.adv = q_adv; gq.count = q_count;
-    gq.old_loc = old_loc; gq.old_scale = old_scale; gq.coef = pl.q.coef; gq.dmu = pl.q.dmu; gq.drho = pl.lam + p->o_sigma;
+    gq.mu = pl.q.a.mu; gq.rho = thK + p->o_sigma; gq.rstride = P; gq.act = c.qry.actions; gq.adv = c.qry.adv; gq.count = c.qry.count;
+    gq.old_loc = c.old_loc; gq.old_scale = c.old_scale; gq.coef = pl.q.coef; gq.dmu = pl.q.dmu; gq.drho = pl.lam + p->o_sigma;
     gq.gstride = P; gq.loss = pl.loss_t; gq.kl = pl.kl_t; gq.B = B; gq.A = p->A; gq.mode = G_SURROGATE;
     PCHK(p, gauss(st, T, gq));
   }
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, pl.loss_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, loss_out);
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, pl.kl_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, kl_out);
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, pl.loss_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, c.loss_out);
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(1), dim3(64), 0, st, pl.kl_t, T, 1, 1.f / (float)T, (const float*)nullptr, 0.f, c.kl_out);
   PCHK(p, hipGetLastError());
-  if (!grad_out) return MI_OK;
+  if (!c.grad_out) return MI_OK;
   const float* gt = pl.lam;                                       // J_t^T grad S_t(theta_K)
   if (fused) {                                                    // one HVP sweep along lam_t + fold, instead of ~10 per-layer launches
-    SweepArgs hs = sweep_hvp_args(p, pl, T, B, sup_at(p, sup, T, B, 0));
-    hs.dir = lrc ? pl.g : pl.lam; hs.dstride = P;                 // (vector: d (.) lam, written by the fold that finished lam)
+    SweepArgs hs = sweep_hvp_args(p, pl, T, B, sup_at(p, c.sup, T, B, 0));
+    hs.dir = c.step.table() ? pl.g : pl.lam; hs.dstride = P;      // (vector: d (.) lam, written by the fold that finished lam)
     PCHK(p, launch_policy_sweep(st, hs, pl.sweep_grid, SW_HVP));
-    FoldArgs f = fold_base(p, pl, T, inner_lr, lrc ? trpo_lr_row(lrc, 0, P) : nullptr);
+    FoldArgs f = fold_base(p, pl, T, c.step);
     f.mode = 2; f.out = pl.hv; f.w = pl.lam;
     PCHK(p, launch_policy_sweep_fold(st, f, T));
     gt = pl.hv;
   } else {
-    rc = mlp_backward(p, st, T, B, q_states, thK, P, pl.q.a, pl.q.dmu, pl.q.d2, pl.q.d1, pl.lam);
+    rc = mlp_backward(p, st, T, B, c.qry.states, thK, P, pl.q.a, pl.q.dmu, pl.q.d2, pl.q.d1, pl.lam);
     if (rc) return rc;
-    rc = jac_apply(p, st, pl, sup, T, B, K, true, inner_lr, lrc, pl.lam);
+    rc = jac_apply(p, st, pl, c.sup, T, B, K, true, c.step, pl.lam);
     if (rc) return rc;
   }
   hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gt, T, (int)P, 1.f / (float)T,
-                     (const float*)nullptr, 0.f, grad_out);
+                     (const float*)nullptr, 0.f, c.grad_out);
   PCHK(p, hipGetLastError());
   return MI_OK;
 }
@@ -1632,33 +1665,21 @@ extern "C" int mi_trpo_surrogate_steps(mi_policy* p, void* stream, const float* 
                                        const float* q_actions, const float* q_adv, const int32_t* q_count, const float* old_loc,
                                        const float* old_scale, int tasks, int batch, float inner_lr, float* loss_out,
                                        float* kl_out, float* grad_out, void* workspace, size_t workspace_bytes) {
-  return trpo_surrogate_impl(p, stream, theta, steps, s_states, s_actions, s_adv, s_count, q_states, q_actions, q_adv, q_count, old_loc,
-                             old_scale, tasks, batch, inner_lr, nullptr, loss_out, kl_out, grad_out, workspace, workspace_bytes);
-}
-// The checks the step-size-vector entries make of their own arguments, before any HIP call (fn: the entry's name)
-static int trpo_lr_args(mi_policy* p, const char* name, const float* lr_vec, int lr_rows, const int32_t* step_lr_row, int steps, int tasks,
-                        int batch) {
-  const std::string fn = std::string(name) + ": ";
-  if (!p) return pfail(nullptr, MI_ERR_ARG, fn + "null policy handle");
-  if (!lr_vec) return pfail(p, MI_ERR_ARG, fn + "lr_vec is NULL");
-  if (lr_rows < 1 || lr_rows > MI_POLICY_LR_MAX_ROWS)
-    return pfail(p, MI_ERR_ARG, fn + "lr_rows " + std::to_string(lr_rows) + " (must be 1.." + std::to_string(MI_POLICY_LR_MAX_ROWS) + ")");
-  if (steps < 1) return pfail(p, MI_ERR_ARG, fn + "steps " + std::to_string(steps) + " (must be >= 1)");
-  if (tasks < 1) return pfail(p, MI_ERR_ARG, fn + "tasks " + std::to_string(tasks) + " (must be >= 1)");
-  if (batch < 1) return pfail(p, MI_ERR_ARG, fn + "batch " + std::to_string(batch) + " (must be >= 1)");
-  for (int k = 0; step_lr_row && k < steps; ++k)
-    if (step_lr_row[k] < 0 || step_lr_row[k] >= lr_rows)
-      return pfail(p, MI_ERR_ARG, fn + "step_lr_row[" + std::to_string(k) + "] " + std::to_string(step_lr_row[k]) + " (must be 0.." +
-                                      std::to_string(lr_rows - 1) + ")");
-  return MI_OK;
+  PolicyCall c{};
+  c.stream = stream; c.steps = steps; c.sup = {s_states, s_actions, s_adv, s_count, nullptr}; c.qry = {q_states, q_actions, q_adv, q_count, nullptr};
+  c.tasks = tasks; c.batch = batch; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.theta = theta; c.old_loc = old_loc; c.old_scale = old_scale; c.loss_out = loss_out; c.kl_out = kl_out; c.grad_out = grad_out; c.step.lr = inner_lr;
+  return trpo_surrogate_impl(p, c);
 }
 extern "C" int mi_policy_adapt_lr(mi_policy* p, void* stream, const float* theta, size_t tstride, const float* states,
                                   const float* actions, const float* adv, const int32_t* count, int tasks, int batch, const float* lr_vec,
                                   int head_only, float* theta_out, float* loss_out, void* workspace, size_t workspace_bytes) {
-  int rc = trpo_lr_args(p, "mi_policy_adapt_lr", lr_vec, 1, nullptr, 1, tasks, batch);
-  if (rc) return rc;
-  return policy_adapt_impl(p, "mi_policy_adapt_lr: ", stream, theta, tstride, states, actions, adv, count, tasks, batch, 0.f, lr_vec, head_only,
-                           theta_out, loss_out, workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.theta = theta; c.tstride = tstride; c.sup = {states, actions, adv, count, nullptr}; c.tasks = tasks; c.batch = batch;
+  c.head_only = head_only; c.theta_out = theta_out; c.loss_out = loss_out; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.step.vec = lr_vec; c.step.rows = 1; c.step.fn = "mi_policy_adapt_lr";
+  const int rc = check_table(p, c.step, 1, ONE_STEP, tasks, batch);
+  return rc ? rc : policy_adapt_impl(p, c);
 }
 // The fused sweeps and the per-layer recursions take their extra direction d (.) x in the plan's g slot, idle once the inner updates are
 // done: the MAML-TRPO plan does not grow.
@@ -1672,68 +1693,69 @@ extern "C" int mi_trpo_surrogate_steps_lr(mi_policy* p, void* stream, const floa
                                           const float* old_scale, int tasks, int batch, const float* lr_vec, int lr_rows,
                                           const int32_t* step_lr_row, float* loss_out, float* kl_out, float* grad_out, void* workspace,
                                           size_t workspace_bytes) {
-  int rc = trpo_lr_args(p, "mi_trpo_surrogate_steps_lr", lr_vec, lr_rows, step_lr_row, steps, tasks, batch);
-  if (rc) return rc;
-  const LrCall lrc{lr_vec, lr_rows, step_lr_row, nullptr, "mi_trpo_surrogate_steps_lr"};
-  return trpo_surrogate_impl(p, stream, theta, steps, s_states, s_actions, s_adv, s_count, q_states, q_actions, q_adv, q_count, old_loc,
-                             old_scale, tasks, batch, 0.f, &lrc, loss_out, kl_out, grad_out, workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.steps = steps; c.sup = {s_states, s_actions, s_adv, s_count, nullptr}; c.qry = {q_states, q_actions, q_adv, q_count, nullptr};
+  c.tasks = tasks; c.batch = batch; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.theta = theta; c.old_loc = old_loc; c.old_scale = old_scale; c.loss_out = loss_out; c.kl_out = kl_out; c.grad_out = grad_out;
+  c.step.vec = lr_vec; c.step.rows = lr_rows; c.step.step_row = step_lr_row; c.step.fn = "mi_trpo_surrogate_steps_lr";
+  const int rc = check_table(p, c.step, steps, TRPO_STEPS, tasks, batch);
+  return rc ? rc : trpo_surrogate_impl(p, c);
 }
 
 // Fvp(v) = mean_t J_t^T F_t J_t v + damping v (cherry trpo.hessian_vector_product of the mean KL at the point where the adapted
 // policy equals the old policy, rl.py:417), at the theta of the preceding mi_trpo_surrogate_steps on this workspace and replays.
-static int trpo_fvp_impl(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
-                         const int32_t* s_count, const float* q_states, const int32_t* q_count, int tasks, int batch,
-                         float inner_lr, const LrCall* lrc, float damping, const float* v, float* out, void* workspace,
-                         size_t workspace_bytes) {
-  const std::string fn = lrc ? std::string(lrc->fn) + ": " : std::string();
-  if (!p || !s_states || !s_actions || !q_states || !v || !out || !workspace || steps < 1) return pfail(p, MI_ERR_ARG, fn + "null argument");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, B = batch, K = steps;
+static int trpo_fvp_impl(mi_policy* p, const PolicyCall& c) {
+  const std::string fn = c.step.prefix();
+  if (!p || !c.sup.states || !c.sup.actions || !c.qry.states || !c.v || !c.out || !c.workspace || c.steps < 1) return pfail(p, MI_ERR_ARG, fn + "null argument");
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+  const int T = c.tasks, B = c.batch, K = c.steps;
   const size_t P = p->P, TP = (size_t)T * P;
   StepsPlan pl;
-  steps_plan(p, workspace, T, B, K, pl);
-  if (pl.bytes > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small");
-  const SupStack sup{s_states, s_actions, nullptr, s_count};
-  if (fused_steps(p, K))
-    return fused_fvp(p, st, pl, sup_at(p, sup, T, B, 0), q_states, q_count, T, B, inner_lr, lrc ? trpo_lr_row(lrc, 0, P) : nullptr, damping, v, out);
+  steps_plan(p, c.workspace, T, B, K, pl);
+  if (pl.bytes > c.workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small");
+  if (fused_steps(p, K)) return fused_fvp(p, st, pl, sup_at(p, c.sup, T, B, 0), c);
   // u = J v   (pl.vmask holds u)
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (size_t)0, pl.g, 0.f, (int)P, pl.vmask);
+  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, c.v, (size_t)0, pl.g, 0.f, (int)P, pl.vmask);
   PCHK(p, hipGetLastError());
-  int rc = jac_apply(p, st, pl, sup, T, B, K, false, inner_lr, lrc, pl.vmask);
+  int rc = jac_apply(p, st, pl, c.sup, T, B, K, false, c.step, pl.vmask);
   if (rc) return rc;
   // w = F u at the query (Gaussian Fisher at new == old)
   float* thK = pl.theta + (size_t)K * TP;
-  rc = mlp_tangent_forward(p, st, T, B, q_states, thK, P, pl.q.a, pl.vmask, pl.ta);
+  rc = mlp_tangent_forward(p, st, T, B, c.qry.states, thK, P, pl.q.a, pl.vmask, pl.ta);
   if (rc) return rc;
   PCHK(p, hipMemsetAsync(pl.lam, 0, TP * sizeof(float), st));
   GaussArgs gf{};
   gf.mu = pl.q.a.mu; gf.mud = pl.ta.mu; gf.rho = thK + p->o_sigma; gf.rstride = P; gf.rhod = pl.vmask + p->o_sigma; gf.vstride = P;
-  gf.count = q_count; gf.dmu = pl.rdmu; gf.drho = pl.lam + p->o_sigma; gf.gstride = P; gf.B = B; gf.A = p->A; gf.mode = G_FISHER;
+  gf.count = c.qry.count; gf.dmu = pl.rdmu; gf.drho = pl.lam + p->o_sigma; gf.gstride = P; gf.B = B; gf.A = p->A; gf.mode = G_FISHER;
   PCHK(p, gauss(st, T, gf));
-  rc = mlp_backward(p, st, T, B, q_states, thK, P, pl.q.a, pl.rdmu, pl.r2, pl.r1, pl.lam);
+  rc = mlp_backward(p, st, T, B, c.qry.states, thK, P, pl.q.a, pl.rdmu, pl.r2, pl.r1, pl.lam);
   if (rc) return rc;
   // out = mean_t J^T w + damping v
-  rc = jac_apply(p, st, pl, sup, T, B, K, true, inner_lr, lrc, pl.lam);
+  rc = jac_apply(p, st, pl, c.sup, T, B, K, true, c.step, pl.lam);
   if (rc) return rc;
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.lam, T, (int)P, 1.f / (float)T, v, damping, out);
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, pl.lam, T, (int)P, 1.f / (float)T, c.v, c.damping, c.out);
   PCHK(p, hipGetLastError());
   return MI_OK;
 }
 extern "C" int mi_trpo_fvp_steps(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
                                  const int32_t* s_count, const float* q_states, const int32_t* q_count, int tasks, int batch,
                                  float inner_lr, float damping, const float* v, float* out, void* workspace, size_t workspace_bytes) {
-  return trpo_fvp_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, tasks, batch, inner_lr, nullptr, damping, v, out,
-                       workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.steps = steps; c.sup = {s_states, s_actions, nullptr, s_count, nullptr}; c.qry = {q_states, nullptr, nullptr, q_count, nullptr};
+  c.tasks = tasks; c.batch = batch; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.damping = damping; c.v = v; c.out = out;
+  c.step.lr = inner_lr;
+  return trpo_fvp_impl(p, c);
 }
 extern "C" int mi_trpo_fvp_steps_lr(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
                                     const int32_t* s_count, const float* q_states, const int32_t* q_count, int tasks, int batch,
                                     const float* lr_vec, int lr_rows, const int32_t* step_lr_row, float damping, const float* v, float* out,
                                     void* workspace, size_t workspace_bytes) {
-  int rc = trpo_lr_args(p, "mi_trpo_fvp_steps_lr", lr_vec, lr_rows, step_lr_row, steps, tasks, batch);
-  if (rc) return rc;
-  const LrCall lrc{lr_vec, lr_rows, step_lr_row, nullptr, "mi_trpo_fvp_steps_lr"};
-  return trpo_fvp_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, tasks, batch, 0.f, &lrc, damping, v, out, workspace,
-                       workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.steps = steps; c.sup = {s_states, s_actions, nullptr, s_count, nullptr}; c.qry = {q_states, nullptr, nullptr, q_count, nullptr};
+  c.tasks = tasks; c.batch = batch; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.damping = damping; c.v = v; c.out = out;
+  c.step.vec = lr_vec; c.step.rows = lr_rows; c.step.step_row = step_lr_row; c.step.fn = "mi_trpo_fvp_steps_lr";
+  const int rc = check_table(p, c.step, steps, TRPO_STEPS, tasks, batch);
+  return rc ? rc : trpo_fvp_impl(p, c);
 }
 
 // =====================================================================================================================
@@ -2019,12 +2041,6 @@ static int sweep_hvp(mi_policy* p, hipStream_t st, const PassRef& ps, int T, int
     PCHK(p, dense_bwd_w_n(st, T, B, p->S, p->H1, tm, 1, hv + p->o_w1, hv + p->o_b1, P)); }
   return MI_OK;
 }
-// out = a - alpha (h + s3): one step of the rho recursion in one launch (out may be a)
-__global__ void step_back_kernel(const float* a, const float* __restrict__ h, const float* __restrict__ s3, float alpha, size_t n,
-                                 float* out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = a[i] - alpha * (h[i] + s3[i]);
-}
 
 // The step-size-vector form keeps ONE more array behind the scalar plan, whose offsets do not move: dlam [K][T][P], row k = d_k (.) lam_{k+1},
 // the direction of the context's sweep of update k and the second argument of T_k in every product.
@@ -2052,60 +2068,49 @@ static int steps_args(mi_policy* p, const char* fn, int steps, int tasks, int ba
 // theta_K (into buffers of its own: the surrogate's query cotangents stay), lam_k for every k, and the tangent sweep of every
 // update along lam_{k+1}.  kl_grad_out (optional, [P]) = d mean_t KL_t / d theta = mean_t lam_0; without it lam_0 is not formed
 // (the products read lam_{k+1} only): update 0 gets its tangent sweep and no weight-gradient products.
-// Vector form (lrc):  lam_k = lam_{k+1} - H_k (d_k (.) lam_{k+1}).  The sweep of update k runs along dlam_k = d_k (.) lam_{k+1}, which the launch
-// that finished lam_{k+1} wrote (lr_adjoint_kernel), and stays for the products like the scalar one.
-static int trpo_kl_prepare_impl(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
-                                const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
-                                const float* old_scale, int tasks, int batch, float inner_lr, const LrCall* lrc, float* kl_grad_out,
-                                void* workspace, size_t workspace_bytes) {
-  const std::string fn = lrc ? std::string(lrc->fn) + ": " : std::string();
-  if (!p || !s_states || !s_actions || !q_states || !old_loc || !old_scale || !workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
-  int rc = steps_args(p, lrc ? lrc->fn : "mi_trpo_kl_prepare_steps", steps, tasks, batch);
+// Table form:  lam_k = lam_{k+1} - H_k (d_k (.) lam_{k+1}).  The sweep of update k runs along dlam_k = d_k (.) lam_{k+1}, which the launch
+// that finished lam_{k+1} wrote (AdjointWalk), and stays for the products like the scalar one.
+static int trpo_kl_prepare_impl(mi_policy* p, const PolicyCall& c) {
+  const std::string fn = c.step.prefix();
+  if (!p || !c.sup.states || !c.sup.actions || !c.qry.states || !c.old_loc || !c.old_scale || !c.workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
+  int rc = steps_args(p, c.step.fn ? c.step.fn : "mi_trpo_kl_prepare_steps", c.steps, c.tasks, c.batch);
   if (rc) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, B = batch, K = steps;
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+  const int T = c.tasks, B = c.batch, K = c.steps;
   const size_t P = p->P, TP = (size_t)T * P;
   StepsPlan pl; GenStepsPlan gp;
-  gen_steps_plan(p, workspace, T, B, K, pl, gp);
+  gen_steps_plan(p, c.workspace, T, B, K, pl, gp);
   size_t need = gp.bytes;
-  float* dlam = lrc ? gen_lr_plan(p, workspace, gp, T, K, need) : nullptr;
-  if (need > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(need));
-  const SupStack sup{s_states, s_actions, nullptr, s_count};
+  float* dlam = c.step.table() ? gen_lr_plan(p, c.workspace, gp, T, K, need) : nullptr;
+  if (need > c.workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(need));
   const float* thK = pl.theta + (size_t)K * TP;
   float* lamK = gp.lam + (size_t)K * TP;
   PCHK(p, hipMemsetAsync(lamK, 0, TP * sizeof(float), st));
   GaussKlArgs gk{};
-  gk.mu = pl.q.a.mu; gk.rho = thK + p->o_sigma; gk.rstride = P; gk.old_loc = old_loc; gk.old_scale = old_scale; gk.count = q_count;
+  gk.mu = pl.q.a.mu; gk.rho = thK + p->o_sigma; gk.rstride = P; gk.old_loc = c.old_loc; gk.old_scale = c.old_scale; gk.count = c.qry.count;
   gk.dmu = gp.k_dmu; gk.drho = lamK + p->o_sigma; gk.gstride = P; gk.B = B; gk.A = p->A; gk.mode = KL_GRAD;
   hipLaunchKernelGGL(gauss_kl_kernel, dim3(T), dim3(256), 0, st, gk);
   PCHK(p, hipGetLastError());
-  rc = mlp_backward(p, st, T, B, q_states, thK, P, pl.q.a, gp.k_dmu, gp.k_d2, gp.k_d1, lamK, gp.k_pre2, gp.k_pre1);
+  rc = mlp_backward(p, st, T, B, c.qry.states, thK, P, pl.q.a, gp.k_dmu, gp.k_d2, gp.k_d1, lamK, gp.k_pre2, gp.k_pre1);
   if (rc) return rc;
-  const dim3 pgrid(ceil_div((int)P, 256), T);
-  const float* none = nullptr;
-  if (lrc) {
-    hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)lamK, none, none, trpo_lr_row(lrc, K - 1, P), none, (int)P, 0, 0,
-                       lamK, dlam + (size_t)(K - 1) * TP, (float*)nullptr);
-    PCHK(p, hipGetLastError());
-  }
+  const AdjointWalk adj{p, st, T, c.step, false, false};
+  auto dlam_of = [&](int k) { return dlam && k >= 0 ? dlam + (size_t)k * TP : (float*)nullptr; };
+  rc = adj.seed(K, lamK, nullptr, dlam_of(K - 1), nullptr);
+  if (rc) return rc;
   for (int k = K - 1; k >= 0; --k) {
-    const float* lam1 = gp.lam + (size_t)(k + 1) * TP;
-    const float* dir = lrc ? dlam + (size_t)k * TP : lam1;
-    const SupRef r = sup_at(p, sup, T, B, k);
-    if (k == 0 && !kl_grad_out)      // (pl.hv takes the sweep's R{d L / d sigma}: scratch)
+    const float *lam1 = gp.lam + (size_t)(k + 1) * TP, *dir;
+    rc = adj.drive(lam1, dlam_of(k), &dir);
+    if (rc) return rc;
+    const SupRef r = sup_at(p, c.sup, T, B, k);
+    if (k == 0 && !c.grad_out)      // (pl.hv takes the sweep's R{d L / d sigma}: scratch)
       return tan_sweep(p, st, pass_of(pl.st[0]), T, B, pl.theta, theta_stride(p, 0), r.xs, r.as, r.cn, dir, P, gp.sc[0], pl.hv);
     rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), r.xs, r.as, r.cn, dir, P, gp.sc[k], pl.hv);
     if (rc) return rc;
-    if (lrc)
-      hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, lam1, (const float*)pl.hv, none, k > 0 ? trpo_lr_row(lrc, k - 1, P) : none,
-                         none, (int)P, 0, 0, gp.lam + (size_t)k * TP, k > 0 ? dlam + (size_t)(k - 1) * TP : (float*)nullptr, (float*)nullptr);
-    else
-      hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, lam1, P, pl.hv, inner_lr, (int)P,
-                         gp.lam + (size_t)k * TP);
-    PCHK(p, hipGetLastError());
+    rc = adj.back(k, lam1, pl.hv, nullptr, nullptr, gp.lam + (size_t)k * TP, dlam_of(k - 1), nullptr);
+    if (rc) return rc;
   }
   hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gp.lam, T, (int)P, 1.f / (float)T,
-                     (const float*)nullptr, 0.f, kl_grad_out);
+                     (const float*)nullptr, 0.f, c.grad_out);
   PCHK(p, hipGetLastError());
   return MI_OK;
 }
@@ -2113,99 +2118,88 @@ extern "C" int mi_trpo_kl_prepare_steps(mi_policy* p, void* stream, int steps, c
                                         const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
                                         const float* old_scale, int tasks, int batch, float inner_lr, float* kl_grad_out,
                                         void* workspace, size_t workspace_bytes) {
-  return trpo_kl_prepare_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, old_loc, old_scale, tasks, batch, inner_lr,
-                              nullptr, kl_grad_out, workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.steps = steps; c.sup = {s_states, s_actions, nullptr, s_count, nullptr}; c.qry = {q_states, nullptr, nullptr, q_count, nullptr};
+  c.tasks = tasks; c.batch = batch; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.old_loc = old_loc; c.old_scale = old_scale; c.grad_out = kl_grad_out;
+  c.step.lr = inner_lr;
+  return trpo_kl_prepare_impl(p, c);
 }
 extern "C" int mi_trpo_kl_prepare_steps_lr(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
                                            const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_loc,
                                            const float* old_scale, int tasks, int batch, const float* lr_vec, int lr_rows,
                                            const int32_t* step_lr_row, float* kl_grad_out, void* workspace, size_t workspace_bytes) {
-  int rc = trpo_lr_args(p, "mi_trpo_kl_prepare_steps_lr", lr_vec, lr_rows, step_lr_row, steps, tasks, batch);
-  if (rc) return rc;
-  const LrCall lrc{lr_vec, lr_rows, step_lr_row, nullptr, "mi_trpo_kl_prepare_steps_lr"};
-  return trpo_kl_prepare_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, old_loc, old_scale, tasks, batch, 0.f, &lrc,
-                              kl_grad_out, workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.steps = steps; c.sup = {s_states, s_actions, nullptr, s_count, nullptr}; c.qry = {q_states, nullptr, nullptr, q_count, nullptr};
+  c.tasks = tasks; c.batch = batch; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.old_loc = old_loc; c.old_scale = old_scale; c.grad_out = kl_grad_out;
+  c.step.vec = lr_vec; c.step.rows = lr_rows; c.step.step_row = step_lr_row; c.step.fn = "mi_trpo_kl_prepare_steps_lr";
+  const int rc = check_table(p, c.step, steps, TRPO_STEPS, tasks, batch);
+  return rc ? rc : trpo_kl_prepare_impl(p, c);
 }
 
 // trpo.hessian_vector_product(mean KL, params, damping)(v) (rl.py:417) at the parameters of the preceding
 // mi_trpo_surrogate_steps + mi_trpo_kl_prepare_steps on this workspace; any number of calls.  11 + 36 K kernels and 1 + 3 K
 // memsets, whatever the number of tasks.
-// Vector form (lrc):  u_{k+1} = u_k - d_k (.) (H_k u_k);   rho_k = rho_{k+1} - (H_k (d_k (.) rho_{k+1}) + T_k[u_k, d_k (.) lam_{k+1}]):  the stored
+// Table form:  u_{k+1} = u_k - d_k (.) (H_k u_k);   rho_k = rho_{k+1} - (H_k (d_k (.) rho_{k+1}) + T_k[u_k, d_k (.) lam_{k+1}]):  the stored
 // sweeps run along u_k and along dlam_k, the sweep of its own along d_k (.) rho_{k+1} (in pl.g, written by the launch that finished rho_{k+1}).
-static int trpo_fvp_general_impl(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
-                                 const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
-                                 int tasks, int batch, float inner_lr, const LrCall* lrc, float damping, const float* v, float* out,
-                                 void* workspace, size_t workspace_bytes) {
-  const std::string fn = lrc ? std::string(lrc->fn) + ": " : std::string();
-  if (!p || !s_states || !s_actions || !q_states || !old_scale || !v || !out || !workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
-  int rc = steps_args(p, lrc ? lrc->fn : "mi_trpo_fvp_general_steps", steps, tasks, batch);
+static int trpo_fvp_general_impl(mi_policy* p, const PolicyCall& c) {
+  const std::string fn = c.step.prefix();
+  if (!p || !c.sup.states || !c.sup.actions || !c.qry.states || !c.old_scale || !c.v || !c.out || !c.workspace) return pfail(p, MI_ERR_ARG, fn + "null argument");
+  int rc = steps_args(p, c.step.fn ? c.step.fn : "mi_trpo_fvp_general_steps", c.steps, c.tasks, c.batch);
   if (rc) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int T = tasks, B = batch, K = steps;
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+  const int T = c.tasks, B = c.batch, K = c.steps;
   const size_t P = p->P, TP = (size_t)T * P;
   StepsPlan pl; GenStepsPlan gp;
-  gen_steps_plan(p, workspace, T, B, K, pl, gp);
+  gen_steps_plan(p, c.workspace, T, B, K, pl, gp);
   size_t need = gp.bytes;
-  const float* dlam = lrc ? gen_lr_plan(p, workspace, gp, T, K, need) : nullptr;
-  if (need > workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(need));
-  const SupStack sup{s_states, s_actions, nullptr, s_count};
-  const dim3 pgrid(ceil_div((int)P, 256), T);
-  const float* none = nullptr;
+  const float* dlam = c.step.table() ? gen_lr_plan(p, c.workspace, gp, T, K, need) : nullptr;
+  if (need > c.workspace_bytes) return pfail(p, MI_ERR_WORKSPACE, fn + "workspace too small: need " + std::to_string(need));
   // ---- u_0 = v for every task, u_{k+1} = u_k - lr H_k u_k; the sweep along u_k stays for the way back
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, v, (size_t)0, pl.g, 0.f, (int)P, gp.u);
+  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, c.v, (size_t)0, pl.g, 0.f, (int)P, gp.u);
   PCHK(p, hipGetLastError());
   for (int k = 0; k < K; ++k) {
-    const SupRef r = sup_at(p, sup, T, B, k);
+    const SupRef r = sup_at(p, c.sup, T, B, k);
     const float* uk = gp.u + (size_t)k * TP;
     rc = sweep_hvp(p, st, pass_of(pl.st[k]), T, B, pl.theta + (size_t)k * TP, theta_stride(p, k), r.xs, r.as, r.cn, uk, P, gp.sv[k], pl.hv);
     if (rc) return rc;
-    if (lrc)
-      hipLaunchKernelGGL(lr_advance_kernel, pgrid, dim3(256), 0, st, uk, P, (const float*)pl.hv, trpo_lr_row(lrc, k, P), (int)P, 0, 0,
-                         gp.u + (size_t)(k + 1) * TP);
-    else
-      hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ceil_div((int)P, 256), T), dim3(256), 0, st, uk, P, pl.hv, inner_lr, (int)P,
-                         gp.u + (size_t)(k + 1) * TP);
-    PCHK(p, hipGetLastError());
+    rc = step_advance(p, st, T, c.step, k, false, false, uk, P, pl.hv, gp.u + (size_t)(k + 1) * TP);
+    if (rc) return rc;
   }
   // ---- rho_K = Hess KL_t(theta_K) u_K: tangent forward on the query pass, exact output Hessian, tangent backward
   const float* thK = pl.theta + (size_t)K * TP;
   const float* uK = gp.u + (size_t)K * TP;
-  rc = mlp_tangent_forward(p, st, T, B, q_states, thK, P, pl.q.a, uK, pl.ta);
+  rc = mlp_tangent_forward(p, st, T, B, c.qry.states, thK, P, pl.q.a, uK, pl.ta);
   if (rc) return rc;
   PCHK(p, hipMemsetAsync(gp.rho, 0, TP * sizeof(float), st));
   GaussKlArgs gh{};
-  gh.mu = pl.q.a.mu; gh.rho = thK + p->o_sigma; gh.rstride = P; gh.old_scale = old_scale; gh.mud = pl.ta.mu;
-  gh.rhod = uK + p->o_sigma; gh.vstride = P; gh.count = q_count; gh.dmu = pl.rdmu; gh.drho = gp.rho + p->o_sigma; gh.gstride = P;
+  gh.mu = pl.q.a.mu; gh.rho = thK + p->o_sigma; gh.rstride = P; gh.old_scale = c.old_scale; gh.mud = pl.ta.mu;
+  gh.rhod = uK + p->o_sigma; gh.vstride = P; gh.count = c.qry.count; gh.dmu = pl.rdmu; gh.drho = gp.rho + p->o_sigma; gh.gstride = P;
   gh.B = B; gh.A = p->A; gh.mode = KL_HESS;
   hipLaunchKernelGGL(gauss_kl_kernel, dim3(T), dim3(256), 0, st, gh);
   PCHK(p, hipGetLastError());
-  rc = mlp_tangent_backward(p, st, T, B, q_states, thK, P, pl.q.a, pl.ta, uK, gp.k_dmu, gp.k_d2, gp.k_d1, gp.k_pre2, gp.k_pre1, pl.rdmu,
+  rc = mlp_tangent_backward(p, st, T, B, c.qry.states, thK, P, pl.q.a, pl.ta, uK, gp.k_dmu, gp.k_d2, gp.k_d1, gp.k_pre2, gp.k_pre1, pl.rdmu,
                             pl.r2, pl.r1, gp.rho);
   if (rc) return rc;
   // ---- rho_k = rho_{k+1} - lr (H_k rho_{k+1} + T_k[u_k, lam_{k+1}])
-  if (lrc) {
-    hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)gp.rho, none, none, trpo_lr_row(lrc, K - 1, P), none, (int)P, 0, 0,
-                       gp.rho, pl.g, (float*)nullptr);
-    PCHK(p, hipGetLastError());
-  }
+  const AdjointWalk adj{p, st, T, c.step, false, false};
+  rc = adj.seed(K, gp.rho, nullptr, pl.g, nullptr);
+  if (rc) return rc;
   for (int k = K - 1; k >= 0; --k) {
-    const SupRef r = sup_at(p, sup, T, B, k);
-    const float* th = pl.theta + (size_t)k * TP;
+    const SupRef r = sup_at(p, c.sup, T, B, k);
+    const float *th = pl.theta + (size_t)k * TP, *dir;
     const size_t ts = theta_stride(p, k);
-    rc = hvp_step(p, st, pl, pl.st[k], T, B, th, ts, r, lrc ? pl.g : gp.rho, pl.hv);
+    rc = adj.drive(gp.rho, pl.g, &dir);
+    if (rc) return rc;
+    rc = hvp_step(p, st, pl, pl.st[k], T, B, th, ts, r, dir, pl.hv);
     if (rc) return rc;
     PCHK(p, hipMemsetAsync(gp.s3, 0, TP * sizeof(float), st));
-    rc = mixed_sweep(p, st, pass_of(pl.st[k]), T, B, th, ts, r.xs, r.as, r.cn, lrc ? dlam + (size_t)k * TP : gp.lam + (size_t)(k + 1) * TP, P,
+    rc = mixed_sweep(p, st, pass_of(pl.st[k]), T, B, th, ts, r.xs, r.as, r.cn, dlam ? dlam + (size_t)k * TP : gp.lam + (size_t)(k + 1) * TP, P,
                      gp.u + (size_t)k * TP, P, gp.sc[k], gp.sv[k], gp.mx, gp.s3);
     if (rc) return rc;
-    if (lrc)
-      hipLaunchKernelGGL(lr_adjoint_kernel, pgrid, dim3(256), 0, st, (const float*)gp.rho, (const float*)pl.hv, (const float*)gp.s3,
-                         k > 0 ? trpo_lr_row(lrc, k - 1, P) : none, none, (int)P, 0, 0, gp.rho, pl.g, (float*)nullptr);
-    else
-      hipLaunchKernelGGL(step_back_kernel, dim3((unsigned)((TP + 255) / 256)), dim3(256), 0, st, gp.rho, pl.hv, gp.s3, inner_lr, TP, gp.rho);
-    PCHK(p, hipGetLastError());
+    rc = adj.back(k, gp.rho, pl.hv, gp.s3, nullptr, gp.rho, pl.g, nullptr);
+    if (rc) return rc;
   }
-  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gp.rho, T, (int)P, 1.f / (float)T, v, damping, out);
+  hipLaunchKernelGGL(mean_tasks_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, gp.rho, T, (int)P, 1.f / (float)T, c.v, c.damping, c.out);
   PCHK(p, hipGetLastError());
   return MI_OK;
 }
@@ -2213,16 +2207,20 @@ extern "C" int mi_trpo_fvp_general_steps(mi_policy* p, void* stream, int steps, 
                                          const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
                                          int tasks, int batch, float inner_lr, float damping, const float* v, float* out,
                                          void* workspace, size_t workspace_bytes) {
-  return trpo_fvp_general_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, old_scale, tasks, batch, inner_lr, nullptr,
-                               damping, v, out, workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.steps = steps; c.sup = {s_states, s_actions, nullptr, s_count, nullptr}; c.qry = {q_states, nullptr, nullptr, q_count, nullptr};
+  c.tasks = tasks; c.batch = batch; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.old_scale = old_scale; c.damping = damping; c.v = v; c.out = out;
+  c.step.lr = inner_lr;
+  return trpo_fvp_general_impl(p, c);
 }
 extern "C" int mi_trpo_fvp_general_steps_lr(mi_policy* p, void* stream, int steps, const float* s_states, const float* s_actions,
                                             const int32_t* s_count, const float* q_states, const int32_t* q_count, const float* old_scale,
                                             int tasks, int batch, const float* lr_vec, int lr_rows, const int32_t* step_lr_row, float damping,
                                             const float* v, float* out, void* workspace, size_t workspace_bytes) {
-  int rc = trpo_lr_args(p, "mi_trpo_fvp_general_steps_lr", lr_vec, lr_rows, step_lr_row, steps, tasks, batch);
-  if (rc) return rc;
-  const LrCall lrc{lr_vec, lr_rows, step_lr_row, nullptr, "mi_trpo_fvp_general_steps_lr"};
-  return trpo_fvp_general_impl(p, stream, steps, s_states, s_actions, s_count, q_states, q_count, old_scale, tasks, batch, 0.f, &lrc, damping,
-                               v, out, workspace, workspace_bytes);
+  PolicyCall c{};
+  c.stream = stream; c.steps = steps; c.sup = {s_states, s_actions, nullptr, s_count, nullptr}; c.qry = {q_states, nullptr, nullptr, q_count, nullptr};
+  c.tasks = tasks; c.batch = batch; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.old_scale = old_scale; c.damping = damping; c.v = v; c.out = out;
+  c.step.vec = lr_vec; c.step.rows = lr_rows; c.step.step_row = step_lr_row; c.step.fn = "mi_trpo_fvp_general_steps_lr";
+  const int rc = check_table(p, c.step, steps, TRPO_STEPS, tasks, batch);
+  return rc ? rc : trpo_fvp_general_impl(p, c);
 }

@@ -678,8 +678,11 @@ class PolicyEngine:
             self._check(self.lib.mi_trpo_general_steps_lr_workspace_bytes(self._h, T, B, K, lr_rows, C.byref(b)))
         else:
             self._check(self.lib.mi_trpo_general_steps_workspace_bytes(self._h, T, B, K, C.byref(b)))
-        if self._ws is None or self._ws.numel() < b.value:
-            self._ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
+        return self._grow_workspace(b.value)
+
+    def _grow_workspace(self, nbytes):
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
 
     @_on_device
@@ -741,27 +744,40 @@ class PolicyEngine:
             _ptr(out['ep_len']), _ptr(out.get('noise')), _ptr(ws), ws.numel() if ws is not None else 0))
         return out
 
-    def _lr_table(self, lr, K, step_lr_row):
-        """The step of a TRPO call: None for a number (the scalar entries), else (lr_vec [rows, P] fp32 contiguous on the device, rows,
-        the int32 array of the K updates' rows or None = row 0 for all) for a [rows, P] / [P] tensor in the engine's parameter order."""
+    def _lr_table(self, lr, K, step_lr_row, one_row=False, row0_default=False):
+        """THE check of a call's step: None for a number (the scalar entries), else (lr_vec [rows, P] fp32 contiguous on the device, rows,
+        the int32 array of the K updates' rows or None = row 0 for all) for a [rows, P] / [P] tensor in the engine's parameter order.
+        one_row: adapt / update take [P] only.  row0_default: the meta-batch reads row 0 of any table where no rows are named."""
         if not torch.is_tensor(lr):
             if step_lr_row is not None:
                 raise ValueError('step_lr_row goes with a step-size tensor, not with a number')
             return None
         P = self.param_count
         lr = lr.detach()
+        if one_row and lr.dim() != 1:
+            raise ValueError(f'lr must be a number or ONE row [P] of step sizes, got {tuple(lr.shape)}')
         if lr.dim() == 1:
             lr = lr.unsqueeze(0)
         if lr.dim() != 2 or lr.shape[1] != P or lr.shape[0] < 1 or lr.dtype != torch.float32 or not lr.is_cuda:
             raise ValueError(f'the step must be a number or an fp32 tensor on the GPU, [rows, P] or [P] with P={P}, got {tuple(lr.shape)} {lr.dtype}')
         rows = lr.shape[0]
         if step_lr_row is None:
-            if rows != 1:
+            if rows != 1 and not row0_default:
                 raise ValueError(f'a step-size table of {rows} rows needs step_lr_row (the row each of the {K} updates reads)')
             return lr.contiguous(), rows, None
         if len(step_lr_row) != K:
             raise ValueError(f'step_lr_row holds {len(step_lr_row)} rows for {K} updates')
         return lr.contiguous(), rows, (C.c_int32 * max(K, 1))(*[int(x) for x in step_lr_row])
+
+    def _step_args(self, lr, K, step_lr_row, one_row=False):
+        """The header's rule for the step-size-table entries ("its scalar namesake with lr_vec, lr_rows, step_lr_row where that takes
+        float inner_lr"; adapt / update, ``one_row``: lr_vec alone) -> (the suffix of the entry's symbol, the arguments that stand
+        there, the table's rows or 0, the table itself: it must outlive the call)."""
+        tab = self._lr_table(lr, K, step_lr_row, one_row)
+        if tab is None:
+            return '', (float(lr),), 0, None
+        vec, rows, sr = tab
+        return '_lr', ((_ptr(vec),) if one_row else (_ptr(vec), rows, sr)), rows, vec
 
     @_on_device
     def adapt(self, theta, states, actions, adv, count, lr, head_only=False):
@@ -773,16 +789,10 @@ class PolicyEngine:
         out = torch.empty(T, self.param_count, device=self.device)
         loss = torch.empty(T, device=self.device)
         stride = 0 if theta.dim() == 1 else self.param_count
-        if torch.is_tensor(lr):
-            if lr.dim() != 1:
-                raise ValueError(f'lr must be a number or ONE row [P] of step sizes, got {tuple(lr.shape)}')
-            vec = self._lr_table(lr, 1, None)[0]
-            self._check(self.lib.mi_policy_adapt_lr(self._h, _stream(self.device), _ptr(theta.contiguous()), stride, _ptr(states), _ptr(actions),
-                                                    _ptr(adv), _ptr(count), T, B, _ptr(vec), int(head_only), _ptr(out), _ptr(loss), _ptr(ws),
-                                                    ws.numel()))
-            return out, loss
-        self._check(self.lib.mi_policy_adapt(self._h, _stream(self.device), _ptr(theta.contiguous()), stride, _ptr(states), _ptr(actions),
-                                             _ptr(adv), _ptr(count), T, B, float(lr), int(head_only), _ptr(out), _ptr(loss), _ptr(ws), ws.numel()))
+        sfx, step, _, _keep = self._step_args(lr, 1, None, one_row=True)
+        self._check(getattr(self.lib, 'mi_policy_adapt' + sfx)(
+            self._h, _stream(self.device), _ptr(theta.contiguous()), stride, _ptr(states), _ptr(actions), _ptr(adv), _ptr(count), T, B, *step,
+            int(head_only), _ptr(out), _ptr(loss), _ptr(ws), ws.numel()))
         return out, loss
 
     def _trpo_shapes(self, sup, qry, theta=None, old_loc=None, old_scale=None, v=None):
@@ -811,38 +821,27 @@ class PolicyEngine:
         ``inner_lr``: a number, or (here and in ``fvp`` / ``kl_prepare`` / ``fvp_general``, which must be given the same) a [rows, P] / [P]
         fp32 tensor of fixed per-parameter step sizes in the engine's order, update k reading row ``step_lr_row[k]`` (None: one row)."""
         K, T, B = self._trpo_shapes(sup, qry, theta=theta, old_loc=old_loc, old_scale=old_scale)
-        tab = self._lr_table(inner_lr, K, step_lr_row)
-        ws = self._workspace(T, B, K, tab[1] if tab else 0)
+        sfx, step, rows, _keep = self._step_args(inner_lr, K, step_lr_row)
+        ws = self._workspace(T, B, K, rows)
         loss = torch.empty(1, device=self.device)
         kl = torch.empty(1, device=self.device)
         grad = torch.empty(self.param_count, device=self.device) if want_grad else None
-        if tab:
-            self._check(self.lib.mi_trpo_surrogate_steps_lr(
-                self._h, _stream(self.device), _ptr(theta), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['adv']), _ptr(sup['count']),
-                _ptr(qry['states']), _ptr(qry['actions']), _ptr(qry['adv']), _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B,
-                _ptr(tab[0]), tab[1], tab[2], _ptr(loss), _ptr(kl), _ptr(grad), _ptr(ws), ws.numel()))
-            return loss, kl, grad
-        self._check(self.lib.mi_trpo_surrogate_steps(
+        self._check(getattr(self.lib, 'mi_trpo_surrogate_steps' + sfx)(
             self._h, _stream(self.device), _ptr(theta), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['adv']), _ptr(sup['count']),
             _ptr(qry['states']), _ptr(qry['actions']), _ptr(qry['adv']), _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B,
-            float(inner_lr), _ptr(loss), _ptr(kl), _ptr(grad), _ptr(ws), ws.numel()))
+            *step, _ptr(loss), _ptr(kl), _ptr(grad), _ptr(ws), ws.numel()))
         return loss, kl, grad
 
     @_on_device
     def fvp(self, sup, qry, inner_lr, damping, v, step_lr_row=None):
         """Fisher-vector product at the theta of the preceding ``surrogate`` call (same replays, same step)."""
         K, T, B = self._trpo_shapes(sup, qry, v=v)
-        tab = self._lr_table(inner_lr, K, step_lr_row)
-        ws = self._workspace(T, B, K, tab[1] if tab else 0)
+        sfx, step, rows, _keep = self._step_args(inner_lr, K, step_lr_row)
+        ws = self._workspace(T, B, K, rows)
         out = torch.empty(self.param_count, device=self.device)
-        if tab:
-            self._check(self.lib.mi_trpo_fvp_steps_lr(self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']),
-                                                      _ptr(sup['count']), _ptr(qry['states']), _ptr(qry['count']), T, B, _ptr(tab[0]), tab[1],
-                                                      tab[2], float(damping), _ptr(v.contiguous()), _ptr(out), _ptr(ws), ws.numel()))
-            return out
-        self._check(self.lib.mi_trpo_fvp_steps(self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']),
-                                               _ptr(qry['states']), _ptr(qry['count']), T, B, float(inner_lr), float(damping),
-                                               _ptr(v.contiguous()), _ptr(out), _ptr(ws), ws.numel()))
+        self._check(getattr(self.lib, 'mi_trpo_fvp_steps' + sfx)(
+            self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
+            _ptr(qry['count']), T, B, *step, float(damping), _ptr(v.contiguous()), _ptr(out), _ptr(ws), ws.numel()))
         return out
 
     @_on_device
@@ -850,36 +849,24 @@ class PolicyEngine:
         """After ``surrogate`` at the same theta and replays: the context of the exact KL Hessian-vector product for
         new != old with K = sup['states'].shape[0] inner updates (ANIL-TRPO).  Returns d mean KL / d theta [P] if ``want_grad``."""
         K, T, B = self._trpo_shapes(sup, qry, old_loc=old_loc, old_scale=old_scale)
-        tab = self._lr_table(inner_lr, K, step_lr_row)
-        ws = self._workspace(T, B, K, tab[1] if tab else 0)
+        sfx, step, rows, _keep = self._step_args(inner_lr, K, step_lr_row)
+        ws = self._workspace(T, B, K, rows)
         grad = torch.empty(self.param_count, device=self.device) if want_grad else None
-        if tab:
-            self._check(self.lib.mi_trpo_kl_prepare_steps_lr(
-                self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
-                _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B, _ptr(tab[0]), tab[1], tab[2], _ptr(grad), _ptr(ws), ws.numel()))
-            return grad
-        self._check(self.lib.mi_trpo_kl_prepare_steps(
+        self._check(getattr(self.lib, 'mi_trpo_kl_prepare_steps' + sfx)(
             self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
-            _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B, float(inner_lr), _ptr(grad), _ptr(ws), ws.numel()))
+            _ptr(qry['count']), _ptr(old_loc), _ptr(old_scale), T, B, *step, _ptr(grad), _ptr(ws), ws.numel()))
         return grad
 
     @_on_device
     def fvp_general(self, sup, qry, old_scale, inner_lr, damping, v, step_lr_row=None):
         """Exact Hessian-vector product of the mean KL at the theta of the preceding ``surrogate`` + ``kl_prepare``."""
         K, T, B = self._trpo_shapes(sup, qry, old_scale=old_scale, v=v)
-        tab = self._lr_table(inner_lr, K, step_lr_row)
-        ws = self._workspace(T, B, K, tab[1] if tab else 0)
+        sfx, step, rows, _keep = self._step_args(inner_lr, K, step_lr_row)
+        ws = self._workspace(T, B, K, rows)
         out = torch.empty(self.param_count, device=self.device)
-        if tab:
-            self._check(self.lib.mi_trpo_fvp_general_steps_lr(
-                self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
-                _ptr(qry['count']), _ptr(old_scale), T, B, _ptr(tab[0]), tab[1], tab[2], float(damping), _ptr(v.contiguous()), _ptr(out),
-                _ptr(ws), ws.numel()))
-            return out
-        self._check(self.lib.mi_trpo_fvp_general_steps(
+        self._check(getattr(self.lib, 'mi_trpo_fvp_general_steps' + sfx)(
             self._h, _stream(self.device), K, _ptr(sup['states']), _ptr(sup['actions']), _ptr(sup['count']), _ptr(qry['states']),
-            _ptr(qry['count']), _ptr(old_scale), T, B, float(inner_lr), float(damping), _ptr(v.contiguous()), _ptr(out), _ptr(ws),
-            ws.numel()))
+            _ptr(qry['count']), _ptr(old_scale), T, B, *step, float(damping), _ptr(v.contiguous()), _ptr(out), _ptr(ws), ws.numel()))
         return out
 
     @_on_device
@@ -889,40 +876,47 @@ class PolicyEngine:
         tasks (mi_policy_meta_batch: fast_adapt_vpg / fast_adapt_ppo, reference rl.py:231-255,267-318).
         sup: dict states [NB,T,B,S], actions [NB,T,B,A], adv [NB,T,B], count [NB,T] int32 (NB support batches); qry: the same
         without the NB axis.  Returns (loss [T], theta_adapted [T,P], grad [P] summed over tasks or None)."""
-        import numpy as np
+        return self._meta_call(theta, sup, qry, step_batch, float(inner_lr), None, loss, clip, step_new_old, head_only, first_order, with_grad,
+                               False)[:3]
+
+    def _meta_call(self, theta, sup, qry, step_batch, lr, step_lr_row, loss, clip, step_new_old, head_only, first_order, with_grad, want_lr_grad):
+        """``meta_batch`` (``lr`` a number: mi_policy_meta_batch_dones, whose flags only the DiCE objective reads) and ``meta_batch_lr``
+        (a tensor: mi_policy_meta_batch_lr) -> (loss, theta_adapted, grad or None, lr_grad or None)."""
         K = len(step_batch)
-        T, B = qry['states'].shape[0], qry['states'].shape[1]
+        T, B, P = qry['states'].shape[0], qry['states'].shape[1], self.param_count
         NB = sup['states'].shape[0] if K else 0
         kind = {'a2c': 0, 'ppo': 1, 'dice': 2}[loss]
+        tab = self._lr_table(lr, K, step_lr_row, row0_default=True)
+        want_lr_grad = bool(tab and want_lr_grad and with_grad)
         sb = (C.c_int32 * max(K, 1))(*[int(x) for x in step_batch])
         if step_new_old is None:
             step_new_old = [1 if (k == 0 or step_batch[k] != step_batch[k - 1]) else 0 for k in range(K)]
         sn = (C.c_int32 * max(K, 1))(*[int(x) for x in step_new_old])
-        so = (not first_order) and with_grad
-        b = C.c_size_t()
-        self._check(self.lib.mi_policy_meta_workspace_bytes(self._h, T, B, K, NB, int(so), C.byref(b)))
-        if self._ws is None or self._ws.numel() < b.value:
-            self._ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
+        dice = loss == 'dice'    # the DiCE objective couples the samples of an episode: the replays' `dones` travel with them
+        if dice and ('done' not in qry or (K and 'done' not in sup)):
+            raise ValueError("loss='dice' needs the episode-end flags of every replay (key 'done', float32, like 'adv')")
+        b, so = C.c_size_t(), int(not first_order and with_grad)
+        if tab:
+            self._check(self.lib.mi_policy_meta_lr_workspace_bytes(self._h, T, B, K, NB, so, tab[1], int(want_lr_grad), C.byref(b)))
+        else:
+            self._check(self.lib.mi_policy_meta_workspace_bytes(self._h, T, B, K, NB, so, C.byref(b)))
+        ws = self._grow_workspace(b.value)
         loss_t = torch.empty(T, device=self.device)
-        theta_out = torch.empty(T, self.param_count, device=self.device)
-        grad = torch.empty(self.param_count, device=self.device) if with_grad else None
+        theta_out = torch.empty(T, P, device=self.device)
+        grad = torch.empty(P, device=self.device) if with_grad else None
+        lr_grad = torch.empty(tab[1], P, device=self.device) if want_lr_grad else None
         g = lambda d, k: _ptr(d[k].contiguous()) if d is not None and K else C.c_void_p(0)
-        if loss == 'dice':       # the DiCE objective couples the samples of an episode: the replays' `dones` travel with them
-            if 'done' not in qry or (K and 'done' not in sup):
-                raise ValueError("loss='dice' needs the episode-end flags of every replay (key 'done', float32, like 'adv')")
-            self._check(self.lib.mi_policy_meta_batch_dones(
-                self._h, _stream(self.device), _ptr(theta.contiguous()), K, sb, sn, NB, g(sup, 'states'), g(sup, 'actions'), g(sup, 'adv'),
-                g(sup, 'count'), g(sup, 'done'), _ptr(qry['states'].contiguous()), _ptr(qry['actions'].contiguous()),
-                _ptr(qry['adv'].contiguous()), _ptr(qry['count'].contiguous()), _ptr(qry['done'].contiguous()), T, B, kind, float(clip),
-                float(inner_lr), int(head_only), int(not first_order), int(with_grad), _ptr(loss_t), _ptr(theta_out), _ptr(grad),
-                _ptr(self._ws), self._ws.numel()))
-            return loss_t, theta_out, grad
-        self._check(self.lib.mi_policy_meta_batch(
-            self._h, _stream(self.device), _ptr(theta.contiguous()), K, sb, sn, NB, g(sup, 'states'), g(sup, 'actions'), g(sup, 'adv'),
-            g(sup, 'count'), _ptr(qry['states'].contiguous()), _ptr(qry['actions'].contiguous()), _ptr(qry['adv'].contiguous()),
-            _ptr(qry['count'].contiguous()), T, B, kind, float(clip), float(inner_lr), int(head_only), int(not first_order),
-            int(with_grad), _ptr(loss_t), _ptr(theta_out), _ptr(grad), _ptr(self._ws), self._ws.numel()))
-        return loss_t, theta_out, grad
+        head = (self._h, _stream(self.device), _ptr(theta.contiguous()), K, sb, sn)
+        replays = (NB, g(sup, 'states'), g(sup, 'actions'), g(sup, 'adv'), g(sup, 'count'), g(sup, 'done') if dice else None,
+                   _ptr(qry['states'].contiguous()), _ptr(qry['actions'].contiguous()), _ptr(qry['adv'].contiguous()),
+                   _ptr(qry['count'].contiguous()), _ptr(qry['done'].contiguous()) if dice else None, T, B, kind, float(clip))
+        flags = (int(head_only), int(not first_order), int(with_grad), _ptr(loss_t), _ptr(theta_out), _ptr(grad))
+        if tab:
+            self._check(self.lib.mi_policy_meta_batch_lr(*head, tab[2], *replays, _ptr(tab[0]), tab[1], *flags, _ptr(lr_grad), _ptr(ws),
+                                                         ws.numel()))
+        else:
+            self._check(self.lib.mi_policy_meta_batch_dones(*head, *replays, float(lr), *flags, _ptr(ws), ws.numel()))
+        return loss_t, theta_out, grad, lr_grad
 
     @_on_device
     def meta_batch_lr(self, theta, sup, qry, step_batch, lr_vec, step_lr_row=None, loss='a2c', clip=0.1, step_new_old=None, head_only=False,
@@ -931,46 +925,10 @@ class PolicyEngine:
         parameter order, update k reads row step_lr_row[k] (None: row 0).  Returns (loss [T], theta_adapted [T,P], grad [P] summed over
         tasks or None, lr_grad [rows, P] = d sum_t loss / d lr_vec or None).  ``want_lr_grad`` needs ``with_grad``; loss='dice' takes
         the replays' 'done' like ``meta_batch``."""
-        K = len(step_batch)
-        T, B = qry['states'].shape[0], qry['states'].shape[1]
-        NB = sup['states'].shape[0] if K else 0
-        kind = {'a2c': 0, 'ppo': 1, 'dice': 2}[loss]
-        P = self.param_count
-        lr_vec = lr_vec.detach()
-        if lr_vec.dim() == 1:
-            lr_vec = lr_vec.unsqueeze(0)
-        if lr_vec.dim() != 2 or lr_vec.shape[1] != P or lr_vec.dtype != torch.float32 or not lr_vec.is_cuda:
-            raise ValueError(f'lr_vec must be fp32 on the GPU, [rows, P] with P={P}, got {tuple(lr_vec.shape)} {lr_vec.dtype}')
-        lr_vec = lr_vec.contiguous()
-        rows = lr_vec.shape[0]
-        if step_lr_row is not None and len(step_lr_row) != K:
-            raise ValueError(f'step_lr_row holds {len(step_lr_row)} rows for {K} updates')
-        want_lr_grad = bool(want_lr_grad and with_grad)
-        sb = (C.c_int32 * max(K, 1))(*[int(x) for x in step_batch])
-        if step_new_old is None:
-            step_new_old = [1 if (k == 0 or step_batch[k] != step_batch[k - 1]) else 0 for k in range(K)]
-        sn = (C.c_int32 * max(K, 1))(*[int(x) for x in step_new_old])
-        sr = None if step_lr_row is None else (C.c_int32 * max(K, 1))(*[int(x) for x in step_lr_row])
-        if loss == 'dice' and ('done' not in qry or (K and 'done' not in sup)):
-            raise ValueError("loss='dice' needs the episode-end flags of every replay (key 'done', float32, like 'adv')")
-        b = C.c_size_t()
-        self._check(self.lib.mi_policy_meta_lr_workspace_bytes(self._h, T, B, K, NB, int(not first_order and with_grad), rows,
-                                                                int(want_lr_grad), C.byref(b)))
-        if self._ws is None or self._ws.numel() < b.value:
-            self._ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
-        loss_t = torch.empty(T, device=self.device)
-        theta_out = torch.empty(T, P, device=self.device)
-        grad = torch.empty(P, device=self.device) if with_grad else None
-        lr_grad = torch.empty(rows, P, device=self.device) if want_lr_grad else None
-        g = lambda d, k: _ptr(d[k].contiguous()) if d is not None and K else C.c_void_p(0)
-        dice = loss == 'dice'
-        self._check(self.lib.mi_policy_meta_batch_lr(
-            self._h, _stream(self.device), _ptr(theta.contiguous()), K, sb, sn, sr, NB, g(sup, 'states'), g(sup, 'actions'), g(sup, 'adv'),
-            g(sup, 'count'), g(sup, 'done') if dice else None, _ptr(qry['states'].contiguous()), _ptr(qry['actions'].contiguous()),
-            _ptr(qry['adv'].contiguous()), _ptr(qry['count'].contiguous()), _ptr(qry['done'].contiguous()) if dice else None, T, B, kind,
-            float(clip), _ptr(lr_vec), rows, int(head_only), int(not first_order), int(with_grad), _ptr(loss_t), _ptr(theta_out), _ptr(grad),
-            _ptr(lr_grad), _ptr(self._ws), self._ws.numel()))
-        return loss_t, theta_out, grad, lr_grad
+        if not torch.is_tensor(lr_vec):
+            raise ValueError(f'lr_vec must be fp32 on the GPU, [rows, P] with P={self.param_count}, got {type(lr_vec).__name__}: meta_batch takes a number')
+        return self._meta_call(theta, sup, qry, step_batch, lr_vec, step_lr_row, loss, clip, step_new_old, head_only, first_order, with_grad,
+                               want_lr_grad)
 
     @_on_device
     def update(self, theta, states, actions, adv, count, lr, loss='a2c', epochs=1, clip=0.1, done=None, head_only=False):
@@ -986,8 +944,7 @@ class PolicyEngine:
             raise ValueError("loss='dice' needs the episode-end flags of the replay (done [T, B], float32)")
         b = C.c_size_t()
         self._check(self.lib.mi_policy_update_workspace_bytes(self._h, T, B, C.byref(b)))
-        if self._ws is None or self._ws.numel() < b.value:
-            self._ws = torch.empty(b.value, dtype=torch.uint8, device=self.device)
+        ws = self._grow_workspace(b.value)
         theta = theta.detach()
         if theta.dim() == 2 and theta.shape[0] != T:
             raise ValueError(f'theta has {theta.shape[0]} rows for {T} tasks')
@@ -996,17 +953,10 @@ class PolicyEngine:
         stride = 0 if theta.dim() == 1 else self.param_count
         c = lambda t: None if t is None else t.contiguous()
         theta, states, actions, adv, count, done = c(theta), c(states), c(actions), c(adv), c(count), c(done)
-        if torch.is_tensor(lr):
-            lr = lr.detach()
-            if tuple(lr.shape) != (self.param_count,) or lr.dtype != torch.float32 or not lr.is_cuda:
-                raise ValueError(f'lr must be a number or an fp32 [P] tensor on the GPU with P={self.param_count}, got {tuple(lr.shape)} {lr.dtype}')
-            self._check(self.lib.mi_policy_update_lr(self._h, _stream(self.device), _ptr(theta), stride, _ptr(states), _ptr(actions), _ptr(adv),
-                                                     _ptr(count), _ptr(done), T, B, kind, int(epochs), float(clip), _ptr(lr.contiguous()),
-                                                     int(head_only), _ptr(out), _ptr(losses), _ptr(self._ws), self._ws.numel()))
-            return out, losses
-        self._check(self.lib.mi_policy_update(self._h, _stream(self.device), _ptr(theta), stride, _ptr(states), _ptr(actions), _ptr(adv),
-                                              _ptr(count), _ptr(done), T, B, kind, int(epochs), float(clip), float(lr), int(head_only),
-                                              _ptr(out), _ptr(losses), _ptr(self._ws), self._ws.numel()))
+        sfx, step, _, _keep = self._step_args(lr, 1, None, one_row=True)
+        self._check(getattr(self.lib, 'mi_policy_update' + sfx)(
+            self._h, _stream(self.device), _ptr(theta), stride, _ptr(states), _ptr(actions), _ptr(adv), _ptr(count), _ptr(done), T, B, kind,
+            int(epochs), float(clip), *step, int(head_only), _ptr(out), _ptr(losses), _ptr(ws), ws.numel()))
         return out, losses
 
     # ------------------------------------------------------------------------------------------------- step-wise learner
