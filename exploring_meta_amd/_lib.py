@@ -94,6 +94,11 @@ _SIGS = {
     'mi_meta_batch_maml_steps': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    'mi_workspace_bytes_offsets': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(C.c_size_t)]),
+    'mi_meta_batch_maml_offsets': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     'mi_engine_set_fused_tail': (C.c_int, [C.c_void_p, C.c_int]),
     'mi_engine_set_fused_last_block': (C.c_int, [C.c_void_p, C.c_int]),
     'mi_debug_tail_stamps': (C.c_int, [C.c_void_p, C.c_void_p]),

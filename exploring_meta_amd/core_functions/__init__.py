@@ -3,6 +3,7 @@ from .vision import fast_adapt, accuracy, evaluate, meta_batch_adapt, meta_batch
 from .vision_models import OmniglotCNN, MiniImagenetCNN, ConvBase, ConvBlock
 from .maml import MAML
 from .inner_lr import InnerLR
+from .step_offsets import StepOffsets
 from .anil import meta_batch_adapt_anil, meta_batch_adapt_anil_steps
 from ..utils.data_pre import prepare_batch
 from .policies import DiagNormalPolicy, DiagNormalPolicyANIL

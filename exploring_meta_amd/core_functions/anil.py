@@ -107,6 +107,8 @@ class _FusedAnilSteps(torch.autograd.Function):
 def _anil_call_args(learner, features, data, ways):
     """What every batched ANIL entry needs: (engine, head, parameters in the reference's optimizer order, first order?, lr_flat or None)."""
     head = learner.module if isinstance(learner, MAML) else learner
+    if isinstance(learner, MAML) and learner.offsets_flat() is not None:
+        raise NotImplementedError('per-step offsets are implemented for the fused MAML vision call, not for the ANIL head')
     if not isinstance(head, torch.nn.Linear) or head.out_features != ways:
         raise ValueError('ANIL learner must wrap torch.nn.Linear(fc_neurons, ways) (reference anil_vision.py:93)')
     base = _find_convbase(features)

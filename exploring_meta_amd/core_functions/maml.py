@@ -20,6 +20,9 @@ learner that was never adapted acts through the bare policy exactly as before.
 per entry / per inner step, learnable or not.  A learnable ``InnerLR`` is a submodule, so its values are among ``maml.parameters()``
 (learn2learn ``MetaSGD``).  ``allow_nograd=True`` gives parameters with ``requires_grad=False`` the step 0, in the fused call and in
 ``adapt`` (learn2learn's ``adapt`` skips them).
+
+``offsets`` is ``None`` or a ``StepOffsets`` (step_offsets.py): per-step parameter offsets, ``theta - lr * g + s_j`` after inner step j --
+MAML++'s per-step BatchNorm weights and biases.  It is a submodule too: a learnable one is among ``maml.parameters()``.
 """
 import copy
 
@@ -27,13 +30,17 @@ import copy
 import torch
 
 from .inner_lr import InnerLR
+from .step_offsets import StepOffsets
 
 
 class MAML(torch.nn.Module):
-    def __init__(self, model, lr, first_order=False, allow_unused=None, allow_nograd=False):
+    def __init__(self, model, lr, first_order=False, allow_unused=None, allow_nograd=False, offsets=None):
         super().__init__()
+        if offsets is not None and not isinstance(offsets, StepOffsets):
+            raise TypeError(f'offsets must be a StepOffsets or None, got {type(offsets).__name__}')
         self.module = model
         self.lr = lr                       # a number, or an InnerLR (a submodule: parameters when learnable, a buffer otherwise)
+        self.offsets = offsets             # None, or a StepOffsets (a submodule likewise)
         self.first_order = first_order
         self.allow_nograd = allow_nograd
         self.allow_unused = allow_nograd if allow_unused is None else allow_unused
@@ -64,6 +71,20 @@ class MAML(torch.nn.Module):
             return None
         return self._engine_order(torch.cat([torch.full((p.numel(),), 0.0 if not p.requires_grad else float(lr), dtype=torch.float32,
                                                         device=p.device) for p in self.module.parameters()]).unsqueeze(0))
+
+    def offsets_flat(self):
+        """None without per-step offsets; else the offsets [steps, P] in ``parameters()`` order (``StepOffsets.flat``)."""
+        return None if self.offsets is None else self.offsets.flat()
+
+    def _step_offset(self):
+        """The row of offsets this learner's next ``adapt`` adds after its update, or None."""
+        flat = self.offsets_flat()
+        if flat is None:
+            return None
+        k = self.__dict__['_steps_done']
+        if k >= flat.shape[0]:
+            raise RuntimeError(f'this learner holds offsets for {flat.shape[0]} inner steps and has taken {k}')
+        return flat[k]
 
     def _engine_order(self, flat):
         """Around a policy the step sizes leave in the ENGINE's parameter order (``_engine_params()``: sigma first), which is the order
@@ -162,7 +183,7 @@ class MAML(torch.nn.Module):
             allow_unused = self.allow_unused
         if allow_nograd is None:
             allow_nograd = self.allow_nograd
-        c = MAML(self.module, lr=self.lr, first_order=first_order, allow_unused=allow_unused, allow_nograd=allow_nograd)
+        c = MAML(self.module, lr=self.lr, first_order=first_order, allow_unused=allow_unused, allow_nograd=allow_nograd, offsets=self.offsets)
         c.__dict__['_fast'] = self.__dict__['_fast']
         c.__dict__['_steps_done'] = self.__dict__['_steps_done']
         return c
@@ -182,6 +203,9 @@ class MAML(torch.nn.Module):
         second_order = not first_order
         if allow_unused is None:
             allow_unused = self.allow_unused
+        s = self._step_offset()            # theta - lr * g + s: the row of the step this learner is at (autograd differentiates it)
+        if s is not None and self._is_policy():
+            raise NotImplementedError('per-step offsets are implemented for the fused MAML vision call')
         if self.__dict__['_fast'] is None and self._is_policy():
             # first step of a policy learner: the loss came from the parameters themselves (``_policy_theta``)
             params = self.module._engine_params()
@@ -194,7 +218,8 @@ class MAML(torch.nn.Module):
         if not theta.requires_grad:
             raise RuntimeError('learner.adapt needs parameters that require grad')
         (g,) = torch.autograd.grad(loss, theta, retain_graph=second_order, create_graph=second_order, allow_unused=bool(allow_unused))
-        self.__dict__['_fast'] = theta if g is None else theta - self._step_lr() * g
+        new = theta if g is None else theta - self._step_lr() * g
+        self.__dict__['_fast'] = new if s is None else new + s
         self.__dict__['_steps_done'] += 1
 
     def get_rep(self, input_d):

@@ -849,6 +849,8 @@ def _policy_lr_vector(learner):
     number for its policy; None for everything else -- the bare policy, a wrapper with a number: ``params['inner_lr']`` is the step."""
     if not (hasattr(learner, 'lr_flat') and hasattr(learner, 'module')):
         return None
+    if learner.offsets_flat() is not None:
+        raise NotImplementedError('per-step offsets are implemented for the fused MAML vision call, not for the policy calls')
     return learner.lr_flat()
 
 

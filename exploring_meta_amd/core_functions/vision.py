@@ -78,11 +78,75 @@ class _FusedFastAdapt(torch.autograd.Function):
         return (None,) * 10 + (lr_grad * gsum if lr_grad.numel() else None,) + split_grad(grad, ctx.shapes, gsum)
 
 
+class _FusedFastAdaptOffsets(torch.autograd.Function):
+    """``_FusedFastAdapt`` / ``_FusedFastAdaptSteps`` through mi_meta_batch_maml_offsets: per-step parameter offsets ``ofs_flat`` [steps, P]
+    (``MAML.offsets_flat()``) are one more input of the function, and ``backward`` hands autograd their gradient beside the model's and the
+    step sizes' (``StepOffsets.flat`` carries it to the stored values).  ``step_w`` None: the plain objective, the sum of the train tasks'
+    final query losses; else the multi-step loss."""
+
+    @staticmethod
+    def forward(ctx, engine, data, labels, shots, steps, lr, first_order, need_grad, need_lr_grad, need_ofs_grad, grad_tasks, step_w, lr_flat,
+                ofs_flat, *params):
+        theta = flat_theta(params)
+        lr_vec = None if lr_flat is None else lr_flat.detach().float().contiguous()
+        if lr_vec is not None and lr_vec.shape[0] not in (1, max(int(steps), 1)):
+            raise ValueError(f'the learner holds step sizes for {lr_vec.shape[0]} inner steps, the call adapts for {steps}')
+        if ofs_flat.shape[0] != int(steps):
+            raise ValueError(f'the learner holds per-step offsets for {ofs_flat.shape[0]} inner steps, the call adapts for {steps}')
+        offsets = ofs_flat.detach().float().contiguous()
+        gt = data.shape[0] if grad_tasks is None else int(grad_tasks)
+
+        def call(with_grad):
+            """(loss, acc, grad, lr_grad, offsets_grad) of the fused call, evaluation only or with the gradients."""
+            return engine.meta_batch_offsets(theta, data, labels, shots, steps, offsets, inner_lr=lr if lr_vec is None else None, lr_vec=lr_vec,
+                                             step_w=step_w, first_order=first_order, grad_tasks=gt if with_grad else 0,
+                                             want_lr_grad=with_grad and need_lr_grad and lr_vec is not None,
+                                             want_offsets_grad=with_grad and need_ofs_grad)[:5]
+        ctx.deferred = call if need_grad and DEFERRED_OUTER_BACKWARD else None
+        loss, acc, grad, lr_grad, ofs_grad = call(need_grad and ctx.deferred is None)
+        ctx.shapes = [p.shape for p in params]
+        empty = torch.empty(0, device=data.device)
+        ctx.save_for_backward(*(empty if t is None else t for t in (grad, lr_grad, ofs_grad)))
+        ctx.mark_non_differentiable(loss, acc)       # (values: only the objective carries the gradients, as in _FusedFastAdapt)
+        return (loss[:gt].sum() if step_w is None else (step_w.unsqueeze(1) * loss[1:, :gt]).sum()), loss, acc
+
+    @staticmethod
+    def backward(ctx, gsum, gloss, gacc):
+        grad, lr_grad, ofs_grad = ctx.saved_tensors
+        if ctx.deferred is not None:
+            _, _, grad, lr_grad, ofs_grad = ctx.deferred(True)
+            lr_grad = grad.new_empty(0) if lr_grad is None else lr_grad
+            ofs_grad = grad.new_empty(0) if ofs_grad is None else ofs_grad
+        if grad.numel() == 0:
+            raise RuntimeError('the fused call was run without gradients (torch.no_grad or no parameter requires grad)')
+        return (None,) * 12 + (lr_grad * gsum if lr_grad.numel() else None, ofs_grad * gsum if ofs_grad.numel() else None) + \
+            split_grad(grad, ctx.shapes, gsum)
+
+
+def _adapt_with_offsets(learner, model, data, labels, K, shots, fo, grad_tasks, step_w, ofs_flat):
+    """The offsets call of ``meta_batch_adapt`` (step_w None) and ``meta_batch_adapt_steps``."""
+    if not hasattr(model, 'spec') or not hasattr(model, 'engine'):
+        raise NotImplementedError('per-step offsets are implemented for the fused MAML vision call')
+    if ofs_flat.shape[0] != K:
+        raise ValueError(f'the learner holds per-step offsets for {ofs_flat.shape[0]} inner steps, adaptation_steps is {K} '
+                         '(StepOffsets(model, steps) must have one row per inner step)')
+    params = list(model.parameters())
+    ge = torch.is_grad_enabled()
+    need = ge and any(p.requires_grad for p in params)
+    lr_flat = learner.lr_flat()
+    need_lr = lr_flat is not None and ge and lr_flat.requires_grad
+    need_ofs = ge and ofs_flat.requires_grad
+    return _FusedFastAdaptOffsets.apply(model.engine(), data, labels.contiguous(), shots, K, learner.lr, fo, need or need_lr or need_ofs, need_lr,
+                                        need_ofs, grad_tasks, step_w, lr_flat, ofs_flat, *params)
+
+
 def meta_batch_adapt(learner, data, labels, adaptation_steps, shots, ways, first_order=None, grad_tasks=None):
     """Batched entry: data [T, 2*shots*ways, C, H, W], labels [T, 2*shots*ways] on the GPU.
     Returns (loss_sum, loss[T], acc[T]); ``loss_sum.backward()`` accumulates the SUM over tasks of d valid_loss/d theta
     into the base parameters' ``.grad`` -- what T iterations of the reference loop body leave there.  ``loss[T]`` and ``acc[T]``
     are plain values (not differentiable): weight tasks by scaling ``loss_sum``, or call once per group of tasks.
+    A learner with per-step offsets (``MAML(..., offsets=StepOffsets(...))``) takes mi_meta_batch_maml_offsets, and ``.backward()`` fills
+    ``StepOffsets.values.grad`` too; its offsets must hold ``adaptation_steps`` rows.
     ``grad_tasks = G``: the first G tasks are the iteration's train tasks (``loss_sum`` and the gradient cover them), the others its
     validation tasks (reference maml_vision.py:117-124), adapted and scored in the same launches without a backward half."""
     model = learner.module if isinstance(learner, MAML) else learner
@@ -94,6 +158,9 @@ def meta_batch_adapt(learner, data, labels, adaptation_steps, shots, ways, first
     if spec.ways != ways:
         raise ValueError(f'model has {spec.ways} outputs but ways={ways}')
     data = data.reshape(data.shape[0], data.shape[1], spec.in_channels, spec.in_h, spec.in_w).float().contiguous()
+    ofs_flat = learner.offsets_flat() if isinstance(learner, MAML) else None
+    if ofs_flat is not None:       # per-step offsets (StepOffsets): the offsets call, plain objective
+        return _adapt_with_offsets(learner, model, data, labels, int(adaptation_steps), shots, fo, grad_tasks, None, ofs_flat)
     lr_flat = learner.lr_flat() if isinstance(learner, MAML) else None
     # step sizes per parameter (InnerLR, allow_nograd): the vector call, whose step sizes may want a gradient too
     need_lr = lr_flat is not None and torch.is_grad_enabled() and lr_flat.requires_grad
@@ -170,6 +237,9 @@ def meta_batch_adapt_steps(learner, data, labels, adaptation_steps, shots, ways,
     if not torch.is_tensor(step_weights):
         step_weights = torch.tensor([float(w) for w in step_weights], dtype=torch.float32, device=data.device)
     data = data.reshape(data.shape[0], data.shape[1], spec.in_channels, spec.in_h, spec.in_w).float().contiguous()
+    ofs_flat = learner.offsets_flat() if isinstance(learner, MAML) else None
+    if ofs_flat is not None:       # per-step offsets (StepOffsets): the offsets call, multi-step loss
+        return _adapt_with_offsets(learner, model, data, labels, K, shots, fo, grad_tasks, step_weights, ofs_flat)
     lr_flat = learner.lr_flat() if isinstance(learner, MAML) else None
     need_lr = lr_flat is not None and torch.is_grad_enabled() and lr_flat.requires_grad
     return _FusedFastAdaptSteps.apply(engine, data, labels.contiguous(), shots, K, lr, fo, need or need_lr, need_lr, grad_tasks,

@@ -27,7 +27,7 @@ struct Layer {
   size_t off_gamma, off_beta, off_w, off_b;
 };
 
-typedef std::array<unsigned long long, 31> GraphKey;   // graph_key(): what a captured fused call depends on
+typedef std::array<unsigned long long, 33> GraphKey;   // graph_key(): what a captured fused call depends on
 struct mi_engine {
   mi_model_desc d;
   int device;
@@ -423,6 +423,7 @@ struct Plan {
   // direction lr_k * lam_{k+1} of the Hessian-vector passes [T][PS], twice (ping-pong, like lam / lam2), and the products g_k * lam_{k+1}
   // [K][T][PS] the step-size gradient sums
   float *lrv = nullptr, *dir = nullptr, *dir2 = nullptr, *prod = nullptr;
+  float* ofs = nullptr; // per-step parameter offsets (mi_meta_batch_maml_offsets) in engine layout [K][PS], else nullptr
   float* qg = nullptr;  // multi-step loss (mi_meta_batch_maml_steps) with a gradient: the query gradients q_1..q_K [K][T][PS], else nullptr
   float *xs, *xq;
   int32_t *ys, *yq;
@@ -490,7 +491,8 @@ static unsigned long long kernel_selection_key() {
 // a tangent set is planned; lr_steps > 0: the step-size-vector call's buffers (want_lr_grad: its products too).  Every size query and the call
 // it sizes build their shape with the same helper below, so the two cannot disagree.
 // steps (mi_meta_batch_maml_steps): 0 = not that call, 1 = its query passes at every theta_j, forward only, 2 = with their gradients.
-struct PlanShape { int T, ns, nq, K, second_order, lr_steps, want_lr_grad, steps; };
+// ofs (mi_meta_batch_maml_offsets): the K rows of per-step offsets in engine layout, behind everything else.
+struct PlanShape { int T, ns, nq, K, second_order, lr_steps, want_lr_grad, steps; int ofs = 0; };
 static PlanShape maml_shape(int tasks, int ways, int shots, int K, int second_order, int lr_steps, int want_lr_grad, int steps = 0) {
   return PlanShape{tasks, ways * shots, ways * shots, K, second_order, lr_steps, want_lr_grad, steps};
 }
@@ -619,6 +621,7 @@ static void make_plan(const mi_engine* e, void* ws, const PlanShape& s, Plan& pl
     }
   }
   if (s.steps == 2) pl.qg = b.take<float>(TP * K);
+  if (s.ofs) pl.ofs = b.take<float>((size_t)K * e->PS);
   pl.bytes = align_up(b.off, 256);
 }
 
@@ -711,6 +714,21 @@ extern "C" int mi_workspace_bytes_steps(const mi_engine* e, int tasks, int grad_
   if (!e || !bytes || tasks < 1 || grad_tasks < 0 || grad_tasks > tasks || ways < 1 || shots < 1 || adapt_steps < 1) return MI_ERR_ARG;
   if (lr_steps != 0 && !lr_steps_ok(lr_steps, adapt_steps)) return MI_ERR_ARG;
   return plan_bytes(e, steps_shape(tasks, grad_tasks, ways, shots, adapt_steps, second_order, lr_steps, want_lr_grad), bytes);
+}
+
+// mi_meta_batch_maml_offsets: the plain plan (with_steps = 0: step_w NULL) or the steps call's, lr_steps = 0 for the scalar step, plus the
+// offsets in engine layout.
+static PlanShape offsets_shape(int tasks, int grad_tasks, int ways, int shots, int K, int second_order, int lr_steps, int want_lr_grad, int with_steps) {
+  PlanShape s = with_steps ? steps_shape(tasks, grad_tasks, ways, shots, K, second_order, lr_steps, want_lr_grad)
+                           : maml_shape(tasks, ways, shots, K, (second_order && grad_tasks > 0) ? 1 : 0, lr_steps, want_lr_grad);
+  s.ofs = 1;
+  return s;
+}
+extern "C" int mi_workspace_bytes_offsets(const mi_engine* e, int tasks, int grad_tasks, int ways, int shots, int adapt_steps, int second_order,
+                                          int lr_steps, int want_lr_grad, int with_steps, size_t* bytes) {
+  if (!e || !bytes || tasks < 1 || grad_tasks < 0 || grad_tasks > tasks || ways < 1 || shots < 1 || adapt_steps < 1) return MI_ERR_ARG;
+  if (lr_steps != 0 && !lr_steps_ok(lr_steps, adapt_steps)) return MI_ERR_ARG;
+  return plan_bytes(e, offsets_shape(tasks, grad_tasks, ways, shots, adapt_steps, second_order, lr_steps, want_lr_grad, with_steps), bytes);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1183,7 +1201,9 @@ static AdvanceArgs advance_base(const mi_engine* e, float* g) {
 // are the per-step outputs, row j of K + 1 holding what the plain call writes for theta_j.  lr_vec may be null (scalar step) or not.
 // ALGO_ANIL_LR / ALGO_ANIL_STEPS (mi_meta_batch_anil_lr / _steps): the same fields read by meta_batch_anil_impl; lr_vec and lr_grad_out are
 // [lr_steps][Ph] (the head's entries only), grad_tasks is tasks or 0.
-enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS = 3, ALGO_ANIL_LR = 4, ALGO_ANIL_STEPS = 5 };
+// ALGO_MAML_OFFSETS (mi_meta_batch_maml_offsets): offsets = the [adapt_steps][P] per-step parameter offsets on the device, offsets_grad_out
+// their gradient or null; step_w null: the plain call's outputs and objective, else the steps call's; lr_vec null or not as in the steps call.
+enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS = 3, ALGO_ANIL_LR = 4, ALGO_ANIL_STEPS = 5, ALGO_MAML_OFFSETS = 6 };
 static bool is_anil(MetaAlgo a) { return a == ALGO_ANIL || a == ALGO_ANIL_LR || a == ALGO_ANIL_STEPS; }
 struct MetaCall {
   MetaAlgo algo;
@@ -1194,6 +1214,7 @@ struct MetaCall {
   float *loss_out, *acc_out, *meta_grad_out, *logits_out;
   void* workspace; size_t workspace_bytes;
   const float* step_w = nullptr;
+  const float* offsets = nullptr; float* offsets_grad_out = nullptr;
 };
 
 // Every check of a fused call that needs no plan: before the graph cache and before any HIP call.
@@ -1206,7 +1227,17 @@ static int check_call(mi_engine* e, const MetaCall& c) {
     if (e->trace) return fail(e, MI_ERR_ARG, "the debug trace does not cover mi_meta_batch_maml_steps");
     if (!c.lr_vec && c.lr_grad_out) return fail(e, MI_ERR_ARG, "lr_grad_out given without lr_vec");
   }
-  if (c.algo == ALGO_MAML_LR || (c.algo == ALGO_MAML_STEPS && c.lr_vec)) {
+  if (c.algo == ALGO_MAML_OFFSETS) {
+    if (c.adapt_steps < 1) return fail(e, MI_ERR_ARG, "mi_meta_batch_maml_offsets needs adapt_steps >= 1: row k of the offsets is added to theta_{k+1}");
+    if (!c.offsets) return fail(e, MI_ERR_ARG, "offsets is NULL: mi_meta_batch_maml_offsets takes adapt_steps * P offsets on the device");
+    if (c.offsets_grad_out && c.grad_tasks == 0)
+      return fail(e, MI_ERR_ARG, "offsets_grad_out given but grad_tasks = 0: the offset gradient is summed over the train tasks");
+    if (e->trace) return fail(e, MI_ERR_ARG, "the debug trace does not cover mi_meta_batch_maml_offsets");
+    if (!c.lr_vec && c.lr_grad_out) return fail(e, MI_ERR_ARG, "lr_grad_out given without lr_vec");
+  } else if (c.offsets || c.offsets_grad_out) {
+    return fail(e, MI_ERR_ARG, "per-step offsets are taken by mi_meta_batch_maml_offsets only");
+  }
+  if (c.algo == ALGO_MAML_LR || ((c.algo == ALGO_MAML_STEPS || c.algo == ALGO_MAML_OFFSETS) && c.lr_vec)) {
     if (!lr_steps_ok(c.lr_steps, c.adapt_steps))
       return fail(e, MI_ERR_ARG, "lr_steps = " + std::to_string(c.lr_steps) + " must be 1 or adapt_steps = " + std::to_string(c.adapt_steps) +
                                      (c.adapt_steps == 0 ? " (without inner steps: 1)" : ""));
@@ -1260,8 +1291,9 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
   const float inner_lr = c.inner_lr;
   e->export_pass = 0;
   Plan pl;
-  const bool msl = c.algo == ALGO_MAML_STEPS;      // query passes at every theta_j, the multi-step loss's terms in the adjoint recursion
+  const bool msl = c.algo == ALGO_MAML_STEPS || (c.algo == ALGO_MAML_OFFSETS && c.step_w);      // query passes at every theta_j, the multi-step loss's terms in the adjoint recursion
   const int prc = plan_in(e, c.workspace, c.workspace_bytes,
+                          c.offsets ? offsets_shape(T, Tg, c.ways, c.shots, K, so, c.lr_vec ? c.lr_steps : 0, c.lr_grad_out != nullptr, msl) :
                           msl ? steps_shape(T, Tg, c.ways, c.shots, K, so, c.lr_vec ? c.lr_steps : 0, c.lr_grad_out != nullptr)
                               : maml_shape(T, c.ways, c.shots, K, so, c.lr_vec ? c.lr_steps : 0, c.lr_grad_out != nullptr), pl);
   if (prc) return prc;
@@ -1276,6 +1308,8 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
   // the step sizes in engine layout, once per call (padding entries zero): row k of lr_of is D_k
   if (c.lr_vec) LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, c.lr_vec, e->P, e->perm_dev, (int)e->P, (int)e->PS, c.lr_steps, pl.lrv));
   auto lr_of = [&](int k) { return pl.lrv + (c.lr_steps == 1 ? 0 : (size_t)k * e->PS); };
+  // the per-step offsets in engine layout, once per call (padding entries zero): row k is s_{k+1}, added to theta_{k+1}
+  if (c.offsets) LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, c.offsets, e->P, e->perm_dev, (int)e->P, (int)e->PS, K, pl.ofs));
   if (pl.gram_s)
     LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, pl.xs, T, ns, e->L[0].h, e->L[0].w, e->L[0].ci, pl.gram_part, pl.gram_s));
   const double* gq = pl.gram_q;          // (also for forward-only calls and tasks: the same query forward whether or not a backward half follows)
@@ -1322,6 +1356,7 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
     if (tail) {   // g_k finished, theta_{k+1} = theta_k - lr g_k, and block 1's statistics of the next support pass
       adv.a = th; adv.out = th + TP; adv.alpha = inner_lr;
       if (c.lr_vec) adv.lr = lr_of(k);
+      if (c.offsets) adv.ofs = pl.ofs + (size_t)k * e->PS;      // theta_{k+1} = (theta_k - D_k g_k) + s_{k+1}, the statistics from the shifted weights
       if (pl.gram_s && k + 1 < K) {
         ActSet& An = so ? pl.sup[k + 1] : pl.sup[0];
         adv.stats = 1; adv.gram = pl.gram_s; adv.out0 = An.mu[0]; adv.out1 = An.rstd[0]; adv.inv_m = inv_m0;
@@ -1332,6 +1367,7 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
     } else {
       LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, th, gk, inner_lr, TP, th + TP));
     }
+    if (c.offsets && !tail) LAUNCH(e, st, OP_MISC, 2, launch_add_offsets(st, th + TP, pl.ofs + (size_t)k * e->PS, (int)e->PS, T));
   }
   float* thK = pl.theta + (size_t)K * TP;
   // the steps call with the fused tail: q_K is finished in pl.qg[K - 1] and lam_K = w_K q_K goes to pl.lam (AdvanceArgs::inj_w); without it the
@@ -1373,8 +1409,14 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
     LAUNCH(e, st, OP_MISC, 2, launch_advance(st, advq, Tg));
   }
   float *lam_cur = pl.lam, *lam_nxt = pl.lam2;
+  // offsets_grad[k] = sum_t lam_{k+1}: the offset is additive, so the recursion is unchanged and each complete lam_{k+1} (its w_{k+1} q_{k+1}
+  // in) is folded where it stands, before the pass that consumes it
+  auto ofs_fold = [&](const float* lam, int k) -> hipError_t {
+    return launch_offsets_grad_fold(st, lam, 0, e->perm_dev, (int)e->P, (int)e->PS, Tg, 1, c.offsets_grad_out + (size_t)k * e->P);
+  };
   if (so) {
     for (int k = K - 1; k >= 0; --k) {
+      if (c.offsets_grad_out) LAUNCH(e, st, OP_MISC, 3, ofs_fold(lam_cur, k));
       if (tr) HIPCHK(e, launch_scatter_tasks(st, lam_cur, e->perm_dev, (int)e->P, (int)e->PS, T, e->trace + (size_t)(2 * K + 1 + k) * TPr));
       if (c.lr_vec && !tail) {   // the separate launches of the vector form: dir = D_k lam, the products; below lam -= 1 * H dir
         LAUNCH(e, st, OP_MISC, 2, launch_scale_vec(st, lam_cur, lr_of(k), (int)e->PS, Tg, dir_cur));
@@ -1402,9 +1444,12 @@ static int meta_batch_maml_impl(mi_engine* e, void* stream, const MetaCall& c) {
     }
   } else if (msl) {   // first order: lam_k = sum_{j >= max(k, 1)} w_j q_j, the products g_k * lam_{k+1} of the step-size gradient on the way down
     for (int k = K - 1; k >= 0; --k) {
+      if (c.offsets_grad_out) LAUNCH(e, st, OP_MISC, 3, ofs_fold(pl.lam, k));
       if (pl.prod) LAUNCH(e, st, OP_MISC, 2, launch_product(st, pl.g + (size_t)k * TP, pl.lam, (int)e->PS, Tg, pl.prod + (size_t)k * TP));
       if (k > 0) LAUNCH(e, st, OP_MISC, 2, launch_fma_dev(st, pl.lam, pl.qg + (size_t)(k - 1) * TP, c.step_w + (k - 1), (size_t)Tg * e->PS));
     }
+  } else if (c.offsets_grad_out) {   // first order, plain objective: every lam_{k+1} is the constant lam_K, the K rows in one launch
+    LAUNCH(e, st, OP_MISC, 3, launch_offsets_grad_fold(st, pl.lam, 0, e->perm_dev, (int)e->P, (int)e->PS, Tg, K, c.offsets_grad_out));
   }
   if (tr) {
     for (int k = 0; k <= K; ++k)
@@ -1654,7 +1699,7 @@ static GraphKey graph_key(const mi_engine* e, void* stream, const MetaCall& c) {
                   (u)c.lr_steps, (u)(uintptr_t)c.lr_grad_out, (u)(uintptr_t)c.loss_out, (u)(uintptr_t)c.acc_out,
                   (u)(uintptr_t)c.meta_grad_out, (u)(uintptr_t)c.logits_out, (u)(uintptr_t)c.workspace, (u)c.workspace_bytes,
                   (u)e->fuse1, (u)e->gram1, (u)e->gramq, (u)e->overlap, (u)e->fuse_fin, (u)e->fuse_b1red, (u)e->fuse_tail, (u)e->fuse_last,
-                  kernel_selection_key(), (u)(uintptr_t)c.step_w};
+                  kernel_selection_key(), (u)(uintptr_t)c.step_w, (u)(uintptr_t)c.offsets, (u)(uintptr_t)c.offsets_grad_out};
 }
 
 static int meta_batch_entry(mi_engine* e, void* stream, const MetaCall& c) {
@@ -1742,6 +1787,20 @@ extern "C" int mi_meta_batch_maml_steps(mi_engine* e, void* stream, const float*
   MetaCall c{ALGO_MAML_STEPS, theta, data, labels, tasks, grad_tasks, ways, shots, adapt_steps, second_order, lr_vec ? 0.f : inner_lr, lr_vec,
              lr_vec ? lr_steps : 0, lr_grad_out, loss_steps_out, acc_steps_out, meta_grad_out, logits_steps_out, workspace, workspace_bytes};
   c.step_w = step_w;
+  return meta_batch_entry(e, stream, c);
+}
+// mi_meta_batch_maml_tv / _lr / _steps with per-step parameter offsets theta_{k+1} = (theta_k - D_k g_k) + offsets[k] and their gradient
+// (include/mi_maml.h).  step_w NULL: the plain call's outputs and objective.
+extern "C" int mi_meta_batch_maml_offsets(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels, int tasks,
+                                          int grad_tasks, int ways, int shots, int adapt_steps, float inner_lr, const float* lr_vec, int lr_steps,
+                                          const float* step_w, const float* offsets, int second_order, float* loss_out, float* acc_out,
+                                          float* meta_grad_out, float* lr_grad_out, float* offsets_grad_out, float* logits_out, void* workspace,
+                                          size_t workspace_bytes) {
+  MetaCall c{ALGO_MAML_OFFSETS, theta, data, labels, tasks, grad_tasks, ways, shots, adapt_steps, second_order, lr_vec ? 0.f : inner_lr, lr_vec,
+             lr_vec ? lr_steps : 0, lr_grad_out, loss_out, acc_out, meta_grad_out, logits_out, workspace, workspace_bytes};
+  c.step_w = step_w;
+  c.offsets = offsets;
+  c.offsets_grad_out = offsets_grad_out;
   return meta_batch_entry(e, stream, c);
 }
 extern "C" int mi_meta_batch_anil(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,

@@ -759,17 +759,27 @@ __device__ __forceinline__ float advance_step(const AdvanceArgs& a, unsigned e) 
 // on the device -- lam_k = fmaf(w_k, q_k, a - step * g) applied to the unchanged update expression, or (a.inj == nullptr: the launch finishes
 // the last query gradient g = q_K, a.a is not read) lam_K = w_K * g into out; g itself stays unscaled, the row workgroups read its block-1
 // dgamma / dbeta.  The term is in `fin` before advance_vec_tail forms dir / prod, and its block-1 entries take the stores the statistics' last
-// arriver reads back.  The two other instantiations compile without any of it.
-template <bool VEC, bool INJ>
+// arriver reads back.  The instantiations without INJ compile without any of it.
+// OFS (mi_meta_batch_maml_offsets, on top of VEC, never with INJ): the launch finishes a fast weight theta_{k+1} of a call that carries
+// per-step offsets.  The unchanged update expression first, u = a - step * g, then res = (s == 0) ? u : u + s with s = a.ofs[e] (row k of the
+// offsets in engine layout): a zero offset leaves the element's bits, signed zeros included.  res is what the caller stores -- chunk and
+// block-1 row workgroups alike, through the write-through stores the statistics' last arriver reads back -- so everything that reads
+// theta_{k+1} sees the shifted value.  The three other instantiations compile without any of it.
+template <bool VEC, bool INJ, bool OFS>
 __device__ __forceinline__ float advance_result(const AdvanceArgs& a, int task, unsigned e, float gv) {
   if constexpr (INJ) {
     const float w = *a.inj_w;
     if (!a.inj) return w * gv;
     return fmaf(w, a.inj[(size_t)task * a.ostride + e], a.a[(size_t)task * a.ostride + e] - advance_step<VEC>(a, e) * gv);
   }
+  if constexpr (OFS) {
+    const float u = a.a[(size_t)task * a.ostride + e] - advance_step<VEC>(a, e) * gv;
+    const float s = a.ofs[e];
+    return (s == 0.0f) ? u : u + s;
+  }
   return a.a[(size_t)task * a.ostride + e] - advance_step<VEC>(a, e) * gv;
 }
-template <bool VEC, bool INJ = false>
+template <bool VEC, bool INJ = false, bool OFS = false>
 __global__ __launch_bounds__(1024) void advance_kernel(AdvanceArgs a, int ng, int kp, int S, int nchunk_wg, unsigned arrivals) {
   extern __shared__ double sm[];
   const int task = blockIdx.y, tid = threadIdx.x;
@@ -798,7 +808,7 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceArgs a, int ng, in
       }
       float fin = gv;
       if (a.out) {
-        const float res = advance_result<VEC, INJ>(a, task, e, gv);
+        const float res = advance_result<VEC, INJ, OFS>(a, task, e, gv);
         float* o = a.out + (size_t)task * a.ostride + e;
         if (in_w1) __hip_atomic_store(o, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else *o = res;
@@ -835,7 +845,7 @@ __global__ __launch_bounds__(1024) void advance_kernel(AdvanceArgs a, int ng, in
       else g_t[e] = gv;
       float fin = gv;
       if (a.out) {
-        const float res = advance_result<VEC, INJ>(a, task, e, gv);
+        const float res = advance_result<VEC, INJ, OFS>(a, task, e, gv);
         float* o = a.out + (size_t)task * a.ostride + e;
         if (a.stats) __hip_atomic_store(o, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else *o = res;
@@ -1036,7 +1046,10 @@ hipError_t launch_advance(hipStream_t st, const AdvanceArgs& a_in, int tasks) {
   if (smem < 4160 + (size_t)1024 * sizeof(double)) smem = 4160 + (size_t)1024 * sizeof(double);
   if (a.inj_w && (!a.out || (a.inj && !a.a) || a.out == a.g)) return hipErrorInvalidValue;
   if (!a.inj_w && a.out && !a.a) return hipErrorInvalidValue;
-  if (a.inj_w || a.lr || a.dir) {
+  if (a.ofs) {      // a fast weight of a call that carries offsets: no adjoint vector is finished here
+    if (!a.out || !a.a || a.inj_w || a.inj || a.dir || a.out == a.g) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((advance_kernel<true, false, true>), dim3(nchunk_wg + nrow_wg, tasks), dim3(1024), smem, st, a, ng, kp, S, nchunk_wg, arrivals);
+  } else if (a.inj_w || a.lr || a.dir) {
     if (a.dir && (!a.dlr || (a.prod && !a.dg))) return hipErrorInvalidValue;
     // the row workgroups read the direction this pass was driven with (gw.wd, gammad): the new one goes to another buffer
     if (a.dir && a.b1_wgrad && a.gw_tangent && a.dir + a.off_w1 == a.gw.wd) return hipErrorInvalidValue;

@@ -212,6 +212,11 @@ struct AdvanceArgs {
   const float* inj;                          // out != nullptr: out = fmaf(*inj_w, inj[task][e], a - step * g), inj [T][ostride] (a query gradient q_j);
                                              // out == nullptr: the finished g itself is scaled, g = *inj_w * g (lam_K = w_K q_K).  Either way the
                                              // term is in before dir, prod and the statistics are formed, and under the same write-through stores
+  // Per-step parameter offsets (mi_meta_batch_maml_offsets).  ofs set selects the kernel's offset instantiation (the vector one plus this
+  // term); only launches that finish a fast weight theta_{k+1} set it (out = theta_{k+1}; no inj_w, no dir).
+  const float* ofs;                          // [n] row k of the offsets in engine layout, shared by the tasks: with u = a - step * g,
+                                             // out = (ofs[e] == 0) ? u : u + ofs[e] -- formed before the statistics are taken from it, stored
+                                             // by the same write-through stores
 };
 hipError_t launch_advance(hipStream_t st, const AdvanceArgs& a, int tasks);
 
@@ -298,6 +303,12 @@ hipError_t launch_product(hipStream_t st, const float* a, const float* b, int ps
 // multi-step loss without the one-launch advance, one weight *w on the device:  x = *w * x;  x = fmaf(*w, q, x)  (x, q [n])
 hipError_t launch_scale_dev(hipStream_t st, float* x, const float* w, size_t n);
 hipError_t launch_fma_dev(hipStream_t st, float* x, const float* q, const float* w, size_t n);
+// per-step parameter offsets without the one-launch advance (s [pstride], shared by the tasks; x [tasks][pstride]):  x = (s == 0) ? x : x + s
+hipError_t launch_add_offsets(hipStream_t st, float* x, const float* s, int pstride, int tasks);
+// out_ref[r][perm[i]] = sum over tasks t < grad_tasks of lam[r * row_stride + t * pstride + i], r < rows: one fp64 chain in task order,
+// rounded once (row_stride 0: every row from the same lam)
+hipError_t launch_offsets_grad_fold(hipStream_t st, const float* lam, size_t row_stride, const int32_t* perm, int p, int pstride,
+                                    int grad_tasks, int rows, float* out_ref);
 // out_ref[s][perm[i]] = -sum over the steps k of s (all K when lr_steps == 1, else k == s), then over tasks t < grad_tasks, of
 // prod[k][t][i] (prod != nullptr) or g[k][t][i] * lam[t][i] (first order): fp32 products, one fp64 chain in that fixed order, rounded once
 hipError_t launch_lr_grad_fold(hipStream_t st, const float* prod, const float* g, const float* lam, const int32_t* perm, int p, int pstride,

@@ -166,6 +166,26 @@ __global__ void fma_dev_kernel(float* __restrict__ x, const float* __restrict__ 
   if (o < n) x[o] = fmaf(*w, q[o], x[o]);
 }
 
+// Per-step parameter offsets (mi_meta_batch_maml_offsets) without the one-launch advance, behind axpy / axpy_vec: theta_{k+1} += s_{k+1}.
+// The select is the advance kernel's: a zero offset leaves the element's bits, signed zeros included.
+__global__ void add_offsets_kernel(float* __restrict__ x, const float* __restrict__ s, int pstride, size_t n) {
+  const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= n) return;
+  const float u = x[o], sv = s[o % pstride];
+  x[o] = (sv == 0.0f) ? u : u + sv;
+}
+// offsets_grad[r][perm[i]] = sum_t lam_{r+1}[t][i] over the train tasks: one fp64 chain in task order, rounded once, scattered to the
+// reference's order like scatter_sum -- no atomics, bitwise reproducible.  grid (ceil(p / 256), rows).
+__global__ void offsets_grad_fold_kernel(const float* __restrict__ lam, size_t row_stride, const int32_t* __restrict__ perm, int p, int pstride,
+                                         int grad_tasks, float* __restrict__ out_ref) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p) return;
+  const float* l = lam + (size_t)blockIdx.y * row_stride;
+  double acc = 0.0;
+  for (int t = 0; t < grad_tasks; ++t) acc += (double)l[(size_t)t * pstride + i];
+  out_ref[(size_t)blockIdx.y * p + perm[i]] = (float)acc;
+}
+
 // lr_grad[s][perm[i]] = -sum_k sum_t g_k[t][i] * lam_{k+1}[t][i]: the products are fp32 (stored by the advance launches, or formed here
 // from g and the constant lam of a first-order call), their sum is one fp64 chain over (step, task) in that order, rounded once.
 // grid (ceil(p / 256), lr_steps).
@@ -302,6 +322,17 @@ hipError_t launch_scale_dev(hipStream_t st, float* x, const float* w, size_t n) 
 }
 hipError_t launch_fma_dev(hipStream_t st, float* x, const float* q, const float* w, size_t n) {
   hipLaunchKernelGGL(fma_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, q, w, n);
+  return hipGetLastError();
+}
+hipError_t launch_add_offsets(hipStream_t st, float* x, const float* s, int pstride, int tasks) {
+  const size_t n = (size_t)tasks * pstride;
+  hipLaunchKernelGGL(add_offsets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, s, pstride, n);
+  return hipGetLastError();
+}
+hipError_t launch_offsets_grad_fold(hipStream_t st, const float* lam, size_t row_stride, const int32_t* perm, int p, int pstride,
+                                    int grad_tasks, int rows, float* out_ref) {
+  hipLaunchKernelGGL(offsets_grad_fold_kernel, dim3(ceil_div(p, 256), rows), dim3(256), 0, st, lam, row_stride, perm, p, pstride, grad_tasks,
+                     out_ref);
   return hipGetLastError();
 }
 hipError_t launch_lr_grad_fold(hipStream_t st, const float* prod, const float* g, const float* lam, const int32_t* perm, int p, int pstride,

@@ -254,11 +254,22 @@ class MetaEngine:
         return T
 
     def _maml_call(self, theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, first_order, grad_tasks, want_lr_grad, return_logits,
-                   step_w=None):
+                   step_w=None, offsets=None, want_offsets_grad=False):
         """mi_meta_batch_maml_tv, or mi_meta_batch_maml_lr when the step sizes are a vector, or -- step_w given -- mi_meta_batch_maml_steps
-        with either kind of step (loss, acc and logits then carry a leading axis of adapt_steps + 1).  Returns (loss, acc, grad, lr_grad, logits)."""
+        with either kind of step (loss, acc and logits then carry a leading axis of adapt_steps + 1).  Returns (loss, acc, grad, lr_grad, logits).
+        offsets given: mi_meta_batch_maml_offsets with any of those forms, and offsets_grad as a sixth result."""
         s = self.spec
         T = self._check_batch(theta, data, labels, shots, lr_vec)
+        if offsets is not None:
+            # the library reads adapt_steps * P floats at offsets on the device: anything else is refused here, before any launch
+            if adapt_steps < 1:
+                raise _lib.MiError('libmi_maml error -1: meta_batch_offsets needs adapt_steps >= 1')
+            if not torch.is_tensor(offsets) or offsets.dtype != torch.float32 or not offsets.is_cuda or offsets.device != theta.device or \
+                    not offsets.is_contiguous() or tuple(offsets.shape) != (adapt_steps, self.param_count):
+                raise _lib.MiError(f'libmi_maml error -1: offsets must be a contiguous fp32 tensor of shape ({adapt_steps}, {self.param_count}) '
+                                   f'on {theta.device}')
+            if want_offsets_grad and grad_tasks == 0:
+                raise _lib.MiError('libmi_maml error -1: offsets_grad wanted but grad_tasks = 0: the offset gradient is summed over the train tasks')
         if step_w is not None:
             # the library reads adapt_steps floats at step_w on the device: anything else is refused here, before any launch
             if adapt_steps < 1:
@@ -277,7 +288,14 @@ class MetaEngine:
             raise ValueError(f'grad_tasks must be in 0..{T}, got {grad_tasks}')
         with_grad = grad_tasks > 0
         so = (not first_order) and with_grad
-        b = C.c_size_t(0 if lr_vec is not None or step_w is not None else self.workspace_bytes(T, shots, adapt_steps, so))
+        b = C.c_size_t(0 if lr_vec is not None or step_w is not None or offsets is not None else self.workspace_bytes(T, shots, adapt_steps, so))
+        if offsets is not None:
+            if self.lib.mi_workspace_bytes_offsets(self._h, T, int(grad_tasks), s.ways, shots, adapt_steps, int(so),
+                                                   lr_steps if lr_vec is not None else 0, int(bool(want_lr_grad)), int(step_w is not None),
+                                                   C.byref(b)):
+                raise _lib.MiError(f'libmi_maml error -1: lr_steps must be 1 or adapt_steps = {adapt_steps}')
+            return self._offsets_call(theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, first_order, grad_tasks, want_lr_grad,
+                                      return_logits, step_w, offsets, want_offsets_grad, T, self._workspace(b.value))
         if step_w is not None:
             if self.lib.mi_workspace_bytes_steps(self._h, T, int(grad_tasks), s.ways, shots, adapt_steps, int(so),
                                                  lr_steps if lr_vec is not None else 0, int(bool(want_lr_grad)), C.byref(b)):
@@ -326,6 +344,52 @@ class MetaEngine:
                               int(not first_order), _ptr(loss), _ptr(acc), _ptr(grad), _ptr(lr_grad), _ptr(logits), _ptr(ws), ws.numel())
         _lib.check(rc, self._h)
         return loss, acc, grad, lr_grad, logits
+
+    def _offsets_call(self, theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, first_order, grad_tasks, want_lr_grad, return_logits,
+                      step_w, offsets, want_offsets_grad, T, ws):
+        """The C call of `_maml_call` for mi_meta_batch_maml_offsets: the plain outputs [T, ...], or with step_w [adapt_steps + 1, T, ...]."""
+        s = self.spec
+        lead = () if step_w is None else (adapt_steps + 1,)
+        with_grad = grad_tasks > 0
+        lr_steps = 0 if lr_vec is None else lr_vec.numel() // self.param_count
+        P = self.param_count
+
+        def fresh():
+            return (torch.empty(*lead, T, dtype=torch.float32, device=self.device), torch.empty(*lead, T, dtype=torch.float32, device=self.device),
+                    torch.empty(P, dtype=torch.float32, device=self.device) if with_grad else None,
+                    torch.empty(*lead, T, shots * s.ways, s.ways, dtype=torch.float32, device=self.device) if return_logits else None)
+        loss, acc, grad, logits = self._persistent(('offsets', lr_vec is None, lead, adapt_steps, T, shots * s.ways, with_grad, bool(return_logits)),
+                                                   fresh)
+        lr_grad = offsets_grad = None
+        if lr_vec is not None and want_lr_grad:
+            lr_grad = self._persistent(('lr_grad_offsets', T, lr_steps), lambda: torch.empty(lr_steps, P, dtype=torch.float32, device=self.device))
+        if want_offsets_grad:
+            offsets_grad = self._persistent(('offsets_grad', T, adapt_steps),
+                                            lambda: torch.empty(adapt_steps, P, dtype=torch.float32, device=self.device))
+        rc = self._fused_call(self.lib.mi_meta_batch_maml_offsets, _ptr(theta), _ptr(data), _ptr(labels), T, int(grad_tasks), s.ways, shots,
+                              adapt_steps, float(inner_lr) if lr_vec is None else 0.0, _ptr(lr_vec), lr_steps, _ptr(step_w), _ptr(offsets),
+                              int(not first_order), _ptr(loss), _ptr(acc), _ptr(grad), _ptr(lr_grad), _ptr(offsets_grad), _ptr(logits), _ptr(ws),
+                              ws.numel())
+        _lib.check(rc, self._h)
+        return loss, acc, grad, lr_grad, logits, offsets_grad
+
+    @_on_device
+    def meta_batch_offsets(self, theta, data, labels, shots, adapt_steps, offsets, inner_lr=None, lr_vec=None, step_w=None, first_order=False,
+                           grad_tasks=None, want_lr_grad=False, want_offsets_grad=False, return_logits=False):
+        """`meta_batch` / `meta_batch_lr` / `meta_batch_steps` with per-step parameter offsets (mi_meta_batch_maml_offsets): inner step k
+        ends in theta_{k+1} = (theta_k - D_k g_k) + offsets[k].  offsets [adapt_steps, P] contiguous fp32 on the engine's device,
+        parameters() order, shared by the tasks; its values are read on the device by every call, graph replays included.  inner_lr (a
+        number) or lr_vec; step_w None: the plain objective and outputs [T, ..], else the multi-step loss and outputs [K + 1, T, ..].
+        Returns (loss, acc, meta_grad [P] or None, lr_grad or None, offsets_grad [adapt_steps, P] or None, logits or None);
+        offsets_grad (``want_offsets_grad``) is the gradient of the train tasks' summed objective with respect to offsets."""
+        if (inner_lr is None) == (lr_vec is None):
+            raise ValueError('meta_batch_offsets takes exactly one of inner_lr and lr_vec')
+        if offsets is None:
+            raise ValueError('meta_batch_offsets needs offsets [adapt_steps, P]')
+        loss, acc, grad, lr_grad, logits, offsets_grad = self._maml_call(
+            theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, first_order, data.shape[0] if grad_tasks is None else grad_tasks,
+            want_lr_grad, return_logits, step_w=step_w, offsets=offsets, want_offsets_grad=want_offsets_grad)
+        return loss, acc, grad, lr_grad, offsets_grad, logits
 
     @_on_device
     def meta_batch_steps(self, theta, data, labels, shots, adapt_steps, step_w, inner_lr=None, lr_vec=None, first_order=False, grad_tasks=None,

@@ -18,7 +18,7 @@ import random
 import numpy as np
 import torch
 
-from ..core_functions import MAML, InnerLR, MiniImagenetCNN, OmniglotCNN, evaluate, meta_batch_adapt, meta_batch_adapt_steps, msl_weights
+from ..core_functions import MAML, InnerLR, StepOffsets, MiniImagenetCNN, OmniglotCNN, evaluate, meta_batch_adapt, meta_batch_adapt_steps, msl_weights
 from ..core_functions.vision_models import RunningStatsFold
 from ..sharding import init_process_group, reduce_meta_batch, shard_range
 from ..utils import synthetic
@@ -50,9 +50,21 @@ def inner_lr_of(model, p):
     --inner_lr_per / --learn_inner_lr / --per_step_lr / --freeze asks for step sizes per parameter."""
     per, learn, per_step, freeze = p.get('inner_lr_per', 'scalar'), p.get('learn_inner_lr', False), p.get('per_step_lr', False), \
         tuple(p.get('freeze') or ())
+    if p.get('per_step_bn') and not p.get('per_step_bn_adapt_bn'):
+        # MAML++'s default: the BatchNorm tensors carry per-step offsets and leave the inner loop (step size 0)
+        freeze += tuple(n for n in StepOffsets(model, 1, 'bn', learnable=False).bn_prefixes() if not any(n.startswith(f) for f in freeze))
     if per == 'scalar' and not learn and not per_step and not freeze:
         return p['inner_lr']
     return InnerLR(model, p['inner_lr'], per=per, steps=max(p['adapt_steps'], 1) if per_step else 1, learnable=learn, frozen=freeze)
+
+
+def step_offsets_of(model, p):
+    """The ``offsets`` argument of ``MAML``: None (today's run) unless --per_step_bn asks for per-step BatchNorm weights and biases."""
+    if not p.get('per_step_bn'):
+        return None
+    if p['adapt_steps'] < 1:
+        raise ValueError('--per_step_bn needs --adapt_steps >= 1')
+    return StepOffsets(model, p['adapt_steps'], 'bn')
 
 
 def run(dataset, p, first_order=False, log=print):
@@ -65,8 +77,12 @@ def run(dataset, p, first_order=False, log=print):
     random.seed(p['seed']); np.random.seed(p['seed']); torch.manual_seed(p['seed']); torch.cuda.manual_seed(p['seed'])
     device = torch.device('cuda', local)
     model = (OmniglotCNN(p['ways']) if dataset == 'omni' else MiniImagenetCNN(p['ways'])).to(device)
-    maml = MAML(model, lr=inner_lr_of(model, p), first_order=first_order)
+    maml = MAML(model, lr=inner_lr_of(model, p), first_order=first_order, offsets=step_offsets_of(model, p))
     opt = torch.optim.Adam(maml.parameters(), p['outer_lr'])
+    # MAML++'s cosine outer schedule over the run (--cosine_outer_lr); None: the constant outer_lr, today's run
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=max(p['num_iterations'], 1), eta_min=p.get('min_outer_lr', 0.0)) \
+        if p.get('cosine_outer_lr') else None
+    fo_its = int(p.get('first_order_iterations', 0))      # MAML++'s derivative-order annealing: iterations < N make the first-order call
     loss = torch.nn.CrossEntropyLoss(reduction='mean')
     T = p['meta_batch_size']
     lo, hi = shard_range(T, rank, world)
@@ -82,10 +98,11 @@ def run(dataset, p, first_order=False, log=print):
     def adapt(it, data, labels, grad_tasks=None):
         """One fused call for these tasks: the multi-step loss of MAML++ while it < --msl_iterations (--multi_step_loss), else the plain call.
         (objective, losses [T], accs [T]) -- the logged loss and accuracy are those of the last step either way."""
+        learner = maml.clone(first_order=True) if it < fo_its else maml.clone()
         if it >= msl_its or not torch.is_grad_enabled():
-            return meta_batch_adapt(maml.clone(), data, labels, p['adapt_steps'], p['shots'], p['ways'], grad_tasks=grad_tasks)
+            return meta_batch_adapt(learner, data, labels, p['adapt_steps'], p['shots'], p['ways'], grad_tasks=grad_tasks)
         step_w.copy_(torch.tensor(msl_weights(p['adapt_steps'], it, msl_its)))
-        total, losses, accs = meta_batch_adapt_steps(maml.clone(), data, labels, p['adapt_steps'], p['shots'], p['ways'], step_weights=step_w,
+        total, losses, accs = meta_batch_adapt_steps(learner, data, labels, p['adapt_steps'], p['shots'], p['ways'], step_weights=step_w,
                                                      grad_tasks=grad_tasks)
         return total, losses[-1], accs[-1]
 
@@ -127,6 +144,8 @@ def run(dataset, p, first_order=False, log=print):
             q.grad = g.clone() if q.grad is None else q.grad.copy_(g)
             off += q.numel()
         opt.step()
+        if sched is not None:
+            sched.step()
         metrics = {'train_loss': (lsum / T).item(), 'train_acc': (asum / T).item(),
                    'valid_loss': (vlsum / T).item(), 'valid_acc': (vasum / T).item()}
         if rank == 0:
@@ -141,6 +160,8 @@ def run(dataset, p, first_order=False, log=print):
         torch.save(model.state_dict(), os.path.join(save_dir, 'model.pt'))       # utils/experiment.py:85-87
         if isinstance(maml.lr, InnerLR):
             torch.save(maml.lr.state_dict(), os.path.join(save_dir, 'inner_lr.pt'))
+        if maml.offsets is not None:
+            torch.save(maml.offsets.state_dict(), os.path.join(save_dir, 'step_offsets.pt'))
     return model, metrics
 
 
@@ -160,6 +181,13 @@ def build_parser():
                         help='MAML++ multi-step loss: the outer objective weights the query loss after every inner step (msl_weights)')
     parser.add_argument('--msl_iterations', type=int, default=0, metavar='N',
                         help='iterations over which the multi-step weights anneal to the final step; from iteration N on the plain call runs')
+    parser.add_argument('--per_step_bn', action='store_true',
+                        help='MAML++ per-step BatchNorm weights and biases: learnable per-step offsets on the BatchNorm tensors, which leave the inner loop')
+    parser.add_argument('--per_step_bn_adapt_bn', action='store_true', help='with --per_step_bn: the BatchNorm tensors stay in the inner loop')
+    parser.add_argument('--first_order_iterations', type=int, default=0, metavar='N',
+                        help='MAML++ derivative-order annealing: iterations < N make the first-order call')
+    parser.add_argument('--cosine_outer_lr', action='store_true', help='cosine-anneal the outer learning rate over num_iterations')
+    parser.add_argument('--min_outer_lr', type=float, default=0.0, metavar='X', help='the floor of --cosine_outer_lr')
     return parser
 
 
@@ -167,7 +195,9 @@ def params_of(args):
     """The run's parameter dict from parsed flags (the defaults are the reference's run)."""
     p = {k: getattr(args, k) for k in params}
     p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
-             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations)
+             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations,
+             per_step_bn=args.per_step_bn, per_step_bn_adapt_bn=args.per_step_bn_adapt_bn, first_order_iterations=args.first_order_iterations,
+             cosine_outer_lr=args.cosine_outer_lr, min_outer_lr=args.min_outer_lr)
     return p
 
 

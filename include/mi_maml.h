@@ -189,6 +189,36 @@ int mi_meta_batch_maml_steps(mi_engine* e, void* stream, const float* theta, con
                              const float* step_w, int second_order, float* loss_steps_out, float* acc_steps_out, float* meta_grad_out,
                              float* lr_grad_out, float* logits_steps_out, void* workspace, size_t workspace_bytes);
 
+/* The calls above with PER-STEP PARAMETER OFFSETS, shared by all tasks and meta-learned with the model: inner step k ends in
+ *   theta_{k+1} = (theta_k - D_k g_k) + offsets[k]            k = 0..K-1   (D_k: the scalar step inner_lr, or row k of lr_vec)
+ * MAML++'s per-step BatchNorm weights and biases (Antoniou et al., 2019) are the preset whose offsets are non-zero on the BatchNorm
+ * tensors only, with those tensors' inner step sizes 0: theta_j then carries gamma + offsets[0] + .. + offsets[j-1].  The reference has
+ * no counterpart.  The objective is the steps call's J = sum_{t < grad_tasks} sum_j step_w[j - 1] L_query,t(theta_j), or with step_w NULL
+ * the plain L_query(theta_K).  The offset is additive, so d theta_{k+1} / d theta_k and with it the adjoint recursion are unchanged
+ * (evaluated on the shifted trajectory), and lam_{k+1} is the total derivative of J with respect to theta_{k+1}:
+ *   offsets_grad[k] = sum_{t < grad_tasks} lam_{k+1,t}         meta_grad and lr_grad keep their formulas
+ *   offsets          [adapt_steps, P]  device memory, fp32, the reference's parameter order and layout; required.  Like lr_vec the VALUES
+ *                                      are read on the device by every call, graph replays included: update the buffer in place.
+ *   offsets_grad_out [adapt_steps, P]  or NULL; needs grad_tasks > 0.  Each row is one fixed-order fp64 chain over the train tasks, rounded
+ *                                      once: bitwise reproducible.
+ *   step_w           NULL: loss_out / acc_out [tasks], logits_out [tasks, ..] and the launches of mi_meta_batch_maml_tv / _lr;
+ *                    else [adapt_steps] and the [adapt_steps + 1, tasks, ..] outputs of mi_meta_batch_maml_steps.
+ *   lr_vec           NULL (the scalar inner_lr) or as in mi_meta_batch_maml_steps.
+ * The finished element is u = a - step * g first, then (s == 0) ? u : u + s: with all offsets zero every output has the bits of the same
+ * call without offsets, signed zeros included.  MI_ERR_ARG before any launch: adapt_steps < 1, offsets NULL, offsets_grad_out with
+ * grad_tasks == 0, lr_grad_out without lr_vec, a debug trace being set, and what the calls above refuse.  Launches beyond the same call
+ * without offsets: + 1 (the offsets into engine layout); with offsets_grad_out + adapt_steps (one fold per complete lam_{k+1}; a
+ * first-order call without step_w: + 1, its lam is one constant); without the one-launch advance + adapt_steps more (the additions).
+ * Workspace: mi_workspace_bytes_offsets (with_steps = step_w != NULL; lr_steps = 0 for the scalar step): the plan of the same call without
+ * offsets plus adapt_steps parameter-shaped rows. */
+int mi_workspace_bytes_offsets(const mi_engine* e, int tasks, int grad_tasks, int ways, int shots, int adapt_steps, int second_order,
+                               int lr_steps, int want_lr_grad, int with_steps, size_t* bytes);
+int mi_meta_batch_maml_offsets(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels, int tasks,
+                               int grad_tasks, int ways, int shots, int adapt_steps, float inner_lr, const float* lr_vec, int lr_steps,
+                               const float* step_w, const float* offsets, int second_order, float* loss_out, float* acc_out,
+                               float* meta_grad_out, float* lr_grad_out, float* offsets_grad_out, float* logits_out, void* workspace,
+                               size_t workspace_bytes);
+
 /* Ablation / test switch: 1 (default) = every pass of mi_meta_batch_maml ends in ONE "advance" launch (weight-gradient partial folds,
  * block 1's Gram-matrix assembly, p <- p - lr g of learn2learn's maml_update / the adjoint recursion, the next pass's Gram statistics);
  * 0 = the separate launches (reduce_partials x3, gram_wgrad, axpy, gram_stats, a memset).  Bit-identical results. */
