@@ -27,7 +27,7 @@ struct Layer {
   size_t off_gamma, off_beta, off_w, off_b;
 };
 
-typedef std::array<unsigned long long, 33> GraphKey;   // graph_key(): what a captured fused call depends on
+typedef std::array<unsigned long long, 35> GraphKey;   // graph_key(): what a captured fused call depends on
 struct mi_engine {
   mi_model_desc d;
   int device;
@@ -90,11 +90,11 @@ struct mi_engine {
 
 enum ProfOp { OP_CONV_FWD = 0, OP_BN_FINALIZE, OP_BN_FWD, OP_HEAD, OP_BN_BWD_REDUCE, OP_BN_BWD_APPLY, OP_WGRAD, OP_WGRAD_REDUCE,
               OP_DGRAD, OP_TAN_CONV, OP_BN_TAN_FWD, OP_HEAD_TAN, OP_BN_TAN_BWD_REDUCE, OP_BN_TAN_BWD_APPLY, OP_TAN_WGRAD,
-              OP_TAN_DGRAD, OP_MISC, OP_GRAM, OP_GRAM_STATS, OP_COUNT };
+              OP_TAN_DGRAD, OP_MISC, OP_GRAM, OP_GRAM_STATS, OP_METRIC_HEAD, OP_COUNT };
 static const char* kOpNames[OP_COUNT] = {"conv_fwd_stats", "bn_finalize", "bn_relu_pool_fwd", "head_fwd_bwd", "bn_bwd_reduce",
                                          "bn_bwd_apply", "wgrad", "wgrad_reduce", "dgrad", "tangent_conv_fwd", "bn_tangent_fwd",
                                          "head_tangent", "bn_tangent_bwd_reduce", "bn_tangent_bwd_apply", "tangent_wgrad",
-                                         "tangent_dgrad", "misc", "input_gram", "gram_stats"};
+                                         "tangent_dgrad", "misc", "input_gram", "gram_stats", "metric_head"};
 
 static bool prof_begin(mi_engine* e, hipStream_t st, int kind) {
   if (!e || !e->prof_on || (e->prof_filter >= 0 && e->prof_filter != kind)) return false;
@@ -140,6 +140,19 @@ static int head_lds_check(mi_engine* e, const char* who, int n, int ways, int ta
                                  " rows per task and ways = " + std::to_string(ways) + " needs " + std::to_string(head_grads_lds_bytes(n, ways, tangent)) +
                                  " bytes of LDS, the device has " + std::to_string(head_lds_limit_bytes()) + " (n * ways <= " + (tangent ? "19712" : "39424") + ")");
 }
+// The metric head keeps a task's class vectors and its dz table in LDS (metric_head.hip): the same rule.
+static int metric_lds_check(mi_engine* e, const char* who, int ns, int nq, int feat, int ways) {
+  if (metric_head_fits(ns, nq, feat, ways)) return MI_OK;
+  return fail(e, MI_ERR_ARG, std::string(who) + ": the metric head with ns = " + std::to_string(ns) + ", nq = " + std::to_string(nq) + ", feat = " +
+                                 std::to_string(feat) + " and ways = " + std::to_string(ways) + " needs ns, nq, feat >= 1, ways in 1..64 and " +
+                                 std::to_string(metric_head_lds_bytes(ns, nq, feat, ways)) + " bytes of LDS, the device has " +
+                                 std::to_string(head_lds_limit_bytes()));
+}
+#define METRIC_LDS(e, who, ns, nq, feat, ways)                                     \
+  do {                                                                             \
+    const int _mrc = metric_lds_check(e, who, ns, nq, feat, ways);                 \
+    if (_mrc) return _mrc;                                                         \
+  } while (0)
 #define HEAD_LDS(e, who, n, ways, tangent)                                         \
   do {                                                                             \
     const int _hrc = head_lds_check(e, who, n, ways, tangent);                     \
@@ -1203,7 +1216,10 @@ static AdvanceArgs advance_base(const mi_engine* e, float* g) {
 // [lr_steps][Ph] (the head's entries only), grad_tasks is tasks or 0.
 // ALGO_MAML_OFFSETS (mi_meta_batch_maml_offsets): offsets = the [adapt_steps][P] per-step parameter offsets on the device, offsets_grad_out
 // their gradient or null; step_w null: the plain call's outputs and objective, else the steps call's; lr_vec null or not as in the steps call.
-enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS = 3, ALGO_ANIL_LR = 4, ALGO_ANIL_STEPS = 5, ALGO_MAML_OFFSETS = 6 };
+// ALGO_METRIC (mi_meta_batch_metric): the ANIL call's trunk pass with a closed-form head (metric, scale) and no inner loop; adapt_steps = 0,
+// grad_tasks is tasks or 0.
+enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS = 3, ALGO_ANIL_LR = 4, ALGO_ANIL_STEPS = 5, ALGO_MAML_OFFSETS = 6,
+                ALGO_METRIC = 7 };
 static bool is_anil(MetaAlgo a) { return a == ALGO_ANIL || a == ALGO_ANIL_LR || a == ALGO_ANIL_STEPS; }
 struct MetaCall {
   MetaAlgo algo;
@@ -1215,6 +1231,7 @@ struct MetaCall {
   void* workspace; size_t workspace_bytes;
   const float* step_w = nullptr;
   const float* offsets = nullptr; float* offsets_grad_out = nullptr;
+  int metric = 0; float scale = 0.f;
 };
 
 // Every check of a fused call that needs no plan: before the graph cache and before any HIP call.
@@ -1269,12 +1286,19 @@ static int check_call(mi_engine* e, const MetaCall& c) {
       if (c.adapt_steps > 0 && c.grad_tasks > 0 && c.second_order) HEAD_LDS(e, who, n, c.ways, 1);
     }
   }
+  if (c.algo == ALGO_METRIC) {
+    if (c.metric != MI_METRIC_PROTO && c.metric != MI_METRIC_COSINE)
+      return fail(e, MI_ERR_ARG, "mi_meta_batch_metric: unknown metric " + std::to_string(c.metric) + " (MI_METRIC_PROTO = 0, MI_METRIC_COSINE = 1)");
+    if (!(c.scale > 0.f)) return fail(e, MI_ERR_ARG, "mi_meta_batch_metric: scale must be positive, got " + std::to_string(c.scale));
+    if (e->trace) return fail(e, MI_ERR_ARG, "the debug trace does not cover mi_meta_batch_metric");
+  }
   if (!c.theta || !c.data || !c.labels || !c.loss_out || !c.acc_out || !c.workspace) return fail(e, MI_ERR_ARG, "null pointer argument");
   if (c.grad_tasks > 0 && !c.meta_grad_out) return fail(e, MI_ERR_ARG, "meta_grad_out is NULL but a gradient was asked for");
-  if (is_anil(c.algo) && e->d.head_mean_pool)
+  if ((is_anil(c.algo) || c.algo == ALGO_METRIC) && e->d.head_mean_pool)
     return fail(e, MI_ERR_ARG, "ANIL features are flattened (view(-1, fc_neurons)), not mean-pooled");
   if (c.tasks < 1 || c.shots < 1 || c.adapt_steps < 0) return fail(e, MI_ERR_ARG, "tasks/shots must be >= 1, adapt_steps >= 0");
   if (c.ways != e->d.ways) return fail(e, MI_ERR_ARG, "ways differs from the engine's classifier width");
+  if (c.algo == ALGO_METRIC) METRIC_LDS(e, "mi_meta_batch_metric", c.ways * c.shots, c.ways * c.shots, e->feat, c.ways);
   return MI_OK;
 }
 
@@ -1686,26 +1710,74 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const MetaCall& c) {
   return MI_OK;
 }
 
+// mi_meta_batch_metric: the launches of meta_batch_anil_impl up to the split of the features, ONE metric-head launch (no head parameters, no
+// inner loop, no tangent pass), then -- with a gradient -- the interleave, the trunk backward and the sum over tasks (without one the call ends
+// at the head).  lam's head entries stay
+// the zeros of the memset, so meta_grad_out's head entries are exact zeros.  The plan is the ANIL call's with K = 0.
+extern "C" int mi_metric_workspace_bytes(const mi_engine* e, int tasks, int ways, int shots, int with_grad, size_t* bytes) {
+  (void)with_grad;                       // (one plan for both: the evaluation call leaves the backward's arrays unused)
+  return mi_anil_workspace_bytes(e, tasks, ways, shots, 0, bytes);
+}
+static int meta_batch_metric_impl(mi_engine* e, void* stream, const MetaCall& c) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int T = c.tasks, n = c.ways * c.shots, nl = (int)e->L.size(), with_grad = c.grad_tasks > 0;
+  AnilPlan ap;
+  make_anil_plan(e, c.workspace, T, n, 0, ap);
+  if (ap.bytes > c.workspace_bytes) return fail(e, MI_ERR_WORKSPACE, "workspace too small: need " + std::to_string(ap.bytes) + " bytes");
+  const size_t TP = (size_t)T * e->PS;
+  LAUNCH(e, st, OP_MISC, 0, launch_nchw_to_nhwc(st, c.data, (size_t)T * 2 * n, e->d.in_channels, e->d.in_h, e->d.in_w, ap.x));
+  LAUNCH(e, st, OP_MISC, 0, launch_split_labels(st, c.labels, T, 2 * n, ap.ys, ap.yq));
+  LAUNCH(e, st, OP_MISC, 1, launch_gather_params(st, c.theta, 0, e->perm_dev, (int)e->P, (int)e->PS, T, ap.theta));
+  // Block 1's statistics through the Gram matrix with or without a backward half (the ANIL call drops it from its evaluation call, whose
+  // forward then rounds differently): the evaluation call here is the training call's forward bit for bit, for one more launch
+  const double* gram = ap.scratch.gram_s;
+  if (gram)
+    LAUNCH(e, st, OP_GRAM, 0, launch_input_gram(st, ap.x, T, 2 * n, e->L[0].h, e->L[0].w, e->L[0].ci, ap.scratch.gram_part, ap.scratch.gram_s));
+  int rc = plan_begin(e, st, ap.scratch);
+  if (rc) return rc;
+  rc = trunk_forward(e, st, ap.scratch, ap.act, ap.x, 2 * n, T, ap.theta, gram);     // features(data) on all rows
+  if (rc) return rc;
+  e->export_pass = 0;
+  rc = export_bn_stats(e, st, ap.act, T);
+  if (rc) return rc;
+  LAUNCH(e, st, OP_MISC, 4, launch_split_rows(st, ap.act.p[nl - 1], T, 2 * n, e->feat, ap.fs, ap.fq));
+  MetricArgs ma{};
+  ma.fs = ap.fs; ma.fq = ap.fq; ma.ys = ap.ys; ma.yq = ap.yq;
+  ma.ns = n; ma.nq = n; ma.feat = e->feat; ma.ways = c.ways; ma.metric = c.metric; ma.scale = c.scale;
+  ma.loss = c.loss_out; ma.acc = c.acc_out; ma.logits = c.logits_out;
+  ma.dfs = with_grad ? ap.dfs : nullptr; ma.dfq = with_grad ? ap.dfq : nullptr;
+  LAUNCH(e, st, OP_METRIC_HEAD, 0, launch_metric_head(st, ma, T));
+  if (!with_grad) return MI_OK;
+  HIPCHK(e, hipMemsetAsync(ap.lam, 0, TP * sizeof(float), st));
+  LAUNCH(e, st, OP_MISC, 4, launch_interleave_rows(st, ap.dfs, ap.dfq, T, n, e->feat, ap.act.dp[nl - 1]));
+  rc = trunk_backward(e, st, ap.scratch, ap.act, ap.x, 2 * n, T, ap.theta, ap.lam, gram);
+  if (rc) return rc;
+  LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, ap.lam, e->perm_dev, (int)e->P, (int)e->PS, T, c.meta_grad_out));
+  return MI_OK;
+}
+
 // ---- graph replay of the fused calls
 // What a captured graph depends on, field by field (never the struct's bytes: its padding is indeterminate): two calls whose keys are equal
 // make the same launches with the same arguments.  Every engine switch and the kernel selection in an element of its own: nothing packed,
 // nothing that can alias.  The step sizes' VALUES are read on the device at every replay, like theta's.
 static GraphKey graph_key(const mi_engine* e, void* stream, const MetaCall& c) {
   typedef unsigned long long u;
-  unsigned lr_bits;
+  unsigned lr_bits, scale_bits;
   memcpy(&lr_bits, &c.inner_lr, sizeof lr_bits);
+  memcpy(&scale_bits, &c.scale, sizeof scale_bits);
   return GraphKey{(u)c.algo, (u)(uintptr_t)stream, (u)(uintptr_t)c.theta, (u)(uintptr_t)c.data, (u)(uintptr_t)c.labels, (u)c.tasks,
                   (u)c.grad_tasks, (u)c.ways, (u)c.shots, (u)c.adapt_steps, (u)c.second_order, (u)lr_bits, (u)(uintptr_t)c.lr_vec,
                   (u)c.lr_steps, (u)(uintptr_t)c.lr_grad_out, (u)(uintptr_t)c.loss_out, (u)(uintptr_t)c.acc_out,
                   (u)(uintptr_t)c.meta_grad_out, (u)(uintptr_t)c.logits_out, (u)(uintptr_t)c.workspace, (u)c.workspace_bytes,
                   (u)e->fuse1, (u)e->gram1, (u)e->gramq, (u)e->overlap, (u)e->fuse_fin, (u)e->fuse_b1red, (u)e->fuse_tail, (u)e->fuse_last,
-                  kernel_selection_key(), (u)(uintptr_t)c.step_w, (u)(uintptr_t)c.offsets, (u)(uintptr_t)c.offsets_grad_out};
+                  kernel_selection_key(), (u)(uintptr_t)c.step_w, (u)(uintptr_t)c.offsets, (u)(uintptr_t)c.offsets_grad_out,
+                  (u)c.metric, (u)scale_bits};
 }
 
 static int meta_batch_entry(mi_engine* e, void* stream, const MetaCall& c) {
   const int crc = check_call(e, c);
   if (crc) return crc;
-  const auto fn = is_anil(c.algo) ? meta_batch_anil_impl : meta_batch_maml_impl;
+  const auto fn = c.algo == ALGO_METRIC ? meta_batch_metric_impl : is_anil(c.algo) ? meta_batch_anil_impl : meta_batch_maml_impl;
   if (!e->graph_on || e->prof_on || e->trace || e->bn_export || !stream)     // (capture is not permitted on the legacy default stream)
     return fn(e, stream, c);
   const GraphKey key = graph_key(e, stream, c);
@@ -1833,6 +1905,18 @@ extern "C" int mi_meta_batch_anil_steps(mi_engine* e, void* stream, const float*
              lr_vec, lr_vec ? lr_steps : 0, lr_grad_out, loss_steps_out, acc_steps_out, meta_grad_out, logits_steps_out, workspace,
              workspace_bytes};
   c.step_w = step_w;
+  return meta_batch_entry(e, stream, c);
+}
+
+// A closed-form head (MI_METRIC_PROTO / MI_METRIC_COSINE) on the ANIL engine's trunk, no inner loop (include/mi_maml.h).
+extern "C" int mi_meta_batch_metric(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
+                                    int tasks, int ways, int shots, int metric, float scale, int with_grad,
+                                    float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
+                                    void* workspace, size_t workspace_bytes) {
+  MetaCall c{ALGO_METRIC, theta, data, labels, tasks, with_grad ? tasks : 0, ways, shots, 0, 0, 0.f, nullptr, 0, nullptr, loss_out, acc_out,
+             meta_grad_out, logits_out, workspace, workspace_bytes};
+  c.metric = metric;
+  c.scale = scale;
   return meta_batch_entry(e, stream, c);
 }
 
@@ -2172,6 +2256,30 @@ extern "C" int mi_head_fwd_bwd(void* stream, const float* f, const float* wl, co
     ha.loss = nullptr; ha.acc = nullptr;
     HIPCHK0(launch_head_grads(reinterpret_cast<hipStream_t>(stream), ha, tasks));
   }
+  return MI_OK;
+}
+
+// launch_metric_head: the metric heads' kernel entry (include/mi_maml.h).  Everything is folded inside the one launch: no scratch.
+extern "C" size_t mi_metric_head_scratch_bytes(int tasks, int ns, int nq, int feat, int ways) {
+  (void)tasks; (void)ns; (void)nq; (void)feat; (void)ways;
+  return 0;
+}
+extern "C" int mi_metric_head(void* stream, const float* fs, const float* fq, const int32_t* ys, const int32_t* yq, int tasks, int ns, int nq,
+                              int feat, int ways, int metric, float scale, float* loss, float* acc, float* logits, float* dfs, float* dfq,
+                              void* scratch, size_t scratch_bytes) {
+  (void)scratch; (void)scratch_bytes;
+  if (!fs || !fq || !ys || !yq || !loss || !acc) return fail(nullptr, MI_ERR_ARG, "mi_metric_head: null pointer argument");
+  if (tasks < 1) return fail(nullptr, MI_ERR_ARG, "mi_metric_head: tasks must be >= 1, got " + std::to_string(tasks));
+  if (metric != MI_METRIC_PROTO && metric != MI_METRIC_COSINE)
+    return fail(nullptr, MI_ERR_ARG, "mi_metric_head: unknown metric " + std::to_string(metric) + " (MI_METRIC_PROTO = 0, MI_METRIC_COSINE = 1)");
+  if (!(scale > 0.f)) return fail(nullptr, MI_ERR_ARG, "mi_metric_head: scale must be positive, got " + std::to_string(scale));
+  if (((reinterpret_cast<uintptr_t>(fs) | reinterpret_cast<uintptr_t>(fq) | reinterpret_cast<uintptr_t>(dfs) | reinterpret_cast<uintptr_t>(dfq)) & 15) != 0)
+    return fail(nullptr, MI_ERR_ARG, "mi_metric_head: fs, fq, dfs and dfq must be 16-byte aligned");
+  METRIC_LDS(nullptr, "mi_metric_head", ns, nq, feat, ways);
+  MetricArgs ma{};
+  ma.fs = fs; ma.fq = fq; ma.ys = ys; ma.yq = yq; ma.ns = ns; ma.nq = nq; ma.feat = feat; ma.ways = ways; ma.metric = metric; ma.scale = scale;
+  ma.loss = loss; ma.acc = acc; ma.logits = logits; ma.dfs = dfs; ma.dfq = dfq;
+  HIPCHK0(launch_metric_head(reinterpret_cast<hipStream_t>(stream), ma, tasks));
   return MI_OK;
 }
 

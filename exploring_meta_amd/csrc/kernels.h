@@ -259,6 +259,22 @@ hipError_t launch_head_grads(hipStream_t st, const HeadArgs& a, int tasks);   //
 hipError_t launch_spatial_mean(hipStream_t st, const float* p, float* f, int rows, int hw, int c);
 hipError_t launch_spatial_mean_bwd(hipStream_t st, const float* df, float* dp, int rows, int hw, int c);
 
+// metric_head.hip: the closed-form heads of Prototypical Networks and NIL on the features of a whole meta-batch, one launch
+struct MetricArgs {
+  const float* fs; const float* fq;      // [T][ns][F], [T][nq][F], 16-byte aligned
+  const int32_t* ys; const int32_t* yq;  // [T][ns], [T][nq] in [0, ways); every class has a support row
+  int ns, nq, feat, ways, metric;        // metric: MI_METRIC_PROTO / MI_METRIC_COSINE
+  float scale;                           // > 0
+  float* loss; float* acc;               // [T]
+  float* logits;                         // [T][nq][ways] (may be null)
+  float* dfs; float* dfq;                // [T][ns][F], [T][nq][F], 16-byte aligned (may be null; both null: forward only)
+};
+// Dynamic LDS of one task (the class vectors and the dz table) against the CU's LDS; the launcher refuses what does not fit with
+// hipErrorInvalidValue before launching anything -- callers check metric_head_fits first and report MI_ERR_ARG.
+size_t metric_head_lds_bytes(int ns, int nq, int feat, int ways);
+bool metric_head_fits(int ns, int nq, int feat, int ways);
+hipError_t launch_metric_head(hipStream_t st, const MetricArgs& a, int tasks);
+
 // tail.hip: the last ConvBlock's BatchNorm + ReLU + MaxPool, the head, the head's backward and that block's BatchNorm-backward SUMS (or their
 // tangents) in one launch, four workgroups (row groups) per task; cross-workgroup sums by the last arriver (finalize.h protocol).
 struct TailArgs {

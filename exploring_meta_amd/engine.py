@@ -100,6 +100,23 @@ def _resolve_device(device):
     return torch.device('cuda', device.index if device.index is not None else torch.cuda.current_device())
 
 
+METRICS = {'proto': 0, 'cosine': 1}          # MI_METRIC_PROTO, MI_METRIC_COSINE (include/mi_maml.h)
+
+
+def metric_id(metric):
+    """The library's id of a metric head; anything else is refused here, before the library is touched."""
+    if metric not in METRICS:
+        raise _lib.MiError(f"libmi_maml error -1: unknown metric {metric!r}: 'proto' (Prototypical Networks) or 'cosine' (NIL)")
+    return METRICS[metric]
+
+
+def check_scale(scale):
+    scale = float(scale)
+    if not scale > 0.0:
+        raise _lib.MiError(f'libmi_maml error -1: the metric head\'s scale must be positive, got {scale}')
+    return scale
+
+
 class MetaEngine:
     """One engine per (model spec, device).  Not re-entrant (one host thread per GPU / rank)."""
 
@@ -527,6 +544,50 @@ class MetaEngine:
             raise _lib.MiError('libmi_maml error -1: step_w is None: meta_batch_anil_steps takes adapt_steps weights on the device')
         return self._anil_call(theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, step_w, first_order, with_grad, want_lr_grad,
                                return_logits)
+
+    @_on_device
+    def meta_batch_metric(self, theta, data, labels, shots, metric='proto', scale=1.0, with_grad=True, return_logits=False):
+        """A closed-form head on the ANIL trunk, no inner loop (mi_meta_batch_metric): metric 'proto' (Prototypical Networks: the class
+        means, logits -scale * squared distance) or 'cosine' (NIL: logits scale * sum of the cosine similarities to a class's support
+        rows).  theta keeps the ANIL layout [features.parameters()..., head.weight, head.bias]; the head's entries are not used and their
+        gradient is exactly zero.  Returns (loss[T], acc[T], meta_grad[P] or None, logits [T, S*W, ways] or None)."""
+        m, scale = metric_id(metric), check_scale(scale)
+        s = self.spec
+        T = self._check_batch(theta, data, labels, shots, flat_data=False)
+        b = C.c_size_t()
+        _lib.check(self.lib.mi_metric_workspace_bytes(self._h, T, s.ways, shots, int(bool(with_grad)), C.byref(b)), self._h)
+        ws = self._workspace(b.value)
+        loss, acc, grad, logits = self._outputs(('metric', m), T, shots * s.ways, with_grad, return_logits)
+        rc = self._fused_call(self.lib.mi_meta_batch_metric, _ptr(theta), _ptr(data), _ptr(labels), T, s.ways, shots, m, scale,
+                              int(bool(with_grad)), _ptr(loss), _ptr(acc), _ptr(grad), _ptr(logits), _ptr(ws), ws.numel())
+        _lib.check(rc, self._h)
+        return loss, acc, grad, logits
+
+    @_on_device
+    def metric_head(self, fs, fq, ys, yq, ways, metric='proto', scale=1.0, with_grad=True):
+        """The metric heads' kernel entry (mi_metric_head) on given features: fs [T, ns, F], fq [T, nq, F] fp32, ys [T, ns], yq [T, nq]
+        int32 in [0, ways), every class with at least one support row.  Returns (loss[T], acc[T], logits [T, nq, ways], dfs, dfq), the
+        last two None without a gradient."""
+        m, scale = metric_id(metric), check_scale(scale)
+        for t, dt in ((fs, torch.float32), (fq, torch.float32), (ys, torch.int32), (yq, torch.int32)):
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                raise ValueError('fs / fq must be contiguous fp32 CUDA tensors, ys / yq contiguous int32 CUDA tensors')
+        if fs.dim() != 3 or fq.dim() != 3 or fs.shape[0] != fq.shape[0] or fs.shape[2] != fq.shape[2] or \
+                tuple(ys.shape) != tuple(fs.shape[:2]) or tuple(yq.shape) != tuple(fq.shape[:2]):
+            raise ValueError(f'fs [T, ns, F], fq [T, nq, F], ys [T, ns], yq [T, nq]; got {tuple(fs.shape)}, {tuple(fq.shape)}, '
+                             f'{tuple(ys.shape)}, {tuple(yq.shape)}')
+        T, ns, feat = fs.shape
+        nq = fq.shape[1]
+        loss = torch.empty(T, dtype=torch.float32, device=self.device)
+        acc = torch.empty(T, dtype=torch.float32, device=self.device)
+        logits = torch.empty(T, nq, ways, dtype=torch.float32, device=self.device)
+        dfs = torch.empty_like(fs) if with_grad else None
+        dfq = torch.empty_like(fq) if with_grad else None
+        nscr = self.lib.mi_metric_head_scratch_bytes(T, ns, nq, feat, int(ways))
+        scr = torch.empty(nscr, dtype=torch.uint8, device=self.device) if nscr else None
+        _lib.check(self.lib.mi_metric_head(_stream(self.device), _ptr(fs), _ptr(fq), _ptr(ys), _ptr(yq), T, ns, nq, feat, int(ways), m, scale,
+                                           _ptr(loss), _ptr(acc), _ptr(logits), _ptr(dfs), _ptr(dfq), _ptr(scr), nscr), None)
+        return loss, acc, logits, dfs, dfq
 
     @_on_device
     def forward_logits(self, theta, x):

@@ -138,6 +138,12 @@ def run(dataset, p, log=print):
         torch.save(head.state_dict(), os.path.join(save_dir, 'head.pt'))
         if isinstance(head.lr, InnerLR):
             torch.save(head.lr.state_dict(), os.path.join(save_dir, 'inner_lr.pt'))
+    if p.get('nil_test'):        # --nil_test: how good are the features alone?  The head is thrown away (NIL, no inner loop)
+        from ..core_functions.metric import evaluate_nil
+        test = SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6)
+        metrics['nil_test_acc'] = evaluate_nil(p, test, features, device)
+        if rank == 0:
+            log(f"nil_test_acc: {metrics['nil_test_acc']}")
     if world > 1:
         torch.distributed.destroy_process_group()
     return (features, head), metrics
@@ -158,6 +164,8 @@ def build_parser():
                         help='MAML++ multi-step loss: the outer objective weights the query loss after every head step (msl_weights)')
     parser.add_argument('--msl_iterations', type=int, default=0, metavar='N',
                         help='iterations over which the multi-step weights anneal to the final step; from iteration N on the plain call runs')
+    parser.add_argument('--nil_test', action='store_true',
+                        help='after training also log nil_test_acc: the trunk scored on meta_batch_size test tasks by the NIL cosine head, no inner loop')
     return parser
 
 
@@ -169,7 +177,7 @@ def params_of(args):
     """The run's parameter dict from parsed flags (the defaults are the reference's run)."""
     p = {k: getattr(args, k) for k in params}
     p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
-             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations)
+             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations, nil_test=args.nil_test)
     return p
 
 

@@ -77,6 +77,8 @@ def run(dataset, p, first_order=False, log=print):
     random.seed(p['seed']); np.random.seed(p['seed']); torch.manual_seed(p['seed']); torch.cuda.manual_seed(p['seed'])
     device = torch.device('cuda', local)
     model = (OmniglotCNN(p['ways']) if dataset == 'omni' else MiniImagenetCNN(p['ways'])).to(device)
+    if p.get('nil_test') and isinstance(model, OmniglotCNN):      # (before the training, not after it)
+        raise NotImplementedError('--nil_test scores flattened features; OmniglotCNN feeds its head their spatial mean (use --dataset min)')
     maml = MAML(model, lr=inner_lr_of(model, p), first_order=first_order, offsets=step_offsets_of(model, p))
     opt = torch.optim.Adam(maml.parameters(), p['outer_lr'])
     # MAML++'s cosine outer schedule over the run (--cosine_outer_lr); None: the constant outer_lr, today's run
@@ -154,6 +156,11 @@ def run(dataset, p, first_order=False, log=print):
                 torch.save(model.state_dict(), os.path.join(save_dir, 'model_checkpoints', f'model_{it}.pt'))
     test = SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6)
     metrics['test_acc'] = evaluate(p, test, maml, loss, device)
+    if p.get('nil_test'):        # --nil_test: the same number of test tasks scored by the NIL cosine head on the trunk alone, no inner loop
+        from ..core_functions.metric import evaluate_nil
+        metrics['nil_test_acc'] = evaluate_nil(p, SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6), model, device)
+        if rank == 0:
+            log(f"nil_test_acc: {metrics['nil_test_acc']}")
     if world > 1:
         torch.distributed.destroy_process_group()
     if save_dir and rank == 0:
@@ -188,6 +195,8 @@ def build_parser():
                         help='MAML++ derivative-order annealing: iterations < N make the first-order call')
     parser.add_argument('--cosine_outer_lr', action='store_true', help='cosine-anneal the outer learning rate over num_iterations')
     parser.add_argument('--min_outer_lr', type=float, default=0.0, metavar='X', help='the floor of --cosine_outer_lr')
+    parser.add_argument('--nil_test', action='store_true',
+                        help='after the test accuracy also log nil_test_acc: the trunk alone under the NIL cosine head (flattened features: --dataset min)')
     return parser
 
 
@@ -197,7 +206,7 @@ def params_of(args):
     p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
              freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations,
              per_step_bn=args.per_step_bn, per_step_bn_adapt_bn=args.per_step_bn_adapt_bn, first_order_iterations=args.first_order_iterations,
-             cosine_outer_lr=args.cosine_outer_lr, min_outer_lr=args.min_outer_lr)
+             cosine_outer_lr=args.cosine_outer_lr, min_outer_lr=args.min_outer_lr, nil_test=args.nil_test)
     return p
 
 

@@ -292,6 +292,42 @@ int mi_meta_batch_anil_steps(mi_engine* e, void* stream, const float* theta, con
                              int second_order, int with_grad, float* loss_steps_out, float* acc_steps_out, float* meta_grad_out,
                              float* lr_grad_out, float* logits_steps_out, void* workspace, size_t workspace_bytes);
 
+/* Metric heads: no inner loop at all.  The class vectors come from the support features in closed form (csrc/metric_head.hip, DESIGN.md
+ * section 27), per task with N_w = #{i : ys_i = w}; THE CONTRACT IS N_w >= 1 FOR EVERY CLASS and labels in [0, ways):
+ *   MI_METRIC_PROTO   (Prototypical Networks)  c_w = (1/N_w) sum_{i in w} fs_i,   z_qw = -scale * |fq_q - c_w|^2  (summed squared differences)
+ *   MI_METRIC_COSINE  (NIL, the ANIL paper)    xh = x / max(|x|_2, 1e-8),  c_w = sum_{i in w} sh_i,   z_qw = scale * <qh_q, c_w>
+ *   loss_t = mean_q CE(z_q, yq_q);  acc_t = mean_q [argmax_w z_q == yq_q] (first maximum);  dfs, dfq = d(sum_t loss_t)/d(fs, fq).
+ * mi_metric_head is the kernel entry: fs [tasks, ns, feat], fq [tasks, nq, feat] fp32 (16-byte aligned, like dfs / dfq), ys [tasks, ns],
+ * yq [tasks, nq] int32; ns != nq and unbalanced classes are fine.  loss, acc [tasks]; logits [tasks, nq, ways], dfs, dfq may be NULL (dfs and
+ * dfq both NULL: the forward-only launch, whose loss, acc and logits are the bits of the forward + backward launch).  ONE launch whatever
+ * `tasks`; a task's results do not depend on the other tasks of the call.  The domain (MI_ERR_ARG before any launch otherwise): tasks, ns,
+ * nq, feat >= 1, 1 <= ways <= 64, metric one of MI_METRIC_*, scale > 0, and one task's class vectors and tables inside the 160 KiB of LDS:
+ *   4 * (roundup4(ways * feat) + nq * ways + ways + ns + 4 * nq) <= 163840 bytes
+ * -- ways * feat <= 40960 - (nq * ways + ways + ns + 4 * nq) rounded down to 4: 5 ways at ns = nq = 5: feat <= 8180 (at ns = nq = 25:
+ * 8140); 20 ways x 1600 features (128 KB): nq * ways + ... leaves nq = ns <= 357; feat = 128, 5 ways: nq = ns <= 4031.
+ * mi_metric_head_scratch_bytes: the kernel folds everything inside its launch and needs no scratch today: 0, and scratch may be NULL. */
+#define MI_METRIC_PROTO 0
+#define MI_METRIC_COSINE 1
+size_t mi_metric_head_scratch_bytes(int tasks, int ns, int nq, int feat, int ways);
+int mi_metric_head(void* stream, const float* fs, const float* fq, const int32_t* ys, const int32_t* yq,
+                   int tasks, int ns, int nq, int feat, int ways, int metric, float scale,
+                   float* loss, float* acc, float* logits /*nullable*/, float* dfs /*nullable*/, float* dfq /*nullable*/,
+                   void* scratch, size_t scratch_bytes);
+/* One meta-batch scored (and differentiated) by a metric head on the ANIL trunk: the engine is one made for mi_meta_batch_anil, theta and
+ * meta_grad_out keep its layout [features.parameters() ..., head.weight, head.bias]; the head's entries of theta do not enter any result
+ * and the head's entries of meta_grad_out are written as exact zeros.  data / labels as mi_meta_batch_anil (the even split of
+ * utils/data_pre.py:118-119: ns = nq = ways * shots), logits_out [tasks, ways * shots, ways] or NULL.  The launches are mi_meta_batch_anil's
+ * up to the split of the features, then ONE metric-head launch, then (with_grad) the interleave, the trunk backward and the sum over
+ * tasks; without a gradient the call ends at the head, and its loss, acc and logits are the bits of the call with one (it keeps the
+ * input Gram matrix that mi_meta_batch_anil drops from its evaluation call, whose block-1 statistics then round differently).  Graph replay and the BatchNorm export (one pass) as for
+ * mi_meta_batch_anil; metric and scale are part of the graph's signature.  MI_ERR_ARG before any launch: a mean-pooled head, an unknown
+ * metric, scale not > 0, sizes outside mi_metric_head's domain, and what mi_meta_batch_anil refuses. */
+int mi_metric_workspace_bytes(const mi_engine* e, int tasks, int ways, int shots, int with_grad, size_t* bytes);
+int mi_meta_batch_metric(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
+                         int tasks, int ways, int shots, int metric, float scale, int with_grad,
+                         float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
+                         void* workspace, size_t workspace_bytes);
+
 /* Plain classifier forward, no adaptation: `learner(x)` / `model(x)` (vision_models.py:51-55,107-110), BatchNorm in train
  * mode over the n images of each of the `tasks` batches.  x [tasks, n, C, H, W] NCHW; logits_out [tasks, n, ways]. */
 int mi_forward_workspace_bytes(const mi_engine* e, int tasks, int n, size_t* bytes);
