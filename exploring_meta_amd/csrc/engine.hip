@@ -27,7 +27,7 @@ struct Layer {
   size_t off_gamma, off_beta, off_w, off_b;
 };
 
-typedef std::array<unsigned long long, 35> GraphKey;   // graph_key(): what a captured fused call depends on
+typedef std::array<unsigned long long, 38> GraphKey;   // graph_key(): what a captured fused call depends on
 struct mi_engine {
   mi_model_desc d;
   int device;
@@ -90,11 +90,11 @@ struct mi_engine {
 
 enum ProfOp { OP_CONV_FWD = 0, OP_BN_FINALIZE, OP_BN_FWD, OP_HEAD, OP_BN_BWD_REDUCE, OP_BN_BWD_APPLY, OP_WGRAD, OP_WGRAD_REDUCE,
               OP_DGRAD, OP_TAN_CONV, OP_BN_TAN_FWD, OP_HEAD_TAN, OP_BN_TAN_BWD_REDUCE, OP_BN_TAN_BWD_APPLY, OP_TAN_WGRAD,
-              OP_TAN_DGRAD, OP_MISC, OP_GRAM, OP_GRAM_STATS, OP_METRIC_HEAD, OP_COUNT };
+              OP_TAN_DGRAD, OP_MISC, OP_GRAM, OP_GRAM_STATS, OP_METRIC_HEAD, OP_RIDGE_HEAD, OP_COUNT };
 static const char* kOpNames[OP_COUNT] = {"conv_fwd_stats", "bn_finalize", "bn_relu_pool_fwd", "head_fwd_bwd", "bn_bwd_reduce",
                                          "bn_bwd_apply", "wgrad", "wgrad_reduce", "dgrad", "tangent_conv_fwd", "bn_tangent_fwd",
                                          "head_tangent", "bn_tangent_bwd_reduce", "bn_tangent_bwd_apply", "tangent_wgrad",
-                                         "tangent_dgrad", "misc", "input_gram", "gram_stats", "metric_head"};
+                                         "tangent_dgrad", "misc", "input_gram", "gram_stats", "metric_head", "ridge_head"};
 
 static bool prof_begin(mi_engine* e, hipStream_t st, int kind) {
   if (!e || !e->prof_on || (e->prof_filter >= 0 && e->prof_filter != kind)) return false;
@@ -148,6 +148,26 @@ static int metric_lds_check(mi_engine* e, const char* who, int ns, int nq, int f
                                  std::to_string(metric_head_lds_bytes(ns, nq, feat, ways)) + " bytes of LDS, the device has " +
                                  std::to_string(head_lds_limit_bytes()));
 }
+// The ridge head keeps a task's Gram system, its factor and the dual coefficients in LDS in fp64 (ridge_head.hip): the same rule, feat capped.
+static int ridge_lds_check(mi_engine* e, const char* who, int ns, int nq, int feat, int ways) {
+  if (ridge_head_fits(ns, nq, feat, ways)) return MI_OK;
+  return fail(e, MI_ERR_ARG, std::string(who) + ": the ridge head with ns = " + std::to_string(ns) + ", nq = " + std::to_string(nq) + ", feat = " +
+                                 std::to_string(feat) + " and ways = " + std::to_string(ways) + " needs ns, nq >= 1, feat in 1.." +
+                                 std::to_string(MI_RIDGE_MAX_FEAT) + ", ways in 1..64 and " +
+                                 std::to_string(ns >= 1 && nq >= 1 && ways >= 1 ? ridge_head_lds_bytes(ns, nq, ways) : 0) +
+                                 " bytes of LDS, the device has " + std::to_string(head_lds_limit_bytes()));
+}
+static int ridge_hyper_check(mi_engine* e, const char* who, float lam, float alpha) {
+  if (!(lam > 0.f) || !std::isfinite(lam)) return fail(e, MI_ERR_ARG, std::string(who) + ": lam must be positive and finite, got " + std::to_string(lam));
+  if (!(alpha > 0.f) || !std::isfinite(alpha))
+    return fail(e, MI_ERR_ARG, std::string(who) + ": alpha must be positive and finite, got " + std::to_string(alpha));
+  return MI_OK;
+}
+#define RIDGE_LDS(e, who, ns, nq, feat, ways)                                      \
+  do {                                                                             \
+    const int _rrc = ridge_lds_check(e, who, ns, nq, feat, ways);                  \
+    if (_rrc) return _rrc;                                                         \
+  } while (0)
 #define METRIC_LDS(e, who, ns, nq, feat, ways)                                     \
   do {                                                                             \
     const int _mrc = metric_lds_check(e, who, ns, nq, feat, ways);                 \
@@ -1219,7 +1239,9 @@ static AdvanceArgs advance_base(const mi_engine* e, float* g) {
 // ALGO_METRIC (mi_meta_batch_metric): the ANIL call's trunk pass with a closed-form head (metric, scale) and no inner loop; adapt_steps = 0,
 // grad_tasks is tasks or 0.
 enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS = 3, ALGO_ANIL_LR = 4, ALGO_ANIL_STEPS = 5, ALGO_MAML_OFFSETS = 6,
-                ALGO_METRIC = 7 };
+                ALGO_METRIC = 7, ALGO_RIDGE = 8 };
+// ALGO_RIDGE (mi_meta_batch_ridge): ALGO_METRIC's launches with the ridge-regression head (lam, alpha) in the metric head's place;
+// dhyper_out [tasks][2] or null.
 static bool is_anil(MetaAlgo a) { return a == ALGO_ANIL || a == ALGO_ANIL_LR || a == ALGO_ANIL_STEPS; }
 struct MetaCall {
   MetaAlgo algo;
@@ -1232,6 +1254,7 @@ struct MetaCall {
   const float* step_w = nullptr;
   const float* offsets = nullptr; float* offsets_grad_out = nullptr;
   int metric = 0; float scale = 0.f;
+  float lam = 0.f, alpha = 0.f; float* dhyper_out = nullptr;
 };
 
 // Every check of a fused call that needs no plan: before the graph cache and before any HIP call.
@@ -1292,13 +1315,19 @@ static int check_call(mi_engine* e, const MetaCall& c) {
     if (!(c.scale > 0.f)) return fail(e, MI_ERR_ARG, "mi_meta_batch_metric: scale must be positive, got " + std::to_string(c.scale));
     if (e->trace) return fail(e, MI_ERR_ARG, "the debug trace does not cover mi_meta_batch_metric");
   }
+  if (c.algo == ALGO_RIDGE) {
+    const int hrc = ridge_hyper_check(e, "mi_meta_batch_ridge", c.lam, c.alpha);
+    if (hrc) return hrc;
+    if (e->trace) return fail(e, MI_ERR_ARG, "the debug trace does not cover mi_meta_batch_ridge");
+  }
   if (!c.theta || !c.data || !c.labels || !c.loss_out || !c.acc_out || !c.workspace) return fail(e, MI_ERR_ARG, "null pointer argument");
   if (c.grad_tasks > 0 && !c.meta_grad_out) return fail(e, MI_ERR_ARG, "meta_grad_out is NULL but a gradient was asked for");
-  if ((is_anil(c.algo) || c.algo == ALGO_METRIC) && e->d.head_mean_pool)
+  if ((is_anil(c.algo) || c.algo == ALGO_METRIC || c.algo == ALGO_RIDGE) && e->d.head_mean_pool)
     return fail(e, MI_ERR_ARG, "ANIL features are flattened (view(-1, fc_neurons)), not mean-pooled");
   if (c.tasks < 1 || c.shots < 1 || c.adapt_steps < 0) return fail(e, MI_ERR_ARG, "tasks/shots must be >= 1, adapt_steps >= 0");
   if (c.ways != e->d.ways) return fail(e, MI_ERR_ARG, "ways differs from the engine's classifier width");
   if (c.algo == ALGO_METRIC) METRIC_LDS(e, "mi_meta_batch_metric", c.ways * c.shots, c.ways * c.shots, e->feat, c.ways);
+  if (c.algo == ALGO_RIDGE) RIDGE_LDS(e, "mi_meta_batch_ridge", c.ways * c.shots, c.ways * c.shots, e->feat, c.ways);
   return MI_OK;
 }
 
@@ -1741,12 +1770,21 @@ static int meta_batch_metric_impl(mi_engine* e, void* stream, const MetaCall& c)
   rc = export_bn_stats(e, st, ap.act, T);
   if (rc) return rc;
   LAUNCH(e, st, OP_MISC, 4, launch_split_rows(st, ap.act.p[nl - 1], T, 2 * n, e->feat, ap.fs, ap.fq));
-  MetricArgs ma{};
-  ma.fs = ap.fs; ma.fq = ap.fq; ma.ys = ap.ys; ma.yq = ap.yq;
-  ma.ns = n; ma.nq = n; ma.feat = e->feat; ma.ways = c.ways; ma.metric = c.metric; ma.scale = c.scale;
-  ma.loss = c.loss_out; ma.acc = c.acc_out; ma.logits = c.logits_out;
-  ma.dfs = with_grad ? ap.dfs : nullptr; ma.dfq = with_grad ? ap.dfq : nullptr;
-  LAUNCH(e, st, OP_METRIC_HEAD, 0, launch_metric_head(st, ma, T));
+  if (c.algo == ALGO_RIDGE) {              // mi_meta_batch_ridge: the ridge head in the metric head's place, nothing else differs
+    RidgeArgs ra{};
+    ra.fs = ap.fs; ra.fq = ap.fq; ra.ys = ap.ys; ra.yq = ap.yq;
+    ra.ns = n; ra.nq = n; ra.feat = e->feat; ra.ways = c.ways; ra.lam = c.lam; ra.alpha = c.alpha;
+    ra.loss = c.loss_out; ra.acc = c.acc_out; ra.logits = c.logits_out;
+    ra.dfs = with_grad ? ap.dfs : nullptr; ra.dfq = with_grad ? ap.dfq : nullptr; ra.dhyper = with_grad ? c.dhyper_out : nullptr;
+    LAUNCH(e, st, OP_RIDGE_HEAD, 0, launch_ridge_head(st, ra, T));
+  } else {
+    MetricArgs ma{};
+    ma.fs = ap.fs; ma.fq = ap.fq; ma.ys = ap.ys; ma.yq = ap.yq;
+    ma.ns = n; ma.nq = n; ma.feat = e->feat; ma.ways = c.ways; ma.metric = c.metric; ma.scale = c.scale;
+    ma.loss = c.loss_out; ma.acc = c.acc_out; ma.logits = c.logits_out;
+    ma.dfs = with_grad ? ap.dfs : nullptr; ma.dfq = with_grad ? ap.dfq : nullptr;
+    LAUNCH(e, st, OP_METRIC_HEAD, 0, launch_metric_head(st, ma, T));
+  }
   if (!with_grad) return MI_OK;
   HIPCHK(e, hipMemsetAsync(ap.lam, 0, TP * sizeof(float), st));
   LAUNCH(e, st, OP_MISC, 4, launch_interleave_rows(st, ap.dfs, ap.dfq, T, n, e->feat, ap.act.dp[nl - 1]));
@@ -1762,8 +1800,10 @@ static int meta_batch_metric_impl(mi_engine* e, void* stream, const MetaCall& c)
 // nothing that can alias.  The step sizes' VALUES are read on the device at every replay, like theta's.
 static GraphKey graph_key(const mi_engine* e, void* stream, const MetaCall& c) {
   typedef unsigned long long u;
-  unsigned lr_bits, scale_bits;
+  unsigned lr_bits, scale_bits, lam_bits, alpha_bits;
   memcpy(&lr_bits, &c.inner_lr, sizeof lr_bits);
+  memcpy(&lam_bits, &c.lam, sizeof lam_bits);
+  memcpy(&alpha_bits, &c.alpha, sizeof alpha_bits);
   memcpy(&scale_bits, &c.scale, sizeof scale_bits);
   return GraphKey{(u)c.algo, (u)(uintptr_t)stream, (u)(uintptr_t)c.theta, (u)(uintptr_t)c.data, (u)(uintptr_t)c.labels, (u)c.tasks,
                   (u)c.grad_tasks, (u)c.ways, (u)c.shots, (u)c.adapt_steps, (u)c.second_order, (u)lr_bits, (u)(uintptr_t)c.lr_vec,
@@ -1771,13 +1811,13 @@ static GraphKey graph_key(const mi_engine* e, void* stream, const MetaCall& c) {
                   (u)(uintptr_t)c.meta_grad_out, (u)(uintptr_t)c.logits_out, (u)(uintptr_t)c.workspace, (u)c.workspace_bytes,
                   (u)e->fuse1, (u)e->gram1, (u)e->gramq, (u)e->overlap, (u)e->fuse_fin, (u)e->fuse_b1red, (u)e->fuse_tail, (u)e->fuse_last,
                   kernel_selection_key(), (u)(uintptr_t)c.step_w, (u)(uintptr_t)c.offsets, (u)(uintptr_t)c.offsets_grad_out,
-                  (u)c.metric, (u)scale_bits};
+                  (u)c.metric, (u)scale_bits, (u)lam_bits, (u)alpha_bits, (u)(uintptr_t)c.dhyper_out};
 }
 
 static int meta_batch_entry(mi_engine* e, void* stream, const MetaCall& c) {
   const int crc = check_call(e, c);
   if (crc) return crc;
-  const auto fn = c.algo == ALGO_METRIC ? meta_batch_metric_impl : is_anil(c.algo) ? meta_batch_anil_impl : meta_batch_maml_impl;
+  const auto fn = (c.algo == ALGO_METRIC || c.algo == ALGO_RIDGE) ? meta_batch_metric_impl : is_anil(c.algo) ? meta_batch_anil_impl : meta_batch_maml_impl;
   if (!e->graph_on || e->prof_on || e->trace || e->bn_export || !stream)     // (capture is not permitted on the legacy default stream)
     return fn(e, stream, c);
   const GraphKey key = graph_key(e, stream, c);
@@ -1917,6 +1957,22 @@ extern "C" int mi_meta_batch_metric(mi_engine* e, void* stream, const float* the
              meta_grad_out, logits_out, workspace, workspace_bytes};
   c.metric = metric;
   c.scale = scale;
+  return meta_batch_entry(e, stream, c);
+}
+
+// The ridge-regression head (R2-D2) on the ANIL engine's trunk: mi_meta_batch_metric's launches around launch_ridge_head (include/mi_maml.h).
+extern "C" int mi_ridge_workspace_bytes(const mi_engine* e, int tasks, int ways, int shots, int with_grad, size_t* bytes) {
+  return mi_metric_workspace_bytes(e, tasks, ways, shots, with_grad, bytes);
+}
+extern "C" int mi_meta_batch_ridge(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
+                                   int tasks, int ways, int shots, float lam, float alpha, int with_grad,
+                                   float* loss_out, float* acc_out, float* meta_grad_out, float* dhyper_out, float* logits_out,
+                                   void* workspace, size_t workspace_bytes) {
+  MetaCall c{ALGO_RIDGE, theta, data, labels, tasks, with_grad ? tasks : 0, ways, shots, 0, 0, 0.f, nullptr, 0, nullptr, loss_out, acc_out,
+             meta_grad_out, logits_out, workspace, workspace_bytes};
+  c.lam = lam;
+  c.alpha = alpha;
+  c.dhyper_out = dhyper_out;
   return meta_batch_entry(e, stream, c);
 }
 
@@ -2280,6 +2336,28 @@ extern "C" int mi_metric_head(void* stream, const float* fs, const float* fq, co
   ma.fs = fs; ma.fq = fq; ma.ys = ys; ma.yq = yq; ma.ns = ns; ma.nq = nq; ma.feat = feat; ma.ways = ways; ma.metric = metric; ma.scale = scale;
   ma.loss = loss; ma.acc = acc; ma.logits = logits; ma.dfs = dfs; ma.dfq = dfq;
   HIPCHK0(launch_metric_head(reinterpret_cast<hipStream_t>(stream), ma, tasks));
+  return MI_OK;
+}
+
+// launch_ridge_head: the ridge head's kernel entry (include/mi_maml.h).  Everything is folded inside the one launch: no scratch.
+extern "C" size_t mi_ridge_head_scratch_bytes(int tasks, int ns, int nq, int feat, int ways) {
+  (void)tasks; (void)ns; (void)nq; (void)feat; (void)ways;
+  return 0;
+}
+extern "C" int mi_ridge_head(void* stream, const float* fs, const float* fq, const int32_t* ys, const int32_t* yq, int tasks, int ns, int nq,
+                             int feat, int ways, float lam, float alpha, float* loss, float* acc, float* logits, float* dfs, float* dfq,
+                             float* dhyper, void* scratch, size_t scratch_bytes) {
+  (void)scratch; (void)scratch_bytes;
+  if (!fs || !fq || !ys || !yq || !loss || !acc) return fail(nullptr, MI_ERR_ARG, "mi_ridge_head: null pointer argument");
+  if (tasks < 1) return fail(nullptr, MI_ERR_ARG, "mi_ridge_head: tasks must be >= 1, got " + std::to_string(tasks));
+  if (const int hrc = ridge_hyper_check(nullptr, "mi_ridge_head", lam, alpha)) return hrc;
+  if (((reinterpret_cast<uintptr_t>(fs) | reinterpret_cast<uintptr_t>(fq) | reinterpret_cast<uintptr_t>(dfs) | reinterpret_cast<uintptr_t>(dfq)) & 15) != 0)
+    return fail(nullptr, MI_ERR_ARG, "mi_ridge_head: fs, fq, dfs and dfq must be 16-byte aligned");
+  RIDGE_LDS(nullptr, "mi_ridge_head", ns, nq, feat, ways);
+  RidgeArgs ra{};
+  ra.fs = fs; ra.fq = fq; ra.ys = ys; ra.yq = yq; ra.ns = ns; ra.nq = nq; ra.feat = feat; ra.ways = ways; ra.lam = lam; ra.alpha = alpha;
+  ra.loss = loss; ra.acc = acc; ra.logits = logits; ra.dfs = dfs; ra.dfq = dfq; ra.dhyper = dhyper;
+  HIPCHK0(launch_ridge_head(reinterpret_cast<hipStream_t>(stream), ra, tasks));
   return MI_OK;
 }
 

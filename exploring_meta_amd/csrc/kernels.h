@@ -275,6 +275,23 @@ size_t metric_head_lds_bytes(int ns, int nq, int feat, int ways);
 bool metric_head_fits(int ns, int nq, int feat, int ways);
 hipError_t launch_metric_head(hipStream_t st, const MetricArgs& a, int tasks);
 
+// ridge_head.hip: the ridge-regression head (R2-D2) on the features of a whole meta-batch, solved and differentiated in one launch
+struct RidgeArgs {
+  const float* fs; const float* fq;      // [T][ns][F], [T][nq][F], 16-byte aligned
+  const int32_t* ys; const int32_t* yq;  // [T][ns], [T][nq] in [0, ways)
+  int ns, nq, feat, ways;
+  float lam, alpha;                      // > 0 and finite
+  float* loss; float* acc;               // [T]
+  float* logits;                         // [T][nq][ways] (may be null)
+  float* dfs; float* dfq;                // [T][ns][F], [T][nq][F], 16-byte aligned (may be null)
+  float* dhyper;                         // [T][2]: (dlam, dalpha) per task (may be null; dfs, dfq and dhyper all null: forward only)
+};
+// Dynamic LDS of one task (everything ns-sized, fp64; feat does not enter) against the CU's LDS; the launcher refuses what does not fit with
+// hipErrorInvalidValue before launching anything -- callers check ridge_head_fits first and report MI_ERR_ARG.
+size_t ridge_head_lds_bytes(int ns, int nq, int ways);
+bool ridge_head_fits(int ns, int nq, int feat, int ways);
+hipError_t launch_ridge_head(hipStream_t st, const RidgeArgs& a, int tasks);
+
 // tail.hip: the last ConvBlock's BatchNorm + ReLU + MaxPool, the head, the head's backward and that block's BatchNorm-backward SUMS (or their
 // tangents) in one launch, four workgroups (row groups) per task; cross-workgroup sums by the last arriver (finalize.h protocol).
 struct TailArgs {

@@ -6,6 +6,7 @@ used only for device memory and streams; all arithmetic runs in libmi_maml's HIP
 """
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 
 import torch
@@ -115,6 +116,15 @@ def check_scale(scale):
     if not scale > 0.0:
         raise _lib.MiError(f'libmi_maml error -1: the metric head\'s scale must be positive, got {scale}')
     return scale
+
+
+def check_ridge(lam, scale):
+    """(lam, scale) of the ridge head as floats; anything not > 0 or not finite is refused here, before the library is touched."""
+    lam, scale = float(lam), float(scale)
+    for name, v in (('lam', lam), ('scale', scale)):
+        if not (v > 0.0 and math.isfinite(v)):
+            raise _lib.MiError(f'libmi_maml error -1: the ridge head\'s {name} must be positive and finite, got {v}')
+    return lam, scale
 
 
 class MetaEngine:
@@ -588,6 +598,51 @@ class MetaEngine:
         _lib.check(self.lib.mi_metric_head(_stream(self.device), _ptr(fs), _ptr(fq), _ptr(ys), _ptr(yq), T, ns, nq, feat, int(ways), m, scale,
                                            _ptr(loss), _ptr(acc), _ptr(logits), _ptr(dfs), _ptr(dfq), _ptr(scr), nscr), None)
         return loss, acc, logits, dfs, dfq
+
+    @_on_device
+    def meta_batch_ridge(self, theta, data, labels, shots, lam=1.0, scale=1.0, with_grad=True, return_logits=False):
+        """The ridge-regression head (R2-D2) on the ANIL trunk (mi_meta_batch_ridge): per task A = (fs fs^T + lam I)^-1 onehot(ys), logits
+        scale * (fq fs^T) A -- the head's inner problem solved exactly, no inner loop.  theta keeps the ANIL layout; the head's entries
+        are not used and their gradient is exactly zero.  Returns (loss[T], acc[T], meta_grad[P] or None, dhyper [T, 2] or None, logits
+        [T, S*W, ways] or None); dhyper[t] = (dloss_t/dlam, dloss_t/dscale), per task: the sum is the caller's."""
+        lam, scale = check_ridge(lam, scale)
+        s = self.spec
+        T = self._check_batch(theta, data, labels, shots, flat_data=False)
+        b = C.c_size_t()
+        _lib.check(self.lib.mi_ridge_workspace_bytes(self._h, T, s.ways, shots, int(bool(with_grad)), C.byref(b)), self._h)
+        ws = self._workspace(b.value)
+        loss, acc, grad, logits = self._outputs(('ridge',), T, shots * s.ways, with_grad, return_logits)
+        dhyper = self._persistent(('ridge_dhyper', T), lambda: torch.empty(T, 2, dtype=torch.float32, device=self.device)) if with_grad else None
+        rc = self._fused_call(self.lib.mi_meta_batch_ridge, _ptr(theta), _ptr(data), _ptr(labels), T, s.ways, shots, lam, scale,
+                              int(bool(with_grad)), _ptr(loss), _ptr(acc), _ptr(grad), _ptr(dhyper), _ptr(logits), _ptr(ws), ws.numel())
+        _lib.check(rc, self._h)
+        return loss, acc, grad, dhyper, logits
+
+    @_on_device
+    def ridge_head(self, fs, fq, ys, yq, ways, lam=1.0, scale=1.0, with_grad=True):
+        """The ridge head's kernel entry (mi_ridge_head) on given features: fs [T, ns, F], fq [T, nq, F] fp32, ys [T, ns], yq [T, nq] int32
+        in [0, ways).  Returns (loss[T], acc[T], logits [T, nq, ways], dfs, dfq, dhyper [T, 2]), the last three None without a gradient."""
+        lam, scale = check_ridge(lam, scale)
+        for t, dt in ((fs, torch.float32), (fq, torch.float32), (ys, torch.int32), (yq, torch.int32)):
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                raise ValueError('fs / fq must be contiguous fp32 CUDA tensors, ys / yq contiguous int32 CUDA tensors')
+        if fs.dim() != 3 or fq.dim() != 3 or fs.shape[0] != fq.shape[0] or fs.shape[2] != fq.shape[2] or \
+                tuple(ys.shape) != tuple(fs.shape[:2]) or tuple(yq.shape) != tuple(fq.shape[:2]):
+            raise ValueError(f'fs [T, ns, F], fq [T, nq, F], ys [T, ns], yq [T, nq]; got {tuple(fs.shape)}, {tuple(fq.shape)}, '
+                             f'{tuple(ys.shape)}, {tuple(yq.shape)}')
+        T, ns, feat = fs.shape
+        nq = fq.shape[1]
+        loss = torch.empty(T, dtype=torch.float32, device=self.device)
+        acc = torch.empty(T, dtype=torch.float32, device=self.device)
+        logits = torch.empty(T, nq, ways, dtype=torch.float32, device=self.device)
+        dfs = torch.empty_like(fs) if with_grad else None
+        dfq = torch.empty_like(fq) if with_grad else None
+        dhyper = torch.empty(T, 2, dtype=torch.float32, device=self.device) if with_grad else None
+        nscr = self.lib.mi_ridge_head_scratch_bytes(T, ns, nq, feat, int(ways))
+        scr = torch.empty(nscr, dtype=torch.uint8, device=self.device) if nscr else None
+        _lib.check(self.lib.mi_ridge_head(_stream(self.device), _ptr(fs), _ptr(fq), _ptr(ys), _ptr(yq), T, ns, nq, feat, int(ways), lam, scale,
+                                          _ptr(loss), _ptr(acc), _ptr(logits), _ptr(dfs), _ptr(dfq), _ptr(dhyper), _ptr(scr), nscr), None)
+        return loss, acc, logits, dfs, dfq, dhyper
 
     @_on_device
     def forward_logits(self, theta, x):

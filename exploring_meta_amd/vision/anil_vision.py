@@ -144,6 +144,12 @@ def run(dataset, p, log=print):
         metrics['nil_test_acc'] = evaluate_nil(p, test, features, device)
         if rank == 0:
             log(f"nil_test_acc: {metrics['nil_test_acc']}")
+    if p.get('ridge_test'):      # --ridge_test: how good is the exactly solved head on these features?  (R2-D2's ridge regression, fixed lam / scale)
+        from ..core_functions.ridge import RidgeHead, evaluate_ridge
+        test = SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6)
+        metrics['ridge_test_acc'] = evaluate_ridge(p, test, features, RidgeHead(p['ridge_lam'], p['ridge_scale'], learnable=False), device)
+        if rank == 0:
+            log(f"ridge_test_acc: {metrics['ridge_test_acc']}")
     if world > 1:
         torch.distributed.destroy_process_group()
     return (features, head), metrics
@@ -166,6 +172,10 @@ def build_parser():
                         help='iterations over which the multi-step weights anneal to the final step; from iteration N on the plain call runs')
     parser.add_argument('--nil_test', action='store_true',
                         help='after training also log nil_test_acc: the trunk scored on meta_batch_size test tasks by the NIL cosine head, no inner loop')
+    parser.add_argument('--ridge_test', action='store_true',
+                        help='after training also log ridge_test_acc: the trunk under the exactly solved ridge-regression head (R2-D2) with the fixed --ridge_lam / --ridge_scale, no inner loop')
+    parser.add_argument('--ridge_lam', type=float, default=1.0, metavar='LAM', help="--ridge_test: the ridge head's regulariser")
+    parser.add_argument('--ridge_scale', type=float, default=1.0, metavar='S', help="--ridge_test: the ridge head's logit scale")
     return parser
 
 
@@ -177,7 +187,8 @@ def params_of(args):
     """The run's parameter dict from parsed flags (the defaults are the reference's run)."""
     p = {k: getattr(args, k) for k in params}
     p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
-             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations, nil_test=args.nil_test)
+             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations, nil_test=args.nil_test,
+             ridge_test=args.ridge_test, ridge_lam=args.ridge_lam, ridge_scale=args.ridge_scale)
     return p
 
 

@@ -77,6 +77,8 @@ def run(dataset, p, first_order=False, log=print):
     random.seed(p['seed']); np.random.seed(p['seed']); torch.manual_seed(p['seed']); torch.cuda.manual_seed(p['seed'])
     device = torch.device('cuda', local)
     model = (OmniglotCNN(p['ways']) if dataset == 'omni' else MiniImagenetCNN(p['ways'])).to(device)
+    if p.get('ridge_test') and isinstance(model, OmniglotCNN):
+        raise NotImplementedError('--ridge_test scores flattened features; OmniglotCNN feeds its head their spatial mean (use --dataset min)')
     if p.get('nil_test') and isinstance(model, OmniglotCNN):      # (before the training, not after it)
         raise NotImplementedError('--nil_test scores flattened features; OmniglotCNN feeds its head their spatial mean (use --dataset min)')
     maml = MAML(model, lr=inner_lr_of(model, p), first_order=first_order, offsets=step_offsets_of(model, p))
@@ -161,6 +163,12 @@ def run(dataset, p, first_order=False, log=print):
         metrics['nil_test_acc'] = evaluate_nil(p, SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6), model, device)
         if rank == 0:
             log(f"nil_test_acc: {metrics['nil_test_acc']}")
+    if p.get('ridge_test'):      # --ridge_test: the same number of test tasks under the exactly solved ridge-regression head on the trunk alone
+        from ..core_functions.ridge import RidgeHead, evaluate_ridge
+        metrics['ridge_test_acc'] = evaluate_ridge(p, SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6), model,
+                                                   RidgeHead(p['ridge_lam'], p['ridge_scale'], learnable=False), device)
+        if rank == 0:
+            log(f"ridge_test_acc: {metrics['ridge_test_acc']}")
     if world > 1:
         torch.distributed.destroy_process_group()
     if save_dir and rank == 0:
@@ -197,6 +205,10 @@ def build_parser():
     parser.add_argument('--min_outer_lr', type=float, default=0.0, metavar='X', help='the floor of --cosine_outer_lr')
     parser.add_argument('--nil_test', action='store_true',
                         help='after the test accuracy also log nil_test_acc: the trunk alone under the NIL cosine head (flattened features: --dataset min)')
+    parser.add_argument('--ridge_test', action='store_true',
+                        help='after the test accuracy also log ridge_test_acc: the trunk under the exactly solved ridge-regression head (R2-D2) with the fixed --ridge_lam / --ridge_scale (flattened features: --dataset min)')
+    parser.add_argument('--ridge_lam', type=float, default=1.0, metavar='LAM', help="--ridge_test: the ridge head's regulariser")
+    parser.add_argument('--ridge_scale', type=float, default=1.0, metavar='S', help="--ridge_test: the ridge head's logit scale")
     return parser
 
 
@@ -206,7 +218,8 @@ def params_of(args):
     p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
              freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations,
              per_step_bn=args.per_step_bn, per_step_bn_adapt_bn=args.per_step_bn_adapt_bn, first_order_iterations=args.first_order_iterations,
-             cosine_outer_lr=args.cosine_outer_lr, min_outer_lr=args.min_outer_lr, nil_test=args.nil_test)
+             cosine_outer_lr=args.cosine_outer_lr, min_outer_lr=args.min_outer_lr, nil_test=args.nil_test,
+             ridge_test=args.ridge_test, ridge_lam=args.ridge_lam, ridge_scale=args.ridge_scale)
     return p
 
 

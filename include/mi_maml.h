@@ -328,6 +328,42 @@ int mi_meta_batch_metric(mi_engine* e, void* stream, const float* theta, const f
                          float* loss_out, float* acc_out, float* meta_grad_out, float* logits_out,
                          void* workspace, size_t workspace_bytes);
 
+/* Ridge-regression head (R2-D2, "Meta-learning with differentiable closed-form solvers"): the head's inner problem under a squared loss,
+ * solved to optimality on the support features in the dual form and differentiated through the solve (csrc/ridge_head.hip, DESIGN.md
+ * section 28).  Per task, Y = onehot(ys) [ns, ways], labels in [0, ways):
+ *   G = fs fs^T + lam I,  A = G^-1 Y,  z = alpha * (fq fs^T) A;  loss_t = mean_q CE(z_q, yq_q);  acc_t = mean_q [argmax_w z_q == yq_q]
+ *   (first maximum of the fp32 logits returned);  dfs, dfq = d(sum_t loss_t)/d(fs, fq);  dhyper[t] = (dloss_t/dlam, dloss_t/dalpha).
+ * No additive logit bias: under softmax cross-entropy its gradient is identically zero.  A class without a support row is legal here (its
+ * column of A is zero).  mi_ridge_head is the kernel entry: fs [tasks, ns, feat], fq [tasks, nq, feat] fp32 (16-byte aligned, like dfs /
+ * dfq), ys [tasks, ns], yq [tasks, nq] int32; ns != nq and unbalanced classes are fine.  loss, acc [tasks]; logits [tasks, nq, ways], dfs,
+ * dfq [as fs, fq] and dhyper [tasks, 2] may each be NULL, in any combination (dfs, dfq and dhyper all NULL: the forward-only launch, whose
+ * loss, acc and logits are the bits of the forward + backward launch).  dhyper is per task, so that the sum over tasks is the caller's and
+ * stays deterministic.  ONE launch whatever `tasks`; a task's results do not depend on the other tasks of the call.  The Gram system is
+ * accumulated, factorised (G = L D L^T) and solved in fp64 in LDS.  A pivot that is not > 0 cannot occur for a sane lam (G is positive
+ * definite); should it occur, every output of that task is NaN -- never a fault, never an endless loop.  The domain (MI_ERR_ARG naming
+ * the sizes before any launch otherwise): tasks, ns, nq >= 1, 1 <= feat <= MI_RIDGE_MAX_FEAT (a stated cap: feat does not enter the LDS
+ * request), 1 <= ways <= 64, lam and alpha > 0 and finite, and one task's tables inside the 160 KiB of LDS:
+ *   8 * (ns (ns + 1) / 2 + nq * ns + 2 * ns * ways + ns + 3 * nq) + 4 * nq * ways <= 163840 bytes
+ * -- ns = nq = 100 with 20 ways (Omniglot 20-way 5-shot) takes 163600; ns = nq = 25, 5 ways: 10900; ns = nq = 5, 5 ways: 980.
+ * mi_ridge_head_scratch_bytes: the kernel folds everything inside its launch and needs no scratch today: 0, and scratch may be NULL. */
+#define MI_RIDGE_MAX_FEAT 65536
+size_t mi_ridge_head_scratch_bytes(int tasks, int ns, int nq, int feat, int ways);
+int mi_ridge_head(void* stream, const float* fs, const float* fq, const int32_t* ys, const int32_t* yq,
+                  int tasks, int ns, int nq, int feat, int ways, float lam, float alpha,
+                  float* loss, float* acc, float* logits /*nullable*/, float* dfs /*nullable*/, float* dfq /*nullable*/,
+                  float* dhyper /*nullable*/, void* scratch, size_t scratch_bytes);
+/* One meta-batch scored (and differentiated) by the ridge head on the ANIL trunk: mi_meta_batch_metric's call with mi_ridge_head's launch
+ * in the metric head's place -- the same engine, theta / meta_grad_out layout (the head's entries of theta are unused, those of
+ * meta_grad_out exact zeros), data / labels, workspace plan, launches, graph replay and BatchNorm export; the evaluation call keeps the
+ * input Gram matrix, so its loss, acc and logits are the bits of the call with a gradient.  dhyper_out [tasks, 2] or NULL: (dlam, dalpha)
+ * per task, written only with a gradient.  The bits of lam and alpha are part of the graph's signature.  MI_ERR_ARG before any launch:
+ * lam or alpha not > 0 or not finite, sizes outside mi_ridge_head's domain, and what mi_meta_batch_metric refuses. */
+int mi_ridge_workspace_bytes(const mi_engine* e, int tasks, int ways, int shots, int with_grad, size_t* bytes);
+int mi_meta_batch_ridge(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
+                        int tasks, int ways, int shots, float lam, float alpha, int with_grad,
+                        float* loss_out, float* acc_out, float* meta_grad_out, float* dhyper_out /*nullable*/, float* logits_out /*nullable*/,
+                        void* workspace, size_t workspace_bytes);
+
 /* Plain classifier forward, no adaptation: `learner(x)` / `model(x)` (vision_models.py:51-55,107-110), BatchNorm in train
  * mode over the n images of each of the `tasks` batches.  x [tasks, n, C, H, W] NCHW; logits_out [tasks, n, ways]. */
 int mi_forward_workspace_bytes(const mi_engine* e, int tasks, int n, size_t* bytes);

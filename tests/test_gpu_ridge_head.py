@@ -1,0 +1,464 @@
+"""The ridge-regression head on the GPU (mi_ridge_head, mi_meta_batch_ridge, include/mi_maml.h): the kernel entry
+against the fp64 oracle of the definition (tests/ridge_head_oracle.py) at sizes on both sides of every path the kernel takes (feat not a
+multiple of 4, one feature, more rows than a tile, one class, unbalanced classes, ns != nq, Omniglot 20-way 5-shot, which fills the LDS),
+its exact edge cases and bitwise relations, its domain; the fused call against the oracle on vision_ref's trunk under every operand
+form; graph replay and the launch make-up; the Python surface and the driver."""
+import ctypes as C
+import functools
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from exploring_meta_amd import _lib
+from exploring_meta_amd import core_functions as cf
+from exploring_meta_amd.engine import MetaEngine, ModelSpec
+from exploring_meta_amd.utils import synthetic
+from oracle import vision_ref as R
+from gpu_utils import dev, ptr, rel_err, report, stream
+import ridge_head_oracle as RH
+
+pytestmark = pytest.mark.gpu
+
+NAMES = ('loss', 'acc', 'logits', 'dfs', 'dfq', 'dhyper')
+
+
+def _np(*ts):
+    torch.cuda.synchronize()
+    return tuple(None if t is None else t.detach().cpu().numpy().copy() for t in ts)
+
+
+def _held(name, err, ref_err, floor):
+    """err <= max(floor, 2 x the fp32 oracle's own error on the same inputs): both terms come from the reference side."""
+    print(f'[held] {name}: err {np.max(err):.3e} fp32-oracle err {np.max(ref_err):.3e} floor {np.max(floor):.3e}')
+    assert np.all(np.asarray(err) <= np.maximum(floor, 2 * np.asarray(ref_err))), (name, err, ref_err, floor)
+
+
+def _same(tag, names, got, want):
+    for name, a, b in zip(names, got, want):
+        assert (a is None and b is None) or np.array_equal(a, b), (tag, name, rel_err(a, b))
+
+
+def _kernel(fs, fq, ys, yq, ways, lam, alpha, dfs=True, dfq=True, dhyper=True, logits=True, fill=None):
+    """mi_ridge_head on numpy inputs -> (rc, numpy loss, acc, logits, dfs, dfq, dhyper); outputs the call does not take are None.  fill:
+    the outputs start as this value (to see that a refused call leaves them alone)."""
+    lib = _lib.load()
+    fsd, fqd, ysd, yqd = dev(fs), dev(fq), dev(ys, torch.int32), dev(yq, torch.int32)
+    T, ns, feat = fs.shape
+    nq = fq.shape[1]
+    mk = (lambda *shape: torch.full(shape, float(fill), device='cuda')) if fill is not None else (lambda *shape: torch.empty(*shape, device='cuda'))
+    loss, acc = mk(T), mk(T)
+    lo = mk(T, nq, ways) if logits else None
+    gs = mk(T, ns, feat) if dfs else None
+    gq = mk(T, nq, feat) if dfq else None
+    dh = mk(T, 2) if dhyper else None
+    nscr = lib.mi_ridge_head_scratch_bytes(T, ns, nq, feat, ways)
+    scr = torch.empty(max(nscr, 1), dtype=torch.uint8, device='cuda')
+    rc = lib.mi_ridge_head(stream(), ptr(fsd), ptr(fqd), ptr(ysd), ptr(yqd), T, ns, nq, feat, ways, float(lam), float(alpha), ptr(loss),
+                           ptr(acc), ptr(lo), ptr(gs), ptr(gq), ptr(dh), ptr(scr), nscr)
+    return (rc,) + _np(loss, acc, lo, gs, gq, dh)
+
+
+def _loss_err(a, b):
+    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300))) if np.any(b != 0) else float(np.max(np.abs(a)))
+
+
+def _check_kernel(tag, got, fs, fq, ys, yq, ways, lam, alpha):
+    """Per quantity: relative error <= max(2 x the fp32 autograd oracle's own error against fp64, 4 eps_fp32 cond_2(G)) -- the second term
+    is the first-order forward error of a backward-stable fp32 solve; argmax and accuracy equal on every row."""
+    o64 = RH.head(fs, fq, ys, yq, ways, lam, alpha, torch.float64)
+    o32 = RH.head(fs, fq, ys, yq, ways, lam, alpha, torch.float32)
+    cond = float(o64[6].max())
+
+    def errs(o):
+        loss, _, logits, dfs, dfq, dh = o[:6]
+        return dict(loss=_loss_err(loss, o64[0]), logits=rel_err(logits, o64[2]), dfs=rel_err(dfs, o64[3]), dfq=rel_err(dfq, o64[4]),
+                    dlam=rel_err(dh[:, 0], o64[5][:, 0]), dalpha=rel_err(dh[:, 1], o64[5][:, 1]))
+    e, r = errs(got), errs(o32)
+    report(f'ridge_head[{tag}]', cond=cond, **{f'{n}_rel_err': v for n, v in e.items()}, **{f'ref_fp32_{n}_rel_err': v for n, v in r.items()})
+    for n in e:
+        _held(f'{tag} {n}', e[n], r[n], 4 * RH.EPS32 * cond)
+    assert np.array_equal(got[2].argmax(axis=-1), o64[2].argmax(axis=-1))
+    assert np.array_equal(got[1], o64[1].astype(np.float32))
+    return o64
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1: the kernel entry
+@pytest.mark.parametrize('lam,alpha', RH.HYPERS)
+@pytest.mark.parametrize('feat,ways,ns,nq,T', RH.KERNEL_CASES)
+def test_kernel_against_the_fp64_oracle(feat, ways, ns, nq, T, lam, alpha):
+    fs, fq, ys, yq = RH.kernel_inputs(feat, ways, ns, nq, T)
+    rc, *got = _kernel(fs, fq, ys, yq, ways, lam, alpha)
+    assert rc == 0, _lib.load().mi_last_error(None)
+    o64 = _check_kernel(f'{feat}-{ways}-{ns}/{nq}-T{T}-lam{lam:g}', got, fs, fq, ys, yq, ways, lam, alpha)
+    if ways == 1:       # one class: loss exactly 0, accuracy 1, every gradient exactly 0
+        assert all(np.all(g == 0) for g in (got[0], got[3], got[4], got[5])) and np.all(got[1] == 1)
+    else:               # the case tests something
+        assert np.all(o64[0] > 1e-3) and np.abs(o64[3]).sum() > 0 and np.abs(o64[4]).sum() > 0 and np.all(o64[5] != 0)
+
+
+def test_domain_limits():
+    """feat = MI_RIDGE_MAX_FEAT at ns = nq = ways = 5 computes; one feature more is MI_ERR_ARG naming the sizes, nothing launched and the
+    outputs untouched; so is the first row count whose tables leave the LDS (101 rows at 20 ways; 100 is a kernel case)."""
+    ways, n = 5, 5
+    feat = RH.MAX_FEAT
+    fs, fq, ys, yq = RH.kernel_inputs(feat, ways, n, n, 1)
+    rc, *got = _kernel(fs, fq, ys, yq, ways, 1.0, 8.0)
+    assert rc == 0, _lib.load().mi_last_error(None)
+    _check_kernel(f'limit-{feat}', got, fs, fq, ys, yq, ways, 1.0, 8.0)
+    fs, fq, ys, yq = RH.kernel_inputs(feat + 1, ways, n, n, 1)
+    rc, *got = _kernel(fs, fq, ys, yq, ways, 1.0, 8.0, fill=-7.0)
+    assert rc == -1
+    msg = _lib.load().mi_last_error(None).decode()
+    assert 'mi_ridge_head' in msg and f'feat = {feat + 1}' in msg and 'ns = 5' in msg and 'LDS' in msg, msg
+    assert all(np.all(g == -7.0) for g in got)
+    assert RH.lds_bytes(100, 100, 20) <= 163840 < RH.lds_bytes(101, 101, 20)
+    fs, fq, ys, yq = RH.kernel_inputs(8, 20, 101, 101, 1)
+    rc, *got = _kernel(fs, fq, ys, yq, 20, 1.0, 8.0, fill=-7.0)
+    msg = _lib.load().mi_last_error(None).decode()
+    assert rc == -1 and 'ns = 101' in msg and str(RH.lds_bytes(101, 101, 20)) in msg, msg
+    assert all(np.all(g == -7.0) for g in got)
+
+
+def test_argument_errors_launch_nothing():
+    fs, fq, ys, yq = RH.kernel_inputs(32, 5, 5, 5, 1)
+    for kw, text in ((dict(ways=65), 'ways'), (dict(lam=0.0), 'lam must be positive'), (dict(lam=float('nan')), 'lam must be positive'),
+                     (dict(lam=float('inf')), 'lam must be positive'), (dict(alpha=-1.0), 'alpha must be positive'),
+                     (dict(alpha=0.0), 'alpha must be positive'), (dict(alpha=float('nan')), 'alpha must be positive')):
+        args = dict(ways=5, lam=1.0, alpha=8.0)
+        args.update(kw)
+        rc, *got = _kernel(fs, fq, ys, yq, args['ways'], args['lam'], args['alpha'], fill=-7.0)
+        assert rc == -1 and text in _lib.load().mi_last_error(None).decode(), _lib.load().mi_last_error(None)
+        assert all(np.all(g == -7.0) for g in got)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2: exact edge cases
+def test_all_features_equal_ties_go_to_class_zero():
+    ways, n, feat = 5, 10, 40
+    fs, fq, ys, yq = RH.kernel_inputs(feat, ways, n, n, 1)
+    fs[:], fq[:] = 1.5, 1.5
+    rc, loss, acc, logits, dfs, dfq, dh = _kernel(fs, fq, ys, yq, ways, 1.0, 8.0)
+    assert rc == 0
+    assert np.all(logits == logits[..., :1]), logits                        # every logit of a row ties
+    assert acc[0] == np.float32((yq[0] == 0).mean())                        # the first maximum: class 0
+    assert loss[0] == pytest.approx(math.log(ways), rel=1e-6)
+
+
+@pytest.mark.parametrize('feat,ways,n', [(33, 5, 5), (128, 20, 20), (1600, 5, 25)])
+def test_features_doubled_lam_quadrupled(feat, ways, n):
+    """(2 f, 4 lam): powers of two pass through the Gram sums, the factor and the solves exactly -- loss, acc, logits and dalpha bit for
+    bit, dfs and dfq exactly halved, dlam exactly quartered."""
+    fs, fq, ys, yq = RH.kernel_inputs(feat, ways, n, n, 2)
+    rc, *a = _kernel(fs, fq, ys, yq, ways, 1.0, 8.0)
+    rc2, *b = _kernel(2 * fs, 2 * fq, ys, yq, ways, 4.0, 8.0)
+    assert rc == 0 and rc2 == 0
+    _same('doubled', NAMES[:3], b[:3], a[:3])
+    assert np.array_equal(b[3], a[3] / 2) and np.array_equal(b[4], a[4] / 2) and np.abs(a[3]).sum() > 0
+    assert np.array_equal(b[5][:, 0], a[5][:, 0] / 4) and np.array_equal(b[5][:, 1], a[5][:, 1]) and np.all(a[5] != 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3: bitwise relations
+@pytest.mark.parametrize('feat,ways,ns,nq', [(128, 5, 5, 5), (33, 3, 6, 4), (1600, 5, 25, 25)])
+def test_bitwise_relations(feat, ways, ns, nq):
+    """Task t of a T = 3 call is the T = 1 call on it; forward-only is the forward half of forward + backward; every combination of the
+    nullable outputs the header lists is accepted and changes no other output."""
+    fs, fq, ys, yq = RH.kernel_inputs(feat, ways, ns, nq, 3)
+    rc, *whole = _kernel(fs, fq, ys, yq, ways, 1.0, 8.0)
+    assert rc == 0
+    for t in range(3):
+        rc, *one = _kernel(fs[t:t + 1], fq[t:t + 1], ys[t:t + 1], yq[t:t + 1], ways, 1.0, 8.0)
+        assert rc == 0
+        _same(('task', t), NAMES, [o[0] for o in one], [w[t] for w in whole])
+    rc, *fwd = _kernel(fs, fq, ys, yq, ways, 1.0, 8.0, dfs=False, dfq=False, dhyper=False)
+    assert rc == 0 and fwd[3] is None and fwd[4] is None and fwd[5] is None
+    _same('forward only', NAMES[:3], fwd[:3], whole[:3])
+    for kw in (dict(logits=False), dict(dhyper=False), dict(dfs=False), dict(dfq=False), dict(dfs=False, dfq=False),
+               dict(dfs=False, dfq=False, dhyper=False, logits=False), dict(dfq=False, dhyper=False, logits=False)):
+        rc, *part = _kernel(fs, fq, ys, yq, ways, 1.0, 8.0, **kw)
+        assert rc == 0
+        for name, a, b in zip(NAMES, part, whole):
+            assert (a is None) == (not kw.get(name, True)) and (a is None or np.array_equal(a, b)), (kw, name)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4: the fused call
+def _mspec(shape):
+    _, (hidden, channels, max_pool), hw, _, ways, _ = RH.SHAPES[shape]
+    return ModelSpec.anil(ways, hidden=hidden, channels=channels, max_pool=max_pool, in_hw=hw)
+
+
+def _inputs(shape, ids=None, head=0.0):
+    """(engine spec, theta, data [T, 2n, C, H, W], labels, ways, shots, trunk parameter count) on the GPU; the head's entries of theta
+    are `head` (they are not read: NaN is as good as 0)."""
+    dataset, (_, channels, _), hw, fc, ways, shots = RH.SHAPES[shape]
+    _, tf, _, _, _, _ = RH.fixtures(shape)
+    trunk = R.flatten_params(tf).float()
+    theta = torch.cat([trunk, torch.full((ways * fc + ways,), float(head))]).cuda().contiguous()
+    data, labels = synthetic.make_meta_batch(dataset, list(ids if ids is not None else RH.FUSED_CASES[shape][0]), ways, shots)
+    data = torch.from_numpy(data).reshape(data.shape[0], data.shape[1], channels, hw, hw).cuda().contiguous()
+    return _mspec(shape), theta, data, torch.from_numpy(labels).cuda().contiguous(), ways, shots, trunk.numel()
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(shape, fp64, ids=None):
+    """One oracle run per case and precision, shared by every test that needs it (never modified)."""
+    return RH.case_oracle(shape, ids, torch.float64 if fp64 else torch.float32)
+
+
+def _check_fused(tag, shape, got, nf, ids=None):
+    loss, acc, grad, dh, logits = got
+    o64, o32 = _oracle(shape, True, ids), _oracle(shape, False, ids)
+    l64, h64 = o64['losses'], o64['dhyper'].sum(axis=0)
+    errs = dict(loss=np.abs(loss - l64) / np.abs(l64), trunk=rel_err(grad[:nf], o64['grad_feat']),
+                dhyper=np.abs(dh.astype(np.float64).sum(axis=0) - h64) / np.abs(h64))
+    refs = dict(loss=np.abs(o32['losses'] - l64) / np.abs(l64), trunk=rel_err(o32['grad_feat'], o64['grad_feat']),
+                dhyper=np.abs(o32['dhyper'].sum(axis=0) - h64) / np.abs(h64))
+    report(f'ridge_fused[{shape}][{tag}]', loss_rel_err=float(errs['loss'].max()), ref_fp32_loss_rel_err=float(refs['loss'].max()),
+           trunk_rel_err=errs['trunk'], ref_fp32_trunk_rel_err=refs['trunk'], dlam_rel_err=float(errs['dhyper'][0]),
+           ref_fp32_dlam_rel_err=float(refs['dhyper'][0]), dalpha_rel_err=float(errs['dhyper'][1]), ref_fp32_dalpha_rel_err=float(refs['dhyper'][1]))
+    _held('loss', errs['loss'], refs['loss'], RH.LOSS_FLOOR)
+    _held('trunk', errs['trunk'], refs['trunk'], RH.GRAD_FLOOR[shape])
+    _held('dhyper', errs['dhyper'], refs['dhyper'], RH.HYPER_FLOOR)
+    assert grad.shape[0] > nf and np.all(grad[nf:] == 0)                     # the head's entries: exact zeros
+    clear = RH.clear_rows(o64['logits'][None])[0]
+    assert np.all((~clear).sum(axis=-1) * 10 <= clear.shape[-1]), (~clear).sum(axis=-1)
+    assert np.array_equal(logits.argmax(axis=-1)[clear], o64['logits'].argmax(axis=-1)[clear])
+    full = clear.all(axis=-1)
+    assert np.array_equal(acc[full], o64['accs'][full].astype(np.float32))
+
+
+@pytest.mark.parametrize('shape', list(RH.FUSED_CASES))
+def test_fused_call_against_the_fp64_oracle(conv_form, shape):
+    """Every operand form: loss and the summed dhyper within max(1e-4, 2 x the fp32 oracle's error), the trunk gradient within max(the
+    ANIL bar of the same trunk, 2 x the fp32 oracle's error), argmax equal on clear rows, the head's gradient entries exactly zero
+    (theta's head entries are NaN: they are not read).  with_grad = 0: loss, acc and logits bit for bit, meta_grad_out and dhyper_out
+    untouched."""
+    mspec, theta, data, labels, ways, shots, nf = _inputs(shape, head=float('nan'))
+    eng = MetaEngine(mspec)
+    _, lam, alpha = RH.FUSED_CASES[shape]
+    got = _np(*eng.meta_batch_ridge(theta, data, labels, shots, lam=lam, scale=alpha, return_logits=True))
+    _check_fused(conv_form, shape, got, nf)
+    # evaluation only, through the C entry so that meta_grad_out and dhyper_out are buffers of ours
+    T, n = data.shape[0], ways * shots
+    b = C.c_size_t()
+    assert eng.lib.mi_ridge_workspace_bytes(eng._h, T, ways, shots, 0, C.byref(b)) == 0
+    ws = eng._workspace(b.value)
+    P = eng.param_count
+    out = torch.full((P + 2 * T + 2 * T + T * n * ways,), -7.0, device='cuda')
+    rc = eng.lib.mi_meta_batch_ridge(eng._h, stream(), ptr(theta), ptr(data), ptr(labels), T, ways, shots, lam, alpha, 0, ptr(out[P:]),
+                                     ptr(out[P + T:]), ptr(out), ptr(out[P + 2 * T:]), ptr(out[P + 4 * T:]), ptr(ws), ws.numel())
+    assert rc == 0, eng.lib.mi_last_error(eng._h)
+    o = _np(out)[0]
+    assert np.all(o[:P] == -7.0) and np.all(o[P + 2 * T:P + 4 * T] == -7.0)
+    _same('with_grad=0', ('loss', 'acc', 'logits'), (o[P:P + T], o[P + T:P + 2 * T], o[P + 4 * T:].reshape(T, n, ways)), (got[0], got[1], got[4]))
+
+
+def test_fused_call_single_task():
+    """omni at T = 1 (task 0): the oracle's bars, and the bits of task 0 of the four-task call's loss, acc, dhyper and logits."""
+    mspec, theta, data, labels, ways, shots, nf = _inputs('omni', (0,))
+    eng = MetaEngine(mspec)
+    _, lam, alpha = RH.FUSED_CASES['omni']
+    got = _np(*eng.meta_batch_ridge(theta, data, labels, shots, lam=lam, scale=alpha, return_logits=True))
+    _check_fused('T1', 'omni', got, nf, ids=(0,))
+    _, _, data4, labels4, _, _, _ = _inputs('omni')
+    whole = _np(*eng.meta_batch_ridge(theta, data4, labels4, shots, lam=lam, scale=alpha, return_logits=True))
+    _same('task 0', ('loss', 'acc', 'dhyper', 'logits'), [got[i][0] for i in (0, 1, 3, 4)], [whole[i][0] for i in (0, 1, 3, 4)])
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5: engine behaviour
+FUSED_NAMES = ('loss', 'acc', 'grad', 'dhyper', 'logits')
+
+
+def test_graph_replay():
+    """Eager, capture and replays on the same buffers give identical bits, also after theta, data and labels are overwritten IN PLACE; a
+    call with another lam or another alpha does not reuse the graph."""
+    mspec, theta, data, labels, ways, shots, nf = _inputs('omni')
+    _, theta2, data2, labels2, _, _, _ = _inputs('omni', (4, 5, 6, 7))
+    _, lam, alpha = RH.FUSED_CASES['omni']
+    fresh = MetaEngine(mspec)
+    call = lambda e, th, d, l, lm=lam, al=alpha: _np(*e.meta_batch_ridge(th, d, l, shots, lam=lm, scale=al, return_logits=True))
+    want = call(fresh, theta, data, labels)
+    want2 = call(fresh, (theta2 * 0.5).contiguous(), data2, labels2)
+    want_lam = call(fresh, theta, data, labels, lm=lam * 2)
+    want_alpha = call(fresh, theta, data, labels, al=alpha * 2)
+    eng = MetaEngine(mspec)
+    eng.set_graph(True)
+    th, d, l = theta.clone(), data.clone(), labels.clone()
+    for i in range(3):                                     # eager, capture, replay
+        _same(('replay', i), FUSED_NAMES, call(eng, th, d, l), want)
+    _same('other lam', FUSED_NAMES, call(eng, th, d, l, lm=lam * 2), want_lam)
+    _same('other alpha', FUSED_NAMES, call(eng, th, d, l, al=alpha * 2), want_alpha)
+    _same('back', FUSED_NAMES, call(eng, th, d, l), want)
+    th.copy_(theta2 * 0.5); d.copy_(data2); l.copy_(labels2)
+    _same('in place', FUSED_NAMES, call(eng, th, d, l), want2)
+    assert not np.array_equal(want2[0], want[0]) and not np.array_equal(want_lam[0], want[0]) and not np.array_equal(want_alpha[0], want[0])
+    eng.set_graph(False)
+
+
+def _census(eng, fn):
+    eng.profile(True)
+    fn()
+    torch.cuda.synchronize()
+    c = {f'{op}/{layer}': int(n) for (op, layer), (_, n) in eng.profile_collect().items()}
+    eng.profile(False)
+    return c
+
+
+def test_launch_make_up():
+    """Exactly one ridge-head launch per call, whatever the task count; apart from it the launches are mi_meta_batch_metric's."""
+    seen = []
+    for ids in ((0,), (0, 1, 2)):
+        mspec, theta, data, labels, ways, shots, nf = _inputs('omni', ids)
+        eng = MetaEngine(mspec)
+        for with_grad in (True, False):
+            c = _census(eng, lambda: eng.meta_batch_ridge(theta, data, labels, shots, lam=1.0, scale=8.0, with_grad=with_grad))
+            m = _census(eng, lambda: eng.meta_batch_metric(theta, data, labels, shots, metric='proto', scale=0.125, with_grad=with_grad))
+            print(f'[census] ridge call, T = {len(ids)}, with_grad {with_grad}: {sorted(c.items())}')
+            assert c.get('ridge_head/0') == 1 and 'metric_head/0' not in c and 'head_fwd_bwd/0' not in c, c
+            seen.append(dict(c))
+            assert c.pop('ridge_head/0') == 1 and m.pop('metric_head/0') == 1 and c == m, (c, m)
+    assert seen[:2] == seen[2:]
+
+
+def test_fused_argument_errors_come_before_any_launch():
+    mspec, theta, data, labels, ways, shots, nf = _inputs('omni')
+    eng = MetaEngine(mspec)
+    T, P = data.shape[0], eng.param_count
+    with pytest.raises(_lib.MiError, match='lam must be positive'):
+        eng.meta_batch_ridge(theta, data, labels, shots, lam=0.0)
+    with pytest.raises(_lib.MiError, match='scale must be positive'):
+        eng.meta_batch_ridge(theta, data, labels, shots, scale=-1.0)
+    b = C.c_size_t()
+    assert eng.lib.mi_ridge_workspace_bytes(eng._h, T, ways, shots, 1, C.byref(b)) == 0
+    ws = eng._workspace(b.value)
+    out = torch.full((P + 4 * T,), -7.0, device='cuda')
+    eng.profile(True)
+    args = lambda lm, al: (eng._h, stream(), ptr(theta), ptr(data), ptr(labels), T, ways, shots, lm, al, 1, ptr(out[P:]), ptr(out[P + T:]),
+                           ptr(out), ptr(out[P + 2 * T:]), None, ptr(ws), ws.numel())
+    for a, text in ((args(0.0, 1.0), 'lam must be positive'), (args(float('nan'), 1.0), 'lam must be positive'),
+                    (args(1.0, -1.0), 'alpha must be positive'), (args(1.0, float('inf')), 'alpha must be positive')):
+        assert eng.lib.mi_meta_batch_ridge(*a) == -1
+        assert text in eng.lib.mi_last_error(eng._h).decode(), eng.lib.mi_last_error(eng._h)
+    pooled = MetaEngine(ModelSpec.omniglot(ways))                       # a mean-pooled head has no flattened feature vector
+    with pytest.raises(_lib.MiError, match='mean-pooled'):
+        pooled.meta_batch_ridge(torch.zeros(pooled.param_count, device='cuda'), data, labels, shots)
+    torch.cuda.synchronize()
+    assert eng.profile_collect() == {} and bool((out == -7.0).all())
+    eng.profile(False)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 6: the Python surface
+def _trunk(shape):
+    _, (hidden, channels, max_pool), _, fc, ways, _ = RH.SHAPES[shape]
+    _, tf, _, _, _, _ = RH.fixtures(shape)
+    trunk = cf.ConvBase(output_size=64, hidden=hidden, channels=channels, max_pool=max_pool)
+    with torch.no_grad():
+        for k, p in trunk.named_parameters():
+            p.copy_(tf['0.' + k].float())
+    return torch.nn.Sequential(trunk).cuda()
+
+
+def _grads(params):
+    return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params]).cpu().numpy()
+
+
+def test_backward_fills_the_trunk_and_the_heads_two_scalars():
+    mspec, theta, data, labels, ways, shots, nf = _inputs('omni')
+    features = _trunk('omni')
+    head = cf.RidgeHead(lam=1.0, scale=8.0).cuda()
+    lam, alpha = head.lam, head.scale
+    params = list(features.parameters())
+    total, losses, accs = cf.meta_batch_adapt_ridge(features, head, data, labels, shots, ways)
+    assert not losses.requires_grad and tuple(losses.shape) == tuple(accs.shape) == (data.shape[0],)
+    total.backward()
+    l, a, g, dh, _ = _np(*MetaEngine(mspec).meta_batch_ridge(theta, data, labels, shots, lam=lam, scale=alpha))
+    assert np.array_equal(_grads(params), g[:nf]) and np.abs(g[:nf]).sum() > 0
+    assert np.array_equal(_np(losses)[0], l) and np.array_equal(_np(accs)[0], a) and total.item() == pytest.approx(float(l.sum()), rel=1e-6)
+    # the chain rule d/dlog x = x d/dx on the sum of the per-task rows
+    hs = dh.astype(np.float64).sum(axis=0)
+    assert hs[0] != 0 and hs[1] != 0                       # (rel 1e-6: one fp32 rounding of the product, whatever the order of the fp64 sum)
+    assert head.log_lam.grad.item() == pytest.approx(hs[0] * lam, rel=1e-6) and head.log_scale.grad.item() == pytest.approx(hs[1] * alpha, rel=1e-6)
+    # only the sum carries the gradient
+    _, losses, _ = cf.meta_batch_adapt_ridge(features, head, data, labels, shots, ways)
+    with pytest.raises(RuntimeError):
+        losses.mean().backward()
+    # no_grad: scores only
+    with torch.no_grad():
+        total, losses2, accs2 = cf.meta_batch_adapt_ridge(features, head, data, labels, shots, ways)
+    assert not total.requires_grad and np.array_equal(_np(losses2)[0], l) and np.array_equal(_np(accs2)[0], a)
+    # a fixed head: the trunk alone gets a gradient
+    for p in params:
+        p.grad = None
+    fixed = cf.RidgeHead(lam=1.0, scale=8.0, learnable=False).cuda()
+    cf.meta_batch_adapt_ridge(features, fixed, data, labels, shots, ways)[0].backward()
+    assert np.array_equal(_grads(params), g[:nf])
+    # the one-task form
+    for p in params + list(head.parameters()):
+        p.grad = None
+    loss, acc = cf.fast_adapt_ridge((data[0].cpu(), labels[0].cpu()), features, head, shots, ways, torch.device('cuda'))
+    loss.backward()
+    l1, a1, g1, dh1, _ = _np(*MetaEngine(mspec).meta_batch_ridge(theta, data[:1].contiguous(), labels[:1].contiguous(), shots, lam=lam, scale=alpha))
+    assert loss.item() == l1[0] and acc.item() == a1[0] and np.array_equal(_grads(params), g1[:nf])
+    assert head.log_lam.grad.item() == pytest.approx(float(dh1[0, 0]) * lam, rel=1e-6)
+    assert head.log_scale.grad.item() == pytest.approx(float(dh1[0, 1]) * alpha, rel=1e-6)
+
+
+def test_evaluate_ridge_is_the_mean_of_the_engines_acc():
+    from exploring_meta_amd.vision.maml_vision import SyntheticTasks
+    shape = 'omni'
+    dataset, _, hw, _, ways, shots = RH.SHAPES[shape]
+    mspec, theta, data, labels, _, _, nf = _inputs(shape, (7, 8, 9))
+    features = _trunk(shape)
+    p = dict(meta_batch_size=3, shots=shots, ways=ways)
+    head = cf.RidgeHead(lam=1.0, scale=8.0, learnable=False)
+    got = cf.evaluate_ridge(p, SyntheticTasks(dataset, ways, shots, 7), features, head, torch.device('cuda'))
+    _, acc, grad, dh, _ = _np(*MetaEngine(mspec).meta_batch_ridge(theta, data, labels, shots, lam=head.lam, scale=head.scale, with_grad=False))
+    assert grad is None and dh is None and got == pytest.approx(float(acc.astype(np.float64).mean()), abs=1e-6)
+    with pytest.raises(NotImplementedError, match='OmniglotCNN'):
+        cf.evaluate_ridge(p, SyntheticTasks(dataset, ways, shots, 7), cf.OmniglotCNN(ways).cuda(), head, torch.device('cuda'))
+
+
+def test_ridge_driver_runs_saves_and_reloads(tmp_path):
+    """Two optimisation steps on synthetic Omniglot tasks: nothing in particular gets lower, but the run moves the trunk and the head's
+    two scalars, saves them under the ANIL driver's names and reloads."""
+    from exploring_meta_amd.vision import anil_vision, ridge_vision
+    p = dict(ridge_vision.params)
+    p.update(meta_batch_size=4, num_iterations=2, ways=5, shots=1, lam=1.0, scale=8.0, save_dir=str(tmp_path))
+    logs = []
+    (features, head), metrics = ridge_vision.run('omni', p, log=logs.append)
+    assert len(logs) == 2 and all(math.isfinite(v) for v in metrics.values()) and 'test_acc' in metrics
+    torch.manual_seed(p['seed']); torch.cuda.manual_seed(p['seed'])
+    init, _ = ridge_vision.build('omni', 5, torch.device('cuda'))
+    assert any(not torch.equal(a, b) for a, b in zip(features.parameters(), init.parameters()))
+    assert all(torch.isfinite(q).all() for q in features.parameters())
+    assert head.lam != 1.0 and head.scale != 8.0 and math.isfinite(head.lam) and math.isfinite(head.scale)
+    for name in ('features.pt', 'ridge_head.pt', os.path.join('model_checkpoints', 'model_features_1.pt'),
+                 os.path.join('model_checkpoints', 'model_ridge_head_1.pt')):
+        assert os.path.exists(tmp_path / name), name
+    loaded, _ = anil_vision.build('omni', 5, 0.5, torch.device('cuda'))
+    loaded.load_state_dict(torch.load(tmp_path / 'features.pt'))
+    assert all(torch.equal(a, b) for a, b in zip(loaded.state_dict().values(), features.state_dict().values()))
+    again = cf.RidgeHead()
+    again.load_state_dict(torch.load(tmp_path / 'ridge_head.pt'))
+    assert again.lam == head.lam and again.scale == head.scale
+    # --fix_head: the two scalars stay where they were put
+    p.update(fix_head=True, save_dir='')
+    (_, fixed), _ = ridge_vision.run('omni', p, log=logs.append)
+    assert fixed.lam == pytest.approx(1.0, rel=1e-6) and fixed.scale == pytest.approx(8.0, rel=1e-6) and list(fixed.parameters()) == []
+
+
+def test_anil_driver_ridge_test_only_adds_its_key():
+    from exploring_meta_amd.vision import anil_vision
+    runs = []
+    for ridge in (False, True):
+        p = dict(anil_vision.params)
+        p.update(anil_vision.params_of(anil_vision.parse_args(['--meta_batch_size', '3', '--num_iterations', '2', '--shots', '1'] +
+                                                               (['--ridge_test', '--ridge_scale', '8'] if ridge else []))))
+        logs = []
+        _, metrics = anil_vision.run('omni', p, log=logs.append)
+        runs.append((logs, metrics))
+    (l0, m0), (l1, m1) = runs
+    assert 'ridge_test_acc' not in m0 and len(l0) == 2
+    assert l1[:len(l0)] == l0 and len(l1) == len(l0) + 1 and l1[-1].startswith('ridge_test_acc: ')
+    assert {k: v for k, v in m1.items() if k != 'ridge_test_acc'} == m0 and 0.0 <= m1['ridge_test_acc'] <= 1.0
