@@ -163,16 +163,36 @@ static int ridge_hyper_check(mi_engine* e, const char* who, float lam, float alp
     return fail(e, MI_ERR_ARG, std::string(who) + ": alpha must be positive and finite, got " + std::to_string(alpha));
   return MI_OK;
 }
-#define RIDGE_LDS(e, who, ns, nq, feat, ways)                                      \
-  do {                                                                             \
-    const int _rrc = ridge_lds_check(e, who, ns, nq, feat, ways);                  \
-    if (_rrc) return _rrc;                                                         \
-  } while (0)
-#define METRIC_LDS(e, who, ns, nq, feat, ways)                                     \
-  do {                                                                             \
-    const int _mrc = metric_lds_check(e, who, ns, nq, feat, ways);                 \
-    if (_mrc) return _mrc;                                                         \
-  } while (0)
+static int metric_hyper_check(mi_engine* e, const char* who, int metric, float scale) {
+  if (metric != MI_METRIC_PROTO && metric != MI_METRIC_COSINE)
+    return fail(e, MI_ERR_ARG, std::string(who) + ": unknown metric " + std::to_string(metric) + " (MI_METRIC_PROTO = 0, MI_METRIC_COSINE = 1)");
+  if (!(scale > 0.f)) return fail(e, MI_ERR_ARG, std::string(who) + ": scale must be positive, got " + std::to_string(scale));
+  return MI_OK;
+}
+// What the closed-form heads' argument structs (A: MetricArgs, RidgeArgs) share, from pointers and sizes; each caller adds its head's own fields.
+template <class A>
+static A closed_form_args(const float* fs, const float* fq, const int32_t* ys, const int32_t* yq, int ns, int nq, int feat, int ways,
+                          float* loss, float* acc, float* logits, float* dfs, float* dfq) {
+  A a{};
+  a.fs = fs; a.fq = fq; a.ys = ys; a.yq = yq; a.ns = ns; a.nq = nq; a.feat = feat; a.ways = ways;
+  a.loss = loss; a.acc = acc; a.logits = logits; a.dfs = dfs; a.dfq = dfq;
+  return a;
+}
+// the closed-form head's LDS check (ridge: the ridge head's, else the metric heads'): the kernel entries and check_call end in it
+static int closed_form_lds_check(mi_engine* e, const char* who, bool ridge, int ns, int nq, int feat, int ways) {
+  return ridge ? ridge_lds_check(e, who, ns, nq, feat, ways) : metric_lds_check(e, who, ns, nq, feat, ways);
+}
+// What the closed-form heads' kernel entries refuse, in their order: null pointers, tasks, the head's own hyper-parameters (`hyper` returns
+// its check's code), alignment, LDS.
+template <class A, class Hyper>
+static int closed_form_entry_check(const char* who, bool ridge, const A& a, int tasks, Hyper hyper) {
+  if (!a.fs || !a.fq || !a.ys || !a.yq || !a.loss || !a.acc) return fail(nullptr, MI_ERR_ARG, std::string(who) + ": null pointer argument");
+  if (tasks < 1) return fail(nullptr, MI_ERR_ARG, std::string(who) + ": tasks must be >= 1, got " + std::to_string(tasks));
+  if (const int hrc = hyper()) return hrc;
+  if (((reinterpret_cast<uintptr_t>(a.fs) | reinterpret_cast<uintptr_t>(a.fq) | reinterpret_cast<uintptr_t>(a.dfs) | reinterpret_cast<uintptr_t>(a.dfq)) & 15) != 0)
+    return fail(nullptr, MI_ERR_ARG, std::string(who) + ": fs, fq, dfs and dfq must be 16-byte aligned");
+  return closed_form_lds_check(nullptr, who, ridge, a.ns, a.nq, a.feat, a.ways);
+}
 #define HEAD_LDS(e, who, n, ways, tangent)                                         \
   do {                                                                             \
     const int _hrc = head_lds_check(e, who, n, ways, tangent);                     \
@@ -1243,6 +1263,7 @@ enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS 
 // ALGO_RIDGE (mi_meta_batch_ridge): ALGO_METRIC's launches with the ridge-regression head (lam, alpha) in the metric head's place;
 // dhyper_out [tasks][2] or null.
 static bool is_anil(MetaAlgo a) { return a == ALGO_ANIL || a == ALGO_ANIL_LR || a == ALGO_ANIL_STEPS; }
+static bool is_closed_form(MetaAlgo a) { return a == ALGO_METRIC || a == ALGO_RIDGE; }
 struct MetaCall {
   MetaAlgo algo;
   const float* theta; const float* data; const int64_t* labels;
@@ -1309,25 +1330,20 @@ static int check_call(mi_engine* e, const MetaCall& c) {
       if (c.adapt_steps > 0 && c.grad_tasks > 0 && c.second_order) HEAD_LDS(e, who, n, c.ways, 1);
     }
   }
-  if (c.algo == ALGO_METRIC) {
-    if (c.metric != MI_METRIC_PROTO && c.metric != MI_METRIC_COSINE)
-      return fail(e, MI_ERR_ARG, "mi_meta_batch_metric: unknown metric " + std::to_string(c.metric) + " (MI_METRIC_PROTO = 0, MI_METRIC_COSINE = 1)");
-    if (!(c.scale > 0.f)) return fail(e, MI_ERR_ARG, "mi_meta_batch_metric: scale must be positive, got " + std::to_string(c.scale));
-    if (e->trace) return fail(e, MI_ERR_ARG, "the debug trace does not cover mi_meta_batch_metric");
-  }
-  if (c.algo == ALGO_RIDGE) {
-    const int hrc = ridge_hyper_check(e, "mi_meta_batch_ridge", c.lam, c.alpha);
+  const bool ridge = c.algo == ALGO_RIDGE;
+  const char* cf_who = ridge ? "mi_meta_batch_ridge" : "mi_meta_batch_metric";
+  if (is_closed_form(c.algo)) {
+    const int hrc = ridge ? ridge_hyper_check(e, cf_who, c.lam, c.alpha) : metric_hyper_check(e, cf_who, c.metric, c.scale);
     if (hrc) return hrc;
-    if (e->trace) return fail(e, MI_ERR_ARG, "the debug trace does not cover mi_meta_batch_ridge");
+    if (e->trace) return fail(e, MI_ERR_ARG, std::string("the debug trace does not cover ") + cf_who);
   }
   if (!c.theta || !c.data || !c.labels || !c.loss_out || !c.acc_out || !c.workspace) return fail(e, MI_ERR_ARG, "null pointer argument");
   if (c.grad_tasks > 0 && !c.meta_grad_out) return fail(e, MI_ERR_ARG, "meta_grad_out is NULL but a gradient was asked for");
-  if ((is_anil(c.algo) || c.algo == ALGO_METRIC || c.algo == ALGO_RIDGE) && e->d.head_mean_pool)
+  if ((is_anil(c.algo) || is_closed_form(c.algo)) && e->d.head_mean_pool)
     return fail(e, MI_ERR_ARG, "ANIL features are flattened (view(-1, fc_neurons)), not mean-pooled");
   if (c.tasks < 1 || c.shots < 1 || c.adapt_steps < 0) return fail(e, MI_ERR_ARG, "tasks/shots must be >= 1, adapt_steps >= 0");
   if (c.ways != e->d.ways) return fail(e, MI_ERR_ARG, "ways differs from the engine's classifier width");
-  if (c.algo == ALGO_METRIC) METRIC_LDS(e, "mi_meta_batch_metric", c.ways * c.shots, c.ways * c.shots, e->feat, c.ways);
-  if (c.algo == ALGO_RIDGE) RIDGE_LDS(e, "mi_meta_batch_ridge", c.ways * c.shots, c.ways * c.shots, e->feat, c.ways);
+  if (is_closed_form(c.algo)) return closed_form_lds_check(e, cf_who, ridge, c.ways * c.shots, c.ways * c.shots, e->feat, c.ways);   // (after ways and shots)
   return MI_OK;
 }
 
@@ -1739,15 +1755,15 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const MetaCall& c) {
   return MI_OK;
 }
 
-// mi_meta_batch_metric: the launches of meta_batch_anil_impl up to the split of the features, ONE metric-head launch (no head parameters, no
-// inner loop, no tangent pass), then -- with a gradient -- the interleave, the trunk backward and the sum over tasks (without one the call ends
+// mi_meta_batch_metric / mi_meta_batch_ridge, the closed-form call: the launches of meta_batch_anil_impl up to the split of the features, ONE
+// head launch chosen by `algo` (no head parameters, no inner loop, no tangent pass), then -- with a gradient -- the interleave, the trunk backward and the sum over tasks (without one the call ends
 // at the head).  lam's head entries stay
 // the zeros of the memset, so meta_grad_out's head entries are exact zeros.  The plan is the ANIL call's with K = 0.
 extern "C" int mi_metric_workspace_bytes(const mi_engine* e, int tasks, int ways, int shots, int with_grad, size_t* bytes) {
   (void)with_grad;                       // (one plan for both: the evaluation call leaves the backward's arrays unused)
   return mi_anil_workspace_bytes(e, tasks, ways, shots, 0, bytes);
 }
-static int meta_batch_metric_impl(mi_engine* e, void* stream, const MetaCall& c) {
+static int meta_batch_closed_form_impl(mi_engine* e, void* stream, const MetaCall& c) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = c.tasks, n = c.ways * c.shots, nl = (int)e->L.size(), with_grad = c.grad_tasks > 0;
   AnilPlan ap;
@@ -1770,19 +1786,15 @@ static int meta_batch_metric_impl(mi_engine* e, void* stream, const MetaCall& c)
   rc = export_bn_stats(e, st, ap.act, T);
   if (rc) return rc;
   LAUNCH(e, st, OP_MISC, 4, launch_split_rows(st, ap.act.p[nl - 1], T, 2 * n, e->feat, ap.fs, ap.fq));
-  if (c.algo == ALGO_RIDGE) {              // mi_meta_batch_ridge: the ridge head in the metric head's place, nothing else differs
-    RidgeArgs ra{};
-    ra.fs = ap.fs; ra.fq = ap.fq; ra.ys = ap.ys; ra.yq = ap.yq;
-    ra.ns = n; ra.nq = n; ra.feat = e->feat; ra.ways = c.ways; ra.lam = c.lam; ra.alpha = c.alpha;
-    ra.loss = c.loss_out; ra.acc = c.acc_out; ra.logits = c.logits_out;
-    ra.dfs = with_grad ? ap.dfs : nullptr; ra.dfq = with_grad ? ap.dfq : nullptr; ra.dhyper = with_grad ? c.dhyper_out : nullptr;
+  float *dfs = with_grad ? ap.dfs : nullptr, *dfq = with_grad ? ap.dfq : nullptr;
+  if (c.algo == ALGO_RIDGE) {              // the head launch is all that `algo` chooses
+    RidgeArgs ra = closed_form_args<RidgeArgs>(ap.fs, ap.fq, ap.ys, ap.yq, n, n, e->feat, c.ways, c.loss_out, c.acc_out, c.logits_out, dfs, dfq);
+    ra.h = {c.lam, c.alpha};
+    ra.dhyper = with_grad ? c.dhyper_out : nullptr;
     LAUNCH(e, st, OP_RIDGE_HEAD, 0, launch_ridge_head(st, ra, T));
   } else {
-    MetricArgs ma{};
-    ma.fs = ap.fs; ma.fq = ap.fq; ma.ys = ap.ys; ma.yq = ap.yq;
-    ma.ns = n; ma.nq = n; ma.feat = e->feat; ma.ways = c.ways; ma.metric = c.metric; ma.scale = c.scale;
-    ma.loss = c.loss_out; ma.acc = c.acc_out; ma.logits = c.logits_out;
-    ma.dfs = with_grad ? ap.dfs : nullptr; ma.dfq = with_grad ? ap.dfq : nullptr;
+    MetricArgs ma = closed_form_args<MetricArgs>(ap.fs, ap.fq, ap.ys, ap.yq, n, n, e->feat, c.ways, c.loss_out, c.acc_out, c.logits_out, dfs, dfq);
+    ma.h = {c.metric, c.scale};
     LAUNCH(e, st, OP_METRIC_HEAD, 0, launch_metric_head(st, ma, T));
   }
   if (!with_grad) return MI_OK;
@@ -1817,7 +1829,7 @@ static GraphKey graph_key(const mi_engine* e, void* stream, const MetaCall& c) {
 static int meta_batch_entry(mi_engine* e, void* stream, const MetaCall& c) {
   const int crc = check_call(e, c);
   if (crc) return crc;
-  const auto fn = (c.algo == ALGO_METRIC || c.algo == ALGO_RIDGE) ? meta_batch_metric_impl : is_anil(c.algo) ? meta_batch_anil_impl : meta_batch_maml_impl;
+  const auto fn = is_closed_form(c.algo) ? meta_batch_closed_form_impl : is_anil(c.algo) ? meta_batch_anil_impl : meta_batch_maml_impl;
   if (!e->graph_on || e->prof_on || e->trace || e->bn_export || !stream)     // (capture is not permitted on the legacy default stream)
     return fn(e, stream, c);
   const GraphKey key = graph_key(e, stream, c);
@@ -2324,39 +2336,27 @@ extern "C" int mi_metric_head(void* stream, const float* fs, const float* fq, co
                               int feat, int ways, int metric, float scale, float* loss, float* acc, float* logits, float* dfs, float* dfq,
                               void* scratch, size_t scratch_bytes) {
   (void)scratch; (void)scratch_bytes;
-  if (!fs || !fq || !ys || !yq || !loss || !acc) return fail(nullptr, MI_ERR_ARG, "mi_metric_head: null pointer argument");
-  if (tasks < 1) return fail(nullptr, MI_ERR_ARG, "mi_metric_head: tasks must be >= 1, got " + std::to_string(tasks));
-  if (metric != MI_METRIC_PROTO && metric != MI_METRIC_COSINE)
-    return fail(nullptr, MI_ERR_ARG, "mi_metric_head: unknown metric " + std::to_string(metric) + " (MI_METRIC_PROTO = 0, MI_METRIC_COSINE = 1)");
-  if (!(scale > 0.f)) return fail(nullptr, MI_ERR_ARG, "mi_metric_head: scale must be positive, got " + std::to_string(scale));
-  if (((reinterpret_cast<uintptr_t>(fs) | reinterpret_cast<uintptr_t>(fq) | reinterpret_cast<uintptr_t>(dfs) | reinterpret_cast<uintptr_t>(dfq)) & 15) != 0)
-    return fail(nullptr, MI_ERR_ARG, "mi_metric_head: fs, fq, dfs and dfq must be 16-byte aligned");
-  METRIC_LDS(nullptr, "mi_metric_head", ns, nq, feat, ways);
-  MetricArgs ma{};
-  ma.fs = fs; ma.fq = fq; ma.ys = ys; ma.yq = yq; ma.ns = ns; ma.nq = nq; ma.feat = feat; ma.ways = ways; ma.metric = metric; ma.scale = scale;
-  ma.loss = loss; ma.acc = acc; ma.logits = logits; ma.dfs = dfs; ma.dfq = dfq;
+  MetricArgs ma = closed_form_args<MetricArgs>(fs, fq, ys, yq, ns, nq, feat, ways, loss, acc, logits, dfs, dfq);
+  ma.h = {metric, scale};
+  if (const int rc = closed_form_entry_check("mi_metric_head", false, ma, tasks, [&] { return metric_hyper_check(nullptr, "mi_metric_head", metric, scale); }))
+    return rc;
   HIPCHK0(launch_metric_head(reinterpret_cast<hipStream_t>(stream), ma, tasks));
   return MI_OK;
 }
 
-// launch_ridge_head: the ridge head's kernel entry (include/mi_maml.h).  Everything is folded inside the one launch: no scratch.
+// launch_ridge_head: the ridge head's kernel entry (include/mi_maml.h), likewise.
 extern "C" size_t mi_ridge_head_scratch_bytes(int tasks, int ns, int nq, int feat, int ways) {
-  (void)tasks; (void)ns; (void)nq; (void)feat; (void)ways;
-  return 0;
+  return mi_metric_head_scratch_bytes(tasks, ns, nq, feat, ways);
 }
 extern "C" int mi_ridge_head(void* stream, const float* fs, const float* fq, const int32_t* ys, const int32_t* yq, int tasks, int ns, int nq,
                              int feat, int ways, float lam, float alpha, float* loss, float* acc, float* logits, float* dfs, float* dfq,
                              float* dhyper, void* scratch, size_t scratch_bytes) {
   (void)scratch; (void)scratch_bytes;
-  if (!fs || !fq || !ys || !yq || !loss || !acc) return fail(nullptr, MI_ERR_ARG, "mi_ridge_head: null pointer argument");
-  if (tasks < 1) return fail(nullptr, MI_ERR_ARG, "mi_ridge_head: tasks must be >= 1, got " + std::to_string(tasks));
-  if (const int hrc = ridge_hyper_check(nullptr, "mi_ridge_head", lam, alpha)) return hrc;
-  if (((reinterpret_cast<uintptr_t>(fs) | reinterpret_cast<uintptr_t>(fq) | reinterpret_cast<uintptr_t>(dfs) | reinterpret_cast<uintptr_t>(dfq)) & 15) != 0)
-    return fail(nullptr, MI_ERR_ARG, "mi_ridge_head: fs, fq, dfs and dfq must be 16-byte aligned");
-  RIDGE_LDS(nullptr, "mi_ridge_head", ns, nq, feat, ways);
-  RidgeArgs ra{};
-  ra.fs = fs; ra.fq = fq; ra.ys = ys; ra.yq = yq; ra.ns = ns; ra.nq = nq; ra.feat = feat; ra.ways = ways; ra.lam = lam; ra.alpha = alpha;
-  ra.loss = loss; ra.acc = acc; ra.logits = logits; ra.dfs = dfs; ra.dfq = dfq; ra.dhyper = dhyper;
+  RidgeArgs ra = closed_form_args<RidgeArgs>(fs, fq, ys, yq, ns, nq, feat, ways, loss, acc, logits, dfs, dfq);
+  ra.h = {lam, alpha};
+  ra.dhyper = dhyper;
+  if (const int rc = closed_form_entry_check("mi_ridge_head", true, ra, tasks, [&] { return ridge_hyper_check(nullptr, "mi_ridge_head", lam, alpha); }))
+    return rc;
   HIPCHK0(launch_ridge_head(reinterpret_cast<hipStream_t>(stream), ra, tasks));
   return MI_OK;
 }

@@ -929,21 +929,11 @@ int sparse_wgrad_blocks_per_task(int n, int h, int w, int co, int tasks) {
   sparse_wgrad_grid(n, h, w, co, tasks, ntiles, tpw, grid, true);
   return fp32_blocks > 2 * (int)grid.x ? fp32_blocks : 2 * (int)grid.x;
 }
-static hipError_t sparse_dynamic_lds(const void* k, size_t lds, unsigned* done_mask) {     // (conv_mfma.hip's ensure_dynamic_lds: once per kernel and device)
-  if (lds <= 64 * 1024) return hipSuccess;
-  int dev = 0;
-  if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-  const unsigned bit = 1u << (dev & 31);
-  if (*done_mask & bit) return hipSuccess;
-  if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
-  *done_mask |= bit;
-  return hipSuccess;
-}
 template <bool TAN, int CO>
 static hipError_t launch_sparse_rows_bf(hipStream_t st, dim3 grid, size_t smem, const SparseWgArgs& a) {
   auto k = sparse_wgrad_rows_kernel<3, TAN, CO, 3, 7, true>;
-  static unsigned attr_done = 0;
-  if (hipError_t e = sparse_dynamic_lds(reinterpret_cast<const void*>(k), smem, &attr_done); e != hipSuccess) return e;
+  static unsigned attr_done = 0;             // one bit per device (allow_dynamic_lds, mi_common.h)
+  if (smem > 64 * 1024) if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(k), smem, &attr_done); e != hipSuccess) return e;
   hipLaunchKernelGGL(k, grid, dim3(256), smem, st, a);
   return hipGetLastError();
 }

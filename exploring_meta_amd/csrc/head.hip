@@ -69,21 +69,16 @@ size_t head_grads_lds_bytes(int n, int ways, int tangent) { return ((size_t)(tan
 size_t head_lds_limit_bytes() { return (size_t)160 * 1024; }
 bool head_lds_fits(int n, int ways, int tangent) { return n >= 1 && ways >= 1 && head_grads_lds_bytes(n, ways, tangent) <= head_lds_limit_bytes(); }
 
-// A request above 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize, once per (kernel, device): raised to the device's whole LDS, so that
-// a later, larger request of the same process is covered too.  A request above the device's LDS is refused before anything is launched.
+// A request above 64 KiB needs allow_dynamic_lds (mi_common.h): raised to the device's whole LDS, so that a later, larger request of the same
+// process is covered too.  A request above the device's LDS is refused before anything is launched.
 template <bool TANGENT>
 static hipError_t head_grads_launch(hipStream_t st, const HeadArgs& a, int tasks) {
   const size_t sm = head_grads_lds_bytes(a.n, a.ways, TANGENT ? 1 : 0);
   if (sm > head_lds_limit_bytes()) return hipErrorInvalidValue;
   if (sm > 64 * 1024) {
     static unsigned attr_done = 0;             // one bit per device: the attribute belongs to the device's copy of the kernel
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (!(attr_done & (1u << (dev & 31)))) {
-      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(head_grads_kernel<TANGENT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)head_lds_limit_bytes()); e != hipSuccess) return e;
-      attr_done |= 1u << (dev & 31);
-    }
+    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(head_grads_kernel<TANGENT>), head_lds_limit_bytes(), &attr_done); e != hipSuccess)
+      return e;
   }
   hipLaunchKernelGGL(head_grads_kernel<TANGENT>, dim3(tasks, ceil_div(a.feat, 64)), dim3(256), sm, st, a);
   return hipGetLastError();

@@ -259,31 +259,36 @@ hipError_t launch_head_grads(hipStream_t st, const HeadArgs& a, int tasks);   //
 hipError_t launch_spatial_mean(hipStream_t st, const float* p, float* f, int rows, int hw, int c);
 hipError_t launch_spatial_mean_bwd(hipStream_t st, const float* df, float* dp, int rows, int hw, int c);
 
-// metric_head.hip: the closed-form heads of Prototypical Networks and NIL on the features of a whole meta-batch, one launch
-struct MetricArgs {
+// What every closed-form head on the features of a whole meta-batch takes and gives (metric_head.hip, ridge_head.hip).  H: the head's own
+// hyper-parameters, kept between the sizes and the outputs.
+template <class H>
+struct ClosedFormArgs {
   const float* fs; const float* fq;      // [T][ns][F], [T][nq][F], 16-byte aligned
-  const int32_t* ys; const int32_t* yq;  // [T][ns], [T][nq] in [0, ways); every class has a support row
-  int ns, nq, feat, ways, metric;        // metric: MI_METRIC_PROTO / MI_METRIC_COSINE
-  float scale;                           // > 0
+  const int32_t* ys; const int32_t* yq;  // [T][ns], [T][nq] in [0, ways) (the metric heads: every class has a support row)
+  int ns, nq, feat, ways;
+  H h;
   float* loss; float* acc;               // [T]
   float* logits;                         // [T][nq][ways] (may be null)
-  float* dfs; float* dfq;                // [T][ns][F], [T][nq][F], 16-byte aligned (may be null; both null: forward only)
+  float* dfs; float* dfq;                // [T][ns][F], [T][nq][F], 16-byte aligned (may be null; every gradient output null: forward only)
 };
+
+// metric_head.hip: the closed-form heads of Prototypical Networks and NIL, one launch
+struct MetricHyper {
+  int metric;                            // MI_METRIC_PROTO / MI_METRIC_COSINE
+  float scale;                           // > 0
+};
+struct MetricArgs : ClosedFormArgs<MetricHyper> {};
 // Dynamic LDS of one task (the class vectors and the dz table) against the CU's LDS; the launcher refuses what does not fit with
 // hipErrorInvalidValue before launching anything -- callers check metric_head_fits first and report MI_ERR_ARG.
 size_t metric_head_lds_bytes(int ns, int nq, int feat, int ways);
 bool metric_head_fits(int ns, int nq, int feat, int ways);
 hipError_t launch_metric_head(hipStream_t st, const MetricArgs& a, int tasks);
 
-// ridge_head.hip: the ridge-regression head (R2-D2) on the features of a whole meta-batch, solved and differentiated in one launch
-struct RidgeArgs {
-  const float* fs; const float* fq;      // [T][ns][F], [T][nq][F], 16-byte aligned
-  const int32_t* ys; const int32_t* yq;  // [T][ns], [T][nq] in [0, ways)
-  int ns, nq, feat, ways;
+// ridge_head.hip: the ridge-regression head (R2-D2), solved and differentiated in one launch
+struct RidgeHyper {
   float lam, alpha;                      // > 0 and finite
-  float* loss; float* acc;               // [T]
-  float* logits;                         // [T][nq][ways] (may be null)
-  float* dfs; float* dfq;                // [T][ns][F], [T][nq][F], 16-byte aligned (may be null)
+};
+struct RidgeArgs : ClosedFormArgs<RidgeHyper> {
   float* dhyper;                         // [T][2]: (dlam, dalpha) per task (may be null; dfs, dfq and dhyper all null: forward only)
 };
 // Dynamic LDS of one task (everything ns-sized, fp64; feat does not enter) against the CU's LDS; the launcher refuses what does not fit with

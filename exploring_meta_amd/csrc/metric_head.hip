@@ -27,25 +27,6 @@ namespace {
 constexpr int kThreads = 512, kWaves = kThreads / 64;
 constexpr float kEps = 1e-8f;
 
-template <int VW>
-__device__ __forceinline__ void ld(const float* p, float (&x)[VW]) {
-  if constexpr (VW == 4) {
-    const floatx4 v = *reinterpret_cast<const floatx4*>(p);
-    x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
-  } else {
-    x[0] = *p;
-  }
-}
-template <int VW>
-__device__ __forceinline__ void st(float* p, const float (&x)[VW]) {
-  if constexpr (VW == 4) {
-    const floatx4 v = {x[0], x[1], x[2], x[3]};
-    *reinterpret_cast<floatx4*>(p) = v;
-  } else {
-    *p = x[0];
-  }
-}
-
 // max(|x|, 1e-8) of a row, NEGATED when the clamp is active (the backward then has no projection term).  Rows are DIVIDED by it, as the
 // definition says: a one-feature row is then exactly +-1 and its gradient exactly 0.
 __device__ __forceinline__ float signed_norm(float ss) {
@@ -73,8 +54,8 @@ template <bool BWD, int VW>
 __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
   const int task = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int NS = a.ns, NQ = a.nq, F = a.feat, WY = a.ways;
-  const bool cosine = a.metric == MI_METRIC_COSINE;
-  const float scale = a.scale;
+  const bool cosine = a.h.metric == MI_METRIC_COSINE;
+  const float scale = a.h.scale;
   const float* fs = a.fs + (size_t)task * NS * F;
   const float* fq = a.fq + (size_t)task * NQ * F;
   const int32_t* ys = a.ys + (size_t)task * NS;
@@ -92,7 +73,7 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
       float ss = 0.f;
       for (int i = lane * VW; i < F; i += 64 * VW) {
         float x[VW];
-        ld<VW>(fs + (size_t)s * F + i, x);
+        row_ld<VW>(fs + (size_t)s * F + i, x);
 #pragma unroll
         for (int u = 0; u < VW; ++u) ss = fmaf(x[u], x[u], ss);
       }
@@ -107,26 +88,26 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
     float z[VW];
 #pragma unroll
     for (int u = 0; u < VW; ++u) z[u] = 0.f;
-    for (int w = 0; w < WY; ++w) st<VW>(l.c + (size_t)w * F + i, z);
+    for (int w = 0; w < WY; ++w) row_st<VW>(l.c + (size_t)w * F + i, z);
     for (int s = 0; s < NS; ++s) {
       const int w = ys[s];
       if ((unsigned)w >= (unsigned)WY) continue;
       float x[VW], cur[VW];
-      ld<VW>(fs + (size_t)s * F + i, x);
-      ld<VW>(l.c + (size_t)w * F + i, cur);
+      row_ld<VW>(fs + (size_t)s * F + i, x);
+      row_ld<VW>(l.c + (size_t)w * F + i, cur);
       const float r = cosine ? fabsf(l.rns[s]) : 1.f;
 #pragma unroll
       for (int u = 0; u < VW; ++u) cur[u] += cosine ? x[u] / r : x[u];
-      st<VW>(l.c + (size_t)w * F + i, cur);
+      row_st<VW>(l.c + (size_t)w * F + i, cur);
     }
     if (!cosine) {
       for (int w = 0; w < WY; ++w) {
         float cur[VW];
-        ld<VW>(l.c + (size_t)w * F + i, cur);
+        row_ld<VW>(l.c + (size_t)w * F + i, cur);
         const float nw = l.cnt[w];
 #pragma unroll
         for (int u = 0; u < VW; ++u) cur[u] = cur[u] / nw;
-        st<VW>(l.c + (size_t)w * F + i, cur);
+        row_st<VW>(l.c + (size_t)w * F + i, cur);
       }
     }
   }
@@ -144,7 +125,7 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
       float ssp = 0.f;
       for (int i = lane * VW; i < F; i += 64 * VW) {
         float x[VW];
-        ld<VW>(xq + i, x);
+        row_ld<VW>(xq + i, x);
         if (cosine && c0 == 0) {
 #pragma unroll
           for (int u = 0; u < VW; ++u) ssp = fmaf(x[u], x[u], ssp);
@@ -153,7 +134,7 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
         for (int w = 0; w < 8; ++w) {
           if (c0 + w < WY) {
             float cv[VW];
-            ld<VW>(l.c + (size_t)(c0 + w) * F + i, cv);
+            row_ld<VW>(l.c + (size_t)(c0 + w) * F + i, cv);
 #pragma unroll
             for (int u = 0; u < VW; ++u) {
               if (cosine) {
@@ -199,14 +180,14 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
         for (int w = 0; w < 8; ++w) g[w] = __shfl(dl, (c0 + w) & 63, 64);
         for (int i = lane * VW; i < F; i += 64 * VW) {
           float x[VW], av[VW];
-          ld<VW>(xq + i, x);
+          row_ld<VW>(xq + i, x);
 #pragma unroll
           for (int u = 0; u < VW; ++u) av[u] = 0.f;
 #pragma unroll
           for (int w = 0; w < 8; ++w) {
             if (c0 + w < WY) {
               float cv[VW];
-              ld<VW>(l.c + (size_t)(c0 + w) * F + i, cv);
+              row_ld<VW>(l.c + (size_t)(c0 + w) * F + i, cv);
 #pragma unroll
               for (int u = 0; u < VW; ++u) av[u] = fmaf(g[w], cv[u], av[u]);
             }
@@ -248,11 +229,11 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
       for (int w = 0; w < 8; ++w) {
 #pragma unroll
         for (int u = 0; u < VW; ++u) { cv[w][u] = 0.f; dc[w][u] = 0.f; }
-        if (c0 + w < WY) ld<VW>(l.c + (size_t)(c0 + w) * F + i, cv[w]);
+        if (c0 + w < WY) row_ld<VW>(l.c + (size_t)(c0 + w) * F + i, cv[w]);
       }
       for (int q = 0; q < NQ; ++q) {
         float x[VW], av[VW];
-        ld<VW>(fq + (size_t)q * F + i, x);
+        row_ld<VW>(fq + (size_t)q * F + i, x);
         const float rq = l.rnq[q], ra = fabsf(rq);
         if (cosine) {
 #pragma unroll
@@ -284,11 +265,11 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
           for (int u = 0; u < VW; ++u) o[u] = cosine ? (scale * av[u] - proj * x[u]) / ra : -two_s * av[u];
           if (c0 > 0) {                  // more than 8 classes: this thread's own element again, chunks ascending
             float prev[VW];
-            ld<VW>(dfq + (size_t)q * F + i, prev);
+            row_ld<VW>(dfq + (size_t)q * F + i, prev);
 #pragma unroll
             for (int u = 0; u < VW; ++u) o[u] = prev[u] + o[u];
           }
-          st<VW>(dfq + (size_t)q * F + i, o);
+          row_st<VW>(dfq + (size_t)q * F + i, o);
         }
       }
 #pragma unroll
@@ -296,7 +277,7 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
         if (c0 + w < WY) {
 #pragma unroll
           for (int u = 0; u < VW; ++u) dc[w][u] = (cosine ? scale : two_s) * dc[w][u];
-          st<VW>(l.c + (size_t)(c0 + w) * F + i, dc[w]);
+          row_st<VW>(l.c + (size_t)(c0 + w) * F + i, dc[w]);
         }
       }
     }
@@ -316,8 +297,8 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
     if (cosine && rs > 0.f) {
       for (int i = lane * VW; i < F; i += 64 * VW) {
         float x[VW], d[VW];
-        ld<VW>(xs + i, x);
-        ld<VW>(dcw + i, d);
+        row_ld<VW>(xs + i, x);
+        row_ld<VW>(dcw + i, d);
 #pragma unroll
         for (int u = 0; u < VW; ++u) dot = fmaf(d[u], x[u] / ra, dot);
       }
@@ -326,10 +307,10 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
     const float nw = ok ? l.cnt[w] : 1.f;
     for (int i = lane * VW; i < F; i += 64 * VW) {
       float d[VW], o[VW];
-      ld<VW>(dcw + i, d);
+      row_ld<VW>(dcw + i, d);
       if (cosine) {
         float x[VW];
-        ld<VW>(xs + i, x);
+        row_ld<VW>(xs + i, x);
 #pragma unroll
         for (int u = 0; u < VW; ++u) o[u] = (d[u] - dot * (x[u] / ra)) / ra;
       } else {
@@ -340,7 +321,7 @@ __device__ __forceinline__ void metric_task(const MetricArgs& a, float* sm) {
 #pragma unroll
         for (int u = 0; u < VW; ++u) o[u] = 0.f;
       }
-      st<VW>(dfs + (size_t)s * F + i, o);
+      row_st<VW>(dfs + (size_t)s * F + i, o);
     }
   }
 }
@@ -365,20 +346,15 @@ bool metric_head_fits(int ns, int nq, int feat, int ways) {
   return ns >= 1 && nq >= 1 && feat >= 1 && ways >= 1 && ways <= 64 && metric_head_lds_bytes(ns, nq, feat, ways) <= head_lds_limit_bytes();
 }
 
-// A request above 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize, once per (kernel, device): raised to the device's whole LDS (not to
-// this launch's size), so that a later, larger request of the same process is covered too.
+// A request above 64 KiB needs allow_dynamic_lds (mi_common.h): raised to the device's whole LDS (not to this launch's size), so that a later,
+// larger request of the same process is covered too.
 template <bool BWD>
 static hipError_t metric_launch(hipStream_t st, const MetricArgs& a, int tasks) {
   const size_t sm = metric_head_lds_bytes(a.ns, a.nq, a.feat, a.ways);
   if (sm > 64 * 1024) {
     static unsigned attr_done = 0;             // one bit per device: the attribute belongs to the device's copy of the kernel
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (!(attr_done & (1u << (dev & 31)))) {
-      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(metric_head_kernel<BWD>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)head_lds_limit_bytes()); e != hipSuccess) return e;
-      attr_done |= 1u << (dev & 31);
-    }
+    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(metric_head_kernel<BWD>), head_lds_limit_bytes(), &attr_done); e != hipSuccess)
+      return e;
   }
   hipLaunchKernelGGL(metric_head_kernel<BWD>, dim3(tasks), dim3(kThreads), sm, st, a);
   return hipGetLastError();
@@ -387,7 +363,7 @@ static hipError_t metric_launch(hipStream_t st, const MetricArgs& a, int tasks) 
 // Forward (a.dfs == a.dfq == NULL) or forward + backward, one launch either way.  Outside the domain: hipErrorInvalidValue, nothing launched
 // (callers check metric_head_fits first and report MI_ERR_ARG).
 hipError_t launch_metric_head(hipStream_t st, const MetricArgs& a, int tasks) {
-  if (tasks < 1 || !metric_head_fits(a.ns, a.nq, a.feat, a.ways) || (a.metric != MI_METRIC_PROTO && a.metric != MI_METRIC_COSINE) || !(a.scale > 0.f))
+  if (tasks < 1 || !metric_head_fits(a.ns, a.nq, a.feat, a.ways) || (a.h.metric != MI_METRIC_PROTO && a.h.metric != MI_METRIC_COSINE) || !(a.h.scale > 0.f))
     return hipErrorInvalidValue;
   return (a.dfs || a.dfq) ? metric_launch<true>(st, a, tasks) : metric_launch<false>(st, a, tasks);
 }

@@ -151,5 +151,39 @@ __device__ __forceinline__ unsigned mi_cell_fold(unsigned m) {
   return (unsigned)__builtin_amdgcn_readfirstlane((int)m);
 }
 
+// VW adjacent floats of a row: one 16-byte access (VW == 4; p 16-byte aligned) or one word (VW == 1).  Global memory and LDS alike.
+template <int VW>
+__device__ __forceinline__ void row_ld(const float* p, float (&x)[VW]) {
+  if constexpr (VW == 4) {
+    const floatx4 v = *reinterpret_cast<const floatx4*>(p);
+    x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
+  } else {
+    x[0] = *p;
+  }
+}
+template <int VW>
+__device__ __forceinline__ void row_st(float* p, const float (&x)[VW]) {
+  if constexpr (VW == 4) {
+    const floatx4 v = {x[0], x[1], x[2], x[3]};
+    *reinterpret_cast<floatx4*>(p) = v;
+  } else {
+    *p = x[0];
+  }
+}
+
+// A launch with more than 64 KiB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize on its kernel, once per (kernel, device):
+// a process that drives a second GPU launches that device's copy of the kernel, which needs the attribute too.  `done_mask` is the caller's
+// static word for kernel `k`, one bit per device.  The caller keeps its own threshold and chooses `allow`: this launch's (constant) request,
+// or a cap above every request when later launches of the same kernel may ask for more -- the attribute is set once.
+static inline hipError_t allow_dynamic_lds(const void* k, size_t allow, unsigned* done_mask) {
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+  const unsigned bit = 1u << (dev & 31);
+  if (*done_mask & bit) return hipSuccess;
+  if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)allow); e != hipSuccess) return e;
+  *done_mask |= bit;
+  return hipSuccess;
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -31,25 +31,6 @@
 namespace {
 constexpr int kThreads = 512, kWaves = kThreads / 64, kRows = 8;
 
-template <int VW>
-__device__ __forceinline__ void ld(const float* p, float (&x)[VW]) {
-  if constexpr (VW == 4) {
-    const floatx4 v = *reinterpret_cast<const floatx4*>(p);
-    x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
-  } else {
-    x[0] = *p;
-  }
-}
-template <int VW>
-__device__ __forceinline__ void st(float* p, const float (&x)[VW]) {
-  if constexpr (VW == 4) {
-    const floatx4 v = {x[0], x[1], x[2], x[3]};
-    *reinterpret_cast<floatx4*>(p) = v;
-  } else {
-    *p = x[0];
-  }
-}
-
 __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }      // j <= i
 
 struct Lds {
@@ -99,7 +80,7 @@ template <bool BWD, int VW>
 __device__ __forceinline__ void ridge_task(const RidgeArgs& a, double* sm) {
   const int task = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int NS = a.ns, NQ = a.nq, F = a.feat, WY = a.ways;
-  const double lam = (double)a.lam, alpha = (double)a.alpha;
+  const double lam = (double)a.h.lam, alpha = (double)a.h.alpha;
   const float* fs = a.fs + (size_t)task * NS * F;
   const float* fq = a.fq + (size_t)task * NQ * F;
   const int32_t* ys = a.ys + (size_t)task * NS;
@@ -137,7 +118,7 @@ __device__ __forceinline__ void ridge_task(const RidgeArgs& a, double* sm) {
       for (int i = lane * VW; i < F; i += 64 * VW) {
         float x[4][VW], y[4][VW];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { ld<VW>(xr[r] + i, x[r]); ld<VW>(yr[r] + i, y[r]); }
+        for (int r = 0; r < 4; ++r) { row_ld<VW>(xr[r] + i, x[r]); row_ld<VW>(yr[r] + i, y[r]); }
 #pragma unroll
         for (int u = 0; u < VW; ++u)
 #pragma unroll
@@ -299,7 +280,7 @@ __device__ __forceinline__ void ridge_task(const RidgeArgs& a, double* sm) {
 #pragma unroll 4
       for (int j = 0; j < NS; ++j) {
         float x[VW];
-        ld<VW>(fs + (size_t)j * F + col, x);
+        row_ld<VW>(fs + (size_t)j * F + col, x);
 #pragma unroll
         for (int r = 0; r < kRows; ++r) {
           const double c = l.k[min(r0 + r, NQ - 1) * NS + j];
@@ -311,7 +292,7 @@ __device__ __forceinline__ void ridge_task(const RidgeArgs& a, double* sm) {
 #pragma unroll 4
       for (int q = 0; q < NQ; ++q) {
         float x[VW];
-        ld<VW>(fq + (size_t)q * F + col, x);
+        row_ld<VW>(fq + (size_t)q * F + col, x);
 #pragma unroll
         for (int r = 0; r < kRows; ++r) {
           const double c = l.k[q * NS + min(r0 + r, NS - 1)];
@@ -322,7 +303,7 @@ __device__ __forceinline__ void ridge_task(const RidgeArgs& a, double* sm) {
 #pragma unroll 4
       for (int j = 0; j < NS; ++j) {
         float x[VW];
-        ld<VW>(fs + (size_t)j * F + col, x);
+        row_ld<VW>(fs + (size_t)j * F + col, x);
 #pragma unroll
         for (int r = 0; r < kRows; ++r) {
           const int i = min(r0 + r, NS - 1);
@@ -340,7 +321,7 @@ __device__ __forceinline__ void ridge_task(const RidgeArgs& a, double* sm) {
         float o[VW];
 #pragma unroll
         for (int u = 0; u < VW; ++u) o[u] = bad ? nanf_ : (float)acc[r][u];
-        st<VW>(out + (size_t)(r0 + r) * F + col, o);
+        row_st<VW>(out + (size_t)(r0 + r) * F + col, o);
       }
     }
   }
@@ -368,19 +349,14 @@ bool ridge_head_fits(int ns, int nq, int feat, int ways) {
          ridge_head_lds_bytes(ns, nq, ways) <= head_lds_limit_bytes();
 }
 
-// A request above 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize, once per (kernel, device): head_grads_launch's rule.
+// A request above 64 KiB needs allow_dynamic_lds (mi_common.h), raised to the device's whole LDS: head_grads_launch's rule.
 template <bool BWD>
 static hipError_t ridge_launch(hipStream_t st, const RidgeArgs& a, int tasks) {
   const size_t sm = ridge_head_lds_bytes(a.ns, a.nq, a.ways);
   if (sm > 64 * 1024) {
     static unsigned attr_done = 0;             // one bit per device: the attribute belongs to the device's copy of the kernel
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (!(attr_done & (1u << (dev & 31)))) {
-      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ridge_head_kernel<BWD>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)head_lds_limit_bytes()); e != hipSuccess) return e;
-      attr_done |= 1u << (dev & 31);
-    }
+    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(ridge_head_kernel<BWD>), head_lds_limit_bytes(), &attr_done); e != hipSuccess)
+      return e;
   }
   hipLaunchKernelGGL(ridge_head_kernel<BWD>, dim3(tasks), dim3(kThreads), sm, st, a);
   return hipGetLastError();
@@ -389,7 +365,7 @@ static hipError_t ridge_launch(hipStream_t st, const RidgeArgs& a, int tasks) {
 // Forward (a.dfs == a.dfq == a.dhyper == NULL) or forward + backward, one launch either way.  Outside the domain: hipErrorInvalidValue,
 // nothing launched (callers check ridge_head_fits first and report MI_ERR_ARG).
 hipError_t launch_ridge_head(hipStream_t st, const RidgeArgs& a, int tasks) {
-  if (tasks < 1 || !ridge_head_fits(a.ns, a.nq, a.feat, a.ways) || !(a.lam > 0.f) || !(a.alpha > 0.f) || !std::isfinite(a.lam) || !std::isfinite(a.alpha))
+  if (tasks < 1 || !ridge_head_fits(a.ns, a.nq, a.feat, a.ways) || !(a.h.lam > 0.f) || !(a.h.alpha > 0.f) || !std::isfinite(a.h.lam) || !std::isfinite(a.h.alpha))
     return hipErrorInvalidValue;
   return (a.dfs || a.dfq || a.dhyper) ? ridge_launch<true>(st, a, tasks) : ridge_launch<false>(st, a, tasks);
 }

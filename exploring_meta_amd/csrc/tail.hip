@@ -634,15 +634,8 @@ size_t tail_scr_floats(int tasks, int n, int ways) { return (size_t)tasks * TAIL
 
 template <class K>
 static hipError_t tail_launch(K kern, hipStream_t st, const TailArgs& t, int tasks, size_t lds, unsigned* attr_done) {
-  if (lds > 64 * 1024) {
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (!(*attr_done & (1u << (dev & 31)))) {
-      // (raised to the cap, not to this launch's request: the attribute is set once, and a later launch of the same kernel may ask for more)
-      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_CAP); e != hipSuccess) return e;
-      *attr_done |= 1u << (dev & 31);
-    }
-  }
+  // (raised to the cap, not to this launch's request: the attribute is set once, and a later launch of the same kernel may ask for more)
+  if (lds > 64 * 1024) if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), TAIL_LDS_CAP, attr_done); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(TAIL_GROUPS, tasks), dim3(TAIL_THREADS), lds, st, t);
   return hipGetLastError();
 }

@@ -537,13 +537,8 @@ hipError_t launch_wgrad_strips_bf16(hipStream_t st, WgradArgs a, dim3 grid, int 
   if (a.form != 2 && a.g.ci == 32 && wgrad_lds_rows()) {
     const size_t lds = (size_t)4 * MI_WG_RING * (MI_WG_XSLOT + MI_WG_DSLOT) * sizeof(float);
     auto k = wgrad3x3_strip_bf16_kernel<32, false, true>;
-    static unsigned attr_done = 0;
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (!(attr_done & (1u << (dev & 31)))) {
-      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
-      attr_done |= 1u << (dev & 31);
-    }
+    static unsigned attr_done = 0;             // one bit per device (allow_dynamic_lds, mi_common.h); no threshold: lds is a constant above 64 KiB
+    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(k), lds, &attr_done); e != hipSuccess) return e;
     hipLaunchKernelGGL(k, grid, dim3(256), lds, st, a);
     return hipGetLastError();
   }

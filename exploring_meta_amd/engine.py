@@ -555,6 +555,49 @@ class MetaEngine:
         return self._anil_call(theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, step_w, first_order, with_grad, want_lr_grad,
                                return_logits)
 
+    def _closed_form_call(self, name, key, theta, data, labels, shots, hyper, with_grad, return_logits, n_hyper=0):
+        """mi_meta_batch_<name>, the fused call of a closed-form head with the hyper-parameters `hyper`.  `key`: the outputs' persistent set in
+        graph mode, distinct per head (and per metric).  n_hyper > 0: a call with a gradient also gives the per-task hyper-parameter
+        gradients [T, n_hyper], between meta_grad and logits in the arguments and in the result."""
+        s = self.spec
+        T = self._check_batch(theta, data, labels, shots, flat_data=False)
+        b = C.c_size_t()
+        _lib.check(getattr(self.lib, f'mi_{name}_workspace_bytes')(self._h, T, s.ways, shots, int(bool(with_grad)), C.byref(b)), self._h)
+        ws = self._workspace(b.value)
+        loss, acc, grad, logits = self._outputs(key, T, shots * s.ways, with_grad, return_logits)
+        dhyper = ()
+        if n_hyper:
+            dhyper = (self._persistent((f'{name}_dhyper', T), lambda: torch.empty(T, n_hyper, dtype=torch.float32, device=self.device))
+                      if with_grad else None,)
+        rc = self._fused_call(getattr(self.lib, f'mi_meta_batch_{name}'), _ptr(theta), _ptr(data), _ptr(labels), T, s.ways, shots, *hyper,
+                              int(bool(with_grad)), _ptr(loss), _ptr(acc), _ptr(grad), *map(_ptr, dhyper), _ptr(logits), _ptr(ws), ws.numel())
+        _lib.check(rc, self._h)
+        return (loss, acc, grad) + dhyper + (logits,)
+
+    def _head_entry(self, name, fs, fq, ys, yq, ways, hyper, with_grad, n_hyper=0):
+        """mi_<name>_head, the kernel entry of a closed-form head on given features.  Returns (loss, acc, logits, dfs, dfq), and with
+        n_hyper > 0 the per-task hyper-parameter gradients [T, n_hyper] as a sixth; the gradients are None without with_grad."""
+        for t, dt in ((fs, torch.float32), (fq, torch.float32), (ys, torch.int32), (yq, torch.int32)):
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                raise ValueError('fs / fq must be contiguous fp32 CUDA tensors, ys / yq contiguous int32 CUDA tensors')
+        if fs.dim() != 3 or fq.dim() != 3 or fs.shape[0] != fq.shape[0] or fs.shape[2] != fq.shape[2] or \
+                tuple(ys.shape) != tuple(fs.shape[:2]) or tuple(yq.shape) != tuple(fq.shape[:2]):
+            raise ValueError(f'fs [T, ns, F], fq [T, nq, F], ys [T, ns], yq [T, nq]; got {tuple(fs.shape)}, {tuple(fq.shape)}, '
+                             f'{tuple(ys.shape)}, {tuple(yq.shape)}')
+        T, ns, feat = fs.shape
+        nq = fq.shape[1]
+        loss = torch.empty(T, dtype=torch.float32, device=self.device)
+        acc = torch.empty(T, dtype=torch.float32, device=self.device)
+        logits = torch.empty(T, nq, ways, dtype=torch.float32, device=self.device)
+        grads = (torch.empty_like(fs) if with_grad else None, torch.empty_like(fq) if with_grad else None)
+        if n_hyper:
+            grads += (torch.empty(T, n_hyper, dtype=torch.float32, device=self.device) if with_grad else None,)
+        nscr = getattr(self.lib, f'mi_{name}_head_scratch_bytes')(T, ns, nq, feat, int(ways))
+        scr = torch.empty(nscr, dtype=torch.uint8, device=self.device) if nscr else None
+        _lib.check(getattr(self.lib, f'mi_{name}_head')(_stream(self.device), _ptr(fs), _ptr(fq), _ptr(ys), _ptr(yq), T, ns, nq, feat, int(ways),
+                                                        *hyper, _ptr(loss), _ptr(acc), _ptr(logits), *map(_ptr, grads), _ptr(scr), nscr), None)
+        return (loss, acc, logits) + grads
+
     @_on_device
     def meta_batch_metric(self, theta, data, labels, shots, metric='proto', scale=1.0, with_grad=True, return_logits=False):
         """A closed-form head on the ANIL trunk, no inner loop (mi_meta_batch_metric): metric 'proto' (Prototypical Networks: the class
@@ -562,16 +605,7 @@ class MetaEngine:
         rows).  theta keeps the ANIL layout [features.parameters()..., head.weight, head.bias]; the head's entries are not used and their
         gradient is exactly zero.  Returns (loss[T], acc[T], meta_grad[P] or None, logits [T, S*W, ways] or None)."""
         m, scale = metric_id(metric), check_scale(scale)
-        s = self.spec
-        T = self._check_batch(theta, data, labels, shots, flat_data=False)
-        b = C.c_size_t()
-        _lib.check(self.lib.mi_metric_workspace_bytes(self._h, T, s.ways, shots, int(bool(with_grad)), C.byref(b)), self._h)
-        ws = self._workspace(b.value)
-        loss, acc, grad, logits = self._outputs(('metric', m), T, shots * s.ways, with_grad, return_logits)
-        rc = self._fused_call(self.lib.mi_meta_batch_metric, _ptr(theta), _ptr(data), _ptr(labels), T, s.ways, shots, m, scale,
-                              int(bool(with_grad)), _ptr(loss), _ptr(acc), _ptr(grad), _ptr(logits), _ptr(ws), ws.numel())
-        _lib.check(rc, self._h)
-        return loss, acc, grad, logits
+        return self._closed_form_call('metric', ('metric', m), theta, data, labels, shots, (m, scale), with_grad, return_logits)
 
     @_on_device
     def metric_head(self, fs, fq, ys, yq, ways, metric='proto', scale=1.0, with_grad=True):
@@ -579,25 +613,7 @@ class MetaEngine:
         int32 in [0, ways), every class with at least one support row.  Returns (loss[T], acc[T], logits [T, nq, ways], dfs, dfq), the
         last two None without a gradient."""
         m, scale = metric_id(metric), check_scale(scale)
-        for t, dt in ((fs, torch.float32), (fq, torch.float32), (ys, torch.int32), (yq, torch.int32)):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise ValueError('fs / fq must be contiguous fp32 CUDA tensors, ys / yq contiguous int32 CUDA tensors')
-        if fs.dim() != 3 or fq.dim() != 3 or fs.shape[0] != fq.shape[0] or fs.shape[2] != fq.shape[2] or \
-                tuple(ys.shape) != tuple(fs.shape[:2]) or tuple(yq.shape) != tuple(fq.shape[:2]):
-            raise ValueError(f'fs [T, ns, F], fq [T, nq, F], ys [T, ns], yq [T, nq]; got {tuple(fs.shape)}, {tuple(fq.shape)}, '
-                             f'{tuple(ys.shape)}, {tuple(yq.shape)}')
-        T, ns, feat = fs.shape
-        nq = fq.shape[1]
-        loss = torch.empty(T, dtype=torch.float32, device=self.device)
-        acc = torch.empty(T, dtype=torch.float32, device=self.device)
-        logits = torch.empty(T, nq, ways, dtype=torch.float32, device=self.device)
-        dfs = torch.empty_like(fs) if with_grad else None
-        dfq = torch.empty_like(fq) if with_grad else None
-        nscr = self.lib.mi_metric_head_scratch_bytes(T, ns, nq, feat, int(ways))
-        scr = torch.empty(nscr, dtype=torch.uint8, device=self.device) if nscr else None
-        _lib.check(self.lib.mi_metric_head(_stream(self.device), _ptr(fs), _ptr(fq), _ptr(ys), _ptr(yq), T, ns, nq, feat, int(ways), m, scale,
-                                           _ptr(loss), _ptr(acc), _ptr(logits), _ptr(dfs), _ptr(dfq), _ptr(scr), nscr), None)
-        return loss, acc, logits, dfs, dfq
+        return self._head_entry('metric', fs, fq, ys, yq, ways, (m, scale), with_grad)
 
     @_on_device
     def meta_batch_ridge(self, theta, data, labels, shots, lam=1.0, scale=1.0, with_grad=True, return_logits=False):
@@ -605,44 +621,13 @@ class MetaEngine:
         scale * (fq fs^T) A -- the head's inner problem solved exactly, no inner loop.  theta keeps the ANIL layout; the head's entries
         are not used and their gradient is exactly zero.  Returns (loss[T], acc[T], meta_grad[P] or None, dhyper [T, 2] or None, logits
         [T, S*W, ways] or None); dhyper[t] = (dloss_t/dlam, dloss_t/dscale), per task: the sum is the caller's."""
-        lam, scale = check_ridge(lam, scale)
-        s = self.spec
-        T = self._check_batch(theta, data, labels, shots, flat_data=False)
-        b = C.c_size_t()
-        _lib.check(self.lib.mi_ridge_workspace_bytes(self._h, T, s.ways, shots, int(bool(with_grad)), C.byref(b)), self._h)
-        ws = self._workspace(b.value)
-        loss, acc, grad, logits = self._outputs(('ridge',), T, shots * s.ways, with_grad, return_logits)
-        dhyper = self._persistent(('ridge_dhyper', T), lambda: torch.empty(T, 2, dtype=torch.float32, device=self.device)) if with_grad else None
-        rc = self._fused_call(self.lib.mi_meta_batch_ridge, _ptr(theta), _ptr(data), _ptr(labels), T, s.ways, shots, lam, scale,
-                              int(bool(with_grad)), _ptr(loss), _ptr(acc), _ptr(grad), _ptr(dhyper), _ptr(logits), _ptr(ws), ws.numel())
-        _lib.check(rc, self._h)
-        return loss, acc, grad, dhyper, logits
+        return self._closed_form_call('ridge', ('ridge',), theta, data, labels, shots, check_ridge(lam, scale), with_grad, return_logits, n_hyper=2)
 
     @_on_device
     def ridge_head(self, fs, fq, ys, yq, ways, lam=1.0, scale=1.0, with_grad=True):
         """The ridge head's kernel entry (mi_ridge_head) on given features: fs [T, ns, F], fq [T, nq, F] fp32, ys [T, ns], yq [T, nq] int32
         in [0, ways).  Returns (loss[T], acc[T], logits [T, nq, ways], dfs, dfq, dhyper [T, 2]), the last three None without a gradient."""
-        lam, scale = check_ridge(lam, scale)
-        for t, dt in ((fs, torch.float32), (fq, torch.float32), (ys, torch.int32), (yq, torch.int32)):
-            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-                raise ValueError('fs / fq must be contiguous fp32 CUDA tensors, ys / yq contiguous int32 CUDA tensors')
-        if fs.dim() != 3 or fq.dim() != 3 or fs.shape[0] != fq.shape[0] or fs.shape[2] != fq.shape[2] or \
-                tuple(ys.shape) != tuple(fs.shape[:2]) or tuple(yq.shape) != tuple(fq.shape[:2]):
-            raise ValueError(f'fs [T, ns, F], fq [T, nq, F], ys [T, ns], yq [T, nq]; got {tuple(fs.shape)}, {tuple(fq.shape)}, '
-                             f'{tuple(ys.shape)}, {tuple(yq.shape)}')
-        T, ns, feat = fs.shape
-        nq = fq.shape[1]
-        loss = torch.empty(T, dtype=torch.float32, device=self.device)
-        acc = torch.empty(T, dtype=torch.float32, device=self.device)
-        logits = torch.empty(T, nq, ways, dtype=torch.float32, device=self.device)
-        dfs = torch.empty_like(fs) if with_grad else None
-        dfq = torch.empty_like(fq) if with_grad else None
-        dhyper = torch.empty(T, 2, dtype=torch.float32, device=self.device) if with_grad else None
-        nscr = self.lib.mi_ridge_head_scratch_bytes(T, ns, nq, feat, int(ways))
-        scr = torch.empty(nscr, dtype=torch.uint8, device=self.device) if nscr else None
-        _lib.check(self.lib.mi_ridge_head(_stream(self.device), _ptr(fs), _ptr(fq), _ptr(ys), _ptr(yq), T, ns, nq, feat, int(ways), lam, scale,
-                                          _ptr(loss), _ptr(acc), _ptr(logits), _ptr(dfs), _ptr(dfq), _ptr(dhyper), _ptr(scr), nscr), None)
-        return loss, acc, logits, dfs, dfq, dhyper
+        return self._head_entry('ridge', fs, fq, ys, yq, ways, check_ridge(lam, scale), with_grad, n_hyper=2)
 
     @_on_device
     def forward_logits(self, theta, x):

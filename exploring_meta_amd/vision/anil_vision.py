@@ -12,16 +12,13 @@ generator (datasets are not available offline).
 """
 import argparse
 import os
-import random
 
-import numpy as np
 import torch
 
 from ..core_functions import MAML, ConvBase, InnerLR, msl_weights
-from ..core_functions.anil import anil_engine, meta_batch_adapt_anil, meta_batch_adapt_anil_steps
-from ..core_functions.vision_models import RunningStatsFold
-from ..sharding import init_process_group, reduce_meta_batch, shard_range
-from .maml_vision import SyntheticTasks, inner_lr_of
+from ..core_functions.anil import meta_batch_adapt_anil, meta_batch_adapt_anil_steps
+from .maml_vision import add_trunk_test_flags, inner_lr_of, trunk_test_params, trunk_tests
+from .trunk_loop import train_trunk
 
 params = {
     "ways": 5, "shots": 5, "outer_lr": 0.003, "inner_lr": 0.5, "adapt_steps": 1, "meta_batch_size": 32,
@@ -57,102 +54,34 @@ def build(dataset, ways, inner_lr, device, p=None):
 
 
 def run(dataset, p, log=print):
-    world = int(os.environ.get('WORLD_SIZE', '1'))
-    rank = int(os.environ.get('RANK', '0'))
-    local = int(os.environ.get('LOCAL_RANK', '0'))
-    torch.cuda.set_device(local)
-    if world > 1:
-        init_process_group(local)
-    random.seed(p['seed']); np.random.seed(p['seed']); torch.manual_seed(p['seed']); torch.cuda.manual_seed(p['seed'])
-    device = torch.device('cuda', local)
-    features, head = build(dataset, p['ways'], p['inner_lr'], device, p)
-    # anil_vision.py:97; head.parameters() includes a learnable InnerLR's values (a submodule of MAML), so they are stepped by the
-    # optimiser and all-reduced with the rest
-    all_parameters = list(features.parameters()) + list(head.parameters())
-    opt = torch.optim.Adam(all_parameters, lr=p['outer_lr'])
-    T = p['meta_batch_size']
-    lo, hi = shard_range(T, rank, world)
-    train, valid = SyntheticTasks(dataset, p['ways'], p['shots'], 0), SyntheticTasks(dataset, p['ways'], p['shots'], 10 ** 6)
-    metrics = {}
-    zero = torch.zeros((), device=device)
-    save_dir = p.get('save_dir') or ''
-    if save_dir and rank == 0:
-        os.makedirs(os.path.join(save_dir, 'model_checkpoints'), exist_ok=True)
-    msl_its = int(p.get('msl_iterations', 0)) if p.get('multi_step_loss') and p['adapt_steps'] >= 1 else 0
-    step_w = torch.zeros(max(p['adapt_steps'], 1), device=device)      # annealed in place: the engine reads the weights on the device
+    def setup(device):
+        features, head = build(dataset, p['ways'], p['inner_lr'], device, p)
+        msl_its = int(p.get('msl_iterations', 0)) if p.get('multi_step_loss') and p['adapt_steps'] >= 1 else 0
+        step_w = torch.zeros(max(p['adapt_steps'], 1), device=device)      # annealed in place: the engine reads the weights on the device
 
-    def adapt(it, data, labels):
-        """One fused call: the multi-step loss while it < --msl_iterations (--multi_step_loss), else the plain call.  The logged loss and
-        accuracy are those of the last step either way."""
-        if it >= msl_its or not torch.is_grad_enabled():
-            return meta_batch_adapt_anil(head.clone(), features, data, labels, p['adapt_steps'], p['shots'], p['ways'])
-        step_w.copy_(torch.tensor(msl_weights(p['adapt_steps'], it, msl_its)))
-        total, losses, accs = meta_batch_adapt_anil_steps(head.clone(), features, data, labels, p['adapt_steps'], p['shots'], p['ways'],
-                                                          step_weights=step_w)
-        return total, losses[-1], accs[-1]
+        def adapt(it, data, labels):
+            """One fused call: the multi-step loss while it < --msl_iterations (--multi_step_loss), else the plain call.  The logged loss and
+            accuracy are those of the last step either way."""
+            if it >= msl_its or not torch.is_grad_enabled():
+                return meta_batch_adapt_anil(head.clone(), features, data, labels, p['adapt_steps'], p['shots'], p['ways'])
+            step_w.copy_(torch.tensor(msl_weights(p['adapt_steps'], it, msl_its)))
+            total, losses, accs = meta_batch_adapt_anil_steps(head.clone(), features, data, labels, p['adapt_steps'], p['shots'], p['ways'],
+                                                              step_weights=step_w)
+            return total, losses[-1], accs[-1]
 
-    for it in range(p['num_iterations']):
-        opt.zero_grad()
-        ids = list(range(it * T + lo, it * T + hi))
-        # BatchNorm buffers of `features` (saved with every checkpoint): one features(data) pass per task and phase (anil.py fast_adapt)
-        fold = None
-        if save_dir:
-            eng = anil_engine(features, p['ways'], 28 if dataset == 'omni' else 84, device)
-            fold = RunningStatsFold(eng, features[0], eng.spec, T, lo, hi, 1, 2 * p['ways'] * p['shots'])
-        if ids:
-            d, l = train.sample_batch(ids)
-            total, losses, accs = adapt(it, d.to(device), l.to(device))
-            total.backward()
-            if fold:
-                fold.collect(0)
-            with torch.no_grad():
-                d, l = valid.sample_batch([10 ** 6 + i for i in ids])
-                _, vlosses, vaccs = meta_batch_adapt_anil(head.clone(), features, d.to(device), l.to(device), p['adapt_steps'],
-                                                          p['shots'], p['ways'])
-            if fold:
-                fold.collect(1)
-            sums = [losses.sum(), accs.sum(), vlosses.sum(), vaccs.sum()]
-        else:                                    # meta_batch_size < world size: this rank owns no task, contributes zeros
-            sums = [zero, zero, zero, zero]
-        flat = torch.cat([(q.grad if q.grad is not None else torch.zeros_like(q)).reshape(-1) for q in all_parameters])
-        flat, lsum, asum, ex = reduce_meta_batch(flat, sums[0], sums[1], extra=sums[2:] + ([fold.contribution] if fold else []))
-        vlsum, vasum = ex[0], ex[1]                                           # one all-reduce, valid sums (and buffers) included
-        if fold:
-            fold.apply(ex[2])
-        off = 0
-        for q in all_parameters:                                                     # anil_vision.py:139-140
-            g = flat[off:off + q.numel()].view_as(q) * (1.0 / T)
-            q.grad = g.clone() if q.grad is None else q.grad.copy_(g)
-            off += q.numel()
-        opt.step()
-        metrics = {'train_loss': (lsum / T).item(), 'train_acc': (asum / T).item(),
-                   'valid_loss': (vlsum / T).item(), 'valid_acc': (vasum / T).item()}
-        if rank == 0:
-            log(f'iter {it}: {metrics}')
-            if save_dir and it % p['save_every'] == 0:                                # anil_vision.py:143-145
-                # save_model_checkpoint(m, 'features_<it+1>') -> model_checkpoints/model_features_<it+1>.pt (utils/experiment.py:89-90)
-                torch.save(features.state_dict(), os.path.join(save_dir, 'model_checkpoints', f'model_features_{it + 1}.pt'))
-                torch.save(head.state_dict(), os.path.join(save_dir, 'model_checkpoints', f'model_head_{it + 1}.pt'))
-    if rank == 0 and save_dir:                                                        # anil_vision.py:163-164
-        torch.save(features.state_dict(), os.path.join(save_dir, 'features.pt'))
-        torch.save(head.state_dict(), os.path.join(save_dir, 'head.pt'))
-        if isinstance(head.lr, InnerLR):
-            torch.save(head.lr.state_dict(), os.path.join(save_dir, 'inner_lr.pt'))
-    if p.get('nil_test'):        # --nil_test: how good are the features alone?  The head is thrown away (NIL, no inner loop)
-        from ..core_functions.metric import evaluate_nil
-        test = SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6)
-        metrics['nil_test_acc'] = evaluate_nil(p, test, features, device)
-        if rank == 0:
-            log(f"nil_test_acc: {metrics['nil_test_acc']}")
-    if p.get('ridge_test'):      # --ridge_test: how good is the exactly solved head on these features?  (R2-D2's ridge regression, fixed lam / scale)
-        from ..core_functions.ridge import RidgeHead, evaluate_ridge
-        test = SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6)
-        metrics['ridge_test_acc'] = evaluate_ridge(p, test, features, RidgeHead(p['ridge_lam'], p['ridge_scale'], learnable=False), device)
-        if rank == 0:
-            log(f"ridge_test_acc: {metrics['ridge_test_acc']}")
-    if world > 1:
-        torch.distributed.destroy_process_group()
-    return (features, head), metrics
+        def after(metrics, test_tasks, rank, save_final):
+            save_final()
+            if rank == 0 and p.get('save_dir') and isinstance(head.lr, InnerLR):
+                torch.save(head.lr.state_dict(), os.path.join(p['save_dir'], 'inner_lr.pt'))
+            trunk_tests(p, test_tasks, features, device, rank, metrics, log)
+
+        # anil_vision.py:97; head.parameters() includes a learnable InnerLR's values (a submodule of MAML), so they are stepped by the
+        # optimiser and all-reduced with the rest
+        return dict(features=features, parameters=list(features.parameters()) + list(head.parameters()), train=adapt,
+                    valid=lambda d, l: meta_batch_adapt_anil(head.clone(), features, d, l, p['adapt_steps'], p['shots'], p['ways']),
+                    checkpoints={'features': features, 'head': head}, after=after, result=(features, head))
+
+    return train_trunk(dataset, p, log, setup)
 
 
 def build_parser():
@@ -170,12 +99,7 @@ def build_parser():
                         help='MAML++ multi-step loss: the outer objective weights the query loss after every head step (msl_weights)')
     parser.add_argument('--msl_iterations', type=int, default=0, metavar='N',
                         help='iterations over which the multi-step weights anneal to the final step; from iteration N on the plain call runs')
-    parser.add_argument('--nil_test', action='store_true',
-                        help='after training also log nil_test_acc: the trunk scored on meta_batch_size test tasks by the NIL cosine head, no inner loop')
-    parser.add_argument('--ridge_test', action='store_true',
-                        help='after training also log ridge_test_acc: the trunk under the exactly solved ridge-regression head (R2-D2) with the fixed --ridge_lam / --ridge_scale, no inner loop')
-    parser.add_argument('--ridge_lam', type=float, default=1.0, metavar='LAM', help="--ridge_test: the ridge head's regulariser")
-    parser.add_argument('--ridge_scale', type=float, default=1.0, metavar='S', help="--ridge_test: the ridge head's logit scale")
+    add_trunk_test_flags(parser, 'after training')
     return parser
 
 
@@ -187,8 +111,7 @@ def params_of(args):
     """The run's parameter dict from parsed flags (the defaults are the reference's run)."""
     p = {k: getattr(args, k) for k in params}
     p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
-             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations, nil_test=args.nil_test,
-             ridge_test=args.ridge_test, ridge_lam=args.ridge_lam, ridge_scale=args.ridge_scale)
+             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations, **trunk_test_params(args))
     return p
 
 

@@ -67,6 +67,36 @@ def step_offsets_of(model, p):
     return StepOffsets(model, p['adapt_steps'], 'bn')
 
 
+def add_trunk_test_flags(parser, when, note=''):
+    """--nil_test / --ridge_test (--ridge_lam, --ridge_scale): the trunk alone under a closed-form head, scored ``when``."""
+    parser.add_argument('--nil_test', action='store_true',
+                        help=f'{when} also log nil_test_acc: the trunk scored on meta_batch_size test tasks by the NIL cosine head, no inner loop{note}')
+    parser.add_argument('--ridge_test', action='store_true',
+                        help=f'{when} also log ridge_test_acc: the trunk under the exactly solved ridge-regression head (R2-D2) with the fixed '
+                             f'--ridge_lam / --ridge_scale, no inner loop{note}')
+    parser.add_argument('--ridge_lam', type=float, default=1.0, metavar='LAM', help="--ridge_test: the ridge head's regulariser")
+    parser.add_argument('--ridge_scale', type=float, default=1.0, metavar='S', help="--ridge_test: the ridge head's logit scale")
+
+
+def trunk_test_params(args):
+    return dict(nil_test=args.nil_test, ridge_test=args.ridge_test, ridge_lam=args.ridge_lam, ridge_scale=args.ridge_scale)
+
+
+def trunk_tests(p, test_tasks, trunk, device, rank, metrics, log):
+    """--nil_test: how good are the features alone?  The head is thrown away (NIL, no inner loop).  --ridge_test: how good is the exactly
+    solved head on these features (R2-D2's ridge regression, fixed lam / scale)?  Each on meta_batch_size tasks of its own ``test_tasks()``."""
+    if p.get('nil_test'):
+        from ..core_functions.metric import evaluate_nil
+        metrics['nil_test_acc'] = evaluate_nil(p, test_tasks(), trunk, device)
+        if rank == 0:
+            log(f"nil_test_acc: {metrics['nil_test_acc']}")
+    if p.get('ridge_test'):
+        from ..core_functions.ridge import RidgeHead, evaluate_ridge
+        metrics['ridge_test_acc'] = evaluate_ridge(p, test_tasks(), trunk, RidgeHead(p['ridge_lam'], p['ridge_scale'], learnable=False), device)
+        if rank == 0:
+            log(f"ridge_test_acc: {metrics['ridge_test_acc']}")
+
+
 def run(dataset, p, first_order=False, log=print):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -158,17 +188,7 @@ def run(dataset, p, first_order=False, log=print):
                 torch.save(model.state_dict(), os.path.join(save_dir, 'model_checkpoints', f'model_{it}.pt'))
     test = SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6)
     metrics['test_acc'] = evaluate(p, test, maml, loss, device)
-    if p.get('nil_test'):        # --nil_test: the same number of test tasks scored by the NIL cosine head on the trunk alone, no inner loop
-        from ..core_functions.metric import evaluate_nil
-        metrics['nil_test_acc'] = evaluate_nil(p, SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6), model, device)
-        if rank == 0:
-            log(f"nil_test_acc: {metrics['nil_test_acc']}")
-    if p.get('ridge_test'):      # --ridge_test: the same number of test tasks under the exactly solved ridge-regression head on the trunk alone
-        from ..core_functions.ridge import RidgeHead, evaluate_ridge
-        metrics['ridge_test_acc'] = evaluate_ridge(p, SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6), model,
-                                                   RidgeHead(p['ridge_lam'], p['ridge_scale'], learnable=False), device)
-        if rank == 0:
-            log(f"ridge_test_acc: {metrics['ridge_test_acc']}")
+    trunk_tests(p, lambda: SyntheticTasks(dataset, p['ways'], p['shots'], 2 * 10 ** 6), model, device, rank, metrics, log)
     if world > 1:
         torch.distributed.destroy_process_group()
     if save_dir and rank == 0:
@@ -203,12 +223,7 @@ def build_parser():
                         help='MAML++ derivative-order annealing: iterations < N make the first-order call')
     parser.add_argument('--cosine_outer_lr', action='store_true', help='cosine-anneal the outer learning rate over num_iterations')
     parser.add_argument('--min_outer_lr', type=float, default=0.0, metavar='X', help='the floor of --cosine_outer_lr')
-    parser.add_argument('--nil_test', action='store_true',
-                        help='after the test accuracy also log nil_test_acc: the trunk alone under the NIL cosine head (flattened features: --dataset min)')
-    parser.add_argument('--ridge_test', action='store_true',
-                        help='after the test accuracy also log ridge_test_acc: the trunk under the exactly solved ridge-regression head (R2-D2) with the fixed --ridge_lam / --ridge_scale (flattened features: --dataset min)')
-    parser.add_argument('--ridge_lam', type=float, default=1.0, metavar='LAM', help="--ridge_test: the ridge head's regulariser")
-    parser.add_argument('--ridge_scale', type=float, default=1.0, metavar='S', help="--ridge_test: the ridge head's logit scale")
+    add_trunk_test_flags(parser, 'after the test accuracy', ' (flattened features: --dataset min)')
     return parser
 
 
@@ -218,8 +233,7 @@ def params_of(args):
     p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
              freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations,
              per_step_bn=args.per_step_bn, per_step_bn_adapt_bn=args.per_step_bn_adapt_bn, first_order_iterations=args.first_order_iterations,
-             cosine_outer_lr=args.cosine_outer_lr, min_outer_lr=args.min_outer_lr, nil_test=args.nil_test,
-             ridge_test=args.ridge_test, ridge_lam=args.ridge_lam, ridge_scale=args.ridge_scale)
+             cosine_outer_lr=args.cosine_outer_lr, min_outer_lr=args.min_outer_lr, **trunk_test_params(args))
     return p
 
 

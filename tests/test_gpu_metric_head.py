@@ -19,6 +19,8 @@ from exploring_meta_amd.utils import synthetic
 from oracle import vision_ref as R
 from gpu_utils import dev, ptr, rel_err, report, stream
 import metric_head_oracle as M
+import closed_form_utils as U
+from closed_form_utils import census as _census, grads as _grads, held as _held, np_of as _np, same as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -28,20 +30,7 @@ KERNEL_BAR = 2e-6          # tests/test_gpu_kernels.py's kernel bar
 NAMES = ('loss', 'acc', 'logits', 'dfs', 'dfq')
 
 
-def _np(*ts):
-    torch.cuda.synchronize()
-    return tuple(None if t is None else t.detach().cpu().numpy().copy() for t in ts)
-
-
-def _held(name, err, ref_err, floor):
-    """The project's rule: err <= max(floor, 2 x the fp32 oracle's own error on the same inputs)."""
-    print(f'[held] {name}: err {np.max(err):.3e} fp32-oracle err {np.max(ref_err):.3e} floor {floor:.0e}')
-    assert np.all(np.asarray(err) <= np.maximum(floor, 2 * np.asarray(ref_err))), (name, err, ref_err, floor)
-
-
-def _same(tag, names, got, want):
-    for name, a, b in zip(names, got, want):
-        assert (a is None and b is None) or np.array_equal(a, b), (tag, name, rel_err(a, b))
+_mspec, _inputs, _trunk = (functools.partial(f, M) for f in (U.mspec, U.inputs, U.trunk))
 
 
 def _kernel(fs, fq, ys, yq, ways, metric, scale, grad=True, logits=True, fill=None):
@@ -209,23 +198,6 @@ def test_bitwise_relations(feat, ways, ns, nq, metric):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4: the fused call
-def _mspec(shape):
-    _, (hidden, channels, max_pool), hw, _, ways, _ = M.SHAPES[shape]
-    return ModelSpec.anil(ways, hidden=hidden, channels=channels, max_pool=max_pool, in_hw=hw)
-
-
-def _inputs(shape, ids=None, head=0.0):
-    """(engine spec, theta, data [T, 2n, C, H, W], labels, ways, shots, trunk parameter count) on the GPU; the head's entries of theta
-    are `head` (they are not read: NaN is as good as 0)."""
-    dataset, (_, channels, _), hw, fc, ways, shots = M.SHAPES[shape]
-    _, tf, _, _, _, _ = M.fixtures(shape)
-    trunk = R.flatten_params(tf).float()
-    theta = torch.cat([trunk, torch.full((ways * fc + ways,), float(head))]).cuda().contiguous()
-    data, labels = synthetic.make_meta_batch(dataset, list(ids if ids is not None else M.FUSED_CASES[shape][0]), ways, shots)
-    data = torch.from_numpy(data).reshape(data.shape[0], data.shape[1], channels, hw, hw).cuda().contiguous()
-    return _mspec(shape), theta, data, torch.from_numpy(labels).cuda().contiguous(), ways, shots, trunk.numel()
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle(shape, fp64, ids=None):
     """One oracle run per case and precision (both metrics from one trunk pass), shared by every test that needs it (never modified)."""
@@ -336,15 +308,6 @@ def test_bn_export_is_the_anil_calls(metric):
     eng.set_bn_export(0)
 
 
-def _census(eng, fn):
-    eng.profile(True)
-    fn()
-    torch.cuda.synchronize()
-    c = {f'{op}/{layer}': int(n) for (op, layer), (_, n) in eng.profile_collect().items()}
-    eng.profile(False)
-    return c
-
-
 @pytest.mark.parametrize('metric', METRICS)
 def test_launch_make_up(metric):
     """Exactly one metric-head launch per call, no classifier-head or head-tangent launch, and a census that does not depend on the task
@@ -396,20 +359,6 @@ def test_fused_argument_errors_come_before_any_launch():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6: the Python surface
-def _trunk(shape):
-    _, (hidden, channels, max_pool), _, fc, ways, _ = M.SHAPES[shape]
-    _, tf, _, _, _, _ = M.fixtures(shape)
-    trunk = cf.ConvBase(output_size=64, hidden=hidden, channels=channels, max_pool=max_pool)
-    with torch.no_grad():
-        for k, p in trunk.named_parameters():
-            p.copy_(tf['0.' + k].float())
-    return torch.nn.Sequential(trunk).cuda()
-
-
-def _grads(params):
-    return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params]).cpu().numpy()
-
-
 @pytest.mark.parametrize('metric', METRICS)
 def test_backward_fills_the_trunk_and_nothing_else(metric):
     mspec, theta, data, labels, ways, shots, nf = _inputs('omni')

@@ -19,26 +19,15 @@ from exploring_meta_amd.utils import synthetic
 from oracle import vision_ref as R
 from gpu_utils import dev, ptr, rel_err, report, stream
 import ridge_head_oracle as RH
+import closed_form_utils as U
+from closed_form_utils import census as _census, grads as _grads, held as _held, np_of as _np, same as _same
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ('loss', 'acc', 'logits', 'dfs', 'dfq', 'dhyper')
 
 
-def _np(*ts):
-    torch.cuda.synchronize()
-    return tuple(None if t is None else t.detach().cpu().numpy().copy() for t in ts)
-
-
-def _held(name, err, ref_err, floor):
-    """err <= max(floor, 2 x the fp32 oracle's own error on the same inputs): both terms come from the reference side."""
-    print(f'[held] {name}: err {np.max(err):.3e} fp32-oracle err {np.max(ref_err):.3e} floor {np.max(floor):.3e}')
-    assert np.all(np.asarray(err) <= np.maximum(floor, 2 * np.asarray(ref_err))), (name, err, ref_err, floor)
-
-
-def _same(tag, names, got, want):
-    for name, a, b in zip(names, got, want):
-        assert (a is None and b is None) or np.array_equal(a, b), (tag, name, rel_err(a, b))
+_mspec, _inputs, _trunk = (functools.partial(f, RH) for f in (U.mspec, U.inputs, U.trunk))
 
 
 def _kernel(fs, fq, ys, yq, ways, lam, alpha, dfs=True, dfq=True, dhyper=True, logits=True, fill=None):
@@ -183,23 +172,6 @@ def test_bitwise_relations(feat, ways, ns, nq):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4: the fused call
-def _mspec(shape):
-    _, (hidden, channels, max_pool), hw, _, ways, _ = RH.SHAPES[shape]
-    return ModelSpec.anil(ways, hidden=hidden, channels=channels, max_pool=max_pool, in_hw=hw)
-
-
-def _inputs(shape, ids=None, head=0.0):
-    """(engine spec, theta, data [T, 2n, C, H, W], labels, ways, shots, trunk parameter count) on the GPU; the head's entries of theta
-    are `head` (they are not read: NaN is as good as 0)."""
-    dataset, (_, channels, _), hw, fc, ways, shots = RH.SHAPES[shape]
-    _, tf, _, _, _, _ = RH.fixtures(shape)
-    trunk = R.flatten_params(tf).float()
-    theta = torch.cat([trunk, torch.full((ways * fc + ways,), float(head))]).cuda().contiguous()
-    data, labels = synthetic.make_meta_batch(dataset, list(ids if ids is not None else RH.FUSED_CASES[shape][0]), ways, shots)
-    data = torch.from_numpy(data).reshape(data.shape[0], data.shape[1], channels, hw, hw).cuda().contiguous()
-    return _mspec(shape), theta, data, torch.from_numpy(labels).cuda().contiguous(), ways, shots, trunk.numel()
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle(shape, fp64, ids=None):
     """One oracle run per case and precision, shared by every test that needs it (never modified)."""
@@ -296,15 +268,6 @@ def test_graph_replay():
     eng.set_graph(False)
 
 
-def _census(eng, fn):
-    eng.profile(True)
-    fn()
-    torch.cuda.synchronize()
-    c = {f'{op}/{layer}': int(n) for (op, layer), (_, n) in eng.profile_collect().items()}
-    eng.profile(False)
-    return c
-
-
 def test_launch_make_up():
     """Exactly one ridge-head launch per call, whatever the task count; apart from it the launches are mi_meta_batch_metric's."""
     seen = []
@@ -349,20 +312,6 @@ def test_fused_argument_errors_come_before_any_launch():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6: the Python surface
-def _trunk(shape):
-    _, (hidden, channels, max_pool), _, fc, ways, _ = RH.SHAPES[shape]
-    _, tf, _, _, _, _ = RH.fixtures(shape)
-    trunk = cf.ConvBase(output_size=64, hidden=hidden, channels=channels, max_pool=max_pool)
-    with torch.no_grad():
-        for k, p in trunk.named_parameters():
-            p.copy_(tf['0.' + k].float())
-    return torch.nn.Sequential(trunk).cuda()
-
-
-def _grads(params):
-    return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params]).cpu().numpy()
-
-
 def test_backward_fills_the_trunk_and_the_heads_two_scalars():
     mspec, theta, data, labels, ways, shots, nf = _inputs('omni')
     features = _trunk('omni')

@@ -2,7 +2,6 @@
 (tests/metric_head_oracle.py), the margin property the GPU test relies on, the drivers' flags, the C symbols, and what the Python
 surface refuses without a GPU."""
 import functools
-import os
 import re
 
 import numpy as np
@@ -12,8 +11,8 @@ import torch
 from exploring_meta_amd import _lib
 from exploring_meta_amd import core_functions as cf
 import metric_head_oracle as M
+from closed_form_utils import symbols_declared_and_bound
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ('mi_metric_head_scratch_bytes', 'mi_metric_head', 'mi_metric_workspace_bytes', 'mi_meta_batch_metric')
 
 
@@ -69,12 +68,7 @@ def test_oracle_margins_of_the_gpu_cases(shape, metric):
 
 
 def test_symbols_declared_and_bound():
-    header = open(os.path.join(REPO, 'include', 'mi_maml.h')).read()
-    for name in SYMBOLS:
-        m = re.search(r'\b(?:int|size_t) ' + name + r'\(([^;]*)\);', header)
-        assert m, name
-        assert name in _lib.EXPORTS
-        assert len(_lib._SIGS[name][1]) == re.sub(r'/\*.*?\*/', '', m.group(1)).count(',') + 1, name
+    header = symbols_declared_and_bound(SYMBOLS)
     assert re.search(r'#define MI_METRIC_PROTO 0\b', header) and re.search(r'#define MI_METRIC_COSINE 1\b', header)
     from exploring_meta_amd.engine import METRICS
     assert METRICS == {'proto': 0, 'cosine': 1}

@@ -14,6 +14,7 @@ import torch
 from exploring_meta_amd import _lib
 from exploring_meta_amd import core_functions as cf
 import ridge_head_oracle as RH
+from closed_form_utils import symbols_declared_and_bound
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ('mi_ridge_head_scratch_bytes', 'mi_ridge_head', 'mi_ridge_workspace_bytes', 'mi_meta_batch_ridge')
@@ -119,12 +120,7 @@ def test_kernel_cases_and_the_domain():
 
 
 def test_symbols_declared_and_bound():
-    header = open(os.path.join(REPO, 'include', 'mi_maml.h')).read()
-    for name in SYMBOLS:
-        m = re.search(r'\b(?:int|size_t) ' + name + r'\(([^;]*)\);', header)
-        assert m, name
-        assert name in _lib.EXPORTS
-        assert len(_lib._SIGS[name][1]) == re.sub(r'/\*.*?\*/', '', m.group(1)).count(',') + 1, name
+    symbols_declared_and_bound(SYMBOLS)
     # the metric entries keep their two metrics: the ridge head has entries of its own
     from exploring_meta_amd.engine import METRICS
     assert METRICS == {'proto': 0, 'cosine': 1}
