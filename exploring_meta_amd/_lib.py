@@ -113,6 +113,11 @@ _SIGS = {
     'mi_meta_batch_anil_steps': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    'mi_anil_proto_workspace_bytes': (C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_size_t)]),
+    'mi_meta_batch_anil_proto': (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int] +
+                                 [C.c_void_p] * 7 + [C.c_size_t]),
+    'mi_proto_init': (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_size_t]),
+    'mi_proto_init_bwd': (C.c_int, [C.c_void_p] * 4 + [C.c_size_t] + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p]),
     'mi_metric_head_scratch_bytes': (C.c_size_t, [C.c_int] * 5),
     'mi_metric_head': (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 6 + [C.c_size_t]),
     'mi_metric_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),

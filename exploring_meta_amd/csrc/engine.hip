@@ -90,11 +90,11 @@ struct mi_engine {
 
 enum ProfOp { OP_CONV_FWD = 0, OP_BN_FINALIZE, OP_BN_FWD, OP_HEAD, OP_BN_BWD_REDUCE, OP_BN_BWD_APPLY, OP_WGRAD, OP_WGRAD_REDUCE,
               OP_DGRAD, OP_TAN_CONV, OP_BN_TAN_FWD, OP_HEAD_TAN, OP_BN_TAN_BWD_REDUCE, OP_BN_TAN_BWD_APPLY, OP_TAN_WGRAD,
-              OP_TAN_DGRAD, OP_MISC, OP_GRAM, OP_GRAM_STATS, OP_METRIC_HEAD, OP_RIDGE_HEAD, OP_COUNT };
+              OP_TAN_DGRAD, OP_MISC, OP_GRAM, OP_GRAM_STATS, OP_METRIC_HEAD, OP_RIDGE_HEAD, OP_PROTO_INIT, OP_COUNT };
 static const char* kOpNames[OP_COUNT] = {"conv_fwd_stats", "bn_finalize", "bn_relu_pool_fwd", "head_fwd_bwd", "bn_bwd_reduce",
                                          "bn_bwd_apply", "wgrad", "wgrad_reduce", "dgrad", "tangent_conv_fwd", "bn_tangent_fwd",
                                          "head_tangent", "bn_tangent_bwd_reduce", "bn_tangent_bwd_apply", "tangent_wgrad",
-                                         "tangent_dgrad", "misc", "input_gram", "gram_stats", "metric_head", "ridge_head"};
+                                         "tangent_dgrad", "misc", "input_gram", "gram_stats", "metric_head", "ridge_head", "proto_init"};
 
 static bool prof_begin(mi_engine* e, hipStream_t st, int kind) {
   if (!e || !e->prof_on || (e->prof_filter >= 0 && e->prof_filter != kind)) return false;
@@ -162,6 +162,12 @@ static int ridge_hyper_check(mi_engine* e, const char* who, float lam, float alp
   if (!(alpha > 0.f) || !std::isfinite(alpha))
     return fail(e, MI_ERR_ARG, std::string(who) + ": alpha must be positive and finite, got " + std::to_string(alpha));
   return MI_OK;
+}
+// The Proto-MAML initialisation keeps nothing task-sized on chip: its domain is the stated one (proto_init.hip).
+static int proto_init_size_fail(mi_engine* e, const char* who, int tasks, int ns, int feat, int ways) {
+  return fail(e, MI_ERR_ARG, std::string(who) + ": the prototype initialisation with tasks = " + std::to_string(tasks) + ", ns = " + std::to_string(ns) +
+                                 ", feat = " + std::to_string(feat) + " and ways = " + std::to_string(ways) + " needs tasks, ns >= 1, feat in 1.." +
+                                 std::to_string(MI_RIDGE_MAX_FEAT) + " and ways in 1..64");
 }
 static int metric_hyper_check(mi_engine* e, const char* who, int metric, float scale) {
   if (metric != MI_METRIC_PROTO && metric != MI_METRIC_COSINE)
@@ -1259,10 +1265,12 @@ static AdvanceArgs advance_base(const mi_engine* e, float* g) {
 // ALGO_METRIC (mi_meta_batch_metric): the ANIL call's trunk pass with a closed-form head (metric, scale) and no inner loop; adapt_steps = 0,
 // grad_tasks is tasks or 0.
 enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS = 3, ALGO_ANIL_LR = 4, ALGO_ANIL_STEPS = 5, ALGO_MAML_OFFSETS = 6,
-                ALGO_METRIC = 7, ALGO_RIDGE = 8 };
+                ALGO_METRIC = 7, ALGO_RIDGE = 8, ALGO_ANIL_PROTO = 9 };
 // ALGO_RIDGE (mi_meta_batch_ridge): ALGO_METRIC's launches with the ridge-regression head (lam, alpha) in the metric head's place;
 // dhyper_out [tasks][2] or null.
-static bool is_anil(MetaAlgo a) { return a == ALGO_ANIL || a == ALGO_ANIL_LR || a == ALGO_ANIL_STEPS; }
+// ALGO_ANIL_PROTO (mi_meta_batch_anil_proto): ALGO_ANIL_LR / _STEPS' fields read by meta_batch_anil_impl, theta_0's head derived per task from
+// the support prototypes with `scale` (proto_init.hip); lr_vec and step_w each null or not, dhyper_out [tasks] (d objective_t / d scale) or null.
+static bool is_anil(MetaAlgo a) { return a == ALGO_ANIL || a == ALGO_ANIL_LR || a == ALGO_ANIL_STEPS || a == ALGO_ANIL_PROTO; }
 static bool is_closed_form(MetaAlgo a) { return a == ALGO_METRIC || a == ALGO_RIDGE; }
 struct MetaCall {
   MetaAlgo algo;
@@ -1312,8 +1320,18 @@ static int check_call(mi_engine* e, const MetaCall& c) {
     if (!c.step_w) return fail(e, MI_ERR_ARG, "step_w is NULL: mi_meta_batch_anil_steps takes adapt_steps weights on the device");
     if (!c.lr_vec && c.lr_grad_out) return fail(e, MI_ERR_ARG, "mi_meta_batch_anil_steps: lr_grad_out given without lr_vec");
   }
-  if (c.algo == ALGO_ANIL_LR || c.algo == ALGO_ANIL_STEPS) {
-    const char* who = c.algo == ALGO_ANIL_LR ? "mi_meta_batch_anil_lr" : "mi_meta_batch_anil_steps";
+  if (c.algo == ALGO_ANIL_PROTO) {
+    const char* who = "mi_meta_batch_anil_proto";
+    if (!(c.scale > 0.f) || !std::isfinite(c.scale))
+      return fail(e, MI_ERR_ARG, std::string(who) + ": scale must be positive and finite, got " + std::to_string(c.scale));
+    if (c.dhyper_out && c.grad_tasks == 0)
+      return fail(e, MI_ERR_ARG, std::string(who) + ": dscale_out given but with_grad = 0: the scale's gradient comes with the meta-gradient");
+    if (c.step_w && c.adapt_steps < 1)
+      return fail(e, MI_ERR_ARG, std::string(who) + ": step_w needs adapt_steps >= 1, got " + std::to_string(c.adapt_steps) + ": its weights are those of theta_1 .. theta_K");
+    if (!c.lr_vec && c.lr_grad_out) return fail(e, MI_ERR_ARG, std::string(who) + ": lr_grad_out given without lr_vec");
+  }
+  if (c.algo == ALGO_ANIL_LR || c.algo == ALGO_ANIL_STEPS || c.algo == ALGO_ANIL_PROTO) {
+    const char* who = c.algo == ALGO_ANIL_LR ? "mi_meta_batch_anil_lr" : c.algo == ALGO_ANIL_STEPS ? "mi_meta_batch_anil_steps" : "mi_meta_batch_anil_proto";
     if (e->trace) return fail(e, MI_ERR_ARG, std::string("the debug trace does not cover ") + who);
     if (c.algo == ALGO_ANIL_LR && !c.lr_vec)
       return fail(e, MI_ERR_ARG, "lr_vec is NULL: mi_meta_batch_anil_lr takes lr_steps * (ways * fc + ways) step sizes on the device");
@@ -1328,6 +1346,7 @@ static int check_call(mi_engine* e, const MetaCall& c) {
       const int n = c.ways * c.shots;
       if (c.adapt_steps > 0 || c.grad_tasks > 0) HEAD_LDS(e, who, n, c.ways, 0);
       if (c.adapt_steps > 0 && c.grad_tasks > 0 && c.second_order) HEAD_LDS(e, who, n, c.ways, 1);
+      if (c.algo == ALGO_ANIL_PROTO && c.tasks >= 1 && !proto_init_fits(c.tasks, n, e->feat, c.ways)) return proto_init_size_fail(e, who, c.tasks, n, e->feat, c.ways);
     }
   }
   const bool ridge = c.algo == ALGO_RIDGE;
@@ -1613,13 +1632,12 @@ static void make_anil_ext(const mi_engine* e, void* ws, size_t plain_bytes, int 
   ax.bytes = align_up(b.off, 256);
 }
 
-// One workspace query for both entries.  lr_steps = 0: the scalar step (the steps call only); step_outputs: 0 = mi_meta_batch_anil_lr,
-// 1 = mi_meta_batch_anil_steps.
-extern "C" int mi_anil_workspace_bytes_steps(const mi_engine* e, int tasks, int ways, int shots, int adapt_steps, int with_grad, int second_order,
+// One workspace query for the three entries.  lr_steps = 0: the scalar step; step_outputs: 0 = the plain call's outputs, 1 = the per-step ones.
+// mi_meta_batch_anil_proto takes every combination; mi_meta_batch_anil_lr is (lr_steps > 0, 0), mi_meta_batch_anil_steps (any, 1).
+extern "C" int mi_anil_proto_workspace_bytes(const mi_engine* e, int tasks, int ways, int shots, int adapt_steps, int with_grad, int second_order,
                                              int lr_steps, int want_lr_grad, int step_outputs, size_t* bytes) {
   if (!e || !bytes || tasks < 1 || ways < 1 || shots < 1 || adapt_steps < 0 || lr_steps < 0) return MI_ERR_ARG;
   if (lr_steps != 0 && !lr_steps_ok(lr_steps, adapt_steps)) return MI_ERR_ARG;
-  if (lr_steps == 0 && !step_outputs) return MI_ERR_ARG;
   AnilPlan ap;
   make_anil_plan(e, nullptr, tasks, ways * shots, adapt_steps, ap);
   AnilExt ax;
@@ -1627,6 +1645,11 @@ extern "C" int mi_anil_workspace_bytes_steps(const mi_engine* e, int tasks, int 
                 step_outputs != 0, ax);
   *bytes = ax.bytes;
   return MI_OK;
+}
+extern "C" int mi_anil_workspace_bytes_steps(const mi_engine* e, int tasks, int ways, int shots, int adapt_steps, int with_grad, int second_order,
+                                             int lr_steps, int want_lr_grad, int step_outputs, size_t* bytes) {
+  if (lr_steps == 0 && !step_outputs) return MI_ERR_ARG;
+  return mi_anil_proto_workspace_bytes(e, tasks, ways, shots, adapt_steps, with_grad, second_order, lr_steps, want_lr_grad, step_outputs, bytes);
 }
 
 // c.lr_vec / c.step_w (mi_meta_batch_anil_lr / _steps; `ext` below), per task with D_k = diag(lr_k) or inner_lr * I:
@@ -1640,7 +1663,8 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const MetaCall& c) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int T = c.tasks, K = c.adapt_steps, n = c.ways * c.shots, nl = (int)e->L.size(), with_grad = c.grad_tasks > 0;
   const float inner_lr = c.inner_lr;
-  const bool ext = c.lr_vec || c.step_w, msl = c.step_w != nullptr, so = c.second_order && with_grad;
+  const bool proto = c.algo == ALGO_ANIL_PROTO;      // (always `ext`: the head-slice launches, whatever the step and the objective)
+  const bool ext = c.lr_vec || c.step_w || proto, msl = c.step_w != nullptr, so = c.second_order && with_grad;
   AnilPlan ap;
   make_anil_plan(e, c.workspace, T, n, K, ap);
   AnilExt ax{};
@@ -1666,6 +1690,13 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const MetaCall& c) {
   rc = export_bn_stats(e, st, ap.act, T);
   if (rc) return rc;
   LAUNCH(e, st, OP_MISC, 4, launch_split_rows(st, ap.act.p[nl - 1], T, 2 * n, e->feat, ap.fs, ap.fq));
+  // Proto-MAML: theta_0's head entries of every task from its support prototypes, over what the gather put there
+  ProtoInitArgs pa{};
+  pa.fs = ap.fs; pa.ys = ap.ys; pa.ns = n; pa.feat = e->feat; pa.ways = c.ways; pa.scale = c.scale; pa.stride = e->PS;
+  if (proto) {
+    pa.head = ap.theta + hbase;
+    LAUNCH(e, st, OP_PROTO_INIT, 0, launch_proto_init(st, pa, T));
+  }
   if (c.lr_vec) LAUNCH(e, st, OP_MISC, 1, launch_anil_gather_lr(st, c.lr_vec, hperm, hbase, Ph, (int)ax.hs, c.lr_steps, ax.lrh));
   if (msl && with_grad) HIPCHK(e, hipMemsetAsync(ap.dfq, 0, fsz * sizeof(float), st));
   // The steps call: the query set at theta_j with the launch of the final query pass (row j of the outputs; prob / dl in the final pass's
@@ -1743,10 +1774,19 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const MetaCall& c) {
       LAUNCH(e, st, OP_MISC, 2, launch_axpy(st, ap.lam, ap.hv, inner_lr, TP, ap.lam));     // lam -= lr * H lam
     }
   }
+  // Proto-MAML: lam's head entries are lam_0 = d objective / d theta_0's head; through the initialisation they reach the support features
+  // (on top of the loop's own df_s) and the scale
+  if (proto) {
+    pa.lam = ap.lam + hbase; pa.dfs = ap.dfs; pa.dscale = c.dhyper_out;
+    LAUNCH(e, st, OP_PROTO_INIT, 1, launch_proto_init_bwd(st, pa, T));
+  }
   LAUNCH(e, st, OP_MISC, 4, launch_interleave_rows(st, ap.dfs, ap.dfq, T, n, e->feat, ap.act.dp[nl - 1]));
   rc = trunk_backward(e, st, ap.scratch, ap.act, ap.x, 2 * n, T, ap.theta, ap.lam, gram);  // trunk grads join the head part in lam
   if (rc) return rc;
   LAUNCH(e, st, OP_MISC, 3, launch_scatter_sum(st, ap.lam, e->perm_dev, (int)e->P, (int)e->PS, T, c.meta_grad_out));
+  // Proto-MAML: the learner's head enters no result.  Its entries of the gradient (the last Ph in reference order) are exact zeros; lam
+  // itself keeps lam_0, which the first-order fold below still reads
+  if (proto) HIPCHK(e, hipMemsetAsync(c.meta_grad_out + (e->P - Ph), 0, (size_t)Ph * sizeof(float), st));
   // lr_grad in head.parameters() order: the stored products, or (first order, final loss only) g_k times the one constant lam, whose head
   // entries the trunk backward has left as they were
   if (c.lr_vec && c.lr_grad_out)
@@ -1957,6 +1997,19 @@ extern "C" int mi_meta_batch_anil_steps(mi_engine* e, void* stream, const float*
              lr_vec, lr_vec ? lr_steps : 0, lr_grad_out, loss_steps_out, acc_steps_out, meta_grad_out, logits_steps_out, workspace,
              workspace_bytes};
   c.step_w = step_w;
+  return meta_batch_entry(e, stream, c);
+}
+
+// mi_meta_batch_anil_lr / _steps with theta_0's head derived per task from the support prototypes (Proto-MAML; include/mi_maml.h).
+extern "C" int mi_meta_batch_anil_proto(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels, int tasks,
+                                        int ways, int shots, int adapt_steps, int second_order, float inner_lr, const float* lr_vec, int lr_steps,
+                                        const float* step_w, float scale, int with_grad, float* loss_out, float* acc_out, float* meta_grad_out,
+                                        float* lr_grad_out, float* dscale_out, float* logits_out, void* workspace, size_t workspace_bytes) {
+  MetaCall c{ALGO_ANIL_PROTO, theta, data, labels, tasks, with_grad ? tasks : 0, ways, shots, adapt_steps, second_order, lr_vec ? 0.f : inner_lr,
+             lr_vec, lr_vec ? lr_steps : 0, lr_grad_out, loss_out, acc_out, meta_grad_out, logits_out, workspace, workspace_bytes};
+  c.step_w = step_w;
+  c.scale = scale;
+  c.dhyper_out = dscale_out;
   return meta_batch_entry(e, stream, c);
 }
 
@@ -2358,6 +2411,36 @@ extern "C" int mi_ridge_head(void* stream, const float* fs, const float* fq, con
   if (const int rc = closed_form_entry_check("mi_ridge_head", true, ra, tasks, [&] { return ridge_hyper_check(nullptr, "mi_ridge_head", lam, alpha); }))
     return rc;
   HIPCHK0(launch_ridge_head(reinterpret_cast<hipStream_t>(stream), ra, tasks));
+  return MI_OK;
+}
+
+// launch_proto_init / launch_proto_init_bwd: the Proto-MAML initialisation's kernel entries (include/mi_maml.h).
+static int proto_init_entry_check(const char* who, const ProtoInitArgs& a, int tasks) {
+  if (!proto_init_fits(tasks, a.ns, a.feat, a.ways)) return proto_init_size_fail(nullptr, who, tasks, a.ns, a.feat, a.ways);
+  if (!(a.scale > 0.f) || !std::isfinite(a.scale))
+    return fail(nullptr, MI_ERR_ARG, std::string(who) + ": scale must be positive and finite, got " + std::to_string(a.scale));
+  if (a.stride < (size_t)a.ways * a.feat + a.ways)
+    return fail(nullptr, MI_ERR_ARG, std::string(who) + ": the stride between the tasks' heads, " + std::to_string(a.stride) + ", is below ways * feat + ways = " +
+                                         std::to_string((size_t)a.ways * a.feat + a.ways));
+  return MI_OK;
+}
+extern "C" int mi_proto_init(void* stream, const float* fs, const int32_t* ys, int tasks, int ns, int feat, int ways, float scale,
+                             float* head_out, size_t head_stride) {
+  if (!fs || !ys || !head_out) return fail(nullptr, MI_ERR_ARG, "mi_proto_init: null pointer argument");
+  ProtoInitArgs a{};
+  a.fs = fs; a.ys = ys; a.ns = ns; a.feat = feat; a.ways = ways; a.scale = scale; a.stride = head_stride; a.head = head_out;
+  if (const int rc = proto_init_entry_check("mi_proto_init", a, tasks)) return rc;
+  HIPCHK0(launch_proto_init(reinterpret_cast<hipStream_t>(stream), a, tasks));
+  return MI_OK;
+}
+extern "C" int mi_proto_init_bwd(void* stream, const float* fs, const int32_t* ys, const float* lam_head, size_t lam_stride, int tasks, int ns,
+                                 int feat, int ways, float scale, float* dfs, float* dscale) {
+  if (!fs || !ys || !lam_head || !dfs) return fail(nullptr, MI_ERR_ARG, "mi_proto_init_bwd: null pointer argument");
+  ProtoInitArgs a{};
+  a.fs = fs; a.ys = ys; a.ns = ns; a.feat = feat; a.ways = ways; a.scale = scale; a.stride = lam_stride; a.lam = lam_head; a.dfs = dfs;
+  a.dscale = dscale;
+  if (const int rc = proto_init_entry_check("mi_proto_init_bwd", a, tasks)) return rc;
+  HIPCHK0(launch_proto_init_bwd(reinterpret_cast<hipStream_t>(stream), a, tasks));
   return MI_OK;
 }
 

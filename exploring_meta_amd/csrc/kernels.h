@@ -297,6 +297,23 @@ size_t ridge_head_lds_bytes(int ns, int nq, int ways);
 bool ridge_head_fits(int ns, int nq, int feat, int ways);
 hipError_t launch_ridge_head(hipStream_t st, const RidgeArgs& a, int tasks);
 
+// proto_init.hip: the Proto-MAML head initialisation (W_0, b_0) = (2 s c, -s |c|^2) from the support prototypes, and its backward
+struct ProtoInitArgs {
+  const float* fs; const int32_t* ys;    // [T][ns][F], [T][ns] in [0, ways) (every class has a support row)
+  int ns, feat, ways;
+  float scale;                           // > 0 and finite
+  size_t stride;                         // floats between the tasks' heads in `head` / `lam`
+  float* head;                           // forward: [W_0 | b_0] (ways * F + ways floats) per task
+  const float* lam;                      // backward: d objective / d [W_0 | b_0], laid out as `head`
+  float* dfs;                            // backward: [T][ns][F], accumulated into
+  float* dscale;                         // backward: [T] (may be null)
+};
+// Outside the domain the launchers return hipErrorInvalidValue before launching anything -- callers check proto_init_fits (and the scale)
+// first and report MI_ERR_ARG.
+bool proto_init_fits(int tasks, int ns, int feat, int ways);
+hipError_t launch_proto_init(hipStream_t st, const ProtoInitArgs& a, int tasks);
+hipError_t launch_proto_init_bwd(hipStream_t st, const ProtoInitArgs& a, int tasks);
+
 // tail.hip: the last ConvBlock's BatchNorm + ReLU + MaxPool, the head, the head's backward and that block's BatchNorm-backward SUMS (or their
 // tangents) in one launch, four workgroups (row groups) per task; cross-workgroup sums by the last arriver (finalize.h protocol).
 struct TailArgs {

@@ -477,12 +477,14 @@ class MetaEngine:
         (_, ws), (_, bs) = self.spec.param_shapes()[-2:]
         return ws[0] * ws[1] + bs[0]
 
-    def _anil_call(self, theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, step_w, first_order, with_grad, want_lr_grad, return_logits):
+    def _anil_call(self, theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, step_w, first_order, with_grad, want_lr_grad, return_logits,
+                   proto_scale=None):
         """mi_meta_batch_anil_lr (step_w None) or mi_meta_batch_anil_steps (loss, acc and logits then carry a leading axis of
-        adapt_steps + 1).  Returns (loss, acc, grad, lr_grad, logits)."""
+        adapt_steps + 1).  Returns (loss, acc, grad, lr_grad, logits).  proto_scale: mi_meta_batch_anil_proto with that scale (scalar or
+        vector step, with or without step_w); the per-task scale gradient [T] (None without a gradient) then comes before logits."""
         s, K, Ph = self.spec, int(adapt_steps), self.head_param_count()
         T = self._check_batch(theta, data, labels, shots, flat_data=False)
-        steps = step_w is not None
+        steps, proto = step_w is not None, proto_scale is not None
 
         def refuse(name, t, shape_text, ok_shape):
             # the library sizes its reads of lr_vec / step_w from the call's integers: anything else is refused here, before any launch
@@ -504,7 +506,7 @@ class MetaEngine:
         so = (not first_order) and with_grad
         want_lr_grad = bool(want_lr_grad) and lr_vec is not None and bool(with_grad)
         b = C.c_size_t()
-        _lib.check(self.lib.mi_anil_workspace_bytes_steps(self._h, T, s.ways, shots, K, int(bool(with_grad)), int(so), lr_steps,
+        _lib.check((self.lib.mi_anil_proto_workspace_bytes if proto else self.lib.mi_anil_workspace_bytes_steps)(self._h, T, s.ways, shots, K, int(bool(with_grad)), int(so), lr_steps,
                                                           int(want_lr_grad), int(steps), C.byref(b)), self._h)
         ws = self._workspace(b.value)
         nlog = shots * s.ways
@@ -513,14 +515,21 @@ class MetaEngine:
                 return (torch.empty(K + 1, T, dtype=torch.float32, device=self.device), torch.empty(K + 1, T, dtype=torch.float32, device=self.device),
                         torch.empty(self.param_count, dtype=torch.float32, device=self.device) if with_grad else None,
                         torch.empty(K + 1, T, nlog, s.ways, dtype=torch.float32, device=self.device) if return_logits else None)
-            loss, acc, grad, logits = self._persistent(('anil_steps', lr_vec is None, K + 1, T, nlog, bool(with_grad), bool(return_logits)), fresh)
+            loss, acc, grad, logits = self._persistent(('anil_steps', proto, lr_vec is None, K + 1, T, nlog, bool(with_grad), bool(return_logits)), fresh)
         else:
-            loss, acc, grad, logits = self._outputs('anil_lr', T, nlog, with_grad, return_logits)
+            loss, acc, grad, logits = self._outputs('anil_proto' if proto else 'anil_lr', T, nlog, with_grad, return_logits)
         lr_grad = None
         if want_lr_grad:
-            lr_grad = self._persistent(('anil_lr_grad', steps, T, lr_steps), lambda: torch.empty(lr_steps, Ph, dtype=torch.float32, device=self.device))
+            lr_grad = self._persistent(('anil_lr_grad', proto, steps, T, lr_steps), lambda: torch.empty(lr_steps, Ph, dtype=torch.float32, device=self.device))
         head = (_ptr(theta), _ptr(data), _ptr(labels), T, s.ways, shots, K)
         tail = (_ptr(loss), _ptr(acc), _ptr(grad), _ptr(lr_grad), _ptr(logits), _ptr(ws), ws.numel())
+        if proto:
+            dscale = self._persistent(('anil_proto_dscale', steps, T), lambda: torch.empty(T, dtype=torch.float32, device=self.device)) if with_grad else None
+            rc = self._fused_call(self.lib.mi_meta_batch_anil_proto, *head, int(not first_order), float(inner_lr) if lr_vec is None else 0.0,
+                                  _ptr(lr_vec), lr_steps, _ptr(step_w), proto_scale, int(bool(with_grad)), _ptr(loss), _ptr(acc), _ptr(grad),
+                                  _ptr(lr_grad), _ptr(dscale), _ptr(logits), _ptr(ws), ws.numel())
+            _lib.check(rc, self._h)
+            return loss, acc, grad, lr_grad, dscale, logits
         if steps:
             rc = self._fused_call(self.lib.mi_meta_batch_anil_steps, *head, float(inner_lr) if lr_vec is None else 0.0, _ptr(lr_vec), lr_steps,
                                   _ptr(step_w), int(not first_order), int(bool(with_grad)), *tail)
@@ -554,6 +563,56 @@ class MetaEngine:
             raise _lib.MiError('libmi_maml error -1: step_w is None: meta_batch_anil_steps takes adapt_steps weights on the device')
         return self._anil_call(theta, data, labels, shots, adapt_steps, inner_lr, lr_vec, step_w, first_order, with_grad, want_lr_grad,
                                return_logits)
+
+    @_on_device
+    def meta_batch_anil_proto(self, theta, data, labels, shots, adapt_steps, scale, inner_lr=None, lr_vec=None, step_w=None, first_order=False,
+                              with_grad=True, want_lr_grad=False, return_logits=False):
+        """Proto-MAML on the ANIL trunk (mi_meta_batch_anil_proto): `meta_batch_anil_lr` / `meta_batch_anil_steps` with the head's
+        initialisation derived per task from the support prototypes, W_0[w] = 2 scale c_w, b_0[w] = -scale |c_w|^2, and differentiated
+        through.  adapt_steps = 0 (without step_w) is Prototypical Networks; with step_w, row 0 of the outputs is its score.  The head's
+        entries of theta are not used and their gradient is exactly zero.  Exactly one of inner_lr and lr_vec (adapt_steps = 0: neither is
+        fine).  Returns (loss, acc, meta_grad[P] or None, lr_grad or None, dscale [T] or None, logits or None), loss / acc / logits with a
+        leading axis of adapt_steps + 1 when step_w is given; dscale[t] = d objective_t / d scale, per task: the sum is the caller's."""
+        scale = float(scale)
+        if not (scale > 0.0 and math.isfinite(scale)):
+            raise _lib.MiError(f'libmi_maml error -1: the prototype initialisation\'s scale must be positive and finite, got {scale}')
+        if inner_lr is not None and lr_vec is not None or (inner_lr is None and lr_vec is None and int(adapt_steps) > 0):
+            raise ValueError('meta_batch_anil_proto takes exactly one of inner_lr and lr_vec')
+        return self._anil_call(theta, data, labels, shots, adapt_steps, 0.0 if inner_lr is None else inner_lr, lr_vec, step_w, first_order,
+                               with_grad, want_lr_grad, return_logits, proto_scale=scale)
+
+    @_on_device
+    def proto_init(self, fs, ys, ways, scale):
+        """The prototype initialisation's kernel entry (mi_proto_init) on given support features: fs [T, ns, F] fp32, ys [T, ns] int32 in
+        [0, ways), every class with at least one support row.  Returns [T, ways * F + ways]: per task W_0 [ways, F], then b_0 [ways]."""
+        T, ns, feat = self._proto_check(fs, ys)
+        head = torch.empty(T, int(ways) * feat + int(ways), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.mi_proto_init(_stream(self.device), _ptr(fs), _ptr(ys), T, ns, feat, int(ways), float(scale), _ptr(head), head.shape[1]), None)
+        return head
+
+    @_on_device
+    def proto_init_bwd(self, fs, ys, lam_head, ways, scale, dfs=None, want_dscale=True):
+        """mi_proto_init_bwd: lam_head [T, ways * F + ways] = d objective / d (W_0, b_0) as `proto_init` lays them out.  Adds the gradient
+        through the initialisation INTO dfs [T, ns, F] (zeros when None) and returns (dfs, dscale [T] or None)."""
+        T, ns, feat = self._proto_check(fs, ys)
+        ph = int(ways) * feat + int(ways)
+        if lam_head.dtype != torch.float32 or not lam_head.is_cuda or not lam_head.is_contiguous() or tuple(lam_head.shape) != (T, ph):
+            raise ValueError(f'lam_head must be a contiguous fp32 CUDA tensor of shape {(T, ph)}, got {tuple(lam_head.shape)}')
+        if dfs is None:
+            dfs = torch.zeros_like(fs)
+        elif dfs.dtype != torch.float32 or not dfs.is_cuda or not dfs.is_contiguous() or dfs.shape != fs.shape:
+            raise ValueError('dfs must be a contiguous fp32 CUDA tensor of fs\'s shape')
+        dscale = torch.empty(T, dtype=torch.float32, device=self.device) if want_dscale else None
+        _lib.check(self.lib.mi_proto_init_bwd(_stream(self.device), _ptr(fs), _ptr(ys), _ptr(lam_head), ph, T, ns, feat, int(ways), float(scale),
+                                              _ptr(dfs), _ptr(dscale)), None)
+        return dfs, dscale
+
+    @staticmethod
+    def _proto_check(fs, ys):
+        if fs.dtype != torch.float32 or ys.dtype != torch.int32 or not (fs.is_cuda and ys.is_cuda) or not (fs.is_contiguous() and ys.is_contiguous()) \
+                or fs.dim() != 3 or tuple(ys.shape) != tuple(fs.shape[:2]):
+            raise ValueError(f'fs [T, ns, F] contiguous fp32 CUDA, ys [T, ns] contiguous int32 CUDA; got {tuple(fs.shape)}, {tuple(ys.shape)}')
+        return tuple(fs.shape)
 
     def _closed_form_call(self, name, key, theta, data, labels, shots, hyper, with_grad, return_logits, n_hyper=0):
         """mi_meta_batch_<name>, the fused call of a closed-form head with the hyper-parameters `hyper`.  `key`: the outputs' persistent set in

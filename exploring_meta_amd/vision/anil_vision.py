@@ -9,6 +9,10 @@ trunk and head), task-sharded over ranks under ``torchrun`` with one RCCL all-re
 generator (datasets are not available offline).
 
     python -m exploring_meta_amd.vision.anil_vision --dataset min --shots 5 --adapt_steps 1 --num_iterations 10
+
+``--proto_init`` (Proto-MAML, ``core_functions/proto_anil.py``): the head's inner loop starts, per task, from the support prototypes instead
+of from the learned ``head``; ``log_scale`` is optimised beside trunk and step sizes (``--fix_proto_scale``: it stays at
+``--proto_scale``), ``proto_init.pt`` is saved beside ``head.pt``, and the driver returns ``(features, head, init)``.
 """
 import argparse
 import os
@@ -17,6 +21,7 @@ import torch
 
 from ..core_functions import MAML, ConvBase, InnerLR, msl_weights
 from ..core_functions.anil import meta_batch_adapt_anil, meta_batch_adapt_anil_steps
+from ..core_functions.proto_anil import ProtoInit, meta_batch_adapt_proto_anil
 from .maml_vision import add_trunk_test_flags, inner_lr_of, trunk_test_params, trunk_tests
 from .trunk_loop import train_trunk
 
@@ -58,15 +63,25 @@ def run(dataset, p, log=print):
         features, head = build(dataset, p['ways'], p['inner_lr'], device, p)
         msl_its = int(p.get('msl_iterations', 0)) if p.get('multi_step_loss') and p['adapt_steps'] >= 1 else 0
         step_w = torch.zeros(max(p['adapt_steps'], 1), device=device)      # annealed in place: the engine reads the weights on the device
+        init = ProtoInit(p.get('proto_scale', 1.0), learnable=not p.get('fix_proto_scale')).to(device) if p.get('proto_init') else None
+
+        def plain(data, labels):
+            if init is None:
+                return meta_batch_adapt_anil(head.clone(), features, data, labels, p['adapt_steps'], p['shots'], p['ways'])
+            return meta_batch_adapt_proto_anil(head.clone(), features, init, data, labels, p['adapt_steps'], p['shots'], p['ways'])
 
         def adapt(it, data, labels):
             """One fused call: the multi-step loss while it < --msl_iterations (--multi_step_loss), else the plain call.  The logged loss and
             accuracy are those of the last step either way."""
             if it >= msl_its or not torch.is_grad_enabled():
-                return meta_batch_adapt_anil(head.clone(), features, data, labels, p['adapt_steps'], p['shots'], p['ways'])
+                return plain(data, labels)
             step_w.copy_(torch.tensor(msl_weights(p['adapt_steps'], it, msl_its)))
-            total, losses, accs = meta_batch_adapt_anil_steps(head.clone(), features, data, labels, p['adapt_steps'], p['shots'], p['ways'],
-                                                              step_weights=step_w)
+            if init is None:
+                total, losses, accs = meta_batch_adapt_anil_steps(head.clone(), features, data, labels, p['adapt_steps'], p['shots'], p['ways'],
+                                                                  step_weights=step_w)
+            else:
+                total, losses, accs = meta_batch_adapt_proto_anil(head.clone(), features, init, data, labels, p['adapt_steps'], p['shots'],
+                                                                  p['ways'], step_weights=step_w)
             return total, losses[-1], accs[-1]
 
         def after(metrics, test_tasks, rank, save_final):
@@ -77,9 +92,13 @@ def run(dataset, p, log=print):
 
         # anil_vision.py:97; head.parameters() includes a learnable InnerLR's values (a submodule of MAML), so they are stepped by the
         # optimiser and all-reduced with the rest
-        return dict(features=features, parameters=list(features.parameters()) + list(head.parameters()), train=adapt,
-                    valid=lambda d, l: meta_batch_adapt_anil(head.clone(), features, d, l, p['adapt_steps'], p['shots'], p['ways']),
-                    checkpoints={'features': features, 'head': head}, after=after, result=(features, head))
+        s = dict(features=features, parameters=list(features.parameters()) + list(head.parameters()), train=adapt, valid=plain,
+                 checkpoints={'features': features, 'head': head}, after=after, result=(features, head))
+        if init is not None:             # log_scale beside trunk and step sizes; the head's weight and bias receive zeros and stay
+            s['parameters'] += list(init.parameters())
+            s['checkpoints']['proto_init'] = init
+            s.update(extra_metrics=lambda: {'proto_scale': init.scale}, result=(features, head, init))
+        return s
 
     return train_trunk(dataset, p, log, setup)
 
@@ -99,6 +118,10 @@ def build_parser():
                         help='MAML++ multi-step loss: the outer objective weights the query loss after every head step (msl_weights)')
     parser.add_argument('--msl_iterations', type=int, default=0, metavar='N',
                         help='iterations over which the multi-step weights anneal to the final step; from iteration N on the plain call runs')
+    parser.add_argument('--proto_init', action='store_true',
+                        help="Proto-MAML: the head's inner loop starts from the task's support prototypes (W_0 = 2 s c, b_0 = -s |c|^2), not from the learned head")
+    parser.add_argument('--proto_scale', type=float, default=1.0, metavar='S', help='the initial scale s of --proto_init')
+    parser.add_argument('--fix_proto_scale', action='store_true', help='s stays at --proto_scale (not meta-learned)')
     add_trunk_test_flags(parser, 'after training')
     return parser
 
@@ -111,12 +134,13 @@ def params_of(args):
     """The run's parameter dict from parsed flags (the defaults are the reference's run)."""
     p = {k: getattr(args, k) for k in params}
     p.update(save_dir=args.save_dir, inner_lr_per=args.inner_lr_per, learn_inner_lr=args.learn_inner_lr, per_step_lr=args.per_step_lr,
-             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations, **trunk_test_params(args))
+             freeze=list(args.freeze), multi_step_loss=args.multi_step_loss, msl_iterations=args.msl_iterations, proto_init=args.proto_init,
+             proto_scale=args.proto_scale, fix_proto_scale=args.fix_proto_scale, **trunk_test_params(args))
     return p
 
 
 def main(argv=None, log=print):
-    """Parse the flags and run; returns ((features, head), metrics of the last iteration)."""
+    """Parse the flags and run; returns ((features, head), metrics of the last iteration); with --proto_init (features, head, init)."""
     args = parse_args(argv)
     p = dict(params)
     p.update(params_of(args))

@@ -364,6 +364,54 @@ int mi_meta_batch_ridge(mi_engine* e, void* stream, const float* theta, const fl
                         float* loss_out, float* acc_out, float* meta_grad_out, float* dhyper_out /*nullable*/, float* logits_out /*nullable*/,
                         void* workspace, size_t workspace_bytes);
 
+/* Proto-MAML head initialisation (Triantafillou et al., "Meta-Dataset", eq. 8; csrc/proto_init.hip): the linear head
+ * whose logits are the Prototypical-Networks logits up to a per-row constant, derived per task from the support features, and its
+ * backward.  Per task, N_w = #{i : ys_i = w}; THE CONTRACT IS N_w >= 1 FOR EVERY CLASS and labels in [0, ways), as for mi_metric_head (a
+ * class without a support row gets W_0 = 0, b_0 = 0 and no gradient: never a fault, but not the definition):
+ *   c_w = (1/N_w) sum_{i in w} fs_i,   W_0[w] = 2 scale c_w,   b_0[w] = -scale |c_w|^2
+ *   2 scale <q, c_w> - scale |c_w|^2 = -scale |q - c_w|^2 + scale |q|^2
+ * mi_proto_init: fs [tasks, ns, feat] fp32, ys [tasks, ns] int32; writes [W_0 (ways x feat, row w = class w) | b_0 (ways)] of task t at
+ * head_out + t * head_stride (floats; head_stride >= ways * feat + ways).
+ * mi_proto_init_bwd: lam_head, laid out like head_out at lam_stride, holds d objective / d (W_0, b_0) = (lamW, lamb);
+ *   dc_w = 2 scale (lamW[w] - lamb[w] c_w),   dfs_i += dc_{ys_i} / N_{ys_i},   dscale[t] = sum_w (2 <lamW[w], c_w> - lamb[w] |c_w|^2)
+ * dfs [tasks, ns, feat] is ACCUMULATED INTO (every element read, modified and written by the one thread that owns it); dscale [tasks] may be
+ * NULL, which changes no other output.  It is per task, so that the sum over tasks is the caller's and stays deterministic.  c_w is
+ * recomputed by the forward's code in the forward's order (nothing is kept between the two launches).
+ * ONE launch each whatever `tasks`; a task's bits do not depend on `tasks`, on the workgroup that ran it, or on the alignment of the
+ * pointers (16-byte accesses when feat % 4 == 0, the strides are multiples of 4 and the bases 16-byte aligned; words otherwise, same bits).
+ * fp32 arithmetic on the elements; |c_w|^2 and dscale, the two sums over feat, are accumulated in fp64 in a fixed order and rounded once.
+ * No float atomics.  The domain (MI_ERR_ARG naming the sizes before any launch otherwise, the outputs untouched): tasks, ns, feat >= 1,
+ * feat <= MI_RIDGE_MAX_FEAT, 1 <= ways <= 64, scale > 0 and finite. */
+int mi_proto_init(void* stream, const float* fs, const int32_t* ys, int tasks, int ns, int feat, int ways, float scale,
+                  float* head_out, size_t head_stride);
+int mi_proto_init_bwd(void* stream, const float* fs, const int32_t* ys, const float* lam_head, size_t lam_stride,
+                      int tasks, int ns, int feat, int ways, float scale, float* dfs /*accumulated into*/, float* dscale /*[tasks], nullable*/);
+/* Proto-MAML on the ANIL trunk: mi_meta_batch_anil_lr / _steps with theta_0's head of every task derived from its support prototypes by
+ * mi_proto_init's kernel, and differentiated through -- the inner loop, the adjoint recursion, the step sizes and the multi-step loss are
+ * those calls', with two launches added: the initialisation after the split of the features, and (with_grad) its backward between the
+ * adjoint recursion and the interleave, which adds dfs through theta_0 on top of the loop's own and writes dscale_out.
+ *   theta_0^head = (2 s c, -s |c|^2);  theta_{k+1} = theta_k - D_k g_k;  objective = L_q(theta_K), or sum_j step_w[j-1] L_q(theta_j)
+ *   lam_0 = d objective / d theta_0^head (what the adjoint recursion leaves);  first order keeps theta_0's dependence on fs: lam_0 = sum_j
+ *   w_j q_j, only the g_k are constants.
+ * Every combination is one entry: lr_vec NULL = the scalar step inner_lr, else [lr_steps, Ph] as in mi_meta_batch_anil_lr (lr_grad_out
+ * likewise); step_w NULL = the plain outputs loss_out / acc_out [tasks], logits_out [tasks, ways * shots, ways]; step_w [adapt_steps] = the
+ * per-step outputs [adapt_steps + 1, tasks(, ..)] of mi_meta_batch_anil_steps, row 0 being the Prototypical-Networks score of the query
+ * set.  adapt_steps = 0 without step_w is Prototypical Networks (loss, accuracy and trunk gradient of mi_meta_batch_metric(MI_METRIC_PROTO,
+ * scale) up to rounding; the logits differ by scale |q|^2 per row).  The head's entries of theta enter no result; the head's entries of
+ * meta_grad_out are written as exact zeros.  dscale_out [tasks] or NULL: d objective_t / d scale, written only with a gradient.  The bits
+ * of scale are part of the graph's signature.  The profile shows the launches as proto_init/0 and proto_init/1.  MI_ERR_ARG before any
+ * launch: scale not > 0 or not finite, dscale_out with with_grad == 0, step_w with adapt_steps < 1, a debug trace being set, sizes outside
+ * mi_proto_init's domain, and what mi_meta_batch_anil_steps refuses.  Workspace: mi_anil_proto_workspace_bytes, the arguments of
+ * mi_anil_workspace_bytes_steps (lr_steps = 0 with step_outputs = 0 is legal here). */
+int mi_anil_proto_workspace_bytes(const mi_engine* e, int tasks, int ways, int shots, int adapt_steps, int with_grad, int second_order,
+                                  int lr_steps, int want_lr_grad, int step_outputs, size_t* bytes);
+int mi_meta_batch_anil_proto(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
+                             int tasks, int ways, int shots, int adapt_steps, int second_order,
+                             float inner_lr, const float* lr_vec /*nullable*/, int lr_steps, const float* step_w /*nullable*/,
+                             float scale, int with_grad,
+                             float* loss_out, float* acc_out, float* meta_grad_out, float* lr_grad_out /*nullable*/,
+                             float* dscale_out /*[tasks], nullable*/, float* logits_out /*nullable*/, void* workspace, size_t workspace_bytes);
+
 /* Plain classifier forward, no adaptation: `learner(x)` / `model(x)` (vision_models.py:51-55,107-110), BatchNorm in train
  * mode over the n images of each of the `tasks` batches.  x [tasks, n, C, H, W] NCHW; logits_out [tasks, n, ways]. */
 int mi_forward_workspace_bytes(const mi_engine* e, int tasks, int n, size_t* bytes);

@@ -1,0 +1,149 @@
+"""Host tests of the Proto-MAML head initialisation: the formulas the kernels implement against fp64 autograd, the
+K = 0 case against the Prototypical-Networks head of tests/metric_head_oracle.py, the init path under first order, the two conditions the
+GPU test's cases rest on (loss range, clear accuracy margins), the C symbols, the driver's flags and the Python surface."""
+import functools
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import vision_ref as R
+from gpu_utils import REPO
+import closed_form_utils as U
+import metric_head_oracle as M
+import proto_init_oracle as P
+
+SYMBOLS = ('mi_proto_init', 'mi_proto_init_bwd', 'mi_anil_proto_workspace_bytes', 'mi_meta_batch_anil_proto')
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(case):
+    return P.case_oracle(case)
+
+
+# (feat, ways, ns, T): KERNEL_CASES' small ones -- class counts (1, 2, 3), one class, feat = 1 among them
+@pytest.mark.parametrize('feat,ways,ns,T', [(1, 5, 5, 1), (33, 5, 5, 1), (128, 5, 5, 3), (128, 1, 3, 1), (128, 3, 6, 1), (8, 64, 64, 1)])
+def test_formulas_equal_fp64_autograd(feat, ways, ns, T):
+    fs, ys, lam, dfs0 = P.kernel_inputs(feat, ways, ns, T)
+    if (ways, ns) == (3, 6):
+        assert np.bincount(ys[0]).tolist() == [1, 2, 3]
+    scale = 1.0 / feat
+    head, dfs, dscale = P.init_autograd(fs, ys, lam, ways, scale)
+    got_dfs, got_dscale = P.init_bwd(fs, ys, lam, ways, scale, dfs0)
+    assert P.rel_err(P.init(fs, ys, ways, scale), head) < 1e-10
+    assert P.rel_err(got_dfs, dfs0.astype(np.float64) + dfs) < 1e-10 and P.rel_err(got_dscale, dscale) < 1e-10
+    assert np.abs(dfs).sum() > 0 and np.abs(dscale).sum() > 0
+
+
+def _k0(fs, fq, ys, yq, ways, scale):
+    """The linear head at theta_0 on given features, by autograd: (loss [T], acc [T], logits, dfs, dfq) as metric_head_oracle.head."""
+    fs = torch.as_tensor(fs).double().requires_grad_(True)
+    fq = torch.as_tensor(fq).double().requires_grad_(True)
+    ys, yq = torch.as_tensor(ys).long(), torch.as_tensor(yq).long()
+    losses, accs, logits = [], [], []
+    for t in range(fs.shape[0]):
+        w0, b0 = P.head_init(fs[t], ys[t], ways, scale)
+        z = fq[t] @ w0.t() + b0
+        losses.append(F.cross_entropy(z, yq[t]))
+        accs.append(float(R.accuracy(z, yq[t])))
+        logits.append(z.detach())
+    torch.stack(losses).sum().backward()
+    return torch.stack(losses).detach().numpy(), np.asarray(accs), torch.stack(logits).numpy(), fs.grad.numpy(), fq.grad.numpy()
+
+
+@pytest.mark.parametrize('feat,ways,ns,nq,T', [(33, 5, 5, 5, 1), (128, 5, 5, 5, 3), (128, 3, 6, 4, 1)])
+def test_no_inner_step_is_prototypical_networks(feat, ways, ns, nq, T):
+    """2 s <q, c_w> - s |c_w|^2 = -s |q - c_w|^2 + s |q|^2: loss, accuracy and both feature gradients are the metric head's; the logits
+    after the per-row constant is taken off."""
+    fs, fq, ys, yq = M.kernel_inputs(feat, ways, ns, nq, T)
+    s = 1.0 / feat
+    loss, acc, logits, dfs, dfq = _k0(fs, fq, ys, yq, ways, s)
+    want = M.head(fs, fq, ys, yq, ways, M.PROTO, s)
+    for got, ref in ((loss, want[0]), (dfs, want[3]), (dfq, want[4]), (logits - s * (fq.astype(np.float64) ** 2).sum(axis=-1)[..., None], want[2])):
+        assert P.rel_err(got, ref) < 1e-9
+    assert np.array_equal(acc, want[1]) and np.all(want[0] > 1e-3)
+
+
+def test_fused_oracle_at_no_inner_step_is_the_metric_oracle():
+    shape = 'omni'
+    ids, scale, _ = P.CASES[shape]
+    base, tf, _, fc, ways, shots = P.fixtures(shape)
+    datas, labels = P.tasks(shape, list(ids))
+    want = M.meta_batch(tf, base, fc, datas, labels, shots, ways, M.PROTO, scale)
+    got = _oracle('omni_K0')
+    assert P.rel_err(got['losses'][0], want['losses']) < 1e-9 and P.rel_err(got['grad_feat'], want['grad_feat']) < 1e-9
+    assert np.array_equal(got['accs'][0], want['accs'])
+
+
+def test_first_order_keeps_the_init_path():
+    """First order treats the g_k as constants, not theta_0: the trunk gradient differs from the one with theta_0 detached, and the scale
+    keeps a gradient."""
+    case = 'omni_K2_fo_vector'
+    shape, _, K, _, fo, w = P.FUSED[case]
+    assert fo
+    base, tf, _, fc, ways, shots = P.fixtures(shape)
+    datas, labels = P.tasks(shape, P.case_ids(case))
+    cut = P.meta_batch(tf, base, fc, datas, labels, K, shots, ways, P.CASES[shape][1], P.case_lr(case), w, True, detach_init=True)
+    kept = _oracle(case)
+    assert np.array_equal(cut['losses'], kept['losses'])
+    assert P.rel_err(cut['grad_feat'], kept['grad_feat']) > 0.1 and cut['dscale'] == 0.0 and abs(kept['dscale']) > 1e-3
+    # and second order differs from first order through the loop
+    so = P.meta_batch(tf, base, fc, datas, labels, K, shots, ways, P.CASES[shape][1], P.case_lr(case), w, False)
+    assert P.rel_err(so['grad_feat'], kept['grad_feat']) > 1e-3
+
+
+@pytest.mark.parametrize('case', list(P.FUSED))
+def test_fused_cases_meet_the_conditions_the_gpu_test_rests_on(case):
+    """At every step and task the fp64 loss lies in [0.05, 3] (a relative loss bar means something), and at most one query row in ten of
+    any (step, task) is under clear_rows' margin (accuracy is compared on the clear rows).  Inside the loop the loss moves."""
+    o = _oracle(case)
+    K = P.FUSED[case][2]
+    assert o['losses'].shape[0] == K + 1 and np.all(o['losses'] >= 0.05) and np.all(o['losses'] <= 3.0), o['losses']
+    clear = P.clear_rows(o['logits'])
+    assert np.all((~clear).sum(axis=-1) * 10 <= clear.shape[-1]), (~clear).sum(axis=-1)
+    if K >= 1:
+        assert np.all(o['losses'][K] < 0.995 * o['losses'][0])
+    assert np.isfinite(o['grad_feat']).all() and np.abs(o['grad_feat']).sum() > 0 and np.all(np.abs(o['dscale_tasks']) > 1e-3)
+    assert (o['lr_grad'] is not None) == (P.FUSED[case][3] != 'scalar')
+
+
+def test_cases_cover_what_the_issue_lists():
+    assert [c[:4] for c in P.KERNEL_CASES[:7]] == [(f, w, ns, t) for f, w, ns, _, t in M.KERNEL_CASES]
+    assert P.KERNEL_CASES[7:] == [(128, 20, 100, 1), (8, 64, 64, 1)]
+    assert P.CASES['omni'][1] == M.case_scale('omni', M.PROTO) and P.CASES['min'][1] == M.case_scale('min', M.PROTO)
+    assert all(P.CASES[s][2] < 0.4 for s in P.CASES)            # below anil_steps_oracle.BASE_LR
+
+
+def test_symbols_header_and_makefile():
+    header = U.symbols_declared_and_bound(SYMBOLS)
+    assert re.search(r'#define MI_RIDGE_MAX_FEAT %d\b' % P.MAX_FEAT, header)
+    assert 'N_w >= 1 FOR EVERY CLASS' in header[header.index('Proto-MAML head initialisation'):header.index('int mi_proto_init(')]
+    import os
+    assert re.search(r'^SRCS = .*\bproto_init\.hip\b', open(os.path.join(REPO, 'exploring_meta_amd', 'csrc', 'Makefile')).read(), re.M)
+
+
+def test_driver_flags_and_python_surface():
+    from exploring_meta_amd import core_functions as cf
+    from exploring_meta_amd.engine import MetaEngine
+    from exploring_meta_amd.vision import anil_vision
+    off = anil_vision.params_of(anil_vision.parse_args([]))
+    assert off['proto_init'] is False and off['proto_scale'] == 1.0 and off['fix_proto_scale'] is False
+    on = anil_vision.params_of(anil_vision.parse_args(['--proto_init', '--proto_scale', '0.125', '--fix_proto_scale']))
+    assert on['proto_init'] is True and on['proto_scale'] == 0.125 and on['fix_proto_scale'] is True
+    for name in ('meta_batch_anil_proto', 'proto_init', 'proto_init_bwd'):
+        assert callable(getattr(MetaEngine, name))
+    init = cf.ProtoInit(0.125)
+    assert [n for n, _ in init.named_parameters()] == ['log_scale'] and init.scale == pytest.approx(0.125, rel=1e-6)
+    fixed = cf.ProtoInit(2.0, learnable=False)
+    assert list(fixed.parameters()) == [] and 'log_scale' in fixed.state_dict() and fixed.scale == pytest.approx(2.0, rel=1e-6)
+    for bad in (0.0, -1.0, float('nan'), float('inf')):
+        with pytest.raises(ValueError, match='positive and finite'):
+            cf.ProtoInit(bad)
+    with pytest.raises(NotImplementedError, match='spatial MEAN'):
+        cf.meta_batch_adapt_proto_anil(cf.MAML(torch.nn.Linear(64, 5), lr=0.1), cf.OmniglotCNN(5), init, torch.zeros(1, 10, 1, 28, 28),
+                                       torch.zeros(1, 10, dtype=torch.long), 1, 1, 5)
+    with pytest.raises(TypeError, match='ProtoInit'):
+        cf.meta_batch_adapt_proto_anil(None, None, 0.125, None, None, 1, 1, 5)
+    assert callable(cf.fast_adapt_proto_anil) and callable(cf.evaluate_proto_anil)
