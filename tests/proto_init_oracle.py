@@ -58,9 +58,10 @@ def case_lr(case):
 
 
 def head_init(fs, ys, ways, scale):
-    """(W_0 [ways, F], b_0 [ways]) of one task from the definition; differentiable in fs and scale."""
+    """(W_0 [ways, F], b_0 [ways]) of one task from the definition; differentiable in fs and scale.  A class without a support row is outside
+    the definition; it is treated as include/mi_maml.h states (c_w = 0: W_0 = 0, b_0 = 0, no gradient), which changes nothing for N_w >= 1."""
     onehot = F.one_hot(ys.long(), ways).to(fs.dtype)
-    c = (onehot.t() @ fs) / onehot.sum(dim=0)[:, None]
+    c = (onehot.t() @ fs) / onehot.sum(dim=0).clamp(min=1)[:, None]
     return 2 * scale * c, -scale * (c * c).sum(dim=-1)
 
 
@@ -165,6 +166,10 @@ def init_bwd(fs, ys, lam, ways, scale, dfs0=None):
 # ---- the kernel-entry cases: (feat, ways, ns, tasks); metric_head_oracle.kernel_inputs' features, a hash-uniform cotangent in [-1, 1)
 KERNEL_CASES = [(1, 5, 5, 1), (33, 5, 5, 1), (128, 5, 5, 3), (1600, 5, 25, 2), (128, 1, 3, 1), (128, 20, 20, 1), (128, 3, 6, 1), (128, 20, 100, 1),
                 (8, 64, 64, 1)]
+# the paths no case above runs: stride 4 * 1028 + 4 = 4116, a multiple of 4, so the 16-byte forward loop wraps past column 1024 and the vector
+# backward has 1028 items (> 512); a partial last chunk (nv = 3) after the wrap with class counts (1, 2, 3); classes 1 and 3 without a
+# support row (metric_head_oracle.ABSENT) on odd feat > 512
+EDGE_CASES = [(1028, 4, 8, 1), (1027, 3, 6, 1), (515, 5, 3, 1)]
 MAX_FEAT = 65536                     # MI_RIDGE_MAX_FEAT
 
 

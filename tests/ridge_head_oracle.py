@@ -1,7 +1,10 @@
 """Oracle (TEST INFRASTRUCTURE) for the ridge-regression head (mi_ridge_head, mi_meta_batch_ridge): the definition
 of R2-D2's head written out in torch with autograd through ``torch.linalg.solve`` (``head``), the fused call on oracle/vision_ref.py's
 conv_base and prepare_batch exactly as tests/metric_head_oracle.py builds its features (``meta_batch``), and the closed form the kernel
-implements, without autograd (``closed_form``), for the host test that pins one against the other."""
+implements, without autograd (``closed_form``), for the host test that pins one against the other; the same closed form in NumPy at a chosen precision (``closed_form_np``), which in
+``np.longdouble`` is the extended-precision reference (``closed_form_ext``) the kernel's fp64 claim is held to (``tight_errors``), and in
+fp64 with fp32 stores the host's model of the kernel."""
+import hashlib
 from collections import OrderedDict
 
 import numpy as np
@@ -28,6 +31,10 @@ FUSED_CASES = {
 
 # ---- the kernel-entry cases: metric_head_oracle's (feat, ways, ns, nq, tasks) and Omniglot 20-way 5-shot, each under two (lam, alpha)
 KERNEL_CASES = list(M.KERNEL_CASES) + [(128, 20, 100, 100, 1)]
+# the paths no case above runs: 64 ways on odd feat > 512 (lanes 32..63, rstep = 8, the scalar loops past one trip, 138128 bytes of LDS: the
+# dynamic-LDS attribute); ns < ways with absent classes (metric_head_oracle.ABSENT's labels) and nq > 64; ns = nq = 1 on one vector chunk;
+# one class, ns = 1 on one scalar chunk
+EDGE_CASES = [(515, 64, 64, 70, 1), (515, 5, 3, 75, 2), (4, 2, 1, 1, 1), (5, 1, 1, 3, 1)]
 HYPERS = [(1.0, 8.0), (50.0, 8.0)]
 MAX_FEAT = 65536                                            # MI_RIDGE_MAX_FEAT
 
@@ -103,6 +110,168 @@ def closed_form(fs, fq, ys, yq, ways, lam, alpha, dtype=torch.float64):
         for o, v in zip(out, (loss, acc, z, dfs, dfq, torch.stack([dlam, dalpha]))):
             o.append(v)
     return tuple(torch.stack(o).double().numpy() for o in out)
+
+
+# ---- the closed form in NumPy at a chosen precision: np.longdouble (the x87 80-bit format, eps = 2^-63) is the reference the kernel's
+# fp64 claim is held to; there is no LAPACK for that type, so the factor and the substitutions are written out (sizes are at most 100 x 100)
+def ldl(g):
+    """G = L D L^T in g's own dtype, no pivoting: (L, unit lower triangular; d, the pivots).  A pivot that is not > 0 is returned as it is
+    (the column under it is then not finite)."""
+    n = g.shape[0]
+    low, d = np.eye(n, dtype=g.dtype), np.zeros(n, dtype=g.dtype)
+    with np.errstate(all='ignore'):
+        for j in range(n):
+            v = low[j, :j] * d[:j]
+            d[j] = g[j, j] - low[j, :j] @ v
+            low[j + 1:, j] = (g[j + 1:, j] - low[j + 1:, :j] @ v) / d[j]
+    return low, d
+
+
+def ldl_solve(low, d, x):
+    """G^-1 X from ``ldl``'s factor: forward, diagonal and backward substitution."""
+    x = x.copy()
+    n = x.shape[0]
+    for k in range(1, n):
+        x[k] -= low[k, :k] @ x[:k]
+    x /= d[:, None]
+    for k in range(n - 2, -1, -1):
+        x[k] -= low[k + 1:, k] @ x[k + 1:]
+    return x
+
+
+_CACHE = {}
+
+
+def _key(*arrays):
+    h = hashlib.sha1()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(str((a.dtype, a.shape)).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def _products(s32, q32, dtype):
+    """(Fs Fs^T, Fq Fs^T) of one task in ``dtype``; the longdouble products, the slow part, are kept: every (lam, alpha) reuses them."""
+    if dtype is not np.longdouble:
+        s, q = s32.astype(dtype), q32.astype(dtype)
+        return s @ s.T, q @ s.T
+    key = ('products', _key(s32, q32))
+    if key not in _CACHE:
+        s, q = s32.astype(dtype), q32.astype(dtype)
+        _CACHE[key] = (s @ s.T, q @ s.T)
+    return _CACHE[key]
+
+
+def closed_form_np(fs, fq, ys, yq, ways, lam, alpha, dtype=np.float64, round_dp=False, gram_dtype=None, round_out=False):
+    """``closed_form`` in NumPy with every intermediate in ``dtype`` and the hand-written ``ldl`` / ``ldl_solve``; lam and alpha are the
+    fp32 values the C entry receives.  round_dp: dP = alpha dz is rounded to fp32 where the kernel stores it.  gram_dtype: Fs Fs^T is
+    accumulated in that type instead (np.float32: the regression the header rules out).  round_out: loss, logits, dfs, dfq and dhyper are
+    rounded to fp32 as a store does.  Returns ``closed_form``'s tuple as ``dtype`` arrays."""
+    fs, fq = np.asarray(fs, dtype=np.float32), np.asarray(fq, dtype=np.float32)
+    ys, yq = np.asarray(ys), np.asarray(yq)
+    lam, alpha = dtype(np.float32(lam)), dtype(np.float32(alpha))
+    T, ns, _ = fs.shape
+    nq = fq.shape[1]
+    out = [[], [], [], [], [], []]
+    for t in range(T):
+        s, q = fs[t].astype(dtype), fq[t].astype(dtype)
+        gram, k = _products(fs[t], fq[t], dtype)
+        if gram_dtype is not None:
+            gram = (fs[t].astype(gram_dtype) @ fs[t].astype(gram_dtype).T).astype(dtype)
+        y = (ys[t][:, None] == np.arange(ways)[None, :]).astype(dtype)
+        hit = yq[t][:, None] == np.arange(ways)[None, :]
+        low, d = ldl(gram + lam * np.eye(ns, dtype=dtype))
+        a = ldl_solve(low, d, y)
+        p = k @ a
+        z = alpha * p
+        mx = z.max(axis=-1, keepdims=True)
+        ex = np.exp(z - mx)
+        se = ex.sum(axis=-1, keepdims=True)
+        loss = ((mx + np.log(se))[:, 0] - z[hit]).sum() / nq
+        acc = dtype((z.argmax(axis=-1) == yq[t]).mean())
+        dz = (ex / se - hit.astype(dtype)) / nq
+        dalpha = (dz * p).sum()
+        dp = alpha * dz
+        if round_dp:
+            dp = dp.astype(np.float32).astype(dtype)
+        dk = dp @ a.T
+        b = ldl_solve(low, d, k.T @ dp)
+        sm = -(b @ a.T + a @ b.T)
+        dlam = -(b * a).sum()
+        for o, v in zip(out, (loss, acc, z, dk.T @ q + sm @ s, dk @ s, np.array([dlam, dalpha], dtype=dtype))):
+            o.append(v)
+    res = tuple(np.asarray(o, dtype=dtype) for o in out)
+    if round_out:
+        res = tuple(r if i == 1 else r.astype(np.float32).astype(dtype) for i, r in enumerate(res))
+    return res
+
+
+def closed_form_ext(fs, fq, ys, yq, ways, lam, alpha, round_dp):
+    """The closed form the kernel implements in np.longdouble: the reference of ``tight_errors``.  One run per (inputs, lam, alpha,
+    round_dp), kept and never modified."""
+    assert np.finfo(np.longdouble).eps <= 2.0 ** -63, 'np.longdouble is not an extended format here: the ridge reference needs 64 bits of mantissa'
+    key = ('ext', _key(np.asarray(fs, np.float32), np.asarray(fq, np.float32), np.asarray(ys, np.int64), np.asarray(yq, np.int64)), int(ways),
+           float(np.float32(lam)), float(np.float32(alpha)), bool(round_dp))
+    if key not in _CACHE:
+        res = closed_form_np(fs, fq, ys, yq, ways, lam, alpha, np.longdouble, round_dp=round_dp)
+        for r in res:
+            r.setflags(write=False)
+        _CACHE[key] = res
+    return _CACHE[key]
+
+
+# ---- the bar that holds the kernel to its fp64 claim; every term comes from references, none from the code under test
+QUANTITIES = ('loss', 'logits', 'dfs', 'dfq', 'dlam', 'dalpha')
+ROWWISE = ('logits', 'dfs', 'dfq')              # held per row as well: rows of nq, ns, nq
+ULP32 = 2.0 ** -23
+
+
+def quantities(o):
+    """{name: array} of a (loss, acc, logits, dfs, dfq, dhyper, ...) tuple."""
+    return dict(loss=o[0], logits=o[2], dfs=o[3], dfq=o[4], dlam=o[5][:, 0], dalpha=o[5][:, 1])
+
+
+def rel_ext(a, b, rows=False):
+    """|a - b| / |b| in np.longdouble, over everything or per row of the last axis; a zero reference divides by 1e-300 as ``rel_err``."""
+    a, b = np.asarray(a, dtype=np.longdouble), np.asarray(b, dtype=np.longdouble)
+    if rows:
+        a, b = a.reshape(-1, a.shape[-1]), b.reshape(-1, b.shape[-1])
+        return (np.sqrt(((a - b) ** 2).sum(axis=-1)) / np.maximum(np.sqrt((b ** 2).sum(axis=-1)), 1e-300)).astype(np.float64)
+    return float(np.sqrt(((a - b) ** 2).sum()) / max(np.sqrt((b ** 2).sum()), 1e-300))
+
+
+def tight_errors(got, o64, fs, fq, ys, yq, ways, lam, alpha):
+    """{name: (error, bar)} for QUANTITIES and {name + '_rows': (errors, bars)} for ROWWISE.  The error is relative in norm against
+    closed_form_ext(round_dp=False); the bar is 2^-23 + 2 e_dp + 2 e64 with
+      e_dp = rel(closed_form_ext(round_dp=True), closed_form_ext(round_dp=False)): what the kernel's one stated fp32 intermediate may cost
+             (0 for loss, logits and dalpha),
+      e64  = rel(o64, closed_form_ext(round_dp=False)), o64 = head(..., float64): the fp64 reference's own distance from the truth,
+      2^-23 one fp32 ulp: the output's own rounding takes half, device exp / log and the order of the fp64 sums the other half."""
+    ext = quantities(closed_form_ext(fs, fq, ys, yq, ways, lam, alpha, False))
+    ext_dp = quantities(closed_form_ext(fs, fq, ys, yq, ways, lam, alpha, True))
+    got, o64 = quantities(got), quantities(o64)
+    res = {}
+    for n in QUANTITIES:
+        for rows in ((False, True) if n in ROWWISE else (False,)):
+            err, e_dp, e64 = (rel_ext(x[n], ext[n], rows) for x in (got, ext_dp, o64))
+            res[n + '_rows' if rows else n] = (err, ULP32 + 2 * e_dp + 2 * e64)
+    return res
+
+
+# ---- the non-positive pivot: lam = 2^-80 is inside the domain (positive, finite, a normal fp32) and vanishes against G_ii = 4 in fp64
+PIVOT_LAM = 2.0 ** -80
+
+
+def pivot_inputs(plant_nan=False):
+    """(fs, fq, ys, yq) of the (feat 4, ways 2, ns 2, nq 2) case at T = 3 whose task 1 has two support rows of all 1.0: G = [[4, 4], [4, 4]] +
+    lam I rounds to [[4, 4], [4, 4]] at PIVOT_LAM, so the second pivot is exactly 0; tasks 0 and 2 keep their random features.  plant_nan:
+    one element of task 1's fs is NaN as well."""
+    fs, fq, ys, yq = kernel_inputs(4, 2, 2, 2, 3)
+    fs[1] = 1.0
+    if plant_nan:
+        fs[1, 1, 2] = np.nan
+    return fs, fq, ys, yq
 
 
 def bias_gradient(fs, fq, ys, yq, ways, lam, alpha):

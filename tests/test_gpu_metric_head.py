@@ -2,7 +2,11 @@
 fp64 oracle of the definitions (tests/metric_head_oracle.py) at sizes on both sides of every path the kernel takes (feat not a multiple of
 4, more than 8 classes, one class, unbalanced classes, ns != nq, the largest ways * feat the header admits and the first it refuses), its
 exact edge cases and bitwise relations; the fused call against the oracle on vision_ref's trunk under every operand form; graph replay,
-the BatchNorm export, the launch make-up; the Python surface and the drivers."""
+the BatchNorm export, the launch make-up; the Python surface and the drivers.
+The edge cases (metric_head_oracle.EDGE_CASES) run what the cases above do not: 64 classes on odd feat > 512 (class lanes 32 to 63, eight
+chunks of 8 classes with dfq's read-modify-write over them, the scalar loops past one trip, 37848 of 40960 LDS floats), exactly 8 classes
+and 9, nq > 64, nq = 1; a first maximum that sits in the ballot's upper half; 257 tasks against their T = 1 calls; the 16-byte alignment
+refusal."""
 import ctypes as C
 import functools
 import math
@@ -74,7 +78,7 @@ def _scale_of(metric, feat):
 
 # ---------------------------------------------------------------------------------------------------------------- 1: the kernel entry
 @pytest.mark.parametrize('metric', METRICS)
-@pytest.mark.parametrize('feat,ways,ns,nq,T', M.KERNEL_CASES)
+@pytest.mark.parametrize('feat,ways,ns,nq,T', M.KERNEL_CASES + M.EDGE_CASES)
 def test_kernel_against_the_fp64_oracle(feat, ways, ns, nq, T, metric):
     fs, fq, ys, yq = M.kernel_inputs(feat, ways, ns, nq, T)
     scale = _scale_of(metric, feat)
@@ -195,6 +199,61 @@ def test_bitwise_relations(feat, ways, ns, nq, metric):
     rc, *nolog = _kernel(fs, fq, ys, yq, ways, metric, scale, logits=False)
     assert rc == 0 and nolog[2] is None
     _same('no logits', ('loss', 'acc', 'dfs', 'dfq'), nolog[:2] + nolog[3:], whole[:2] + whole[3:])
+
+
+@pytest.mark.parametrize('metric', METRICS)
+def test_first_maximum_in_the_upper_lanes(metric):
+    """64 classes, one shot, support row 50 a copy of row 40, query rows 0 and 1 that row with labels (40, 50): the logits of classes 40 and
+    50 are the row's maximum and bit-equal, the first of them (lane 40, found in the ballot's upper half) is the prediction -- row 0 a hit,
+    row 1 a miss; the oracle's argmax takes the first maximum too."""
+    ways, feat = 64, 33
+    fs, fq, ys, yq = M.kernel_inputs(feat, ways, ways, 2, 1)
+    fs[0, 50] = fs[0, 40]
+    fq[0, :] = fs[0, 40]
+    yq[0] = (40, 50)
+    scale = _scale_of(metric, feat)
+    rc, loss, acc, logits, dfs, dfq = _kernel(fs, fq, ys, yq, ways, metric, scale)
+    assert rc == 0, _lib.load().mi_last_error(None)
+    assert np.array_equal(logits[0, :, 40], logits[0, :, 50]) and np.all(logits[0].max(axis=-1) == logits[0, :, 40])
+    assert np.all((logits[0] == logits[0, :, 40:41]).sum(axis=-1) == 2)            # (no third class ties)
+    assert acc[0] == np.float32(0.5)
+    o64 = M.head(fs, fq, ys, yq, ways, metric, scale)
+    assert np.array_equal(o64[2][0, :, 40], o64[2][0, :, 50]) and np.array_equal(o64[2][0].argmax(axis=-1), [40, 40]) and o64[1][0] == 0.5
+    assert np.array_equal(logits[0].argmax(axis=-1), [40, 40])
+
+
+@pytest.mark.parametrize('metric', METRICS)
+def test_task_independence_beyond_the_cu_count(metric):
+    """257 tasks, one more than the 256 CUs: every task of the one launch is the T = 1 call on it, bit for bit."""
+    T = 257
+    fs, fq, ys, yq = M.kernel_inputs(8, 5, 5, 5, T)
+    scale = _scale_of(metric, 8)
+    rc, *whole = _kernel(fs, fq, ys, yq, 5, metric, scale)
+    assert rc == 0 and all(np.isfinite(w).all() for w in whole) and len({w.tobytes() for w in whole[3]}) == T
+    for t in range(T):
+        rc, *one = _kernel(fs[t:t + 1], fq[t:t + 1], ys[t:t + 1], yq[t:t + 1], 5, metric, scale)
+        assert rc == 0
+        _same(('task', t), NAMES, [o[0] for o in one], [w[t] for w in whole])
+
+
+def test_misaligned_feature_pointers_are_refused():
+    """fs, fq, dfs, dfq in turn one float into a larger buffer: MI_ERR_ARG naming the rule, nothing launched, the outputs untouched."""
+    lib = _lib.load()
+    feat, ways, n = 32, 5, 5
+    fs, fq, ys, yq = M.kernel_inputs(feat, ways, n, n, 1)
+    ysd, yqd = dev(ys, torch.int32), dev(yq, torch.int32)
+    for which in ('fs', 'fq', 'dfs', 'dfq'):
+        big = {k: torch.full((n * feat + 8,), -7.0, device='cuda') for k in ('fs', 'fq', 'dfs', 'dfq')}
+        v = {k: b[1:1 + n * feat] if k == which else b[4:4 + n * feat] for k, b in big.items()}
+        assert all((v[k].data_ptr() % 16 == 0) == (k != which) for k in v)
+        v['fs'].copy_(dev(fs).reshape(-1)); v['fq'].copy_(dev(fq).reshape(-1))
+        out = torch.full((36,), -7.0, device='cuda')                          # loss at 0, acc at 4, logits (25) at 8
+        rc = lib.mi_metric_head(stream(), ptr(v['fs']), ptr(v['fq']), ptr(ysd), ptr(yqd), 1, n, n, feat, ways, MID[M.PROTO], 1.0, ptr(out),
+                                ptr(out[4:]), ptr(out[8:]), ptr(v['dfs']), ptr(v['dfq']), None, 0)
+        msg = lib.mi_last_error(None).decode()
+        assert rc == -1 and 'mi_metric_head' in msg and 'must be 16-byte aligned' in msg, (which, rc, msg)
+        torch.cuda.synchronize()
+        assert bool((out == -7.0).all()) and bool((big['dfs'] == -7.0).all()) and bool((big['dfq'] == -7.0).all()), which
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4: the fused call

@@ -2,7 +2,10 @@
 section 30): the two kernel entries against the fp64 oracle of the definitions (tests/proto_init_oracle.py) at sizes on both sides of every
 path they take (feat not a multiple of 4, more than one sweep of the columns, one class, unbalanced classes, 64 classes), their exact
 properties and domain; the fused call against the autograd oracle whose theta_0 is built inside the graph, at K = 0 also against the
-merged metric head; graph replay, the launch make-up; the Python surface and the driver."""
+merged metric head; graph replay, the launch make-up; the Python surface and the driver.
+The edge cases (proto_init_oracle.EDGE_CASES) run what the cases above do not: the 16-byte forward loop past column 1024 and the vector
+backward with more items than threads (stride 4116), a partial last chunk after the wrap, classes without a support row (W_0 = 0, b_0 = 0,
+no gradient); the same bits from bases one float off a 16-byte boundary; 257 tasks against their T = 1 calls."""
 import ctypes as C
 import functools
 import math
@@ -36,27 +39,39 @@ def _err():
     return _lib.load().mi_last_error(None).decode()
 
 
-def _fwd(fs, ys, ways, scale, fill=None, pad=0):
-    """mi_proto_init on numpy inputs -> (rc, head [T, Ph] numpy); pad: extra floats between the tasks' heads."""
+def _shifted(t, off):
+    """t's values in a buffer of its own that starts `off` floats past an allocation's (16-byte aligned) base."""
+    if not off:
+        return t
+    big = torch.empty(t.numel() + off, dtype=t.dtype, device='cuda')
+    view = big[off:].view(t.shape)
+    view.copy_(t)
+    assert view.data_ptr() % 16 == (4 * off) % 16
+    return view
+
+
+def _fwd(fs, ys, ways, scale, fill=None, pad=0, off=0):
+    """mi_proto_init on numpy inputs -> (rc, head [T, Ph] numpy); pad: extra floats between the tasks' heads; off: fs and head_out start
+    this many floats past a 16-byte boundary."""
     T, ns, feat = fs.shape
     ph = ways * feat + ways
-    fsd, ysd = dev(fs), dev(ys, torch.int32)
-    head = torch.full((T, ph + pad), float(fill if fill is not None else 0.0), device='cuda')
+    fsd, ysd = _shifted(dev(fs), off), dev(ys, torch.int32)
+    head = _shifted(torch.full((T, ph + pad), float(fill if fill is not None else 0.0), device='cuda'), off)
     rc = _lib.load().mi_proto_init(stream(), ptr(fsd), ptr(ysd), T, ns, feat, ways, float(scale), ptr(head), ph + pad)
     return rc, _np(head)[0][:, :ph]
 
 
-def _bwd(fs, ys, lam, ways, scale, dfs0, want_dscale=True, fill=None):
-    """mi_proto_init_bwd -> (rc, dfs, dscale or None)."""
+def _bwd(fs, ys, lam, ways, scale, dfs0, want_dscale=True, fill=None, off=0):
+    """mi_proto_init_bwd -> (rc, dfs, dscale or None); off: fs, lam_head and dfs start this many floats past a 16-byte boundary."""
     T, ns, feat = fs.shape
-    fsd, ysd, lamd, dfs = dev(fs), dev(ys, torch.int32), dev(lam), dev(dfs0).clone()
+    fsd, ysd, lamd, dfs = _shifted(dev(fs), off), dev(ys, torch.int32), _shifted(dev(lam), off), _shifted(dev(dfs0).clone(), off)
     dscale = torch.full((T,), float(fill if fill is not None else 0.0), device='cuda') if want_dscale else None
     rc = _lib.load().mi_proto_init_bwd(stream(), ptr(fsd), ptr(ysd), ptr(lamd), lam.shape[1], T, ns, feat, ways, float(scale), ptr(dfs), ptr(dscale))
     return (rc,) + _np(dfs, dscale)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1: the kernel entries
-@pytest.mark.parametrize('feat,ways,ns,T', P.KERNEL_CASES)
+@pytest.mark.parametrize('feat,ways,ns,T', P.KERNEL_CASES + P.EDGE_CASES)
 def test_kernels_against_the_fp64_oracle(feat, ways, ns, T):
     """W_0, b_0, dfs and dscale each within max(2 x the fp32 autograd oracle's own error against fp64, 4 * 2^-24), relative in norm."""
     fs, ys, lam, dfs0 = P.kernel_inputs(feat, ways, ns, T)
@@ -99,6 +114,60 @@ def test_exact_properties_of_the_kernels():
         assert np.array_equal(h1[0], head[t]) and np.array_equal(d1[0], dfs[t]) and np.array_equal(s1[0], dscale[t])
     # the labels select the rows: another labelling of the same features gives another head
     assert not np.array_equal(_fwd(fs, ys[:, ::-1].copy(), ways, scale)[1], head)
+
+
+def test_a_class_without_a_support_row():
+    """What the header states for N_w = 0 (outside the definition, never a fault): with ys = (0, 2, 4) of 5 classes, rows 1 and 3 of W_0 and
+    entries 1 and 3 of b_0 are exactly 0 (the other rows are not), and dfs and dscale are the oracle's, which gives such a class no gradient
+    (test_kernels_against_the_fp64_oracle holds the same case to the bars)."""
+    feat, ways, ns = 515, 5, 3
+    fs, ys, lam, dfs0 = P.kernel_inputs(feat, ways, ns, 1)
+    assert ys[0].tolist() == [0, 2, 4]
+    rc, head = _fwd(fs, ys, ways, 1.0 / feat, fill=-7.0)
+    assert rc == 0, _err()
+    w0, b0 = head[0, :ways * feat].reshape(ways, feat), head[0, ways * feat:]
+    assert np.all(w0[[1, 3]] == 0) and np.all(b0[[1, 3]] == 0) and np.all(w0[[0, 2, 4]] != 0) and np.all(b0[[0, 2, 4]] < 0)
+    # the cotangent of an absent class enters nothing: another lamW[1], lamb[3] gives the same bits
+    rc, dfs, dscale = _bwd(fs, ys, lam, ways, 1.0 / feat, dfs0)
+    lam2 = lam.copy()
+    lam2[0, feat:2 * feat] += 1.0
+    lam2[0, ways * feat + 3] -= 2.0
+    rc2, dfs2, dscale2 = _bwd(fs, ys, lam2, ways, 1.0 / feat, dfs0)
+    assert rc == 0 and rc2 == 0 and np.array_equal(dfs2, dfs) and np.array_equal(dscale2, dscale) and not np.array_equal(dfs, dfs0)
+
+
+def test_bits_do_not_depend_on_the_alignment_of_the_bases():
+    """(132, 4, 8) at T = 2, stride 532: every row on a 16-byte boundary takes the 16-byte path; fs, head_out, lam_head and dfs each one float
+    into a larger buffer take the word path -- W_0, b_0, dfs and dscale bit for bit."""
+    feat, ways, ns, T = 132, 4, 8, 2
+    fs, ys, lam, dfs0 = P.kernel_inputs(feat, ways, ns, T)
+    assert (ways * feat + ways) % 4 == 0 and feat % 4 == 0
+    scale = 1.0 / feat
+    rc, head = _fwd(fs, ys, ways, scale)
+    rc1, head1 = _fwd(fs, ys, ways, scale, off=1)
+    assert rc == 0 and rc1 == 0, _err()
+    assert np.array_equal(head1, head) and np.abs(head).min() > 0
+    rc, dfs, dscale = _bwd(fs, ys, lam, ways, scale, dfs0)
+    rc1, dfs1, dscale1 = _bwd(fs, ys, lam, ways, scale, dfs0, off=1)
+    assert rc == 0 and rc1 == 0, _err()
+    assert np.array_equal(dfs1, dfs) and np.array_equal(dscale1, dscale) and not np.array_equal(dfs, dfs0) and np.all(dscale != 0)
+
+
+def test_task_independence_beyond_the_cu_count():
+    """257 tasks, one more than the 256 CUs (1285 forward workgroups): every task of the one launch is the T = 1 call on it, bit for bit."""
+    feat, ways, ns, T = 8, 5, 5, 257
+    fs, ys, lam, dfs0 = P.kernel_inputs(feat, ways, ns, T)
+    scale = 1.0 / feat
+    rc, head = _fwd(fs, ys, ways, scale)
+    rc2, dfs, dscale = _bwd(fs, ys, lam, ways, scale, dfs0)
+    assert rc == 0 and rc2 == 0, _err()
+    assert len({h.tobytes() for h in head}) == T and np.isfinite(head).all() and np.isfinite(dfs).all()
+    for t in range(T):
+        one = slice(t, t + 1)
+        rc, h1 = _fwd(fs[one], ys[one], ways, scale)
+        rc2, d1, s1 = _bwd(fs[one], ys[one], lam[one], ways, scale, dfs0[one])
+        assert rc == 0 and rc2 == 0
+        assert np.array_equal(h1[0], head[t]) and np.array_equal(d1[0], dfs[t]) and np.array_equal(s1[0], dscale[t]), t
 
 
 def test_domain_errors_launch_nothing():

@@ -113,3 +113,28 @@ def test_the_surface_refuses_without_a_gpu():
         cf.meta_batch_adapt_metric(cf.OmniglotCNN(5), data, labels, 1, 5)
     from exploring_meta_amd.engine import MetaEngine
     assert callable(MetaEngine.meta_batch_metric) and callable(MetaEngine.metric_head)
+
+
+@pytest.mark.parametrize('metric', (M.PROTO, M.COSINE))
+def test_edge_cases_take_the_paths_they_are_there_for(metric):
+    """Settled on the fp64 reference alone: every edge case is inside the header's LDS inequality (the 64-way one at 37848 of 40960
+    floats), keeps the contract N_w >= 1, has a loss above 1e-3 and gradients that are not zero; the 64-way query labels reach lanes 32 to
+    63; (8, 9) classes are one full chunk of 8 and one class into the second; 515 is odd and above one trip of the 512 threads."""
+    assert M.lds_floats(64, 70, 515, 64) == 37848
+    assert [c[1] for c in M.EDGE_CASES[1:3]] == [8, 9] and M.EDGE_CASES[0][0] == 515 and 515 % 2 == 1 and 515 > 512 and M.EDGE_CASES[3][3] > 64
+    for feat, ways, ns, nq, T in M.EDGE_CASES:
+        assert M.lds_floats(ns, nq, feat, ways) <= 40960
+        fs, fq, ys, yq = M.kernel_inputs(feat, ways, ns, nq, T)
+        assert all(np.bincount(y, minlength=ways).min() >= 1 for y in ys)
+        loss, _, _, dfs, dfq = M.head(fs, fq, ys, yq, ways, metric, (1.0 / feat) if metric == M.PROTO else 4.0)
+        assert np.all(loss > 1e-3) and np.abs(dfs).sum() > 0 and np.abs(dfq).sum() > 0
+    assert set(M.kernel_inputs(515, 64, 64, 70, 1)[3][0].tolist()) == set(range(64))
+
+
+def test_kernel_inputs_labels():
+    """ns < ways takes ABSENT's labels, explicit labels win, everything else is as it was."""
+    assert M.kernel_inputs(8, 5, 3, 4, 2)[2].tolist() == [[0, 2, 4]] * 2 and M.kernel_inputs(8, 2, 1, 1, 1)[2].tolist() == [[1]]
+    assert M.kernel_inputs(8, 5, 3, 4, 1, ys=(4, 0, 2))[2].tolist() == [[4, 0, 2]]
+    assert M.kernel_inputs(8, 3, 6, 4, 1)[2].tolist() == [[0, 1, 1, 2, 2, 2]] and M.kernel_inputs(8, 5, 10, 4, 1)[2].tolist() == [[0, 0, 1, 1, 2, 2, 3, 3, 4, 4]]
+    with pytest.raises(AssertionError):
+        M.kernel_inputs(8, 5, 3, 4, 1, ys=(0, 2, 5))

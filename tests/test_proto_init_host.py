@@ -147,3 +147,27 @@ def test_driver_flags_and_python_surface():
     with pytest.raises(TypeError, match='ProtoInit'):
         cf.meta_batch_adapt_proto_anil(None, None, 0.125, None, None, 1, 1, 5)
     assert callable(cf.fast_adapt_proto_anil) and callable(cf.evaluate_proto_anil)
+
+
+def test_edge_cases_take_the_paths_they_are_there_for():
+    """(1028, 4, 8): feat and the stride 4116 are multiples of 4 (the 16-byte path), the forward loop of 256 threads x 4 columns wraps past
+    column 1024 and the backward has 1028 items for 512 threads; (1027, 3, 6): a last chunk of 3 columns after the wrap, class counts (1, 2,
+    3); (515, 5, 3): classes 1 and 3 have no support row, and the oracle then gives W_0 = 0, b_0 = 0 and finite gradients, as the header
+    states."""
+    assert P.EDGE_CASES == [(1028, 4, 8, 1), (1027, 3, 6, 1), (515, 5, 3, 1)]
+    assert 1028 % 4 == 0 and (4 * 1028 + 4) % 4 == 0 and 4 * 1028 + 4 == 4116 and 1028 > 256 * 4 and 4 * (1028 // 4) > 512
+    assert 1027 > 256 * 4 and 1027 - 1024 == 3 and np.bincount(P.kernel_inputs(1027, 3, 6, 1)[1][0]).tolist() == [1, 2, 3]
+    feat, ways, ns, T = P.EDGE_CASES[2]
+    fs, ys, lam, dfs0 = P.kernel_inputs(feat, ways, ns, T)
+    assert ys.tolist() == [[0, 2, 4]]
+    head, dfs, dscale = P.init_autograd(fs, ys, lam, ways, 1.0 / feat)
+    w0, b0 = head[0, :ways * feat].reshape(ways, feat), head[0, ways * feat:]
+    assert np.all(w0[[1, 3]] == 0) and np.all(b0[[1, 3]] == 0) and np.all(np.abs(w0[[0, 2, 4]]).sum(axis=-1) > 0) and np.all(b0[[0, 2, 4]] < 0)
+    assert np.isfinite(dfs).all() and np.abs(dfs).sum() > 0 and np.isfinite(dscale).all() and np.all(dscale != 0)
+    # with every class present the empty-class rule changes nothing: the formulas without it agree
+    for feat, ways, ns, T in P.EDGE_CASES[:2]:
+        fs, ys, lam, dfs0 = P.kernel_inputs(feat, ways, ns, T)
+        head, dfs, dscale = P.init_autograd(fs, ys, lam, ways, 1.0 / feat)
+        got_dfs, got_dscale = P.init_bwd(fs, ys, lam, ways, 1.0 / feat, dfs0)
+        assert P.rel_err(P.init(fs, ys, ways, 1.0 / feat), head) < 1e-10
+        assert P.rel_err(got_dfs, dfs0.astype(np.float64) + dfs) < 1e-10 and P.rel_err(got_dscale, dscale) < 1e-10

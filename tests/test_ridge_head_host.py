@@ -1,7 +1,9 @@
 """CPU tests of the ridge-regression head: the closed form the kernel implements against fp64 autograd of the
 definition (tests/ridge_head_oracle.py), the omitted bias, the conditions the GPU test puts on its fused-call inputs, the kernel's
 square-root-free factor and substitution loops restated in numpy, the drivers' flags, the C symbols, and what the Python surface refuses
-without a GPU."""
+without a GPU; the bar that holds the kernel to its fp64 claim (ridge_head_oracle.tight_errors, against the closed form in np.longdouble):
+the reference itself, an fp64 model of the kernel inside it, the same model with an fp32 Gram matrix outside it, and the conditions the edge
+cases and the pivot case of the GPU test rest on."""
 import functools
 import math
 import os
@@ -117,6 +119,126 @@ def test_kernel_cases_and_the_domain():
     header = open(os.path.join(REPO, 'include', 'mi_maml.h')).read()
     assert re.search(r'#define MI_RIDGE_MAX_FEAT %d\b' % RH.MAX_FEAT, header)
     assert '8 * (ns (ns + 1) / 2 + nq * ns + 2 * ns * ways + ns + 3 * nq) + 4 * nq * ways <= 163840' in header
+
+
+# ---------------------------------------------------------------------------------------------------------------- the fp64 claim's bar
+# Fail loudly, never skip: without an extended format the reference is no better than what it judges.
+assert np.finfo(np.longdouble).eps <= 2.0 ** -63, 'np.longdouble must be the 80-bit extended format (eps 2^-63) for the ridge reference'
+
+# every case the GPU test sends through _check_kernel: the kernel cases, the edge cases, and test_domain_limits' feat = MI_RIDGE_MAX_FEAT
+BAR_CASES = [c + h for c in RH.KERNEL_CASES + RH.EDGE_CASES for h in RH.HYPERS] + [(RH.MAX_FEAT, 5, 5, 5, 1, 1.0, 8.0)]
+BAR_IDS = ['-'.join(f'{v:g}' for v in c) for c in BAR_CASES]
+
+
+@functools.lru_cache(maxsize=None)
+def _o64(case):
+    """(inputs, fp64 autograd oracle) of a BAR_CASES entry, shared by the tests below (never modified)."""
+    feat, ways, ns, nq, T, lam, alpha = case
+    inputs = RH.kernel_inputs(feat, ways, ns, nq, T)
+    return inputs, RH.head(*inputs, ways, lam, alpha, torch.float64)
+
+
+def _model(case, **kw):
+    """The kernel's arithmetic as the header states it, in NumPy: fp64 sums, factor and solves, dP and every output rounded to fp32."""
+    (fs, fq, ys, yq), _ = _o64(case)
+    return RH.closed_form_np(fs, fq, ys, yq, case[1], case[5], case[6], np.float64, round_dp=True, round_out=True, **kw)
+
+
+def _tight(case, got):
+    (fs, fq, ys, yq), o64 = _o64(case)
+    return RH.tight_errors(got, o64, fs, fq, ys, yq, case[1], case[5], case[6])
+
+
+@pytest.mark.parametrize('case', BAR_CASES, ids=BAR_IDS)
+def test_extended_reference_is_the_closed_form(case):
+    """closed_form_ext (np.longdouble, hand-written L D L^T) = closed_form (fp64, LAPACK) to 1e-9 wherever cond_2(G) < 1e3, and rounding dP
+    to fp32 moves loss, logits and dalpha by nothing at all."""
+    (fs, fq, ys, yq), o64 = _o64(case)
+    ways, lam, alpha = case[1], case[5], case[6]
+    ext, ext_dp = (RH.quantities(RH.closed_form_ext(fs, fq, ys, yq, ways, lam, alpha, r)) for r in (False, True))
+    for n in ('loss', 'logits', 'dalpha'):
+        assert np.array_equal(ext[n], ext_dp[n]), n
+    if o64[6].max() < 1e3:
+        want = RH.quantities(RH.closed_form(fs, fq, ys, yq, ways, lam, alpha))
+        for n in RH.QUANTITIES:
+            assert ext[n].shape == want[n].shape and RH.rel_ext(want[n], ext[n]) < 1e-9, (n, RH.rel_ext(want[n], ext[n]))
+        acc = RH.closed_form_ext(fs, fq, ys, yq, ways, lam, alpha, False)[1]
+        assert np.allclose(acc.astype(np.float64), o64[1], rtol=0, atol=1e-6)  # (the oracle's accuracy is vision_ref's fp32 ratio)
+
+
+def test_extended_reference_was_compared_somewhere():
+    assert sum(float(_o64(c)[1][6].max()) < 1e3 for c in BAR_CASES) >= len(BAR_CASES) // 2
+
+
+@pytest.mark.parametrize('case', BAR_CASES, ids=BAR_IDS)
+def test_the_kernels_model_stays_inside_the_tight_bar(case):
+    """The reference alone stays within it: fp64 arithmetic with fp32 dP and fp32 stores meets 2^-23 + 2 e_dp + 2 e64 on every quantity
+    and on every row of logits, dfs and dfq."""
+    res = _tight(case, _model(case))
+    print(f'[tight bar, model] {case}: ' + ', '.join(f'{n} {np.max(e):.2e} ({np.max(e / b):.2f} of its bar)' for n, (e, b) in res.items()))
+    for n, (err, bar) in res.items():
+        assert np.all(err <= bar), (n, np.max(err / bar))
+
+
+@pytest.mark.parametrize('case', [c for c in BAR_CASES if c[2] >= 20], ids=[i for c, i in zip(BAR_CASES, BAR_IDS) if c[2] >= 20])
+def test_an_fp32_gram_matrix_breaks_the_tight_bar(case):
+    """The bar has teeth: the same model with Fs Fs^T accumulated in fp32 -- the regression the header rules out -- is rejected on logits,
+    dfs and dfq in every case with ns >= 20."""
+    res = _tight(case, _model(case, gram_dtype=np.float32))
+    print(f'[tight bar, fp32 Gram] {case}: ' + ', '.join(f'{n} {np.max(e):.2e} ({np.max(e / b):.2f} of its bar)' for n, (e, b) in res.items()))
+    for n in RH.ROWWISE:
+        assert res[n][0] > res[n][1], (n, res[n])
+
+
+@pytest.mark.parametrize('case', [c + h for c in RH.EDGE_CASES for h in RH.HYPERS])
+def test_edge_cases_meet_the_conditions_the_gpu_test_rests_on(case):
+    """Settled on the fp64 reference alone.  ways > 1: every task's loss above 1e-3 and no gradient zero, so a relative bar means
+    something; every row's top-2 logit margin is at least 10 x what the tight bar lets two returned logits move against each other (twice
+    the row's bar times the row's norm; 1 x would do), so `argmax equal on every row` cannot turn on a rounding."""
+    (fs, fq, ys, yq), o64 = _o64(case)
+    ways = case[1]
+    if ways == 1:
+        assert np.all(o64[0] == 0) and np.all(o64[5] == 0)
+        return
+    assert np.all(o64[0] > 1e-3) and np.abs(o64[3]).sum() > 0 and np.abs(o64[4]).sum() > 0 and np.all(o64[5] != 0), (o64[0], o64[5])
+    bar = RH.tight_errors(o64, o64, fs, fq, ys, yq, ways, case[5], case[6])['logits_rows'][1]
+    z = o64[2].reshape(-1, ways)
+    top2 = np.sort(z, axis=-1)[:, -2:]
+    margin, moves = top2[:, 1] - top2[:, 0], 2 * bar * np.linalg.norm(z, axis=-1)
+    print(f'[edge case] {case}: loss {o64[0]}, smallest margin {margin.min():.3e}, largest move {moves.max():.3e}')
+    assert np.all(margin > 10 * moves), (margin.min(), moves.max())
+
+
+def test_edge_cases_take_the_paths_they_are_there_for():
+    """Every edge case is inside the header's LDS inequality; the 64-way one asks for 138128 bytes, above the 64 KiB a kernel gets without
+    the dynamic-LDS attribute, and its query labels reach lanes 32 to 63; 515 is odd and above one trip of the 512 threads; (5 ways, 3
+    rows) has classes 1 and 3 without a support row and nq > 64."""
+    assert RH.EDGE_CASES == [(515, 64, 64, 70, 1), (515, 5, 3, 75, 2), (4, 2, 1, 1, 1), (5, 1, 1, 3, 1)]
+    for feat, ways, ns, nq, T in RH.EDGE_CASES:
+        assert RH.lds_bytes(ns, nq, ways) <= 163840 and feat <= RH.MAX_FEAT
+    assert RH.lds_bytes(64, 70, 64) == 138128 > 64 * 1024
+    fs, fq, ys, yq = RH.kernel_inputs(515, 64, 64, 70, 1)
+    assert set(yq[0].tolist()) == set(range(64)) and ys[0].tolist() == list(range(64))
+    assert RH.kernel_inputs(515, 5, 3, 75, 2)[2].tolist() == [[0, 2, 4]] * 2 and 75 > 64 and 515 % 2 == 1 and 515 > 512
+
+
+@pytest.mark.parametrize('plant_nan', [False, True])
+def test_the_pivot_case_has_one_bad_task(plant_nan):
+    """lam = 2^-80 is a positive normal fp32; in fp64 task 1's pivots are exactly (4, 0) (NaN with a NaN planted), those of tasks 0 and 2
+    are positive by a wide margin, and their results are finite."""
+    fs, fq, ys, yq = RH.pivot_inputs(plant_nan)
+    lam = np.float32(RH.PIVOT_LAM)
+    assert lam > 0 and np.isfinite(lam) and float(lam) == RH.PIVOT_LAM and lam >= np.finfo(np.float32).tiny
+    for t in range(3):
+        s = fs[t].astype(np.float64)
+        _, d = RH.ldl(s @ s.T + float(lam) * np.eye(2))
+        if t == 1:
+            assert d[0] == 4.0 or plant_nan
+            assert not d[1] > 0 and (plant_nan or d[1] == 0.0), d
+        else:
+            assert np.all(d > 1e-2), d
+    good = RH.closed_form_np(fs[::2], fq[::2], ys[::2], yq[::2], 2, lam, 8.0)
+    assert all(np.isfinite(g).all() for g in good)
 
 
 def test_symbols_declared_and_bound():
