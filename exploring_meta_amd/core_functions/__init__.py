@@ -7,6 +7,7 @@ from .step_offsets import StepOffsets
 from .anil import meta_batch_adapt_anil, meta_batch_adapt_anil_steps
 from .metric import meta_batch_adapt_metric, fast_adapt_metric, evaluate_nil
 from .ridge import RidgeHead, meta_batch_adapt_ridge, fast_adapt_ridge, evaluate_ridge
+from .logreg import LogRegHead, meta_batch_adapt_logreg, fast_adapt_logreg, evaluate_logreg
 from .proto_anil import ProtoInit, meta_batch_adapt_proto_anil, fast_adapt_proto_anil, evaluate_proto_anil
 from ..utils.data_pre import prepare_batch
 from .policies import DiagNormalPolicy, DiagNormalPolicyANIL

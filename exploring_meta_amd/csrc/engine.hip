@@ -90,11 +90,11 @@ struct mi_engine {
 
 enum ProfOp { OP_CONV_FWD = 0, OP_BN_FINALIZE, OP_BN_FWD, OP_HEAD, OP_BN_BWD_REDUCE, OP_BN_BWD_APPLY, OP_WGRAD, OP_WGRAD_REDUCE,
               OP_DGRAD, OP_TAN_CONV, OP_BN_TAN_FWD, OP_HEAD_TAN, OP_BN_TAN_BWD_REDUCE, OP_BN_TAN_BWD_APPLY, OP_TAN_WGRAD,
-              OP_TAN_DGRAD, OP_MISC, OP_GRAM, OP_GRAM_STATS, OP_METRIC_HEAD, OP_RIDGE_HEAD, OP_PROTO_INIT, OP_COUNT };
+              OP_TAN_DGRAD, OP_MISC, OP_GRAM, OP_GRAM_STATS, OP_METRIC_HEAD, OP_RIDGE_HEAD, OP_PROTO_INIT, OP_LOGREG_HEAD, OP_COUNT };
 static const char* kOpNames[OP_COUNT] = {"conv_fwd_stats", "bn_finalize", "bn_relu_pool_fwd", "head_fwd_bwd", "bn_bwd_reduce",
                                          "bn_bwd_apply", "wgrad", "wgrad_reduce", "dgrad", "tangent_conv_fwd", "bn_tangent_fwd",
                                          "head_tangent", "bn_tangent_bwd_reduce", "bn_tangent_bwd_apply", "tangent_wgrad",
-                                         "tangent_dgrad", "misc", "input_gram", "gram_stats", "metric_head", "ridge_head", "proto_init"};
+                                         "tangent_dgrad", "misc", "input_gram", "gram_stats", "metric_head", "ridge_head", "proto_init", "logreg_head"};
 
 static bool prof_begin(mi_engine* e, hipStream_t st, int kind) {
   if (!e || !e->prof_on || (e->prof_filter >= 0 && e->prof_filter != kind)) return false;
@@ -157,6 +157,15 @@ static int ridge_lds_check(mi_engine* e, const char* who, int ns, int nq, int fe
                                  std::to_string(ns >= 1 && nq >= 1 && ways >= 1 ? ridge_head_lds_bytes(ns, nq, ways) : 0) +
                                  " bytes of LDS, the device has " + std::to_string(head_lds_limit_bytes()));
 }
+// The logistic-regression head keeps G, K, the dual coefficients and its solver's tables in LDS in fp64 (logreg_head.hip): the same rule.
+static int logreg_lds_check(mi_engine* e, const char* who, int ns, int nq, int feat, int ways) {
+  if (logreg_head_fits(ns, nq, feat, ways)) return MI_OK;
+  return fail(e, MI_ERR_ARG, std::string(who) + ": the logistic-regression head with ns = " + std::to_string(ns) + ", nq = " + std::to_string(nq) +
+                                 ", feat = " + std::to_string(feat) + " and ways = " + std::to_string(ways) + " needs ns, nq >= 1, feat in 1.." +
+                                 std::to_string(MI_RIDGE_MAX_FEAT) + ", ways in 1..64 and " +
+                                 std::to_string(ns >= 1 && nq >= 1 && ways >= 1 ? logreg_head_lds_bytes(ns, nq, ways) : 0) +
+                                 " bytes of LDS, the device has " + std::to_string(head_lds_limit_bytes()));
+}
 static int ridge_hyper_check(mi_engine* e, const char* who, float lam, float alpha) {
   if (!(lam > 0.f) || !std::isfinite(lam)) return fail(e, MI_ERR_ARG, std::string(who) + ": lam must be positive and finite, got " + std::to_string(lam));
   if (!(alpha > 0.f) || !std::isfinite(alpha))
@@ -175,7 +184,7 @@ static int metric_hyper_check(mi_engine* e, const char* who, int metric, float s
   if (!(scale > 0.f)) return fail(e, MI_ERR_ARG, std::string(who) + ": scale must be positive, got " + std::to_string(scale));
   return MI_OK;
 }
-// What the closed-form heads' argument structs (A: MetricArgs, RidgeArgs) share, from pointers and sizes; each caller adds its head's own fields.
+// What the closed-form heads' argument structs (A: MetricArgs, RidgeArgs, LogregArgs) share, from pointers and sizes; each caller adds its head's own fields.
 template <class A>
 static A closed_form_args(const float* fs, const float* fq, const int32_t* ys, const int32_t* yq, int ns, int nq, int feat, int ways,
                           float* loss, float* acc, float* logits, float* dfs, float* dfq) {
@@ -184,20 +193,23 @@ static A closed_form_args(const float* fs, const float* fq, const int32_t* ys, c
   a.loss = loss; a.acc = acc; a.logits = logits; a.dfs = dfs; a.dfq = dfq;
   return a;
 }
-// the closed-form head's LDS check (ridge: the ridge head's, else the metric heads'): the kernel entries and check_call end in it
-static int closed_form_lds_check(mi_engine* e, const char* who, bool ridge, int ns, int nq, int feat, int ways) {
-  return ridge ? ridge_lds_check(e, who, ns, nq, feat, ways) : metric_lds_check(e, who, ns, nq, feat, ways);
+// the closed-form head's LDS check (head: CF_METRIC, CF_RIDGE or CF_LOGREG; the ridge and metric callers' bool is the first two): the kernel
+// entries and check_call end in it
+enum { CF_METRIC = 0, CF_RIDGE = 1, CF_LOGREG = 2 };
+static int closed_form_lds_check(mi_engine* e, const char* who, int head, int ns, int nq, int feat, int ways) {
+  return head == CF_LOGREG ? logreg_lds_check(e, who, ns, nq, feat, ways)
+         : head == CF_RIDGE ? ridge_lds_check(e, who, ns, nq, feat, ways) : metric_lds_check(e, who, ns, nq, feat, ways);
 }
 // What the closed-form heads' kernel entries refuse, in their order: null pointers, tasks, the head's own hyper-parameters (`hyper` returns
 // its check's code), alignment, LDS.
 template <class A, class Hyper>
-static int closed_form_entry_check(const char* who, bool ridge, const A& a, int tasks, Hyper hyper) {
+static int closed_form_entry_check(const char* who, int head, const A& a, int tasks, Hyper hyper) {
   if (!a.fs || !a.fq || !a.ys || !a.yq || !a.loss || !a.acc) return fail(nullptr, MI_ERR_ARG, std::string(who) + ": null pointer argument");
   if (tasks < 1) return fail(nullptr, MI_ERR_ARG, std::string(who) + ": tasks must be >= 1, got " + std::to_string(tasks));
   if (const int hrc = hyper()) return hrc;
   if (((reinterpret_cast<uintptr_t>(a.fs) | reinterpret_cast<uintptr_t>(a.fq) | reinterpret_cast<uintptr_t>(a.dfs) | reinterpret_cast<uintptr_t>(a.dfq)) & 15) != 0)
     return fail(nullptr, MI_ERR_ARG, std::string(who) + ": fs, fq, dfs and dfq must be 16-byte aligned");
-  return closed_form_lds_check(nullptr, who, ridge, a.ns, a.nq, a.feat, a.ways);
+  return closed_form_lds_check(nullptr, who, head, a.ns, a.nq, a.feat, a.ways);
 }
 #define HEAD_LDS(e, who, n, ways, tangent)                                         \
   do {                                                                             \
@@ -1265,13 +1277,13 @@ static AdvanceArgs advance_base(const mi_engine* e, float* g) {
 // ALGO_METRIC (mi_meta_batch_metric): the ANIL call's trunk pass with a closed-form head (metric, scale) and no inner loop; adapt_steps = 0,
 // grad_tasks is tasks or 0.
 enum MetaAlgo { ALGO_MAML = 0, ALGO_ANIL = 1, ALGO_MAML_LR = 2, ALGO_MAML_STEPS = 3, ALGO_ANIL_LR = 4, ALGO_ANIL_STEPS = 5, ALGO_MAML_OFFSETS = 6,
-                ALGO_METRIC = 7, ALGO_RIDGE = 8, ALGO_ANIL_PROTO = 9 };
+                ALGO_METRIC = 7, ALGO_RIDGE = 8, ALGO_ANIL_PROTO = 9, ALGO_LOGREG = 10 };
 // ALGO_RIDGE (mi_meta_batch_ridge): ALGO_METRIC's launches with the ridge-regression head (lam, alpha) in the metric head's place;
-// dhyper_out [tasks][2] or null.
+// dhyper_out [tasks][2] or null.  ALGO_LOGREG (mi_meta_batch_logreg): the same with the logistic-regression head's launch.
 // ALGO_ANIL_PROTO (mi_meta_batch_anil_proto): ALGO_ANIL_LR / _STEPS' fields read by meta_batch_anil_impl, theta_0's head derived per task from
 // the support prototypes with `scale` (proto_init.hip); lr_vec and step_w each null or not, dhyper_out [tasks] (d objective_t / d scale) or null.
 static bool is_anil(MetaAlgo a) { return a == ALGO_ANIL || a == ALGO_ANIL_LR || a == ALGO_ANIL_STEPS || a == ALGO_ANIL_PROTO; }
-static bool is_closed_form(MetaAlgo a) { return a == ALGO_METRIC || a == ALGO_RIDGE; }
+static bool is_closed_form(MetaAlgo a) { return a == ALGO_METRIC || a == ALGO_RIDGE || a == ALGO_LOGREG; }
 struct MetaCall {
   MetaAlgo algo;
   const float* theta; const float* data; const int64_t* labels;
@@ -1349,10 +1361,10 @@ static int check_call(mi_engine* e, const MetaCall& c) {
       if (c.algo == ALGO_ANIL_PROTO && c.tasks >= 1 && !proto_init_fits(c.tasks, n, e->feat, c.ways)) return proto_init_size_fail(e, who, c.tasks, n, e->feat, c.ways);
     }
   }
-  const bool ridge = c.algo == ALGO_RIDGE;
-  const char* cf_who = ridge ? "mi_meta_batch_ridge" : "mi_meta_batch_metric";
+  const int cf_head = c.algo == ALGO_LOGREG ? CF_LOGREG : c.algo == ALGO_RIDGE ? CF_RIDGE : CF_METRIC;
+  const char* cf_who = cf_head == CF_LOGREG ? "mi_meta_batch_logreg" : cf_head == CF_RIDGE ? "mi_meta_batch_ridge" : "mi_meta_batch_metric";
   if (is_closed_form(c.algo)) {
-    const int hrc = ridge ? ridge_hyper_check(e, cf_who, c.lam, c.alpha) : metric_hyper_check(e, cf_who, c.metric, c.scale);
+    const int hrc = cf_head != CF_METRIC ? ridge_hyper_check(e, cf_who, c.lam, c.alpha) : metric_hyper_check(e, cf_who, c.metric, c.scale);
     if (hrc) return hrc;
     if (e->trace) return fail(e, MI_ERR_ARG, std::string("the debug trace does not cover ") + cf_who);
   }
@@ -1362,7 +1374,7 @@ static int check_call(mi_engine* e, const MetaCall& c) {
     return fail(e, MI_ERR_ARG, "ANIL features are flattened (view(-1, fc_neurons)), not mean-pooled");
   if (c.tasks < 1 || c.shots < 1 || c.adapt_steps < 0) return fail(e, MI_ERR_ARG, "tasks/shots must be >= 1, adapt_steps >= 0");
   if (c.ways != e->d.ways) return fail(e, MI_ERR_ARG, "ways differs from the engine's classifier width");
-  if (is_closed_form(c.algo)) return closed_form_lds_check(e, cf_who, ridge, c.ways * c.shots, c.ways * c.shots, e->feat, c.ways);   // (after ways and shots)
+  if (is_closed_form(c.algo)) return closed_form_lds_check(e, cf_who, cf_head, c.ways * c.shots, c.ways * c.shots, e->feat, c.ways);   // (after ways and shots)
   return MI_OK;
 }
 
@@ -1795,7 +1807,7 @@ static int meta_batch_anil_impl(mi_engine* e, void* stream, const MetaCall& c) {
   return MI_OK;
 }
 
-// mi_meta_batch_metric / mi_meta_batch_ridge, the closed-form call: the launches of meta_batch_anil_impl up to the split of the features, ONE
+// mi_meta_batch_metric / mi_meta_batch_ridge / mi_meta_batch_logreg, the closed-form call: the launches of meta_batch_anil_impl up to the split of the features, ONE
 // head launch chosen by `algo` (no head parameters, no inner loop, no tangent pass), then -- with a gradient -- the interleave, the trunk backward and the sum over tasks (without one the call ends
 // at the head).  lam's head entries stay
 // the zeros of the memset, so meta_grad_out's head entries are exact zeros.  The plan is the ANIL call's with K = 0.
@@ -1832,6 +1844,11 @@ static int meta_batch_closed_form_impl(mi_engine* e, void* stream, const MetaCal
     ra.h = {c.lam, c.alpha};
     ra.dhyper = with_grad ? c.dhyper_out : nullptr;
     LAUNCH(e, st, OP_RIDGE_HEAD, 0, launch_ridge_head(st, ra, T));
+  } else if (c.algo == ALGO_LOGREG) {
+    LogregArgs la = closed_form_args<LogregArgs>(ap.fs, ap.fq, ap.ys, ap.yq, n, n, e->feat, c.ways, c.loss_out, c.acc_out, c.logits_out, dfs, dfq);
+    la.h = {c.lam, c.alpha};
+    la.dhyper = with_grad ? c.dhyper_out : nullptr;
+    LAUNCH(e, st, OP_LOGREG_HEAD, 0, launch_logreg_head(st, la, T));
   } else {
     MetricArgs ma = closed_form_args<MetricArgs>(ap.fs, ap.fq, ap.ys, ap.yq, n, n, e->feat, c.ways, c.loss_out, c.acc_out, c.logits_out, dfs, dfq);
     ma.h = {c.metric, c.scale};
@@ -2034,6 +2051,22 @@ extern "C" int mi_meta_batch_ridge(mi_engine* e, void* stream, const float* thet
                                    float* loss_out, float* acc_out, float* meta_grad_out, float* dhyper_out, float* logits_out,
                                    void* workspace, size_t workspace_bytes) {
   MetaCall c{ALGO_RIDGE, theta, data, labels, tasks, with_grad ? tasks : 0, ways, shots, 0, 0, 0.f, nullptr, 0, nullptr, loss_out, acc_out,
+             meta_grad_out, logits_out, workspace, workspace_bytes};
+  c.lam = lam;
+  c.alpha = alpha;
+  c.dhyper_out = dhyper_out;
+  return meta_batch_entry(e, stream, c);
+}
+
+// The logistic-regression head on the ANIL engine's trunk: mi_meta_batch_ridge's call around launch_logreg_head (include/mi_maml.h).
+extern "C" int mi_logreg_workspace_bytes(const mi_engine* e, int tasks, int ways, int shots, int with_grad, size_t* bytes) {
+  return mi_metric_workspace_bytes(e, tasks, ways, shots, with_grad, bytes);
+}
+extern "C" int mi_meta_batch_logreg(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
+                                    int tasks, int ways, int shots, float lam, float alpha, int with_grad,
+                                    float* loss_out, float* acc_out, float* meta_grad_out, float* dhyper_out, float* logits_out,
+                                    void* workspace, size_t workspace_bytes) {
+  MetaCall c{ALGO_LOGREG, theta, data, labels, tasks, with_grad ? tasks : 0, ways, shots, 0, 0, 0.f, nullptr, 0, nullptr, loss_out, acc_out,
              meta_grad_out, logits_out, workspace, workspace_bytes};
   c.lam = lam;
   c.alpha = alpha;
@@ -2411,6 +2444,23 @@ extern "C" int mi_ridge_head(void* stream, const float* fs, const float* fq, con
   if (const int rc = closed_form_entry_check("mi_ridge_head", true, ra, tasks, [&] { return ridge_hyper_check(nullptr, "mi_ridge_head", lam, alpha); }))
     return rc;
   HIPCHK0(launch_ridge_head(reinterpret_cast<hipStream_t>(stream), ra, tasks));
+  return MI_OK;
+}
+
+// launch_logreg_head: the logistic-regression head's kernel entry (include/mi_maml.h), likewise.
+extern "C" size_t mi_logreg_head_scratch_bytes(int tasks, int ns, int nq, int feat, int ways) {
+  return mi_metric_head_scratch_bytes(tasks, ns, nq, feat, ways);
+}
+extern "C" int mi_logreg_head(void* stream, const float* fs, const float* fq, const int32_t* ys, const int32_t* yq, int tasks, int ns, int nq,
+                              int feat, int ways, float lam, float alpha, float* loss, float* acc, float* logits, float* dfs, float* dfq,
+                              float* dhyper, void* scratch, size_t scratch_bytes) {
+  (void)scratch; (void)scratch_bytes;
+  LogregArgs la = closed_form_args<LogregArgs>(fs, fq, ys, yq, ns, nq, feat, ways, loss, acc, logits, dfs, dfq);
+  la.h = {lam, alpha};
+  la.dhyper = dhyper;
+  if (const int rc = closed_form_entry_check("mi_logreg_head", CF_LOGREG, la, tasks, [&] { return ridge_hyper_check(nullptr, "mi_logreg_head", lam, alpha); }))
+    return rc;
+  HIPCHK0(launch_logreg_head(reinterpret_cast<hipStream_t>(stream), la, tasks));
   return MI_OK;
 }
 

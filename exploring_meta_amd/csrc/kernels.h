@@ -259,7 +259,7 @@ hipError_t launch_head_grads(hipStream_t st, const HeadArgs& a, int tasks);   //
 hipError_t launch_spatial_mean(hipStream_t st, const float* p, float* f, int rows, int hw, int c);
 hipError_t launch_spatial_mean_bwd(hipStream_t st, const float* df, float* dp, int rows, int hw, int c);
 
-// What every closed-form head on the features of a whole meta-batch takes and gives (metric_head.hip, ridge_head.hip).  H: the head's own
+// What every closed-form head on the features of a whole meta-batch takes and gives (metric_head.hip, ridge_head.hip, logreg_head.hip).  H: the head's own
 // hyper-parameters, kept between the sizes and the outputs.
 template <class H>
 struct ClosedFormArgs {
@@ -296,6 +296,16 @@ struct RidgeArgs : ClosedFormArgs<RidgeHyper> {
 size_t ridge_head_lds_bytes(int ns, int nq, int ways);
 bool ridge_head_fits(int ns, int nq, int feat, int ways);
 hipError_t launch_ridge_head(hipStream_t st, const RidgeArgs& a, int tasks);
+
+// logreg_head.hip: the logistic-regression head (the inner problem under softmax cross-entropy, solved to optimality), one launch
+struct LogregArgs : ClosedFormArgs<RidgeHyper> {
+  float* dhyper;                         // [T][2]: (dlam, dalpha) per task (may be null; dfs, dfq and dhyper all null: forward only)
+};
+// Dynamic LDS of one task (everything ns-sized and the solver's tables, fp64; feat does not enter) against the CU's LDS; the launcher refuses
+// what does not fit with hipErrorInvalidValue before launching anything -- callers check logreg_head_fits first and report MI_ERR_ARG.
+size_t logreg_head_lds_bytes(int ns, int nq, int ways);
+bool logreg_head_fits(int ns, int nq, int feat, int ways);
+hipError_t launch_logreg_head(hipStream_t st, const LogregArgs& a, int tasks);
 
 // proto_init.hip: the Proto-MAML head initialisation (W_0, b_0) = (2 s c, -s |c|^2) from the support prototypes, and its backward
 struct ProtoInitArgs {

@@ -127,6 +127,15 @@ def check_ridge(lam, scale):
     return lam, scale
 
 
+def check_logreg(lam, scale):
+    """(lam, scale) of the logistic-regression head as floats; anything not > 0 or not finite is refused here, before the library is touched."""
+    lam, scale = float(lam), float(scale)
+    for name, v in (('lam', lam), ('scale', scale)):
+        if not (v > 0.0 and math.isfinite(v)):
+            raise _lib.MiError(f'libmi_maml error -1: the logistic-regression head\'s {name} must be positive and finite, got {v}')
+    return lam, scale
+
+
 class MetaEngine:
     """One engine per (model spec, device).  Not re-entrant (one host thread per GPU / rank)."""
 
@@ -687,6 +696,22 @@ class MetaEngine:
         """The ridge head's kernel entry (mi_ridge_head) on given features: fs [T, ns, F], fq [T, nq, F] fp32, ys [T, ns], yq [T, nq] int32
         in [0, ways).  Returns (loss[T], acc[T], logits [T, nq, ways], dfs, dfq, dhyper [T, 2]), the last three None without a gradient."""
         return self._head_entry('ridge', fs, fq, ys, yq, ways, check_ridge(lam, scale), with_grad, n_hyper=2)
+
+    @_on_device
+    def meta_batch_logreg(self, theta, data, labels, shots, lam=1.0, scale=1.0, with_grad=True, return_logits=False):
+        """The logistic-regression head on the ANIL trunk (mi_meta_batch_logreg): per task the head's inner problem under softmax
+        cross-entropy, W* = argmin sum_i CE(W fs_i, ys_i) + lam/2 |W|^2, solved to optimality and differentiated through the optimum; logits
+        scale * fq W*^T.  theta keeps the ANIL layout; the head's entries are not used and their gradient is exactly zero.  Returns
+        (loss[T], acc[T], meta_grad[P] or None, dhyper [T, 2] or None, logits [T, S*W, ways] or None); dhyper[t] = (dloss_t/dlam,
+        dloss_t/dscale), per task: the sum is the caller's.  A task whose solve does not converge within the header's caps is NaN."""
+        return self._closed_form_call('logreg', ('logreg',), theta, data, labels, shots, check_logreg(lam, scale), with_grad, return_logits, n_hyper=2)
+
+    @_on_device
+    def logreg_head(self, fs, fq, ys, yq, ways, lam=1.0, scale=1.0, with_grad=True):
+        """The logistic-regression head's kernel entry (mi_logreg_head) on given features: fs [T, ns, F], fq [T, nq, F] fp32, ys [T, ns],
+        yq [T, nq] int32 in [0, ways).  Returns (loss[T], acc[T], logits [T, nq, ways], dfs, dfq, dhyper [T, 2]), the last three None
+        without a gradient."""
+        return self._head_entry('logreg', fs, fq, ys, yq, ways, check_logreg(lam, scale), with_grad, n_hyper=2)
 
     @_on_device
     def forward_logits(self, theta, x):

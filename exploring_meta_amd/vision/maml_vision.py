@@ -68,7 +68,8 @@ def step_offsets_of(model, p):
 
 
 def add_trunk_test_flags(parser, when, note=''):
-    """--nil_test / --ridge_test (--ridge_lam, --ridge_scale): the trunk alone under a closed-form head, scored ``when``."""
+    """--nil_test / --ridge_test (--ridge_lam, --ridge_scale) / --logreg_test (--logreg_lam, --logreg_scale): the trunk alone under a
+    closed-form or exactly solved head, scored ``when``."""
     parser.add_argument('--nil_test', action='store_true',
                         help=f'{when} also log nil_test_acc: the trunk scored on meta_batch_size test tasks by the NIL cosine head, no inner loop{note}')
     parser.add_argument('--ridge_test', action='store_true',
@@ -76,15 +77,22 @@ def add_trunk_test_flags(parser, when, note=''):
                              f'--ridge_lam / --ridge_scale, no inner loop{note}')
     parser.add_argument('--ridge_lam', type=float, default=1.0, metavar='LAM', help="--ridge_test: the ridge head's regulariser")
     parser.add_argument('--ridge_scale', type=float, default=1.0, metavar='S', help="--ridge_test: the ridge head's logit scale")
+    parser.add_argument('--logreg_test', action='store_true',
+                        help=f'{when} also log logreg_test_acc: the trunk under the logistic-regression head solved to convergence (the limit of '
+                             f"ANIL's inner loop under its own loss) with the fixed --logreg_lam / --logreg_scale{note}")
+    parser.add_argument('--logreg_lam', type=float, default=1.0, metavar='LAM', help="--logreg_test: the head's regulariser")
+    parser.add_argument('--logreg_scale', type=float, default=1.0, metavar='S', help="--logreg_test: the head's logit scale")
 
 
 def trunk_test_params(args):
-    return dict(nil_test=args.nil_test, ridge_test=args.ridge_test, ridge_lam=args.ridge_lam, ridge_scale=args.ridge_scale)
+    return dict(nil_test=args.nil_test, ridge_test=args.ridge_test, ridge_lam=args.ridge_lam, ridge_scale=args.ridge_scale,
+                logreg_test=args.logreg_test, logreg_lam=args.logreg_lam, logreg_scale=args.logreg_scale)
 
 
 def trunk_tests(p, test_tasks, trunk, device, rank, metrics, log):
     """--nil_test: how good are the features alone?  The head is thrown away (NIL, no inner loop).  --ridge_test: how good is the exactly
-    solved head on these features (R2-D2's ridge regression, fixed lam / scale)?  Each on meta_batch_size tasks of its own ``test_tasks()``."""
+    solved head on these features (R2-D2's ridge regression, fixed lam / scale)?  --logreg_test: the same question under the loss ANIL's
+    inner loop runs (logistic regression solved to convergence).  Each on meta_batch_size tasks of its own ``test_tasks()``."""
     if p.get('nil_test'):
         from ..core_functions.metric import evaluate_nil
         metrics['nil_test_acc'] = evaluate_nil(p, test_tasks(), trunk, device)
@@ -95,6 +103,11 @@ def trunk_tests(p, test_tasks, trunk, device, rank, metrics, log):
         metrics['ridge_test_acc'] = evaluate_ridge(p, test_tasks(), trunk, RidgeHead(p['ridge_lam'], p['ridge_scale'], learnable=False), device)
         if rank == 0:
             log(f"ridge_test_acc: {metrics['ridge_test_acc']}")
+    if p.get('logreg_test'):
+        from ..core_functions.logreg import LogRegHead, evaluate_logreg
+        metrics['logreg_test_acc'] = evaluate_logreg(p, test_tasks(), trunk, LogRegHead(p['logreg_lam'], p['logreg_scale'], learnable=False), device)
+        if rank == 0:
+            log(f"logreg_test_acc: {metrics['logreg_test_acc']}")
 
 
 def run(dataset, p, first_order=False, log=print):
@@ -109,6 +122,8 @@ def run(dataset, p, first_order=False, log=print):
     model = (OmniglotCNN(p['ways']) if dataset == 'omni' else MiniImagenetCNN(p['ways'])).to(device)
     if p.get('ridge_test') and isinstance(model, OmniglotCNN):
         raise NotImplementedError('--ridge_test scores flattened features; OmniglotCNN feeds its head their spatial mean (use --dataset min)')
+    if p.get('logreg_test') and isinstance(model, OmniglotCNN):
+        raise NotImplementedError('--logreg_test scores flattened features; OmniglotCNN feeds its head their spatial mean (use --dataset min)')
     if p.get('nil_test') and isinstance(model, OmniglotCNN):      # (before the training, not after it)
         raise NotImplementedError('--nil_test scores flattened features; OmniglotCNN feeds its head their spatial mean (use --dataset min)')
     maml = MAML(model, lr=inner_lr_of(model, p), first_order=first_order, offsets=step_offsets_of(model, p))

@@ -1,5 +1,5 @@
 """The training loop of the drivers whose iteration is one fused call per half on the ANIL trunk (``vision.anil_vision``,
-``vision.protonet_vision``, ``vision.ridge_vision``): rank setup, seeding, per-iteration train + validation meta-batches task-sharded over
+``vision.protonet_vision``, ``vision.ridge_vision``, ``vision.logreg_vision``): rank setup, seeding, per-iteration train + validation meta-batches task-sharded over
 ranks, the BatchNorm buffers of the trunk folded when checkpoints are written, ONE all-reduce, gradient / meta_batch_size, Adam, the
 checkpoint cadence.  What differs between the drivers comes from ``setup``."""
 import os

@@ -364,6 +364,50 @@ int mi_meta_batch_ridge(mi_engine* e, void* stream, const float* theta, const fl
                         float* loss_out, float* acc_out, float* meta_grad_out, float* dhyper_out /*nullable*/, float* logits_out /*nullable*/,
                         void* workspace, size_t workspace_bytes);
 
+/* Logistic-regression head: the head's inner problem under the loss ANIL's inner loop runs -- L2-regularised multinomial logistic regression
+ * (softmax cross-entropy, no bias) on the support features -- solved to optimality and differentiated through the optimum by the implicit
+ * function theorem (csrc/logreg_head.hip; LR-D2 of the R2-D2 paper for any number of classes, MetaOptNet's convex head).
+ * Per task, Y = onehot(ys) [ns, ways], labels in [0, ways), in the dual form W = A^T fs:
+ *   G = fs fs^T,  R(A) = lam A + softmax_rows(G A) - Y = 0  (one solution for lam > 0, also when G is singular),  z = alpha * (fq fs^T) A;
+ *   loss_t = mean_q CE(z_q, yq_q);  acc_t = mean_q [argmax_w z_q == yq_q] (first maximum of the fp32 logits returned);
+ *   dfs, dfq = d(sum_t loss_t)/d(fs, fq);  dhyper[t] = (dloss_t/dlam, dloss_t/dalpha).
+ * A class without a support row is legal.  mi_logreg_head is the kernel entry, with mi_ridge_head's arguments and rules: fs [tasks, ns, feat],
+ * fq [tasks, nq, feat] fp32 (16-byte aligned, like dfs / dfq), ys, yq int32; logits, dfs, dfq and dhyper [tasks, 2] may each be NULL, in any
+ * combination (dfs, dfq and dhyper all NULL: the forward-only launch, whose loss, acc and logits are the bits of the forward + backward
+ * launch).  ONE launch whatever `tasks`; a task's results do not depend on the other tasks of the call.  G, K, the solver and the backward
+ * are fp64 in LDS; no intermediate is kept in fp32.
+ * The solver: Newton from A = 0; each step solves (lam I + D G) dA = -R (D_i = diag(p_i) - p_i p_i^T, row-wise) through the symmetric
+ * positive definite system lam I + C^T G C (D = C C^T) by conjugate gradients to |r| <= 1e-13 |b|; a step is accepted if it lowers |R|_inf, or,
+ * while |R|_inf > 1e-10, if it meets Armijo's condition (1e-4) on the inner objective, else halved; the iteration stops at |R|_inf <= 1e-13, or
+ * at |R|_inf <= 1e-10 when the step no longer lowers it.  Every rule is scale-free: features times 2 with lam times 4 gives loss, acc, logits
+ * and dalpha bit for bit, dfs and dfq exactly halved, dlam exactly quartered.  The loops are bounded by the caps below (at least twice the
+ * largest count over the tests' cases: 10 Newton steps, 52 CG steps, 1 halving) and leave at once on a residual that is not finite.  A task
+ * that has not reached |R|_inf <= 1e-10 at the caps, whose residual is not finite, or whose backward solve has not met its tolerance gets NaN
+ * in every output -- never a fault, never an endless loop; other tasks are untouched.  The domain (MI_ERR_ARG naming the sizes and the bytes
+ * before any launch otherwise, the outputs untouched): tasks, ns, nq >= 1, 1 <= feat <= MI_RIDGE_MAX_FEAT, 1 <= ways <= 64, lam and alpha > 0
+ * and finite, and one task's tables inside the 160 KiB of LDS:
+ *   8 * (ns * ns + nq * ns + 10 * ns * ways + nq * ways + 2 * ns + 3 * nq + 32) <= 163840 bytes
+ * -- ns = nq = 25, 5 ways: 22256; ns = nq = 20, 20 ways: 42656; ns = nq = 5, 5 ways: 3056.  (The ridge head's 100 x 100 x 20 is outside.)
+ * mi_logreg_head_scratch_bytes: no scratch today: 0, and scratch may be NULL. */
+#define MI_LOGREG_NEWTON_CAP 32
+#define MI_LOGREG_CG_CAP 256
+#define MI_LOGREG_HALVE_CAP 8
+size_t mi_logreg_head_scratch_bytes(int tasks, int ns, int nq, int feat, int ways);
+int mi_logreg_head(void* stream, const float* fs, const float* fq, const int32_t* ys, const int32_t* yq,
+                   int tasks, int ns, int nq, int feat, int ways, float lam, float alpha,
+                   float* loss, float* acc, float* logits /*nullable*/, float* dfs /*nullable*/, float* dfq /*nullable*/,
+                   float* dhyper /*nullable*/, void* scratch, size_t scratch_bytes);
+/* One meta-batch scored (and differentiated) by the logistic-regression head on the ANIL trunk: mi_meta_batch_ridge's call with
+ * mi_logreg_head's launch in the ridge head's place (`logreg_head/0` in the profile) -- the same theta / meta_grad_out layout (the head's
+ * entries of theta are unused, those of meta_grad_out exact zeros), workspace plan, launches, graph replay (the bits of lam and alpha are
+ * part of the graph's signature) and dhyper_out [tasks, 2] or NULL, written only with a gradient.  MI_ERR_ARG before any launch: lam or
+ * alpha not > 0 or not finite, sizes outside mi_logreg_head's domain, and what mi_meta_batch_metric refuses. */
+int mi_logreg_workspace_bytes(const mi_engine* e, int tasks, int ways, int shots, int with_grad, size_t* bytes);
+int mi_meta_batch_logreg(mi_engine* e, void* stream, const float* theta, const float* data, const int64_t* labels,
+                         int tasks, int ways, int shots, float lam, float alpha, int with_grad,
+                         float* loss_out, float* acc_out, float* meta_grad_out, float* dhyper_out /*nullable*/, float* logits_out /*nullable*/,
+                         void* workspace, size_t workspace_bytes);
+
 /* Proto-MAML head initialisation (Triantafillou et al., "Meta-Dataset", eq. 8; csrc/proto_init.hip): the linear head
  * whose logits are the Prototypical-Networks logits up to a per-row constant, derived per task from the support features, and its
  * backward.  Per task, N_w = #{i : ys_i = w}; THE CONTRACT IS N_w >= 1 FOR EVERY CLASS and labels in [0, ways), as for mi_metric_head (a
